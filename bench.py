@@ -80,8 +80,12 @@ def parse():
                          "as one launch (round 4's line); 'torch-sgd' = torch.optim.SGD.step()")
     ap.add_argument('--check', action='store_true', help='dev: print gradient / parameter checksums (the launch modes must train identically)')
     ap.add_argument('--split', action='store_true', help='dev, --mode train: serialised wall-clock split of the step')
-    ap.add_argument('--min-seconds', type=float, default=1.0,
-                    help='--mode infer: the K-step window is repeated until this much time has been measured; the line carries min / median / max')
+    ap.add_argument('--min-seconds', type=float, default=0.0,
+                    help='--mode infer: the K-step window is repeated until this much time has been measured; the line carries min / median / max '
+                         '(0 = one window: exactly --steps timed steps)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all; '
+                         'a fixed seeded sample of larger arrays)')
     ap.add_argument('--no-roofline', action='store_true', help='dev: skip the kernel-level roofline section (roofline = null)')
     ap.add_argument('--no-stress', action='store_true',
                     help='skip the all-visible stress launches of the gather kernels (SURVEY 8d): a rocprofv3 --stats run then '
@@ -89,7 +93,28 @@ def parse():
     ap.add_argument('--cpu-threads', type=int, default=None, help='torch threads of the CPU baseline (default: min(cores, 16), the fastest measured)')
     ap.add_argument('--cpu-layers', type=int, default=None,
                     help='decoder layers of the CPU-baseline sample (default: bounded automatically)')
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.dump_outputs and a.mode == 'infer' and (a.only_f2b or a.min_seconds > 0):
+        ap.error('--dump-outputs needs the headline figure timed over exactly --steps steps (no --only-f2b, --min-seconds 0)')
+    return a
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32, DUMP_BYTES in all.  An array larger than its equal share
+    is written as a fixed seeded sample of its flattened elements (sorted indices; the same ones in every run with the same
+    arguments), so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = (DUMP_BYTES - 4096 * len(arrays)) // (4 * len(arrays))           # elements per array (4096: room for the .npy headers)
+    for name, t in arrays.items():
+        x = t.detach().float()
+        if x.numel() > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, x.numel(), cap))
+            x = x.reshape(-1)[torch.from_numpy(idx).to(x.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(x.cpu().numpy(), dtype=np.float32))
 
 
 def build_decoder(G, num_cams, layers, value_dtype, seed):
@@ -330,20 +355,23 @@ def main():
                       'check': 'every graph replayed on a sample it was not captured on (features, queries written into its static buffers '
                                'in place, lidar2img refreshed outside the graph): equal to the eager result bit for bit'}
         rot_step = [0]
+        last_out = [None]                             # what the latest step returned (a graph's static outputs, or the eager call's)
 
         def run_one():
             with torch.cuda.stream(streams[0]), Fn.request_slot(0):
                 if rot_graphs:
-                    rot_graphs[rot_step[0] % len(rot_graphs)].replay()
+                    k = rot_step[0] % len(rot_graphs)
+                    rot_graphs[k].replay()
                     rot_step[0] += 1
+                    last_out[0] = rot_outs[k] if rotate is not None else static_out0
                 else:
-                    request(0)
+                    last_out[0] = request(0)
 
         stats = {}
         torch.cuda.synchronize()
         # THE figure: one request at a time, batch 1.  A window = exactly `steps` samples, barrier + synchronise on
-        # both sides, MAX over ranks; windows are repeated until --min-seconds of them have been measured (a 20-step window is
-        # 32 ms: one window is at the mercy of a clock ramp) - value = the MEDIAN window, min / max beside it.
+        # both sides, MAX over ranks; with --min-seconds S windows are repeated until S seconds of them have been measured (a
+        # 20-step window is 32 ms) - value = the MEDIAN window, min / max beside it.  Default: one window, --steps timed steps.
         windows, measured = [], 0.0
         while True:
             el = D.timed_steps(run_one, a.steps, a.warmup if not windows else 0, dev, stats if not windows else {})
@@ -352,6 +380,8 @@ def main():
             if measured >= a.min_seconds or len(windows) >= 200:
                 break
         ops.check_handoff()                           # a SIGNAL / WAIT hand-off that timed out inside a replayed graph raises here
+        if a.dump_outputs and rank == 0:              # (before any later replay overwrites the graphs' static outputs)
+            dump_outputs(a.dump_outputs, dict(zip(('inter_states', 'init_reference', 'inter_references'), last_out[0])))
         windows_ms = sorted(w / a.steps * 1e3 for w in windows)
         elapsed = sorted(windows)[len(windows) // 2]
         single_ms = elapsed / a.steps * 1e3
@@ -719,6 +749,11 @@ def train_bench(a, D, tr, regs, feats, query_embed, metas, dev, rank, n_cams, le
     _ops.check_handoff()                              # a hand-off that timed out inside the replayed step raises here
     if a.criterion:
         crit.assigner.check_status()                  # ... and so does an assignment that met a label out of range
+    if a.dump_outputs and rank == 0:                  # what the last step leaves: updated parameters, their gradients, the pyramid's
+        grad = lambda t: t.grad if t.grad is not None else torch.zeros_like(t)        # noqa: E731
+        dump_outputs(a.dump_outputs, {'params': torch.cat([p.detach().reshape(-1) for p in params]),
+                                      'grads': torch.cat([grad(p).reshape(-1) for p in params]),
+                                      **{f'feature_grad_l{i}': grad(f) for i, f in enumerate(feats)}})
     if rank == 0 and a.check:                                 # dev: the launch modes must train identically
         flat = reducer.flat
         psum = sum(float(p.detach().double().sum()) for p in params)
