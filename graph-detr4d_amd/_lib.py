@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GD4D_LIB_PATH') or os.path.join(_HERE, 'libgd4d.so')   # env override: dev A/B builds
-ABI_VERSION = 55
+ABI_VERSION = 56
 PIXEL_MAJOR, HEAD_MAJOR = 0, 1
 
 F32, BF16 = 0, 1
@@ -127,6 +127,10 @@ SIGNATURES = {
     'gd4d_value_proj_bwd_input': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'gd4d_value_proj_bwd_weight_workspace_bytes': (_c.c_size_t, []),
     'gd4d_value_proj_bwd_weight': (_i, [_vp] * 6 + [_c.c_size_t, _i, _i, _i, _vp]),
+    'gd4d_depth_net_image_bytes': (_c.c_size_t, [_i]),
+    'gd4d_depth_net_image': (_i, [_vp, _i, _vp, _vp]),
+    'gd4d_cam_gate_fwd': (_i, [_vp, _vp, _i, _i, _f] + [_vp] * 8 + [_i, _vp, _vp]),
+    'gd4d_depth_conv_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i] + [_vp] * 6 + [_f, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,231 @@
+"""Camera-aware DepthNet of Detr3DHeadPECAM - the stage in front of the head's position embedding.
+
+Mirror of `DepthNet` (projects/mmdet3d_plugin/models/dense_heads/detr3d_head_pe_camaware.py:59-105, built at :198 as
+`DepthNet(256, 256, 80)`, applied to every level at :313-320): same submodule names (`reduce_conv.{0,1}`, `context_conv`,
+`mlp.fc{1,2}`, `se.conv_{reduce,expand}`), so the head checkpoint's `depth_net.` slice loads with strict=True.
+
+Per level x (1, N, 256, H, W) and camera n:
+    out[n] = relu(BN(conv3x3(x[n]))) * sigmoid(se(mlp(s[n]))),   s[n] = |(inv(K_n)[0,0], inv(K_n)[1,1])| * 1000 / aug_scale
+with K_n the camera's 4x4 intrinsics and aug_scale from the image-augmentation matrix.  `context_conv` is computed and discarded by
+the reference (`forward` returns x); it is not computed here, its parameters are kept so the state dict loads.
+
+What runs where (inference): the gate is one kernel (ops.cam_gate_fwd) reading the intrinsics / ida scales from a persistent device
+buffer (a captured graph serves new cameras after refresh_matrices), the 3x3 convolution with bias, BatchNorm (running statistics),
+ReLU and the gate as its epilogue is ONE launch over all levels (ops.depth_conv_fwd, split-bf16 x 3 on the bf16 matrix cores).
+Training (BatchNorm on batch statistics) and shapes the kernels do not take run only on the torch-op route, when chosen
+(`torch_ops=True` or GD4D_TORCH_OPS=1): the module's own nn.Conv2d / BatchNorm2d / MLP / SE, the reference arithmetic.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from . import functional as Fn
+from . import ops
+
+MAX_LEVELS_PER_LAUNCH = 4
+
+
+class Mlp(nn.Module):
+    """detr3d_head_pe_camaware.py:33-56 (drop = 0)."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.ReLU, drop=0.0):
+        super().__init__()
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        self.fc1 = nn.Linear(in_features, hidden_features)
+        self.act = act_layer()
+        self.drop1 = nn.Dropout(drop)
+        self.fc2 = nn.Linear(hidden_features, out_features)
+        self.drop2 = nn.Dropout(drop)
+
+    def forward(self, x):
+        return self.drop2(self.fc2(self.drop1(self.act(self.fc1(x)))))
+
+
+class SELayer(nn.Module):
+    """detr3d_head_pe_camaware.py:20-31."""
+
+    def __init__(self, channels, act_layer=nn.ReLU, gate_layer=nn.Sigmoid):
+        super().__init__()
+        self.conv_reduce = nn.Conv2d(channels, channels, 1, bias=True)
+        self.act1 = act_layer()
+        self.conv_expand = nn.Conv2d(channels, channels, 1, bias=True)
+        self.gate = gate_layer()
+
+    def forward(self, x, x_se):
+        return x * self.gate(self.conv_expand(self.act1(self.conv_reduce(x_se))))
+
+
+def _intrinsics(mats):
+    """(N, 16) fp32 host array of the cameras' 4x4 intrinsics (img_metas[0]['intrinsics'], the pipeline's float32 viewpads)."""
+    a = np.asarray([np.asarray(torch.as_tensor(m).cpu() if torch.is_tensor(m) else m, dtype=np.float32) for m in mats],
+                   dtype=np.float32)
+    if a.ndim != 3 or a.shape[1:] != (4, 4):
+        raise ValueError(f'DepthNet: intrinsics must be N 4x4 matrices, got shape {a.shape}')
+    return np.ascontiguousarray(a.reshape(-1, 16))
+
+
+def _ida00(ida_mats, n):
+    """ida[..., 0, 0] of torch.stack(ida_mats) (:87, :93-94) as an (N,) fp32 host array.  The list holds 1 matrix (the pipeline keeps
+    one: transform_3d.py:389 resets the list per camera), broadcast over the cameras here, or N: either way the device buffer has
+    the same shape, so a graph captured on one form serves the other."""
+    a = np.asarray([np.asarray(m.detach().cpu() if torch.is_tensor(m) else m, dtype=np.float32) for m in ida_mats], dtype=np.float32)
+    if a.ndim < 3:
+        raise ValueError(f'DepthNet: ida_mats must be a list of square matrices, got shape {a.shape}')
+    d = np.ascontiguousarray(a[..., 0, 0].reshape(-1))
+    if d.shape[0] not in (1, n):
+        raise ValueError(f'DepthNet: {d.shape[0]} ida matrices for {n} cameras (1 or {n} expected)')
+    return np.array(np.broadcast_to(d, (n,)), dtype=np.float32)          # (a writable copy)
+
+
+class DepthNet(nn.Module):
+    def __init__(self, in_channels, mid_channels, context_channels, torch_ops=False):
+        """torch_ops (not a keyword of the reference): run the module's own torch layers (the reference arithmetic, trainable) instead
+        of the library's kernels - the only route for training and for shapes the kernels do not take."""
+        super().__init__()
+        self.reduce_conv = nn.Sequential(
+            nn.Conv2d(in_channels, mid_channels, kernel_size=3, stride=1, padding=1),
+            nn.BatchNorm2d(mid_channels),
+            nn.ReLU(inplace=True),
+        )
+        self.context_conv = nn.Conv2d(mid_channels, context_channels, kernel_size=1, stride=1, padding=0)
+        self.mlp = Mlp(1, mid_channels, mid_channels)
+        self.se = SELayer(mid_channels)
+        self.torch_ops = bool(torch_ops)
+        self._image_cache = None    # (key, weight image of reduce_conv[0])
+        self._mats = {}             # (device, request slot, N) -> [host intrinsics, host ida00 (N), device buffer]
+
+    # ---- routes ---------------------------------------------------------------------------------------------------------
+    def _route_name(self, x):
+        return (f'camera-aware DepthNet with in / mid channels {self.reduce_conv[0].in_channels} / {self.reduce_conv[0].out_channels}, '
+                f'{x.shape[-3]}-channel {x.dtype} maps (kernels: 256 channels, float32, eval mode)')
+
+    def _uses_torch_ops(self, feats):
+        """True for the torch-op route; raises where the kernels cannot serve and that route was not chosen."""
+        for f in feats:
+            Fn.require_gpu(f, 'mlvl_feats')
+        if Fn.torch_ops_route(self._route_name(feats[0]), True, module=self):
+            return True
+        if self.training:
+            raise _lib.Gd4dError('DepthNet in train() mode: BatchNorm then normalises with batch statistics and the 3x3 convolution '
+                                 'needs a backward, which graph-detr4d_amd\'s kernels do not provide.  `torch_ops=True` (or '
+                                 'GD4D_TORCH_OPS=1) runs the module\'s own torch layers, the reference arithmetic, trainable by autograd.')
+        conv = self.reduce_conv[0]
+        ok = conv.in_channels == 256 and conv.out_channels == 256 and all(f.shape[-3] == 256 and f.dtype == torch.float32 for f in feats)
+        Fn.torch_ops_route(self._route_name(feats[0]), ok, module=self)       # raises when not ok
+        if Fn.wants_grad(self, *feats):
+            raise _lib.Gd4dError('DepthNet: autograd is on, and graph-detr4d_amd\'s kernels have no backward for this stage.  Run '
+                                 'inference under torch.no_grad(), or choose the torch-op route (`torch_ops=True` / GD4D_TORCH_OPS=1).')
+        return False
+
+    @staticmethod
+    def _squeeze_batch(x):
+        if x.dim() == 5:
+            if x.shape[0] != 1:
+                raise ValueError(f'DepthNet: batch size {x.shape[0]}; the reference squeezes B and takes B = 1 only')
+            return x[0]
+        if x.dim() != 4:
+            raise ValueError(f'DepthNet: (1, N, C, H, W) or (N, C, H, W) maps expected, got {tuple(x.shape)}')
+        return x
+
+    # ---- torch-op route: the reference arithmetic --------------------------------------------------------------------------
+    def _gate_input_torch(self, intrin, ida00, scale_depth_factor, device):
+        """(N, 1) scaled pixel sizes (:86-97); the 4x4 inverses of a few cameras are taken on the host."""
+        inv = torch.inverse(torch.from_numpy(intrin).view(-1, 4, 4))                                          # :89
+        pixel_size = torch.norm(torch.stack([inv[..., 0, 0], inv[..., 1, 1]], dim=-1), dim=-1).reshape(-1, 1)  # :91-93
+        ida00 = torch.from_numpy(ida00)
+        aug_scale = torch.sqrt(ida00 ** 2 + ida00 ** 2).reshape(-1, 1)     # :93-94 ([0, 0] twice, as written)
+        return (pixel_size * scale_depth_factor / aug_scale).float().to(device)
+
+    def _forward_torch(self, feats, intrin, ida00, scale_depth_factor):
+        s = self._gate_input_torch(intrin, ida00, scale_depth_factor, feats[0].device)
+        x_se = self.mlp(s)[..., None, None]
+        return [self.se(self.reduce_conv(f), x_se) for f in feats]
+
+    # ---- kernel route -------------------------------------------------------------------------------------------------
+    def _image(self):
+        """The 3x3 weight's fragment image, remade when the weight changes (load_state_dict, an optimizer step, an in-place edit)."""
+        w = self.reduce_conv[0].weight
+        key = (str(w.device), w.data_ptr(), w._version)
+        if self._image_cache is None or self._image_cache[0] != key:
+            self._image_cache = (key, ops.depth_net_image(w.detach()))
+        return self._image_cache[1]
+
+    def _matrices_device(self, intrin, ida00, dev, capturing=False):
+        """The intrinsics (N, 4, 4) and ida scales (N) on the device: ONE persistent buffer per (device, request slot, N),
+        refreshed in place when the host values differ - a hipGraph captured over this module keeps a valid address, and a replay
+        for new cameras only needs refresh_matrices() outside the graph (the pattern of FeaturePositionEmbedding)."""
+        n = intrin.shape[0]
+        key = (str(dev), Fn.slot_key(dev), n)
+        ent = self._mats.get(key)
+        if ent is None or not (np.array_equal(ent[0], intrin) and np.array_equal(ent[1], ida00)):
+            if capturing:
+                if ent is None:
+                    raise RuntimeError('DepthNet under hipGraph capture: call the module (or refresh_matrices) once eagerly with these '
+                                       'img_metas first - their matrices are not on the device yet')
+                raise RuntimeError('DepthNet under hipGraph capture: img_metas changed since the last eager call; '
+                                   'refresh_matrices(img_metas) first')
+            src = torch.from_numpy(np.concatenate([intrin.reshape(-1), ida00]))
+            if ent is None:
+                ent = self._mats[key] = [intrin.copy(), ida00.copy(), src.to(dev)]
+            else:
+                ent[2].copy_(src)
+                ent[0], ent[1] = intrin.copy(), ida00.copy()
+        buf = ent[2]
+        return buf[:16 * n].view(n, 4, 4), buf[16 * n:]
+
+    def refresh_matrices(self, img_metas, device):
+        """For the owner of a hipGraph captured over this module: put the new sample's intrinsics and ida scales into the persistent
+        device buffer the graph reads (outside the graph, before the replay).  The graph recomputes the gate from them; nothing
+        derived from the cameras is kept between calls."""
+        intrin = _intrinsics(img_metas[0]['intrinsics'])
+        return self._matrices_device(intrin, _ida00(img_metas[0]['ida_mats'], intrin.shape[0]), torch.device(device))
+
+    def _gate(self, intrin, ida00, scale_depth_factor, dev):
+        k_dev, ida_dev = self._matrices_device(intrin, ida00, dev, capturing=torch.cuda.is_current_stream_capturing())
+        fc1, fc2, cr, ce = self.mlp.fc1, self.mlp.fc2, self.se.conv_reduce, self.se.conv_expand
+        return ops.cam_gate_fwd(k_dev, ida_dev, fc1.weight, fc1.bias, fc2.weight, fc2.bias, cr.weight, cr.bias, ce.weight, ce.bias,
+                                scale_depth_factor)
+
+    def _forward_hip(self, feats, intrin, ida00, scale_depth_factor):
+        dev = feats[0].device
+        gate = self._gate(intrin, ida00, scale_depth_factor, dev)
+        conv, bn = self.reduce_conv[0], self.reduce_conv[1]
+        image = self._image()
+        feats = [f.contiguous() for f in feats]
+        outs = []
+        for i in range(0, len(feats), MAX_LEVELS_PER_LAUNCH):
+            outs += ops.depth_conv_fwd(feats[i:i + MAX_LEVELS_PER_LAUNCH], image, conv.bias.detach(), bn.running_mean, bn.running_var,
+                                       bn.weight.detach(), bn.bias.detach(), bn.eps, gate)
+        return outs
+
+    def _run(self, feats, intrin, ida00, scale_depth_factor):
+        if len({f.shape[0] for f in feats}) != 1:
+            raise ValueError('DepthNet: every level must hold the same cameras')
+        if self._uses_torch_ops(feats):
+            return self._forward_torch(feats, intrin, ida00, scale_depth_factor)
+        with torch.no_grad():
+            return self._forward_hip(feats, intrin, ida00, scale_depth_factor)
+
+    # ---- the stage ------------------------------------------------------------------------------------------------------
+    def forward(self, x, mats_dict, scale_depth_factor=1000.0):
+        """The reference's per-level call (:79-105): x (1, N, C, H, W) (or (N, C, H, W)), mats_dict {'intrin_mats': N 4x4,
+        'ida_mats': list of 1 or N 3x3} -> (N, C, H, W), which the head unsqueezes (:319)."""
+        x = self._squeeze_batch(x)
+        intrin = _intrinsics(mats_dict['intrin_mats'])
+        if intrin.shape[0] != x.shape[0]:
+            raise ValueError(f'DepthNet: {intrin.shape[0]} intrinsics for {x.shape[0]} cameras')
+        return self._run([x], intrin, _ida00(mats_dict['ida_mats'], x.shape[0]), scale_depth_factor)[0]
+
+    def forward_levels(self, mlvl_feats, img_metas, scale_depth_factor=1000.0):
+        """The head's loop over the levels (:313-320) as one call: mlvl_feats, a list of (1, N, C, H_l, W_l) maps -> the list of
+        (1, N, C, H_l, W_l) maps FeaturePositionEmbedding takes.  The gate is computed once and the levels share one launch."""
+        if len(img_metas) != 1:
+            raise ValueError(f'DepthNet: {len(img_metas)} samples; the reference takes B = 1 only')
+        feats = [self._squeeze_batch(f) for f in mlvl_feats]
+        intrin = _intrinsics(img_metas[0]['intrinsics'])
+        if intrin.shape[0] != feats[0].shape[0]:
+            raise ValueError(f'DepthNet: {intrin.shape[0]} intrinsics for {feats[0].shape[0]} cameras')
+        outs = self._run(feats, intrin, _ida00(img_metas[0]['ida_mats'], intrin.shape[0]), scale_depth_factor)
+        return [o.unsqueeze(0) for o in outs]

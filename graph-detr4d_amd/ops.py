@@ -2429,6 +2429,69 @@ def mha_core_presplit_fwd(q, kv, num_heads, attn_mask=None, want_lse=False, drop
     return (out, lse) if want_lse else out
 
 
+def depth_net_image(conv_w):
+    """gd4d_depth_net_image: the camera-aware DepthNet's 3x3 weight (256, 256, 3, 3) fp32 -> its bf16 hi / lo fragment image for
+    depth_conv_fwd (2.25 MB; remake it when the weight changes)."""
+    lib = _lib.load()
+    c = conv_w.shape[0]
+    nbytes = int(lib.gd4d_depth_net_image_bytes(int(c)))
+    if nbytes == 0 or tuple(conv_w.shape) != (c, c, 3, 3):
+        raise _lib.Gd4dError(f'depth_net_image: weight {tuple(conv_w.shape)}; the kernel takes (256, 256, 3, 3)')
+    img = torch.empty(nbytes, device=conv_w.device, dtype=torch.uint8)
+    code = lib.gd4d_depth_net_image(_dev(conv_w.contiguous(), 'conv_w', torch.float32), int(c), _dev(img, 'image', torch.uint8), _stream())
+    _lib.check(code, 'gd4d_depth_net_image')
+    return img
+
+
+def cam_gate_fwd(intrinsics, ida00, fc1_w, fc1_b, fc2_w, fc2_b, se_reduce_w, se_reduce_b, se_expand_w, se_expand_b,
+                 scale_depth_factor=1000.0, out=None):
+    """gd4d_cam_gate_fwd: intrinsics (N, 4, 4), ida00 (1 or N) = ida[..., 0, 0] -> the camera gate (N, 256) =
+    sigmoid(se(mlp(pixel_size * scale_depth_factor / aug_scale))) of DepthNet.forward (detr3d_head_pe_camaware.py:86-100).
+    The weights as the modules hold them (mlp.fc1 (256, 1), 1x1 convolutions (256, 256, 1, 1))."""
+    lib = _lib.load()
+    f32 = torch.float32
+    n = intrinsics.shape[0]
+    if tuple(intrinsics.shape) != (n, 4, 4) or ida00.dim() != 1:
+        raise ValueError('cam_gate_fwd: intrinsics (N, 4, 4) and ida00 (1 or N) expected')
+    c = fc2_w.shape[0]
+    if out is None:
+        out = torch.empty(n, c, device=intrinsics.device, dtype=f32)
+    elif tuple(out.shape) != (n, c):
+        raise ValueError(f'cam_gate_fwd: out must be ({n}, {c})')
+    w = [t.detach().contiguous() for t in (fc1_w, fc1_b, fc2_w, fc2_b, se_reduce_w, se_reduce_b, se_expand_w, se_expand_b)]
+    names = ('fc1_w', 'fc1_b', 'fc2_w', 'fc2_b', 'se_reduce_w', 'se_reduce_b', 'se_expand_w', 'se_expand_b')
+    code = lib.gd4d_cam_gate_fwd(_dev(intrinsics, 'intrinsics', f32), _dev(ida00, 'ida00', f32), int(n), int(ida00.shape[0]),
+                                 float(scale_depth_factor), *[_dev(t, nm, f32) for t, nm in zip(w, names)], int(c),
+                                 _dev(out, 'out', f32), _stream())
+    _lib.check(code, 'gd4d_cam_gate_fwd')
+    return out
+
+
+def depth_conv_fwd(feats, image, bias, bn_mean, bn_var, bn_weight, bn_bias, eps, gate, outs=None):
+    """gd4d_depth_conv_fwd: L <= 4 levels (N, 256, H_l, W_l) fp32 NCHW -> relu(BN(conv3x3(x) + bias)) * gate[:, :, None, None]
+    per level, all levels in one launch.  image = depth_net_image(reduce_conv[0].weight); BN with its running statistics;
+    gate (N, 256) (cam_gate_fwd).  outs: the L (N, 256, H_l, W_l) tensors to write."""
+    lib = _lib.load()
+    f32 = torch.float32
+    nl = len(feats)
+    n = feats[0].shape[0]
+    if any(f.dim() != 4 or f.shape[0] != n or f.shape[1] != feats[0].shape[1] for f in feats):
+        raise ValueError('depth_conv_fwd: levels (N, C, H, W) with the same N and C expected')
+    if outs is None:
+        outs = [torch.empty(f.shape, device=f.device, dtype=f32) for f in feats]
+    elif len(outs) != nl or any(tuple(o.shape) != tuple(f.shape) for o, f in zip(outs, feats)):
+        raise ValueError('depth_conv_fwd: outs must match the levels\' shapes')
+    fp = (ctypes.c_void_p * nl)(*[_dev(f, 'feats', f32).value for f in feats])
+    op = (ctypes.c_void_p * nl)(*[_dev(o, 'outs', f32).value for o in outs])
+    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in feats for x in f.shape[2:]])
+    code = lib.gd4d_depth_conv_fwd(fp, op, lv, nl, int(n), int(feats[0].shape[1]), _dev(image, 'image', torch.uint8),
+                                   _dev(bias, 'bias', f32), _dev(bn_mean, 'bn_mean', f32), _dev(bn_var, 'bn_var', f32),
+                                   _dev(bn_weight, 'bn_weight', f32), _dev(bn_bias, 'bn_bias', f32), float(eps),
+                                   _dev(gate, 'gate', f32), _stream())
+    _lib.check(code, 'gd4d_depth_conv_fwd')
+    return outs
+
+
 def _first_tensor(args):
     for a in args:
         if torch.is_tensor(a):

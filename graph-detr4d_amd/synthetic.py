@@ -49,6 +49,19 @@ def camera_rig(num_frames=1, img_hw=(900, 1600), cam_radius=1.5, cam_height=1.5,
     return np.stack(mats).astype(dtype)
 
 
+def camera_intrinsics(num_frames=1, img_hw=(900, 1600), dtype=np.float32):
+    """(6*num_frames, 4, 4) viewpads of camera_rig's cameras (the same K; img_metas['intrinsics'] of the camera-aware head)."""
+    h, w = img_hw
+    mats = []
+    for _ in range(num_frames):
+        for f in _FOCALS:
+            m = np.eye(4)
+            m[0, 0] = m[1, 1] = f * w / 1600.0
+            m[0, 2], m[1, 2] = w / 2.0, h / 2.0
+            mats.append(m)
+    return np.stack(mats).astype(dtype)
+
+
 def make_img_metas(lidar2img, img_shape=IMG_SHAPE, batch=1, pad_shape=None):
     """The `img_metas` contract of the attention modules; `pad_shape` (read by the head's feature
     position embedding) defaults to the image height rounded up to a multiple of 32 (900 -> 928, config ...ceph.py)."""

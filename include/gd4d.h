@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GD4D_ABI_VERSION 55
+#define GD4D_ABI_VERSION 56
 
 enum { GD4D_F32 = 0, GD4D_BF16 = 1 };
 
@@ -1090,6 +1090,29 @@ int gd4d_linear_sum_assignment_batch(const float* cost, const int64_t* cost_offs
 size_t gd4d_hungarian_assign_workspace_bytes(int NL, int B, int Q, int max_gt);
 int gd4d_hungarian_assign_fwd(const float* cost, const int32_t* gt_start, int32_t* assigned, int32_t* status, void* workspace,
                               size_t workspace_bytes, int NL, int B, int Q, int sum_gt, int max_gt, void* stream);
+
+/* Camera-aware DepthNet of Detr3DHeadPECAM (models/dense_heads/detr3d_head_pe_camaware.py:59-105, applied per level at :313-320),
+ * inference, B = 1, 256 channels (gd4d_depth_net.hip):
+ *     out[n, c] = relu(BN(conv3x3(x[n]) + bias))[c] * gate[n, c]
+ * gd4d_depth_net_image - the 3x3 weight (256, 256, 3, 3) fp32 (reduce_conv.0) split into bf16 hi / lo MFMA fragments for
+ * gd4d_depth_conv_fwd; image: gd4d_depth_net_image_bytes(channels) bytes, 16-B aligned (0 bytes: channels other than 256).  Remake it
+ * when the weight changes.
+ * gd4d_cam_gate_fwd - gate (N, 256) = sigmoid(se(mlp(s[n]))), s[n] = |(inv(K_n)[0,0], inv(K_n)[1,1])| * scale_depth_factor /
+ * sqrt(2 ida00[n]^2) (:86-100; the reference reads ida[..., 0, 0] twice) from intrinsics (N, 4, 4) and ida00 (n_ida = 1: broadcast
+ * over the cameras, or N): mlp.fc1 (256, 1) + (256), ReLU, mlp.fc2 (256, 256) + (256), se.conv_reduce (256, 256) + (256), ReLU,
+ * se.conv_expand (256, 256) + (256), all fp32 (the three square weights 16-B aligned).
+ * gd4d_depth_conv_fwd - the convolution (pad 1, stride 1) and its epilogue (+ bias, BatchNorm2d with running statistics bn_mean /
+ * bn_var / bn_weight / bn_bias and eps, ReLU, x gate) for 1 <= levels <= 4 NCHW levels x[l] / out[l] (N, 256, H_l, W_l) in ONE launch;
+ * x / out / level_hw ({H_0, W_0, H_1, ...}) are HOST arrays of device pointers / sizes.  Channels other than 256, no level or more
+ * than 4, N <= 0: GD4D_EUNSUPPORTED; an image not 16-B aligned: GD4D_EALIGN. */
+size_t gd4d_depth_net_image_bytes(int channels);
+int gd4d_depth_net_image(const float* conv_w, int channels, void* image, void* stream);
+int gd4d_cam_gate_fwd(const float* intrinsics, const float* ida00, int n, int n_ida, float scale_depth_factor, const float* fc1_w,
+                      const float* fc1_b, const float* fc2_w, const float* fc2_b, const float* se_reduce_w, const float* se_reduce_b,
+                      const float* se_expand_w, const float* se_expand_b, int channels, float* gate, void* stream);
+int gd4d_depth_conv_fwd(const float* const* x, float* const* out, const int32_t* level_hw, int levels, int n, int channels,
+                        const void* image, const float* bias, const float* bn_mean, const float* bn_var, const float* bn_weight,
+                        const float* bn_bias, float eps, const float* gate, void* stream);
 
 #ifdef __cplusplus
 }

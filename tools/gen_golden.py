@@ -566,6 +566,107 @@ def case_head_pe(name, *, frames, img_hw, pad_hw, strides, seed, depth_num=64, n
     save(name, meta, **arrays)
 
 
+def case_head_pe_cam(name, *, img_hw, pad_hw, strides, seed, ida_scale, cams, weight_keep, depth_num=64, num_query=8,
+                     num_layers=1):
+    """The camera-aware head's feature stage from the reference's own `Detr3DHeadPECAM.forward`
+    (dense_heads/detr3d_head_pe_camaware.py:297-420), run unmodified on a shell object as case_head_pe does for Detr3DHeadPE: its
+    `depth_net` is the reference's `DepthNet` (:59-105) with non-trivial BatchNorm running statistics, the transformer a recorder
+    of the maps handed over.  Cameras `cams` of the rig with their intrinsics (front and back: two focal lengths, two gates), one
+    non-identity ida matrix (the pipeline keeps one: transform_3d.py:389), four levels 9 x 9 down to 2 x 2 (tile tails and borders of
+    the convolution; the reference's squeeze() would also drop a level of height or width 1).  The fixture stays under 1 MB."""
+    import importlib
+    import types
+    head_mod, pe_mod = refstub.load_head_pe()
+    cam_mod = importlib.import_module('projects.mmdet3d_plugin.models.dense_heads.detr3d_head_pe_camaware')
+    torch.manual_seed(seed)
+    n = len(cams)
+    levels = [(-(-pad_hw[0] // s), -(-pad_hw[1] // s)) for s in strides]
+    feats, packed = grid_features(n, levels, 1, seed)
+    rig = small_rig(1, img_hw)[list(cams)]
+    intrinsics = synthetic.camera_intrinsics(1, img_hw)[list(cams)]
+    ida = torch.tensor([[ida_scale, 0., -3.], [0., ida_scale, -5.], [0., 0., 1.]])
+    embed = 256
+    g = torch.Generator().manual_seed(seed + 5)
+    hs = torch.round(torch.randn(num_layers, num_query, 1, embed, generator=g) * 64) / 64
+    init_ref = torch.rand(1, num_query, 3, generator=g)
+    inter_ref = torch.rand(num_layers, 1, num_query, 3, generator=g)
+    recorded = {}
+
+    class Recorder(nn.Module):
+        def forward(self, mlvl_feats, query_embeds, reg_branches=None, img_metas=None):
+            recorded['feats'] = [f.detach().clone() for f in mlvl_feats]
+            return hs.clone(), init_ref.clone(), inter_ref.clone()
+
+    class Shell(nn.Module):                       # the attributes Detr3DHeadPECAM.forward / position_embeding read
+        def __init__(self):
+            super().__init__()
+            self.embed_dims, self.depth_num, self.depth_start = embed, depth_num, 1
+            self.pc_range = PC_RANGE
+            self.position_dim = 3 * depth_num
+            self.with_box_refine, self.scale_pred = True, False
+            self.position_encoder = nn.Sequential(nn.Conv2d(self.position_dim, embed * 4, 1), nn.ReLU(),
+                                                  nn.Conv2d(embed * 4, embed, 1))
+            self.adapt_pos3d = nn.Sequential(nn.Conv2d(embed * 3 // 2, embed * 4, 1), nn.ReLU(),
+                                             nn.Conv2d(embed * 4, embed, 1))
+            self.fpe = cam_mod.SELayer(embed)
+            self.depth_net = cam_mod.DepthNet(256, 256, 80)                                  # :198
+            self.positional_encoding = pe_mod.SinePositionalEncoding3D(num_feats=128, normalize=True, offset=-0.5)
+            self.query_embedding = nn.Embedding(num_query, embed * 2)
+            cls = lambda: nn.Sequential(nn.Linear(embed, embed), nn.LayerNorm(embed), nn.ReLU(inplace=True),
+                                        nn.Linear(embed, embed), nn.LayerNorm(embed), nn.ReLU(inplace=True),
+                                        nn.Linear(embed, 10))
+            reg = lambda: nn.Sequential(nn.Linear(embed, embed), nn.ReLU(), nn.Linear(embed, embed), nn.ReLU(),
+                                        nn.Linear(embed, 10))
+            self.cls_branches = nn.ModuleList(cls() for _ in range(num_layers))
+            self.reg_branches = nn.ModuleList(reg() for _ in range(num_layers))
+            self.transformer = Recorder()
+    shell = Shell().eval()
+    quantise_params_(shell, seed + 1, std=0.02)
+    bn = shell.depth_net.reduce_conv[1]
+    gb = torch.Generator().manual_seed(seed + 7)
+    bn.running_mean.copy_(torch.round(torch.randn(embed, generator=gb) * 0.3 * W_SCALE) / W_SCALE)
+    bn.running_var.copy_(torch.round((0.25 + 2 * torch.rand(embed, generator=gb)) * W_SCALE) / W_SCALE)
+    # the weight matrices (2.6 M entries) on a coarse grid (k/128), all but a fraction `weight_keep` of them zero, so that they
+    # compress to a fraction of their int8 size; the camera gate's MLP and SE dense and with a wider spread (a gate away from 0.5)
+    gate_params = {id(p) for p in list(shell.depth_net.mlp.parameters()) + list(shell.depth_net.se.parameters())}
+    for p in shell.parameters():
+        if p.dim() < 2:
+            continue
+        std = 0.045 if id(p) in gate_params else 0.03
+        keep = torch.rand(p.shape, generator=gb) < (1.0 if id(p) in gate_params else weight_keep)
+        p.data.copy_(torch.round((torch.randn(p.shape, generator=gb) * std).clamp(-0.12, 0.12) * 128) / 128 * keep)
+    shell.position_embeding = types.MethodType(cam_mod.Detr3DHeadPECAM.position_embeding, shell)
+    img_shapes = [(img_hw[0] - (4 if c % 3 == 1 else 0), img_hw[1] - (8 if c % 3 == 2 else 0), 3) for c in range(n)]
+    metas = [dict(lidar2img=[rig[i] for i in range(n)], img_shape=img_shapes, pad_shape=[(pad_hw[0], pad_hw[1], 3)] * n,
+                  intrinsics=[intrinsics[i] for i in range(n)], ida_mats=[ida])]
+    with torch.no_grad():
+        outs = cam_mod.Detr3DHeadPECAM.forward(shell, [f.clone() for f in feats], metas)    # the reference forward
+        arrays = {}
+        for l in range(len(levels)):                  # the DepthNet's own output per level, from the same reference module
+            mats = dict(intrin_mats=metas[0]['intrinsics'], ida_mats=metas[0]['ida_mats'])
+            arrays[f'depth{l}'] = shell.depth_net(feats[l].clone(), mats)
+            arrays[f'out{l}'] = recorded['feats'][l]
+        dn = shell.depth_net                          # the camera gate (:86-100 restated from its pieces), for finer tests
+        inv = torch.inverse(torch.tensor(intrinsics))
+        pixel = torch.norm(torch.stack([inv[..., 0, 0], inv[..., 1, 1]], dim=-1), dim=-1).reshape(-1, 1)
+        aug = torch.sqrt(ida[0, 0] ** 2 + ida[0, 0] ** 2)
+        arrays['cam_gate'] = torch.sigmoid(dn.se.conv_expand(dn.se.act1(dn.se.conv_reduce(
+            dn.mlp(pixel * 1000.0 / aug)[..., None, None])))).view(n, embed)
+    assert outs['enc_cls_scores'] is None
+    arrays.update(all_cls_scores=outs['all_cls_scores'], all_bbox_preds=outs['all_bbox_preds'], hs=hs,
+                  init_reference=init_ref, inter_references=inter_ref)
+    for l, pk in enumerate(packed):
+        arrays[f'feat{l}@q'] = pk
+    arrays['lidar2img'] = rig.astype(np.float32)
+    arrays['intrinsics'] = intrinsics
+    arrays['ida'] = ida.numpy()
+    arrays.update(pack_state(shell))
+    meta = dict(kind='head_pe_cam', num_cams=n, levels=levels, pc_range=PC_RANGE, depth_num=depth_num, depth_start=1,
+                img_shapes=img_shapes, pad_shape=[pad_hw[0], pad_hw[1], 3], feat_scale=FEAT_SCALE, w_scale=W_SCALE,
+                batch=1, num_query=num_query, num_layers=num_layers, scale_depth_factor=1000.0, bn_eps=bn.eps)
+    save(name, meta, **arrays)
+
+
 def case_head_loss(name, *, num_query, gts, seed, num_layers=3, degenerate=False):
     """Training-side step after the path: the reference's own `Detr3DHeadPE.loss`
     (dense_heads/detr3d_head_pe.py:1014-1094) -> `loss_single` (:782-845) -> `get_targets` / `_get_target_single`
@@ -701,6 +802,8 @@ def main():
     case_decoder('decoder_detr3d', cross='Detr3DCrossAtten', num_query=32, frames=1, batch=1,
                  img_hw=(64, 112), seed=402, num_layers=2)
     case_head_pe('head_pe', frames=1, img_hw=(64, 112), pad_hw=(64, 112), strides=(8, 16), seed=601)
+    case_head_pe_cam('head_pe_cam', img_hw=(72, 72), pad_hw=(72, 72), strides=(8, 16, 32, 64), seed=611, ida_scale=0.75, cams=(0, 3),
+                     weight_keep=0.08)
     case_decode('decode', num_query=90, batch=2, seed=501, max_num=300)
     case_decode('decode_thr', num_query=64, batch=1, seed=502, max_num=100, score_threshold=0.2)
     case_decode('decode_code8', num_query=20, batch=1, seed=503, max_num=100, code_size=8)
