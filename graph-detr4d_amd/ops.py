@@ -1783,6 +1783,65 @@ def hungarian_assign_fwd(cost, gt_start, nl, b, q, sum_gt, max_gt, assigned=None
     return assigned, status
 
 
+
+def distill_match_cost_fwd(s_cls, s_box, t_cls, t_box, cls_weight=1.0, reg_weight=0.25, pseudo_gt=False):
+    """gd4d_distill_match_cost_fwd.  s_cls (NL, B, Qs, C), s_box (NL, B, Qs, code), t_cls (NL, B, Qt, C), t_box (NL, B, Qt, 10) fp32 on
+    the GPU: the teacher head's logits and box codes.  pseudo_gt=True: t_cls the soft labels per sample, t_box (NL, B, Qt, 9) the
+    denormalised boxes.  Returns the flat cost buffer (NL * B * Qs * Qt): block (l, b) at Qs * (l * B * Qt + b * Qt), shape (Qs, Qt)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    nl, b, qs, c = s_cls.shape
+    qt = t_cls.shape[2]
+    if tuple(s_box.shape[:3]) != (nl, b, qs) or tuple(t_cls.shape) != (nl, b, qt, c) or tuple(t_box.shape) != (nl, b, qt, 9 if pseudo_gt else 10):
+        raise ValueError('distill_match_cost_fwd: s_cls / s_box / t_cls / t_box shapes disagree')
+    cost = torch.empty(nl * b * qs * qt, device=s_cls.device, dtype=f32)
+    code = lib.gd4d_distill_match_cost_fwd(_dev(s_cls, 's_cls', f32), _dev(s_box, 's_box', f32), _dev(t_cls, 't_cls', f32),
+                                           _dev(t_box, 't_box', f32), _dev(cost, 'cost'), nl, b, qs, qt, c, s_box.shape[-1],
+                                           1 if pseudo_gt else 0, float(cls_weight), float(reg_weight), _stream())
+    _lib.check(code, 'gd4d_distill_match_cost_fwd')
+    return cost
+
+
+def lsa_dense_fwd(cost, gt_start, nl, b, q, sum_gt, max_gt, assigned=None, status=None, workspace=None):
+    """gd4d_lsa_dense_fwd: hungarian_assign_fwd's contract (same buffers, same outputs and status words) solved by the dense-problem
+    kernel.  Returns (assigned (NL, B, Q) int32, status (NL * B) int32).  No host synchronisation."""
+    lib = _lib.load()
+    dev = cost.device
+    i32 = torch.int32
+    if assigned is None:
+        assigned = torch.empty(nl, b, q, device=dev, dtype=i32)
+    if status is None:
+        status = torch.empty(nl * b, device=dev, dtype=i32)
+    nbytes = int(lib.gd4d_lsa_dense_workspace_bytes(nl, b, q, max(int(max_gt), 1)))
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    code = lib.gd4d_lsa_dense_fwd(_dev(cost, 'cost', torch.float32), _dev(gt_start, 'gt_start', i32), _dev(assigned, 'assigned', i32),
+                                  _dev(status, 'status', i32), _dev(workspace, 'workspace', torch.uint8), workspace.numel(),
+                                  int(nl), int(b), int(q), int(sum_gt), int(max_gt), _stream())
+    _lib.check(code, 'gd4d_lsa_dense_fwd')
+    return assigned, status
+
+
+def distill_loss_fwd_bwd(s_cls, s_box, t_cls, t_box, assigned, code_weights, avg_factors, reweight_score=False,
+                         loss_cls_weight=1.0, loss_reg_weight=1.0):
+    """gd4d_distill_loss_fwd_bwd.  Returns (loss (NL, 2), grad_s_cls like s_cls, grad_s_box like s_box)."""
+    lib = _lib.load()
+    f32, i32 = torch.float32, torch.int32
+    nl, b, qs, c = s_cls.shape
+    qt = t_cls.shape[2]
+    if tuple(assigned.shape) != (nl, b, qs) or tuple(t_box.shape) != (nl, b, qt, 10) or tuple(t_cls.shape) != (nl, b, qt, c):
+        raise ValueError('distill_loss_fwd_bwd: shapes disagree')
+    loss = torch.empty(nl, 2, device=s_cls.device, dtype=f32)
+    gcls, gbox = torch.empty_like(s_cls), torch.empty_like(s_box)
+    code = lib.gd4d_distill_loss_fwd_bwd(_dev(s_cls, 's_cls', f32), _dev(s_box, 's_box', f32), _dev(t_cls, 't_cls', f32),
+                                         _dev(t_box, 't_box', f32), _dev(assigned, 'assigned', i32),
+                                         _dev(code_weights, 'code_weights', f32), _dev(avg_factors, 'avg_factors', f32),
+                                         _dev(loss, 'loss'), _dev(gcls, 'grad_cls'), _dev(gbox, 'grad_box'), nl, b, qs, qt, c,
+                                         s_box.shape[-1], 1 if reweight_score else 0, float(loss_cls_weight), float(loss_reg_weight),
+                                         _stream())
+    _lib.check(code, 'gd4d_distill_loss_fwd_bwd')
+    return loss, gcls, gbox
+
 class ChainOp(ctypes.Structure):
     """gd4d_chain_op (include/gd4d.h)."""
     _fields_ = [('kind', ctypes.c_int32), ('src', ctypes.c_int32), ('dst', ctypes.c_int32), ('res', ctypes.c_int32),

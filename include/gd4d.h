@@ -1114,6 +1114,45 @@ int gd4d_depth_conv_fwd(const float* const* x, float* const* out, const int32_t*
                         const void* image, const float* bias, const float* bn_mean, const float* bn_var, const float* bn_weight,
                         const float* bn_bias, float eps, const float* gate, void* stream);
 
+/* Detr4D_Distiller's instance distillation term (distillation/distillers/detr4d_distiller.py:143-166, gd4d_distill.hip): the student's
+ * predictions of every decoder layer are MATCHED against the teacher's, which act as pseudo ground truth.
+ *
+ * gd4d_distill_match_cost_fwd - DistillHungarianAssigner3D's cost (core/bbox/assigners/distill_hungarian_assigner_3d.py:106-114) for
+ *   every (layer, sample) in one launch: cost[q, t] = cls_weight * (pos[q] . p[t] + neg[q] . (1 - p[t]))          (match_cost.py:52-91)
+ *   + reg_weight * sum_{k<8} |s_box[q, k] - normalize_bbox(denormalize_bbox(t_box[t]))[k]|                         (core/bbox/util.py:38-87)
+ *   with pos / neg = BCE-with-logits of s_cls against 1 / 0 and p = sigmoid(t_cls[l, 0]) - batch 0 for EVERY sample, the reference's
+ *   indexing (detr4d_distiller.py:159).  s_cls (NL, B, Qs, C <= 64), s_box (NL, B, Qs, code >= 8), t_cls (NL, B, Qt, C),
+ *   t_box (NL, B, Qt, 10).  cost: block (l, b) at Qs (l B Qt + b Qt), (Qs, Qt) row-major - the layout gd4d_hungarian_assign_fwd and
+ *   gd4d_lsa_dense_fwd read with gt_start = {0, Qt, 2 Qt, ...}, sum_gt = B Qt, max_gt = Qt.  No nan_to_num (the reference has none): +inf
+ *   stays; NaN and -inf, which scipy refuses, are written as NaN (gd4d_match_cost_fwd's marker: status 1 of the solvers).
+ *   pseudo_gt != 0: the teacher is given as the assigner receives it - t_cls the soft labels of each sample (no sigmoid, no batch-0
+ *   indexing), t_box the denormalised boxes (NL, B, Qt, 9), only normalize_bbox applied (DistillHungarianAssigner3D.assign's inputs).
+ *
+ * gd4d_lsa_dense_fwd - an exact linear sum assignment for dense problems on the device, same arguments, layout, output and status words
+ *   as gd4d_hungarian_assign_fwd (status 0 solved, 1 a NaN or -inf cost: nothing matched, 2 infeasible).  One 1024-thread workgroup per
+ *   problem: a parallel warm start (square: column reduction; rectangular: row reduction), then a shortest augmenting path in fp64 per row
+ *   left free, from those duals (the arithmetic of scipy's solver, from the fp32 costs).  The assignment is optimal: IDENTICAL to
+ *   scipy's / gd4d_linear_sum_assignment_batch's whenever the optimum is unique (the case for continuous costs); with exact ties its total
+ *   cost equals theirs (to fp64 rounding, 1e-9 relative) but the matching may differ.  max(Q, max_gt) <= 4096; workspace:
+ *   gd4d_lsa_dense_workspace_bytes (a transposed fp32 copy of problems with fewer columns than rows).
+ *
+ * gd4d_distill_loss_fwd_bwd - Detr3DHeadPE.loss_distill_single (dense_heads/detr3d_head_pe.py:851-925, targets :927-1012) for every
+ *   layer: loss (NL, 2) = (distill_loss_cls, distill_loss_reg) and grad_cls / grad_box = d loss[l, 0] / d s_cls[l], d loss[l, 1] / d s_box[l].
+ *   assigned (NL, B, Qs) = b Qt + teacher index or -1 (what the solvers write).  Matched rows take the soft labels sigmoid(t_cls[l, 0, t])
+ *   and the target normalize_bbox(denormalize_bbox(t_box[l, b, t])); the others label num_classes (= C) and a zero target, which the
+ *   isfinite filter drops.  code_weights (10); avg_factors DEVICE 2 floats (cls_avg_factor, num_total_pos, reduce_mean-ed, clamped to >= 1
+ *   here); reweight != 0: the reg weights are multiplied by max_c labels and divided by the local sum of that maximum over rows with
+ *   labels[:, 0] != 10 (:908-911) instead of num_total_pos.  Both terms through nan_to_num.  code in 10..16. */
+int gd4d_distill_match_cost_fwd(const float* s_cls, const float* s_box, const float* t_cls, const float* t_box, float* cost, int NL,
+                                int B, int Qs, int Qt, int C, int code, int pseudo_gt, float cls_weight, float reg_weight, void* stream);
+size_t gd4d_lsa_dense_workspace_bytes(int NL, int B, int Q, int max_gt);
+int gd4d_lsa_dense_fwd(const float* cost, const int32_t* gt_start, int32_t* assigned, int32_t* status, void* workspace,
+                       size_t workspace_bytes, int NL, int B, int Q, int sum_gt, int max_gt, void* stream);
+int gd4d_distill_loss_fwd_bwd(const float* s_cls, const float* s_box, const float* t_cls, const float* t_box, const int32_t* assigned,
+                              const float* code_weights, const float* avg_factors, float* loss, float* grad_cls, float* grad_box, int NL,
+                              int B, int Qs, int Qt, int C, int code, int reweight, float loss_cls_weight, float loss_reg_weight,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

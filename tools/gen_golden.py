@@ -778,6 +778,88 @@ def case_distill(name, *, num_query, batch, seed, num_layers=3, num_classes=10, 
          losses=torch.stack([losses[k].detach() for k in keys]), grad_s_cls=s_cls.grad, grad_s_box=s_box.grad)
 
 
+def case_detr4d_distill(name, *, num_student, num_teacher, batch, seed, num_layers=2, reweight_score=False, loss_cls_weight=1.0,
+                        loss_reg_weight=0.25, degenerate=False):
+    """Detr4D_Distiller.get_instance_distill_loss (distillation/distillers/detr4d_distiller.py:143-168), called unbound on a shell whose
+    student head runs the reference's own `loss_distill_single` / `get_distill_targets` / `_get_distill_target_single`
+    (dense_heads/detr3d_head_pe.py:851-1012) with its `DistillHungarianAssigner3D` (DistillCrossEntropyLossCost + BBox3DL1Cost 0.25, the
+    distill configs') and `DistillCrossEntropyLoss`.  scipy is spied on: every cost matrix and every assignment is recorded, with the
+    loss terms and the gradients of their sum with respect to the student's outputs.  degenerate: one teacher box per layer and sample
+    whose exp(w) overflows (its cost column is +inf; with more teacher than student queries it stays unmatched)."""
+    distiller, head_mod, asg_mod, loss_mod = refstub.load_detr4d_distiller()
+    g = torch.Generator().manual_seed(seed)
+    pc_range = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
+
+    def boxes(n):
+        b = torch.randn(num_layers, batch, n, 10, generator=g)
+        b[..., 0:2] *= 20.
+        b[..., 2:4] = b[..., 2:4] * 0.5 + 0.5              # log w, log l
+        b[..., 5] = b[..., 5] * 0.3 + 0.4                  # log h
+        return b
+    t_cls = torch.randn(num_layers, batch, num_teacher, 10, generator=g) * 2 - 1
+    t_box = boxes(num_teacher)
+    if degenerate:
+        t_box[:, :, 1, 2] = 120.                            # exp overflows to inf
+    s_cls = (torch.randn(num_layers, batch, num_student, 10, generator=g) * 2 - 1)
+    s_box = boxes(num_student)
+    k = min(num_student, num_teacher) // 2                  # half the student queries near a (permuted) teacher query
+    perm = torch.randperm(num_teacher, generator=g)[:k]
+    s_box[:, :, :k] = t_box[:, :, perm] + 0.1 * torch.randn(num_layers, batch, k, 10, generator=g)
+    s_box[:, :, :k, 2] = torch.randn(num_layers, batch, k, generator=g) * 0.5 + 0.5
+    s_cls, s_box = s_cls.requires_grad_(), s_box.requires_grad_()
+    code_weights = [1., 1., 1., 1., 1., 1., 1., 1., 0.2, 0.2]
+
+    class Head(nn.Module):                                  # what loss_distill_single and its targets read of the student head
+        def __init__(self):
+            super().__init__()
+            self.num_classes = self.cls_out_channels = 10
+            self.code_size = 10
+            self.bg_cls_weight, self.sync_cls_avg_factor = 0.0, True
+            self.pc_range = pc_range
+            self.code_weights = nn.Parameter(torch.tensor(code_weights), requires_grad=False)
+            self.distill_assigner = asg_mod.DistillHungarianAssigner3D(
+                cls_cost=dict(type='DistillCrossEntropyLossCost', weight=1.0), reg_cost=dict(type='BBox3DL1Cost', weight=0.25),
+                iou_cost=dict(type='IoUCost', weight=0.0), pc_range=pc_range)
+            self.distill_sampler = refstub.PseudoSampler()
+            self.loss_cls_distill = loss_mod.DistillCrossEntropyLoss(use_sigmoid=True, loss_weight=loss_cls_weight)
+            self.loss_reg_distill = refstub.L1Loss(loss_weight=loss_reg_weight)
+    head = Head()
+    for fn in ('loss_distill_single', 'get_distill_targets', '_get_distill_target_single'):
+        setattr(head, fn, types.MethodType(getattr(head_mod.Detr3DHeadPE, fn), head))
+    shell = types.SimpleNamespace(reweight_score=reweight_score, student=types.SimpleNamespace(pts_bbox_head=head),
+                                  teacher=types.SimpleNamespace(pts_bbox_head=types.SimpleNamespace(pc_range=pc_range)))
+    costs, assigned = [], []
+    real_lsa = asg_mod.linear_sum_assignment
+
+    def spy(cost):
+        costs.append(cost.clone())
+        return real_lsa(cost)
+    real_assign = head.distill_assigner.assign
+
+    def assign_spy(*a, **kw):
+        r = real_assign(*a, **kw)
+        assigned.append(r.gt_inds.clone())
+        return r
+    asg_mod.linear_sum_assignment = spy
+    head.distill_assigner.assign = assign_spy
+    try:
+        losses = distiller.Detr4D_Distiller.get_instance_distill_loss(shell, dict(all_cls_scores=t_cls, all_bbox_preds=t_box),
+                                                                       dict(all_cls_scores=s_cls, all_bbox_preds=s_box))
+    finally:
+        asg_mod.linear_sum_assignment = real_lsa
+    sum(losses.values()).backward()
+    keys = list(losses.keys())
+    arrays = dict(t_cls=t_cls, t_box=t_box, s_cls=s_cls.detach(), s_box=s_box.detach(), grad_s_cls=s_cls.grad, grad_s_box=s_box.grad,
+                  losses=torch.stack([losses[k].detach().reshape(()) for k in keys]))
+    for i in range(num_layers * batch):
+        arrays[f'cost_l{i // batch}_b{i % batch}'] = costs[i]
+        arrays[f'assigned_l{i // batch}_b{i % batch}'] = assigned[i]
+    meta = dict(kind='detr4d_distill', num_student=num_student, num_teacher=num_teacher, batch=batch, num_layers=num_layers, seed=seed,
+                reweight_score=reweight_score, loss_cls_weight=loss_cls_weight, loss_reg_weight=loss_reg_weight, loss_keys=keys,
+                cls_cost_weight=1.0, reg_cost_weight=0.25, code_weights=code_weights, pc_range=pc_range, degenerate=degenerate)
+    save(name, meta, **arrays)
+
+
 def main():
     torch.set_num_threads(8)
     case_deform('deform_n6', num_query=48, frames=1, batch=1, img_hw=(128, 224), seed=101)
@@ -814,6 +896,13 @@ def main():
     case_distill('distill_loss', num_query=50, batch=1, seed=801)
     case_distill('distill_loss_b2_mean', num_query=30, batch=2, seed=802, num_layers=2, reweight_score=False,
                  loss_cls_weight=2.0, loss_reg_weight=0.25)
+    case_detr4d_distill('detr4d_distill_b1_rw', num_student=40, num_teacher=40, batch=1, seed=901, reweight_score=True,
+                        loss_cls_weight=1.0, loss_reg_weight=0.25)
+    case_detr4d_distill('detr4d_distill_b2', num_student=32, num_teacher=32, batch=2, seed=902, loss_cls_weight=1.0, loss_reg_weight=0.25)
+    case_detr4d_distill('detr4d_distill_fewer_teacher', num_student=40, num_teacher=24, batch=2, seed=903, reweight_score=True,
+                        loss_cls_weight=1.0, loss_reg_weight=0.25)
+    case_detr4d_distill('detr4d_distill_degenerate', num_student=24, num_teacher=32, batch=1, seed=904, degenerate=True,
+                        loss_cls_weight=0.0, loss_reg_weight=0.25)
 
 
 if __name__ == '__main__':

@@ -655,3 +655,37 @@ def load_distiller():
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         return importlib.import_module(rel + '.distillers.mix_distill')
+
+
+# --------------------------------------------------------------------------------------
+# Detr4D_Distiller: the instance term that MATCHES the student's predictions to the teacher's
+# --------------------------------------------------------------------------------------
+def load_detr4d_distiller():
+    """Import, unmodified, the reference's distillation/distillers/detr4d_distiller.py (for the unbound
+    `Detr4D_Distiller.get_instance_distill_loss`), its Detr3DHeadPE (`loss_distill_single`, `get_distill_targets`,
+    `_get_distill_target_single`), `DistillHungarianAssigner3D` with `DistillCrossEntropyLossCost` / `BBox3DL1Cost` and
+    `DistillCrossEntropyLoss`.  The mmdet pieces they call (AssignResult, PseudoSampler, L1Loss, weight_reduce_loss, multi_apply,
+    reduce_mean) are restated above from their published definitions (single process: reduce_mean is the identity).
+    Returns (distiller module, head module, assigner module, loss module)."""
+    dist_mod = load_distiller()                          # the distillation package namespace + detector stubs
+    head, _ = load_head_loss()
+    sys.modules['mmdet.models'].build_detector = None
+    sys.modules['mmdet.models'].LOSSES = Registry('loss')
+    _mod('mmdet.models.builder', LOSSES=sys.modules['mmdet.models'].LOSSES)
+
+    def weight_reduce_loss(loss, weight=None, reduction='mean', avg_factor=None):
+        assert reduction == 'mean' and avg_factor is not None
+        return _weight_reduce_mean(loss, weight, avg_factor)
+    _mod('mmdet.models.losses', weight_reduce_loss=weight_reduce_loss)
+    full = 'projects.mmdet3d_plugin.models.losses'
+    if full not in sys.modules:
+        m = types.ModuleType(full)
+        m.__path__ = [os.path.join(REFERENCE_ROOT, *full.split('.'))]
+        sys.modules[full] = m
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        loss_mod = importlib.import_module(full + '.distill_cross_entropy_loss')
+        asg = importlib.import_module('projects.mmdet3d_plugin.core.bbox.assigners.distill_hungarian_assigner_3d')
+        distiller = importlib.import_module('projects.mmdet3d_plugin.distillation.distillers.detr4d_distiller')
+    del dist_mod
+    return distiller, head, asg, loss_mod
