@@ -40,12 +40,9 @@
 // matrix pipe busy 62 %, waves waiting on instruction dependencies 66 % of their cycles; LDS bank conflicts present, not located.
 // Left off: padding the stages, two workgroups per CU, fusing the epilogue into the position embedding's gate / fuse kernel.
 #include "gd4d_common.h"
+#include "gd4d_bf16x3.h"
 
 namespace gd4d {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 dn_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float dn_f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned dn_u32x4;
 
 constexpr int DN_C = 256, DN_KC = 32, DN_CHUNKS = DN_C / DN_KC, DN_TAPS = 9, DN_STEPS = DN_CHUNKS * DN_TAPS;
 constexpr int DN_T = 16, DN_HE = DN_T + 2, DN_HALO = DN_HE * DN_HE;          // 16 x 16 tile, 18 x 18 halo
@@ -63,26 +60,6 @@ constexpr int DN_MAX_LEVELS = 4;
 
 static_assert(DN_LDS <= 160 * 1024, "LDS budget of a CU");
 
-__device__ __forceinline__ unsigned dn_cvt_pk_bf16(float lo_elem, float hi_elem) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo_elem), "v"(hi_elem));
-  return r;
-}
-
-// 8 floats -> 16 bytes of bf16 "hi" halves and 16 bytes of bf16 residuals
-__device__ __forceinline__ void dn_split8(const float (&v)[8], dn_u32x4& h, dn_u32x4& l) {
-  unsigned hh[4], ll[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hh[i] = dn_cvt_pk_bf16(v[2 * i], v[2 * i + 1]);
-    const float ra = v[2 * i] - __uint_as_float(hh[i] << 16);              // exact: hi is a rounding of the value
-    const float rb = v[2 * i + 1] - __uint_as_float(hh[i] & 0xffff0000u);
-    ll[i] = dn_cvt_pk_bf16(ra, rb);
-  }
-  h = dn_u32x4{hh[0], hh[1], hh[2], hh[3]};
-  l = dn_u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
-
 // ---- weight image ---------------------------------------------------------------------------------------------------------
 // item i = ((step * 2 + plane) * 4 + k-group) * 256 + out channel, 16 bytes each: byte offset 16 i
 __global__ __launch_bounds__(256) void depth_net_image_kernel(const float* __restrict__ w, char* __restrict__ image) {
@@ -98,10 +75,10 @@ __global__ __launch_bounds__(256) void depth_net_image_kernel(const float* __res
     const uint16_t h = f32_to_bf16(v);
     e[j] = plane ? f32_to_bf16(v - bf16_to_f32(h)) : h;
   }
-  dn_u32x4 o;
+  u32x4 o;
 #pragma unroll
   for (int j = 0; j < 4; ++j) o[j] = (unsigned)e[2 * j] | ((unsigned)e[2 * j + 1] << 16);
-  *reinterpret_cast<dn_u32x4*>(image + (size_t)i * 16) = o;
+  *reinterpret_cast<u32x4*>(image + (size_t)i * 16) = o;
 }
 
 // ---- camera gate ------------------------------------------------------------------------------------------------------------
@@ -254,25 +231,25 @@ __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvP
     if (h_live[ps]) {
       char* base = hbuf + buf * DN_H_STAGE;
       const int off = (tid + DN_THREADS * ps) * 16;
-      dn_u32x4 hi, lo;
-      dn_split8(hr, hi, lo);
-      *reinterpret_cast<dn_u32x4*>(base + off) = hi;
-      *reinterpret_cast<dn_u32x4*>(base + DN_H_ARR + off) = lo;
+      u32x4 hi, lo;
+      split8(hr, hi, lo);
+      *reinterpret_cast<u32x4*>(base + off) = hi;
+      *reinterpret_cast<u32x4*>(base + DN_H_ARR + off) = lo;
     }
   };
-  dn_u32x4 wr[2];
+  u32x4 wr[2];
   auto issue_w = [&](int s) {
     const char* src = p.image + (size_t)s * DN_W_STAGE + tid * 16;
-    wr[0] = *reinterpret_cast<const dn_u32x4*>(src);
-    wr[1] = *reinterpret_cast<const dn_u32x4*>(src + DN_W_ARR);
+    wr[0] = *reinterpret_cast<const u32x4*>(src);
+    wr[1] = *reinterpret_cast<const u32x4*>(src + DN_W_ARR);
   };
   auto park_w = [&](int buf) {
     char* base = wbuf + buf * DN_W_STAGE + tid * 16;
-    *reinterpret_cast<dn_u32x4*>(base) = wr[0];
-    *reinterpret_cast<dn_u32x4*>(base + DN_W_ARR) = wr[1];
+    *reinterpret_cast<u32x4*>(base) = wr[0];
+    *reinterpret_cast<u32x4*>(base + DN_W_ARR) = wr[1];
   };
 
-  dn_f32x16 acc[2][2];
+  f32x16 acc[2][2];
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
@@ -312,24 +289,20 @@ __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvP
 #pragma unroll 1                                       // (unrolled, the compiler hoists both halves' 64 fragment registers: 67 spilled)
       for (int ks = 0; ks < 2; ++ks) {
         const int kgrp = 2 * ks + kg;
-        dn_bf16x8 ah[2], al[2], bh[2], bl[2];
+        u32x4 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int aoff = (kgrp * DN_C + 64 * wm + 32 * i + l32) * 16;
           const int boff = (kgrp * DN_HALO + pix_hp[i] + tap_off) * 16;
-          ah[i] = __builtin_bit_cast(dn_bf16x8, *reinterpret_cast<const dn_u32x4*>(wb + aoff));
-          al[i] = __builtin_bit_cast(dn_bf16x8, *reinterpret_cast<const dn_u32x4*>(wb + DN_W_ARR + aoff));
-          bh[i] = __builtin_bit_cast(dn_bf16x8, *reinterpret_cast<const dn_u32x4*>(hb + boff));
-          bl[i] = __builtin_bit_cast(dn_bf16x8, *reinterpret_cast<const dn_u32x4*>(hb + DN_H_ARR + boff));
+          ah[i] = *reinterpret_cast<const u32x4*>(wb + aoff);
+          al[i] = *reinterpret_cast<const u32x4*>(wb + DN_W_ARR + aoff);
+          bh[i] = *reinterpret_cast<const u32x4*>(hb + boff);
+          bl[i] = *reinterpret_cast<const u32x4*>(hb + DN_H_ARR + boff);
         }
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < 2; ++ni) {
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-          }
+          for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma_32x32x16_x3(ah[mi], al[mi], bh[ni], bl[ni], acc[mi][ni]);
       }
       if (s + 1 < DN_STEPS) {
         park_w((s + 1) & 1);                                  // its readers finished before the last barrier

@@ -14,12 +14,9 @@
 // step k+2 are issued into registers as soon as step k+1 has been converted / parked into the other buffer (before the
 // barrier), so they are in flight across the barrier and the MFMAs of step k+1: one barrier per step.  128 KB of LDS, one workgroup of 16 waves per CU.
 #include "gd4d_common.h"
+#include "gd4d_bf16x3.h"
 
 namespace gd4d {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int GM_BM = 256, GM_BN = 256, GM_BK = 32, GM_THREADS = 1024;   // 16 waves, 4 x 4, each 64 x 64
 constexpr int GM_ARR = 4 * GM_BM * 16;               // bytes of one [4 k-groups][256 rows][16 B] array: 16 KB
@@ -33,27 +30,6 @@ struct GemmParams {
   float* c;
   int M, N, K, lda, ldc, relu, relu_in, mask_c;
 };
-
-__device__ __forceinline__ unsigned gm_cvt_pk_bf16(float lo_elem, float hi_elem) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo_elem), "v"(hi_elem));
-  return r;
-}
-
-// 8 consecutive floats -> 16 bytes of bf16 "hi" halves and 16 bytes of bf16 "lo" (residual) halves
-__device__ __forceinline__ void gm_split8(const float4& p, const float4& q, u32x4& h, u32x4& l) {
-  const float v[8] = {p.x, p.y, p.z, p.w, q.x, q.y, q.z, q.w};
-  unsigned hh[4], ll[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hh[i] = gm_cvt_pk_bf16(v[2 * i], v[2 * i + 1]);
-    const float ra = v[2 * i] - __uint_as_float(hh[i] << 16);            // exact: hi is a rounding of the value
-    const float rb = v[2 * i + 1] - __uint_as_float(hh[i] & 0xffff0000u);
-    ll[i] = gm_cvt_pk_bf16(ra, rb);
-  }
-  h = u32x4{hh[0], hh[1], hh[2], hh[3]};
-  l = u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
 
 __global__ __launch_bounds__(GM_THREADS) void gemm_bf16x3_kernel(const GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -101,7 +77,8 @@ __global__ __launch_bounds__(GM_THREADS) void gemm_bf16x3_kernel(const GemmParam
         x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f);
         y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f);
       }
-      gm_split8(ra[ps][0], ra[ps][1], h, l);
+      const float v[8] = {ra[ps][0].x, ra[ps][0].y, ra[ps][0].z, ra[ps][0].w, ra[ps][1].x, ra[ps][1].y, ra[ps][1].z, ra[ps][1].w};
+      split8(v, h, l);
       *reinterpret_cast<u32x4*>(base + off) = h;
       *reinterpret_cast<u32x4*>(base + GM_ARR + off) = l;
       *reinterpret_cast<u32x4*>(base + 2 * GM_ARR + off) = rwh[ps];
@@ -127,24 +104,20 @@ __global__ __launch_bounds__(GM_THREADS) void gemm_bf16x3_kernel(const GemmParam
     const char* base = smem + cur * GM_STAGE;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 ah[2], al[2], bh[2], bl[2];
+      u32x4 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int aoff = ((2 * ks + kg) * GM_BM + 64 * wm + 32 * i + l32) * 16;
         const int boff = ((2 * ks + kg) * GM_BM + 64 * wn + 32 * i + l32) * 16;
-        ah[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + aoff));
-        al[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + GM_ARR + aoff));
-        bh[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + 2 * GM_ARR + boff));
-        bl[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(base + 3 * GM_ARR + boff));
+        ah[i] = *reinterpret_cast<const u32x4*>(base + aoff);
+        al[i] = *reinterpret_cast<const u32x4*>(base + GM_ARR + aoff);
+        bh[i] = *reinterpret_cast<const u32x4*>(base + 2 * GM_ARR + boff);
+        bl[i] = *reinterpret_cast<const u32x4*>(base + 3 * GM_ARR + boff);
       }
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-        }
+        for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma_32x32x16_x3(ah[mi], al[mi], bh[ni], bl[ni], acc[mi][ni]);
     }
     if (s + 1 < steps) {
       park(cur ^ 1);                                     // the other buffer: its readers finished before the last barrier
@@ -207,19 +180,6 @@ struct GemmTnParams {
   int M, N, lda, ldb, rows_per_split, relu_b;
 };
 
-__device__ __forceinline__ void tn_split8(const float (&v)[8], bf16x8& h, bf16x8& l) {
-  unsigned hh[4], ll[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hh[i] = gm_cvt_pk_bf16(v[2 * i], v[2 * i + 1]);
-    const float ra = v[2 * i] - __uint_as_float(hh[i] << 16);
-    const float rb = v[2 * i + 1] - __uint_as_float(hh[i] & 0xffff0000u);
-    ll[i] = gm_cvt_pk_bf16(ra, rb);
-  }
-  h = __builtin_bit_cast(bf16x8, u32x4{hh[0], hh[1], hh[2], hh[3]});
-  l = __builtin_bit_cast(bf16x8, u32x4{ll[0], ll[1], ll[2], ll[3]});
-}
-
 __global__ __launch_bounds__(256) void gemm_tn_bf16x3_kernel(const GemmTnParams p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -255,7 +215,7 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16x3_kernel(const GemmTnParams 
   };
   issue(r_begin);
   for (long long r0 = r_begin; r0 < r_end; r0 += 16) {
-    bf16x8 ah[4], al[4], bh[2], bl[2];
+    u32x4 ah[4], al[4], bh[2], bl[2];
     {
       float va[4][8], vb[2][8];
 #pragma unroll
@@ -271,20 +231,16 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16x3_kernel(const GemmTnParams 
       for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) csum[mi] += va[mi][j];
-        tn_split8(va[mi], ah[mi], al[mi]);
+        split8(va[mi], ah[mi], al[mi]);
       }
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni) tn_split8(vb[ni], bh[ni], bl[ni]);
+      for (int ni = 0; ni < 2; ++ni) split8(vb[ni], bh[ni], bl[ni]);
     }
     if (r0 + 16 < r_end) issue(r0 + 16);                // the raw registers are free: next rows in flight under the MFMAs
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
-        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-      }
+      for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma_32x32x16_x3(ah[mi], al[mi], bh[ni], bl[ni], acc[mi][ni]);
   }
 
   // tile (mi, ni), element (i, jn) is C[m_base + 4 i + mi][n_base + 2 jn + ni]; a lane holds jn = l32 and

@@ -62,14 +62,9 @@ __global__ __launch_bounds__(256) void frustum_pe_input_kernel(const FrustumPara
 // Round 6: the kernel was bound by its ARITHMETIC, not by its 568 MB of stores (0.33 ms = 142 M elements x ~90 instructions: an
 // IEEE division and libm's logf per element inside inv_sigmoid).  The projection and the normalisation keep the reference's fp32
 // operation sequence (c, which decides the clamps, is bit-identical); inv_sigmoid of the clamped value is taken on the
-// transcendental unit - log(a / b) = (log2 a - log2 b) ln 2, v_log_f32 at ~1 ulp, |error| <~ 2e-6 on a value of up to 11.5 that
-// enters a 192 -> 1024 -> 256 MLP (the module's 2e-4 / fp64 tests bound the result) - and the 3 D floats of a pixel leave as 16-byte
-// stores (through a 768-byte LDS patch per wave) instead of three 4-byte stores per lane.
-__device__ __forceinline__ float inv_sigmoid_fast(float x) {
-  x = fminf(fmaxf(x, 0.f), 1.f);
-  const float a = fminf(fmaxf(x, 1e-5f), 1.f), b = fminf(fmaxf(1.f - x, 1e-5f), 1.f);
-  return (__builtin_amdgcn_logf(a) - __builtin_amdgcn_logf(b)) * 0.69314718055994530942f;
-}
+// transcendental unit (inv_sigmoid_fast, gd4d_common.h) - log(a / b) = (log2 a - log2 b) ln 2, v_log_f32 at ~1 ulp, |error| <~ 2e-6
+// on a value of up to 11.5 that enters a 192 -> 1024 -> 256 MLP (the module's 2e-4 / fp64 tests bound the result) - and the 3 D
+// floats of a pixel leave as 16-byte stores (through a 768-byte LDS patch per wave) instead of three 4-byte stores per lane.
 
 constexpr int FR_PIX = 1;       // pixels per wave (16 per wave measured 65 against 58 us per launch: the kernel is not bound by the rate waves are launched at)
 

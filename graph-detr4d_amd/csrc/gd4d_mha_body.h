@@ -3,11 +3,10 @@
 // Reference: see gd4d_self_attn.hip.
 #pragma once
 #include "gd4d_common.h"
+#include "gd4d_bf16x3.h"
 #include "gd4d_mha_dropout.h"
 
 namespace gd4d {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 struct MhaParams {
   const float* q; const float* k; const float* v;   // row (l*B + b), row strides ldq/ldk/ldv, head h at +32*h
@@ -46,30 +45,6 @@ constexpr int MHA_PF = MHA_PF_N;       // tiles of keys a wave requests ahead (o
 // C/D layout leaves lane (query qi, g) the scores of keys kbase + 16 t + 4 g + r; numbering the k index of the second product
 // O^T = V^T P^T as 8 g + j <-> (t = j >> 2, r = j & 3) makes those eight probabilities exactly the lane's B operand: they
 // never move between lanes (the trick of the fp32 kernel, for the 32-deep instruction).
-typedef __attribute__((ext_vector_type(8))) __bf16 mha_bf16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned mha_u4;
-
-__device__ __forceinline__ unsigned mha_cvt_pk_bf16(float lo_elem, float hi_elem) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo_elem), "v"(hi_elem));
-  return r;
-}
-__device__ __forceinline__ void mha_split8(const float* v, mha_u4& h, mha_u4& l) {
-  unsigned hh[4], ll[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hh[i] = mha_cvt_pk_bf16(v[2 * i], v[2 * i + 1]);
-    ll[i] = mha_cvt_pk_bf16(v[2 * i] - __uint_as_float(hh[i] << 16), v[2 * i + 1] - __uint_as_float(hh[i] & 0xffff0000u));
-  }
-  h = mha_u4{hh[0], hh[1], hh[2], hh[3]};
-  l = mha_u4{ll[0], ll[1], ll[2], ll[3]};
-}
-__device__ __forceinline__ f32x4 mha_mfma3(mha_u4 ah, mha_u4 al, mha_u4 bh, mha_u4 bl, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mha_bf16x8, al), __builtin_bit_cast(mha_bf16x8, bh), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mha_bf16x8, ah), __builtin_bit_cast(mha_bf16x8, bl), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mha_bf16x8, ah), __builtin_bit_cast(mha_bf16x8, bh), acc, 0, 0, 0);
-  return acc;
-}
 
 // LDS of one workgroup (the kernel's own static arrays, or a piece of the fused launch's dynamic allocation)
 struct MhaShared {
@@ -96,13 +71,13 @@ __device__ __forceinline__ void mha_core_bf16x3_body(const MhaParams& p, const i
   constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
   const float qscale = p.scale * LOG2E;                       // base-2 softmax, as above
 
-  mha_u4 qh, ql;                                              // Q^T as B operand: lane (query qi, g) holds q[qi][8 g .. 8 g + 7]
+  u32x4 qh, ql;                                              // Q^T as B operand: lane (query qi, g) holds q[qi][8 g .. 8 g + 7]
   {
     const int qrow = min(q0 + qi, p.Lq - 1);
     const float* src = p.q + ((size_t)qrow * p.B + b) * p.ldq + h * MHA_D + 8 * g;
     const float4 a = *reinterpret_cast<const float4*>(src), c = *reinterpret_cast<const float4*>(src + 4);
     const float qf[8] = {a.x * qscale, a.y * qscale, a.z * qscale, a.w * qscale, c.x * qscale, c.y * qscale, c.z * qscale, c.w * qscale};
-    mha_split8(qf, qh, ql);
+    split8(qf, qh, ql);
   }
   f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};    // O^T rows d = 4g + r, and 16 + 4g + r
   float m = NEG_INF, l = 0.f;
@@ -119,7 +94,7 @@ __device__ __forceinline__ void mha_core_bf16x3_body(const MhaParams& p, const i
   // requested before this step's are consumed.
   // PRE: K and V arrive as the MFMA operands themselves (bf16 hi / lo planes): 8 loads of 16 / 8 bytes per step instead of 4
   // float4 + 16 dwords, and none of the 112 conversion instructions per step (two thirds of the kernel's splits)
-  struct StepData { float4 ka[2], kc[2]; float v0[8], v1[8], mk[8]; mha_u4 pkh[2], pkl[2], pvh[2], pvl[2]; };
+  struct StepData { float4 ka[2], kc[2]; float v0[8], v1[8], mk[8]; u32x4 pkh[2], pkl[2], pvh[2], pvl[2]; };
   auto fetch = [&](int kt, StepData& d) {
     const int kbase = min(kt, nsteps - 1) * 32;
     if (PRE) {
@@ -127,14 +102,14 @@ __device__ __forceinline__ void mha_core_bf16x3_body(const MhaParams& p, const i
 #pragma unroll
       for (int t = 0; t < 2; ++t) {                          // (a tile past the end: the last one again - its scores are -inf)
         const unsigned short* src = p.ksp + (((size_t)h * tiles + min(kbase / 16 + t, tiles - 1)) * 64 + lane) * 8;
-        d.pkh[t] = *reinterpret_cast<const mha_u4*>(src);
-        d.pkl[t] = *reinterpret_cast<const mha_u4*>(src + p.ks_plane);
+        d.pkh[t] = *reinterpret_cast<const u32x4*>(src);
+        d.pkl[t] = *reinterpret_cast<const u32x4*>(src + p.ks_plane);
       }
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         const unsigned short* src = p.vsp + ((((size_t)h * nsteps + kbase / 32) * 2 + half) * 64 + lane) * 8;
-        d.pvh[half] = *reinterpret_cast<const mha_u4*>(src);
-        d.pvl[half] = *reinterpret_cast<const mha_u4*>(src + p.vs_plane);
+        d.pvh[half] = *reinterpret_cast<const u32x4*>(src);
+        d.pvl[half] = *reinterpret_cast<const u32x4*>(src + p.vs_plane);
       }
       if (MASK) {
 #pragma unroll
@@ -182,10 +157,10 @@ __device__ __forceinline__ void mha_core_bf16x3_body(const MhaParams& p, const i
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const float kf[8] = {ka[t].x, ka[t].y, ka[t].z, ka[t].w, kc[t].x, kc[t].y, kc[t].z, kc[t].w};
-      mha_u4 kh, kl;
+      u32x4 kh, kl;
       if (PRE) { kh = d.pkh[t]; kl = d.pkl[t]; }
-      else mha_split8(kf, kh, kl);
-      const f32x4 st = mha_mfma3(kh, kl, qh, ql, f32x4{0.f, 0.f, 0.f, 0.f});
+      else split8(kf, kh, kl);
+      const f32x4 st = mfma_16x16x32_x3(kh, kl, qh, ql, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
       for (int r = 0; r < 4; ++r) {                            // lane (qi, g) reg r <-> key kbase + 16 t + 4 g + r
         const int key = kbase + 16 * t + 4 * g + r;
@@ -220,14 +195,14 @@ __device__ __forceinline__ void mha_core_bf16x3_body(const MhaParams& p, const i
 #pragma unroll
     for (int r = 0; r < 4; ++r) { o0[r] *= corr; o1[r] *= corr; }
     // ---- O^T += V^T P^T: A = V^T[d = lane & 15 (+ 16)][k = 8 g + j], B = P^T = this lane's own eight probabilities ----
-    mha_u4 ph, pl, vh, vl;
-    mha_split8(pr, ph, pl);
+    u32x4 ph, pl, vh, vl;
+    split8(pr, ph, pl);
     if (PRE) { vh = d.pvh[0]; vl = d.pvl[0]; }
-    else mha_split8(v0, vh, vl);
-    o0 = mha_mfma3(vh, vl, ph, pl, o0);
+    else split8(v0, vh, vl);
+    o0 = mfma_16x16x32_x3(vh, vl, ph, pl, o0);
     if (PRE) { vh = d.pvh[1]; vl = d.pvl[1]; }
-    else mha_split8(v1, vh, vl);
-    o1 = mha_mfma3(vh, vl, ph, pl, o1);
+    else split8(v1, vh, vl);
+    o1 = mfma_16x16x32_x3(vh, vl, ph, pl, o1);
   };
   if (AHEAD > 1) {
     // the fused launch's form (gd4d_row_chain_mha_fwd): ONE workgroup per compute unit there, nobody else's work hides a round

@@ -21,6 +21,7 @@
 // ~300 registers: ONE wave per SIMD (4 waves = 128 rows per workgroup, 512 registers each), the instruction stream itself keeps the
 // matrix pipe busy (phase B: 48 MFMAs against 32 LDS reads).  One barrier per chunk.  114 KB of LDS, one workgroup per compute unit.
 #include "gd4d_common.h"
+#include "gd4d_bf16x3.h"
 
 // Measured and left off (docs/measurements_r05.md section 5; 2.16 ms with neither): the next stage's DMA pieces issued during phase A as
 // well (2.23 - 2.27 ms), two alternating accumulators in phase A (2.23), both (2.31); a branch-free stage (padded piece count) with
@@ -46,10 +47,6 @@
 #endif
 
 namespace gd4d {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 ml_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float ml_f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned ml_u32x4;
 
 constexpr int ML_WAVES = 4, ML_THREADS = 64 * ML_WAVES, ML_BM = 32 * ML_WAVES, ML_HC = 32, ML_N2 = 256, ML_NT = ML_N2 / 32;
 constexpr int ML_S2 = ML_NT * 2 * 2 * 1024;          // bytes of a chunk of W2's image: [tile][step][plane][1 KB]
@@ -100,12 +97,6 @@ struct Mlp2Fr {
   float lo[3], span[3];
 };
 
-__device__ __forceinline__ float ml_inv_sigmoid_fast(float x) {      // gd4d_head_pe.hip's inv_sigmoid_fast
-  x = fminf(fmaxf(x, 0.f), 1.f);
-  const float a = fminf(fmaxf(x, 1e-5f), 1.f), b = fminf(fmaxf(1.f - x, 1e-5f), 1.f);
-  return (__builtin_amdgcn_logf(a) - __builtin_amdgcn_logf(b)) * 0.69314718055994530942f;
-}
-
 __device__ __forceinline__ Mlp2Row ml_row_of(const Mlp2Se& q, int m) {
   const int r = m / q.S;
   const int rem = m - r * q.S;
@@ -113,26 +104,6 @@ __device__ __forceinline__ Mlp2Row ml_row_of(const Mlp2Se& q, int m) {
   const int hw = q.hw[l];
   return Mlp2Row{q.feat[l] + (size_t)r * ML_N2 * hw, q.out[l] + (size_t)r * hw * ML_N2, rem - q.start[l], hw};
 }
-
-__device__ __forceinline__ unsigned ml_cvt_pk_bf16(float lo_elem, float hi_elem) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo_elem), "v"(hi_elem));
-  return r;
-}
-// 8 floats -> 16 bytes of bf16 "hi" halves and 16 bytes of bf16 "lo" (residual) halves
-__device__ __forceinline__ void ml_split8(const float (&v)[8], ml_u32x4& h, ml_u32x4& l) {
-  unsigned hh[4], ll[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hh[i] = ml_cvt_pk_bf16(v[2 * i], v[2 * i + 1]);
-    const float ra = v[2 * i] - __uint_as_float(hh[i] << 16);              // exact: hi is a rounding of the value
-    const float rb = v[2 * i + 1] - __uint_as_float(hh[i] & 0xffff0000u);
-    ll[i] = ml_cvt_pk_bf16(ra, rb);
-  }
-  h = ml_u32x4{hh[0], hh[1], hh[2], hh[3]};
-  l = ml_u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
-__device__ __forceinline__ ml_bf16x8 ml_frag(const ml_u32x4& v) { return __builtin_bit_cast(ml_bf16x8, v); }
 
 // hidden unit (inside its chunk of 32) that accumulator register r of a lane with k-group kg holds after phase A: the C / D row
 // of v_mfma_f32_32x32x16 - and, read as r = 8 s + e, the k-slot e of phase B's step s
@@ -199,7 +170,7 @@ __global__ __launch_bounds__(ML_THREADS, 1) void mlp2_kernel(const Mlp2Params p,
           const float v = ((mm[4 * k] * px + mm[4 * k + 1] * py) + mm[4 * k + 2] * depth) + mm[4 * k + 3];   // :469
           const float c = (v - fr.lo[k]) / fr.span[k];                               // :470-475
           const int j = 3 * dd + k;
-          xr[j >> 3][j & 7] = ml_inv_sigmoid_fast(c);                               // :480-481
+          xr[j >> 3][j & 7] = inv_sigmoid_fast(c);                                  // :480-481
         }
       }
     } else if (SE) {
@@ -224,14 +195,14 @@ __global__ __launch_bounds__(ML_THREADS, 1) void mlp2_kernel(const Mlp2Params p,
 
   for (;;) {
   const int m0 = tile * ML_BM + wave * 32;
-  ml_u32x4 xh[STEPS1], xl[STEPS1];
+  u32x4 xh[STEPS1], xl[STEPS1];
 #pragma unroll
-  for (int st = 0; st < STEPS1; ++st) ml_split8(xr[st], xh[st], xl[st]);
+  for (int st = 0; st < STEPS1; ++st) split8(xr[st], xh[st], xl[st]);
   const int next_tile = tile + (int)gridDim.x;
   const bool last_tile = next_tile >= ntiles;
   if (!last_tile) load_x(next_tile);
 
-  ml_f32x16 acc[ML_NT];
+  f32x16 acc[ML_NT];
 #pragma unroll
   for (int t = 0; t < ML_NT; ++t)
 #pragma unroll
@@ -251,30 +222,26 @@ __global__ __launch_bounds__(ML_THREADS, 1) void mlp2_kernel(const Mlp2Params p,
     // ---- phase A: H^T = W1c X^T (A operand = W1 fragment, B operand = X fragment) ----
     // Two accumulators, even and odd steps: an MFMA that follows a gap in the instruction stream (the LDS requests, a DMA piece)
     // then depends on a result two steps old, not on the one just issued (a dependent MFMA behind a gap waits out the full latency).
-    ml_f32x16 h, h_odd;
+    f32x16 h, h_odd;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { h[r] = 0.f; h_odd[r] = 0.f; }
     // (one wave per SIMD: nobody else hides an LDS round trip, so a step's fragments are requested a step ahead and the matrix
     //  pipe works on step st while they travel; the next chunk's stage goes out a piece per step - the other buffer is free
     //  since the barrier above)
     const char* f1 = s1 + lane * 16;
-    ml_u32x4 wh = *reinterpret_cast<const ml_u32x4*>(f1), wl = *reinterpret_cast<const ml_u32x4*>(f1 + 1024);
+    u32x4 wh = *reinterpret_cast<const u32x4*>(f1), wl = *reinterpret_cast<const u32x4*>(f1 + 1024);
 #pragma unroll
     for (int st = 0; st < STEPS1; ++st) {
-      ml_u32x4 nh = wh, nl = wl;
+      u32x4 nh = wh, nl = wl;
       if (st + 1 < STEPS1) {
-        nh = *reinterpret_cast<const ml_u32x4*>(f1 + (st + 1) * 2048);
-        nl = *reinterpret_cast<const ml_u32x4*>(f1 + (st + 1) * 2048 + 1024);
+        nh = *reinterpret_cast<const u32x4*>(f1 + (st + 1) * 2048);
+        nl = *reinterpret_cast<const u32x4*>(f1 + (st + 1) * 2048 + 1024);
       }
       if (ML_DMA_IN_A && more && st < PER_WAVE) stage_piece(cn, (cc + 1) & 1, st);
       if (ML_TWO_ACC && (st & 1)) {
-        h_odd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(wl), ml_frag(xh[st]), h_odd, 0, 0, 0);
-        h_odd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(wh), ml_frag(xl[st]), h_odd, 0, 0, 0);
-        h_odd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(wh), ml_frag(xh[st]), h_odd, 0, 0, 0);
+        h_odd = mfma_32x32x16_x3(wh, wl, xh[st], xl[st], h_odd);
       } else {
-        h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(wl), ml_frag(xh[st]), h, 0, 0, 0);
-        h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(wh), ml_frag(xl[st]), h, 0, 0, 0);
-        h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(wh), ml_frag(xh[st]), h, 0, 0, 0);
+        h = mfma_32x32x16_x3(wh, wl, xh[st], xl[st], h);
       }
       __builtin_amdgcn_sched_barrier(0);               // (keep the requests in front of the MFMAs they travel under)
       wh = nh; wl = nl;
@@ -285,7 +252,7 @@ __global__ __launch_bounds__(ML_THREADS, 1) void mlp2_kernel(const Mlp2Params p,
     }
     // bias, ReLU, hi / lo split: registers 8 s .. 8 s + 7 are the A operand of phase B's step s; b1's entries of registers
     // 4 j .. 4 j + 3 are the consecutive hidden units 4 kg + 8 j + (0 .. 3)
-    ml_u32x4 ah[2], al[2];
+    u32x4 ah[2], al[2];
     {
       const float* b1c = reinterpret_cast<const float*>(s1 + STEPS1 * 2048);
       float4 bq[4];
@@ -297,7 +264,7 @@ __global__ __launch_bounds__(ML_THREADS, 1) void mlp2_kernel(const Mlp2Params p,
         const float v[8] = {fmaxf(h[8 * s] + ba.x, 0.f), fmaxf(h[8 * s + 1] + ba.y, 0.f), fmaxf(h[8 * s + 2] + ba.z, 0.f),
                             fmaxf(h[8 * s + 3] + ba.w, 0.f), fmaxf(h[8 * s + 4] + bb.x, 0.f), fmaxf(h[8 * s + 5] + bb.y, 0.f),
                             fmaxf(h[8 * s + 6] + bb.z, 0.f), fmaxf(h[8 * s + 7] + bb.w, 0.f)};
-        ml_split8(v, ah[s], al[s]);
+        split8(v, ah[s], al[s]);
       }
     }
     // ---- phase B: out += H W2c^T (step-major: the first step's MFMAs run while the second step's operand is still being split) ----
@@ -307,19 +274,17 @@ __global__ __launch_bounds__(ML_THREADS, 1) void mlp2_kernel(const Mlp2Params p,
     }
     constexpr int GROUPS = 2 * ML_NT;
     const char* f2 = s2 + lane * 16;
-    ml_u32x4 vh = *reinterpret_cast<const ml_u32x4*>(f2), vl = *reinterpret_cast<const ml_u32x4*>(f2 + 1024);
+    u32x4 vh = *reinterpret_cast<const u32x4*>(f2), vl = *reinterpret_cast<const u32x4*>(f2 + 1024);
 #pragma unroll
     for (int grp = 0; grp < GROUPS; ++grp) {
       const int s = grp / ML_NT, t = grp % ML_NT;
-      ml_u32x4 nh = vh, nl = vl;
+      u32x4 nh = vh, nl = vl;
       if (grp + 1 < GROUPS) {                          // the next group's fragments: [tile][step][plane]
         const int s_n = (grp + 1) / ML_NT, t_n = (grp + 1) % ML_NT;
-        nh = *reinterpret_cast<const ml_u32x4*>(f2 + ((t_n * 2 + s_n) * 2) * 1024);
-        nl = *reinterpret_cast<const ml_u32x4*>(f2 + ((t_n * 2 + s_n) * 2) * 1024 + 1024);
+        nh = *reinterpret_cast<const u32x4*>(f2 + ((t_n * 2 + s_n) * 2) * 1024);
+        nl = *reinterpret_cast<const u32x4*>(f2 + ((t_n * 2 + s_n) * 2) * 1024 + 1024);
       }
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(al[s]), ml_frag(vh), acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(ah[s]), ml_frag(vl), acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(ah[s]), ml_frag(vh), acc[t], 0, 0, 0);
+      acc[t] = mfma_32x32x16_x3(ah[s], al[s], vh, vl, acc[t]);
       // the next chunk's stage, a piece per MFMA group (the other buffer: nobody reads it until the next barrier)
       if (more && (ML_DMA_IN_A ? STEPS1 : 0) + grp < PER_WAVE) stage_piece(cn, (cc + 1) & 1, (ML_DMA_IN_A ? STEPS1 : 0) + grp);
       __builtin_amdgcn_sched_barrier(0);
@@ -414,7 +379,7 @@ __global__ __launch_bounds__(ML_THREADS, 1) void mlp2_kernel(const Mlp2Params p,
 // A phase = one MLP's walk over its hidden chunks (mlp2_kernel's chunk body, one tile per workgroup, no ring across tiles).
 template <int STEPS1>
 __device__ __forceinline__ void ml_phase(const char* __restrict__ w1img, const char* __restrict__ w2img, const int nchunks, char* smem,
-                                         const ml_u32x4 (&xh)[STEPS1], const ml_u32x4 (&xl)[STEPS1], ml_f32x16 (&acc)[ML_NT],
+                                         const u32x4 (&xh)[STEPS1], const u32x4 (&xl)[STEPS1], f32x16 (&acc)[ML_NT],
                                          const int wave, const int lane) {
   typedef __attribute__((address_space(3))) void lds_void_t;
   typedef const __attribute__((address_space(1))) void glb_void_t;
@@ -438,25 +403,23 @@ __device__ __forceinline__ void ml_phase(const char* __restrict__ w1img, const c
     const bool more = c + 1 < nchunks;
     const char* s1 = smem + (c & 1) * STAGE;
     const char* s2 = s1 + S1;
-    ml_f32x16 h;
+    f32x16 h;
 #pragma unroll
     for (int r = 0; r < 16; ++r) h[r] = 0.f;
     const char* f1 = s1 + lane * 16;
-    ml_u32x4 wh = *reinterpret_cast<const ml_u32x4*>(f1), wl = *reinterpret_cast<const ml_u32x4*>(f1 + 1024);
+    u32x4 wh = *reinterpret_cast<const u32x4*>(f1), wl = *reinterpret_cast<const u32x4*>(f1 + 1024);
 #pragma unroll
     for (int st = 0; st < STEPS1; ++st) {
-      ml_u32x4 nh = wh, nl = wl;
+      u32x4 nh = wh, nl = wl;
       if (st + 1 < STEPS1) {
-        nh = *reinterpret_cast<const ml_u32x4*>(f1 + (st + 1) * 2048);
-        nl = *reinterpret_cast<const ml_u32x4*>(f1 + (st + 1) * 2048 + 1024);
+        nh = *reinterpret_cast<const u32x4*>(f1 + (st + 1) * 2048);
+        nl = *reinterpret_cast<const u32x4*>(f1 + (st + 1) * 2048 + 1024);
       }
-      h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(wl), ml_frag(xh[st]), h, 0, 0, 0);
-      h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(wh), ml_frag(xl[st]), h, 0, 0, 0);
-      h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(wh), ml_frag(xh[st]), h, 0, 0, 0);
+      h = mfma_32x32x16_x3(wh, wl, xh[st], xl[st], h);
       __builtin_amdgcn_sched_barrier(0);
       wh = nh; wl = nl;
     }
-    ml_u32x4 ah[2], al[2];
+    u32x4 ah[2], al[2];
     {
       const float* b1c = reinterpret_cast<const float*>(s1 + STEPS1 * 2048);
       float4 bq[4];
@@ -468,7 +431,7 @@ __device__ __forceinline__ void ml_phase(const char* __restrict__ w1img, const c
         const float v[8] = {fmaxf(h[8 * s] + ba.x, 0.f), fmaxf(h[8 * s + 1] + ba.y, 0.f), fmaxf(h[8 * s + 2] + ba.z, 0.f),
                             fmaxf(h[8 * s + 3] + ba.w, 0.f), fmaxf(h[8 * s + 4] + bb.x, 0.f), fmaxf(h[8 * s + 5] + bb.y, 0.f),
                             fmaxf(h[8 * s + 6] + bb.z, 0.f), fmaxf(h[8 * s + 7] + bb.w, 0.f)};
-        ml_split8(v, ah[s], al[s]);
+        split8(v, ah[s], al[s]);
       }
     }
     if (ML_SPLIT_WAIT) {
@@ -479,22 +442,20 @@ __device__ __forceinline__ void ml_phase(const char* __restrict__ w1img, const c
     const char* f2 = s2 + lane * 16;
     // group g's fragments: [tile][step][plane]; requested ML_AHEAD groups before their MFMAs
     auto frag_at = [&](int g) -> const char* { return f2 + (((g % ML_NT) * 2 + g / ML_NT) * 2) * 1024; };
-    ml_u32x4 qh[ML_AHEAD + 1], ql[ML_AHEAD + 1];
+    u32x4 qh[ML_AHEAD + 1], ql[ML_AHEAD + 1];
 #pragma unroll
     for (int a = 0; a < ML_AHEAD; ++a) {
-      qh[a] = *reinterpret_cast<const ml_u32x4*>(frag_at(a));
-      ql[a] = *reinterpret_cast<const ml_u32x4*>(frag_at(a) + 1024);
+      qh[a] = *reinterpret_cast<const u32x4*>(frag_at(a));
+      ql[a] = *reinterpret_cast<const u32x4*>(frag_at(a) + 1024);
     }
 #pragma unroll
     for (int grp = 0; grp < GROUPS; ++grp) {
       const int s = grp / ML_NT, t = grp % ML_NT;
       if (grp + ML_AHEAD < GROUPS) {
-        qh[ML_AHEAD] = *reinterpret_cast<const ml_u32x4*>(frag_at(grp + ML_AHEAD));
-        ql[ML_AHEAD] = *reinterpret_cast<const ml_u32x4*>(frag_at(grp + ML_AHEAD) + 1024);
+        qh[ML_AHEAD] = *reinterpret_cast<const u32x4*>(frag_at(grp + ML_AHEAD));
+        ql[ML_AHEAD] = *reinterpret_cast<const u32x4*>(frag_at(grp + ML_AHEAD) + 1024);
       }
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(al[s]), ml_frag(qh[0]), acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(ah[s]), ml_frag(ql[0]), acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml_frag(ah[s]), ml_frag(qh[0]), acc[t], 0, 0, 0);
+      acc[t] = mfma_32x32x16_x3(ah[s], al[s], qh[0], ql[0], acc[t]);
       if (more && grp < PER_WAVE) stage_piece(c + 1, (c + 1) & 1, grp);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -520,13 +481,13 @@ __global__ __launch_bounds__(ML_THREADS, 1) void mlp2_pe_se_kernel(const Mlp2PeS
   const int m0 = blockIdx.x * ML_BM + wave * 32;
   const int m = min(m0 + l32, p.M - 1);
   // ---- position_encoder(frustum): the inputs generated (mlp2_kernel's frustum form) ----
-  ml_f32x16 pe[ML_NT];
+  f32x16 pe[ML_NT];
 #pragma unroll
   for (int t = 0; t < ML_NT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) pe[t][r] = 0.f;
   {
-    ml_u32x4 fh[12], fl[12];
+    u32x4 fh[12], fl[12];
     {
       const int r = m / fr.S;
       const int rem = m - r * fr.S;
@@ -553,11 +514,11 @@ __global__ __launch_bounds__(ML_THREADS, 1) void mlp2_pe_se_kernel(const Mlp2PeS
           const float v = ((mm[4 * k] * px + mm[4 * k + 1] * py) + mm[4 * k + 2] * depth) + mm[4 * k + 3];
           const float c = (v - fr.lo[k]) / fr.span[k];
           const int j = 3 * dd + k;
-          xf[j >> 3][j & 7] = ml_inv_sigmoid_fast(c);
+          xf[j >> 3][j & 7] = inv_sigmoid_fast(c);
         }
       }
 #pragma unroll
-      for (int st = 0; st < 12; ++st) ml_split8(xf[st], fh[st], fl[st]);
+      for (int st = 0; st < 12; ++st) split8(xf[st], fh[st], fl[st]);
     }
     ml_phase<12>(p.pe_w1, p.pe_w2, p.pe_h / ML_HC, ml_smem, fh, fl, pe, wave, lane);
   }
@@ -577,7 +538,7 @@ __global__ __launch_bounds__(ML_THREADS, 1) void mlp2_pe_se_kernel(const Mlp2PeS
       }
   }
   // ---- the gate ----
-  ml_f32x16 acc[ML_NT];
+  f32x16 acc[ML_NT];
 #pragma unroll
   for (int t = 0; t < ML_NT; ++t)
 #pragma unroll
@@ -592,9 +553,9 @@ __global__ __launch_bounds__(ML_THREADS, 1) void mlp2_pe_se_kernel(const Mlp2PeS
 #pragma unroll
         for (int e = 0; e < 8; ++e) xr[st][e] = xc[(size_t)(16 * st + e) * g.hw];
     }
-    ml_u32x4 xh[16], xl[16];
+    u32x4 xh[16], xl[16];
 #pragma unroll
-    for (int st = 0; st < 16; ++st) ml_split8(xr[st], xh[st], xl[st]);
+    for (int st = 0; st < 16; ++st) split8(xr[st], xh[st], xl[st]);
     ml_phase<16>(p.se_w1, p.se_w2, p.se_h / ML_HC, ml_smem, xh, xl, acc, wave, lane);
   }
   // ---- out = feat + (pe * sigmoid(gate) + sine): mlp2_kernel's SE epilogue with pe in registers ----
@@ -681,10 +642,10 @@ __global__ __launch_bounds__(256) void mlp2_image_kernel(const float* __restrict
   } else {
     return;
   }
-  ml_u32x4 h, l;
-  ml_split8(v, h, l);
-  *reinterpret_cast<ml_u32x4*>(dst) = h;
-  *reinterpret_cast<ml_u32x4*>(dst + 1024) = l;
+  u32x4 h, l;
+  split8(v, h, l);
+  *reinterpret_cast<u32x4*>(dst) = h;
+  *reinterpret_cast<u32x4*>(dst + 1024) = l;
 }
 
 // One workgroup per tile.  (The kernel walks tiles blockIdx, blockIdx + grid, .. with the next tile's rows requested a tile ahead and the

@@ -21,13 +21,12 @@
 #include <stdlib.h>
 
 #include "gd4d_common.h"
+#include "gd4d_bf16x3.h"
 #include "gd4d_pyramid_fill.h"
 #include "gd4d_mha_dropout.h"
 #include "gd4d_value_proj_body.h"
 
 namespace gd4d {
-
-typedef __attribute__((ext_vector_type(4))) float rc4;
 
 GD4D_TRACE_UNIT(rowchain)
 
@@ -90,41 +89,6 @@ __device__ __forceinline__ float rc_act_in(float v, int flags) { return (flags &
 #ifndef RC_DBG
 #define RC_DBG 0      // dev ablation (compile with -DRC_DBG=n): 1 = no MFMAs, 2 = no weight loads
 #endif
-typedef __attribute__((ext_vector_type(8))) __bf16 rc_bf16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned rc_u4;
-
-__device__ __forceinline__ unsigned rc_cvt_pk_bf16(float lo_elem, float hi_elem) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo_elem), "v"(hi_elem));
-  return r;
-}
-// 8 consecutive floats -> bf16 hi halves and bf16 lo halves (x ~= hi + lo)
-__device__ __forceinline__ void rc_split8(const float* v, rc_u4& h, rc_u4& l) {
-  unsigned hh[4], ll[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hh[i] = rc_cvt_pk_bf16(v[2 * i], v[2 * i + 1]);
-    ll[i] = rc_cvt_pk_bf16(v[2 * i] - __uint_as_float(hh[i] << 16), v[2 * i + 1] - __uint_as_float(hh[i] & 0xffff0000u));
-  }
-  h = rc_u4{hh[0], hh[1], hh[2], hh[3]};
-  l = rc_u4{ll[0], ll[1], ll[2], ll[3]};
-}
-// 8 consecutive floats -> three bf16 pieces (x = hi + mid + lo to ~2^-25: GD4D_CHAIN_EXACT)
-__device__ __forceinline__ void rc_split8x3(const float* v, rc_u4& h, rc_u4& m, rc_u4& l) {
-  unsigned hh[4], mm[4], ll[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hh[i] = rc_cvt_pk_bf16(v[2 * i], v[2 * i + 1]);
-    const float r0 = v[2 * i] - __uint_as_float(hh[i] << 16), r1 = v[2 * i + 1] - __uint_as_float(hh[i] & 0xffff0000u);
-    mm[i] = rc_cvt_pk_bf16(r0, r1);
-    ll[i] = rc_cvt_pk_bf16(r0 - __uint_as_float(mm[i] << 16), r1 - __uint_as_float(mm[i] & 0xffff0000u));
-  }
-  h = rc_u4{hh[0], hh[1], hh[2], hh[3]};
-  m = rc_u4{mm[0], mm[1], mm[2], mm[3]};
-  l = rc_u4{ll[0], ll[1], ll[2], ll[3]};
-}
-__device__ __forceinline__ rc_bf16x8 rc_frag(rc_u4 v) { return __builtin_bit_cast(rc_bf16x8, v); }
-
 // Weight image (gd4d_chain_weight_image): [tile t of 16 output columns][k-step s of 32][hi, lo][lane][8 bf16]; lane l of
 // a fragment holds W[n = 16 t + (l & 15)][k = 32 s + {4 g .. 4 g + 3, 16 + 4 g .. 16 + 4 g + 3}], g = l >> 4 (RC_KPERM above) - the
 // B operand of v_mfma_f32_16x16x32_bf16.
@@ -142,16 +106,16 @@ __global__ __launch_bounds__(256) void chain_weight_image_kernel(const float* __
   for (int j = 0; j < 8; ++j) v[j] = n < N ? w[(size_t)n * K + 32 * s + RC_KG * (lane >> 4) + (j < 4 ? j : RC_K2 + j - 4)] : 0.f;
   char* dst = img + (size_t)frag * (PLANES * 1024) + lane * 16;
   if (PLANES == 3) {
-    rc_u4 h, m, l;
-    rc_split8x3(v, h, m, l);
-    *reinterpret_cast<rc_u4*>(dst) = h;
-    *reinterpret_cast<rc_u4*>(dst + 1024) = m;
-    *reinterpret_cast<rc_u4*>(dst + 2048) = l;
+    u32x4 h, m, l;
+    split8x3(v, h, m, l);
+    *reinterpret_cast<u32x4*>(dst) = h;
+    *reinterpret_cast<u32x4*>(dst + 1024) = m;
+    *reinterpret_cast<u32x4*>(dst + 2048) = l;
   } else {
-    rc_u4 h, l;
-    rc_split8(v, h, l);
-    *reinterpret_cast<rc_u4*>(dst) = h;
-    *reinterpret_cast<rc_u4*>(dst + 1024) = l;
+    u32x4 h, l;
+    split8(v, h, l);
+    *reinterpret_cast<u32x4*>(dst) = h;
+    *reinterpret_cast<u32x4*>(dst + 1024) = l;
   }
 }
 
@@ -214,16 +178,16 @@ __global__ __launch_bounds__(256) void chain_weight_image_group_kernel(const gd4
   }
   char* dst = static_cast<char*>(J.image) + (size_t)f * (J.planes * 1024) + lane * 16;
   if (J.planes == 3) {
-    rc_u4 h, m, l;
-    rc_split8x3(v, h, m, l);
-    *reinterpret_cast<rc_u4*>(dst) = h;
-    *reinterpret_cast<rc_u4*>(dst + 1024) = m;
-    *reinterpret_cast<rc_u4*>(dst + 2048) = l;
+    u32x4 h, m, l;
+    split8x3(v, h, m, l);
+    *reinterpret_cast<u32x4*>(dst) = h;
+    *reinterpret_cast<u32x4*>(dst + 1024) = m;
+    *reinterpret_cast<u32x4*>(dst + 2048) = l;
   } else {
-    rc_u4 h, l;
-    rc_split8(v, h, l);
-    *reinterpret_cast<rc_u4*>(dst) = h;
-    *reinterpret_cast<rc_u4*>(dst + 1024) = l;
+    u32x4 h, l;
+    split8(v, h, l);
+    *reinterpret_cast<u32x4*>(dst) = h;
+    *reinterpret_cast<u32x4*>(dst + 1024) = l;
   }
 }
 
@@ -265,9 +229,9 @@ __device__ __forceinline__ void rc_gemm(const ChainOp& op, float (*bufs)[RC_M][R
     const char* wf[RC_TILES];                                  // tiles past the end re-read the last one (never stored)
 #pragma unroll
     for (int c = 0; c < RC_TILES; ++c) wf[c] = img + (size_t)min(n_base / 16 + c, tiles - 1) * steps * FRAG + lane * 16;
-    rc4 acc[RC_TILES];
+    f32x4 acc[RC_TILES];
 #pragma unroll
-    for (int c = 0; c < RC_TILES; ++c) acc[c] = rc4{0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < RC_TILES; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
     // bias: unconditional loads from clamped addresses, issued before the K loop (a load under a predicate becomes its
     // own basic block closed by s_waitcnt vmcnt(0): a dozen serialised L2 round trips in the epilogue otherwise)
     float e_bias[RC_TILES];
@@ -292,21 +256,21 @@ __device__ __forceinline__ void rc_gemm(const ChainOp& op, float (*bufs)[RC_M][R
         }
       }
     }
-    rc_u4 bh[RC_DEPTH][RC_TILES], bl[RC_DEPTH][RC_TILES], bm[EXACT ? RC_DEPTH : 1][RC_TILES];
+    u32x4 bh[RC_DEPTH][RC_TILES], bl[RC_DEPTH][RC_TILES], bm[EXACT ? RC_DEPTH : 1][RC_TILES];
     auto issue = [&](int slot, int j) {
       if (RC_DBG & 2) return;
 #pragma unroll
       for (int c = 0; c < RC_TILES; ++c) {
-        bh[slot][c] = *reinterpret_cast<const rc_u4*>(wf[c] + (size_t)j * FRAG);
-        if (EXACT) bm[slot][c] = *reinterpret_cast<const rc_u4*>(wf[c] + (size_t)j * FRAG + 1024);
-        bl[slot][c] = *reinterpret_cast<const rc_u4*>(wf[c] + (size_t)j * FRAG + (EXACT ? 2048 : 1024));
+        bh[slot][c] = *reinterpret_cast<const u32x4*>(wf[c] + (size_t)j * FRAG);
+        if (EXACT) bm[slot][c] = *reinterpret_cast<const u32x4*>(wf[c] + (size_t)j * FRAG + 1024);
+        bl[slot][c] = *reinterpret_cast<const u32x4*>(wf[c] + (size_t)j * FRAG + (EXACT ? 2048 : 1024));
       }
     };
     if (RC_DBG & 2) {
 #pragma unroll
       for (int d = 0; d < RC_DEPTH; ++d)
 #pragma unroll
-        for (int c = 0; c < RC_TILES; ++c) { bh[d][c] = rc_u4{1u, 2u, 3u, (unsigned)lane}; bl[d][c] = bh[d][c]; if (EXACT) bm[d][c] = bh[d][c]; }
+        for (int c = 0; c < RC_TILES; ++c) { bh[d][c] = u32x4{1u, 2u, 3u, (unsigned)lane}; bl[d][c] = bh[d][c]; if (EXACT) bm[d][c] = bh[d][c]; }
     }
     // The workgroups of a launch run in lock step and stream the SAME weight image: un-rotated, the ~7 workgroups that
     // share an XCD ask one L2 channel for one fragment at the same instant and take turns (17 B/clk per CU measured).
@@ -322,27 +286,27 @@ __device__ __forceinline__ void rc_gemm(const ChainOp& op, float (*bufs)[RC_M][R
       const float4 t1 = *reinterpret_cast<const float4*>(a_row + 32 * j + RC_K2);
       const float a[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
       if (EXACT) {
-        rc_u4 ah, am, al;
-        rc_split8x3(a, ah, am, al);
+        u32x4 ah, am, al;
+        split8x3(a, ah, am, al);
 #pragma unroll
-        for (int c = 0; c < RC_TILES; ++c) {                   // smallest terms first
-          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(al), rc_frag(bh[d][c]), acc[c], 0, 0, 0);
-          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(ah), rc_frag(bl[d][c]), acc[c], 0, 0, 0);
-          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(am), rc_frag(bm[d][c]), acc[c], 0, 0, 0);
-          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(am), rc_frag(bh[d][c]), acc[c], 0, 0, 0);
-          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(ah), rc_frag(bm[d][c]), acc[c], 0, 0, 0);
-          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(ah), rc_frag(bh[d][c]), acc[c], 0, 0, 0);
+        for (int c = 0; c < RC_TILES; ++c) {                   // smallest terms first (a deliberate order: it is the fp32 sum)
+          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(al), frag(bh[d][c]), acc[c], 0, 0, 0);
+          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bl[d][c]), acc[c], 0, 0, 0);
+          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(am), frag(bm[d][c]), acc[c], 0, 0, 0);
+          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(am), frag(bh[d][c]), acc[c], 0, 0, 0);
+          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bm[d][c]), acc[c], 0, 0, 0);
+          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bh[d][c]), acc[c], 0, 0, 0);
         }
         return;
       }
-      rc_u4 ah, al;
-      rc_split8(a, ah, al);
+      u32x4 ah, al;
+      split8(a, ah, al);
       if (RC_DBG & 1) { asm volatile("" ::"v"(ah), "v"(al), "v"(bh[d][0]), "v"(bl[d][3])); return; }
 #pragma unroll
-      for (int c = 0; c < RC_TILES; ++c) {
-        acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(ah), rc_frag(bh[d][c]), acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(al), rc_frag(bh[d][c]), acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(ah), rc_frag(bl[d][c]), acc[c], 0, 0, 0);
+      for (int c = 0; c < RC_TILES; ++c) {                     // hi hi first: not mfma_16x16x32_x3's order, on purpose (the fp32 sum)
+        acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bh[d][c]), acc[c], 0, 0, 0);
+        acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(al), frag(bh[d][c]), acc[c], 0, 0, 0);
+        acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bl[d][c]), acc[c], 0, 0, 0);
       }
     };
     // host guarantees steps % RC_DEPTH == 0 (K % (32 RC_DEPTH) == 0)
@@ -386,9 +350,9 @@ __device__ __forceinline__ void rc_gemm(const ChainOp& op, float (*bufs)[RC_M][R
         }
       }
       if (split_kv && n_base >= RC_COLS * RC_WAVES) {          // (pass-uniform: pass 1 = K, pass 2 = V)
-        const unsigned h01 = rc_cvt_pk_bf16(kv[0], kv[1]), h23 = rc_cvt_pk_bf16(kv[2], kv[3]);
-        const unsigned l01 = rc_cvt_pk_bf16(kv[0] - __uint_as_float(h01 << 16), kv[1] - __uint_as_float(h01 & 0xffff0000u));
-        const unsigned l23 = rc_cvt_pk_bf16(kv[2] - __uint_as_float(h23 << 16), kv[3] - __uint_as_float(h23 & 0xffff0000u));
+        const unsigned h01 = cvt_pk_bf16(kv[0], kv[1]), h23 = cvt_pk_bf16(kv[2], kv[3]);
+        const unsigned l01 = cvt_pk_bf16(kv[0] - __uint_as_float(h01 << 16), kv[1] - __uint_as_float(h01 & 0xffff0000u));
+        const unsigned l23 = cvt_pk_bf16(kv[2] - __uint_as_float(h23 << 16), kv[3] - __uint_as_float(h23 & 0xffff0000u));
         constexpr int C3 = RC_COLS * RC_WAVES;                 // = N / 3
         const int blk = m0 / RC_M, blocks = (M + RC_M - 1) / RC_M;
         if (n_base < 2 * C3) {
@@ -447,9 +411,9 @@ __device__ __forceinline__ void rc_headgemm(const ChainOp& op, float (*bufs)[RC_
       hg[gi] = min((n_base + 16 * TPG * gi) / Dh, heads - 1);
       ag[gi] = op.p2 + ((size_t)m_ld * heads + hg[gi]) * K + RC_KG * g;
     }
-    rc4 acc[RC_TILES];
+    f32x4 acc[RC_TILES];
 #pragma unroll
-    for (int c = 0; c < RC_TILES; ++c) acc[c] = rc4{0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < RC_TILES; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
     float e_bias[RC_TILES];
     {
       const float* bias_p = op.p1 ? op.p1 : reinterpret_cast<const float*>(op.p0);
@@ -469,13 +433,13 @@ __device__ __forceinline__ void rc_headgemm(const ChainOp& op, float (*bufs)[RC_
     // (Round 6, measured and not kept: ALL k-steps' aggregate rows requested at once - 64 registers - instead of this two-deep
     //  ring: chain B' 55.7 against 55.7 us.  HEADGEMM's 18 us in block 0's timeline are the launch (~5 us until a first operation
     //  completes in any chain) and the program's weight touches, which its first loads queue behind: not its own ring.)
-    rc_u4 bh[HD][RC_TILES], bl[HD][RC_TILES];
+    u32x4 bh[HD][RC_TILES], bl[HD][RC_TILES];
     float4 av[HD][NG][2];
     auto issue = [&](int slot, int j) {
 #pragma unroll
       for (int c = 0; c < RC_TILES; ++c) {
-        bh[slot][c] = *reinterpret_cast<const rc_u4*>(wf[c] + (size_t)j * 2048);
-        bl[slot][c] = *reinterpret_cast<const rc_u4*>(wf[c] + (size_t)j * 2048 + 1024);
+        bh[slot][c] = *reinterpret_cast<const u32x4*>(wf[c] + (size_t)j * 2048);
+        bl[slot][c] = *reinterpret_cast<const u32x4*>(wf[c] + (size_t)j * 2048 + 1024);
       }
 #pragma unroll
       for (int gi = 0; gi < NG; ++gi) {
@@ -488,13 +452,13 @@ __device__ __forceinline__ void rc_headgemm(const ChainOp& op, float (*bufs)[RC_
       for (int hh = 0; hh < NG; ++hh) {
         const float a[8] = {av[d][hh][0].x, av[d][hh][0].y, av[d][hh][0].z, av[d][hh][0].w,
                             av[d][hh][1].x, av[d][hh][1].y, av[d][hh][1].z, av[d][hh][1].w};
-        rc_u4 ah, al;
-        rc_split8(a, ah, al);
+        u32x4 ah, al;
+        split8(a, ah, al);
 #pragma unroll
-        for (int c = TPG * hh; c < TPG * hh + TPG; ++c) {
-          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(ah), rc_frag(bh[d][c]), acc[c], 0, 0, 0);
-          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(al), rc_frag(bh[d][c]), acc[c], 0, 0, 0);
-          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rc_frag(ah), rc_frag(bl[d][c]), acc[c], 0, 0, 0);
+        for (int c = TPG * hh; c < TPG * hh + TPG; ++c) {      // hi hi first: not mfma_16x16x32_x3's order, on purpose
+          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bh[d][c]), acc[c], 0, 0, 0);
+          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(al), frag(bh[d][c]), acc[c], 0, 0, 0);
+          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bl[d][c]), acc[c], 0, 0, 0);
         }
       }
     };

@@ -5,12 +5,11 @@
 // are hand-written so that a training step's kernel table is gd4d:: only (plus optimizer and collectives).
 // Everything fp32; reductions in a fixed order (run-to-run identical results).
 #include "gd4d_common.h"
+#include "gd4d_bf16x3.h"
 #include "gd4d_mha_dropout.h"
 #include "gd4d_pyramid_fill.h"
 
 namespace gd4d {
-
-typedef __attribute__((ext_vector_type(4))) float t4;
 
 // ---------------------------------------------------------------------------------------------------------------
 // LayerNorm backward.  y = [ReLU] LN(x [+ res]) * gamma + beta  (gd4d_layernorm_fwd); given dy:
@@ -217,8 +216,8 @@ constexpr int TB_D = 32, TB_WAVES = TB_WAVES_N;
 // A 16 x 16 score-like tile, transposed: T^T[row][col] = sum_d R[row][d] C[col][d], rows permuted so that lane
 // (col = lane & 15, g = lane >> 4) register r holds row g + 4 r.  rowv = the row operand's 8 values of this lane (row
 // rho = (lane & 15 >> 2) + 4 (lane & 3), dims 8 g ..), colv = the column operand's 8 values (col lane & 15, dims 8 g ..).
-__device__ __forceinline__ t4 tb_tile(const float* rowv, const float* colv) {
-  t4 s = {0.f, 0.f, 0.f, 0.f};
+__device__ __forceinline__ f32x4 tb_tile(const float* rowv, const float* colv) {
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int i = 0; i < 8; ++i) s = __builtin_amdgcn_mfma_f32_16x16x4f32(rowv[i], colv[i], s, 0, 0, 0);
   return s;
@@ -227,26 +226,11 @@ __device__ __forceinline__ t4 tb_tile(const float* rowv, const float* colv) {
 // The same tile on the 32-deep bf16 MFMA with split operands (x = hi + lo; hi hi + lo hi + hi lo: ~2^-16 relative per product, the
 // arithmetic of the forward kernel): a lane's eight values ARE its k-group of the 16 x 16 x 32 instruction (dims 8 g .. 8 g + 7) and
 // the C/D rows come out in the same order, so the operands and the row permutation above carry over unchanged - 3 instructions
-// instead of 8.  -DTB_SCORES_FP32=1 keeps the fp32 MFMA.
-typedef __attribute__((ext_vector_type(8))) __bf16 tb_bf16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned tb_u4;
-struct TbSplit { tb_u4 h, l; };
-__device__ __forceinline__ TbSplit tb_split8(const float* v) {
-  unsigned hh[4], ll[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hh[i]) : "v"(v[2 * i]), "v"(v[2 * i + 1]));
-    const float r0 = v[2 * i] - __uint_as_float(hh[i] << 16), r1 = v[2 * i + 1] - __uint_as_float(hh[i] & 0xffff0000u);
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(ll[i]) : "v"(r0), "v"(r1));
-  }
-  return TbSplit{tb_u4{hh[0], hh[1], hh[2], hh[3]}, tb_u4{ll[0], ll[1], ll[2], ll[3]}};
-}
-__device__ __forceinline__ t4 tb_tile3(const TbSplit& row, const TbSplit& col) {
-  t4 s = {0.f, 0.f, 0.f, 0.f};
-  s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(tb_bf16x8, row.l), __builtin_bit_cast(tb_bf16x8, col.h), s, 0, 0, 0);
-  s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(tb_bf16x8, row.h), __builtin_bit_cast(tb_bf16x8, col.l), s, 0, 0, 0);
-  s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(tb_bf16x8, row.h), __builtin_bit_cast(tb_bf16x8, col.h), s, 0, 0, 0);
-  return s;
+// instead of 8.  The row operand is split here, the column operand comes split (ch, cl).  -DTB_SCORES_FP32=1 keeps the fp32 MFMA.
+__device__ __forceinline__ f32x4 tb_tile3(const float* rowv, u32x4 ch, u32x4 cl) {
+  u32x4 rh, rl;
+  split8(rowv, rh, rl);
+  return mfma_16x16x32_x3(rh, rl, ch, cl, f32x4{0.f, 0.f, 0.f, 0.f});
 }
 #ifndef TB_SCORES_FP32
 #define TB_SCORES_FP32 0
@@ -294,11 +278,13 @@ __device__ __forceinline__ void mha_bwd_body(const MhaBwdParams& p, const int bx
     tb_load8(p.v + ((size_t)crow * p.B + b) * p.ldv + hoff + 8 * g, cd, 1.f);
   }
 
-  const TbSplit cq3 = tb_split8(cq), cd3 = tb_split8(cd);          // the column side's operands: split once
+  u32x4 cqh, cql, cdh, cdl;                                        // the column side's operands: split once
+  split8(cq, cqh, cql);
+  split8(cd, cdh, cdl);
   uint32_t seed_lo = 0, seed_hi = 0;
   if (DROP) { seed_lo = p.seed[0]; seed_hi = p.seed[1]; }
   const uint32_t drop_base = DROP ? mha_drop_row(b, h, 0, p.H, p.Lq, p.Lk) : 0u;
-  t4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, b0 = a0, b1 = a0;   // SIDE 0: dq^T (a);  SIDE 1: dk^T (a), dv^T (b)
+  f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, b0 = a0, b1 = a0;   // SIDE 0: dq^T (a);  SIDE 1: dk^T (a), dv^T (b)
   const int ntiles = (Lr + 15) / 16;
   // Everything a tile reads from memory, requested one tile ahead of its use (a wave has ~2 neighbours on its SIMD: without
   // the look-ahead every tile pays a full round trip to the L2).  Both kernels at 900 x 900 x 8 heads, back to back from a
@@ -343,8 +329,8 @@ __device__ __forceinline__ void mha_bwd_body(const MhaBwdParams& p, const int bx
     Tile nxt;
     load_tile(min(rt + TB_WAVES, ntiles - 1), nxt);
     // S^T and dP^T tiles: lane (col ci, g) register r <-> row rbase + g + 4 r
-    const t4 s = TB_SCORES_FP32 ? tb_tile(cur.rk, cq) : tb_tile3(tb_split8(cur.rk), cq3);
-    const t4 dp = TB_SCORES_FP32 ? tb_tile(cur.rv, cd) : tb_tile3(tb_split8(cur.rv), cd3);
+    const f32x4 s = TB_SCORES_FP32 ? tb_tile(cur.rk, cq) : tb_tile3(cur.rk, cqh, cql);
+    const f32x4 dp = TB_SCORES_FP32 ? tb_tile(cur.rv, cd) : tb_tile3(cur.rv, cdh, cdl);
     float pr[4], ds[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {

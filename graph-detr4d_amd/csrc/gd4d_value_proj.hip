@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void value_proj_wimg_kernel(const VpaWeights p
     const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
     const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     u32x4 h, l;
-    va_split8(v, h, l);
+    split8(v, h, l);
     *reinterpret_cast<u32x4*>(dst + (s * PARTS) * 1024 + lane * 16) = h;
     if (!SINGLE) *reinterpret_cast<u32x4*>(dst + (s * PARTS + 1) * 1024 + lane * 16) = l;
   }

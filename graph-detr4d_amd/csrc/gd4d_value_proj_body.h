@@ -3,12 +3,10 @@
 // the coarse pyramid levels, riding in the launch of the previous layer's row chain) run the same body.
 #pragma once
 #include "gd4d_common.h"
+#include "gd4d_bf16x3.h"
 
 namespace gd4d {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
 
@@ -34,28 +32,6 @@ struct VpaParams {
   int R, L, S, NL, Hh, Dh, total;
   unsigned long long* trace;           // dev (DBG & 16): per wave of the first 8 workgroups, cycles spent per phase segment
 };
-
-__device__ __forceinline__ unsigned va_cvt_pk_bf16(float lo_elem, float hi_elem) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo_elem), "v"(hi_elem));
-  return r;
-}
-
-// 8 consecutive floats -> one 16-byte chunk of bf16 hi halves and one of bf16 lo halves; x ~= hi + lo to ~2^-17 relative
-__device__ __forceinline__ void va_split8(const float* v, u32x4& h, u32x4& l) {
-  unsigned hh[4], ll[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hh[i] = va_cvt_pk_bf16(v[2 * i], v[2 * i + 1]);
-    const float ra = v[2 * i] - __uint_as_float(hh[i] << 16);              // exact: hi is a rounding of the input
-    const float rb = v[2 * i + 1] - __uint_as_float(hh[i] & 0xffff0000u);
-    ll[i] = va_cvt_pk_bf16(ra, rb);
-  }
-  h = u32x4{hh[0], hh[1], hh[2], hh[3]};
-  l = u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
-
-__device__ __forceinline__ bf16x8 va_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 
 // gd4d_chain_guest -> the kernel's parameters (one layer, pixel-major fp32 rows): gd4d_row_chain_guest_fwd and gd4d_value_proj_guest_fwd
 inline int va_guest_params(const gd4d_chain_guest* guest, VpaParams& g) {
@@ -159,7 +135,6 @@ __device__ __forceinline__ void value_proj_astat_body(const VpaParams& p, const 
   // 4 (lane & 7) .. + 4 of pixel 8 m + lane / 8.  Inline asm on purpose: hipcc would put "s_waitcnt vmcnt(0)" in front of
   // a visible LDS store while LDS-DMA is in flight (it cannot tell the patch from the ring).
   auto transpose_prev = [&](f32x16& acc) {
-    typedef __attribute__((ext_vector_type(4))) float f32x4;
     f32x4 q0 = {acc[0], acc[1], acc[2], acc[3]}, q1 = {acc[4], acc[5], acc[6], acc[7]};
     f32x4 q2 = {acc[8], acc[9], acc[10], acc[11]}, q3 = {acc[12], acc[13], acc[14], acc[15]};
     // LDS operations of a wave execute in order: the reads below see the writes, and may land in the registers the
@@ -250,7 +225,7 @@ __device__ __forceinline__ void value_proj_astat_body(const VpaParams& p, const 
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           u32x4 h, l;
-          va_split8(v[s], h, l);
+          split8(v[s], h, l);
           ahi[s4 + s] = h;
           alo[s4 + s] = l;
         }
@@ -313,11 +288,11 @@ __device__ __forceinline__ void value_proj_astat_body(const VpaParams& p, const 
                 xh[(s + 1) & 1] = *reinterpret_cast<const u32x4*>(wb2 + ((s + 1) * PARTS) * 1024 + lane * 16);
                 xl[(s + 1) & 1] = *reinterpret_cast<const u32x4*>(wb2 + ((s + 1) * PARTS + 1) * 1024 + lane * 16);
               }
-              cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va_frag(xh[s & 1]), va_frag(ahi[s]), cur, 0, 0, 0);
-              cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va_frag(xh[s & 1]), va_frag(alo[s]), cur, 0, 0, 0);
-              cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va_frag(xl[s & 1]), va_frag(ahi[s]), cur, 0, 0, 0);
+              // (the production order below, hi hi first)
+              cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(xh[s & 1]), frag(ahi[s]), cur, 0, 0, 0);
+              cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(xh[s & 1]), frag(alo[s]), cur, 0, 0, 0);
+              cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(xl[s & 1]), frag(ahi[s]), cur, 0, 0, 0);
             }
-            typedef __attribute__((ext_vector_type(4))) float f32x4;
             f32x4 q0 = {cur[0], cur[1], cur[2], cur[3]}, q1 = {cur[4], cur[5], cur[6], cur[7]};
             f32x4 q2 = {cur[8], cur[9], cur[10], cur[11]}, q3 = {cur[12], cur[13], cur[14], cur[15]};
             const unsigned wa = st_w + rep * (WAVES / 2) * (VA_TILE * PITCH);     // own patch, then the partner's
@@ -337,7 +312,6 @@ __device__ __forceinline__ void value_proj_astat_body(const VpaParams& p, const 
           }
           if (have_prev) {
             for (int rep = 0; rep < 2; ++rep) {
-              typedef __attribute__((ext_vector_type(4))) float f32x4;
               f32x4 q0, q1, q2, q3;
               const unsigned ra = st_r - rep * (WAVES / 2) * (VA_TILE * PITCH);
               asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:%5\n\tds_read_b128 %2, %4 offset:%6\n\t"
@@ -412,10 +386,11 @@ __device__ __forceinline__ void value_proj_astat_body(const VpaParams& p, const 
         }
         }
         if (DBG & 2) { asm volatile("" ::"v"(wh[s & 1]), "v"(wl[s & 1]), "v"(ahi[s]), "v"(alo[s])); continue; }
-        cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va_frag(wh[s & 1]), va_frag(ahi[s]), cur, 0, 0, 0);
+        // hi hi, hi lo, lo hi (SINGLE: hi hi alone): not mfma_32x32x16_x3's order, on purpose - reordering changes the fp32 sums
+        cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(wh[s & 1]), frag(ahi[s]), cur, 0, 0, 0);
         if (!SINGLE) {
-          cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va_frag(wh[s & 1]), va_frag(alo[s]), cur, 0, 0, 0);
-          cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va_frag(wl[s & 1]), va_frag(ahi[s]), cur, 0, 0, 0);
+          cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(wh[s & 1]), frag(alo[s]), cur, 0, 0, 0);
+          cur = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(wl[s & 1]), frag(ahi[s]), cur, 0, 0, 0);
         }
       }
       // a full tile issues exactly 4 store instructions (a partial one may skip instructions whose 8 pixels are all absent)

@@ -13,12 +13,9 @@
 #include <stdlib.h>
 
 #include "gd4d_common.h"
+#include "gd4d_bf16x3.h"
 
 namespace gd4d {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int VB_C = 256;
 
@@ -35,28 +32,6 @@ struct VpBwdParams {
   int R, L, S;
   int dbg;                              // dev ablation bits (GD4D_VW_DBG): 1 = no MFMAs, 2 = no global loads, 4 = no conversion / LDS writes, 8 = no pyramid loads, 16 = no grad_out loads
 };
-
-__device__ __forceinline__ unsigned vb_cvt_pk_bf16(float lo_elem, float hi_elem) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo_elem), "v"(hi_elem));
-  return r;
-}
-
-// 8 floats -> 16 bytes of bf16 "hi" halves and 16 bytes of bf16 residuals
-__device__ __forceinline__ void vb_split8(const float* v, u32x4& h, u32x4& l) {
-  unsigned hh[4], ll[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hh[i] = vb_cvt_pk_bf16(v[2 * i], v[2 * i + 1]);
-    const float ra = v[2 * i] - __uint_as_float(hh[i] << 16);            // exact: hi is a rounding of the value
-    const float rb = v[2 * i + 1] - __uint_as_float(hh[i] & 0xffff0000u);
-    ll[i] = vb_cvt_pk_bf16(ra, rb);
-  }
-  h = u32x4{hh[0], hh[1], hh[2], hh[3]};
-  l = u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
-
-__device__ __forceinline__ bf16x8 vb_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 
 // byte offset of 16-byte chunk `chunk` (8 bf16) of row `row` in a [rows][256] bf16 LDS image (XOR swizzle: the
 // b128 writes of 32 consecutive chunks and the b128 fragment reads of 32 consecutive rows are both conflict free)
@@ -132,7 +107,7 @@ __global__ __launch_bounds__(512, 2) void value_proj_bwd_input_kernel(const VpBw
   const int col = lane & 31, kg = lane >> 5;
 
   // A fragments: m = ci = 32 wave + col, k = co = 16 s + 8 kg + j
-  bf16x8 whi[KSTEPS], wlo[KSTEPS];
+  u32x4 whi[KSTEPS], wlo[KSTEPS];
   {
     const float* wcol = p.weight + (size_t)(8 * kg) * VB_C + 32 * wave + col;
 #pragma unroll
@@ -140,10 +115,7 @@ __global__ __launch_bounds__(512, 2) void value_proj_bwd_input_kernel(const VpBw
       float v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = wcol[(size_t)(16 * s + j) * VB_C];
-      u32x4 h, l;
-      vb_split8(v, h, l);
-      whi[s] = vb_frag(h);
-      wlo[s] = vb_frag(l);
+      split8(v, whi[s], wlo[s]);
     }
   }
 
@@ -183,7 +155,7 @@ __global__ __launch_bounds__(512, 2) void value_proj_bwd_input_kernel(const VpBw
                           in ? stage[i][0].w : 0.f, in ? stage[i][1].x : 0.f, in ? stage[i][1].y : 0.f,
                           in ? stage[i][1].z : 0.f, in ? stage[i][1].w : 0.f};
       u32x4 h, l;
-      vb_split8(v, h, l);
+      split8(v, h, l);
       const int off = vb_lds_off(q >> 5, q & 31);
       *reinterpret_cast<u32x4*>(hi_img + off) = h;
       *reinterpret_cast<u32x4*>(lo_img + off) = l;
@@ -231,11 +203,8 @@ __global__ __launch_bounds__(512, 2) void value_proj_bwd_input_kernel(const VpBw
 #pragma unroll
       for (int m = 0; m < SUB; ++m) {
         const int off = vb_lds_off(32 * m + col, 2 * s + kg);
-        const bf16x8 bhi = vb_frag(*reinterpret_cast<const u32x4*>(hi_img + off));
-        const bf16x8 blo = vb_frag(*reinterpret_cast<const u32x4*>(lo_img + off));
-        acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wlo[s], bhi, acc[m], 0, 0, 0);
-        acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi[s], blo, acc[m], 0, 0, 0);
-        acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi[s], bhi, acc[m], 0, 0, 0);
+        const u32x4 bhi = *reinterpret_cast<const u32x4*>(hi_img + off), blo = *reinterpret_cast<const u32x4*>(lo_img + off);
+        acc[m] = mfma_32x32x16_x3(whi[s], wlo[s], bhi, blo, acc[m]);
       }
     }
     {
@@ -341,11 +310,11 @@ __global__ __launch_bounds__(VW_THREADS) void value_proj_bwd_weight_kernel(const
       }
     }
     bsum += ((ys[0] + ys[1]) + (ys[2] + ys[3])) + ((ys[4] + ys[5]) + (ys[6] + ys[7]));
-    vb_split8(ys, h, l);
+    split8(ys, h, l);
     const int yoff = (yg * VB_C + yco) * 16;
     *reinterpret_cast<u32x4*>(base + yoff) = h;
     *reinterpret_cast<u32x4*>(base + VW_ARR + yoff) = l;
-    vb_split8(xs, h, l);
+    split8(xs, h, l);
     const int xoff = (xg * VB_C + xci) * 16;
     *reinterpret_cast<u32x4*>(base + 2 * VW_ARR + xoff) = h;
     *reinterpret_cast<u32x4*>(base + 3 * VW_ARR + xoff) = l;
@@ -379,24 +348,20 @@ __global__ __launch_bounds__(VW_THREADS) void value_proj_bwd_weight_kernel(const
     if (!(p.dbg & 1))
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 ah[2], al[2], bh[2], bl[2];
+      u32x4 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int aoff = ((2 * ks + kg) * VB_C + 64 * wm + 32 * i + l32) * 16;
         const int boff = ((2 * ks + kg) * VB_C + 64 * wn + 32 * i + l32) * 16;
-        ah[i] = vb_frag(*reinterpret_cast<const u32x4*>(base + aoff));
-        al[i] = vb_frag(*reinterpret_cast<const u32x4*>(base + VW_ARR + aoff));
-        bh[i] = vb_frag(*reinterpret_cast<const u32x4*>(base + 2 * VW_ARR + boff));
-        bl[i] = vb_frag(*reinterpret_cast<const u32x4*>(base + 3 * VW_ARR + boff));
+        ah[i] = *reinterpret_cast<const u32x4*>(base + aoff);
+        al[i] = *reinterpret_cast<const u32x4*>(base + VW_ARR + aoff);
+        bh[i] = *reinterpret_cast<const u32x4*>(base + 2 * VW_ARR + boff);
+        bl[i] = *reinterpret_cast<const u32x4*>(base + 3 * VW_ARR + boff);
       }
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-        }
+        for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma_32x32x16_x3(ah[mi], al[mi], bh[ni], bl[ni], acc[mi][ni]);
     }
     if (has_next) {
       park(cur ^ 1, rem_next);
