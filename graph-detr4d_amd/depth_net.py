@@ -93,7 +93,7 @@ class DepthNet(nn.Module):
         self.mlp = Mlp(1, mid_channels, mid_channels)
         self.se = SELayer(mid_channels)
         self.torch_ops = bool(torch_ops)
-        self._image_cache = None    # (key, weight image of reduce_conv[0])
+        self._image_cache = None    # (ops._Stamp, weight image of reduce_conv[0])
         self._mats = {}             # (device, request slot, N) -> [host intrinsics, host ida00 (N), device buffer]
 
     # ---- routes ---------------------------------------------------------------------------------------------------------
@@ -145,11 +145,10 @@ class DepthNet(nn.Module):
 
     # ---- kernel route -------------------------------------------------------------------------------------------------
     def _image(self):
-        """The 3x3 weight's fragment image, remade when the weight changes (load_state_dict, an optimizer step, an in-place edit)."""
+        """The 3x3 weight's fragment image, remade when the weight changes (ops.invalidate_chain_images states when)."""
         w = self.reduce_conv[0].weight
-        key = (str(w.device), w.data_ptr(), w._version)
-        if self._image_cache is None or self._image_cache[0] != key:
-            self._image_cache = (key, ops.depth_net_image(w.detach()))
+        if self._image_cache is None or not self._image_cache[0].valid((w,)):
+            self._image_cache = (ops._Stamp((w,)), ops.depth_net_image(w.detach()))
         return self._image_cache[1]
 
     def _matrices_device(self, intrin, ida00, dev, capturing=False):

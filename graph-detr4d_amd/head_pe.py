@@ -227,13 +227,13 @@ class FeaturePositionEmbedding(nn.Module):
         return out, out_masks
 
     def _sine_branch(self, masks, chlast=False):
-        """adapt_pos3d(sine(mask)); cached while the masks (and the weights) do not change.  chlast=False: per level
-        (B, N, C, H, W) through the library convolutions; chlast=True: one (B*N, S, C) channels-last tensor for all
-        levels through gd4d_gemm_bf16x3_fwd (no library call at all)."""
-        key = (chlast,) + tuple(p._version for p in self.adapt_pos3d.parameters())
+        """adapt_pos3d(sine(mask)); cached while the masks and the weights (ops.invalidate_chain_images) do not change.
+        chlast=False: per level (B, N, C, H, W) through the library convolutions; chlast=True: one (B*N, S, C) channels-last
+        tensor for all levels through gd4d_gemm_bf16x3_fwd (no library call at all)."""
+        params = list(self.adapt_pos3d.parameters())
         c = self._sine_cache
-        if c is not None and c[0] == key and len(c[1]) == len(masks) and all(a is m for a, m in zip(c[1], masks)):
-            return c[2]                              # same mask objects as last time (padding_masks caches by shapes)
+        if c is not None and c[0] == chlast and c[1].valid(params) and len(c[2]) == len(masks) and all(a is m for a, m in zip(c[2], masks)):
+            return c[3]                              # same mask objects as last time (padding_masks caches by shapes)
         if chlast:
             b, n = masks[0].shape[:2]
             sizes = [m.shape[2] * m.shape[3] for m in masks]
@@ -253,19 +253,18 @@ class FeaturePositionEmbedding(nn.Module):
             for m in masks:
                 s = self.sine_embedding(m)
                 res.append(self.adapt_pos3d(s.flatten(0, 1)).view(m.shape[0], m.shape[1], self.embed_dims, *m.shape[2:]))
-        if not any(p.requires_grad and torch.is_grad_enabled() for p in self.adapt_pos3d.parameters()):
-            self._sine_cache = (key, list(masks), res)
+        if not any(p.requires_grad and torch.is_grad_enabled() for p in params):
+            self._sine_cache = (chlast, ops._Stamp(params), list(masks), res)
         return res
 
     # ---- split-bf16 GEMM path ----------------------------------------------------------------------------------------
     def _split_weights(self):
-        """bf16 (hi, lo) splits of the five 1x1-conv weights for gd4d_gemm_bf16x3_fwd, remade when a weight changes."""
+        """bf16 (hi, lo) splits of the five 1x1-conv weights for gd4d_gemm_bf16x3_fwd, remade when a weight changes; the stamp also
+        covers position_encoder[2].bias and keys the kept embedding (ops.invalidate_chain_images)."""
         convs = dict(pe0=self.position_encoder[0], pe2=self.position_encoder[2], se1=self.fpe.conv_expand)
         cr = self.fpe.conv_reduce
-        key = tuple((c.weight.data_ptr(), c.weight._version) for c in convs.values()) + \
-            (self.position_encoder[0].bias.data_ptr(), self.position_encoder[0].bias._version) + \
-            (cr.weight.data_ptr(), cr.weight._version, cr.bias.data_ptr(), cr.bias._version)
-        if self._split_cache is None or self._split_cache[0] != key:
+        sources = [c.weight for c in convs.values()] + [convs['pe0'].bias, convs['pe2'].bias, cr.weight, cr.bias]
+        if self._split_cache is None or not self._split_cache['stamp'].valid(sources):
             flat = lambda c: c.weight.detach().view(c.out_channels, c.in_channels).contiguous()      # noqa: E731
             cache = {k: ops.split_bf16_fwd(flat(c)) for k, c in convs.items()}
             pe0, pe2 = convs['pe0'], convs['pe2']
@@ -280,9 +279,9 @@ class FeaturePositionEmbedding(nn.Module):
             ce = convs['se1']
             cache['se_mlp'] = ops.mlp2_image(flat(cr), cr.bias.detach(), flat(ce)) \
                 if cr.in_channels == 256 and ops.mlp2_supported(cr.in_channels, cr.out_channels, ce.out_channels) else None
-            cache['key'] = key
-            self._split_cache = (key, cache)
-        return self._split_cache[1]
+            cache['stamp'] = ops._Stamp(sources)
+            self._split_cache = cache
+        return self._split_cache
 
     def _position_mlp(self, img2lidar, shapes, starts, s_tot, pad_hw, sw, out=None):
         """position_encoder(frustum) for the cameras of `img2lidar` (R', 4, 4) -> (R', S, C) channels-last rows (`out`: written there)."""
@@ -321,8 +320,7 @@ class FeaturePositionEmbedding(nn.Module):
         # The embedding of a camera is a function of its matrix, the level shapes and the MLP's weights - not of the features.  It is
         # kept per camera and recomputed for the cameras whose matrix changed: the current frame's cameras keep their calibration
         # from sample to sample (the past frames' matrices carry the ego motion and change every time).
-        b2 = self.position_encoder[2].bias
-        pkey = (str(dev), tuple(shapes), tuple(pad_hw), r, sw['key'], b2.data_ptr(), b2._version)
+        pkey = (str(dev), tuple(shapes), tuple(pad_hw), r, sw['stamp'])
         if self.channels_last_out and sw.get('se_mlp') is not None and sw.get('pe_mlp_fr') is not None and len(feats) <= 4 \
                 and os.environ.get('GD4D_PE_FUSED', '1') != '0':
             return self._forward_one_kernel(feats, mats, sw, sine, shapes, starts, s_tot, pad_hw, pkey)

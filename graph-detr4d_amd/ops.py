@@ -7,6 +7,7 @@ import ctypes
 import functools
 import inspect
 import os
+import weakref
 
 import torch
 
@@ -462,9 +463,6 @@ def value_proj_heads_bwd_weight(grad_out, agg, wsum=None, want_bias=True, into=N
     return gw, gb
 
 
-_VPH_WS = {}
-
-
 def value_proj_heads_bwd_weight_group(problems, accumulate=True):
     """gd4d_value_proj_heads_bwd_weight_group: problems = list (<= 8) of (grad_out (..., 256), agg (..., Hh, 256), wsum (..., Hh),
     grad_weight (256, 256), grad_bias (256) or None) - value_proj's gradients of several layers in one pair of launches, added to
@@ -475,10 +473,7 @@ def value_proj_heads_bwd_weight_group(problems, accumulate=True):
     hh, c = problems[0][1].shape[-2], problems[0][1].shape[-1]
     dev = problems[0][0].device
     nbytes = n * int(lib.gd4d_value_proj_heads_bwd_weight_workspace_bytes())
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _VPH_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _VPH_WS[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)             # (scratch of this call only: see _vp_workspace)
     arr = lambda v: (ctypes.c_void_p * n)(*v)          # noqa: E731
     rows = (ctypes.c_int32 * n)(*[int(g.numel() // c) for g, _, _, _, _ in problems])
     code = lib.gd4d_value_proj_heads_bwd_weight_group(
@@ -986,9 +981,6 @@ def linear_bwd_weight_group(problems, accumulate=True):
     _lib.check(code, 'gd4d_linear_bwd_weight_group')
 
 
-_VP_BWD_WS = {}
-
-
 def value_proj_bwd_input(grad_out, weight, shapes, grads=None, accumulate=False):
     """gd4d_value_proj_bwd_input.  grad_out (R, S, C) fp32; weight (C, C); shapes: per level (H_l, W_l).
     Returns the list of L gradients (R, C, H_l, W_l); with `grads` given they are written (accumulate=False) or added
@@ -1020,10 +1012,7 @@ def value_proj_bwd_weight(grad_out, feats, want_bias=True):
     r = feats[0].numel() // (c * feats[0].shape[-1] * feats[0].shape[-2])
     dev = grad_out.device
     nbytes = lib.gd4d_value_proj_bwd_weight_workspace_bytes()
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _VP_BWD_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _VP_BWD_WS[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)             # (scratch of this call only: see _vp_workspace)
     gw = torch.empty(c, c, device=dev, dtype=f32)
     gb = torch.empty(c, device=dev, dtype=f32) if want_bias else None
     ptrs = (ctypes.c_void_p * nl)(*[_dev(f, f'feats[{i}]', f32).value for i, f in enumerate(feats)])
@@ -1575,9 +1564,6 @@ def mlp2_frustum_fwd(img2lidar, level_hw, pad_hw, depth_num, depth_start, pc_ran
     return out.view(r, s_tot, n2)
 
 
-_TN_WS = {}
-
-
 def gemm_tn_bf16x3(a, b, relu_b=False, want_colsum=True):
     """gd4d_gemm_tn_bf16x3: a (R, M), b (R, N) fp32 row-major -> (a^T b (M, N), column sums of a (M) or None): the weight /
     bias gradients of a Linear over R rows (a = output gradient, b = input; relu_b: ReLU on b as it is read)."""
@@ -1588,11 +1574,7 @@ def gemm_tn_bf16x3(a, b, relu_b=False, want_colsum=True):
         raise ValueError(f'gemm_tn_bf16x3: {tuple(a.shape)} against {tuple(b.shape)}')
     dev = a.device
     nbytes = lib.gd4d_gemm_tn_bf16x3_workspace_bytes(r, m, n)
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _TN_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        _TN_WS[key] = ws
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)             # (scratch of this call only: see _vp_workspace)
     c = torch.empty(m, n, device=dev, dtype=torch.float32)
     col = torch.empty(m, device=dev, dtype=torch.float32) if want_colsum else None
     code = lib.gd4d_gemm_tn_bf16x3(_dev(a, 'a', torch.float32), _dev(b, 'b', torch.float32), _dev(c, 'c'), _opt(col, 'colsum'),
@@ -1890,39 +1872,75 @@ _CHAIN_EPOCH = [0]
 
 
 def invalidate_chain_images():
-    """Forget every cached weight image.  The cache notices re-assignment and in-place autograd-visible writes (a tensor's
-    version counter), but NOT writes through `.data` (p.data.copy_(), mmcv's EMA swap): call this after such an update -
-    the package's modules do it from train() / eval() and after load_state_dict."""
-    _CHAIN_IMAGES.clear()
-    _VP_IMAGES.clear()
+    """The one rule for every value kept from parameters (_Stamp): chain_weight_image, value_proj_image, the stacked weights of
+    chain_gemm_three_outputs, DepthNet's weight image, FeaturePositionEmbedding's weight splits, sine branch and kept embedding.
+    Such a value is served while each source is the same live tensor (through its `_base`) with the same address, shape, dtype
+    and version counter, and while this function has not been called since it was built; it is dropped when a source dies.
+    Version counters miss writes through `.data` (p.data.copy_(), mmcv's EMA swap, an optimizer step inside a replayed graph):
+    call this after such an update - the package's modules do it from train() / eval() and after load_state_dict."""
+    for table in (_CHAIN_IMAGES, _VP_IMAGES, _STACKED):
+        table.clear()
     _CHAIN_EPOCH[0] += 1
+
+
+class _Stamp:
+    """Whether a value built from the tensors `sources` (None: an absent one, e.g. a missing bias) still holds, by the rule of
+    invalidate_chain_images; on_death (a weakref callback) runs when a source dies.  A copy (copy.deepcopy, pickle, torch.save of a module that
+    keeps one) is never valid: it must not vouch for the original's tensors."""
+    __slots__ = ('_refs', '_marks', '_epoch')
+
+    def __init__(self, sources=(), on_death=None):
+        self._refs = [weakref.ref(_base(t), on_death) for t in sources if t is not None]
+        self._marks = [_mark(t) for t in sources]
+        self._epoch = _CHAIN_EPOCH[0] if sources else -1
+
+    def valid(self, sources):
+        # (while the referents live, no other object has their id(): equal ids are the same tensors)
+        return self._epoch == _CHAIN_EPOCH[0] and all(r() is not None for r in self._refs) and [_mark(t) for t in sources] == self._marks
+
+    def __reduce__(self):
+        return _Stamp, ()
+
+
+def _base(t):
+    return t if t._base is None else t._base
+
+
+def _mark(t):
+    return None if t is None else (id(_base(t)), t.data_ptr(), t.shape, t.dtype, t.device, t._version)
+
+
+def _kept(table, key, sources, build):
+    """table[key]: build()'s value of `sources`, rebuilt when the stamp it was kept with no longer holds; a source's death drops it."""
+    hit = table.get(key)
+    if hit is not None and hit[0].valid(sources):
+        return hit[1]
+    value = build()
+    table[key] = (_Stamp(sources, lambda _r: table.pop(key, None)), value)
+    return value
 
 
 def chain_weight_image(weight, exact=False):
     """The bf16 hi / lo (exact: hi / mid / lo) MFMA-fragment image of a (N, K) fp32 weight (gd4d_chain_weight_image[_exact]),
-    cached while the weight tensor (address, shape, version counter) does not change - one small launch after a
-    load_state_dict or an optimizer step, none in steady-state inference.  Entries die with their tensor."""
-    import weakref
+    kept while the weight does not change (invalidate_chain_images) - one small launch after a load_state_dict or an optimizer
+    step, none in steady-state inference."""
     if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 2 or weight.stride(1) != 1 \
             or weight.stride(0) != weight.shape[1]:
         raise ValueError('chain weights must be dense (N, K) float32 GPU tensors')
-    base = weight._base if weight._base is not None else weight
-    key = (weight.data_ptr(), tuple(weight.shape), bool(exact))
-    hit = _CHAIN_IMAGES.get(key)
-    if hit is not None and hit[0]() is base and hit[1] == base._version:
-        return hit[2]
-    lib = _lib.load()
-    n, k = weight.shape
-    nbytes = (lib.gd4d_chain_weight_image_exact_bytes if exact else lib.gd4d_chain_weight_image_bytes)(n, k)
-    if nbytes == 0:
-        raise _lib.Gd4dError(f'chain GEMM: K = {k} must be a multiple of 64')
-    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
-    with torch.cuda.device(weight.device):
-        fn = lib.gd4d_chain_weight_image_exact if exact else lib.gd4d_chain_weight_image
-        code = fn(ctypes.c_void_p(weight.data_ptr()), n, k, ctypes.c_void_p(img.data_ptr()), _stream())
-    _lib.check(code, 'gd4d_chain_weight_image')
-    _CHAIN_IMAGES[key] = (weakref.ref(base, lambda _r, key=key: _CHAIN_IMAGES.pop(key, None)), base._version, img)
-    return img
+
+    def build():
+        lib = _lib.load()
+        n, k = weight.shape
+        nbytes = (lib.gd4d_chain_weight_image_exact_bytes if exact else lib.gd4d_chain_weight_image_bytes)(n, k)
+        if nbytes == 0:
+            raise _lib.Gd4dError(f'chain GEMM: K = {k} must be a multiple of 64')
+        img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
+        with torch.cuda.device(weight.device):
+            fn = lib.gd4d_chain_weight_image_exact if exact else lib.gd4d_chain_weight_image
+            code = fn(ctypes.c_void_p(weight.data_ptr()), n, k, ctypes.c_void_p(img.data_ptr()), _stream())
+        _lib.check(code, 'gd4d_chain_weight_image')
+        return img
+    return _kept(_CHAIN_IMAGES, (weight.data_ptr(), tuple(weight.shape), bool(exact)), (weight,), build)
 
 
 class ImageJob(ctypes.Structure):
@@ -2121,23 +2139,15 @@ _STACKED = {}
 
 
 def _stacked_linears(linears):
-    """cat of the Linears' weights / biases, cached while none of them changes: the entry holds weak references to the weight
-    tensors it was built from (an id() or an address alone can be handed to another object after a free) plus their version
-    counters and the image epoch."""
-    import weakref
-    key = tuple(id(m) for m in linears)
-    sig = tuple((m.weight.data_ptr(), m.weight._version, None if m.bias is None else (m.bias.data_ptr(), m.bias._version))
-                for m in linears) + (_CHAIN_EPOCH[0],)
-    hit = _STACKED.get(key)
-    if hit is not None and hit[0] == sig and all(r() is m.weight for r, m in zip(hit[3], linears)):
-        return hit[1], hit[2]
-    with torch.no_grad():
-        w = torch.cat([m.weight for m in linears], 0).contiguous()
-        b = torch.cat([m.bias if m.bias is not None else m.weight.new_zeros(m.weight.shape[0]) for m in linears], 0).contiguous()
+    """cat of the Linears' weights / biases (zeros for a missing bias), kept while none of them changes (invalidate_chain_images)."""
+    def build():
+        with torch.no_grad():
+            w = torch.cat([m.weight for m in linears], 0).contiguous()
+            b = torch.cat([m.bias if m.bias is not None else m.weight.new_zeros(m.weight.shape[0]) for m in linears], 0).contiguous()
+        return w, b
     if len(_STACKED) > 256:                               # modules come and go in long-lived processes
         _STACKED.clear()
-    _STACKED[key] = (sig, w, b, [weakref.ref(m.weight) for m in linears])
-    return w, b
+    return _kept(_STACKED, tuple(id(m) for m in linears), [t for m in linears for t in (m.weight, m.bias)], build)
 
 
 def chain_gemm_three_outputs(src, linears, outs, stacked=None, exact=False):
@@ -2368,29 +2378,20 @@ _VP_IMAGES = {}
 
 def value_proj_image(weight, bias=None):
     """gd4d_value_proj_image of a layer's value_proj (256, 256) weight and bias: the split-bf16 fragment image the guests of
-    row_chain_fwd(..., guest=) stream through LDS.  Cached like chain_weight_image (address, version counters of weight AND bias;
-    invalidate_chain_images() forgets these too)."""
-    import weakref
+    row_chain_fwd(..., guest=) stream through LDS, kept while neither changes (invalidate_chain_images)."""
     if not weight.is_cuda or weight.dtype != torch.float32 or tuple(weight.shape) != (256, 256) or not weight.is_contiguous():
         raise ValueError('value_proj_image: a contiguous (256, 256) float32 GPU weight')
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != 256 or not bias.is_contiguous() or bias.device != weight.device):
         raise ValueError('value_proj_image: bias (256) float32 on the weight\'s GPU')
-    wb = weight._base if weight._base is not None else weight
-    bb = None if bias is None else (bias._base if bias._base is not None else bias)
-    key = (weight.data_ptr(), None if bias is None else bias.data_ptr())
-    hit = _VP_IMAGES.get(key)
-    if hit is not None and hit[0]() is wb and hit[1] == wb._version and hit[4] == _CHAIN_EPOCH[0] and \
-            (bb is None or (hit[2]() is bb and hit[3] == bb._version)):
-        return hit[5]
-    lib = _lib.load()
-    img = torch.empty(int(lib.gd4d_value_proj_image_bytes()), device=weight.device, dtype=torch.uint8)
-    with torch.cuda.device(weight.device):
+
+    def build():
+        lib = _lib.load()
+        img = torch.empty(int(lib.gd4d_value_proj_image_bytes()), device=weight.device, dtype=torch.uint8)
         code = lib.gd4d_value_proj_image(_dev(weight, 'weight', torch.float32), None if bias is None else _dev(bias, 'bias', torch.float32),
-                                         _dev(img, 'image'), _stream())
-    _lib.check(code, 'gd4d_value_proj_image')
-    _VP_IMAGES[key] = (weakref.ref(wb), wb._version, None if bb is None else weakref.ref(bb), None if bb is None else bb._version,
-                       _CHAIN_EPOCH[0], img)
-    return img
+                                         _dev(img, 'image'), _stream())          # (_on_tensor_device: the weight's device is current)
+        _lib.check(code, 'gd4d_value_proj_image')
+        return img
+    return _kept(_VP_IMAGES, (weight.data_ptr(), None if bias is None else bias.data_ptr()), (weight, bias), build)
 
 
 def chain_guest(levels, image, out, workgroups=0):

@@ -258,6 +258,26 @@ def test_output_follows_new_weights():
         assert not torch.equal(a, b) and not torch.equal(b, c) and not torch.equal(c, d)
 
 
+def test_a_write_through_data_reaches_the_weight_image_after_invalidate():
+    """p.data.copy_() bumps no version counter: after ops.invalidate_chain_images() the 3x3 weight's image is rebuilt and the output
+    equals a fresh module's with the new weight bit for bit."""
+    from graph_detr4d_amd import ops
+    n = 6
+    mod = _random_module(13)
+    metas = _rig_metas(n, 13)
+    gen = torch.Generator().manual_seed(13)
+    feats = [torch.randn(1, n, 256, h, w, generator=gen).to(DEV) for h, w in [(20, 33), (10, 17)]]
+    with torch.no_grad():
+        before = mod.forward_levels(feats, metas)
+        mod.reduce_conv[0].weight.data.copy_(_random_module(14).reduce_conv[0].weight)
+        ops.invalidate_chain_images()
+        got = mod.forward_levels(feats, metas)
+        fresh = _random_module(13)
+        fresh.load_state_dict(mod.state_dict())
+        for a, b, c in zip(got, fresh.forward_levels(feats, metas), before):
+            assert torch.equal(a, b) and not torch.equal(a, c)
+
+
 def test_training_needs_the_torch_route():
     """(f) train() without torch_ops raises; with torch_ops=True the module is the reference arithmetic with batch statistics and
     gradients reach every parameter the reference's forward uses (context_conv's output is discarded there too)."""

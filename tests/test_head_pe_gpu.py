@@ -132,6 +132,31 @@ def test_position_embedding_is_kept_per_camera_and_follows_the_matrices():
         ops.mlp2_bf16x3_fwd, ops.mlp2_frustum_fwd = real, real_fr
 
 
+@pytest.mark.parametrize('channels_last_out', [False, True])
+def test_a_write_through_data_reaches_every_kept_value_after_invalidate(channels_last_out):
+    """p.data.copy_() bumps no version counter: after ops.invalidate_chain_images() the weight splits, the sine branch and the kept
+    per-camera embedding are rebuilt, and the output equals a fresh module's with the new weights bit for bit."""
+    from graph_detr4d_amd import ops
+    g = Golden('head_pe')
+    feats = [f.cuda() for f in g.feats()]
+    metas = _metas(g)
+    mod = _module(g)
+    mod.channels_last_out = channels_last_out
+    torch.manual_seed(3)
+    with torch.no_grad():
+        before = mod(feats, metas)
+        for p in (mod.position_encoder[0].weight, mod.adapt_pos3d[2].weight, mod.fpe.conv_expand.weight):
+            p.data.copy_(torch.randn_like(p) * p.std())
+            ops.invalidate_chain_images()
+            got = mod(feats, metas)
+            fresh = _module(g)
+            fresh.load_state_dict(mod.state_dict())
+            fresh.channels_last_out = channels_last_out
+            for a, b, c in zip(got, fresh(feats, metas), before):
+                assert torch.equal(a, b) and not torch.equal(a, c)
+            before = got
+
+
 @pytest.mark.parametrize('levels,r', [([(7, 9), (5, 3), (3, 3)], 3), ([(16, 28), (8, 14), (4, 7), (2, 4)], 2), ([(5, 5)], 1), ([(29, 50), (15, 25)], 5)])
 def test_se_gate_and_fuse_as_one_kernel_matches_fp64(levels, r):
     """gd4d_mlp2_se_fuse_fwd on level sizes that put camera / level boundaries inside its groups of 4 pixels and its 128-row tiles (odd
