@@ -103,12 +103,17 @@ def bilinear_zero_pad(value_l, x, y):
     return out
 
 
-def msda(value, shapes, loc, weights):
+def msda(value, shapes, loc, weights, corners=None):
     """Third-party MSDA (mmcv multi_scale_deformable_attn), call site deform3d_cross_attn.py:302-309.
 
     value (S, sum(HW), Hh, Dh); loc (S, Q, Hh, L, P, 2) in [0,1]; weights (S, Q, Hh, L*P).
     Returns (S, Q, Hh*Dh).  Uses ATen grid_sample (the arbiter for this boundary).
+    corners (S, Q, Hh, L, P, 2) integer, or None: the top-left bilinear corner (x0, y0) of every sample, given from outside
+    instead of floor(pixel coordinate) - the explicit-gather rule of bilinear_zero_pad on those corners; the weights stay
+    continuous in the coordinates (x - x0, y - y0).
     """
+    if corners is not None:
+        return _msda_at_corners(value, shapes, loc, weights, corners)
     s, _, hh, dh = value.shape
     _, q, _, nl, npnt, _ = loc.shape
     parts = value.split([h * w for h, w in shapes], dim=1)
@@ -122,6 +127,42 @@ def msda(value, shapes, loc, weights):
     return (samp * wt).sum(-1).view(s, hh * dh, q).transpose(1, 2).contiguous()
 
 
+def _msda_at_corners(value, shapes, loc, weights, corners):
+    """msda with the bilinear corners given (bilinear_zero_pad's rule: pixel x = loc * W - 0.5, zero padding)."""
+    s, _, hh, dh = value.shape
+    _, q, _, nl, npnt, _ = loc.shape
+    parts = value.split([h * w for h, w in shapes], dim=1)
+    wts = weights.reshape(s, q, hh, nl, npnt)
+    si = torch.arange(s, device=value.device).view(s, 1, 1, 1)
+    hi = torch.arange(hh, device=value.device).view(1, 1, hh, 1)
+    out = 0
+    for lvl, (h, w) in enumerate(shapes):
+        v = parts[lvl].permute(0, 2, 1, 3)                                  # (S, Hh, HW, Dh)
+        x0, y0 = corners[:, :, :, lvl, :, 0].long(), corners[:, :, :, lvl, :, 1].long()     # (S, Q, Hh, P)
+        dx = loc[:, :, :, lvl, :, 0] * w - 0.5 - x0.to(loc.dtype)
+        dy = loc[:, :, :, lvl, :, 1] * h - 0.5 - y0.to(loc.dtype)
+        a = wts[:, :, :, lvl]
+        for (yy, xx, wt) in ((y0, x0, (1 - dy) * (1 - dx)), (y0, x0 + 1, (1 - dy) * dx),
+                             (y0 + 1, x0, dy * (1 - dx)), (y0 + 1, x0 + 1, dy * dx)):
+            ok = (xx >= 0) & (xx <= w - 1) & (yy >= 0) & (yy <= h - 1)
+            flat = yy.clamp(0, h - 1) * w + xx.clamp(0, w - 1)
+            out = out + (v[si, hi, flat] * (a * wt * ok).unsqueeze(-1)).sum(3)        # (S, Q, Hh, Dh)
+    return out.reshape(s, q, hh * dh)
+
+
+def relu_or_mask(z, mask=None):
+    """relu(z); with mask (any shape of z's size): z * mask, the ReLU's decision given from outside."""
+    return F.relu(z) if mask is None else z * mask.reshape(z.shape).to(z.dtype)
+
+
+def dropout_keep(x, site=None):
+    """Identity (eval mode); site = (keep mask of x's size, p): x * keep / (1 - p), the mask given from outside."""
+    if site is None:
+        return x
+    keep, p = site
+    return x * keep.reshape(x.shape).to(x.dtype) * (1.0 / (1.0 - p))
+
+
 def scrambled_cam_weights(cam_logits, num_cams):
     """deform3d_cross_attn.py:211-212: the (B,Q,N) Linear output is VIEWED as (B,N,Q,1)."""
     b, q, n = cam_logits.shape
@@ -129,7 +170,7 @@ def scrambled_cam_weights(cam_logits, num_cams):
 
 
 def sample_aggregate(value, shapes, ref, offsets, attn_logits, cam_logits, lidar2img, pc_range,
-                     img_h, img_w, raw_cam=False):
+                     img_h, img_w, raw_cam=False, vis_mask=None, corners=None):
     """The fused kernel's contract (a3+a5+a6+a7-reduction; deform3d_cross_attn.py:220-324).
 
     value (B*N, sum(HW), Hh, Dh) already value_proj-ed; ref (B,Q,3) in [0,1];
@@ -137,6 +178,8 @@ def sample_aggregate(value, shapes, ref, offsets, attn_logits, cam_logits, lidar
     Linear output; lidar2img (B,N,4,4).
     Returns out (B,Q,Hh*Dh) = sum_n sigmoid(cam[b,n,q]) * MSDA_n, uv (B,N,Q,Hh,P,2) and
     mask (B,N,Q,Hh,P) bool.
+    vis_mask (B,N,Q,Hh,P): the visibility mask used instead of the projection's own (the returned mask stays the
+    projection's); corners (B,N,Q,Hh,L,P,2) integer: the bilinear corners used (msda).
     """
     b, q, hh, p, _ = offsets.shape
     n = lidar2img.shape[1]
@@ -151,8 +194,10 @@ def sample_aggregate(value, shapes, ref, offsets, attn_logits, cam_logits, lidar
     # for B=1 (every shipped config); reproduced for B>1 because it is what the reference computes.
     rows = torch.arange(b * n) % b
     w = attn_logits.softmax(-1)[rows].view(b, n, q, hh, nl, p)
-    w = (w * mask.view(b, n, q, hh, 1, p)).reshape(b * n, q, hh, nl * p)
-    per_cam = msda(value, shapes, loc, w).view(b, n, q, -1)                 # :302-304
+    used = mask if vis_mask is None else vis_mask.reshape(mask.shape).bool()
+    w = (w * used.view(b, n, q, hh, 1, p)).reshape(b * n, q, hh, nl * p)
+    cr = None if corners is None else corners.reshape(b * n, q, hh, nl, p, 2)
+    per_cam = msda(value, shapes, loc, w, corners=cr).view(b, n, q, -1)     # :302-304
     cam = scrambled_cam_weights(cam_logits, n)
     cam = cam if raw_cam else cam.sigmoid()                                 # :320 (MP neighbour pass: raw)
     return (per_cam * cam).sum(1), uv, mask                                  # :322-324
@@ -163,12 +208,15 @@ def _bf16r(t):
 
 
 def deform3d_cross_attn(p, query, value, query_pos, reference_points, img_metas, pc_range,
-                        num_heads=8, num_points=4, depth_encode=False, return_parts=False, value_dtype='fp32'):
+                        num_heads=8, num_points=4, depth_encode=False, return_parts=False, value_dtype='fp32',
+                        vis_mask=None, corners=None, pe_relu_masks=None, drop_out=None):
     """Deform3DCrossAttn.forward in eval mode, deform3d_cross_attn.py:196-339 (Appendix A.1).
 
     value_dtype='bf16' restates the build's opt-in reduced-precision mode (not a reference mode): value_proj on
     bf16-rounded features and weights (exact products, fp32 accumulate, fp32 bias) and the projected value tensor
-    rounded to bf16; everything else fp32.  value_dtype='bf16_features': only the features are rounded to bf16."""
+    rounded to bf16; everything else fp32.  value_dtype='bf16_features': only the features are rounded to bf16.
+    Decisions given from outside (None: the oracle's own): vis_mask / corners (sample_aggregate), pe_relu_masks
+    (position_encoder's relu_masks), drop_out (dropout_keep's site after output_proj, :336)."""
     x = query if query_pos is None else query + query_pos                   # :203-204
     x = x.permute(1, 0, 2)                                                  # :207
     b, q, c = x.shape
@@ -190,17 +238,18 @@ def deform3d_cross_attn(p, query, value, query_pos, reference_points, img_metas,
         val = _linear(flat, p, 'value_proj')
     val = val.view(b * n, flat.shape[1], num_heads, c // num_heads)
     agg, uv, mask = sample_aggregate(val, shapes, reference_points, offsets, attn_logits,
-                                     cam_logits, l2i, pc_range, img_h, img_w)
+                                     cam_logits, l2i, pc_range, img_h, img_w, vis_mask=vis_mask, corners=corners)
     out = _linear(agg, p, 'output_proj').permute(1, 0, 2)                   # :326-327
     ref3d = reference_points
     if depth_encode:                                                        # :331-333
         depth = (ref3d[..., 0:1] ** 2 + ref3d[..., 1:2] ** 2) ** 0.5
         ref3d = torch.cat([ref3d, depth], -1)
-    pos = position_encoder(p, inverse_sigmoid(ref3d)).permute(1, 0, 2)      # :334
-    res = out + query + pos                                                 # :336 (dropout = id)
+    pre = [] if return_parts else None
+    pos = position_encoder(p, inverse_sigmoid(ref3d), relu_masks=pe_relu_masks, pre=pre).permute(1, 0, 2)   # :334
+    res = dropout_keep(out, drop_out) + query + pos                         # :336 (dropout = id in eval)
     if return_parts:
         return res, dict(agg=agg, uv=uv, mask=mask, offsets=offsets, attn_logits=attn_logits,
-                         cam_logits=cam_logits, value=val, pos=pos)
+                         cam_logits=cam_logits, value=val, pos=pos, pe_pre=pre)
     return res
 
 
@@ -245,13 +294,22 @@ def deform3d_cross_attn_mp(p, query, value, reference_points, img_metas, pc_rang
     return res
 
 
-def position_encoder(p, x, prefix='position_encoder'):
-    """deform3d_cross_attn.py:104-111: Linear, LN, ReLU, Linear, LN, ReLU."""
+def position_encoder(p, x, prefix='position_encoder', relu_masks=None, pre=None):
+    """deform3d_cross_attn.py:104-111: Linear, LN, ReLU, Linear, LN, ReLU.
+    relu_masks: (mask of the first ReLU, mask of the second) given from outside (relu_or_mask); pre: a list that receives
+    the two pre-activations."""
     c = p[prefix + '.0.weight'].shape[0]
+    m1, m2 = (None, None) if relu_masks is None else relu_masks
     x = F.linear(x, p[prefix + '.0.weight'], p[prefix + '.0.bias'])
-    x = F.relu(F.layer_norm(x, (c,), p[prefix + '.1.weight'], p[prefix + '.1.bias']))
+    z = F.layer_norm(x, (c,), p[prefix + '.1.weight'], p[prefix + '.1.bias'])
+    if pre is not None:
+        pre.append(z)
+    x = relu_or_mask(z, m1)
     x = F.linear(x, p[prefix + '.3.weight'], p[prefix + '.3.bias'])
-    return F.relu(F.layer_norm(x, (c,), p[prefix + '.4.weight'], p[prefix + '.4.bias']))
+    z = F.layer_norm(x, (c,), p[prefix + '.4.weight'], p[prefix + '.4.bias'])
+    if pre is not None:
+        pre.append(z)
+    return relu_or_mask(z, m2)
 
 
 def feature_sampling(mlvl_feats, reference_points, pc_range, img_metas):
@@ -305,12 +363,14 @@ def detr3d_cross_atten(p, query, value, query_pos, reference_points, img_metas, 
     return out + query + pos                                                # :390
 
 
-def multihead_self_attn(p, query, query_pos, num_heads=8, attn_mask=None, prefix='attn.'):
+def multihead_self_attn(p, query, query_pos, num_heads=8, attn_mask=None, prefix='attn.', drop_attn=None, drop_out=None):
     """Decoder self-attention: third-party mmcv MultiheadAttention -> nn.MultiheadAttention
     (config call site: projects/configs/detr4d/detr4d_res50_deform_pe_testaug_320_fullset_ceph.py:74-78).
 
     q = k = query + query_pos, v = query; packed in_proj; softmax(q k^T / sqrt(d)) v; out_proj;
     returns identity + out (dropout = identity in eval).  query (Q, B, C).
+    drop_attn / drop_out: dropout_keep sites given from outside - the attention probabilities (keep mask (B, heads, Q, Q))
+    and the output after out_proj.
     """
     nq, b, c = query.shape
     d = c // num_heads
@@ -329,15 +389,20 @@ def multihead_self_attn(p, query, query_pos, num_heads=8, attn_mask=None, prefix
             scores = scores.masked_fill(attn_mask, float('-inf'))
         else:
             scores = scores + attn_mask
-    o = torch.bmm(scores.softmax(-1), vh).transpose(0, 1).reshape(nq, b, c)
+    o = torch.bmm(dropout_keep(scores.softmax(-1), drop_attn), vh).transpose(0, 1).reshape(nq, b, c)
     o = F.linear(o, p[prefix + 'out_proj.weight'], p[prefix + 'out_proj.bias'])
-    return query + o
+    return query + dropout_keep(o, drop_out)
 
 
-def ffn(p, x, prefix='ffns.0.'):
-    """Third-party mmcv FFN (config :86-87): x + W2 relu(W1 x)."""
-    h = F.relu(F.linear(x, p[prefix + 'layers.0.0.weight'], p[prefix + 'layers.0.0.bias']))
-    return x + F.linear(h, p[prefix + 'layers.1.weight'], p[prefix + 'layers.1.bias'])
+def ffn(p, x, prefix='ffns.0.', relu_mask=None, drop_hidden=None, drop_out=None, pre=None):
+    """Third-party mmcv FFN (config :86-87): x + W2 relu(W1 x).
+    relu_mask: the hidden ReLU's decision given from outside (relu_or_mask); drop_hidden / drop_out: dropout_keep sites
+    after the ReLU and after W2; pre: a list that receives the hidden pre-activation."""
+    z = F.linear(x, p[prefix + 'layers.0.0.weight'], p[prefix + 'layers.0.0.bias'])
+    if pre is not None:
+        pre.append(z)
+    h = dropout_keep(relu_or_mask(z, relu_mask), drop_hidden)
+    return x + dropout_keep(F.linear(h, p[prefix + 'layers.1.weight'], p[prefix + 'layers.1.bias']), drop_out)
 
 
 def _sub(p, prefix):
@@ -346,30 +411,57 @@ def _sub(p, prefix):
 
 def decoder_layer(p, query, value, query_pos, reference_points, img_metas, pc_range,
                   cross='Deform3DCrossAttn', num_heads=8, num_points=4, attn_mask=None,
-                  depth_encode=False, return_parts=False, value_dtype='fp32'):
+                  depth_encode=False, return_parts=False, value_dtype='fp32',
+                  vis_mask=None, corners=None, relu_masks=None, dropout=None):
     """Post-norm DetrTransformerDecoderLayer (third-party mmdet/mmcv), order
     self_attn, norm, cross_attn, norm, ffn, norm (config :88-89; Appendix A.4).
-    return_parts (Deform3DCrossAttn only): also return the cross-attention's intermediates (mask, uv, ...)."""
+    return_parts (Deform3DCrossAttn only): also return the cross-attention's intermediates (mask, uv, ...) and the
+    pre-activations of the ReLUs ('pre_pe1', 'pre_pe4', 'pre_ffn').
+    Discontinuous decisions given from outside (Deform3DCrossAttn only; None: the oracle's own, bit-identical to the
+    call without them): vis_mask (B, N, Q, Hh, P) and corners (B, N, Q, Hh, L, P, 2) of the gather (sample_aggregate);
+    relu_masks {'pe1', 'pe4', 'ffn'}: the ReLU decisions of position_encoder's two stages and of the FFN hidden unit;
+    dropout: five sites, each (keep mask, p) or None - attention probabilities (B, heads, Q, Q), self-attention output,
+    cross-attention output, FFN hidden, FFN output ((Q, C) / (Q, FC)): kept entries scaled by 1 / (1 - p)."""
     c = query.shape[-1]
+    rm = relu_masks or {}
+    dr = [None] * 5 if dropout is None else list(dropout)
 
     def ln(x, i):
         return F.layer_norm(x, (c,), p[f'norms.{i}.weight'], p[f'norms.{i}.bias'])
-    x = multihead_self_attn(p, query, query_pos, num_heads, attn_mask, prefix='attentions.0.attn.')
+    x = multihead_self_attn(p, query, query_pos, num_heads, attn_mask, prefix='attentions.0.attn.',
+                            drop_attn=dr[0], drop_out=dr[1])
     x = ln(x, 0)
     cp = _sub(p, 'attentions.1.')
     parts = None
     if cross == 'Deform3DCrossAttn':
+        pe_masks = (rm['pe1'], rm['pe4']) if 'pe1' in rm else None
         x = deform3d_cross_attn(cp, x, value, query_pos, reference_points, img_metas, pc_range,
                                 num_heads, num_points, depth_encode, return_parts=return_parts,
-                                value_dtype=value_dtype)
+                                value_dtype=value_dtype, vis_mask=vis_mask, corners=corners,
+                                pe_relu_masks=pe_masks, drop_out=dr[2])
         if return_parts:
             x, parts = x
     else:
+        if vis_mask is not None or corners is not None or rm or dropout is not None:
+            raise ValueError('decisions given from outside: Deform3DCrossAttn only')
         x = detr3d_cross_atten(cp, x, value, query_pos, reference_points, img_metas, pc_range,
                                num_points)
     x = ln(x, 1)
-    x = ffn(p, x)
+    pre = [] if parts is not None else None
+    x = ffn(p, x, relu_mask=rm.get('ffn'), drop_hidden=dr[3], drop_out=dr[4], pre=pre)
+    if parts is not None:
+        pe_pre = parts.pop('pe_pre')
+        parts.update(pre_pe1=pe_pre[0], pre_pe4=pe_pre[1], pre_ffn=pre[0])
     return (ln(x, 2), parts) if return_parts else ln(x, 2)
+
+
+def refine_points(reg_branch, out, reference_points):
+    """Reference-point refinement after a decoder layer, detr3d_transformer.py:199-214: the refined points are DETACHED."""
+    tmp = reg_branch(out.permute(1, 0, 2))                                  # :199-202
+    new = torch.zeros_like(reference_points)
+    new[..., :2] = tmp[..., :2] + inverse_sigmoid(reference_points[..., :2])
+    new[..., 2:3] = tmp[..., 4:5] + inverse_sigmoid(reference_points[..., 2:3])
+    return new.sigmoid().detach()                                           # :212-214
 
 
 def decoder(layer_params, query, value, query_pos, reference_points, img_metas, pc_range,
@@ -381,11 +473,7 @@ def decoder(layer_params, query, value, query_pos, reference_points, img_metas, 
     for lid, p in enumerate(layer_params):
         out = decoder_layer(p, out, value, query_pos, reference_points, img_metas, pc_range, **kw)
         if reg_branches is not None:
-            tmp = reg_branches[lid](out.permute(1, 0, 2))                   # :199-202
-            new = torch.zeros_like(reference_points)
-            new[..., :2] = tmp[..., :2] + inverse_sigmoid(reference_points[..., :2])
-            new[..., 2:3] = tmp[..., 4:5] + inverse_sigmoid(reference_points[..., 2:3])
-            reference_points = new.sigmoid().detach()                       # :212-214
+            reference_points = refine_points(reg_branches[lid], out, reference_points)
         inter.append(out)
         inter_ref.append(reference_points)
     return torch.stack(inter), torch.stack(inter_ref)

@@ -150,7 +150,8 @@ def test_six_layer_call_900q_24cams_student_and_teacher_queries_step_the_oracle(
 
 def test_training_forward_900q_24cams_six_layers_steps_the_oracle(timed):
     """fused_train.DecoderTrainFunction's forward (autograd on, eval mode, reg branches on): its out_all / ref_all stepped against
-    the oracle.  The backward is pinned per module elsewhere (tests/test_timed_size_parity_gpu.py)."""
+    the oracle.  The backward of the same call is stepped layer by layer against the fp64 oracle in
+    tests/test_train_layers_gpu.py."""
     before = fused_train.CALLS[0]
     with torch.enable_grad(), MaskSpy() as spy:
         states, init_ref, refs = timed.tr(timed.feats_d, timed.qe_d, reg_branches=timed.regs, img_metas=timed.metas)
