@@ -113,6 +113,9 @@ SIGNATURES = {
                                   _vp, _vp]),
     'gd4d_adamw_flat_workspace_bytes': (_c.c_size_t, []),
     'gd4d_adamw_flat': (_i, [_vp] * 6 + [_c.c_size_t, _c.c_int64] + [_f] * 6 + [_vp]),
+    'gd4d_adamw_recipe_flat_workspace_bytes': (_c.c_size_t, []),
+    'gd4d_adamw_recipe_flat_state_bytes': (_c.c_size_t, []),
+    'gd4d_adamw_recipe_flat': (_i, [_vp] * 5 + [_c.c_size_t, _vp, _c.c_size_t, _c.c_int64, _vp, _vp, _vp, _i, _vp]),
     'gd4d_chain_weight_image_bytes': (_c.c_size_t, [_i, _i]),
     'gd4d_chain_weight_image': (_i, [_vp, _i, _i, _vp, _vp]),
     'gd4d_chain_weight_image_exact_bytes': (_c.c_size_t, [_i, _i]),

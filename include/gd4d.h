@@ -770,6 +770,73 @@ int gd4d_adamw_flat(float* params, const float* grads, float* exp_avg, float* ex
                     size_t workspace_bytes, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                     float max_norm, void* stream);
 
+/* gd4d_adamw_recipe_flat - gd4d_adamw_flat with everything else a training run changes from step to step on the device as well, so ONE
+ * captured step replays correctly for the whole run: the learning-rate schedule (lr_config), the loss scale of fp16 training and its
+ * skip-on-overflow (fp16 = dict(loss_scale=512.) -> mmcv's Fp16OptimizerHook, apis/mmdet_distill_train.py:119-122), and per-group
+ * multipliers (paramwise_cfg custom_keys, ...fullset_ceph.py:208-211).  Still two launches whatever the number of parameters / groups:
+ *   pass 1  per-block sums of squares of g / scale (gd4d_adamw_flat's order) and a per-block "saw a non-finite g / scale" flag; one
+ *           thread evaluates the schedule for this iteration in double, stores it as fp32, advances `iteration`, and latches the scale
+ *           (scale_in_use) and Adam's t this step would be (step_in_flight);
+ *   pass 2  every block combines sums and flags in the same order (every block - and, after an all-reduce, every rank - decides alike);
+ *           non-finite: params, exp_avg, exp_avg_sq and optimizer_steps stay as they were, skipped_steps advances; else
+ *           g = g / scale * min(1, max_norm / (norm + 1e-6)) and gd4d_adamw_flat's update with lr * lr_mult, weight_decay * decay_mult of
+ *           the element's range, optimizer_steps advances.  zero_grads: the gradients read are overwritten with zeros (skipped steps
+ *           too).  One thread then updates the loss scale as torch.amp.GradScaler.update does: static - reset to init_scale; dynamic -
+ *           x backoff_factor on overflow, x growth_factor after growth_interval clean steps unless the product is not finite.
+ * No word a step's blocks read is written by that step's pass 2: the new scale is visible to the NEXT step only.
+ * With scale 1, policy fixed and one range with multipliers 1 the arithmetic is gd4d_adamw_flat's, bit for bit.
+ *
+ * The schedule, restated from mmcv 1.x's LrUpdaterHook (it = iterations finished before this one, ep = it / iters_per_epoch, integer):
+ *   regular = base_lr                                                         GD4D_LR_FIXED
+ *           = end_lr + 0.5 (base_lr - end_lr) (cos(pi f) + 1)                 GD4D_LR_COSINE  (end_lr = base_lr * min_lr_ratio, or min_lr)
+ *             f = ep / max_epochs (by_epoch) | it / max_iters
+ *           = base_lr * gamma^e                                               GD4D_LR_STEP
+ *             e = progress / step_every (step_every > 0) | number of milestones <= progress;  progress = ep (by_epoch) | it
+ *   lr      = regular                                                         it >= warmup_iters or GD4D_WARMUP_NONE
+ *           = regular * (1 - (1 - it / warmup_iters) (1 - warmup_ratio))      GD4D_WARMUP_LINEAR
+ *           = regular * warmup_ratio                                          GD4D_WARMUP_CONSTANT
+ *           = regular * warmup_ratio^(1 - it / warmup_iters)                  GD4D_WARMUP_EXP
+ *
+ * ranges: 1 .. GD4D_RECIPE_MAX_RANGES ranges covering [0, n) in order without gap or overlap, every begin a multiple of 4 (a 16-byte
+ * quad never straddles two ranges: FlatGradAllReducer(align=4) lays parameters out so); `ranges` is the host copy the call validates,
+ * `ranges_dev` the same table in device memory (8-byte aligned) that pass 2 searches - once per change of range, not per element.
+ * state: gd4d_recipe_state on the device, 8-byte aligned; before the first step all zero except loss_scale = init_scale.
+ * params / grads / exp_avg / exp_avg_sq as gd4d_adamw_flat (grads is written when zero_grads is set). */
+#define GD4D_RECIPE_MAX_RANGES 1024
+#define GD4D_RECIPE_MAX_MILESTONES 16
+enum { GD4D_LR_FIXED = 0, GD4D_LR_COSINE = 1, GD4D_LR_STEP = 2 };
+enum { GD4D_WARMUP_NONE = 0, GD4D_WARMUP_CONSTANT = 1, GD4D_WARMUP_LINEAR = 2, GD4D_WARMUP_EXP = 3 };
+typedef struct gd4d_recipe_range {     /* 24 bytes */
+  int64_t begin, end;                  /* [begin, end) in elements of the flat buffer */
+  float lr_mult, decay_mult;
+} gd4d_recipe_range;
+typedef struct gd4d_recipe_state {     /* 64 bytes of device memory; counters are exact integers */
+  int64_t iteration;                   /*  0  iterations finished (applied + skipped): the schedule's clock */
+  int64_t optimizer_steps;             /*  8  Adam's t: updates applied */
+  int64_t skipped_steps;               /* 16  steps skipped for non-finite gradients */
+  int64_t step_in_flight;              /* 24  optimizer_steps + 1 as pass 1 latched it */
+  float loss_scale;                    /* 32  what the NEXT backward is seeded with */
+  float scale_in_use;                  /* 36  what the last step unscaled with */
+  float lr;                            /* 40  the base rate the last step used (before lr_mult) */
+  float grad_norm;                     /* 44  L2 norm of the unscaled gradients of the last step, before clipping */
+  int32_t found_inf;                   /* 48  the last step saw a non-finite gradient (and was skipped) */
+  int32_t growth_tracker;              /* 52  clean steps since the scale last changed (dynamic scale) */
+  int32_t reserved[2];
+} gd4d_recipe_state;
+typedef struct gd4d_recipe_config {    /* host memory; copied into the launches */
+  double base_lr, end_lr, gamma, warmup_ratio;
+  double init_scale, growth_factor, backoff_factor;          /* growth_factor > 1, 0 < backoff_factor < 1 (checked also when static) */
+  int64_t iters_per_epoch, max_epochs, max_iters, warmup_iters, step_every;
+  int64_t milestones[GD4D_RECIPE_MAX_MILESTONES];            /* ascending */
+  int32_t policy, by_epoch, warmup, n_milestones, dynamic_scale, growth_interval, zero_grads, reserved;
+  float beta1, beta2, eps, weight_decay, max_norm, reserved_f; /* max_norm <= 0: no clipping */
+} gd4d_recipe_config;
+size_t gd4d_adamw_recipe_flat_workspace_bytes(void);
+size_t gd4d_adamw_recipe_flat_state_bytes(void);
+int gd4d_adamw_recipe_flat(float* params, float* grads, float* exp_avg, float* exp_avg_sq, void* state, size_t state_bytes,
+                           void* workspace, size_t workspace_bytes, int64_t n, const gd4d_recipe_config* config,
+                           const gd4d_recipe_range* ranges, const gd4d_recipe_range* ranges_dev, int n_ranges, void* stream);
+
 /* gd4d_xcd_placement_probe - out[b] = the XCC (XCD) id workgroup b of a `blocks`-workgroup launch ran on: the self-test behind
  * SIGNAL / WAIT above (expected: out[b] == out[b % 8]). */
 int gd4d_xcd_placement_probe(int32_t* out, int blocks, void* stream);
