@@ -6,6 +6,7 @@ Build it with `python -c "import __graft_entry__ as g; g.build()"` or
 """
 import ctypes
 import os
+import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GD4D_LIB_PATH') or os.path.join(_HERE, 'libgd4d.so')   # env override: dev A/B builds
@@ -140,9 +141,35 @@ SIGNATURES = {
     'gd4d_lsa_dense_workspace_bytes': (_c.c_size_t, [_i] * 4),
     'gd4d_lsa_dense_fwd': (_i, [_vp] * 5 + [_c.c_size_t] + [_i] * 5 + [_vp]),
     'gd4d_distill_loss_fwd_bwd': (_i, [_vp] * 10 + [_i] * 7 + [_f, _f, _vp]),
+    'gd4d_request_step_bytes': (_c.c_size_t, []),
+    'gd4d_decoder_request_create': (_i, [_vp, _i, _i, _vp]),
+    'gd4d_decoder_request_run': (_i, [_vp, _vp, _i, _vp, _vp]),
+    'gd4d_decoder_request_destroy': (_i, [_vp]),
+    'gd4d_decoder_request_describe': (_c.c_char_p, [_vp, _i]),
 }
 
 _lib = None
+_recording = threading.local()        # .rec: the StepRecorder of THIS thread (another thread's requests keep launching)
+
+
+class recording:
+    """`with _lib.recording(rec):` - load() hands out `rec` (ops.StepRecorder) instead of the library, in this thread only: the
+    wrappers in ops.py run as they always do, and each launching entry point they call becomes a step of a request program instead
+    of a launch."""
+
+    def __init__(self, rec):
+        self.rec, self.prev = rec, None
+
+    def __enter__(self):
+        self.prev, _recording.rec = recorder(), self.rec
+        return self.rec
+
+    def __exit__(self, *exc):
+        _recording.rec = self.prev
+
+
+def recorder():
+    return getattr(_recording, 'rec', None)
 
 
 class Gd4dError(RuntimeError):
@@ -152,6 +179,9 @@ class Gd4dError(RuntimeError):
 def load():
     """dlopen libgd4d.so once; raises Gd4dError if it is absent or has the wrong ABI."""
     global _lib
+    rec = recorder()
+    if rec is not None:
+        return rec
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):

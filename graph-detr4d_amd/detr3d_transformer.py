@@ -385,6 +385,15 @@ class Detr3DTransformerDecoder(TransformerLayerSequence):
         output = query
         intermediate, intermediate_reference_points = [], []
         from . import fused_decoder
+        asked = kwargs.pop(fused_decoder.REQUEST_OK_KEY, None)        # (Detr3DTransformer.forward's note to this call only: never handed on)
+        if not args and fused_decoder.request_enabled():
+            if asked is not None:
+                kwargs[fused_decoder.REQUEST_OK_KEY] = asked
+            # GD4D_REQUEST=1, an eager call that ends in the single-stream loop: the whole request from ONE host call
+            done = fused_decoder.request_forward(self, query, reference_points, reg_branches, kwargs)
+            kwargs.pop(fused_decoder.REQUEST_OK_KEY, None)
+            if done is not None:
+                return done
         fused = not args and kwargs.get('key') is None and kwargs.get('query_pos') is not None and 'img_metas' in kwargs \
             and kwargs.get('key_padding_mask') is None and kwargs.get('query_key_padding_mask') is None \
             and fused_decoder.applicable(self, query, kwargs.get('value'), reference_points, reg_branches,
@@ -521,7 +530,15 @@ class Detr3DTransformer(nn.Module):
         from . import fused_decoder
         own_late = None
         fast = fused_decoder.fast_input(self, query_embed, mlvl_feats)
-        if fast and kwargs.get(Fn.LATE_VALUES_KEY) is None and kwargs.get(Fn.VALUE_CACHE_KEY) is None:
+        covered = None
+        if fast and fused_decoder.request_enabled():
+            # GD4D_REQUEST=1 and a call the decoder's request program covers: the copy is a step of that program, not forked here
+            dec_kwargs = dict(kwargs, key=None, value=mlvl_feats, query_pos=query_pos.unsqueeze(1))
+            covered = fused_decoder.request_covers(self.decoder, query.unsqueeze(1), None, reg_branches, dec_kwargs)
+            if covered is not None:
+                kwargs = dict(kwargs)
+                kwargs[fused_decoder.REQUEST_OK_KEY] = covered
+        if fast and covered is None and kwargs.get(Fn.LATE_VALUES_KEY) is None and kwargs.get(Fn.VALUE_CACHE_KEY) is None:
             # the channels-last copy of the pyramid needs nothing but the pyramid: fork it first, before the query side
             cross = [a for layer in self.decoder.layers for a in layer.attentions if getattr(a, 'operation_name', '') == 'cross_attn']
             if cross and all(isinstance(a, Deform3DCrossAttn) for a in cross) and Fn.LateValues.applicable(cross, mlvl_feats):

@@ -629,6 +629,33 @@ class ValuePipeline:
         self.ready.clear()
 
 
+def _wait_stream(waiter, other):
+    """waiter.wait_stream(other) - or, while a request program is being recorded (ops.StepRecorder), its two steps."""
+    rec = _lib.recorder()
+    if rec is None:
+        waiter.wait_stream(other)
+    else:
+        rec.wait_event(waiter, rec.record_event(other))
+
+
+def _record_event(stream):
+    """A new event recorded on `stream` (recording: the event's id in the request program)."""
+    rec = _lib.recorder()
+    if rec is not None:
+        return rec.record_event(stream)
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    return ev
+
+
+def _wait_event(stream, event):
+    rec = _lib.recorder()
+    if rec is None:
+        stream.wait_event(event)
+    else:
+        rec.wait_event(stream, event)
+
+
 LATE_VALUES_KEY = '_gd4d_late_values'
 AGG_DEFAULT = 'sliced'
 
@@ -672,18 +699,17 @@ class LateValues:
             self.pyramid = ops.PyramidView.channels_last_levels(list(value))
             if coarse_for and self.coarse_setup(coarse_for):
                 self.side = _companion_stream(_SIDE_STREAMS, dev)
-                self.side.wait_stream(self.main)
+                _wait_stream(self.side, self.main)
                 with torch.cuda.stream(self.side):
                     self._project_first(coarse_for[0])
-                    self.event = torch.cuda.Event()
-                    self.event.record(self.side)
+                    self.event = _record_event(self.side)
                 self.coarse.rows.record_stream(self.main)
             return
         self.mode = os.environ.get('GD4D_AGG', AGG_DEFAULT)
         if self.mode == 'rows' and value[0].shape[0] != 1:
             self.mode = 'sliced'                     # B > 1: the row % B pairing lives in the plan kernel
         self.side = _companion_stream(_SIDE_STREAMS, dev)
-        self.side.wait_stream(self.main)             # the pyramid was produced on the main stream
+        _wait_stream(self.side, self.main)             # the pyramid was produced on the main stream
         with torch.cuda.stream(self.side):
             # GD4D_COPY_CUS: compute units of the persistent copy (default 3/4 of the device: the query side of the first layer and the
             # first projection of the coarse levels run on the rest, underneath it - round 6, samples/s one request / two in flight:
@@ -715,8 +741,7 @@ class LateValues:
                     self.pyramid = ops.PyramidView.slice_planar(self.cl, self.shapes)
             else:
                 self.cl, _ = ops.pyramid_channels_last_fwd(src, max_cus=copy_cus, out_dtype=dtype)
-            self.event = torch.cuda.Event()
-            self.event.record(self.side)
+            self.event = _record_event(self.side)
         # allocated under the side stream, read by kernels of the main stream: tell the allocator, so that the block is
         # not handed out again (to a side-stream allocation) while those kernels are still queued
         self.cl.record_stream(self.main)
@@ -793,7 +818,7 @@ class LateValues:
         made = [t for t in (self.cl, None if self.coarse is None else self.coarse.rows) if t is not None]   # what the side stream wrote
         cur = torch.cuda.current_stream(made[0].device)
         if cur.cuda_stream not in self.waited:
-            cur.wait_event(self.event)
+            _wait_event(cur, self.event)
             self.waited.add(cur.cuda_stream)
             if cur.cuda_stream != self.main.cuda_stream:
                 for t in made:
@@ -847,7 +872,7 @@ class LateValues:
 
     def finish(self):
         if self.side is not None:
-            self.main.wait_stream(self.side)         # join (keeps a graph capture well-formed)
+            _wait_stream(self.main, self.side)         # join (keeps a graph capture well-formed)
 
 
 def pipeline_groups(spec, n):

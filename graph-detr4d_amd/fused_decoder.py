@@ -15,11 +15,14 @@ Same arithmetic as the module path (fp32 MFMA products, two-pass LayerNorm), oth
 reductions only.  Used by Detr3DTransformerDecoder.forward when every layer has this shape, batch 1, fp32, no autograd
 (GD4D_FUSED_DECODER=0 disables it); anything else takes the generic path.
 """
+import ctypes
 import os
+import weakref
 
 import torch
 import torch.nn as nn
 
+from . import _lib
 from . import functional as Fn
 from . import ops
 from .deform3d_cross_attn import Deform3DCrossAttn
@@ -317,7 +320,7 @@ def run_single(decoder, query, query_pos, value, reference_points, reg_branches,
             else:
                 pending = (lins, x3.view(q, c), ref, new_ref)
         elif return_intermediate or last:
-            ref_all[slot].copy_(ref)
+            ops.copy_into(ref_all[slot], ref)
         if pos_late:
             # position_encoder(l) on the refined points (in global memory since the dual launch), beside chain B'.  The
             # SIGNALling program goes FIRST: its workgroups are dispatched before the waiting ones (gd4d.h).
@@ -327,7 +330,7 @@ def run_single(decoder, query, query_pos, value, reference_points, reg_branches,
             ops.row_chain_fwd(prog, q, guest=guest)
         keep += [o, x1, cam, off, att, agg_raw, wsum, pos_feat, x]
         x = x3.view(q, c)
-    if pos_late:
+    if pos_late and _lib.recorder() is None:
         ops.poll_handoff(dev)                                # non-blocking (eager calls); a graph's owner: ops.check_handoff()
     del keep
     return out_all, ref_all
@@ -504,3 +507,185 @@ def run(decoder, query, query_pos, value, reference_points, reg_branches, img_me
         main.wait_stream(aux)
     del keep
     return out_all, ref_all
+
+
+# ---- the request program: one host call per eager request -------------------------------------------------------------------
+# Switches that select the schedule run_single / LateValues build: part of a program's key.
+ROUTE_SWITCHES = ('GD4D_POS_ENCODER', 'GD4D_COARSE', 'GD4D_FIRST_PROJ', 'GD4D_MHA_FP32', 'GD4D_AGG', 'GD4D_PLAN', 'GD4D_PROJECT',
+                  'GD4D_COPY_CUS', 'GD4D_COARSE_MAX_ROWS', 'GD4D_QUERY_ORDER')
+_PROGRAMS = weakref.WeakKeyDictionary()          # decoder -> {key: RequestProgram}
+_B_QUERY, _B_POS, _B_REF, _B_L2I, _B_IMG_H, _B_IMG_W, _B_MASK, _B_OUT, _B_REFS, _B_LEVEL0 = range(10)
+
+
+def request_enabled():
+    """GD4D_REQUEST=1 (default 0) and no capture in progress: a captured graph keeps the launches of the Python loop, one by one."""
+    return os.environ.get('GD4D_REQUEST', '0') == '1' and _lib.recorder() is None and not torch.cuda.is_current_stream_capturing()
+
+
+class RequestProgram:
+    """The launch sequence of one Detr3DTransformerDecoder.forward - pyramid copy and first coarse projection on the side stream, query
+    order, the loop of run_single, the join - recorded ONCE from the code that issues it eagerly (ops.StepRecorder stands in for the
+    library while decoder.forward runs: same descriptors, weight images, hand-off flags, guests, LateValues set-up) and kept on the C side
+    (gd4d_decoder_request_create).  run() re-issues it with one ctypes call: the stamp check, functional.lidar2img_device, two output
+    allocations and the bindings array are all that is left per request.
+
+    What two requests may differ in is bound per call: the level tensors, query / query_pos (strided column slices allowed), the
+    reference points, the lidar2img buffer, img_h / img_w, the attention mask, the outputs (allocated per call: the caller owns them).
+    Every intermediate - qkv, K / V planes, x1, camera / offset / attention logits, plans, aggregates, position features, the
+    slice-planar copy, the coarse rows - lives in the program's private memory pool.
+
+    One program serves ONE request at a time on ONE stream: it is keyed by (device, stream, request slot - functional.slot_key -, shapes
+    and strides, level layout, mask, route switches - the environment ones and ops.ALL_EXACT, hand-offs in use, value storage type),
+    so a second stream or slot gets a program (and intermediates) of its own; recording is per thread (_lib.recording).  It
+    holds values derived from parameters (weight images, stacked weights, value_proj images): it stands under the one rule of
+    ops.invalidate_chain_images (an ops._Stamp over the decoder's and the reg branches' parameters) and is recorded again before
+    the next run when that no longer holds."""
+
+    def __init__(self, decoder, query, query_pos, reference_points, reg_branches, value, img_metas, mask):
+        dev = query.device
+        self.device = dev
+        self.sources = list(decoder.parameters()) + ([] if reg_branches is None else [p for b in reg_branches for p in b.parameters()])
+        # the reg branches this program was recorded on, by identity (their weights are fixed addresses of its steps): a weak
+        # reference where the container allows one (an id() could come back on another object), else the container itself
+        try:
+            self.regs = None if reg_branches is None else weakref.ref(reg_branches)
+        except TypeError:
+            self.regs = (lambda held: (lambda: held))(reg_branches)
+        self.stamp = ops._Stamp(self.sources)
+        ops.handoff_enabled(dev, 'GD4D_POS_ENCODER')                  # (the placement probe reads back: before, not inside, the recording)
+        main = torch.cuda.current_stream(dev)
+        lib = _lib.load()
+        Fn.lidar2img_device(img_metas, query)                         # (its persistent buffer, if new, outlives this program's pool)
+        self.pool = torch.cuda.MemPool()
+        rec = ops.StepRecorder(lib, main.cuda_stream)
+        kwargs = dict(key=None, value=value, query_pos=query_pos, img_metas=img_metas)
+        if mask is not None:
+            kwargs['attn_masks'] = [mask, None]
+        with torch.cuda.use_mem_pool(self.pool, device=dev), _lib.recording(rec):
+            outs, refs = decoder(query, reference_points=reference_points, reg_branches=reg_branches, **kwargs)
+        lead = () if decoder.return_intermediate else (1,)           # (forward hands out [0] of the stacked outputs then)
+        self.out_shape, self.ref_shape = lead + tuple(outs.shape), lead + tuple(refs.shape)
+        tensors = {_B_QUERY: query, _B_POS: query_pos, _B_REF: reference_points, _B_OUT: outs, _B_REFS: refs}
+        if mask is not None:
+            tensors[_B_MASK] = mask
+        tensors.update({_B_LEVEL0 + i: v for i, v in enumerate(value)})
+        self.nbindings = _B_LEVEL0 + len(value)
+        steps, keep = rec.steps(tensors, {'lidar2img': _B_L2I, 'img_h': _B_IMG_H, 'img_w': _B_IMG_W})
+        handle = ctypes.c_void_p()
+        _lib.check(lib.gd4d_decoder_request_create(ctypes.addressof(steps), len(steps), self.nbindings, ctypes.addressof(handle)),
+                   'gd4d_decoder_request_create')
+        del keep
+        self.handle, self.nsteps, self._lib = handle, len(steps), lib
+        self.main, self.side = main.cuda_stream, rec.side
+        self.bind = (ops.RequestBinding * self.nbindings)()
+        self.polls = ops.handoff_enabled(dev, 'GD4D_POS_ENCODER')
+
+    def valid(self, reg_branches=None):
+        return self.handle is not None and (self.regs is None or self.regs() is reg_branches) and self.stamp.valid(self.sources)
+
+    def describe(self):
+        return [self._lib.gd4d_decoder_request_describe(self.handle, i).decode() for i in range(self.nsteps)]
+
+    def run(self, query, query_pos, reference_points, value, img_metas, mask):
+        b, dev = self.bind, self.device
+        lidar2img = Fn.lidar2img_device(img_metas, query)
+        img_h, img_w = Fn.img_hw(img_metas)
+        out_all = torch.empty(self.out_shape, device=dev, dtype=torch.float32)
+        ref_all = torch.empty(self.ref_shape, device=dev, dtype=torch.float32)
+        b[_B_QUERY].ptr, b[_B_POS].ptr, b[_B_REF].ptr = query.data_ptr(), query_pos.data_ptr(), reference_points.data_ptr()
+        b[_B_L2I].ptr, b[_B_IMG_H].scalar, b[_B_IMG_W].scalar = lidar2img.data_ptr(), img_h, img_w
+        b[_B_MASK].ptr = None if mask is None else mask.data_ptr()
+        b[_B_OUT].ptr, b[_B_REFS].ptr = out_all.data_ptr(), ref_all.data_ptr()
+        for i, v in enumerate(value):
+            b[_B_LEVEL0 + i].ptr = v.data_ptr()
+        code = _lib.load().gd4d_decoder_request_run(self.handle, b, self.nbindings, self.main, self.side)
+        _lib.check(code, 'gd4d_decoder_request_run')
+        if self.polls:
+            ops.poll_handoff(dev)
+        return out_all, ref_all
+
+    def close(self):
+        """Destroy the C side; the intermediates go back to the allocator once the stream has run what was enqueued on them."""
+        if self.handle is not None:
+            torch.cuda.synchronize(self.device)
+            self._lib.gd4d_decoder_request_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _request_mask(attn_masks):
+    """(eligible, the self-attention mask as the attention core takes it without a conversion launch)."""
+    if attn_masks is None:
+        return True, None
+    m = attn_masks if torch.is_tensor(attn_masks) else attn_masks[0]
+    if m is None:
+        return True, None
+    if m.dim() != 2 or not m.is_contiguous() or m.dtype not in (torch.bool, torch.uint8, torch.float32):
+        return False, None
+    return True, m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+REQUEST_OK_KEY = '_gd4d_request_ok'
+
+
+def request_covers(decoder, query, reference_points, reg_branches, kwargs):
+    """Whether a Detr3DTransformerDecoder.forward with these arguments is one a RequestProgram covers: (mask,) - the self-attention
+    mask as the program binds it - or None.  Needs the single-stream loop (takes_single_stream_loop), the aggregate-then-project value
+    path, levels that are ALL dense NCHW or ALL channels-last (a mixed list is copied by LateValues: a torch copy is no step), and
+    nothing prepared by the caller (no LateValues / projected values handed in).  reference_points None: not made yet
+    (Detr3DTransformer.forward asks before initial_reference, whose output is dense fp32)."""
+    if set(kwargs) - {'key', 'value', 'query_pos', 'img_metas', 'attn_masks', 'key_padding_mask', 'query_key_padding_mask', REQUEST_OK_KEY}:
+        return None
+    value, query_pos, masks = kwargs.get('value'), kwargs.get('query_pos'), kwargs.get('attn_masks')
+    if kwargs.get('key') is not None or query_pos is None or 'img_metas' not in kwargs or kwargs.get('key_padding_mask') is not None \
+            or kwargs.get('query_key_padding_mask') is not None:
+        return None
+    ref = query_pos.transpose(0, 1)[..., :3] if reference_points is None else reference_points      # (a stand-in of the right shape)
+    if not takes_single_stream_loop(decoder, query, value, ref, reg_branches, masks, query_pos):
+        return None
+    ok, mask = _request_mask(masks)
+    cross = [l.attentions[1] for l in decoder.layers]
+    if not ok or query.device.index != torch.cuda.current_device() or not Fn.LateValues.applicable(cross, value) \
+            or query_pos.dtype != torch.float32 or query_pos.shape != query.shape or query_pos.stride(-1) != 1 or query.stride(-1) != 1 \
+            or not (all(v.is_contiguous() for v in value) or all(ops.PyramidView.is_channels_last_level(v) for v in value)):
+        return None
+    return (mask,)
+
+
+def request_forward(decoder, query, reference_points, reg_branches, kwargs):
+    """Detr3DTransformerDecoder.forward through a RequestProgram, or None when the call is not one the program covers (request_covers;
+    the caller then takes the path it always took).  kwargs[REQUEST_OK_KEY]: request_covers' answer for this very call, when
+    Detr3DTransformer.forward has asked already."""
+    covered = kwargs.get(REQUEST_OK_KEY)
+    if covered is None:
+        covered = request_covers(decoder, query, reference_points, reg_branches, kwargs)
+    if covered is None or not reference_points.is_contiguous() or reference_points.dtype != torch.float32:
+        return None
+    mask, value, query_pos, img_metas = covered[0], kwargs['value'], kwargs['query_pos'], kwargs['img_metas']
+    dev = query.device
+    # everything that selects the schedule run_single / LateValues build and is not a parameter: shapes and layouts, the environment
+    # switches, and the selectors that are NOT environment variables - ops.ALL_EXACT (`with ops.all_exact():`), whether the device's
+    # steps use hand-offs (a time-out turns them off: ops.check_handoff), the value storage type of the cross-attention modules
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, Fn.slot_key(dev), tuple(query.shape), query.stride(), query_pos.stride(),
+           tuple((tuple(v.shape), v.stride(), v.dtype) for v in value), None if mask is None else (tuple(mask.shape), mask.dtype),
+           reg_branches is None, decoder.return_intermediate, len(img_metas), tuple(os.environ.get(k) for k in ROUTE_SWITCHES),
+           bool(ops.ALL_EXACT[0]), ops.handoff_enabled(dev, 'GD4D_POS_ENCODER'), decoder.layers[0].attentions[1].value_dtype)
+    table = _PROGRAMS.get(decoder)
+    if table is None:
+        table = _PROGRAMS[decoder] = {}
+    prog = table.get(key)
+    if prog is None or not prog.valid(reg_branches):
+        if prog is not None:
+            table.pop(key).close()
+        while len(table) >= 8:                                # (shapes come and go in long-lived processes)
+            table.pop(next(iter(table))).close()
+        prog = table[key] = RequestProgram(decoder, query, query_pos, reference_points, reg_branches, value, img_metas, mask)
+    outs, refs = prog.run(query, query_pos, reference_points, value, img_metas, mask)
+    if decoder.return_intermediate:
+        return outs, refs
+    return outs[0], refs[0]

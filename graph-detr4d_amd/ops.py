@@ -2516,6 +2516,270 @@ def mha_core_presplit_fwd(q, kv, num_heads, attn_mask=None, want_lse=False, drop
     return (out, lse) if want_lse else out
 
 
+class RequestRef(ctypes.Structure):
+    """gd4d_request_ref (include/gd4d.h)."""
+    _fields_ = [('binding', ctypes.c_int32), ('reserved', ctypes.c_int32), ('value', ctypes.c_int64)]
+
+
+class RequestPatch(ctypes.Structure):
+    """gd4d_request_patch (include/gd4d.h)."""
+    _fields_ = [('table', ctypes.c_int32), ('binding', ctypes.c_int32), ('offset', ctypes.c_int64), ('add', ctypes.c_int64)]
+
+
+class RequestBinding(ctypes.Union):
+    """gd4d_request_binding (include/gd4d.h)."""
+    _fields_ = [('ptr', ctypes.c_void_p), ('scalar', ctypes.c_double)]
+
+
+class RequestStep(ctypes.Structure):
+    """gd4d_request_step (include/gd4d.h)."""
+    _fields_ = [('kind', ctypes.c_int32), ('side', ctypes.c_int32), ('event', ctypes.c_int32), ('npatches', ctypes.c_int32),
+                ('nops_a', ctypes.c_int32), ('nops_b', ctypes.c_int32), ('fbind', ctypes.c_int32 * 2),
+                ('prog_a', ctypes.c_void_p), ('prog_b', ctypes.c_void_p), ('guest', ctypes.c_void_p), ('patches', ctypes.c_void_p),
+                ('p', RequestRef * 10), ('i', ctypes.c_int32 * 10), ('l', ctypes.c_int64 * 2), ('f', ctypes.c_float * 2),
+                ('table', ctypes.c_void_p * 5), ('table_bytes', ctypes.c_int64 * 5)]
+
+
+(REQ_ROW_CHAIN, REQ_ROW_CHAIN2, REQ_ROW_CHAIN_GUEST, REQ_MHA_CORE, REQ_MHA_PRESPLIT, REQ_PLAN, REQ_AGG_COARSE, REQ_AGG_ITEMS,
+ REQ_AGG_SLICED, REQ_SLICE_PLANAR, REQ_VALUE_PROJ_GUEST, REQ_QUERY_ORDER, REQ_EVENT_RECORD, REQ_STREAM_WAIT, REQ_COPY) = range(1, 16)
+
+
+def _addr(a):
+    """The address in a pointer argument as the wrappers above hand it to ctypes: None, c_void_p or int."""
+    if a is None:
+        return 0
+    if isinstance(a, int):
+        return a
+    return a.value or 0
+
+
+def tensor_extent(t):
+    """[lo, hi): the bytes a strided tensor can touch."""
+    span = sum((n - 1) * st for n, st in zip(t.shape, t.stride())) + 1 if t.numel() else 0
+    return t.data_ptr(), t.data_ptr() + span * t.element_size()
+
+
+class _Pending:
+    """One recorded enqueue, addresses still raw (StepRecorder.steps resolves them against the bindings)."""
+
+    def __init__(self, kind, side, **kw):
+        self.kind, self.side, self.event = kind, side, 0
+        self.prog_a = self.prog_b = self.guest = None
+        self.p, self.i, self.l, self.f, self.tables, self.special, self.fbind = [], [], [], [], [], {}, [-1, -1]
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+_CHAIN_POINTERS = ('p0', 'p1', 'p2', 'gout', 'p3')
+
+
+class StepRecorder:
+    """What _lib.load() returns inside `with _lib.recording(rec)`: the library with every launching entry point of the decoder request
+    turned into a step record.  The wrappers of this file - and so fused_decoder.run_single, functional.LateValues, the chain_*
+    descriptors, the weight images, the hand-off flags - run unchanged; what they would have enqueued is what gd4d_decoder_request_run
+    enqueues later (one description of the schedule).  Entry points that build a value kept from parameters (weight images) or probe the
+    device run at once, as always; a launching entry point without a step kind raises.  Tensors the recorded code allocates must stay
+    where they are for the life of the program: the caller records under a private memory pool that it keeps."""
+
+    RUN_NOW = {'gd4d_chain_weight_image', 'gd4d_chain_weight_image_exact', 'gd4d_value_proj_image', 'gd4d_xcd_placement_probe'}
+
+    def __init__(self, lib, main_stream):
+        self._lib, self.main, self.side = lib, int(main_stream), None
+        self.pending, self.events = [], 0
+
+    def __getattr__(self, name):
+        if name.startswith('gd4d_'):
+            fn = getattr(self._lib, name)
+            if name in self.RUN_NOW or not fn.argtypes or name.endswith('_bytes') or fn.restype is not ctypes.c_int:
+                return fn
+            raise _lib.Gd4dError(f'{name}: a request program (GD4D_REQUEST=1) has no step for this entry point - the route '
+                                 'switches in force select a schedule it does not cover')
+        raise AttributeError(name)
+
+    # ---- streams and events -------------------------------------------------------------------------------------------
+    def _side(self, handle):
+        handle = int(_addr(handle))
+        if handle == self.main:
+            return 0
+        if self.side not in (None, handle):
+            raise _lib.Gd4dError('a request program runs on two streams: the caller\'s and one side stream')
+        self.side = handle
+        return 1
+
+    def record_event(self, stream):
+        """Event.record(stream): returns the event's id."""
+        if self.events >= 64:
+            raise _lib.Gd4dError('a request program holds at most 64 events')
+        self.pending.append(_Pending(REQ_EVENT_RECORD, self._side(stream.cuda_stream), event=self.events))
+        self.events += 1
+        return self.events - 1
+
+    def wait_event(self, stream, event):
+        self.pending.append(_Pending(REQ_STREAM_WAIT, self._side(stream.cuda_stream), event=event))
+
+    def copy(self, dst, src):
+        if not (dst.is_contiguous() and src.is_contiguous()) or dst.numel() != src.numel() or dst.dtype != src.dtype:
+            raise ValueError('request program: a copy step takes two dense tensors of one size')
+        self.pending.append(_Pending(REQ_COPY, self._side(torch.cuda.current_stream(dst.device).cuda_stream),
+                                     p=[dst.data_ptr(), src.data_ptr()], l=[dst.numel() * dst.element_size()]))
+
+    # ---- the entry points ---------------------------------------------------------------------------------------------
+    @staticmethod
+    def _ops(arr, n):
+        return None if arr is None or n == 0 else (ChainOp * n).from_buffer_copy(arr)
+
+    @staticmethod
+    def _guest(ref):
+        return ChainGuest.from_buffer_copy(ref._obj)
+
+    def gd4d_row_chain_fwd(self, a, na, m, stream):
+        self.pending.append(_Pending(REQ_ROW_CHAIN, self._side(stream), prog_a=self._ops(a, na), i=[m]))
+        return 0
+
+    def gd4d_row_chain2_fwd(self, a, na, b, nb, m, stream):
+        self.pending.append(_Pending(REQ_ROW_CHAIN2, self._side(stream), prog_a=self._ops(a, na), prog_b=self._ops(b, nb), i=[m]))
+        return 0
+
+    def gd4d_row_chain_guest_fwd(self, a, na, b, nb, m, guest, stream):
+        self.pending.append(_Pending(REQ_ROW_CHAIN_GUEST, self._side(stream), prog_a=self._ops(a, na), prog_b=self._ops(b, nb), i=[m],
+                                     guest=self._guest(guest)))
+        return 0
+
+    def gd4d_value_proj_guest_fwd(self, guest, max_cus, stream):
+        self.pending.append(_Pending(REQ_VALUE_PROJ_GUEST, self._side(stream), guest=self._guest(guest), i=[max_cus]))
+        return 0
+
+    def gd4d_mha_core_fwd(self, q, k, v, mask, out, lq, lk, b, h, d, ldq, ldk, ldv, ldo, kind, scale, lse, drop_p, seed, stream):
+        if _addr(lse) or drop_p:
+            raise _lib.Gd4dError('request program: the attention core without lse / dropout (inference)')
+        self.pending.append(_Pending(REQ_MHA_CORE, self._side(stream), p=[q, k, v, mask, out], i=[lq, lk, b, h, d, ldq, ldk, ldv, ldo, kind],
+                                     f=[scale]))
+        return 0
+
+    def gd4d_mha_core_presplit_fwd(self, q, kp, vp, out, l, h, d, ldq, ldo, ks, vs, mask, kind, scale, lse, drop_p, seed, stream):
+        if _addr(lse) or drop_p:
+            raise _lib.Gd4dError('request program: the attention core without lse / dropout (inference)')
+        self.pending.append(_Pending(REQ_MHA_PRESPLIT, self._side(stream), p=[q, kp, vp, out, mask], i=[l, h, d, ldq, ldo, kind], l=[ks, vs],
+                                     f=[scale]))
+        return 0
+
+    def gd4d_cross_attn_plan_fwd(self, ref, off, att, cam, l2i, rng, img_h, img_w, lv, cs, pix, plan, plan_bytes, wsum, mask_out, uv_out,
+                                 b, n, q, hh, nl, p, flags, order, stream):
+        # lidar2img, img_h and img_w are the request's (functional.lidar2img_device / img_hw): bound by position, not by address
+        self.pending.append(_Pending(REQ_PLAN, self._side(stream), p=[ref, off, att, cam, l2i, plan, wsum, mask_out, uv_out, order],
+                                     special={4: 'lidar2img'}, fbind=['img_h', 'img_w'], f=[img_h, img_w], l=[pix, plan_bytes],
+                                     i=[b, n, q, hh, nl, p, flags], tables=[(rng, False), (lv, False), (cs, False)]))
+        return 0
+
+    def gd4d_cross_attn_agg_items_coarse_fwd(self, ptrs, lv, cs, pix, sl, pp, pcs, plan, agg, wsum, pagg, b, n, q, hh, c, nl, p, dt, order,
+                                             stream):
+        self.pending.append(_Pending(REQ_AGG_COARSE, self._side(stream), p=[plan, agg, wsum, pagg, order], l=[pix, sl],
+                                     i=[b, n, q, hh, c, nl, p, dt],
+                                     tables=[(ptrs, True), (lv, False), (cs, False), (pp, True), (pcs, False)]))
+        return 0
+
+    def gd4d_cross_attn_agg_items_fwd(self, ptrs, lv, cs, pix, sl, plan, agg, wsum, b, n, q, hh, c, nl, p, dt, order, lo, cnt, stream):
+        self.pending.append(_Pending(REQ_AGG_ITEMS, self._side(stream), p=[plan, agg, wsum, order], l=[pix, sl],
+                                     i=[b, n, q, hh, c, nl, p, dt, lo, cnt], tables=[(ptrs, True), (lv, False), (cs, False)]))
+        return 0
+
+    def gd4d_cross_attn_agg_sliced_fwd(self, ptrs, sl, plan, agg, b, n, q, hh, c, nl, p, dt, order, lo, cnt, stream):
+        self.pending.append(_Pending(REQ_AGG_SLICED, self._side(stream), p=[plan, agg, order], l=[sl],
+                                     i=[b, n, q, hh, c, nl, p, dt, lo, cnt], tables=[(ptrs, True)]))
+        return 0
+
+    def gd4d_pyramid_slice_planar_fwd(self, feats, lv, out, r, c, nl, in_dt, out_dt, max_cus, stream):
+        self.pending.append(_Pending(REQ_SLICE_PLANAR, self._side(stream), p=[out], i=[r, c, nl, in_dt, out_dt, max_cus],
+                                     tables=[(feats, True), (lv, False)]))
+        return 0
+
+    def gd4d_query_order_fwd(self, ref, rng, order, b, q, stream):
+        self.pending.append(_Pending(REQ_QUERY_ORDER, self._side(stream), p=[ref, order], i=[b, q], tables=[(rng, False)]))
+        return 0
+
+    # ---- resolution ---------------------------------------------------------------------------------------------------
+    def steps(self, bindings, named):
+        """The recorded enqueues as a (RequestStep * n) array plus everything it points to (keep both alive until
+        gd4d_decoder_request_create has copied them).  bindings: {index: tensor} - an address inside a binding's extent becomes
+        (index, offset), the base address of one wins over the extent of another (query and query_pos interleave as column slices of
+        one tensor); named: {'lidar2img': index, 'img_h': index, 'img_w': index}."""
+        exact = {t.data_ptr(): k for k, t in bindings.items()}
+        extents = [(*tensor_extent(t), k) for k, t in bindings.items()]
+
+        def find(addr):
+            if addr == 0:
+                return None
+            if addr in exact:
+                return exact[addr], 0
+            for lo, hi, k in extents:
+                if lo <= addr < hi:
+                    return k, addr - lo
+            return None
+
+        keep, arr = [], (RequestStep * len(self.pending))()
+        for s, pd in zip(arr, self.pending):
+            s.kind, s.side, s.event = pd.kind, pd.side, pd.event
+            patches = []
+            for slot, prog in ((0, pd.prog_a), (1, pd.prog_b)):
+                if prog is None:
+                    continue
+                for n, op in enumerate(prog):
+                    for name in _CHAIN_POINTERS:
+                        hit = find(getattr(op, name) or 0)
+                        if hit is not None:
+                            patches.append(RequestPatch(slot, hit[0], n * ctypes.sizeof(ChainOp) + getattr(ChainOp, name).offset, hit[1]))
+                keep.append(prog)
+                if slot == 0:
+                    s.prog_a, s.nops_a = ctypes.addressof(prog), len(prog)
+                else:
+                    s.prog_b, s.nops_b = ctypes.addressof(prog), len(prog)
+            if pd.guest is not None:
+                g = pd.guest
+                where = [(ChainGuest.feats.offset + 8 * n, g.feats[n] or 0) for n in range(g.L)] + \
+                        [(ChainGuest.image.offset, g.image or 0), (ChainGuest.out.offset, g.out or 0)]
+                for offset, addr in where:
+                    hit = find(addr)
+                    if hit is not None:
+                        patches.append(RequestPatch(2, hit[0], offset, hit[1]))
+                keep.append(g)
+                s.guest = ctypes.addressof(g)
+            for n, a in enumerate(pd.p):
+                addr = int(_addr(a))
+                hit = (named[pd.special[n]], 0) if n in pd.special else find(addr)
+                s.p[n] = RequestRef(-1, 0, addr) if hit is None else RequestRef(hit[0], 0, hit[1])
+            for n, v in enumerate(pd.i):
+                s.i[n] = int(v)
+            for n, v in enumerate(pd.l):
+                s.l[n] = int(v)
+            for n, v in enumerate(pd.f):
+                s.f[n] = float(v)
+            s.fbind[0], s.fbind[1] = [named[x] if isinstance(x, str) else -1 for x in pd.fbind]
+            for n, (table, pointers) in enumerate(pd.tables):
+                raw = bytes(table)
+                buf = ctypes.create_string_buffer(raw, len(raw))
+                if pointers:
+                    for j in range(len(raw) // 8):
+                        hit = find(int.from_bytes(raw[8 * j:8 * j + 8], 'little'))
+                        if hit is not None:
+                            patches.append(RequestPatch(3 + n, hit[0], 8 * j, hit[1]))
+                keep.append(buf)
+                s.table[n], s.table_bytes[n] = ctypes.addressof(buf), len(raw)
+            if patches:
+                parr = (RequestPatch * len(patches))(*patches)
+                keep.append(parr)
+                s.patches, s.npatches = ctypes.addressof(parr), len(patches)
+        return arr, keep
+
+
+def copy_into(dst, src):
+    """dst.copy_(src) - or, while a request program is being recorded, its copy step."""
+    rec = _lib.recorder()
+    if rec is None:
+        return dst.copy_(src)
+    rec.copy(dst, src)
+    return dst
+
+
 def depth_net_image(conv_w):
     """gd4d_depth_net_image: the camera-aware DepthNet's 3x3 weight (256, 256, 3, 3) fp32 -> its bf16 hi / lo fragment image for
     depth_conv_fwd (2.25 MB; remake it when the weight changes)."""

@@ -1237,6 +1237,105 @@ int gd4d_distill_loss_fwd_bwd(const float* s_cls, const float* s_box, const floa
                               int B, int Qs, int Qt, int C, int code, int reweight, float loss_cls_weight, float loss_reg_weight,
                               void* stream);
 
+/* --------------------------------------------------------------------------------------------
+ * Request program (gd4d_request.hip): the launch sequence of ONE eager decoder request - what Detr3DTransformerDecoder.forward
+ * (detr3d_transformer.py:166-225) enqueues through the entry points above, about 35 calls at six layers - prepared once, kept on the
+ * host side of the library and re-issued by ONE call.  HOST code only: no kernel is added or changed; gd4d_decoder_request_run calls the
+ * entry points a step names, with the step's arguments, in the order of the table, on the caller's stream or on `side_stream`.
+ *
+ * A device pointer of a step is a gd4d_request_ref: a fixed address (binding < 0: a weight, a weight image, an intermediate the
+ * program's owner keeps in static storage) or bindings[binding] + value bytes - what differs between two requests: the pyramid levels,
+ * the queries, the lidar2img buffer, the attention mask, the outputs.  Device pointers INSIDE a table a step owns (a gd4d_chain_op's
+ * p0 .. p3 / gout, a gd4d_chain_guest's feats / image / out, the entries of a level-pointer array) are bound by gd4d_request_patch
+ * records: before the step is issued the 8 bytes at `offset` of table `table` become bindings[binding] + add (table 1 exists for
+ * ROW_CHAIN2 and for ROW_CHAIN_GUEST with nops_b > 0 only).
+ * A scalar binding carries a double (PLAN's img_h / img_w).
+ *
+ * Arguments by kind (everything not listed is 0 / NULL; `table[k]` are host arrays, table_bytes[k] their sizes):
+ *   ROW_CHAIN         gd4d_row_chain_fwd(prog_a, nops_a, M = i[0])
+ *   ROW_CHAIN2        gd4d_row_chain2_fwd(prog_a, nops_a, prog_b, nops_b, M = i[0])
+ *   ROW_CHAIN_GUEST   gd4d_row_chain_guest_fwd(prog_a, nops_a, prog_b, nops_b, M = i[0], guest); nops_b == 0: one program - the form of
+ *                     the first layer's in-projection when it carries the first projection of the coarse levels
+ *   MHA_CORE          gd4d_mha_core_fwd: p[0..4] = q, k, v, mask, out; i[0..9] = Lq, Lk, B, H, D, ldq, ldk, ldv, ldo, mask_kind;
+ *                     f[0] = scale (no lse, no dropout: inference)
+ *   MHA_PRESPLIT      gd4d_mha_core_presplit_fwd: p[0..4] = q, k_planes, v_planes, out, mask; i[0..5] = L, H, D, ldq, ldo, mask_kind;
+ *                     l[0..1] = k_plane_stride, v_plane_stride; f[0] = scale
+ *   PLAN              gd4d_cross_attn_plan_fwd: p[0..9] = ref, offsets, attn_logits, cam_logits, lidar2img, plan, wsum, mask_out, uv_out,
+ *                     query_order; table[0] = pc_range (6 doubles), table[1] = level_hw, table[2] = cam_stride_bytes; l[0] =
+ *                     pix_stride_bytes, l[1] = plan_bytes; img_h / img_w = f[0] / f[1], or the scalar bindings fbind[0] / fbind[1]
+ *                     (>= 0); i[0..6] = B, N, Q, Hh, L, P, flags
+ *   AGG_COARSE        gd4d_cross_attn_agg_items_coarse_fwd: table[0] = level_ptrs, table[1] = level_hw, table[2] = cam_stride_bytes,
+ *                     table[3] = proj_ptrs, table[4] = proj_cam_stride_bytes (two entries each - levels 2 and 3 -: 16 bytes); l[0..1] = pix / slice stride; p[0..4] = plan, agg, wsum,
+ *                     pagg, query_order; i[0..7] = B, N, Q, Hh, C, L, P, feats_dtype
+ *   AGG_ITEMS         gd4d_cross_attn_agg_items_fwd: table[0..2], l[0..1] as AGG_COARSE; p[0..3] = plan, agg, wsum, query_order;
+ *                     i[0..9] = B, N, Q, Hh, C, L, P, feats_dtype, slice_lo, slice_n
+ *   AGG_SLICED        gd4d_cross_attn_agg_sliced_fwd: table[0] = level_ptrs; l[0] = slice_stride_bytes; p[0..2] = plan, agg, query_order;
+ *                     i[0..9] as AGG_ITEMS
+ *   SLICE_PLANAR      gd4d_pyramid_slice_planar_fwd: table[0] = feats, table[1] = level_hw; p[0] = out; i[0..5] = R, C, L, in_dtype,
+ *                     out_dtype, max_cus
+ *   VALUE_PROJ_GUEST  gd4d_value_proj_guest_fwd(guest, max_cus = i[0]): the first layer's projection of the coarse levels as a launch of
+ *                     its own, on either stream (GD4D_FIRST_PROJ)
+ *   QUERY_ORDER       gd4d_query_order_fwd: p[0] = ref, p[1] = order; table[0] = pc_range; i[0..1] = B, Q
+ *   EVENT_RECORD      hipEventRecord(event `event`) on the step's stream;  STREAM_WAIT  the step's stream waits for event `event`, which an
+ *                     EARLIER step must record: the fork to and the join from the side stream
+ *   COPY              hipMemcpyAsync(p[0], p[1], l[0] bytes, device to device): the reference points of a decoder without reg branches
+ * side != 0: the step goes to `side_stream`.
+ *
+ * gd4d_decoder_request_create deep-copies the steps and every program, guest, table and patch list they point to, validates them
+ * (GD4D_EINVAL: a NULL table, nsteps <= 0, an unknown kind, a binding index >= nbindings, a chain program without operations, a wait
+ * for an event no earlier step records, a patch outside its table) and creates the events with timing disabled.  It launches nothing.
+ * gd4d_decoder_request_run binds, then issues the steps in order; it allocates nothing and never synchronises.  At the first non-zero
+ * return of an entry point it stops and returns that code - after joining the side stream back into `stream` if a step had gone
+ * there, so the caller's stream never waits for an event nobody records.  A program serves ONE request at a time (the tables are
+ * patched in place): a second stream takes a second program.  gd4d_decoder_request_describe: the name of the entry point step i calls
+ * ("hipEventRecord", "hipStreamWaitEvent", "hipMemcpyAsync" for the three runtime kinds), NULL outside the table. */
+enum { GD4D_REQ_ROW_CHAIN = 1, GD4D_REQ_ROW_CHAIN2 = 2, GD4D_REQ_ROW_CHAIN_GUEST = 3, GD4D_REQ_MHA_CORE = 4, GD4D_REQ_MHA_PRESPLIT = 5,
+       GD4D_REQ_PLAN = 6, GD4D_REQ_AGG_COARSE = 7, GD4D_REQ_AGG_ITEMS = 8, GD4D_REQ_AGG_SLICED = 9, GD4D_REQ_SLICE_PLANAR = 10,
+       GD4D_REQ_VALUE_PROJ_GUEST = 11, GD4D_REQ_QUERY_ORDER = 12, GD4D_REQ_EVENT_RECORD = 13, GD4D_REQ_STREAM_WAIT = 14,
+       GD4D_REQ_COPY = 15 };
+#define GD4D_REQ_MAX_STEPS 1024
+#define GD4D_REQ_MAX_EVENTS 64
+#define GD4D_REQ_PTRS 10
+#define GD4D_REQ_INTS 10
+#define GD4D_REQ_TABLES 5
+typedef struct gd4d_request_ref {
+  int32_t binding;                  /* < 0: `value` is the address */
+  int32_t reserved;
+  int64_t value;                    /* address, or byte offset from bindings[binding] */
+} gd4d_request_ref;
+typedef struct gd4d_request_patch {
+  int32_t table;                    /* 0: prog_a, 1: prog_b, 2: guest, 3 + k: table[k] */
+  int32_t binding;
+  int64_t offset;                   /* of the pointer inside the table, bytes (a multiple of 8) */
+  int64_t add;                      /* bytes added to the binding */
+} gd4d_request_patch;
+typedef union gd4d_request_binding {
+  const void* ptr;
+  double scalar;
+} gd4d_request_binding;
+typedef struct gd4d_request_step {
+  int32_t kind, side, event, npatches;
+  int32_t nops_a, nops_b;
+  int32_t fbind[2];
+  const gd4d_chain_op* prog_a;
+  const gd4d_chain_op* prog_b;
+  const gd4d_chain_guest* guest;
+  const gd4d_request_patch* patches;
+  gd4d_request_ref p[GD4D_REQ_PTRS];
+  int32_t i[GD4D_REQ_INTS];
+  int64_t l[2];
+  float f[2];
+  const void* table[GD4D_REQ_TABLES];
+  int64_t table_bytes[GD4D_REQ_TABLES];
+} gd4d_request_step;
+typedef struct gd4d_decoder_request gd4d_decoder_request;
+size_t gd4d_request_step_bytes(void);
+int gd4d_decoder_request_create(const gd4d_request_step* steps, int nsteps, int nbindings, gd4d_decoder_request** req);
+int gd4d_decoder_request_run(gd4d_decoder_request* req, const gd4d_request_binding* bindings, int nbindings, void* stream,
+                             void* side_stream);
+int gd4d_decoder_request_destroy(gd4d_decoder_request* req);
+const char* gd4d_decoder_request_describe(const gd4d_decoder_request* req, int i);
+
 #ifdef __cplusplus
 }
 #endif
