@@ -15,7 +15,7 @@ from .deform3d_cross_attn import Deform3DCrossAttn  # noqa: F401
 from .deform3d_cross_attn_mp import Deform3DCrossAttnMP  # noqa: F401
 from .bbox_coder import NMSFreeCoder  # noqa: F401
 from .criterion import Detr3DCriterion, HDetr3DCriterion, HungarianAssigner3D  # noqa: F401
-from .distill import DistillHungarianAssigner3D, get_instance_distill_loss  # noqa: F401
+from .distill import DistillHungarianAssigner3D, FeatureDistillLoss, get_feat_distill_loss, get_instance_distill_loss  # noqa: F401
 from .dgcnn_attn import DGCNNAttn  # noqa: F401
 from .head_pe import FeaturePositionEmbedding  # noqa: F401
 from .depth_net import DepthNet  # noqa: F401
@@ -27,4 +27,4 @@ from .detr3d_transformer import (Detr3DCrossAtten, Detr3DCrossAttenV2, Detr3DTra
 __all__ = ['Deform3DCrossAttn', 'Deform3DCrossAttnMP', 'DGCNNAttn', 'Detr3DCrossAtten', 'Detr3DCrossAttenV2', 'feature_sampling', 'Detr3DTransformer',
            'Detr3DTransformerDecoder', 'HDetr3DTransformer', 'MultiheadAttention', 'FFN', 'BaseTransformerLayer',
            'DetrTransformerDecoderLayer', 'TransformerLayerSequence', 'inverse_sigmoid',
-           'NMSFreeCoder', 'HungarianAssigner3D', 'Detr3DCriterion', 'HDetr3DCriterion', 'DistillHungarianAssigner3D', 'get_instance_distill_loss', 'FeaturePositionEmbedding', 'DepthNet', 'TrainRecipe', 'BBOX_CODERS', 'BBOX_ASSIGNERS', 'ATTENTION', 'TRANSFORMER', 'TRANSFORMER_LAYER', 'TRANSFORMER_LAYER_SEQUENCE']
+           'NMSFreeCoder', 'HungarianAssigner3D', 'Detr3DCriterion', 'HDetr3DCriterion', 'DistillHungarianAssigner3D', 'get_instance_distill_loss', 'FeatureDistillLoss', 'get_feat_distill_loss', 'FeaturePositionEmbedding', 'DepthNet', 'TrainRecipe', 'BBOX_CODERS', 'BBOX_ASSIGNERS', 'ATTENTION', 'TRANSFORMER', 'TRANSFORMER_LAYER', 'TRANSFORMER_LAYER_SEQUENCE']

@@ -141,6 +141,10 @@ SIGNATURES = {
     'gd4d_lsa_dense_workspace_bytes': (_c.c_size_t, [_i] * 4),
     'gd4d_lsa_dense_fwd': (_i, [_vp] * 5 + [_c.c_size_t] + [_i] * 5 + [_vp]),
     'gd4d_distill_loss_fwd_bwd': (_i, [_vp] * 10 + [_i] * 7 + [_f, _f, _vp]),
+    'gd4d_feat_distill_stats_workspace_bytes': (_c.c_size_t, [_vp, _i, _i]),
+    'gd4d_feat_distill_stats_fwd': (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _c.c_size_t, _vp]),
+    'gd4d_feat_distill_workspace_bytes': (_c.c_size_t, [_vp, _i, _i]),
+    'gd4d_feat_distill_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _c.c_size_t, _vp]),
     'gd4d_request_step_bytes': (_c.c_size_t, []),
     'gd4d_decoder_request_create': (_i, [_vp, _i, _i, _vp]),
     'gd4d_decoder_request_run': (_i, [_vp, _vp, _i, _vp, _vp]),

@@ -1851,6 +1851,72 @@ def distill_loss_fwd_bwd(s_cls, s_box, t_cls, t_box, assigned, code_weights, avg
     _lib.check(code, 'gd4d_distill_loss_fwd_bwd')
     return loss, gcls, gbox
 
+
+def _feat_distill_levels(levels, name, like=None):
+    """The per-level arguments of the feature-distillation entry points: fp32 (R, 256, H_l, W_l) maps with one R -> (pointer array,
+    level_hw array, R)."""
+    if not levels or any(t.dim() != 4 for t in levels) or any(t.shape[0] != levels[0].shape[0] or t.shape[1] != levels[0].shape[1] for t in levels):
+        raise ValueError(f'{name}: levels (R, C, H_l, W_l) with the same R and C expected')
+    if like is not None and [tuple(t.shape) for t in levels] != [tuple(t.shape) for t in like]:
+        raise ValueError(f'{name}: the levels\' shapes differ from the other pyramid\'s')
+    nl = len(levels)
+    ptrs = (ctypes.c_void_p * nl)(*[_dev(t, name, torch.float32).value for t in levels])
+    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for t in levels for x in t.shape[2:]])
+    return ptrs, lv, int(levels[0].shape[0])
+
+
+def feat_distill_stats_fwd(teacher, temperature=0.5):
+    """gd4d_feat_distill_stats_fwd: teacher levels (R, 256, H_l, W_l) -> the attention maps of MixDistill.get_feat_distill_loss's
+    'attention' type (mix_distill.py:131-135), one pass over each level: a_c[l] (R, H_l W_l) = 256 softmax_p(mean_c |t| / T) and
+    a_s[l] (R, 256) = H W softmax_c(mean_p |t| / T)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    tp, lv, r = _feat_distill_levels(teacher, 'teacher')
+    nl, c, dev = len(teacher), int(teacher[0].shape[1]), teacher[0].device
+    a_c = [torch.empty(r, t.shape[2] * t.shape[3], device=dev, dtype=f32) for t in teacher]
+    a_s = [torch.empty(r, c, device=dev, dtype=f32) for t in teacher]
+    ws = torch.empty(max(int(lib.gd4d_feat_distill_stats_workspace_bytes(lv, nl, r)), 16), device=dev, dtype=torch.uint8)
+    cp = (ctypes.c_void_p * nl)(*[_dev(t, 'a_c', f32).value for t in a_c])
+    sp = (ctypes.c_void_p * nl)(*[_dev(t, 'a_s', f32).value for t in a_s])
+    code = lib.gd4d_feat_distill_stats_fwd(tp, lv, nl, r, c, float(temperature), cp, sp, _dev(ws, 'workspace', torch.uint8), ws.numel(),
+                                           _stream())
+    _lib.check(code, 'gd4d_feat_distill_stats_fwd')
+    return a_c, a_s
+
+
+def feat_distill_fwd(student, teacher, weight, bias, loss_weight, a_c=None, a_s=None):
+    """gd4d_feat_distill_fwd: student / teacher levels (R, 256, H_l, W_l), weight (L, 256, 256) and bias (L, 256) of the lateral 1x1
+    convolutions -> (loss (1), [d loss / d student_l], d loss / d weight (L, 256, 256), d loss / d bias (L, 256)) of
+    loss = loss_weight / L * sum_l mean(a_c a_s (conv_l(student_l) - teacher_l)^2); a_c / a_s from feat_distill_stats_fwd, or None for
+    the vanilla type (plain mse).  The converted student map is never materialised."""
+    lib = _lib.load()
+    f32 = torch.float32
+    sp, lv, r = _feat_distill_levels(student, 'student')
+    tp, _, _ = _feat_distill_levels(teacher, 'teacher', like=student)
+    nl, c, dev = len(student), int(student[0].shape[1]), student[0].device
+    if tuple(weight.shape) != (nl, c, c) or tuple(bias.shape) != (nl, c):
+        raise ValueError(f'feat_distill_fwd: weight ({nl}, {c}, {c}) and bias ({nl}, {c}) expected')
+    if (a_c is None) != (a_s is None):
+        raise ValueError('feat_distill_fwd: both attention maps or neither')
+    cp = ap = None
+    if a_c is not None:
+        if len(a_c) != nl or len(a_s) != nl or any(tuple(m.shape) != (r, s.shape[2] * s.shape[3]) for m, s in zip(a_c, student)) or \
+                any(tuple(m.shape) != (r, c) for m in a_s):
+            raise ValueError('feat_distill_fwd: a_c[l] (R, H_l W_l) and a_s[l] (R, C) expected')
+        cp = (ctypes.c_void_p * nl)(*[_dev(t, 'a_c', f32).value for t in a_c])
+        ap = (ctypes.c_void_p * nl)(*[_dev(t, 'a_s', f32).value for t in a_s])
+    loss = torch.empty(1, device=dev, dtype=f32)
+    gx = [torch.empty_like(s) for s in student]
+    gw, gb = torch.empty_like(weight), torch.empty_like(bias)
+    gp = (ctypes.c_void_p * nl)(*[_dev(t, 'grad_student', f32).value for t in gx])
+    ws = torch.empty(max(int(lib.gd4d_feat_distill_workspace_bytes(lv, nl, r)), 16), device=dev, dtype=torch.uint8)
+    code = lib.gd4d_feat_distill_fwd(sp, tp, lv, nl, r, c, _dev(weight, 'weight', f32), _dev(bias, 'bias', f32), cp, ap, float(loss_weight),
+                                     _dev(loss, 'loss', f32), gp, _dev(gw, 'grad_weight', f32), _dev(gb, 'grad_bias', f32),
+                                     _dev(ws, 'workspace', torch.uint8), ws.numel(), _stream())
+    _lib.check(code, 'gd4d_feat_distill_fwd')
+    return loss, gx, gw, gb
+
+
 class ChainOp(ctypes.Structure):
     """gd4d_chain_op (include/gd4d.h)."""
     _fields_ = [('kind', ctypes.c_int32), ('src', ctypes.c_int32), ('dst', ctypes.c_int32), ('res', ctypes.c_int32),

@@ -1237,6 +1237,40 @@ int gd4d_distill_loss_fwd_bwd(const float* s_cls, const float* s_box, const floa
                               int B, int Qs, int Qt, int C, int code, int reweight, float loss_cls_weight, float loss_reg_weight,
                               void* stream);
 
+/* MixDistill's pyramid feature-distillation loss (distillation/distillers/mix_distill.py:51-55, 118-138, gd4d_feat_distill.hip).  Per
+ * level l the student's map x_l (R, 256, H_l, W_l) - fp32 NCHW as the FPN emits it, R = B * num_cams cameras - goes through
+ * lateral_convs[l], a 1x1 convolution 256 -> 256 with bias, and is compared to the teacher's t_l of the same shape:
+ *     s_l = W_l x_l + b_l                                   (split-bf16 MFMAs, fp32 accumulation: the arithmetic of gd4d_gemm_bf16x3_fwd)
+ *     vanilla:    loss_l = mean((s_l - t_l)^2)                                                                              (:129)
+ *     attention:  loss_l = mean(a_c[r, p] a_s[r, c] (t_l - s_l)^2), both maps from the TEACHER with T = 0.5                 (:131-137):
+ *                 a_c[r, p] = 256 softmax_p(mean_c |t[r, c, p]| / T),  a_s[r, c] = H W softmax_c(mean_p |t[r, c, p]| / T)
+ *     loss = loss_weight * sum_l loss_l / levels                                                                            (:138)
+ * The converted map s_l is never written to memory: one launch per level loads a 64-pixel tile of x_l once, forms s_l's tile in
+ * registers, adds the tile's loss to a per-workgroup partial, forms G = d loss / d s_l = 2 coef (a_c a_s) (s_l - t_l) with
+ * coef = loss_weight / (levels R 256 H W), writes G once (workspace, one level at a time) and dx_l = W_l^T G.  dW_l = sum G x_l^T and
+ * db_l = sum G come from a split-k product over G with per-workgroup partials; every partial sum - loss, dW, db, the channel sums of
+ * the statistics - is added in index order: no floating-point atomics, two runs give the same bits.  Nothing is allocated and nothing
+ * synchronises; the whole term can be captured in a graph on one stream.
+ *
+ * gd4d_feat_distill_stats_fwd - the attention maps of every level: one pass over teacher[l] (each element read once) and the two
+ *   softmaxes, maxima subtracted.  teacher / a_c / a_s are HOST arrays of `levels` device pointers: teacher[l] (R, 256, H_l, W_l),
+ *   a_c[l] (R, H_l W_l), a_s[l] (R, 256); level_hw = {H_0, W_0, H_1, ...} on the host.  temperature > 0 (the reference's T: 0.5).
+ * gd4d_feat_distill_fwd - loss (1 device float) and all gradients.  student / teacher / grad_student: host arrays of device pointers
+ *   (R, 256, H_l, W_l); weight (levels, 256, 256) and bias (levels, 256) the lateral convolutions' parameters stacked by level,
+ *   grad_weight / grad_bias the same shapes; a_c / a_s: the maps of gd4d_feat_distill_stats_fwd, or both NULL for the vanilla type.
+ *   The teacher gets no gradient.  Pixel counts need not be multiples of the tile (1 x 1 levels included).
+ * Workspaces: gd4d_feat_distill_stats_workspace_bytes / gd4d_feat_distill_workspace_bytes (0 for arguments the functions refuse),
+ * 16-B aligned (GD4D_EALIGN), too small: GD4D_EWORKSPACE.  C != 256, more than 8 levels, R H_l W_l >= 2^31: GD4D_EUNSUPPORTED; a NULL
+ * pointer (a level's included), levels / R / a level size <= 0, only one of a_c / a_s: GD4D_EINVAL.  All checked before any launch. */
+size_t gd4d_feat_distill_stats_workspace_bytes(const int32_t* level_hw, int levels, int R);
+int gd4d_feat_distill_stats_fwd(const float* const* teacher, const int32_t* level_hw, int levels, int R, int C, float temperature,
+                                float* const* a_c, float* const* a_s, void* workspace, size_t workspace_bytes, void* stream);
+size_t gd4d_feat_distill_workspace_bytes(const int32_t* level_hw, int levels, int R);
+int gd4d_feat_distill_fwd(const float* const* student, const float* const* teacher, const int32_t* level_hw, int levels, int R, int C,
+                          const float* weight, const float* bias, const float* const* a_c, const float* const* a_s, float loss_weight,
+                          float* loss, float* const* grad_student, float* grad_weight, float* grad_bias, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* --------------------------------------------------------------------------------------------
  * Request program (gd4d_request.hip): the launch sequence of ONE eager decoder request - what Detr3DTransformerDecoder.forward
  * (detr3d_transformer.py:166-225) enqueues through the entry points above, about 35 calls at six layers - prepared once, kept on the

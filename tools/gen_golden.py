@@ -778,6 +778,39 @@ def case_distill(name, *, num_query, batch, seed, num_layers=3, num_classes=10, 
          losses=torch.stack([losses[k].detach() for k in keys]), grad_s_cls=s_cls.grad, grad_s_box=s_box.grad)
 
 
+def case_feat_distill(name, *, kind, seed, levels=((4, 7), (1, 2)), batch=1, num_cams=2, loss_weight=2.0):
+    """MixDistill.get_feat_distill_loss (distillation/distillers/mix_distill.py:118-138), called unbound on a shell carrying
+    `lateral_convs` (nn.Conv2d(256, 256, 1) per level, :51-55) and `loss_feat_distill`: pyramid levels (B, N, 256, H, W) in, `feat_loss`
+    out, with torch autograd's gradients for the student's levels and every conv's weight and bias.  The teacher's magnitudes vary by
+    channel and by pixel, so both attention softmaxes are far from uniform.  Two levels and weights on a grid of 1/64 (they compress;
+    the weight gradients do not) keep the file under the size limit for a committed fixture."""
+    mod = refstub.load_distiller()
+    g = torch.Generator().manual_seed(seed)
+    convs = nn.ModuleList(nn.Conv2d(256, 256, 1, 1, 0) for _ in levels)
+    for conv in convs:
+        with torch.no_grad():
+            conv.weight.copy_(torch.randint(-8, 9, (256, 256, 1, 1), generator=g) / 64.)
+            conv.bias.copy_(torch.randn(256, generator=g) * 0.1)
+    teacher, student = [], []
+    for h, w in levels:
+        t = torch.randn(batch, num_cams, 256, h, w, generator=g)
+        t = t * (0.25 + 2.0 * torch.rand(batch, num_cams, 256, 1, 1, generator=g)) * (0.25 + 2.0 * torch.rand(batch, num_cams, 1, h, w, generator=g))
+        teacher.append(t)
+        student.append(torch.randn(batch, num_cams, 256, h, w, generator=g).requires_grad_())
+    shell = types.SimpleNamespace(lateral_convs=convs, loss_feat_distill=dict(type=kind, loss_weight=loss_weight))
+    out = mod.MixDistill.get_feat_distill_loss(shell, teacher, student)
+    assert list(out) == ['feat_loss']
+    out['feat_loss'].backward()
+    arrays = dict(feat_loss=out['feat_loss'].detach())
+    for l in range(len(levels)):
+        arrays[f'teacher{l}'], arrays[f'student{l}'], arrays[f'grad_student{l}'] = teacher[l], student[l].detach(), student[l].grad
+        arrays[f'lateral_convs.{l}.weight'], arrays[f'lateral_convs.{l}.bias'] = convs[l].weight.detach(), convs[l].bias.detach()
+        arrays[f'grad_weight{l}'], arrays[f'grad_bias{l}'] = convs[l].weight.grad, convs[l].bias.grad
+    meta = dict(kind='feat_distill', type=kind, loss_weight=loss_weight, levels=[list(hw) for hw in levels], batch=batch,
+                num_cams=num_cams, seed=seed)
+    save(name, meta, **arrays)
+
+
 def case_detr4d_distill(name, *, num_student, num_teacher, batch, seed, num_layers=2, reweight_score=False, loss_cls_weight=1.0,
                         loss_reg_weight=0.25, degenerate=False):
     """Detr4D_Distiller.get_instance_distill_loss (distillation/distillers/detr4d_distiller.py:143-168), called unbound on a shell whose
@@ -903,6 +936,8 @@ def main():
                         loss_cls_weight=1.0, loss_reg_weight=0.25)
     case_detr4d_distill('detr4d_distill_degenerate', num_student=24, num_teacher=32, batch=1, seed=904, degenerate=True,
                         loss_cls_weight=0.0, loss_reg_weight=0.25)
+    case_feat_distill('feat_distill_vanilla', kind='vanilla', seed=1001)
+    case_feat_distill('feat_distill_attention', kind='attention', seed=1002)
 
 
 if __name__ == '__main__':
