@@ -137,6 +137,15 @@ SIGNATURES = {
     'gd4d_depth_net_image': (_i, [_vp, _i, _vp, _vp]),
     'gd4d_cam_gate_fwd': (_i, [_vp, _vp, _i, _i, _f] + [_vp] * 8 + [_i, _vp, _vp]),
     'gd4d_depth_conv_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i] + [_vp] * 6 + [_f, _vp, _vp]),
+    'gd4d_depth_net_image_mode': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_depth_conv_tiles': (_c.c_longlong, [_vp, _i, _i]),
+    'gd4d_depth_conv_raw': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'gd4d_depth_bn_stats': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _i, _vp, _vp]),
+    'gd4d_depth_bn_act_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'gd4d_depth_bn_bwd_workspace_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_depth_bn_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 6),
+    'gd4d_depth_conv_wgrad_workspace_bytes': (_c.c_size_t, [_i]),
+    'gd4d_depth_conv_wgrad': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'gd4d_distill_match_cost_fwd': (_i, [_vp] * 5 + [_i] * 7 + [_f, _f, _vp]),
     'gd4d_lsa_dense_workspace_bytes': (_c.c_size_t, [_i] * 4),
     'gd4d_lsa_dense_fwd': (_i, [_vp] * 5 + [_c.c_size_t] + [_i] * 5 + [_vp]),

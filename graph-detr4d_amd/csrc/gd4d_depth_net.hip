@@ -38,6 +38,9 @@
 // Measured (docs/measurements_r07.md): 2.58-2.64 ms per 24-camera sample (0.99-1.02 PFLOP/s of bf16 products, 0.40-0.41 of the
 // spec), 1.34-1.37 ms at 12;
 // matrix pipe busy 62 %, waves waiting on instruction dependencies 66 % of their cycles; LDS bank conflicts present, not located.
+// Training (gd4d_depth_net_train.hip has the rest): depth_conv_kernel<EPI> - the same GEMM with a second epilogue that stores
+// y = conv + bias and each tile's per-channel (mean, M2) (125 VGPRs, no scratch) and a third, plain-store one (121 VGPRs, no scratch)
+// that is also the input gradient: gd4d_depth_net_image_mode(transposed = 1) lays out w'[ic, oc, 2 - ky, 2 - kx] = w[oc, ic, ky, kx].
 // Left off: padding the stages, two workgroups per CU, fusing the epilogue into the position embedding's gate / fuse kernel.
 #include "gd4d_common.h"
 #include "gd4d_bf16x3.h"
@@ -62,7 +65,10 @@ static_assert(DN_LDS <= 160 * 1024, "LDS budget of a CU");
 
 // ---- weight image ---------------------------------------------------------------------------------------------------------
 // item i = ((step * 2 + plane) * 4 + k-group) * 256 + out channel, 16 bytes each: byte offset 16 i
-__global__ __launch_bounds__(256) void depth_net_image_kernel(const float* __restrict__ w, char* __restrict__ image) {
+// transposed (the input gradient's image): the weight w'[ic, oc, 2 - ky, 2 - kx] = w[oc, ic, ky, kx] is laid out instead, so the same
+// kernel run on dy gives dx
+__global__ __launch_bounds__(256) void depth_net_image_kernel(const float* __restrict__ w, char* __restrict__ image,
+                                                              const int transposed) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= DN_STEPS * 2 * 4 * DN_C) return;
   const int oc = i & 255, kgrp = (i >> 8) & 3, plane = (i >> 10) & 1, s = i >> 11;
@@ -71,7 +77,8 @@ __global__ __launch_bounds__(256) void depth_net_image_kernel(const float* __res
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int ci = chunk * DN_KC + kgrp * 8 + j;
-    const float v = w[((size_t)oc * DN_C + ci) * 9 + tap];                // (out, in, ky, kx): tap = 3 ky + kx
+    const float v = transposed ? w[((size_t)ci * DN_C + oc) * 9 + (DN_TAPS - 1 - tap)]
+                               : w[((size_t)oc * DN_C + ci) * 9 + tap];   // (out, in, ky, kx): tap = 3 ky + kx
     const uint16_t h = f32_to_bf16(v);
     e[j] = plane ? f32_to_bf16(v - bf16_to_f32(h)) : h;
   }
@@ -168,10 +175,23 @@ struct DepthConvParams {
   int h[DN_MAX_LEVELS], w[DN_MAX_LEVELS], tiles_x[DN_MAX_LEVELS], tiles_cam[DN_MAX_LEVELS], start[DN_MAX_LEVELS];
   const char* image;
   const float *bias, *mean, *var, *gamma, *beta, *gate;
+  float* partials;         // DN_EPI_STATS: (tiles, 2, 256) per-tile mean and M2 of y, tiles in grid order
   float eps;
   int levels;
 };
 
+// The epilogues of the one implicit GEMM.  INFER: + bias, BatchNorm (running statistics), ReLU, x gate.  STATS (training forward):
+// stores y = conv + bias and each channel's (mean, M2) over the tile's valid pixels, summed in a fixed order (lanes by an xor
+// butterfly, then the four pixel waves).  PLAIN: stores conv (+ bias when given): the frozen-BatchNorm forward and the input gradient.
+enum { DN_EPI_INFER = 0, DN_EPI_STATS = 1, DN_EPI_PLAIN = 2 };
+
+__device__ __forceinline__ float dn_half_wave_sum(float s) {
+#pragma unroll
+  for (int m = 1; m < 32; m <<= 1) s += __shfl_xor(s, m);
+  return s;
+}
+
+template <int EPI>
 __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const wbuf = smem;                                   // [2][hi, lo][4][256][16 B]
@@ -201,13 +221,17 @@ __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvP
   const int ty0 = (rt / p.tiles_x[lv]) * DN_T, tx0 = (rt % p.tiles_x[lv]) * DN_T;
   const float* const xin = p.x[lv] + (size_t)cam * DN_C * HW;
 
-  if (tid < DN_C) {
-    const float sc = p.gamma[tid] / sqrtf(p.var[tid] + p.eps);
-    e_bias[tid] = p.bias[tid];
-    e_mean[tid] = p.mean[tid];
-    e_scale[tid] = sc;
-    e_beta[tid] = p.beta[tid];
-    e_gate[tid] = p.gate[cam * DN_C + tid];
+  if (EPI == DN_EPI_INFER) {
+    if (tid < DN_C) {
+      const float sc = p.gamma[tid] / sqrtf(p.var[tid] + p.eps);
+      e_bias[tid] = p.bias[tid];
+      e_mean[tid] = p.mean[tid];
+      e_scale[tid] = sc;
+      e_beta[tid] = p.beta[tid];
+      e_gate[tid] = p.gate[cam * DN_C + tid];
+    }
+  } else if (tid < DN_C) {
+    e_bias[tid] = p.bias ? p.bias[tid] : 0.f;
   }
 
   // halo staging role: item it = (k-group, halo pixel); 8 channels of one pixel, zero outside the image
@@ -317,22 +341,84 @@ __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvP
 
   // C/D of 32x32x16: column (pixel) = l32, rows (channels) 4 kg + (r & 3) + 8 (r >> 2)
   float* const outp = p.out[lv] + (size_t)cam * DN_C * HW;
+  if (EPI == DN_EPI_INFER) {
 #pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int pp = 64 * wn + 32 * ni + l32;
-    const int y = ty0 + (pp >> 4), x = tx0 + (pp & 15);
-    if (y >= H || x >= W) continue;
-    float* const o = outp + (size_t)y * W + x;
+    for (int ni = 0; ni < 2; ++ni) {
+      const int pp = 64 * wn + 32 * ni + l32;
+      const int y = ty0 + (pp >> 4), x = tx0 + (pp & 15);
+      if (y >= H || x >= W) continue;
+      float* const o = outp + (size_t)y * W + x;
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int c = 64 * wm + 32 * mi + 4 * kg + (r & 3) + 8 * (r >> 2);
+          float v = acc[mi][ni][r] + e_bias[c];                 // conv bias
+          v = (v - e_mean[c]) * e_scale[c] + e_beta[c];          // BatchNorm2d, eval (running statistics)
+          v = fmaxf(v, 0.f);                                     // ReLU
+          o[(size_t)c * HW] = v * e_gate[c];                     // SELayer: x * gate
+        }
+    }
+  } else {
+    // (the main loop's last barrier is behind every wave: the stages are free)
+    float* const red = reinterpret_cast<float*>(smem);          // [4 pixel waves][256]
+    float* const tmean = red + 4 * DN_C;                        // [256]
+    bool ok[2];
+    size_t off[2];
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      const int pp = 64 * wn + 32 * ni + l32;
+      const int y = ty0 + (pp >> 4), x = tx0 + (pp & 15);
+      ok[ni] = y < H && x < W;
+      off[ni] = ok[ni] ? (size_t)y * W + x : 0;
+    }
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int c = 64 * wm + 32 * mi + 4 * kg + (r & 3) + 8 * (r >> 2);
-        float v = acc[mi][ni][r] + e_bias[c];                 // conv bias
-        v = (v - e_mean[c]) * e_scale[c] + e_beta[c];          // BatchNorm2d, eval (running statistics)
-        v = fmaxf(v, 0.f);                                     // ReLU
-        o[(size_t)c * HW] = v * e_gate[c];                     // SELayer: x * gate
+        float s = 0.f;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+          const float v = acc[mi][ni][r] + e_bias[c];
+          acc[mi][ni][r] = v;
+          if (ok[ni]) {
+            outp[(size_t)c * HW + off[ni]] = v;
+            s += v;
+          }
+        }
+        if (EPI == DN_EPI_STATS) {
+          s = dn_half_wave_sum(s);
+          if (l32 == 0) red[wn * DN_C + c] = s;
+        }
       }
+    if (EPI == DN_EPI_STATS) {
+      const int vh = min(DN_T, H - ty0), vw = min(DN_T, W - tx0);
+      __syncthreads();
+      if (tid < DN_C) tmean[tid] = ((red[tid] + red[DN_C + tid]) + (red[2 * DN_C + tid] + red[3 * DN_C + tid])) / (float)(vh * vw);
+      __syncthreads();
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int c = 64 * wm + 32 * mi + 4 * kg + (r & 3) + 8 * (r >> 2);
+          const float m = tmean[c];
+          float s = 0.f;
+#pragma unroll
+          for (int ni = 0; ni < 2; ++ni) {
+            const float d = acc[mi][ni][r] - m;
+            if (ok[ni]) s += d * d;
+          }
+          s = dn_half_wave_sum(s);
+          if (l32 == 0) red[wn * DN_C + c] = s;                 // (tmean is read above, red's sums were consumed before the barrier)
+        }
+      __syncthreads();
+      if (tid < DN_C) {
+        float* const part = p.partials + (size_t)t * 2 * DN_C;
+        part[tid] = tmean[tid];
+        part[DN_C + tid] = (red[tid] + red[DN_C + tid]) + (red[2 * DN_C + tid] + red[3 * DN_C + tid]);
+      }
+    }
   }
 }
 
@@ -340,15 +426,19 @@ __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvP
 
 extern "C" size_t gd4d_depth_net_image_bytes(int channels) { return channels == gd4d::DN_C ? gd4d::DN_IMAGE_BYTES : 0; }
 
-extern "C" int gd4d_depth_net_image(const float* conv_w, int channels, void* image, void* stream) {
+extern "C" int gd4d_depth_net_image_mode(const float* conv_w, int channels, int transposed, void* image, void* stream) {
   using namespace gd4d;
   if (!conv_w || !image) return GD4D_EINVAL;
-  if (channels != DN_C) return GD4D_EUNSUPPORTED;
+  if (channels != DN_C || (transposed != 0 && transposed != 1)) return GD4D_EUNSUPPORTED;
   if (!aligned16(image)) return GD4D_EALIGN;
   const int items = DN_STEPS * 2 * 4 * DN_C;
   hipLaunchKernelGGL(depth_net_image_kernel, dim3((items + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), conv_w,
-                     static_cast<char*>(image));
+                     static_cast<char*>(image), transposed);
   return check_launch();
+}
+
+extern "C" int gd4d_depth_net_image(const float* conv_w, int channels, void* image, void* stream) {
+  return gd4d_depth_net_image_mode(conv_w, channels, 0, image, stream);
 }
 
 extern "C" int gd4d_cam_gate_fwd(const float* intrinsics, const float* ida00, int n, int n_ida, float scale_depth_factor,
@@ -367,15 +457,12 @@ extern "C" int gd4d_cam_gate_fwd(const float* intrinsics, const float* ida00, in
   return check_launch();
 }
 
-extern "C" int gd4d_depth_conv_fwd(const float* const* x, float* const* out, const int32_t* level_hw, int levels, int n, int channels,
-                                   const void* image, const float* bias, const float* bn_mean, const float* bn_var,
-                                   const float* bn_weight, const float* bn_bias, float eps, const float* gate, void* stream) {
-  using namespace gd4d;
-  if (!x || !out || !level_hw || !image || !bias || !bn_mean || !bn_var || !bn_weight || !bn_bias || !gate) return GD4D_EINVAL;
-  if (channels != DN_C || levels < 1 || levels > DN_MAX_LEVELS || n <= 0) return GD4D_EUNSUPPORTED;
-  if (!aligned16(image)) return GD4D_EALIGN;
-  DepthConvParams p{};
-  long long tiles = 0;
+namespace gd4d {
+
+// the level table and the tile count of a launch; GD4D_OK or the error code
+static int depth_conv_levels(DepthConvParams& p, const float* const* x, float* const* out, const int32_t* level_hw, int levels, int n,
+                             long long& tiles) {
+  tiles = 0;
   for (int l = 0; l < levels; ++l) {
     const int h = level_hw[2 * l], w = level_hw[2 * l + 1];
     if (!x[l] || !out[l] || h <= 0 || w <= 0) return GD4D_EINVAL;
@@ -390,6 +477,30 @@ extern "C" int gd4d_depth_conv_fwd(const float* const* x, float* const* out, con
     tiles += (long long)n * p.tiles_cam[l];
     if (tiles > (1ll << 30)) return GD4D_EUNSUPPORTED;
   }
+  p.levels = levels;
+  return GD4D_OK;
+}
+
+template <int EPI>
+static int depth_conv_launch(const DepthConvParams& p, long long tiles, void* stream) {
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(depth_conv_kernel<EPI>), DN_LDS)) return GD4D_ELAUNCH;
+  hipLaunchKernelGGL(depth_conv_kernel<EPI>, dim3((unsigned)tiles), dim3(DN_THREADS), DN_LDS, static_cast<hipStream_t>(stream), p);
+  return check_launch();
+}
+
+}  // namespace gd4d
+
+extern "C" int gd4d_depth_conv_fwd(const float* const* x, float* const* out, const int32_t* level_hw, int levels, int n, int channels,
+                                   const void* image, const float* bias, const float* bn_mean, const float* bn_var,
+                                   const float* bn_weight, const float* bn_bias, float eps, const float* gate, void* stream) {
+  using namespace gd4d;
+  if (!x || !out || !level_hw || !image || !bias || !bn_mean || !bn_var || !bn_weight || !bn_bias || !gate) return GD4D_EINVAL;
+  if (channels != DN_C || levels < 1 || levels > DN_MAX_LEVELS || n <= 0) return GD4D_EUNSUPPORTED;
+  if (!aligned16(image)) return GD4D_EALIGN;
+  DepthConvParams p{};
+  long long tiles = 0;
+  const int code = depth_conv_levels(p, x, out, level_hw, levels, n, tiles);
+  if (code != GD4D_OK) return code;
   p.image = static_cast<const char*>(image);
   p.bias = bias;
   p.mean = bn_mean;
@@ -398,8 +509,32 @@ extern "C" int gd4d_depth_conv_fwd(const float* const* x, float* const* out, con
   p.beta = bn_bias;
   p.gate = gate;
   p.eps = eps;
-  p.levels = levels;
-  if (!allow_dynamic_lds(reinterpret_cast<const void*>(depth_conv_kernel), DN_LDS)) return GD4D_ELAUNCH;
-  hipLaunchKernelGGL(depth_conv_kernel, dim3((unsigned)tiles), dim3(DN_THREADS), DN_LDS, static_cast<hipStream_t>(stream), p);
-  return check_launch();
+  return depth_conv_launch<DN_EPI_INFER>(p, tiles, stream);
+}
+
+extern "C" long long gd4d_depth_conv_tiles(const int32_t* level_hw, int levels, int n) {
+  if (!level_hw || levels < 1 || n <= 0) return 0;
+  long long tiles = 0;
+  for (int l = 0; l < levels; ++l) {
+    const int h = level_hw[2 * l], w = level_hw[2 * l + 1];
+    if (h <= 0 || w <= 0) return 0;
+    tiles += (long long)n * ((h + gd4d::DN_T - 1) / gd4d::DN_T) * ((w + gd4d::DN_T - 1) / gd4d::DN_T);
+  }
+  return tiles;
+}
+
+extern "C" int gd4d_depth_conv_raw(const float* const* x, float* const* y, const int32_t* level_hw, int levels, int n, int channels,
+                                   const void* image, const float* bias, float* partials, void* stream) {
+  using namespace gd4d;
+  if (!x || !y || !level_hw || !image) return GD4D_EINVAL;
+  if (channels != DN_C || levels < 1 || levels > DN_MAX_LEVELS || n <= 0) return GD4D_EUNSUPPORTED;
+  if (!aligned16(image)) return GD4D_EALIGN;
+  DepthConvParams p{};
+  long long tiles = 0;
+  const int code = depth_conv_levels(p, x, y, level_hw, levels, n, tiles);
+  if (code != GD4D_OK) return code;
+  p.image = static_cast<const char*>(image);
+  p.bias = bias;
+  p.partials = partials;
+  return partials ? depth_conv_launch<DN_EPI_STATS>(p, tiles, stream) : depth_conv_launch<DN_EPI_PLAIN>(p, tiles, stream);
 }

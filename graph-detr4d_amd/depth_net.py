@@ -12,12 +12,24 @@ the reference (`forward` returns x); it is not computed here, its parameters are
 What runs where (inference): the gate is one kernel (ops.cam_gate_fwd) reading the intrinsics / ida scales from a persistent device
 buffer (a captured graph serves new cameras after refresh_matrices), the 3x3 convolution with bias, BatchNorm (running statistics),
 ReLU and the gate as its epilogue is ONE launch over all levels (ops.depth_conv_fwd, split-bf16 x 3 on the bf16 matrix cores).
-Training (BatchNorm on batch statistics) and shapes the kernels do not take run only on the torch-op route, when chosen
+Training (BatchNorm on batch statistics) and shapes the kernels do not take run on the torch-op route, when chosen
 (`torch_ops=True` or GD4D_TORCH_OPS=1): the module's own nn.Conv2d / BatchNorm2d / MLP / SE, the reference arithmetic.
+
+Training on the kernels is opt-in (`hip_train=True`; `torch_ops=True` wins over it): one autograd node per call over all levels
+(_DepthNetTrainFunction).  Forward: the same implicit GEMM with a plain-store epilogue keeps y = conv + bias and emits per-tile
+(mean, M2) partials, ops.depth_bn_stats merges them per level in a fixed order and moves the running buffers as L BatchNorm2d calls
+would, ops.depth_bn_act_fwd writes relu(BN(y)) * gate.  Backward: ops.depth_bn_bwd (dgamma, dbeta, the gate's gradient, dy, the
+bias gradient), ops.depth_conv_wgrad (the weight gradient, K over the pixels) and the same GEMM on dy with the transposed, tap-flipped
+weight image (the input gradient).  Kept for backward: x, y, the statistics and the gate - not BatchNorm's, ReLU's or the gate's
+outputs.  In eval() mode with autograd on BatchNorm is frozen (mmdet's norm_eval): the affine map of the running statistics, no
+buffer moves, outputs bit-identical to inference.  The camera gate is ~3 MFLOP per sample: in this route it runs through the
+module's own mlp / se layers, so autograd carries the Function's gate gradient into them; the kernels multiply by the gate
+kernel's value of the same quantity (frozen outputs are then the inference path's bits).
 """
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 from . import functional as Fn
@@ -79,10 +91,74 @@ def _ida00(ida_mats, n):
     return np.array(np.broadcast_to(d, (n,)), dtype=np.float32)          # (a writable copy)
 
 
+class _DepthNetTrainFunction(torch.autograd.Function):
+    """relu(BN(conv3x3(x_l) + b)) * gate for all levels of a call as one node (launches of at most MAX_LEVELS_PER_LAUNCH levels).
+    Keeps x, y = conv + b, the per-level statistics and the gate; out is recomputed from y in backward."""
+
+    @staticmethod
+    def forward(ctx, module, frozen, gate_value, gate, weight, bias, gamma, beta, *feats):
+        # gate: the module's mlp / se layers' (N, 256), the input autograd carries the gate gradient into; gate_value: the gate
+        # kernel's bits of the same quantity, what the kernels multiply by (so that frozen outputs are the inference path's bits)
+        gate = gate_value
+        bn = module.reduce_conv[1]
+        image = module._image()
+        feats = [f.contiguous() for f in feats]
+        gate, bias, gamma, beta = (t.detach().contiguous() for t in (gate, bias, gamma, beta))
+        n = feats[0].shape[0]
+        ys, stats, outs = [], [], []
+        for i in range(0, len(feats), MAX_LEVELS_PER_LAUNCH):
+            grp = feats[i:i + MAX_LEVELS_PER_LAUNCH]
+            hw = [tuple(f.shape[2:]) for f in grp]
+            if frozen:
+                y = ops.depth_conv_raw(grp, image, bias)
+                st = ops.depth_bn_stats(None, hw, n, gamma, bn.running_mean, bn.running_var, 0.0, bn.eps, frozen=True)
+            else:
+                y, partials = ops.depth_conv_raw(grp, image, bias, want_partials=True)
+                st = ops.depth_bn_stats(partials, hw, n, gamma, bn.running_mean, bn.running_var, bn.momentum, bn.eps)
+            outs += ops.depth_bn_act_fwd(y, st, beta, gate)
+            ys += y
+            stats.append(st)
+        ctx.module, ctx.frozen, ctx.levels = module, frozen, len(feats)
+        ctx.save_for_backward(gate, weight, beta, *stats, *ys, *feats)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        saved = ctx.saved_tensors
+        nl = ctx.levels
+        groups = (nl + MAX_LEVELS_PER_LAUNCH - 1) // MAX_LEVELS_PER_LAUNCH
+        gate, weight, beta = saved[:3]
+        stats, ys, feats = saved[3:3 + groups], saved[3 + groups:3 + groups + nl], saved[3 + groups + nl:]
+        need = ctx.needs_input_grad                                         # (module, frozen, gate_value, gate, weight, bias, gamma, beta, *feats)
+        douts = [torch.zeros_like(y) if d is None else d.contiguous() for d, y in zip(douts, ys)]
+        dgate = dw = db = dgamma = dbeta = None
+        dxs = [None] * nl
+        image_t = None
+
+        def add(a, b):
+            return b.clone() if a is None else a + b                         # (the launches of a call in order: a fixed sum)
+        for k in range(groups):
+            lo, hi = k * MAX_LEVELS_PER_LAUNCH, min(nl, (k + 1) * MAX_LEVELS_PER_LAUNCH)
+            dys, g_gamma, g_beta, g_gate, g_bias = ops.depth_bn_bwd(douts[lo:hi], ys[lo:hi], stats[k], beta, gate, frozen=ctx.frozen)
+            dgate, dgamma, dbeta, db = add(dgate, g_gate), add(dgamma, g_gamma), add(dbeta, g_beta), add(db, g_bias)
+            if need[4]:
+                dw = add(dw, ops.depth_conv_wgrad(dys, list(feats[lo:hi])))
+            if any(need[8 + lo:8 + hi]):
+                if image_t is None:
+                    image_t = ctx.module._image_t()
+                for j, dx in enumerate(ops.depth_conv_raw(dys, image_t)):
+                    if need[8 + lo + j]:
+                        dxs[lo + j] = dx
+        return (None, None, None, dgate if need[3] else None, dw, db if need[5] else None, dgamma if need[6] else None,
+                dbeta if need[7] else None, *dxs)
+
+
 class DepthNet(nn.Module):
-    def __init__(self, in_channels, mid_channels, context_channels, torch_ops=False):
+    def __init__(self, in_channels, mid_channels, context_channels, torch_ops=False, hip_train=False):
         """torch_ops (not a keyword of the reference): run the module's own torch layers (the reference arithmetic, trainable) instead
-        of the library's kernels - the only route for training and for shapes the kernels do not take."""
+        of the library's kernels - the only route for shapes the kernels do not take.  hip_train (neither): make the kernel route
+        differentiable - train() mode, or eval() mode with autograd on (frozen BatchNorm), runs on the library's forward and backward
+        kernels.  Both are attributes that may be set after construction; torch_ops wins."""
         super().__init__()
         self.reduce_conv = nn.Sequential(
             nn.Conv2d(in_channels, mid_channels, kernel_size=3, stride=1, padding=1),
@@ -93,6 +169,8 @@ class DepthNet(nn.Module):
         self.mlp = Mlp(1, mid_channels, mid_channels)
         self.se = SELayer(mid_channels)
         self.torch_ops = bool(torch_ops)
+        self.hip_train = bool(hip_train)
+        self._image_t_cache = None  # (ops._Stamp, transposed weight image of reduce_conv[0]: the input gradient's)
         self._image_cache = None    # (ops._Stamp, weight image of reduce_conv[0])
         self._mats = {}             # (device, request slot, N) -> [host intrinsics, host ida00 (N), device buffer]
 
@@ -107,16 +185,24 @@ class DepthNet(nn.Module):
             Fn.require_gpu(f, 'mlvl_feats')
         if Fn.torch_ops_route(self._route_name(feats[0]), True, module=self):
             return True
-        if self.training:
+        if self.training and not self.hip_train:
             raise _lib.Gd4dError('DepthNet in train() mode: BatchNorm then normalises with batch statistics and the 3x3 convolution '
                                  'needs a backward, which graph-detr4d_amd\'s kernels do not provide.  `torch_ops=True` (or '
-                                 'GD4D_TORCH_OPS=1) runs the module\'s own torch layers, the reference arithmetic, trainable by autograd.')
+                                 'GD4D_TORCH_OPS=1) runs the module\'s own torch layers, the reference arithmetic, trainable by autograd.  '
+                                 '`hip_train=True` trains the stage on the library\'s own forward and backward kernels.')
         conv = self.reduce_conv[0]
         ok = conv.in_channels == 256 and conv.out_channels == 256 and all(f.shape[-3] == 256 and f.dtype == torch.float32 for f in feats)
         Fn.torch_ops_route(self._route_name(feats[0]), ok, module=self)       # raises when not ok
+        if self.hip_train:
+            bn = self.reduce_conv[1]
+            if self.training and (bn.momentum is None or not bn.track_running_stats):
+                raise _lib.Gd4dError('DepthNet(hip_train=True): BatchNorm2d with momentum=None or track_running_stats=False is outside '
+                                     'the kernels\' limits; `torch_ops=True` (or GD4D_TORCH_OPS=1) runs the module\'s own torch layers.')
+            return False
         if Fn.wants_grad(self, *feats):
             raise _lib.Gd4dError('DepthNet: autograd is on, and graph-detr4d_amd\'s kernels have no backward for this stage.  Run '
-                                 'inference under torch.no_grad(), or choose the torch-op route (`torch_ops=True` / GD4D_TORCH_OPS=1).')
+                                 'inference under torch.no_grad(), or choose the torch-op route (`torch_ops=True` / GD4D_TORCH_OPS=1).  '
+                                 '`hip_train=True` makes the kernel route differentiable.')
         return False
 
     @staticmethod
@@ -150,6 +236,13 @@ class DepthNet(nn.Module):
         if self._image_cache is None or not self._image_cache[0].valid((w,)):
             self._image_cache = (ops._Stamp((w,)), ops.depth_net_image(w.detach()))
         return self._image_cache[1]
+
+    def _image_t(self):
+        """The transposed, tap-flipped weight's image (the input gradient's GEMM), under the same validity rule as _image."""
+        w = self.reduce_conv[0].weight
+        if self._image_t_cache is None or not self._image_t_cache[0].valid((w,)):
+            self._image_t_cache = (ops._Stamp((w,)), ops.depth_net_image_t(w.detach()))
+        return self._image_t_cache[1]
 
     def _matrices_device(self, intrin, ida00, dev, capturing=False):
         """The intrinsics (N, 4, 4) and ida scales (N) on the device: ONE persistent buffer per (device, request slot, N),
@@ -199,11 +292,39 @@ class DepthNet(nn.Module):
                                        bn.weight.detach(), bn.bias.detach(), bn.eps, gate)
         return outs
 
+    def _gate_torch_device(self, intrin, ida00, scale_depth_factor, dev):
+        """The gate (N, 256) through the module's own mlp / se layers (differentiable), _gate_input_torch's arithmetic on the
+        matrices of the persistent device buffer: nothing waits for the device."""
+        k_dev, ida_dev = self._matrices_device(intrin, ida00, dev, capturing=torch.cuda.is_current_stream_capturing())
+        with torch.no_grad():
+            inv = torch.linalg.inv_ex(k_dev).inverse                                                          # :89 (no error check: no sync)
+            pixel_size = torch.sqrt(inv[:, 0, 0] ** 2 + inv[:, 1, 1] ** 2).reshape(-1, 1)                     # :91-93
+            aug_scale = torch.sqrt(ida_dev ** 2 + ida_dev ** 2).reshape(-1, 1)                                # :93-94
+            s = pixel_size * scale_depth_factor / aug_scale
+        # se's 1x1 convolutions on (N, 256, 1, 1) taken as linears on (N, 256): the same sums, and a backward that repeats bit
+        # for bit (the library convolution's input gradient does not: docs/measurements_r16.md, section 4)
+        se = self.se
+        r = se.act1(F.linear(self.mlp(s), se.conv_reduce.weight.flatten(1), se.conv_reduce.bias))
+        return se.gate(F.linear(r, se.conv_expand.weight.flatten(1), se.conv_expand.bias))
+
+    def _forward_hip_train(self, feats, intrin, ida00, scale_depth_factor):
+        gate = self._gate_torch_device(intrin, ida00, scale_depth_factor, feats[0].device)
+        with torch.no_grad():
+            gate_value = self._gate(intrin, ida00, scale_depth_factor, feats[0].device)
+        conv, bn = self.reduce_conv[0], self.reduce_conv[1]
+        frozen = not self.training
+        outs = _DepthNetTrainFunction.apply(self, frozen, gate_value, gate, conv.weight, conv.bias, bn.weight, bn.bias, *feats)
+        if not frozen:
+            bn.num_batches_tracked.add_(len(feats))          # one BatchNorm2d call per level
+        return list(outs)
+
     def _run(self, feats, intrin, ida00, scale_depth_factor):
         if len({f.shape[0] for f in feats}) != 1:
             raise ValueError('DepthNet: every level must hold the same cameras')
         if self._uses_torch_ops(feats):
             return self._forward_torch(feats, intrin, ida00, scale_depth_factor)
+        if self.hip_train and (self.training or Fn.wants_grad(self, *feats)):
+            return self._forward_hip_train(feats, intrin, ida00, scale_depth_factor)
         with torch.no_grad():
             return self._forward_hip(feats, intrin, ida00, scale_depth_factor)
 

@@ -2909,6 +2909,139 @@ def depth_conv_fwd(feats, image, bias, bn_mean, bn_var, bn_weight, bn_bias, eps,
     return outs
 
 
+def _depth_levels(what, *lists):
+    """The level table of a DepthNet training call: every list holds L (N, C, H_l, W_l) tensors of the same shapes."""
+    first = lists[0]
+    nl, n, c = len(first), first[0].shape[0], first[0].shape[1]
+    if any(f.dim() != 4 or f.shape[0] != n or f.shape[1] != c for f in first):
+        raise ValueError(f'{what}: levels (N, C, H, W) with the same N and C expected')
+    for other in lists[1:]:
+        if len(other) != nl or any(tuple(o.shape) != tuple(f.shape) for o, f in zip(other, first)):
+            raise ValueError(f'{what}: every list must match the levels\' shapes')
+    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in first for x in f.shape[2:]])
+    return nl, int(n), int(c), lv
+
+
+def _depth_ptrs(tensors, name):
+    return (ctypes.c_void_p * len(tensors))(*[_dev(t, name, torch.float32).value for t in tensors])
+
+
+def depth_net_image_t(conv_w):
+    """gd4d_depth_net_image_mode(transposed = 1): the image of w'[ic, oc, 2 - ky, 2 - kx] = w[oc, ic, ky, kx], with which depth_conv_raw run
+    on dy gives the input gradient (remake it when the weight changes, as depth_net_image)."""
+    lib = _lib.load()
+    c = conv_w.shape[0]
+    nbytes = int(lib.gd4d_depth_net_image_bytes(int(c)))
+    if nbytes == 0 or tuple(conv_w.shape) != (c, c, 3, 3):
+        raise _lib.Gd4dError(f'depth_net_image_t: weight {tuple(conv_w.shape)}; the kernel takes (256, 256, 3, 3)')
+    img = torch.empty(nbytes, device=conv_w.device, dtype=torch.uint8)
+    code = lib.gd4d_depth_net_image_mode(_dev(conv_w.contiguous(), 'conv_w', torch.float32), int(c), 1, _dev(img, 'image', torch.uint8),
+                                         _stream())
+    _lib.check(code, 'gd4d_depth_net_image_mode')
+    return img
+
+
+def depth_conv_tiles(level_hw, n):
+    """gd4d_depth_conv_tiles: the number of 16 x 16 tiles of the levels [(H, W), ...] with N cameras (the conv's grid)."""
+    lv = (ctypes.c_int32 * (2 * len(level_hw)))(*[int(v) for hw in level_hw for v in hw])
+    return int(_lib.load().gd4d_depth_conv_tiles(lv, len(level_hw), int(n)))
+
+
+def depth_conv_raw(feats, image, bias=None, want_partials=False, outs=None):
+    """gd4d_depth_conv_raw: L <= 4 levels (N, 256, H_l, W_l) -> conv3x3 (+ bias) per level, one launch, no BatchNorm / ReLU / gate.
+    want_partials: also returns the (tiles, 2, 256) per-tile mean / M2 partials depth_bn_stats merges."""
+    lib = _lib.load()
+    f32 = torch.float32
+    if outs is None:
+        outs = [torch.empty(f.shape, device=f.device, dtype=f32) for f in feats]
+    nl, n, c, lv = _depth_levels('depth_conv_raw', feats, outs)
+    partials = None
+    if want_partials:
+        tiles = int(lib.gd4d_depth_conv_tiles(lv, nl, n))
+        partials = torch.empty(max(tiles, 1), 2, 256, device=feats[0].device, dtype=f32)
+    code = lib.gd4d_depth_conv_raw(_depth_ptrs(feats, 'feats'), _depth_ptrs(outs, 'outs'), lv, nl, n, c, _dev(image, 'image', torch.uint8),
+                                   None if bias is None else _dev(bias, 'bias', f32),
+                                   None if partials is None else _dev(partials, 'partials', f32), _stream())
+    _lib.check(code, 'gd4d_depth_conv_raw')
+    return (outs, partials) if want_partials else outs
+
+
+def depth_bn_stats(partials, level_hw, n, bn_weight, running_mean, running_var, momentum, eps, frozen=False):
+    """gd4d_depth_bn_stats: stats (L, 3, 256) = mu, rstd, scale per level from depth_conv_raw's partials (frozen: from the running
+    buffers, partials may be None); not frozen: running_mean / running_var are updated in place, level after level."""
+    lib = _lib.load()
+    f32 = torch.float32
+    nl = len(level_hw)
+    lv = (ctypes.c_int32 * (2 * nl))(*[int(v) for hw in level_hw for v in hw])
+    if not frozen and partials is None:
+        raise ValueError('depth_bn_stats: partials are needed unless frozen')
+    stats = torch.empty(nl, 3, 256, device=bn_weight.device, dtype=f32)
+    code = lib.gd4d_depth_bn_stats(None if partials is None else _dev(partials, 'partials', f32), lv, nl, int(n), int(bn_weight.shape[0]),
+                                   _dev(bn_weight, 'bn_weight', f32), _dev(running_mean, 'running_mean', f32),
+                                   _dev(running_var, 'running_var', f32), float(momentum), float(eps), int(bool(frozen)),
+                                   _dev(stats, 'stats', f32), _stream())
+    _lib.check(code, 'gd4d_depth_bn_stats')
+    return stats
+
+
+def depth_bn_act_fwd(ys, stats, bn_bias, gate, outs=None):
+    """gd4d_depth_bn_act_fwd: out_l = relu((y_l - mu_l) scale_l + bn_bias) * gate[:, :, None, None] for L <= 4 levels."""
+    lib = _lib.load()
+    f32 = torch.float32
+    if outs is None:
+        outs = [torch.empty_like(y) for y in ys]
+    nl, n, c, lv = _depth_levels('depth_bn_act_fwd', ys, outs)
+    if tuple(stats.shape) != (nl, 3, c) or tuple(gate.shape) != (n, c):
+        raise ValueError(f'depth_bn_act_fwd: stats ({nl}, 3, {c}) and gate ({n}, {c}) expected')
+    code = lib.gd4d_depth_bn_act_fwd(_depth_ptrs(ys, 'ys'), _depth_ptrs(outs, 'outs'), lv, nl, n, c, _dev(stats, 'stats', f32),
+                                     _dev(bn_bias, 'bn_bias', f32), _dev(gate, 'gate', f32), _stream())
+    _lib.check(code, 'gd4d_depth_bn_act_fwd')
+    return outs
+
+
+def depth_bn_bwd(douts, ys, stats, bn_bias, gate, frozen=False):
+    """gd4d_depth_bn_bwd: the BatchNorm / ReLU / gate backward of L <= 4 levels -> (dy list, dgamma, dbeta, dgate (N, 256), dbias),
+    dgamma / dbeta / dgate / dbias summed over the levels of the call."""
+    lib = _lib.load()
+    f32 = torch.float32
+    dys = [torch.empty_like(y) for y in ys]
+    nl, n, c, lv = _depth_levels('depth_bn_bwd', ys, douts, dys)
+    if tuple(stats.shape) != (nl, 3, c) or tuple(gate.shape) != (n, c):
+        raise ValueError(f'depth_bn_bwd: stats ({nl}, 3, {c}) and gate ({n}, {c}) expected')
+    dev = ys[0].device
+    ws = torch.empty(max(int(lib.gd4d_depth_bn_bwd_workspace_bytes(nl, n)) // 4, 1), device=dev, dtype=f32)
+    small = torch.empty(3 + n, c, device=dev, dtype=f32)
+    dgamma, dbeta, dbias, dgate = small[0], small[1], small[2], small[3:]
+    code = lib.gd4d_depth_bn_bwd(_depth_ptrs(douts, 'douts'), _depth_ptrs(ys, 'ys'), _depth_ptrs(dys, 'dys'), lv, nl, n, c,
+                                 _dev(stats, 'stats', f32), _dev(bn_bias, 'bn_bias', f32), _dev(gate, 'gate', f32), int(bool(frozen)),
+                                 _dev(ws, 'workspace', f32), _dev(dgamma, 'dgamma', f32), _dev(dbeta, 'dbeta', f32),
+                                 _dev(dgate, 'dgate', f32), _dev(dbias, 'dbias', f32), _stream())
+    _lib.check(code, 'gd4d_depth_bn_bwd')
+    return dys, dgamma, dbeta, dgate, dbias
+
+
+def depth_conv_wgrad(dys, feats, partitions=None):
+    """gd4d_depth_conv_wgrad: dW (256, 256, 3, 3) = sum over L <= 4 levels, cameras and pixels of dy[oc, p] x[ic, p + tap], one launch
+    plus the reduction over `partitions` partial sums (default: one workgroup per compute unit, at most one partition per tile)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    nl, n, c, lv = _depth_levels('depth_conv_wgrad', feats, dys)
+    dev = feats[0].device
+    if partitions is None:
+        tiles = int(lib.gd4d_depth_conv_tiles(lv, nl, n))
+        partitions = max(1, min(tiles, torch.cuda.get_device_properties(dev).multi_processor_count // 8))
+    partitions = int(partitions)
+    nbytes = int(lib.gd4d_depth_conv_wgrad_workspace_bytes(partitions))
+    if nbytes == 0:
+        raise ValueError(f'depth_conv_wgrad: partitions = {partitions}')
+    ws = torch.empty(nbytes // 4, device=dev, dtype=f32)
+    dw = torch.empty(256, 256, 3, 3, device=dev, dtype=f32)
+    code = lib.gd4d_depth_conv_wgrad(_depth_ptrs(dys, 'dys'), _depth_ptrs(feats, 'feats'), lv, nl, n, c, partitions,
+                                     _dev(ws, 'workspace', f32), _dev(dw, 'dw', f32), _stream())
+    _lib.check(code, 'gd4d_depth_conv_wgrad')
+    return dw
+
+
 def _first_tensor(args):
     for a in args:
         if torch.is_tensor(a):

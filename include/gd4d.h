@@ -1198,6 +1198,42 @@ int gd4d_depth_conv_fwd(const float* const* x, float* const* out, const int32_t*
                         const void* image, const float* bias, const float* bn_mean, const float* bn_var, const float* bn_weight,
                         const float* bn_bias, float eps, const float* gate, void* stream);
 
+/* Training of the same stage (gd4d_depth_net.hip, gd4d_depth_net_train.hip; additive exports, the ABI version stays).  Per level,
+ * y = conv3x3(x) + bias, xhat = (y - mu) rstd, z = bn_weight xhat + bn_bias, out = relu(z) gate[n, c].  Same limits and error codes as
+ * gd4d_depth_conv_fwd; x / y / out / dout / dy / level_hw are HOST arrays of device pointers / sizes; nothing synchronises.
+ * gd4d_depth_net_image_mode - transposed = 0: gd4d_depth_net_image; 1: the image of w'[ic, oc, 2 - ky, 2 - kx] = w[oc, ic, ky, kx], with
+ *   which gd4d_depth_conv_raw run on dy gives dx (other values: GD4D_EUNSUPPORTED).
+ * gd4d_depth_conv_tiles - the number of 16 x 16 tiles of a launch (its grid; 0 on bad arguments).
+ * gd4d_depth_conv_raw - the same implicit GEMM with the plain-store epilogue: y = conv (+ bias when not NULL).  partials not NULL
+ *   (gd4d_depth_conv_tiles x 2 x 256 floats): also each tile's per-channel mean and M2 of y over its valid pixels, in a fixed order.
+ * gd4d_depth_bn_stats - merges the partials per (level, channel) in a fixed order (Chan's update), writes stats (levels, 3, 256) =
+ *   mu, rstd = 1 / sqrt(var + eps) (biased var), scale = bn_weight rstd, and updates running_mean / running_var level after level as
+ *   BatchNorm2d does (momentum; the unbiased variance; N H_l W_l < 2: GD4D_EUNSUPPORTED).  frozen != 0: stats from the running buffers
+ *   (scale = bn_weight / sqrt(var + eps), the inference epilogue's), partials unused, buffers untouched.
+ * gd4d_depth_bn_act_fwd - out = relu((y - mu) scale + bn_bias) gate, elementwise, in gd4d_depth_conv_fwd's order of operations.
+ * gd4d_depth_bn_bwd - with dz = dout gate [z > 0]: dbeta = sum dz, dgamma = sum dz xhat (both over the levels of the call),
+ *   dgate[n, c] = sum dout relu(z), dy = scale (dz - dbeta_l / M_l - xhat dgamma_l / M_l) (frozen: scale dz), dbias = sum dy; every
+ *   sum in a fixed order, no atomics.  workspace: gd4d_depth_bn_bwd_workspace_bytes(levels, n).
+ * gd4d_depth_conv_wgrad - dw (256, 256, 3, 3) = sum over levels, cameras and pixels of dy[oc, p] x[ic, p + (ky - 1, kx - 1)] (zero
+ *   padding) on the split-bf16 x 3 MFMA: 8 x partitions workgroups write partial sums over their share of the tile list into workspace
+ *   (gd4d_depth_conv_wgrad_workspace_bytes(partitions), 16-B aligned; partitions beyond the tile count write zeros), a second kernel
+ *   adds them in order.  1 <= partitions <= 4096. */
+int gd4d_depth_net_image_mode(const float* conv_w, int channels, int transposed, void* image, void* stream);
+long long gd4d_depth_conv_tiles(const int32_t* level_hw, int levels, int n);
+int gd4d_depth_conv_raw(const float* const* x, float* const* y, const int32_t* level_hw, int levels, int n, int channels,
+                        const void* image, const float* bias, float* partials, void* stream);
+int gd4d_depth_bn_stats(const float* partials, const int32_t* level_hw, int levels, int n, int channels, const float* bn_weight,
+                        float* running_mean, float* running_var, float momentum, float eps, int frozen, float* stats, void* stream);
+int gd4d_depth_bn_act_fwd(const float* const* y, float* const* out, const int32_t* level_hw, int levels, int n, int channels,
+                          const float* stats, const float* bn_bias, const float* gate, void* stream);
+size_t gd4d_depth_bn_bwd_workspace_bytes(int levels, int n);
+int gd4d_depth_bn_bwd(const float* const* dout, const float* const* y, float* const* dy, const int32_t* level_hw, int levels, int n,
+                      int channels, const float* stats, const float* bn_bias, const float* gate, int frozen, float* workspace,
+                      float* dgamma, float* dbeta, float* dgate, float* dbias, void* stream);
+size_t gd4d_depth_conv_wgrad_workspace_bytes(int partitions);
+int gd4d_depth_conv_wgrad(const float* const* dy, const float* const* x, const int32_t* level_hw, int levels, int n, int channels,
+                          int partitions, float* workspace, float* dw, void* stream);
+
 /* Detr4D_Distiller's instance distillation term (distillation/distillers/detr4d_distiller.py:143-166, gd4d_distill.hip): the student's
  * predictions of every decoder layer are MATCHED against the teacher's, which act as pseudo ground truth.
  *

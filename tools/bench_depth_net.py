@@ -5,6 +5,12 @@ reference arithmetic) on the same GPU and inputs, the two routes alternated in t
 feature stage (DepthNet + FeaturePositionEmbedding(channels_last_out=True)).  Prints ONE JSON line.
 
     python tools/bench_depth_net.py [--reps 20] [--hip-only]
+    python tools/bench_depth_net.py --train [--reps 10] [--hip-only]
+
+--train: forward + backward of forward_levels in train() mode (loss = sum of the outputs times fixed random tensors; gradients to
+every parameter and to the input maps) at 12 and 24 cameras, `hip_train=True` against `torch_ops=True` (the only training route
+without it), alternated call by call on the same inputs; also each route's peak memory above what is resident before the call
+(torch.cuda.max_memory_allocated).  The weight gradient's share of the bf16 spec is read from a kernel trace, not from here.
 
 Timing: device events around each call, after a warm-up of every shape; medians.  FLOP counts from shapes: the convolution
 needs 2 * 9 * 256 * 256 FLOP per output pixel; the kernel runs three bf16 products per multiply-add (split-bf16 x 3), so its rate of
@@ -66,13 +72,58 @@ def metas_for(n):
     return metas
 
 
+def train_main(a):
+    res = {'metric': 'DepthNet.forward_levels forward + backward ms per sample, train() mode (B = 1, R50 pyramid)', 'levels': R50}
+    for n in (12, 24):
+        feats = [f.requires_grad_() for f in synthetic.feature_pyramid(n, levels=R50, device='cuda')]
+        metas = metas_for(n)
+        torch.manual_seed(n)
+        rs = [torch.randn(f.shape[1:], device='cuda') for f in feats]
+        mods = {'hip': module(0).train()}
+        mods['hip'].hip_train = True
+        if not a.hip_only:
+            mods['torch'] = module(0).train()
+            mods['torch'].torch_ops = True
+
+        def step(mod):
+            def run():
+                for p in mod.parameters():
+                    p.grad = None
+                for f in feats:
+                    f.grad = None
+                outs = mod.forward_levels(feats, metas)
+                sum((o[0] * r).sum() for o, r in zip(outs, rs)).backward()
+            return run
+        fns = {k: step(m) for k, m in mods.items()}
+        t = alternate(fns, a.reps)
+        pixels = n * sum(h * w for h, w in R50)
+        out = {'cams': n, 'pixels': pixels, 'tflop_per_conv_pass': 2 * 9 * 256 * 256 * pixels / 1e12}
+        for k, f in fns.items():
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            f()
+            torch.cuda.synchronize()
+            out[f'{k}_fwd_bwd_ms'] = t[k]
+            out[f'{k}_peak_mib_above_resident'] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+        res[f'cams{n}'] = out
+        del feats, rs, mods, fns
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--reps', type=int, default=None)
+    ap.add_argument('--train', action='store_true', help='forward + backward in train() mode: hip_train=True beside torch_ops=True')
     ap.add_argument('--hip-only', action='store_true', help='only the library\'s route (what a rocprofv3 run should see)')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_depth_net.py needs a GPU')
+    if a.reps is None:
+        a.reps = 10 if a.train else 20
+    if a.train:
+        return train_main(a)
     mod = module(0)
     res = {'metric': 'DepthNet.forward_levels ms per sample (B = 1, R50 pyramid)', 'levels': R50}
     with torch.no_grad():
