@@ -20,6 +20,7 @@ from .dgcnn_attn import DGCNNAttn  # noqa: F401
 from .head_pe import FeaturePositionEmbedding  # noqa: F401
 from .depth_net import DepthNet  # noqa: F401
 from .recipe import TrainRecipe  # noqa: F401
+from .grid_mask import GridMask  # noqa: F401
 from . import functional, plumbing  # noqa: F401
 from .detr3d_transformer import (Detr3DCrossAtten, Detr3DCrossAttenV2, Detr3DTransformer, Detr3DTransformerDecoder,  # noqa: F401
                                  HDetr3DTransformer, feature_sampling, inverse_sigmoid)
@@ -27,4 +28,4 @@ from .detr3d_transformer import (Detr3DCrossAtten, Detr3DCrossAttenV2, Detr3DTra
 __all__ = ['Deform3DCrossAttn', 'Deform3DCrossAttnMP', 'DGCNNAttn', 'Detr3DCrossAtten', 'Detr3DCrossAttenV2', 'feature_sampling', 'Detr3DTransformer',
            'Detr3DTransformerDecoder', 'HDetr3DTransformer', 'MultiheadAttention', 'FFN', 'BaseTransformerLayer',
            'DetrTransformerDecoderLayer', 'TransformerLayerSequence', 'inverse_sigmoid',
-           'NMSFreeCoder', 'HungarianAssigner3D', 'Detr3DCriterion', 'HDetr3DCriterion', 'DistillHungarianAssigner3D', 'get_instance_distill_loss', 'FeatureDistillLoss', 'get_feat_distill_loss', 'FeaturePositionEmbedding', 'DepthNet', 'TrainRecipe', 'BBOX_CODERS', 'BBOX_ASSIGNERS', 'ATTENTION', 'TRANSFORMER', 'TRANSFORMER_LAYER', 'TRANSFORMER_LAYER_SEQUENCE']
+           'NMSFreeCoder', 'HungarianAssigner3D', 'Detr3DCriterion', 'HDetr3DCriterion', 'DistillHungarianAssigner3D', 'get_instance_distill_loss', 'FeatureDistillLoss', 'get_feat_distill_loss', 'FeaturePositionEmbedding', 'DepthNet', 'TrainRecipe', 'GridMask', 'BBOX_CODERS', 'BBOX_ASSIGNERS', 'ATTENTION', 'TRANSFORMER', 'TRANSFORMER_LAYER', 'TRANSFORMER_LAYER_SEQUENCE']

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get('GD4D_LIB_PATH') or os.path.join(_HERE, 'libgd4d.so') 
 ABI_VERSION = 56
 PIXEL_MAJOR, HEAD_MAJOR = 0, 1
 
-F32, BF16 = 0, 1
+F32, BF16, F16 = 0, 1, 2
 
 _c = ctypes
 _vp, _i, _f = _c.c_void_p, _c.c_int, _c.c_float
@@ -159,6 +159,8 @@ SIGNATURES = {
     'gd4d_decoder_request_run': (_i, [_vp, _vp, _i, _vp, _vp]),
     'gd4d_decoder_request_destroy': (_i, [_vp]),
     'gd4d_decoder_request_describe': (_c.c_char_p, [_vp, _i]),
+    'gd4d_grid_mask_fwd': (_i, [_vp, _vp] + [_i] * 14 + [_vp, _vp, _i, _vp]),
+    'gd4d_grid_mask_draw': (_i, [_vp, _vp, _i, _c.c_double, _vp]),
 }
 
 _lib = None

@@ -3042,6 +3042,52 @@ def depth_conv_wgrad(dys, feats, partitions=None):
     return dw
 
 
+_GRID_MASK_DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+GRID_MASK_BLOCK_WORDS, GRID_MASK_STATE_WORDS = 8, 4
+
+
+def grid_mask_fwd(x, d=2, l=1, st_h=0, st_w=0, use_h=True, use_w=True, mode=0, offset=None, out=None, out_dtype=None, apply=True,
+                  block=None, gen_offset=False):
+    """gd4d_grid_mask_fwd: GridMask (models/utils/grid_mask.py:84-123, angle 0) on x (R, C, H, W) fp32 / fp16 / bf16 in one pass.
+    out: None (a new tensor of out_dtype, default x's), a tensor, or x itself (in place).  Parameters by value, or `block`: the (8,)
+    int32 device tensor {apply, d, l, st_h, st_w, seed_lo, seed_hi, step} the kernel reads at run time (grid_mask_draw fills it).
+    offset: (H, W) fp32 device tensor; gen_offset=True: the per-pixel values of gd4d_grid_mask_rng.h from the block's seed and step."""
+    if x.dim() != 4:
+        raise ValueError(f'grid_mask_fwd: x (R, C, H, W) expected, got {tuple(x.shape)}')
+    if x.dtype not in _GRID_MASK_DTYPES:
+        raise TypeError(f'grid_mask_fwd: x must be float32, float16 or bfloat16, got {x.dtype}')
+    xp = _dev(x, 'x')
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=out_dtype or x.dtype)
+    if out.shape != x.shape or out.dtype not in _GRID_MASK_DTYPES or (out_dtype is not None and out.dtype != out_dtype):
+        raise ValueError(f'grid_mask_fwd: out must have x\'s shape and the dtype asked for, got {tuple(out.shape)} {out.dtype}')
+    r, c, h, w = x.shape
+    optr = _dev(offset, 'offset', torch.float32) if offset is not None else None
+    if offset is not None and tuple(offset.shape) != (h, w):
+        raise ValueError(f'grid_mask_fwd: offset ({h}, {w}) expected, got {tuple(offset.shape)}')
+    bptr = None
+    if block is not None:
+        if block.numel() != GRID_MASK_BLOCK_WORDS:
+            raise ValueError('grid_mask_fwd: block is the (8,) int32 parameter block')
+        bptr = _dev(block, 'block', torch.int32)
+    code = _lib.load().gd4d_grid_mask_fwd(xp, _dev(out, 'out'), _GRID_MASK_DTYPES[x.dtype], _GRID_MASK_DTYPES[out.dtype], r, c, h, w,
+                                          int(bool(apply)), int(d), int(l), int(st_h), int(st_w), int(bool(use_h)), int(bool(use_w)),
+                                          int(mode), optr, bptr, int(bool(gen_offset)), _stream())
+    _lib.check(code, 'gd4d_grid_mask_fwd')
+    return out
+
+
+def grid_mask_draw(state, block, h, ratio):
+    """gd4d_grid_mask_draw: one step's draws from state (4,) int32 {seed_lo, seed_hi, step, thresh} into block (8,) int32; the step
+    counter in `state` advances by one.  On the current stream, capturable."""
+    if state.numel() != GRID_MASK_STATE_WORDS or block.numel() != GRID_MASK_BLOCK_WORDS:
+        raise ValueError('grid_mask_draw: state (4,) and block (8,) int32 expected')
+    code = _lib.load().gd4d_grid_mask_draw(_dev(state, 'state', torch.int32), _dev(block, 'block', torch.int32), int(h), float(ratio),
+                                           _stream())
+    _lib.check(code, 'gd4d_grid_mask_draw')
+    return block
+
+
 def _first_tensor(args):
     for a in args:
         if torch.is_tensor(a):

@@ -72,13 +72,23 @@ class ImageFeatureExtractor(nn.Module):
     channels_last=True: the same logical (B, N, C, H, W) tensors, STORED (B, N, H, W, C) - torch.channels_last on the
     folded (B*N, C, H, W) maps, which is what a backbone run in channels_last memory format returns anyway.  The decoder's
     cross-attention then gathers them in place (ops.PyramidView.channels_last_levels): the reference's per-layer
-    flatten / transpose / cat (deform3d_cross_attn.py:264-276) and this build's once-per-sample copy both disappear."""
+    flatten / transpose / cat (deform3d_cross_attn.py:264-276) and this build's once-per-sample copy both disappear.
 
-    def __init__(self, backbone, neck=None, out_device=None, channels_last=False):
+    use_grid_mask=True (every training config of the reference sets it): the detector's
+    GridMask(True, True, rotate=1, offset=False, ratio=0.5, mode=1, prob=0.7) (:36) is applied to the folded images in front of the
+    backbone (:53-54) - in training mode only, as the module itself decides.  grid_mask=<a GridMask>: that module instead (its
+    device_draw route, an out_dtype for a half-precision backbone).  The default builds none."""
+
+    def __init__(self, backbone, neck=None, out_device=None, channels_last=False, use_grid_mask=False, grid_mask=None):
         super().__init__()
         self.img_backbone, self.img_neck = backbone, neck
         self.out_device = out_device
         self.channels_last = bool(channels_last)
+        if grid_mask is None and use_grid_mask:
+            from .grid_mask import GridMask
+            grid_mask = GridMask(True, True, rotate=1, offset=False, ratio=0.5, mode=1, prob=0.7)
+        self.use_grid_mask = grid_mask is not None
+        self.grid_mask = grid_mask
 
     def forward(self, img, img_metas):
         if img is None:
@@ -90,6 +100,8 @@ class ImageFeatureExtractor(nn.Module):
             img = img.unsqueeze(0)
         b, n = img.shape[:2]
         x = img.reshape(b * n, *img.shape[2:])
+        if self.grid_mask is not None:
+            x = self.grid_mask(x)
         feats = self.img_backbone(x)
         if isinstance(feats, dict):
             feats = list(feats.values())

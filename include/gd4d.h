@@ -31,7 +31,7 @@ extern "C" {
 
 #define GD4D_ABI_VERSION 56
 
-enum { GD4D_F32 = 0, GD4D_BF16 = 1 };
+enum { GD4D_F32 = 0, GD4D_BF16 = 1, GD4D_F16 = 2 };   /* GD4D_F16: gd4d_grid_mask_fwd only */
 
 /* Layout of the projected value tensor (output of gd4d_value_proj_*, input of gd4d_cross_attn_fwd):
  *   PIXEL_MAJOR (B*N, S, Hh, Dh) - what mmcv's MultiScaleDeformableAttnFunction takes (deform3d_cross_attn.py:280)
@@ -1405,6 +1405,38 @@ int gd4d_decoder_request_run(gd4d_decoder_request* req, const gd4d_request_bindi
                              void* side_stream);
 int gd4d_decoder_request_destroy(gd4d_decoder_request* req);
 const char* gd4d_decoder_request_describe(const gd4d_decoder_request* req, int i);
+
+/* --------------------------------------------------------------------------------------------
+ * GridMask (models/utils/grid_mask.py:84-123, gd4d_grid_mask.hip): the image augmentation Detr3D.extract_img_feat applies to the
+ * folded (B*N, 3, H, W) images in front of the backbone (detectors/detr3d.py:36, 53-54).  The reference builds a 1.5H x 1.5W mask on
+ * the host, crops and uploads it; with rotate = 1 (angle 0) the cropped mask has a closed form.  With hh = int(1.5 H),
+ * ww = int(1.5 W), Y = y + (hh - H) / 2, X = x + (ww - W) / 2 (integer divisions):
+ *     row y is in a band     <=>  use_h, k = Y - st_h >= 0, k / d < hh / d, k % d < l      (the reference draws hh / d bands only)
+ *     column x likewise with X, st_w, ww, use_w
+ *     mask = 0 in a band row or a band column, else 1;  mode 1: mask = 1 - mask
+ *     out = x mask,  or with an offset map  out = mask ? x : offset[y, x]
+ * Masked elements are written as +0 (or the offset) without being read: inputs are images, which are finite.
+ *
+ * gd4d_grid_mask_fwd - x (R, C, H, W) of in_dtype -> out of out_dtype, one pass; the R C planes share the mask.  in_dtype / out_dtype:
+ *   GD4D_F32 / GD4D_F16 / GD4D_BF16, equal, or GD4D_F32 in and a 16-bit type out (the cast is round-to-nearest-even and rides in the
+ *   same pass); another pair: GD4D_EUNSUPPORTED.  out == x works in place (differing dtypes then: GD4D_EINVAL).  offset: (H, W) fp32
+ *   or NULL.  Parameters: by value (apply, d, l, st_h, st_w), or - block != NULL - eight 32-bit device words
+ *   {apply, d, l, st_h, st_w, seed_lo, seed_hi, step} the KERNEL reads, so a captured launch follows whatever the block holds at
+ *   replay; the values in the call are then ignored.  apply == 0: an out-of-place call copies (and casts), an in-place call changes
+ *   nothing.  gen_offset != 0 (needs block, excludes offset; GD4D_EINVAL otherwise): masked pixels get the per-pixel value of
+ *   gd4d_grid_mask_rng.h for the block's (seed, step, y W + x), in [-1, 1).
+ *   16-byte accesses per lane when W is a multiple of 16 / sizeof(in) and x, out (and offset) are 16-byte aligned; any other width or
+ *   alignment is served element by element.  Nothing is allocated, nothing synchronises.
+ *   GD4D_EINVAL: a NULL x / out, R, C, W <= 0, H < 3, mode not 0 / 1, and - by value - d < 2, l outside [1, d - 1], st_h or st_w
+ *   outside [0, d).  GD4D_EUNSUPPORTED: H W >= 2^31 or R C H >= 2^31.  All checked before any launch.
+ * gd4d_grid_mask_draw - one tiny launch: reads state = {seed_lo, seed_hi, step, thresh} (four 32-bit device words; thresh =
+ *   round(prob 2^32) clamped to 2^32 - 1), writes the step's draws into `block` (gd4d_grid_mask_rng.h is the contract: gate, d in
+ *   [2, H), l = min(max(int(d ratio + 0.5), 1), d - 1), st_h and st_w in [0, d)) together with the seed and the step, and advances
+ *   state's step by one.  GD4D_EINVAL: a NULL pointer, H < 3, ratio outside [0, 65536]. */
+int gd4d_grid_mask_fwd(const void* x, void* out, int in_dtype, int out_dtype, int R, int C, int H, int W, int apply, int d, int l,
+                       int st_h, int st_w, int use_h, int use_w, int mode, const float* offset, const int32_t* block, int gen_offset,
+                       void* stream);
+int gd4d_grid_mask_draw(uint32_t* state, int32_t* block, int H, double ratio, void* stream);
 
 #ifdef __cplusplus
 }
