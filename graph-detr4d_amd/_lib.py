@@ -161,6 +161,11 @@ SIGNATURES = {
     'gd4d_decoder_request_describe': (_c.c_char_p, [_vp, _i]),
     'gd4d_grid_mask_fwd': (_i, [_vp, _vp] + [_i] * 14 + [_vp, _vp, _i, _vp]),
     'gd4d_grid_mask_draw': (_i, [_vp, _vp, _i, _c.c_double, _vp]),
+    'gd4d_fpn_lateral_image_bytes': (_c.c_size_t, [_i]),
+    'gd4d_fpn_lateral_image': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_fpn_lateral_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    'gd4d_fpn_conv_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
+    'gd4d_fpn_extra_conv_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
 }
 
 _lib = None

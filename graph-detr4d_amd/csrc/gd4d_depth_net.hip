@@ -41,6 +41,10 @@
 // Training (gd4d_depth_net_train.hip has the rest): depth_conv_kernel<EPI> - the same GEMM with a second epilogue that stores
 // y = conv + bias and each tile's per-channel (mean, M2) (125 VGPRs, no scratch) and a third, plain-store one (121 VGPRs, no scratch)
 // that is also the input gradient: gd4d_depth_net_image_mode(transposed = 1) lays out w'[ic, oc, 2 - ky, 2 - kx] = w[oc, ic, ky, kx].
+// The FPN neck (gd4d_fpn.hip has its other kernels): gd4d_fpn_conv_fwd is two more epilogues of this GEMM, DN_EPI_LEVELS (plain store,
+// NCHW) and DN_EPI_LEVELS_CL (the tile stored channels-last, (N, H, W, 256): a lane's 16 channels as four 16-byte runs), in which the
+// tile's LEVEL picks the weight image and the bias (level_image / level_bias; the other epilogues never read them and compile to the
+// code they were: second instantiations, not a shared one).
 // Left off: padding the stages, two workgroups per CU, fusing the epilogue into the position embedding's gate / fuse kernel.
 #include "gd4d_common.h"
 #include "gd4d_bf16x3.h"
@@ -178,12 +182,15 @@ struct DepthConvParams {
   float* partials;         // DN_EPI_STATS: (tiles, 2, 256) per-tile mean and M2 of y, tiles in grid order
   float eps;
   int levels;
+  const char* level_image[DN_MAX_LEVELS];   // DN_EPI_LEVELS / DN_EPI_LEVELS_CL: a weight image and a bias (or null) per level
+  const float* level_bias[DN_MAX_LEVELS];
 };
 
 // The epilogues of the one implicit GEMM.  INFER: + bias, BatchNorm (running statistics), ReLU, x gate.  STATS (training forward):
 // stores y = conv + bias and each channel's (mean, M2) over the tile's valid pixels, summed in a fixed order (lanes by an xor
 // butterfly, then the four pixel waves).  PLAIN: stores conv (+ bias when given): the frozen-BatchNorm forward and the input gradient.
-enum { DN_EPI_INFER = 0, DN_EPI_STATS = 1, DN_EPI_PLAIN = 2 };
+// LEVELS / LEVELS_CL (the FPN neck's output convolutions): PLAIN with the level's own image and bias, stored NCHW / channels-last.
+enum { DN_EPI_INFER = 0, DN_EPI_STATS = 1, DN_EPI_PLAIN = 2, DN_EPI_LEVELS = 3, DN_EPI_LEVELS_CL = 4 };
 
 __device__ __forceinline__ float dn_half_wave_sum(float s) {
 #pragma unroll
@@ -231,8 +238,10 @@ __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvP
       e_gate[tid] = p.gate[cam * DN_C + tid];
     }
   } else if (tid < DN_C) {
-    e_bias[tid] = p.bias ? p.bias[tid] : 0.f;
+    const float* const b = EPI >= DN_EPI_LEVELS ? p.level_bias[lv] : p.bias;
+    e_bias[tid] = b ? b[tid] : 0.f;
   }
+  const char* const image = EPI >= DN_EPI_LEVELS ? p.level_image[lv] : p.image;
 
   // halo staging role: item it = (k-group, halo pixel); 8 channels of one pixel, zero outside the image
   const float* h_src[DN_H_PASSES];
@@ -263,7 +272,7 @@ __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvP
   };
   u32x4 wr[2];
   auto issue_w = [&](int s) {
-    const char* src = p.image + (size_t)s * DN_W_STAGE + tid * 16;
+    const char* src = image + (size_t)s * DN_W_STAGE + tid * 16;
     wr[0] = *reinterpret_cast<const u32x4*>(src);
     wr[1] = *reinterpret_cast<const u32x4*>(src + DN_W_ARR);
   };
@@ -357,6 +366,25 @@ __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvP
           v = (v - e_mean[c]) * e_scale[c] + e_beta[c];          // BatchNorm2d, eval (running statistics)
           v = fmaxf(v, 0.f);                                     // ReLU
           o[(size_t)c * HW] = v * e_gate[c];                     // SELayer: x * gate
+        }
+    }
+  } else if (EPI == DN_EPI_LEVELS_CL) {
+    float* const outc = p.out[lv] + (size_t)cam * HW * DN_C;  // (N, H, W, 256)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      const int pp = 64 * wn + 32 * ni + l32;
+      const int y = ty0 + (pp >> 4), x = tx0 + (pp & 15);
+      if (y >= H || x >= W) continue;
+      float* const o = outc + ((size_t)y * W + x) * DN_C;
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int c = 64 * wm + 32 * mi + 4 * kg + 8 * q;     // registers 4 q .. 4 q + 3: channels c .. c + 3
+          f32x4 v;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = acc[mi][ni][4 * q + j] + e_bias[c + j];
+          *reinterpret_cast<f32x4*>(o + c) = v;
         }
     }
   } else {
@@ -537,4 +565,25 @@ extern "C" int gd4d_depth_conv_raw(const float* const* x, float* const* y, const
   p.bias = bias;
   p.partials = partials;
   return partials ? depth_conv_launch<DN_EPI_STATS>(p, tiles, stream) : depth_conv_launch<DN_EPI_PLAIN>(p, tiles, stream);
+}
+
+// The FPN neck's 3x3 output convolutions (mmdet FPN.fpn_convs; CPFPN keeps level 0's only): the plain-store GEMM above with a weight
+// image and a bias per level, all levels in one launch.
+extern "C" int gd4d_fpn_conv_fwd(const float* const* x, float* const* out, const int32_t* level_hw, int levels, int n, int channels,
+                                 const void* const* images, const float* const* biases, int out_channels_last, void* stream) {
+  using namespace gd4d;
+  if (!x || !out || !level_hw || !images) return GD4D_EINVAL;
+  if (channels != DN_C || levels < 1 || levels > DN_MAX_LEVELS || n <= 0 || (out_channels_last != 0 && out_channels_last != 1))
+    return GD4D_EUNSUPPORTED;
+  DepthConvParams p{};
+  long long tiles = 0;
+  const int code = depth_conv_levels(p, x, out, level_hw, levels, n, tiles);
+  if (code != GD4D_OK) return code;
+  for (int l = 0; l < levels; ++l) {
+    if (!images[l]) return GD4D_EINVAL;
+    if (!aligned16(images[l]) || (out_channels_last && !aligned16(out[l]))) return GD4D_EALIGN;
+    p.level_image[l] = static_cast<const char*>(images[l]);
+    p.level_bias[l] = biases ? biases[l] : nullptr;
+  }
+  return out_channels_last ? depth_conv_launch<DN_EPI_LEVELS_CL>(p, tiles, stream) : depth_conv_launch<DN_EPI_LEVELS>(p, tiles, stream);
 }

@@ -3046,6 +3046,121 @@ _GRID_MASK_DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.f
 GRID_MASK_BLOCK_WORDS, GRID_MASK_STATE_WORDS = 8, 4
 
 
+def _is_cl(t):
+    """(N, 256, H, W) stored (N, H, W, 256)."""
+    return t.dim() == 4 and t.permute(0, 2, 3, 1).is_contiguous()
+
+
+def fpn_empty(n, h, w, device, channels_last=False):
+    """An (N, 256, H, W) fp32 map for the neck's kernels to write: contiguous NCHW, or the same logical shape stored (N, H, W, 256)."""
+    if channels_last:
+        return torch.empty(n, h, w, 256, device=device, dtype=torch.float32).permute(0, 3, 1, 2)
+    return torch.empty(n, 256, h, w, device=device, dtype=torch.float32)
+
+
+def _fpn_map(t, name):
+    """(device pointer, channels-last flag) of an (N, 256, H, W) fp32 map in either of the two layouts the neck's kernels take."""
+    if not t.is_cuda:
+        raise _lib.Gd4dError(f'{name} must live on the GPU (no CPU fallback in graph-detr4d_amd)')
+    if t.dtype != torch.float32 or t.dim() != 4:
+        raise TypeError(f'{name} must be a float32 (N, C, H, W) map, got {t.dtype} {tuple(t.shape)}')
+    if t.is_contiguous():
+        return ctypes.c_void_p(t.data_ptr()), 0
+    if _is_cl(t):
+        return ctypes.c_void_p(t.data_ptr()), 1
+    raise ValueError(f'{name} must be contiguous NCHW or channels-last')
+
+
+def fpn_lateral_image(weight):
+    """gd4d_fpn_lateral_image: a lateral's 1x1 weight (256, Cin[, 1, 1]) fp32 -> its bf16 hi / lo fragment image for fpn_lateral_fwd
+    (Cin a multiple of 32 in [32, 2048]; remake it when the weight changes)."""
+    lib = _lib.load()
+    w = weight.reshape(weight.shape[0], -1)
+    cout, cin = w.shape
+    nbytes = int(lib.gd4d_fpn_lateral_image_bytes(int(cin)))
+    if nbytes == 0 or cout != 256 or weight.numel() != cout * cin or (weight.dim() == 4 and tuple(weight.shape[2:]) != (1, 1)):
+        raise _lib.Gd4dError(f'fpn_lateral_image: weight {tuple(weight.shape)}; the kernel takes (256, Cin, 1, 1), Cin a multiple of 32 '
+                             'in [32, 2048]')
+    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
+    code = lib.gd4d_fpn_lateral_image(_dev(w.contiguous(), 'weight', torch.float32), int(cin), int(cout), _dev(img, 'image', torch.uint8),
+                                      _stream())
+    _lib.check(code, 'gd4d_fpn_lateral_image')
+    return img
+
+
+def fpn_lateral_fwd(x, image, bias, up=None, out=None, channels_last_out=False):
+    """gd4d_fpn_lateral_fwd: x (N, Cin, H, W) fp32 NCHW -> (conv1x1(x) + bias) + nearest-upsampled `up` (the finished coarser lateral
+    (N, 256, Hc, Wc), NCHW or channels-last; None: the coarsest level).  out: the (N, 256, H, W) map to write (either layout; default a
+    new one, channels-last when channels_last_out)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    if x.dim() != 4:
+        raise ValueError('fpn_lateral_fwd: x (N, Cin, H, W) expected')
+    n, cin, h, w = (int(v) for v in x.shape)
+    if out is None:
+        out = fpn_empty(n, h, w, x.device, channels_last_out)
+    elif tuple(out.shape) != (n, 256, h, w):
+        raise ValueError(f'fpn_lateral_fwd: out must be ({n}, 256, {h}, {w})')
+    op, out_cl = _fpn_map(out, 'out')
+    up_ptr, up_cl, uh, uw = None, 0, 0, 0
+    if up is not None:
+        if up.dim() != 4 or up.shape[0] != n or up.shape[1] != 256:
+            raise ValueError(f'fpn_lateral_fwd: up must be ({n}, 256, Hc, Wc)')
+        up_ptr, up_cl = _fpn_map(up, 'up')
+        uh, uw = int(up.shape[2]), int(up.shape[3])
+    code = lib.gd4d_fpn_lateral_fwd(_dev(x, 'x', f32), n, cin, h, w, _dev(image, 'image', torch.uint8), _dev(bias, 'bias', f32), up_ptr, uh,
+                                    uw, up_cl, op, 256, out_cl, _stream())
+    _lib.check(code, 'gd4d_fpn_lateral_fwd')
+    return out
+
+
+def fpn_conv_fwd(feats, images, biases, outs=None, channels_last_out=False):
+    """gd4d_fpn_conv_fwd: L <= 4 NCHW levels (N, 256, H_l, W_l) -> conv3x3(x_l; images[l]) + biases[l] (pad 1, stride 1), one launch;
+    images[l] = depth_net_image(weight_l), biases[l] (256) or None.  outs: the L maps to write, all NCHW or all channels-last."""
+    lib = _lib.load()
+    f32 = torch.float32
+    nl = len(feats)
+    if len(images) != nl or len(biases) != nl:
+        raise ValueError('fpn_conv_fwd: one image and one bias (or None) per level')
+    n = feats[0].shape[0]
+    if any(f.dim() != 4 or f.shape[0] != n or f.shape[1] != feats[0].shape[1] for f in feats):
+        raise ValueError('fpn_conv_fwd: levels (N, C, H, W) with the same N and C expected')
+    if outs is None:
+        outs = [fpn_empty(n, int(f.shape[2]), int(f.shape[3]), f.device, channels_last_out) for f in feats]
+    elif len(outs) != nl or any(tuple(o.shape) != tuple(f.shape) for o, f in zip(outs, feats)):
+        raise ValueError('fpn_conv_fwd: outs must match the levels\' shapes')
+    maps = [_fpn_map(o, 'outs') for o in outs]
+    if len({cl for _, cl in maps}) != 1:
+        raise ValueError('fpn_conv_fwd: outs must be all NCHW or all channels-last')
+    fp = (ctypes.c_void_p * nl)(*[_dev(f, 'feats', f32).value for f in feats])
+    op = (ctypes.c_void_p * nl)(*[m[0].value for m in maps])
+    ip = (ctypes.c_void_p * nl)(*[_dev(i, 'images', torch.uint8).value for i in images])
+    bp = (ctypes.c_void_p * nl)(*[None if b is None else _dev(b, 'biases', f32).value for b in biases])
+    lv = (ctypes.c_int32 * (2 * nl))(*[int(v) for f in feats for v in f.shape[2:]])
+    code = lib.gd4d_fpn_conv_fwd(fp, op, lv, nl, int(n), int(feats[0].shape[1]), ip, bp, maps[0][1], _stream())
+    _lib.check(code, 'gd4d_fpn_conv_fwd')
+    return outs
+
+
+def fpn_extra_conv_fwd(x, image, bias=None, relu_in=False, out=None, channels_last_out=False):
+    """gd4d_fpn_extra_conv_fwd: x (N, 256, H, W) fp32, NCHW or channels-last -> conv3x3 stride 2 pad 1 of x (relu_in: of relu(x)) + bias,
+    (N, 256, (H + 1) // 2, (W + 1) // 2); image = depth_net_image(weight)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    xp, x_cl = _fpn_map(x, 'x')
+    n, c, h, w = (int(v) for v in x.shape)
+    ho, wo = (h + 1) // 2, (w + 1) // 2
+    if out is None:
+        out = fpn_empty(n, ho, wo, x.device, channels_last_out)
+    elif tuple(out.shape) != (n, 256, ho, wo):
+        raise ValueError(f'fpn_extra_conv_fwd: out must be ({n}, 256, {ho}, {wo})')
+    op, out_cl = _fpn_map(out, 'out')
+    code = lib.gd4d_fpn_extra_conv_fwd(xp, n, c, h, w, x_cl, _dev(image, 'image', torch.uint8),
+                                       None if bias is None else _dev(bias, 'bias', f32), int(bool(relu_in)), op, out_cl, _stream())
+    _lib.check(code, 'gd4d_fpn_extra_conv_fwd')
+    return out
+
+
 def grid_mask_fwd(x, d=2, l=1, st_h=0, st_w=0, use_h=True, use_w=True, mode=0, offset=None, out=None, out_dtype=None, apply=True,
                   block=None, gen_offset=False):
     """gd4d_grid_mask_fwd: GridMask (models/utils/grid_mask.py:84-123, angle 0) on x (R, C, H, W) fp32 / fp16 / bf16 in one pass.

@@ -68,6 +68,7 @@ TRANSFORMER_LAYER_SEQUENCE = Registry('transformer-layers sequence',
 TRANSFORMER = Registry('transformer', _mmcv('mmdet.models.utils.builder.TRANSFORMER'))
 BBOX_CODERS = Registry('bbox coder', _mmcv('mmdet.core.bbox.builder.BBOX_CODERS'))
 BBOX_ASSIGNERS = Registry('bbox assigner', _mmcv('mmdet.core.bbox.builder.BBOX_ASSIGNERS'))
+NECKS = Registry('neck', _mmcv('mmdet.models.builder.NECKS'))
 
 
 def build_attention(cfg, default_args=None):
@@ -92,3 +93,7 @@ def build_bbox_coder(cfg, default_args=None):
 
 def build_assigner(cfg, default_args=None):
     return build_from_cfg(cfg, BBOX_ASSIGNERS, default_args)
+
+
+def build_neck(cfg, default_args=None):
+    return build_from_cfg(cfg, NECKS, default_args)

@@ -1438,6 +1438,33 @@ int gd4d_grid_mask_fwd(const void* x, void* out, int in_dtype, int out_dtype, in
                        void* stream);
 int gd4d_grid_mask_draw(uint32_t* state, int32_t* block, int H, double ratio, void* stream);
 
+/* The FPN neck, inference (gd4d_fpn.hip; additive exports, the ABI version stays): mmdet's FPN and the reference's CPFPN
+ * (models/necks/cp_fpn.py) with 256 output channels on fp32 maps.  Split-bf16 x 3 MFMA arithmetic, fp32 accumulation, no atomics;
+ * nothing synchronises, every launch goes to `stream`.  A "channels-last" map is (N, H, W, 256) and must be 16-B aligned.
+ * gd4d_fpn_lateral_image - a lateral's (256, cin) weight (1x1 convolution) split into bf16 hi / lo MFMA fragments; image:
+ *   gd4d_fpn_lateral_image_bytes(cin) bytes, 16-B aligned (0 bytes: cin not a multiple of 32 in [32, 2048]).  Remake it when the
+ *   weight changes.
+ * gd4d_fpn_lateral_fwd - out (N, 256, h, w) = (W x + bias) + up[nearest] for NCHW x (N, cin, h, w): the lateral of one level with the
+ *   top-down add of the already finished coarser lateral up (N, 256, up_h, up_w) fused in, in torch's order of the two additions and
+ *   with ATen's nearest index min(floor(float(dst) * (float(in) / float(out))), in - 1); up NULL: the coarsest level (up_h / up_w
+ *   ignored).  up and out are NCHW or channels-last (the flags).  Call it coarse to fine.
+ * gd4d_fpn_conv_fwd - the 3x3 output convolutions (pad 1, stride 1): out[l] = conv3x3(x[l]; images[l]) (+ biases[l] when biases and
+ *   biases[l] are not NULL) for 1 <= levels <= 4 NCHW levels in ONE launch of gd4d_depth_conv_raw's implicit GEMM; images[l]: a
+ *   gd4d_depth_net_image of the level's (256, 256, 3, 3) weight.  out[l] NCHW or channels-last (one flag for all levels).  x / out /
+ *   images / biases / level_hw are HOST arrays.
+ * gd4d_fpn_extra_conv_fwd - an extra level: out (N, 256, (h + 1) / 2, (w + 1) / 2) = conv3x3 stride 2 pad 1 of x (relu_in: of
+ *   relu(x)) + bias (or none: NULL); image as above; x and out NCHW or channels-last.
+ * NULL pointers, sizes <= 0: GD4D_EINVAL; channels other than 256, cin outside the limits, N <= 0, levels outside 1..4, a flag other
+ * than 0 / 1, an `up` finer than the level: GD4D_EUNSUPPORTED; an image or a channels-last map not 16-B aligned: GD4D_EALIGN. */
+size_t gd4d_fpn_lateral_image_bytes(int cin);
+int gd4d_fpn_lateral_image(const float* weight, int cin, int out_channels, void* image, void* stream);
+int gd4d_fpn_lateral_fwd(const float* x, int n, int cin, int h, int w, const void* image, const float* bias, const float* up, int up_h,
+                         int up_w, int up_channels_last, float* out, int out_channels, int out_channels_last, void* stream);
+int gd4d_fpn_conv_fwd(const float* const* x, float* const* out, const int32_t* level_hw, int levels, int n, int channels,
+                      const void* const* images, const float* const* biases, int out_channels_last, void* stream);
+int gd4d_fpn_extra_conv_fwd(const float* x, int n, int channels, int h, int w, int in_channels_last, const void* image,
+                            const float* bias, int relu_in, float* out, int out_channels_last, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

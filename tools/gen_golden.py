@@ -811,6 +811,44 @@ def case_feat_distill(name, *, kind, seed, levels=((4, 7), (1, 2)), batch=1, num
     save(name, meta, **arrays)
 
 
+def case_fpn_cp(name, *, seed, num_cams=2, in_channels=(32, 64, 96, 128), levels=((13, 21), (7, 11), (4, 6), (2, 3)), num_outs=4,
+                weight_keep=0.1, chan_stride=8):
+    """The reference's CPFPN.forward (models/necks/cp_fpn.py:157-208) on a small pyramid: inputs, weights, level 0's lateral (after
+    the top-down path) and every output (no extra level: the reference's forward indexes past fpn_convs for one, :202).  Inputs on the k/32 grid; weights sparse on a grid of 1/64 (they compress).
+    Levels >= 1 of a CPFPN ARE their laterals.  Level 0's two maps are kept for every chan_stride-th channel only: the file stays
+    within the size limit for a committed fixture."""
+    mod = refstub.load_cp_fpn()
+    cfg = dict(in_channels=list(in_channels), out_channels=256, num_outs=num_outs, start_level=0, add_extra_convs='on_output',
+               relu_before_extra_convs=True)
+    neck = mod.CPFPN(**cfg).eval()
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for p_name, p in neck.named_parameters():
+            if p.dim() == 1:
+                p.copy_(torch.randint(-16, 17, p.shape, generator=g) / 64.)
+            else:
+                keep = torch.rand(p.shape, generator=g) < (weight_keep if p.shape[-1] == 3 else 0.5)
+                p.copy_(torch.randint(-8, 9, p.shape, generator=g) / 64. * keep)
+    packed, xs = {}, []
+    for i, (c, (h, w)) in enumerate(zip(in_channels, levels)):
+        q = torch.round(torch.randn(num_cams, c, h, w, generator=g) * FEAT_SCALE).clamp(-127, 127)
+        packed[f'in{i}'] = q.to(torch.int8)
+        xs.append(q / FEAT_SCALE)
+    hooks = Hooks(neck, ['fpn_convs.0'])
+    with torch.no_grad():
+        outs = neck([x.clone() for x in xs])
+    hooks.close()
+    assert len(outs) == num_outs and list(neck.state_dict()) == [f'{m}.{i}.conv.{t}' for m, n in (('lateral_convs', len(in_channels)), ('fpn_convs', 1))
+                                                                 for i in range(n) for t in ('weight', 'bias')]
+    arrays = dict(packed, lat0=hooks.rec['fpn_convs.0.in'][:, ::chan_stride].contiguous())
+    for lvl, o in enumerate(outs):
+        arrays[f'out{lvl}'] = (o[:, ::chan_stride] if lvl == 0 else o).contiguous()
+    arrays.update(pack_state(neck))
+    meta = dict(kind='fpn_cp', cfg=cfg, levels=[list(hw) for hw in levels], num_cams=num_cams, seed=seed, feat_scale=FEAT_SCALE,
+                w_scale=W_SCALE, chan_stride=chan_stride)
+    save(name, meta, **arrays)
+
+
 def case_detr4d_distill(name, *, num_student, num_teacher, batch, seed, num_layers=2, reweight_score=False, loss_cls_weight=1.0,
                         loss_reg_weight=0.25, degenerate=False):
     """Detr4D_Distiller.get_instance_distill_loss (distillation/distillers/detr4d_distiller.py:143-168), called unbound on a shell whose
@@ -938,6 +976,7 @@ def main():
                         loss_cls_weight=0.0, loss_reg_weight=0.25)
     case_feat_distill('feat_distill_vanilla', kind='vanilla', seed=1001)
     case_feat_distill('feat_distill_attention', kind='attention', seed=1002)
+    case_fpn_cp('fpn_cp', seed=1101)
 
 
 if __name__ == '__main__':

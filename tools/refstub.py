@@ -689,3 +689,44 @@ def load_detr4d_distiller():
         distiller = importlib.import_module('projects.mmdet3d_plugin.distillation.distillers.detr4d_distiller')
     del dist_mod
     return distiller, head, asg, loss_mod
+
+
+# --------------------------------------------------------------------------------------
+# CPFPN: the reference's own neck
+# --------------------------------------------------------------------------------------
+class ConvModule(nn.Module):
+    """mmcv.cnn.ConvModule for conv_cfg = norm_cfg = act_cfg = None (what the shipped neck configs pass): an nn.Conv2d with a bias,
+    held as `.conv`; restated from its published definition."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, conv_cfg=None, norm_cfg=None, act_cfg=None,
+                 inplace=True):
+        super().__init__()
+        assert conv_cfg is None and norm_cfg is None and act_cfg is None
+        self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride=stride, padding=padding)
+
+    def forward(self, x):
+        return self.conv(x)
+
+
+def load_cp_fpn():
+    """Import the reference's models/necks/cp_fpn.py unmodified (by path: the package's __init__ is not run) and return the module.
+    ConvModule, BaseModule, auto_fp16 (fp16_enabled is False: the identity) and the NECKS registry are stand-ins."""
+    install_stubs()
+    sys.modules['mmcv.cnn'].ConvModule = ConvModule
+    run = sys.modules['mmcv.runner']
+    run.BaseModule = BaseModule
+    run.auto_fp16 = lambda *a, **k: (lambda f: f)
+    if not hasattr(sys.modules['mmdet.models'], 'NECKS'):
+        sys.modules['mmdet.models'].NECKS = Registry('neck')
+    full = '_gd4d_ref_cp_fpn'
+    if full not in sys.modules:
+        path = os.path.join(REFERENCE_ROOT, 'projects/mmdet3d_plugin/models/necks/cp_fpn.py')
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f'reference not present at {path} (build container only)')
+        spec = importlib.util.spec_from_file_location(full, path)
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules[full] = mod
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            spec.loader.exec_module(mod)
+    return sys.modules[full]
