@@ -166,6 +166,16 @@ SIGNATURES = {
     'gd4d_fpn_lateral_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
     'gd4d_fpn_conv_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     'gd4d_fpn_extra_conv_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    'gd4d_fpn_lateral_image_mode_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_fpn_lateral_image_mode': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'gd4d_fpn_lateral_dgrad': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'gd4d_fpn_lateral_wgrad_workspace_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_fpn_lateral_wgrad_tiles': (_c.c_longlong, [_i, _i, _i]),
+    'gd4d_fpn_lateral_wgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'gd4d_fpn_topdown_bwd': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    'gd4d_fpn_extra_conv_dgrad': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'gd4d_fpn_extra_conv_wgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'gd4d_fpn_bias_grad': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

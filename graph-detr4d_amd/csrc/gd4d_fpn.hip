@@ -29,9 +29,18 @@
 //                            per level (defined there, next to the kernel it instantiates).
 // `up`, the extra convolution's input and every output are NCHW or channels-last ((N, H, W, 256); 16-byte aligned), so that a neck
 // asked for channels-last outputs writes them in place: the decoder then gathers them without the per-sample copy.
+// Training (gd4d_fpn_train.hip has the weight gradients, the top-down adjoint and the bias sums): two more kinds of the same GEMM.
+//   gd4d_fpn_lateral_dgrad     dx (N, Cin, H, W) = W^T g: K = the 256 channels of g (8 steps), the Cin output channels walked in blocks
+//                              of 256 (grid y; a ragged last block: the transposed image of gd4d_fpn_lateral_image_mode is zero
+//                              beyond Cin, waves past it skip their MFMAs and nothing past Cin is stored).
+//   gd4d_fpn_extra_conv_dgrad  the stride-2 level's input gradient: the gather GEMM over gd4d_depth_net_image_mode(transposed = 1)'s
+//                              taps, tap (ky', kx') of pixel (y, x) reading dy at ((y - 1 + ky') / 2, (x - 1 + kx') / 2) where both
+//                              are even and in range (three taps in four contribute zeros: untuned, the levels are tiny); the
+//                              epilogue multiplies by [mask > 0] (the forward's ReLU on read) and adds `add` (the level's own dout).
 // Arithmetic: split-bf16 x 3 on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (gd4d_bf16x3.h).  No atomics: two runs give the same bits.
 #include "gd4d_bf16x3.h"
 #include "gd4d_common.h"
+#include "gd4d_fpn_index.h"
 
 namespace gd4d {
 
@@ -59,6 +68,22 @@ __global__ __launch_bounds__(256) void fpn_lateral_image_kernel(const float* __r
   *reinterpret_cast<u32x4*>(image + (size_t)i * 16) = plane ? lo : hi;
 }
 
+// the input gradient's image, W^T: output channels = the lateral's input channels in blocks of 256 (zeros beyond cin), K = its 256
+// output channels.  item i = (((block * 8 + chunk) * 2 + plane) * 4 + k-group) * 256 + channel of the block
+__global__ __launch_bounds__(256) void fpn_lateral_image_t_kernel(const float* __restrict__ w, char* __restrict__ image, const int cin,
+                                                                  const int blocks) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= blocks * (FPN_C / FPN_KC) * 2 * 4 * FPN_C) return;
+  const int ocl = i & 255, kgrp = (i >> 8) & 3, plane = (i >> 10) & 1, chunk = (i >> 11) & 7, block = i >> 14;
+  const int oc = block * FPN_C + ocl;
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = oc < cin ? w[(size_t)(chunk * FPN_KC + kgrp * 8 + j) * cin + oc] : 0.f;
+  u32x4 hi, lo;
+  split8(v, hi, lo);
+  *reinterpret_cast<u32x4*>(image + (size_t)i * 16) = plane ? lo : hi;
+}
+
 struct FpnGemmParams {
   const float* x;          // LATERAL: (N, Cin, H, W); EXTRA: (N, 256, H, W), NCHW or channels-last (x_cs / x_ps)
   const char* image;
@@ -69,9 +94,12 @@ struct FpnGemmParams {
   int cin, H, W, Ho, Wo, Hc, Wc, tiles, steps;
   int relu_in, up_cl, out_cl;
   float scale_y, scale_x;  // float(Hc) / float(Ho), float(Wc) / float(Wo)
+  int cout;                // LATERAL_DGRAD: output channels (the lateral's Cin); the other kinds write 256
+  const float* mask;       // EXTRA_DGRAD: (N, 256, Ho, Wo) or null: the result is kept where mask > 0
+  const float* add;        // EXTRA_DGRAD: (N, 256, Ho, Wo) or null: added after the mask
 };
 
-enum { FPN_LATERAL = 0, FPN_EXTRA = 1 };
+enum { FPN_LATERAL = 0, FPN_EXTRA = 1, FPN_LATERAL_DGRAD = 2, FPN_EXTRA_DGRAD = 3 };
 
 template <int KIND>
 __global__ __launch_bounds__(FPN_THREADS) void fpn_gemm_kernel(const FpnGemmParams p) {
@@ -79,6 +107,10 @@ __global__ __launch_bounds__(FPN_THREADS) void fpn_gemm_kernel(const FpnGemmPara
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, kg = lane >> 5;
   const int cam = blockIdx.x / p.tiles, p0 = (blockIdx.x - cam * p.tiles) * FPN_PX;
   const int HWo = p.Ho * p.Wo;
+  // LATERAL_DGRAD: grid y walks the output channels in blocks of 256, each with its own run of `steps` weight stages
+  const int ocb = KIND == FPN_LATERAL_DGRAD ? (int)blockIdx.y : 0;
+  const int cout = KIND == FPN_LATERAL_DGRAD ? p.cout : FPN_C;
+  const bool wave_has_channels = KIND != FPN_LATERAL_DGRAD || FPN_C * ocb + 64 * wave < cout;
   const float* const xin = p.x + (size_t)cam * p.cin * p.H * p.W;
 
   // staging role: thread = (pixel of the tile, k-group): 8 input channels of one pixel per step
@@ -95,6 +127,14 @@ __global__ __launch_bounds__(FPN_THREADS) void fpn_gemm_kernel(const FpnGemmPara
       const int tap = s - chunk * FPN_TAPS;
       const int iy = 2 * s_oy - 1 + tap / 3, ix = 2 * s_ox - 1 + tap % 3;
       in = s_ok && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+      pix = (long long)iy * p.W + ix;
+    }
+    if (KIND == FPN_EXTRA_DGRAD) {                      // x is dy (H x W); the tile's pixels are dx's (Ho x Wo)
+      chunk = s / FPN_TAPS;
+      const int tap = s - chunk * FPN_TAPS;
+      const int ty = s_oy - 1 + tap / 3, tx = s_ox - 1 + tap % 3;
+      const int iy = ty >> 1, ix = tx >> 1;
+      in = s_ok && ty >= 0 && tx >= 0 && !(ty & 1) && !(tx & 1) && iy < p.H && ix < p.W;
       pix = (long long)iy * p.W + ix;
     }
     const float* src = xin + (in ? pix * p.x_ps : 0) + (long long)(chunk * FPN_KC + s_kgrp * 8) * p.x_cs;
@@ -126,11 +166,12 @@ __global__ __launch_bounds__(FPN_THREADS) void fpn_gemm_kernel(const FpnGemmPara
   for (int s = 0; s < p.steps; ++s) {
     const bool more = s + 1 < p.steps;
     if (more) issue(s + 1);
-    const char* const wb = p.image + (size_t)s * FPN_W_STEP;
+    const char* const wb = p.image + ((size_t)ocb * p.steps + s) * FPN_W_STEP;
     const u32x4* const bh_plane = s_b[s & 1][0];
     const u32x4* const bl_plane = s_b[s & 1][1];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
+      if (!wave_has_channels) break;                   // (wave-uniform; the wave still stages and meets the barriers)
       const int kgrp = 2 * ks + kg;
       u32x4 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
@@ -158,7 +199,7 @@ __global__ __launch_bounds__(FPN_THREADS) void fpn_gemm_kernel(const FpnGemmPara
     size_t up_pix = 0;
     if (KIND == FPN_LATERAL && p.up) {
       const int y = px / p.Wo, x = px - y * p.Wo;
-      const int sy = min((int)floorf((float)y * p.scale_y), p.Hc - 1), sx = min((int)floorf((float)x * p.scale_x), p.Wc - 1);
+      const int sy = fpn_nearest_src(y, p.scale_y, p.Hc), sx = fpn_nearest_src(x, p.scale_x, p.Wc);
       up_pix = (size_t)sy * p.Wc + sx;
     }
     const size_t HWc = (size_t)p.Hc * p.Wc;
@@ -166,10 +207,19 @@ __global__ __launch_bounds__(FPN_THREADS) void fpn_gemm_kernel(const FpnGemmPara
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int c = 64 * wave + 32 * mi + 4 * kg + 8 * q;
+        const int c = FPN_C * ocb + 64 * wave + 32 * mi + 4 * kg + 8 * q;
+        if (KIND == FPN_LATERAL_DGRAD && c >= cout) continue;                 // (cout is a multiple of 32: four channels at once)
         f32x4 v;
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = p.bias ? acc[mi][ni][4 * q + j] + p.bias[c + j] : acc[mi][ni][4 * q + j];
+        if (KIND == FPN_EXTRA_DGRAD) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const size_t at = ((size_t)cam * FPN_C + c + j) * HWo + px;
+            if (p.mask && !(p.mask[at] > 0.f)) v[j] = 0.f;                    // strict, as torch's ReLU
+            if (p.add) v[j] = p.add[at] + v[j];
+          }
+        }
         if (KIND == FPN_LATERAL && p.up) {
           if (p.up_cl) {
             const f32x4 u = *reinterpret_cast<const f32x4*>(p.up + ((size_t)cam * HWc + up_pix) * FPN_C + c);
@@ -184,7 +234,7 @@ __global__ __launch_bounds__(FPN_THREADS) void fpn_gemm_kernel(const FpnGemmPara
           *reinterpret_cast<f32x4*>(p.out + ((size_t)cam * HWo + px) * FPN_C + c) = v;
         } else {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) p.out[((size_t)cam * FPN_C + c + j) * HWo + px] = v[j];
+          for (int j = 0; j < 4; ++j) p.out[((size_t)cam * cout + c + j) * HWo + px] = v[j];
         }
       }
   }
@@ -198,6 +248,26 @@ extern "C" size_t gd4d_fpn_lateral_image_bytes(int cin) {
   using namespace gd4d;
   if (cin < FPN_KC || cin > FPN_MAX_CIN || cin % FPN_KC != 0) return 0;
   return (size_t)(cin / FPN_KC) * FPN_W_STEP;
+}
+
+extern "C" size_t gd4d_fpn_lateral_image_mode_bytes(int cin, int transposed) {
+  using namespace gd4d;
+  if (transposed == 0) return gd4d_fpn_lateral_image_bytes(cin);
+  if (transposed != 1 || gd4d_fpn_lateral_image_bytes(cin) == 0) return 0;
+  return (size_t)((cin + FPN_C - 1) / FPN_C) * (FPN_C / FPN_KC) * FPN_W_STEP;
+}
+
+extern "C" int gd4d_fpn_lateral_image_mode(const float* weight, int cin, int out_channels, int transposed, void* image, void* stream) {
+  using namespace gd4d;
+  if (transposed == 0) return gd4d_fpn_lateral_image(weight, cin, out_channels, image, stream);
+  if (!weight || !image) return GD4D_EINVAL;
+  if (out_channels != FPN_C || transposed != 1 || gd4d_fpn_lateral_image_bytes(cin) == 0) return GD4D_EUNSUPPORTED;
+  if (!aligned16(image)) return GD4D_EALIGN;
+  const int blocks = (cin + FPN_C - 1) / FPN_C;
+  const int items = blocks * (FPN_C / FPN_KC) * 2 * 4 * FPN_C;
+  hipLaunchKernelGGL(fpn_lateral_image_t_kernel, dim3((items + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), weight,
+                     static_cast<char*>(image), cin, blocks);
+  return check_launch();
 }
 
 extern "C" int gd4d_fpn_lateral_image(const float* weight, int cin, int out_channels, void* image, void* stream) {
@@ -280,5 +350,65 @@ extern "C" int gd4d_fpn_extra_conv_fwd(const float* x, int n, int channels, int 
   p.relu_in = relu_in;
   p.out_cl = out_channels_last;
   hipLaunchKernelGGL(fpn_gemm_kernel<FPN_EXTRA>, dim3((unsigned)(tiles * n)), dim3(FPN_THREADS), 0, static_cast<hipStream_t>(stream), p);
+  return check_launch();
+}
+
+extern "C" int gd4d_fpn_lateral_dgrad(const float* g, int n, int cin, int h, int w, const void* image_t, float* dx, void* stream) {
+  using namespace gd4d;
+  if (!g || !image_t || !dx) return GD4D_EINVAL;
+  if (h <= 0 || w <= 0) return GD4D_EINVAL;
+  if (n <= 0 || gd4d_fpn_lateral_image_bytes(cin) == 0) return GD4D_EUNSUPPORTED;
+  const long long hw = (long long)h * w;
+  if ((long long)n * FPN_MAX_CIN * hw > (1ll << 40) || hw > (1ll << 30)) return GD4D_EUNSUPPORTED;
+  if (!aligned16(image_t)) return GD4D_EALIGN;
+  const long long tiles = (hw + FPN_PX - 1) / FPN_PX;
+  if (tiles * n > (1ll << 30)) return GD4D_EUNSUPPORTED;
+  FpnGemmParams p{};
+  p.x = g;
+  p.image = static_cast<const char*>(image_t);
+  p.out = dx;
+  p.x_cs = hw;
+  p.x_ps = 1;
+  p.cin = FPN_C;                                                        // K: the channels of g
+  p.cout = cin;
+  p.H = p.Ho = h;
+  p.W = p.Wo = w;
+  p.Hc = p.Wc = 1;
+  p.tiles = (int)tiles;
+  p.steps = FPN_C / FPN_KC;
+  hipLaunchKernelGGL(fpn_gemm_kernel<FPN_LATERAL_DGRAD>, dim3((unsigned)(tiles * n), (unsigned)((cin + FPN_C - 1) / FPN_C)),
+                     dim3(FPN_THREADS), 0, static_cast<hipStream_t>(stream), p);
+  return check_launch();
+}
+
+extern "C" int gd4d_fpn_extra_conv_dgrad(const float* dy, int n, int channels, int h, int w, const void* image_t, const float* mask,
+                                         const float* add, float* dx, void* stream) {
+  using namespace gd4d;
+  if (!dy || !image_t || !dx) return GD4D_EINVAL;
+  if (h <= 0 || w <= 0) return GD4D_EINVAL;
+  if (channels != FPN_C || n <= 0) return GD4D_EUNSUPPORTED;
+  const long long hw = (long long)h * w;
+  if ((long long)n * FPN_C * hw > (1ll << 40) || hw > (1ll << 30)) return GD4D_EUNSUPPORTED;
+  if (!aligned16(image_t)) return GD4D_EALIGN;
+  const long long tiles = (hw + FPN_PX - 1) / FPN_PX;
+  if (tiles * n > (1ll << 30)) return GD4D_EUNSUPPORTED;
+  FpnGemmParams p{};
+  p.x = dy;
+  p.image = static_cast<const char*>(image_t);
+  p.out = dx;
+  p.mask = mask;
+  p.add = add;
+  p.H = (h + 1) / 2;                                                    // dy, the forward's output grid
+  p.W = (w + 1) / 2;
+  p.x_cs = (long long)p.H * p.W;
+  p.x_ps = 1;
+  p.cin = FPN_C;
+  p.Ho = h;                                                             // dx, the forward's input grid
+  p.Wo = w;
+  p.Hc = p.Wc = 1;
+  p.tiles = (int)tiles;
+  p.steps = (FPN_C / FPN_KC) * FPN_TAPS;
+  hipLaunchKernelGGL(fpn_gemm_kernel<FPN_EXTRA_DGRAD>, dim3((unsigned)(tiles * n)), dim3(FPN_THREADS), 0, static_cast<hipStream_t>(stream),
+                     p);
   return check_launch();
 }

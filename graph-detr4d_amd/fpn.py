@@ -21,8 +21,24 @@ Two keywords are not the reference's:
     channels_last_out=False  True: the outputs are logical (N, 256, H, W) tensors STORED (N, H, W, 256), written that way by the
                              kernels, so ImageFeatureExtractor(channels_last=True)'s `.contiguous(memory_format=...)` is a no-op and
                              the decoder gathers them in place (ops.PyramidView.channels_last_levels).
-The kernels have no backward: train() mode, or autograd on with a parameter or an input that requires grad, raises Gd4dError unless
-the torch-op route was chosen.
+    hip_train=False          True: the kernel route trains.  In train() mode, or with autograd on and a parameter or an input that
+                             requires grad, the call runs as ONE autograd node (_FpnTrainFunction): its forward is the launches
+                             above (the same bits), its backward the library's kernels (below).  `torch_ops=True` wins over it.
+Without `hip_train` the kernel route has no backward: train() mode, or autograd on with a parameter or an input that requires grad,
+raises Gd4dError unless the torch-op route was chosen.
+
+The backward (hip_train=True), with dout_k the gradient of output k and gl_i the gradient of lateral i:
+    extras     last to first: g(outs[k-1]) = dout_{k-1} + [outs[k-1] > 0]? dgrad_stride2(g(outs[k])) (gd4d_fpn_extra_conv_dgrad, the mask
+               where the forward applied its ReLU on read); dW, db by gd4d_fpn_extra_conv_wgrad
+    3x3        gl_i = conv3x3^T(g(outs[i])): ONE gd4d_fpn_conv_fwd launch on transposed, tap-flipped images; dW by gd4d_depth_conv_wgrad
+               per level, db by gd4d_fpn_bias_grad.  CPFPN's levels >= 1: gl_i = g(outs[i])
+    top-down   fine to coarse, gl_{i+1} += U^T gl_i in place (gd4d_fpn_topdown_bwd), U the forward's nearest upsampling
+    laterals   dW_i, db_i by gd4d_fpn_lateral_wgrad, dx_i = W_i^T gl_i by gd4d_fpn_lateral_dgrad
+Incoming gradients that are not fp32 contiguous NCHW (every one of them when channels_last_out=True) are made so with `.contiguous()`
+first, and so are channels-last outputs the backward reads: torch copies, as the forward's cast of its inputs.  Gradients of inputs
+that do not require grad (a frozen backbone, a teacher, the levels below start_level) and of frozen parameters are not computed.
+On this route the laterals are new tensors every call (the node keeps them until its backward; the kept per-slot buffers would be
+overwritten by the next call).  All sums run in a fixed order: two runs give the same bits.
 
 Kept state: the weights' fragment images, each under ops._Stamp's validity rule and each at a FIXED device address (a changed weight
 is re-imaged into the same buffer), and the intermediate laterals, per (device, request slot, shapes).  The outputs are new tensors
@@ -44,6 +60,82 @@ OUT_CHANNELS = 256
 MAX_LEVELS_PER_LAUNCH = 4
 
 
+class _FpnTrainFunction(torch.autograd.Function):
+    """The neck's kernel route as one autograd node: forward = FPN._forward_hip's launches, backward = the module docstring's data flow.
+    tensors: the lateral (weight, bias) pairs, the fpn_convs (weight, bias) pairs, then the used inputs.  Keeps the inputs, the
+    laterals that feed a 3x3 convolution and the outputs the extra levels read."""
+
+    @staticmethod
+    def forward(ctx, module, *tensors):
+        used, nconv = len(module.lateral_convs), len(module.fpn_convs)
+        xs = tensors[2 * (used + nconv):]
+        outs, laterals, xs = module._forward_hip(list(xs), used_inputs=True, fresh_laterals=True)
+        ctx.module = module
+        ctx.shapes = [tuple(o.shape) for o in outs]
+        ctx.x_dtypes = [t.dtype for t in tensors[2 * (used + nconv):]]
+        has_conv = [module._output_conv_of(i) is not None for i in range(used)]
+        extra_in = list(outs[used - 1:len(outs) - 1])            # the input of extra level e is output used - 1 + e
+        ctx.save_for_backward(*xs, *[l for l, h in zip(laterals, has_conv) if h], *extra_in)
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *douts):
+        m = ctx.module
+        used, nconv, n3 = len(m.lateral_convs), len(m.fpn_convs), m.num_output_convs
+        extras = nconv - n3
+        saved = ctx.saved_tensors
+        xs = saved[:used]
+        has_conv = [m._output_conv_of(i) is not None for i in range(used)]
+        conv_in = dict(zip([i for i in range(used) if has_conv[i]], saved[used:used + sum(has_conv)]))
+        extra_in = [t.contiguous() for t in saved[used + sum(has_conv):]]
+        need = ctx.needs_input_grad[1:]                          # (lateral w, b) * used, (conv w, b) * nconv, inputs * used
+        need_lat = lambda i: (need[2 * i], need[2 * i + 1])                                                      # noqa: E731
+        need_conv = lambda k: (need[2 * (used + k)], need[2 * (used + k) + 1])                                   # noqa: E731
+        need_x = need[2 * (used + nconv):]
+        dev = xs[0].device
+        g = [torch.zeros(s, device=dev, dtype=torch.float32) if d is None else d.float().contiguous() for d, s in zip(douts, ctx.shapes)]
+        grads = [None] * len(need)
+        images_t = m._all_images_t()
+        # extras, last to first
+        for e in range(extras - 1, -1, -1):
+            k, ci = used + e, n3 + e
+            relu = e > 0 and m.relu_before_extra_convs
+            x = extra_in[e]
+            if any(need_conv(ci)):
+                dw, db = ops.fpn_extra_conv_wgrad(g[k], x, relu_in=relu)
+                grads[2 * (used + ci)], grads[2 * (used + ci) + 1] = (dw if need_conv(ci)[0] else None), (db if need_conv(ci)[1] else None)
+            g[k - 1] = ops.fpn_extra_conv_dgrad(g[k], images_t[1][ci], x.shape[2:], mask=x if relu else None, add=g[k - 1])
+        # 3x3 output convolutions: one launch for the input gradients of all levels
+        gl = [None] * used
+        todo = [i for i in range(used) if has_conv[i]]
+        for j in range(0, len(todo), MAX_LEVELS_PER_LAUNCH):
+            grp = todo[j:j + MAX_LEVELS_PER_LAUNCH]
+            res = ops.fpn_conv_fwd([g[i] for i in grp], [images_t[1][m._output_conv_of(i)] for i in grp], [None] * len(grp))
+            for i, r in zip(grp, res):
+                gl[i] = r
+        for i in range(used):
+            k = m._output_conv_of(i)
+            if k is None:                                        # the lateral is the output; level >= 1's gradient is added to in place
+                gl[i] = g[i].clone() if i > 0 and (douts[i] is not None and g[i].data_ptr() == douts[i].data_ptr()) else g[i]
+                continue
+            if need_conv(k)[0]:
+                grads[2 * (used + k)] = ops.depth_conv_wgrad([g[i]], [conv_in[i]])
+            if need_conv(k)[1]:
+                grads[2 * (used + k) + 1] = ops.fpn_bias_grad(g[i])
+        # top-down, fine to coarse
+        for i in range(used - 1):
+            ops.fpn_topdown_bwd(gl[i], gl[i + 1])
+        # laterals
+        for i in range(used):
+            if any(need_lat(i)):
+                dw, db = ops.fpn_lateral_wgrad(gl[i], xs[i])
+                grads[2 * i], grads[2 * i + 1] = (dw if need_lat(i)[0] else None), (db if need_lat(i)[1] else None)
+            if need_x[i]:
+                grads[2 * (used + nconv) + i] = ops.fpn_lateral_dgrad(gl[i], images_t[0][i], xs[i].shape[1]).to(ctx.x_dtypes[i])
+        return (None, *grads)
+
+
 class _ConvModule(nn.Module):
     """mmcv's ConvModule without norm and activation: the convolution is the submodule `conv`."""
 
@@ -63,7 +155,7 @@ class FPN(nn.Module):
     def __init__(self, in_channels, out_channels, num_outs, start_level=0, end_level=-1, add_extra_convs=False,
                  relu_before_extra_convs=False, no_norm_on_lateral=False, conv_cfg=None, norm_cfg=None, act_cfg=None,
                  upsample_cfg=dict(mode='nearest'), init_cfg=dict(type='Xavier', layer='Conv2d', distribution='uniform'),
-                 torch_ops=False, channels_last_out=False):
+                 torch_ops=False, channels_last_out=False, hip_train=False):
         super().__init__()
         assert isinstance(in_channels, (list, tuple))
         self.in_channels = list(in_channels)
@@ -75,6 +167,7 @@ class FPN(nn.Module):
         self.upsample_cfg = dict(upsample_cfg)
         self.torch_ops = bool(torch_ops)
         self.channels_last_out = bool(channels_last_out)
+        self.hip_train = bool(hip_train)
         if end_level == -1:
             self.backbone_end_level = self.num_ins
             assert num_outs >= self.num_ins - start_level
@@ -167,13 +260,17 @@ class FPN(nn.Module):
         for x in inputs:
             Fn.require_gpu(x, 'inputs')
         name = type(self).__name__
+        if self.hip_train:
+            return False
         if self.training:
-            raise _lib.Gd4dError(f'{name} in train() mode: the neck\'s convolutions need a backward, which graph-detr4d_amd\'s kernels do '
-                                 'not provide.  `torch_ops=True` (or GD4D_TORCH_OPS=1) runs the module\'s own torch layers, the reference '
-                                 'arithmetic, trainable by autograd.')
+            raise _lib.Gd4dError(f'{name} in train() mode: the neck\'s convolutions need a backward, which graph-detr4d_amd\'s kernels '
+                                 'provide only on request.  `torch_ops=True` (or GD4D_TORCH_OPS=1) runs the module\'s own torch layers, the '
+                                 'reference arithmetic, trainable by autograd; `hip_train=True` trains the stage on the library\'s own '
+                                 'forward and backward kernels.')
         if Fn.wants_grad(self, *inputs):
-            raise _lib.Gd4dError(f'{name}: autograd is on, and graph-detr4d_amd\'s kernels have no backward for this stage.  Run inference '
-                                 'under torch.no_grad(), or choose the torch-op route (`torch_ops=True` / GD4D_TORCH_OPS=1).')
+            raise _lib.Gd4dError(f'{name}: autograd is on, and graph-detr4d_amd\'s kernels have no backward for this stage unless asked.  '
+                                 'Run inference under torch.no_grad(), choose the torch-op route (`torch_ops=True` / GD4D_TORCH_OPS=1), or '
+                                 'make the kernel route differentiable with `hip_train=True`.')
         return False
 
     # ---- torch-op route: the reference's op sequence -------------------------------------------------------------------
@@ -225,6 +322,12 @@ class FPN(nn.Module):
         conv = [self._image(('conv', i), m.conv.weight, ops.depth_net_image) for i, m in enumerate(self.fpn_convs)]
         return lat, conv
 
+    def _all_images_t(self):
+        """The backward's images: the transposed laterals and the transposed, tap-flipped 3x3 weights, under the forward's rule."""
+        lat = [self._image(('lateral_t', i), m.conv.weight, ops.fpn_lateral_image_t) for i, m in enumerate(self.lateral_convs)]
+        conv = [self._image(('conv_t', i), m.conv.weight, ops.depth_net_image_t) for i, m in enumerate(self.fpn_convs)]
+        return lat, conv
+
     def refresh_images(self):
         """For the owner of a hipGraph captured over this module: after an in-place weight edit, re-image the changed weights into
         the buffers the graph reads (outside the graph, before the replay).  Writes through `.data` need
@@ -243,9 +346,11 @@ class FPN(nn.Module):
             bufs = self._laterals[key] = [None if cl is None else ops.fpn_empty(n, h, w, dev, cl) for (n, h, w), cl in zip(shapes, layouts)]
         return bufs
 
-    def _forward_hip(self, inputs):
+    def _forward_hip(self, inputs, used_inputs=False, fresh_laterals=False):
+        """used_inputs: `inputs` are the used levels only.  fresh_laterals (the training node): the laterals are new tensors, and the
+        call returns (outs, laterals, the fp32 contiguous inputs)."""
         used = len(self.lateral_convs)
-        xs = [inputs[i + self.start_level] for i in range(used)]
+        xs = list(inputs) if used_inputs else [inputs[i + self.start_level] for i in range(used)]
         xs = [x if x.dtype == torch.float32 and x.is_contiguous() else x.float().contiguous() for x in xs]
         if any(x.dim() != 4 or x.shape[0] != xs[0].shape[0] for x in xs):
             raise ValueError(f'{type(self).__name__}: (N, C, H, W) maps of the same N expected')
@@ -258,8 +363,9 @@ class FPN(nn.Module):
         # a lateral that is an output (CPFPN's levels >= 1) is a new tensor in the output layout; the others are kept NCHW buffers
         shapes = [(int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) for x in xs]
         is_out = [self._output_conv_of(i) is None for i in range(used)]
-        laterals = self._lateral_buffers(shapes, [None if o else False for o in is_out], dev)
-        laterals = [ops.fpn_empty(*s, dev, cl) if o else b for s, o, b in zip(shapes, is_out, laterals)]
+        laterals = [None] * used if fresh_laterals else self._lateral_buffers(shapes, [None if o else False for o in is_out], dev)
+        laterals = [ops.fpn_empty(*s, dev, cl) if o else (ops.fpn_empty(*s, dev) if b is None else b)
+                    for s, o, b in zip(shapes, is_out, laterals)]
         for i in range(used - 1, -1, -1):
             ops.fpn_lateral_fwd(xs[i], lat_images[i], self.lateral_convs[i].conv.bias.detach(), up=laterals[i + 1] if i + 1 < used else None,
                                 out=laterals[i])
@@ -275,6 +381,8 @@ class FPN(nn.Module):
         for e, k in enumerate(range(self.num_output_convs, len(self.fpn_convs))):
             outs.append(ops.fpn_extra_conv_fwd(outs[-1], conv_images[k], self.fpn_convs[k].conv.bias.detach(),
                                                relu_in=e > 0 and self.relu_before_extra_convs, channels_last_out=cl))
+        if fresh_laterals:
+            return outs, laterals, xs
         return tuple(outs)
 
     def forward(self, inputs):
@@ -283,6 +391,10 @@ class FPN(nn.Module):
         inputs = list(inputs)
         if self._uses_torch_ops(inputs):
             return self._forward_torch(inputs)
+        if self.hip_train and (self.training or Fn.wants_grad(self, *inputs)):
+            used = len(self.lateral_convs)
+            params = [t for m in list(self.lateral_convs) + list(self.fpn_convs) for t in (m.conv.weight, m.conv.bias)]
+            return _FpnTrainFunction.apply(self, *params, *inputs[self.start_level:self.start_level + used])
         with torch.no_grad():
             return self._forward_hip(inputs)
 

@@ -3161,6 +3161,136 @@ def fpn_extra_conv_fwd(x, image, bias=None, relu_in=False, out=None, channels_la
     return out
 
 
+def fpn_lateral_image_t(weight):
+    """gd4d_fpn_lateral_image_mode(transposed = 1): a lateral's (256, Cin[, 1, 1]) weight -> the image of W^T with which fpn_lateral_dgrad
+    gives the input gradient (the Cin output channels in blocks of 256, zeros beyond Cin; remake it when the weight changes)."""
+    lib = _lib.load()
+    w = weight.reshape(weight.shape[0], -1)
+    cout, cin = w.shape
+    nbytes = int(lib.gd4d_fpn_lateral_image_mode_bytes(int(cin), 1))
+    if nbytes == 0 or cout != 256 or (weight.dim() == 4 and tuple(weight.shape[2:]) != (1, 1)):
+        raise _lib.Gd4dError(f'fpn_lateral_image_t: weight {tuple(weight.shape)}; the kernel takes (256, Cin, 1, 1), Cin a multiple of 32 '
+                             'in [32, 2048]')
+    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
+    code = lib.gd4d_fpn_lateral_image_mode(_dev(w.contiguous(), 'weight', torch.float32), int(cin), int(cout), 1,
+                                           _dev(img, 'image', torch.uint8), _stream())
+    _lib.check(code, 'gd4d_fpn_lateral_image_mode')
+    return img
+
+
+def _fpn_grad_map(t, name, channels=256):
+    if t.dim() != 4 or (channels is not None and t.shape[1] != channels):
+        raise ValueError(f'{name} must be an (N, {channels if channels else "C"}, H, W) map, got {tuple(t.shape)}')
+    return _dev(t, name, torch.float32)
+
+
+def fpn_lateral_dgrad(g, image_t, cin):
+    """gd4d_fpn_lateral_dgrad: g (N, 256, H, W) fp32 NCHW, the lateral's gradient -> dx (N, Cin, H, W) = W^T g;
+    image_t = fpn_lateral_image_t(weight)."""
+    lib = _lib.load()
+    gp = _fpn_grad_map(g, 'g')
+    n, _, h, w = (int(v) for v in g.shape)
+    cin = int(cin)
+    if int(lib.gd4d_fpn_lateral_image_mode_bytes(cin, 1)) != image_t.numel():
+        raise ValueError(f'fpn_lateral_dgrad: image_t of {image_t.numel()} bytes is not the transposed image of a lateral with Cin = {cin}')
+    dx = torch.empty(n, cin, h, w, device=g.device, dtype=torch.float32)
+    code = lib.gd4d_fpn_lateral_dgrad(gp, n, cin, h, w, _dev(image_t, 'image_t', torch.uint8), _dev(dx, 'dx', torch.float32), _stream())
+    _lib.check(code, 'gd4d_fpn_lateral_dgrad')
+    return dx
+
+
+def fpn_lateral_wgrad(g, x, partitions=None):
+    """gd4d_fpn_lateral_wgrad: g (N, 256, H, W), x (N, Cin, H, W) fp32 NCHW -> (dW (256, Cin, 1, 1), db (256)): the sums over cameras and
+    pixels of g[oc, p] x[ic, p] and of g[oc, p], K split over `partitions` partial sums added in order (default: about two workgroups
+    per compute unit, at most one partition per 64-pixel tile)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    gp = _fpn_grad_map(g, 'g')
+    xp = _fpn_grad_map(x, 'x', None)
+    n, cin, h, w = (int(v) for v in x.shape)
+    if tuple(g.shape) != (n, 256, h, w):
+        raise ValueError(f'fpn_lateral_wgrad: g {tuple(g.shape)} for x {tuple(x.shape)}')
+    if partitions is None:
+        tiles = int(lib.gd4d_fpn_lateral_wgrad_tiles(n, h, w))
+        chunks = (cin + 63) // 64
+        cus = torch.cuda.get_device_properties(g.device).multi_processor_count
+        partitions = max(1, min(tiles, (2 * cus + chunks - 1) // chunks))
+    partitions = int(partitions)
+    nbytes = int(lib.gd4d_fpn_lateral_wgrad_workspace_bytes(cin, partitions))
+    if nbytes == 0:
+        raise _lib.Gd4dError(f'fpn_lateral_wgrad: Cin = {cin} (a multiple of 32 in [32, 2048]), partitions = {partitions} (1 .. 4096)')
+    ws = torch.empty(nbytes // 4, device=g.device, dtype=f32)
+    dw = torch.empty(256, cin, 1, 1, device=g.device, dtype=f32)
+    db = torch.empty(256, device=g.device, dtype=f32)
+    code = lib.gd4d_fpn_lateral_wgrad(gp, xp, n, cin, h, w, partitions, _dev(ws, 'workspace', f32), _dev(dw, 'dw', f32), _dev(db, 'db', f32),
+                                      _stream())
+    _lib.check(code, 'gd4d_fpn_lateral_wgrad')
+    return dw, db
+
+
+def fpn_topdown_bwd(g_fine, g_coarse):
+    """gd4d_fpn_topdown_bwd: g_coarse (N, 256, Hc, Wc) += U^T g_fine (N, 256, H, W), IN PLACE: the adjoint of the forward's nearest
+    upsampling add; every coarse pixel adds its children in row-major order.  Returns g_coarse."""
+    lib = _lib.load()
+    fp, cp = _fpn_grad_map(g_fine, 'g_fine'), _fpn_grad_map(g_coarse, 'g_coarse')
+    n, _, h, w = (int(v) for v in g_fine.shape)
+    if g_coarse.shape[0] != n:
+        raise ValueError('fpn_topdown_bwd: the two maps must hold the same cameras')
+    code = lib.gd4d_fpn_topdown_bwd(fp, n, 256, h, w, cp, int(g_coarse.shape[2]), int(g_coarse.shape[3]), _stream())
+    _lib.check(code, 'gd4d_fpn_topdown_bwd')
+    return g_coarse
+
+
+def fpn_extra_conv_dgrad(dy, image_t, hw, mask=None, add=None):
+    """gd4d_fpn_extra_conv_dgrad: dy (N, 256, (H + 1) // 2, (W + 1) // 2) -> the stride-2 level's input gradient (N, 256, H, W), hw = (H, W);
+    image_t = depth_net_image_t(weight).  mask (N, 256, H, W): the result is kept where mask > 0 (the input the forward applied its
+    ReLU to); add (N, 256, H, W): added after that (the level's own incoming gradient)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    dp = _fpn_grad_map(dy, 'dy')
+    n, h, w = int(dy.shape[0]), int(hw[0]), int(hw[1])
+    if tuple(dy.shape[2:]) != ((h + 1) // 2, (w + 1) // 2):
+        raise ValueError(f'fpn_extra_conv_dgrad: dy {tuple(dy.shape)} is not the stride-2 output of an ({h}, {w}) map')
+    for t, name in ((mask, 'mask'), (add, 'add')):
+        if t is not None and tuple(t.shape) != (n, 256, h, w):
+            raise ValueError(f'fpn_extra_conv_dgrad: {name} must be ({n}, 256, {h}, {w})')
+    dx = torch.empty(n, 256, h, w, device=dy.device, dtype=f32)
+    code = lib.gd4d_fpn_extra_conv_dgrad(dp, n, 256, h, w, _dev(image_t, 'image_t', torch.uint8),
+                                         None if mask is None else _dev(mask, 'mask', f32), None if add is None else _dev(add, 'add', f32),
+                                         _dev(dx, 'dx', f32), _stream())
+    _lib.check(code, 'gd4d_fpn_extra_conv_dgrad')
+    return dx
+
+
+def fpn_extra_conv_wgrad(dy, x, relu_in=False):
+    """gd4d_fpn_extra_conv_wgrad: dy (N, 256, (H + 1) // 2, (W + 1) // 2), x (N, 256, H, W) fp32 NCHW -> (dW (256, 256, 3, 3), db (256)) of
+    the stride-2 convolution (relu_in: of relu(x))."""
+    lib = _lib.load()
+    f32 = torch.float32
+    dp, xp = _fpn_grad_map(dy, 'dy'), _fpn_grad_map(x, 'x')
+    n, _, h, w = (int(v) for v in x.shape)
+    if tuple(dy.shape) != (n, 256, (h + 1) // 2, (w + 1) // 2):
+        raise ValueError(f'fpn_extra_conv_wgrad: dy {tuple(dy.shape)} is not the stride-2 output of x {tuple(x.shape)}')
+    dw = torch.empty(256, 256, 3, 3, device=x.device, dtype=f32)
+    db = torch.empty(256, device=x.device, dtype=f32)
+    code = lib.gd4d_fpn_extra_conv_wgrad(dp, xp, n, 256, h, w, int(bool(relu_in)), _dev(dw, 'dw', f32), _dev(db, 'db', f32), _stream())
+    _lib.check(code, 'gd4d_fpn_extra_conv_wgrad')
+    return dw, db
+
+
+def fpn_bias_grad(g):
+    """gd4d_fpn_bias_grad: g (N, 256, H, W) fp32 NCHW -> db (256), its channel sums in a fixed order."""
+    lib = _lib.load()
+    f32 = torch.float32
+    gp = _fpn_grad_map(g, 'g')
+    n, _, h, w = (int(v) for v in g.shape)
+    ws = torch.empty(n * 256, device=g.device, dtype=f32)
+    db = torch.empty(256, device=g.device, dtype=f32)
+    code = lib.gd4d_fpn_bias_grad(gp, n, 256, h, w, _dev(ws, 'workspace', f32), _dev(db, 'db', f32), _stream())
+    _lib.check(code, 'gd4d_fpn_bias_grad')
+    return db
+
+
 def grid_mask_fwd(x, d=2, l=1, st_h=0, st_w=0, use_h=True, use_w=True, mode=0, offset=None, out=None, out_dtype=None, apply=True,
                   block=None, gen_offset=False):
     """gd4d_grid_mask_fwd: GridMask (models/utils/grid_mask.py:84-123, angle 0) on x (R, C, H, W) fp32 / fp16 / bf16 in one pass.

@@ -1465,6 +1465,40 @@ int gd4d_fpn_conv_fwd(const float* const* x, float* const* out, const int32_t* l
 int gd4d_fpn_extra_conv_fwd(const float* x, int n, int channels, int h, int w, int in_channels_last, const void* image,
                             const float* bias, int relu_in, float* out, int out_channels_last, void* stream);
 
+/* The FPN neck, training (gd4d_fpn_train.hip, gd4d_fpn.hip; additive exports, the ABI version stays).  fp32 contiguous NCHW maps
+ * only; split-bf16 x 3 MFMA arithmetic, fp32 accumulation, no atomics: every sum runs in a fixed order.  The 3x3 output convolutions'
+ * gradients are gd4d_fpn_conv_fwd on gd4d_depth_net_image_mode(transposed = 1) images and gd4d_depth_conv_wgrad.
+ * gd4d_fpn_lateral_image_mode - transposed = 0: gd4d_fpn_lateral_image; 1: the image of W^T for gd4d_fpn_lateral_dgrad, the cin output
+ *   channels in blocks of 256 (zeros beyond cin): gd4d_fpn_lateral_image_mode_bytes(cin, 1) bytes, 16-B aligned.
+ * gd4d_fpn_lateral_dgrad - dx (N, cin, h, w) = W^T g for g (N, 256, h, w).
+ * gd4d_fpn_lateral_wgrad - dw (256, cin) = sum over cameras and pixels of g[oc, p] x[ic, p] and db (256) = sum of g[oc, p], K split
+ *   over `partitions` (1 .. 4096) of the gd4d_fpn_lateral_wgrad_tiles(n, h, w) 64-pixel tiles; partial sums go to workspace
+ *   (gd4d_fpn_lateral_wgrad_workspace_bytes(cin, partitions), 16-B aligned; partitions beyond the tile count write zeros) and are added
+ *   in partition order.
+ * gd4d_fpn_topdown_bwd - the adjoint of the forward's nearest-upsampling add, in place: g_coarse (N, 256, coarse_h, coarse_w) +=
+ *   the sum of its children of g_fine (N, 256, h, w) in row-major order, the children being the pixels for which the forward's index
+ *   rule gives this coarse pixel.
+ * gd4d_fpn_extra_conv_dgrad - the stride-2 level's input gradient dx (N, 256, h, w) from dy (N, 256, (h + 1) / 2, (w + 1) / 2);
+ *   image_t: gd4d_depth_net_image_mode(transposed = 1) of its weight; mask (or NULL): dx is kept where mask > 0 (the forward's ReLU on
+ *   read), add (or NULL) is added after that; both (N, 256, h, w).
+ * gd4d_fpn_extra_conv_wgrad - dw (256, 256, 3, 3) = sum of dy[oc, p] relu?(x)[ic, 2 p + tap - 1], db (256, or NULL) = sum of dy.
+ * gd4d_fpn_bias_grad - db (256) = the channel sums of g (N, 256, h, w); workspace: n * 256 floats.
+ * Error codes as the forward's. */
+size_t gd4d_fpn_lateral_image_mode_bytes(int cin, int transposed);
+int gd4d_fpn_lateral_image_mode(const float* weight, int cin, int out_channels, int transposed, void* image, void* stream);
+int gd4d_fpn_lateral_dgrad(const float* g, int n, int cin, int h, int w, const void* image_t, float* dx, void* stream);
+size_t gd4d_fpn_lateral_wgrad_workspace_bytes(int cin, int partitions);
+long long gd4d_fpn_lateral_wgrad_tiles(int n, int h, int w);
+int gd4d_fpn_lateral_wgrad(const float* g, const float* x, int n, int cin, int h, int w, int partitions, float* workspace, float* dw,
+                           float* db, void* stream);
+int gd4d_fpn_topdown_bwd(const float* g_fine, int n, int channels, int h, int w, float* g_coarse, int coarse_h, int coarse_w,
+                         void* stream);
+int gd4d_fpn_extra_conv_dgrad(const float* dy, int n, int channels, int h, int w, const void* image_t, const float* mask,
+                              const float* add, float* dx, void* stream);
+int gd4d_fpn_extra_conv_wgrad(const float* dy, const float* x, int n, int channels, int h, int w, int relu_in, float* dw, float* db,
+                              void* stream);
+int gd4d_fpn_bias_grad(const float* g, int n, int channels, int h, int w, float* workspace, float* db, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,13 @@ F.interpolate in fp32: what a user ran before the kernels existed) on the same G
 call; and each kernel on its own.  Prints ONE JSON line.
 
     python tools/bench_fpn.py [--reps 20] [--cams 24 12] [--hip-only]
+    python tools/bench_fpn.py --train [--reps 10] [--cams 24 12]
+
+--train: forward + backward of `hip_train=True` beside `torch_ops=True` (the module's torch layers under autograd: how the neck was
+trained before the backward kernels existed) on the same inputs, alternated call by call, every parameter and input requiring grad;
+and each backward kernel on its own.  The input gradient of a lateral does 2 Cin 256 FLOP per pixel, its weight gradient the same; the
+top-down adjoint and the lateral weight gradient are also given as bytes (adjoint: the finer map read, the coarser read and written;
+weight gradient: x once and the lateral's gradient once per 64-channel chunk of Cin, which is what the kernel reads) against 8 TB/s.
 
 Workloads: the R50 pyramid (inputs (N, 512, 116, 200), (N, 1024, 58, 100), (N, 2048, 29, 50); mmdet FPN, start_level=1, one extra
 level) and the VoVNet CPFPN shapes (in_channels [256, 512, 768, 1024] at strides 4 .. 32 of a 928 x 1600 image).
@@ -116,12 +123,95 @@ def workload(spec, n, reps, hip_only):
     return out
 
 
+def rate(flop, ms):
+    return {'ms': ms, 'bf16_pflops': 3 * flop / ms / 1e12, 'fraction_of_spec': 3 * flop / (ms * 1e-3) / BF16_SPEC}
+
+
+def traffic(nbytes, ms):
+    return {'gbytes': nbytes / 1e9, 'tbytes_per_s': nbytes / (ms * 1e-3) / 1e12, 'fraction_of_hbm': nbytes / (ms * 1e-3) / HBM_SPEC}
+
+
+def train_workload(spec, n, reps):
+    cfg, s = spec['cfg'], spec['cfg']['start_level']
+    torch.manual_seed(n)
+    hip = getattr(G, spec['cls'])(**cfg, hip_train=True).cuda().train()
+    tor = getattr(G, spec['cls'])(**cfg, torch_ops=True).cuda().train()
+    tor.load_state_dict(hip.state_dict())
+    xs = [torch.randn(n, c, *hw, device='cuda').requires_grad_(i >= s) if i >= s else torch.empty(n, c, 1, 1, device='cuda')
+          for i, (c, hw) in enumerate(zip(cfg['in_channels'], spec['hw']))]
+    used = list(zip(cfg['in_channels'], spec['hw']))[s:]
+    with torch.no_grad():
+        rs = [torch.randn_like(o) for o in tor(xs)]
+
+    def step(m):
+        def f():
+            for p in m.parameters():
+                p.grad = None
+            for x in xs:
+                x.grad = None
+            outs = m(xs)
+            torch.autograd.backward(outs, rs)
+        return f
+    out = {'cams': n}
+    for k, v in alternate({'hip_train': step(hip), 'torch': step(tor)}, reps).items():
+        out[f'{k}_fwd_bwd_ms'] = v
+
+    # the backward kernels on their own, on gradients of the right shapes
+    nconv = len(used) if spec['cls'] == 'FPN' else 1
+    with torch.no_grad():
+        lat_t, conv_t = hip._all_images_t()
+        gls = [torch.randn(n, 256, *hw, device='cuda') for _, hw in used]
+        per = {}
+        for i, (c, hw) in enumerate(used):
+            x = xs[i + s].detach()
+            per[f'lateral{i}_dgrad'] = lambda g=gls[i], img=lat_t[i], c=c: ops.fpn_lateral_dgrad(g, img, c)
+            per[f'lateral{i}_wgrad'] = lambda g=gls[i], x=x: ops.fpn_lateral_wgrad(g, x)
+            if i + 1 < len(used):
+                per[f'topdown{i}'] = lambda g=gls[i], c=gls[i + 1]: ops.fpn_topdown_bwd(g, c)
+        per['conv3x3_dgrad'] = lambda: ops.fpn_conv_fwd(gls[:nconv], conv_t[:nconv], [None] * nconv)
+        per['conv3x3_wgrad'] = lambda: [ops.depth_conv_wgrad([g], [l]) for g, l in zip(gls[:nconv], gls[:nconv])]
+        per['conv3x3_bias'] = lambda: [ops.fpn_bias_grad(g) for g in gls[:nconv]]
+        if len(hip.fpn_convs) > nconv:
+            h, w = used[-1][1]
+            dy = torch.randn(n, 256, (h + 1) // 2, (w + 1) // 2, device='cuda')
+            per['extra_dgrad'] = lambda: ops.fpn_extra_conv_dgrad(dy, conv_t[nconv], (h, w), add=gls[-1])
+            per['extra_wgrad'] = lambda: ops.fpn_extra_conv_wgrad(dy, gls[-1])
+        t = alternate(per, reps)
+    kern = {}
+    for i, (c, (h, w)) in enumerate(used):
+        px, flop = n * h * w, 2 * c * 256 * n * h * w
+        kern[f'lateral{i}_dgrad'] = dict(rate(flop, t[f'lateral{i}_dgrad']), cin=c, hw=[h, w])
+        chunks = (c + 63) // 64
+        kern[f'lateral{i}_wgrad'] = dict(rate(flop, t[f'lateral{i}_wgrad']), **traffic(4 * px * (c + 256 * chunks), t[f'lateral{i}_wgrad']))
+        if i + 1 < len(used):
+            hc, wc = used[i + 1][1]
+            kern[f'topdown{i}'] = dict(ms=t[f'topdown{i}'], **traffic(4 * n * 256 * (h * w + 2 * hc * wc), t[f'topdown{i}']))
+    conv_px = n * sum(h * w for _, (h, w) in used[:nconv])
+    kern['conv3x3_dgrad'] = dict(rate(2 * 2304 * 256 * conv_px, t['conv3x3_dgrad']), pixels=conv_px)
+    kern['conv3x3_wgrad'] = dict(rate(2 * 2304 * 256 * conv_px, t['conv3x3_wgrad']), launches=nconv)
+    kern['conv3x3_bias'] = {'ms': t['conv3x3_bias'], 'launches': nconv}
+    for k in ('extra_dgrad', 'extra_wgrad'):
+        if k in t:
+            kern[k] = {'ms': t[k]}
+    out['kernels'] = kern
+    out['slowest_kernel'] = max(kern, key=lambda k: kern[k]['ms'])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--cams', type=int, nargs='+', default=[24, 12])
     ap.add_argument('--hip-only', action='store_true')
+    ap.add_argument('--train', action='store_true', help='forward + backward: hip_train=True beside torch_ops=True')
     a = ap.parse_args()
+    if a.train:
+        res = {'metric': 'neck forward + backward ms per sample (B = 1), hip_train=True against the module\'s torch-op route'}
+        for n in a.cams:
+            res[f'r50_fpn_cams{n}'] = train_workload(R50, n, a.reps)
+        res[f'vov_cpfpn_cams{a.cams[0]}'] = train_workload(VOV, a.cams[0], a.reps)
+        print(json.dumps(res))
+        return
     res = {'metric': 'neck forward ms per sample (B = 1), kernels against the module\'s torch-op route'}
     for n in a.cams:
         res[f'r50_fpn_cams{n}'] = workload(R50, n, a.reps, a.hip_only)
