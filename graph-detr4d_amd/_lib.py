@@ -176,6 +176,10 @@ SIGNATURES = {
     'gd4d_fpn_extra_conv_dgrad': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'gd4d_fpn_extra_conv_wgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'gd4d_fpn_bias_grad': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'gd4d_dcn_weight_image_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_dcn_weight_image': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_dcn_offset_conv_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'gd4d_dcn_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -3333,6 +3333,81 @@ def grid_mask_draw(state, block, h, ratio):
     return block
 
 
+# ---- DCNv2: the modulated deformable 3x3 convolution (gd4d_dcn.hip) ------------------------------------------------------------
+DCN_OFFSET_CHANNELS = 27
+
+
+def dcn_out_hw(h, w, stride):
+    """The output size of the 3x3 convolution, pad 1."""
+    return (int(h) - 1) // int(stride) + 1, (int(w) - 1) // int(stride) + 1
+
+
+def dcn_weight_image(weight):
+    """gd4d_dcn_weight_image: a 3x3 weight (Cout, Cin, 3, 3) fp32 -> its bf16 hi / lo fragment image.  Cin a multiple of 64 in [64, 512];
+    Cout a multiple of 64 in [64, 512] (dcn_fwd) or 27 (dcn_offset_conv_fwd).  Remake it when the weight changes."""
+    lib = _lib.load()
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise _lib.Gd4dError(f'dcn_weight_image: weight {tuple(weight.shape)}; the kernels take (Cout, Cin, 3, 3)')
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    nbytes = int(lib.gd4d_dcn_weight_image_bytes(cin, cout))
+    if nbytes == 0:
+        raise _lib.Gd4dError(f'dcn_weight_image: weight {tuple(weight.shape)}; the kernels take Cin a multiple of 64 in [64, 512] and Cout '
+                             'a multiple of 64 in [64, 512] (or 27, conv_offset)')
+    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
+    code = lib.gd4d_dcn_weight_image(_dev(weight.contiguous(), 'weight', torch.float32), cin, cout, _dev(img, 'image', torch.uint8), _stream())
+    _lib.check(code, 'gd4d_dcn_weight_image')
+    return img
+
+
+def _dcn_x(x, name):
+    if x.dim() != 4:
+        raise ValueError(f'{name}: x (N, Cin, H, W) expected')
+    return (int(v) for v in x.shape)
+
+
+def dcn_offset_conv_fwd(x, image, bias=None, stride=1, out=None):
+    """gd4d_dcn_offset_conv_fwd: x (N, Cin, H, W) fp32 NCHW -> (N, 27, Ho, Wo): conv3x3(x; stride, pad 1) + bias with the sigmoid applied
+    to channels 18..26 (18 offsets, 9 modulations); image = dcn_weight_image(conv_offset.weight)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    n, cin, h, w = _dcn_x(x, 'dcn_offset_conv_fwd')
+    ho, wo = dcn_out_hw(h, w, stride)
+    if out is None:
+        out = torch.empty(n, DCN_OFFSET_CHANNELS, ho, wo, device=x.device, dtype=f32)
+    elif tuple(out.shape) != (n, DCN_OFFSET_CHANNELS, ho, wo):
+        raise ValueError(f'dcn_offset_conv_fwd: out must be ({n}, {DCN_OFFSET_CHANNELS}, {ho}, {wo})')
+    code = lib.gd4d_dcn_offset_conv_fwd(_dev(x, 'x', f32), n, cin, h, w, int(stride), _dev(image, 'image', torch.uint8),
+                                        None if bias is None else _dev(bias, 'bias', f32), _dev(out, 'out', f32), _stream())
+    _lib.check(code, 'gd4d_dcn_offset_conv_fwd')
+    return out
+
+
+def dcn_fwd(x, offmask, image, cout, stride=1, scale=None, shift=None, relu=False, out=None):
+    """gd4d_dcn_fwd: x (N, Cin, H, W), offmask (N, 27, Ho, Wo) (offsets, then modulations in [0, 1]) -> (N, cout, Ho, Wo), the modulated
+    deformable 3x3 convolution (pad 1) with the weight of image = dcn_weight_image(weight), then * scale + shift per channel (each (cout)
+    or None; shift alone is the bias) and ReLU when asked."""
+    lib = _lib.load()
+    f32 = torch.float32
+    n, cin, h, w = _dcn_x(x, 'dcn_fwd')
+    ho, wo = dcn_out_hw(h, w, stride)
+    if tuple(offmask.shape) != (n, DCN_OFFSET_CHANNELS, ho, wo):
+        raise ValueError(f'dcn_fwd: offmask must be ({n}, {DCN_OFFSET_CHANNELS}, {ho}, {wo}), got {tuple(offmask.shape)}')
+    for t, name in ((scale, 'scale'), (shift, 'shift')):
+        if t is not None and tuple(t.shape) != (int(cout),):
+            raise ValueError(f'dcn_fwd: {name} must be ({int(cout)},)')
+    if int(lib.gd4d_dcn_weight_image_bytes(cin, int(cout))) != image.numel() or int(cout) == DCN_OFFSET_CHANNELS:
+        raise _lib.Gd4dError(f'dcn_fwd: the image is not dcn_weight_image of a ({int(cout)}, {cin}, 3, 3) weight the kernel takes')
+    if out is None:
+        out = torch.empty(n, int(cout), ho, wo, device=x.device, dtype=f32)
+    elif tuple(out.shape) != (n, int(cout), ho, wo):
+        raise ValueError(f'dcn_fwd: out must be ({n}, {int(cout)}, {ho}, {wo})')
+    code = lib.gd4d_dcn_fwd(_dev(x, 'x', f32), _dev(offmask, 'offmask', f32), n, cin, int(cout), h, w, int(stride),
+                            _dev(image, 'image', torch.uint8), None if scale is None else _dev(scale, 'scale', f32),
+                            None if shift is None else _dev(shift, 'shift', f32), int(bool(relu)), _dev(out, 'out', f32), _stream())
+    _lib.check(code, 'gd4d_dcn_fwd')
+    return out
+
+
 def _first_tensor(args):
     for a in args:
         if torch.is_tensor(a):

@@ -69,6 +69,9 @@ TRANSFORMER = Registry('transformer', _mmcv('mmdet.models.utils.builder.TRANSFOR
 BBOX_CODERS = Registry('bbox coder', _mmcv('mmdet.core.bbox.builder.BBOX_CODERS'))
 BBOX_ASSIGNERS = Registry('bbox assigner', _mmcv('mmdet.core.bbox.builder.BBOX_ASSIGNERS'))
 NECKS = Registry('neck', _mmcv('mmdet.models.builder.NECKS'))
+# (not mirrored into a real mmcv / mmdet: 'DCNv2' and 'ResNet' there are mmcv's and mmdet's own classes, which stay theirs)
+CONV_LAYERS = Registry('conv layer')
+BACKBONES = Registry('backbone')
 
 
 def build_attention(cfg, default_args=None):
@@ -97,3 +100,22 @@ def build_assigner(cfg, default_args=None):
 
 def build_neck(cfg, default_args=None):
     return build_from_cfg(cfg, NECKS, default_args)
+
+
+def build_conv_layer(cfg, *args, **kwargs):
+    """mmcv.cnn.build_conv_layer: cfg is dict(type='DCNv2', ...) (None: a plain nn.Conv2d); the layer's own arguments follow."""
+    if cfg is None:
+        import torch.nn as nn
+        return nn.Conv2d(*args, **kwargs)
+    if not isinstance(cfg, dict) or 'type' not in cfg:
+        raise KeyError(f'cfg must be a dict with a "type" key, got {cfg!r}')
+    extra = copy.deepcopy(cfg)
+    typ = extra.pop('type')
+    cls = CONV_LAYERS.get(typ)
+    if cls is None:
+        raise KeyError(f'{typ} is not in the {CONV_LAYERS.name} registry')
+    return cls(*args, **kwargs, **extra)
+
+
+def build_backbone(cfg, default_args=None):
+    return build_from_cfg(cfg, BACKBONES, default_args)

@@ -1499,6 +1499,30 @@ int gd4d_fpn_extra_conv_wgrad(const float* dy, const float* x, int n, int channe
                               void* stream);
 int gd4d_fpn_bias_grad(const float* g, int n, int channels, int h, int w, float* workspace, float* db, void* stream);
 
+/* DCNv2, the modulated deformable 3x3 convolution of the R50 / R101 backbones (mmcv 1.x ModulatedDeformConv2dPack with
+ * deform_groups = groups = dilation = 1, padding 1), inference forward (gd4d_dcn.hip; additive exports, the ABI version stays).
+ * With s the stride, tap k = 3 ky + kx and o (N, 27, Ho, Wo) the offset / modulation map (channel 2 k: dy_k, 2 k + 1: dx_k, 18 + k: m_k,
+ * already through the sigmoid):
+ *     out[n, co, y, x] = sum_{ci, k} w[co, ci, k] m_k[n, y, x] bilinear0(x[n, ci], y s - 1 + ky + dy_k, x s - 1 + kx + dx_k)
+ * bilinear0: corners at floor and floor + 1, a corner outside the image contributes 0.  Ho = (H - 1) / s + 1, Wo likewise.
+ * gd4d_dcn_weight_image - a 3x3 weight (cout, cin, 3, 3) fp32 split into bf16 hi / lo MFMA fragments in the order the kernels walk K;
+ *   image: gd4d_dcn_weight_image_bytes(cin, cout) bytes, 16-B aligned.  cin a multiple of 64 in [64, 512]; cout a multiple of 64 in
+ *   [64, 512] (gd4d_dcn_fwd) or 27 (gd4d_dcn_offset_conv_fwd); anything else: 0 bytes / GD4D_EUNSUPPORTED.  Remake it when the weight
+ *   changes.
+ * gd4d_dcn_offset_conv_fwd - offmask (N, 27, Ho, Wo) = conv3x3(x; stride, pad 1) + bias (27, or NULL), sigmoid on channels 18..26;
+ *   image: gd4d_dcn_weight_image(conv_offset.weight, cin, 27).
+ * gd4d_dcn_fwd - out (N, cout, Ho, Wo) = the sum above, then * scale[co] (or NULL: 1) + shift[co] (or NULL: 0), then ReLU when relu
+ *   != 0: shift alone is the bias; the folded frozen BatchNorm is scale = gamma / sqrt(var + eps), shift = beta + (bias - mean) scale.
+ * x (N, cin, H, W), offmask and out contiguous NCHW fp32.  stride other than 1 or 2, N <= 0, channels outside the image's set, more
+ * than 2^30 elements in one image of x: GD4D_EUNSUPPORTED; an image not 16-B aligned: GD4D_EALIGN; a NULL x / offmask / image / out:
+ * GD4D_EINVAL.  No atomics: two runs give the same bits. */
+size_t gd4d_dcn_weight_image_bytes(int cin, int cout);
+int gd4d_dcn_weight_image(const float* weight, int cin, int cout, void* image, void* stream);
+int gd4d_dcn_offset_conv_fwd(const float* x, int n, int cin, int h, int w, int stride, const void* image, const float* bias,
+                             float* offmask, void* stream);
+int gd4d_dcn_fwd(const float* x, const float* offmask, int n, int cin, int cout, int h, int w, int stride, const void* image,
+                 const float* scale, const float* shift, int relu, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
