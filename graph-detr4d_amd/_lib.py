@@ -180,6 +180,15 @@ SIGNATURES = {
     'gd4d_dcn_weight_image': (_i, [_vp, _i, _i, _vp, _vp]),
     'gd4d_dcn_offset_conv_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'gd4d_dcn_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    'gd4d_dcn_weight_image_t_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_dcn_weight_image_t': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_dcn_bwd_data': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    'gd4d_dcn_wgrad_tiles': (_c.c_longlong, [_i, _i, _i, _i]),
+    'gd4d_dcn_wgrad_workspace_bytes': (_c.c_size_t, [_i, _i, _i]),
+    'gd4d_dcn_wgrad': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'gd4d_dcn_offset_conv_dgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'gd4d_dcn_offset_conv_wgrad_workspace_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_dcn_offset_conv_wgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

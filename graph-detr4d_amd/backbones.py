@@ -9,7 +9,8 @@ trained checkpoint's backbone slice loads with strict=True.
 Every layer is stock torch except the DCN conv2 (dcn.ModulatedDeformConv2dPack, the library's kernels).  With its BatchNorm in eval
 mode - every config: norm_eval=True - a DCN bottleneck computes relu(bn2(conv2(x))) in ONE call, `conv2.forward_bn_relu(x, bn2)`: the
 BatchNorm and the ReLU run in the deformable convolution's epilogue.  `torch_ops=True` is handed to the DCN layers (their
-differentiable grid_sample route: what training takes).
+differentiable grid_sample route), and so is `hip_train=True`: the same one call then trains on the library's own backward kernels
+(dcn.py), with no grid_sample and no tensor of 9 Cin x pixels.
 
 Scope: depth 50 / 101, style 'pytorch', the plain 7x7 stem, BatchNorm, `fallback_on_stride=False`; `num_stages`, `out_indices`,
 `strides`, `dilations`, `frozen_stages`, `norm_eval`, `dcn`, `stage_with_dcn`, `zero_init_residual`.  deep_stem, avg_down, plugins, other
@@ -37,7 +38,8 @@ class Bottleneck(nn.Module):
     """mmdet.models.backbones.resnet.Bottleneck, style 'pytorch' (the stride sits on the 3x3 convolution)."""
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, norm_cfg=None, dcn=None, torch_ops=False):
+    def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, norm_cfg=None, dcn=None, torch_ops=False,
+                 hip_train=False):
         super().__init__()
         self.inplanes, self.planes, self.stride, self.dilation = inplanes, planes, stride, dilation
         self.with_dcn = dcn is not None
@@ -48,7 +50,7 @@ class Bottleneck(nn.Module):
             if dcn.pop('fallback_on_stride', False):
                 raise _lib.Gd4dError('Bottleneck: dcn fallback_on_stride=True is not built (every shipped config sets False)')
             self.conv2 = build_conv_layer(dcn, planes, planes, kernel_size=3, stride=stride, padding=dilation, dilation=dilation,
-                                          bias=False, torch_ops=torch_ops)
+                                          bias=False, torch_ops=torch_ops, hip_train=hip_train)
         else:
             self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=stride, padding=dilation, dilation=dilation, bias=False)
         self.bn2 = _norm(norm_cfg, planes)
@@ -77,7 +79,7 @@ class ResNet(nn.Module):
                  dilations=(1, 1, 1, 1), out_indices=(0, 1, 2, 3), style='pytorch', deep_stem=False, avg_down=False, frozen_stages=-1,
                  conv_cfg=None, norm_cfg=dict(type='BN', requires_grad=True), norm_eval=True, dcn=None,
                  stage_with_dcn=(False, False, False, False), plugins=None, with_cp=False, zero_init_residual=True, pretrained=None,
-                 init_cfg=None, torch_ops=False):
+                 init_cfg=None, torch_ops=False, hip_train=False):
         super().__init__()
         if depth not in self.arch_settings:
             raise _lib.Gd4dError(f'ResNet: depth={depth}; this backbone builds the bottleneck depths {sorted(self.arch_settings)}')
@@ -102,7 +104,7 @@ class ResNet(nn.Module):
         for i, blocks in enumerate(self.arch_settings[depth][:num_stages]):
             planes = base_channels * 2 ** i
             stage_dcn = dcn if dcn is not None and stage_with_dcn[i] else None
-            layer = self._make_stage(inplanes, planes, blocks, strides[i], dilations[i], norm_cfg, stage_dcn, torch_ops)
+            layer = self._make_stage(inplanes, planes, blocks, strides[i], dilations[i], norm_cfg, stage_dcn, torch_ops, hip_train)
             inplanes = planes * Bottleneck.expansion
             name = f'layer{i + 1}'
             self.add_module(name, layer)
@@ -112,15 +114,15 @@ class ResNet(nn.Module):
         self._freeze_stages()
 
     @staticmethod
-    def _make_stage(inplanes, planes, blocks, stride, dilation, norm_cfg, dcn, torch_ops):
+    def _make_stage(inplanes, planes, blocks, stride, dilation, norm_cfg, dcn, torch_ops, hip_train=False):
         downsample = None
         if stride != 1 or inplanes != planes * Bottleneck.expansion:
             downsample = nn.Sequential(nn.Conv2d(inplanes, planes * Bottleneck.expansion, kernel_size=1, stride=stride, bias=False),
                                        _norm(norm_cfg, planes * Bottleneck.expansion))
-        layers = [Bottleneck(inplanes, planes, stride, dilation, downsample, norm_cfg, dcn, torch_ops)]
+        layers = [Bottleneck(inplanes, planes, stride, dilation, downsample, norm_cfg, dcn, torch_ops, hip_train)]
         inplanes = planes * Bottleneck.expansion
         for _ in range(1, blocks):
-            layers.append(Bottleneck(inplanes, planes, 1, dilation, None, norm_cfg, dcn, torch_ops))
+            layers.append(Bottleneck(inplanes, planes, 1, dilation, None, norm_cfg, dcn, torch_ops, hip_train))
         return nn.Sequential(*layers)
 
     def init_weights(self):

@@ -50,26 +50,15 @@
 // Known costs, not yet measured apart: the 2-byte parks of the Mpad = 512 shape are 4-way bank-conflicted ds_write_b16; a lane's four
 // corner loads are separate dword loads.
 // Left off: an LDS-staged input patch; skipping the loads of pixels whose four weights are zero; the conv_offset kernel's reuse of
-// its input across taps (it reads x 9 times through L1 / L2); fusing conv_offset into the main kernel; a backward (training takes the
-// module's torch-op route).
+// its input across taps (it reads x 9 times through L1 / L2); fusing conv_offset into the main kernel.  The backward is
+// gd4d_dcn_train.hip; what both share is gd4d_dcn_common.h.
 #include "gd4d_common.h"
 #include "gd4d_bf16x3.h"
+#include "gd4d_dcn_common.h"
 
 #include <type_traits>
 
 namespace gd4d {
-
-constexpr int DCN_TAPS = 9, DCN_OFF_C = 27, DCN_THREADS = 1024, DCN_TW = 16;
-constexpr int DCN_MIN_C = 64, DCN_MAX_C = 512;
-
-// the image's geometry for Cout output channels; false: not served
-__host__ __device__ inline bool dcn_geometry(int cout, int& mpad, int& kc) {
-  if (cout == DCN_OFF_C) { mpad = 32; kc = 16; return true; }
-  if (cout < DCN_MIN_C || cout > DCN_MAX_C || cout % 64) return false;
-  if (cout <= 256) { mpad = 256; kc = 32; } else { mpad = 512; kc = 16; }
-  return true;
-}
-inline bool dcn_cin_ok(int cin) { return cin >= DCN_MIN_C && cin <= DCN_MAX_C && cin % 64 == 0; }
 
 // ---- weight image ---------------------------------------------------------------------------------------------------------
 // item i = (((tap * chunks + chunk) * 2 + plane) * (KC / 8) + k-group) * Mpad + out channel, 16 bytes each
@@ -258,25 +247,11 @@ __global__ __launch_bounds__(DCN_THREADS) void dcn_kernel(const DcnParams p) {
       dx = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(orsrc, o, (unsigned)(2 * tap + 1) * oplane_bytes, 0));
       m = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(orsrc, o, (unsigned)(18 + tap) * oplane_bytes, 0));
     }
-    // offsets beyond +-2^20 (and NaN) sample nothing; below that floor and fraction of the offset itself are exact
-    const bool sane = fabsf(dy) < 1048576.f && fabsf(dx) < 1048576.f;
-    if (!sane) dy = dx = m = 0.f;
-    const float fy = floorf(dy), fx = floorf(dx);
-    const float ly = dy - fy, lx = dx - fx;
-    const int y0 = s_y * p.stride - 1 + ky + (int)fy, x0 = s_x * p.stride - 1 + kx + (int)fx;
-    const bool ya = y0 >= 0 && y0 < H, yb = y0 + 1 >= 0 && y0 + 1 < H;
-    const bool xa = x0 >= 0 && x0 < W, xb = x0 + 1 >= 0 && x0 + 1 < W;
-    const int yA = min(max(y0, 0), H - 1), yB = min(max(y0 + 1, 0), H - 1);
-    const int xA = min(max(x0, 0), W - 1), xB = min(max(x0 + 1, 0), W - 1);
-    const float hy = 1.f - ly, hx = 1.f - lx;
-    cw[0] = ya && xa ? m * (hy * hx) : 0.f;
-    cw[1] = ya && xb ? m * (hy * lx) : 0.f;
-    cw[2] = yb && xa ? m * (ly * hx) : 0.f;
-    cw[3] = yb && xb ? m * (ly * lx) : 0.f;
-    co[0] = (unsigned)(yA * W + xA) * 4u;
-    co[1] = (unsigned)(yA * W + xB) * 4u;
-    co[2] = (unsigned)(yB * W + xA) * 4u;
-    co[3] = (unsigned)(yB * W + xB) * 4u;
+    // (gd4d_dcn_common.h: offsets beyond +-2^20 and NaN sample nothing; floor and fraction of the offset itself are exact)
+    const DcnCorners c = dcn_corners(dy, dx, m, s_y * p.stride - 1 + ky, s_x * p.stride - 1 + kx, H, W);
+    dcn_modulated_weights(c, m, cw);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) co[j] = c.off[j];
   };
   float sr[4 * S::CPH];                                      // one phase's corner values in flight
   auto issue_samples = [&](int chunk, int ph) {
@@ -291,7 +266,7 @@ __global__ __launch_bounds__(DCN_THREADS) void dcn_kernel(const DcnParams p) {
     float v[2] = {0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < S::CPH; ++j)
-      v[j] = fmaf(cw[3], sr[4 * j + 3], fmaf(cw[2], sr[4 * j + 2], fmaf(cw[1], sr[4 * j + 1], cw[0] * sr[4 * j])));
+      v[j] = dcn_combine(cw, sr[4 * j], sr[4 * j + 1], sr[4 * j + 2], sr[4 * j + 3]);
     const unsigned hh = cvt_pk_bf16(v[0], v[1]);
     const unsigned ll = cvt_pk_bf16(v[0] - __uint_as_float(hh << 16), v[1] - __uint_as_float(hh & 0xffff0000u));
     const int ch = s_c0 + ph * S::CPH;                       // channel inside the chunk
@@ -409,15 +384,6 @@ static int dcn_launch(DcnParams& p, int n, void* stream) {
   if (!allow_dynamic_lds(reinterpret_cast<const void*>(dcn_kernel<WM, KC>), S::LDS)) return GD4D_ELAUNCH;
   hipLaunchKernelGGL((dcn_kernel<WM, KC>), dim3((unsigned)tiles), dim3(DCN_THREADS), S::LDS, static_cast<hipStream_t>(stream), p);
   return check_launch();
-}
-
-// the output size of a 3x3 convolution, pad 1; false: a size or a stride the kernels do not take
-static bool dcn_out_hw(int n, int cin, int cout, int h, int w, int stride, int& ho, int& wo) {
-  if (n <= 0 || h <= 0 || w <= 0 || (stride != 1 && stride != 2)) return false;
-  ho = (h - 1) / stride + 1;
-  wo = (w - 1) / stride + 1;
-  // the sampler addresses one image of x with 32-bit byte offsets; everything else is size_t
-  return (long long)cin * h * w < (1ll << 30) && (long long)n * (cin > cout ? cin : cout) * h * w <= (1ll << 40);
 }
 
 }  // namespace gd4d

@@ -18,9 +18,30 @@ folds an eval()-mode BatchNorm2d and the ReLU behind it into that kernel's epilo
 config (norm_eval=True, frozen).  Inputs that are not fp32 contiguous NCHW are converted with `.float().contiguous()` first (a torch copy).
     torch_ops=False   True (or GD4D_TORCH_OPS=1 for the whole process): K grid_sample calls and one einsum over K Cin - differentiable,
                       any device and dtype, and the route for configurations outside the kernels' limits.
+    hip_train=False   True: the kernel route trains.  In train() mode, or with autograd on and a parameter or an input that requires
+                      grad, the call is ONE autograd node (_DcnTrainFunction): its forward is the two launches above (the same bits),
+                      its backward gd4d_dcn_train.hip's kernels (below).  `torch_ops=True` wins over it.
 The kernels' limits: kernel size 3, padding 1, dilation 1, groups = deform_groups = 1, stride 1 or 2, in / out channels multiples of 64
 in [64, 512].  The default route raises Gd4dError outside them, in train() mode, under autograd (a parameter or an input that
-requires grad), and on CPU tensors; the message names the switch.  There is no HIP backward.
+requires grad), and on CPU tensors; the message names the switches.  Without `hip_train` there is no HIP backward.
+
+The backward (hip_train=True).  The node keeps x (fp32), the 27-channel offset map and - when the ReLU ran - the output (its mask).
+    gd4d_dcn_bwd_data            the offset / modulation gradients and dX in one pass: c = W^T g (g = dout x ReLU mask x BatchNorm scale)
+                                 stays in the MFMA accumulators, never in memory; dX by float atomicAdd (the one output whose last
+                                 bits differ between runs)
+    gd4d_dcn_wgrad               dW, dbias: the modulated samples recomputed as the forward forms them, partial sums per pixel
+                                 partition added in order
+    gd4d_dcn_offset_conv_dgrad / _wgrad   the Pack's conv_offset: dX += conv_transpose(do), dW_off, db_off
+Only what `needs_input_grad` asks for is launched: a frozen `weight` skips gd4d_dcn_wgrad, a frozen `conv_offset` its weight gradient,
+and with nothing upstream needing grad as well the data kernel.  Gradients come back in the dtype of their tensor.  `forward_bn_relu`
+needs the BatchNorm's parameters frozen (requires_grad=False, every config); otherwise it raises and names `torch_ops=True`.  Under
+hipGraph capture with gradients wanted the call raises: the node allocates and re-images changed weights.
+THE CONVENTION AT INTEGER SAMPLE COORDINATES.  The offset gradient has a kink wherever a sample coordinate is an integer - every offset
+of a fresh layer (conv_offset zero-initialised) at training step 0.  The kernels take floor and fraction of the offset, as the forward
+does: corners at floor and floor + 1, the derivative from the RIGHT, mmcv's convention and what fp64 autograd through floor-based index
+arithmetic gives.  The torch-op route's `grid_sample` normalises the coordinate first, rounds some integers down by an ulp and takes
+the LEFT derivative there: on exactly-integer offsets the two routes' offset gradients differ (by as much as the gradient itself); on
+any other offsets they agree to rounding.  The arbiter is the floor-based fp64 form, never grid_sample.
 
 Kept state: the two weight images and the folded (scale, shift) of a BatchNorm, each under ops._Stamp's validity rule and each at a
 FIXED device address (a changed source is rebuilt into the same buffer).  The outputs and the offset map are new tensors every call
@@ -79,6 +100,50 @@ def modulated_deform_conv2d_torch(x, offset, mask, weight, bias=None, stride=1, 
     return out
 
 
+class _DcnTrainFunction(torch.autograd.Function):
+    """The kernel route as one autograd node, for both classes and for forward / forward_bn_relu: forward = the module's two launches,
+    backward = the module docstring's kernels.  offset / mask are the caller's (ModulatedDeformConv2d) or None (the Pack, which hands
+    its conv_offset parameters instead).  Keeps x, the 27-channel offset map and, when the ReLU ran, the output."""
+
+    @staticmethod
+    def forward(ctx, module, bn, relu, x, offset, mask, weight, bias, off_weight, off_bias):
+        xf = module._f32(x)
+        pack = offset is None
+        offmask = module._offmask_hip(xf) if pack else torch.cat((module._f32(offset), module._f32(mask)), dim=1)
+        out = module._hip(xf, offmask, bn, relu=relu)
+        ctx.module, ctx.bn, ctx.relu, ctx.pack = module, bn, relu, pack
+        ctx.dtypes = [None if t is None else t.dtype for t in (x, offset, mask, weight, bias, off_weight, off_bias)]
+        ctx.save_for_backward(xf, offmask, out if relu else None, off_weight)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        m = ctx.module
+        x, offmask, y, off_weight = ctx.saved_tensors
+        need_x, need_off, need_mask, need_w, need_b, need_ow, need_ob = ctx.needs_input_grad[3:]
+        g = dout.float().contiguous()
+        scale = None if ctx.bn is None else m._folded(ctx.bn)[0]
+        stride, cout = m.stride[0], m.out_channels
+        grads = [None] * 7
+        if need_x or need_off or need_mask or need_ow or need_ob:
+            dx, doff = ops.dcn_bwd_data(g, x, offmask, m._weight_image_t(), cout, stride=stride, y=y, scale=scale, sigmoid_grad=ctx.pack,
+                                        want_dx=need_x)
+            if ctx.pack:
+                if need_x:
+                    ops.dcn_offset_conv_dgrad(doff, off_weight.detach().float().contiguous(), dx, stride=stride)
+                if need_ow or need_ob:
+                    grads[5], grads[6] = ops.dcn_offset_conv_wgrad(doff, x, stride=stride)
+            else:
+                grads[1], grads[2] = doff[:, :18], doff[:, 18:]
+            grads[0] = dx
+        if need_w or need_b:
+            grads[3], grads[4] = ops.dcn_wgrad(g, x, offmask, cout, stride=stride, y=y, scale=scale)
+        need = (need_x, need_off, need_mask, need_w, need_b, need_ow, need_ob)
+        grads = [gr.to(dt) if gr is not None and wanted else None for gr, wanted, dt in zip(grads, need, ctx.dtypes)]
+        return (None, None, None, *grads)
+
+
 @CONV_LAYERS.register_module('ModulatedDeformConv2d')
 class ModulatedDeformConv2d(nn.Module):
     """mmcv.ops.ModulatedDeformConv2d: forward(x, offset, mask) with the offset (N, 18, Ho, Wo) and the mask (N, 9, Ho, Wo, already
@@ -86,7 +151,7 @@ class ModulatedDeformConv2d(nn.Module):
     _version = 2
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, deform_groups=1, bias=True,
-                 torch_ops=False):
+                 torch_ops=False, hip_train=False):
         super().__init__()
         self.in_channels, self.out_channels = int(in_channels), int(out_channels)
         self.kernel_size = _pair(kernel_size)
@@ -94,6 +159,7 @@ class ModulatedDeformConv2d(nn.Module):
         self.groups, self.deform_groups = int(groups), int(deform_groups)
         self.transposed, self.output_padding = False, (0, 0)
         self.torch_ops = bool(torch_ops)
+        self.hip_train = bool(hip_train)
         self.weight = nn.Parameter(torch.empty(self.out_channels, self.in_channels // self.groups, *self.kernel_size))
         if bias:
             self.bias = nn.Parameter(torch.empty(self.out_channels))
@@ -143,17 +209,34 @@ class ModulatedDeformConv2d(nn.Module):
             return True
         Fn.torch_ops_route(self._route_name(), not self._kernel_limits, module=self)     # raises when outside the limits
         name = type(self).__name__
-        if self.training:
+        if self.training and not self.hip_train:
             raise _lib.Gd4dError(f'{name} in train() mode: graph-detr4d_amd\'s deformable-convolution kernels have no backward.  '
                                  '`torch_ops=True` (or GD4D_TORCH_OPS=1) runs the module through grid_sample and einsum, trainable by '
-                                 'autograd; a frozen layer belongs in eval() mode.')
-        if Fn.wants_grad(self, *inputs):
+                                 'autograd; a frozen layer belongs in eval() mode.  `hip_train=True` trains the layer on the library\'s '
+                                 'own forward and backward kernels.')
+        if Fn.wants_grad(self, *inputs) and not self.hip_train:
             raise _lib.Gd4dError(f'{name}: autograd is on, and graph-detr4d_amd\'s deformable-convolution kernels have no backward.  Run '
                                  'inference under torch.no_grad() (or freeze the parameters and the input), or choose the torch-op route '
-                                 '(`torch_ops=True` / GD4D_TORCH_OPS=1).')
+                                 '(`torch_ops=True` / GD4D_TORCH_OPS=1).  `hip_train=True` makes the kernel route differentiable.')
         for x in inputs:
             Fn.require_gpu(x, 'inputs')
         return False
+
+    def _trains(self, *inputs):
+        """The call must be an autograd node: hip_train, and train() mode or something that requires grad."""
+        return self.hip_train and torch.is_grad_enabled() and (self.training or Fn.wants_grad(self, *inputs))
+
+    def _train_node(self, x, offset, mask, bn, relu):
+        if bn is not None and any(p is not None and p.requires_grad for p in (bn.weight, bn.bias)):
+            raise _lib.Gd4dError(f'{type(self).__name__}.forward_bn_relu with hip_train: the BatchNorm2d\'s parameters require grad, and '
+                                 'the folded epilogue has no gradient for them.  Freeze them (norm_cfg requires_grad=False, every config) or '
+                                 'choose the torch-op route (`torch_ops=True` / GD4D_TORCH_OPS=1).')
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.Gd4dError(f'{type(self).__name__} with hip_train under hipGraph capture with gradients wanted: the training node '
+                                 'allocates and re-images changed weights.  Capture the forward under torch.no_grad() in eval() mode.')
+        conv_offset = getattr(self, 'conv_offset', None) if offset is None else None
+        off_weight, off_bias = (None, None) if conv_offset is None else (conv_offset.weight, conv_offset.bias)
+        return _DcnTrainFunction.apply(self, bn, relu, x, offset, mask, self.weight, self.bias, off_weight, off_bias)
 
     # ---- kept values ----------------------------------------------------------------------------------------------------
     def _keep(self, key, sources, build):
@@ -175,6 +258,9 @@ class ModulatedDeformConv2d(nn.Module):
 
     def _weight_image(self):
         return self._keep('weight', (self.weight,), lambda: ops.dcn_weight_image(self.weight.detach().float()))
+
+    def _weight_image_t(self):
+        return self._keep('weight_t', (self.weight,), lambda: ops.dcn_weight_image_t(self.weight.detach().float()))
 
     def _folded(self, bn):
         """(2, Cout): scale = gamma / sqrt(var + eps) and shift = beta + (bias - mean) scale of an eval()-mode BatchNorm2d behind the
@@ -230,6 +316,8 @@ class ModulatedDeformConv2d(nn.Module):
     def forward(self, x, offset, mask):
         if self._uses_torch_ops(x, offset, mask):
             return self._torch(x, offset, mask)
+        if self._trains(x, offset, mask):
+            return self._train_node(x, offset, mask, None, False)
         with torch.no_grad():
             return self._hip(self._f32(x), torch.cat((self._f32(offset), self._f32(mask)), dim=1))
 
@@ -238,6 +326,8 @@ class ModulatedDeformConv2d(nn.Module):
         self._check_bn(bn)
         if self._uses_torch_ops(x, offset, mask):
             return F.relu(bn(self._torch(x, offset, mask)))
+        if self._trains(x, offset, mask):
+            return self._train_node(x, offset, mask, bn, True)
         with torch.no_grad():
             return self._hip(self._f32(x), torch.cat((self._f32(offset), self._f32(mask)), dim=1), bn, relu=True)
 
@@ -282,6 +372,8 @@ class ModulatedDeformConv2dPack(ModulatedDeformConv2d):
     def forward(self, x):
         if self._uses_torch_ops(x):
             return self._torch(x, *self.offsets_torch(x))
+        if self._trains(x):
+            return self._train_node(x, None, None, None, False)
         with torch.no_grad():
             x = self._f32(x)
             return self._hip(x, self._offmask_hip(x))
@@ -291,6 +383,8 @@ class ModulatedDeformConv2dPack(ModulatedDeformConv2d):
         self._check_bn(bn)
         if self._uses_torch_ops(x):
             return F.relu(bn(self._torch(x, *self.offsets_torch(x))))
+        if self._trains(x):
+            return self._train_node(x, None, None, bn, True)
         with torch.no_grad():
             x = self._f32(x)
             return self._hip(x, self._offmask_hip(x), bn, relu=True)

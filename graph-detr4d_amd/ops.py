@@ -3408,6 +3408,135 @@ def dcn_fwd(x, offmask, image, cout, stride=1, scale=None, shift=None, relu=Fals
     return out
 
 
+# ---- DCNv2, training (gd4d_dcn_train.hip) ---------------------------------------------------------------------------------------
+def dcn_weight_image_t(weight):
+    """gd4d_dcn_weight_image_t: a 3x3 weight (Cout, Cin, 3, 3) fp32 -> the transposed bf16 hi / lo fragment image dcn_bwd_data reads
+    (rows (tap, ci), K = Cout).  Cin and Cout multiples of 64 in [64, 512].  Remake it when the weight changes."""
+    lib = _lib.load()
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise _lib.Gd4dError(f'dcn_weight_image_t: weight {tuple(weight.shape)}; the kernels take (Cout, Cin, 3, 3)')
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    nbytes = int(lib.gd4d_dcn_weight_image_t_bytes(cin, cout))
+    if nbytes == 0:
+        raise _lib.Gd4dError(f'dcn_weight_image_t: weight {tuple(weight.shape)}; the kernels take Cin and Cout multiples of 64 in [64, 512]')
+    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
+    code = lib.gd4d_dcn_weight_image_t(_dev(weight.contiguous(), 'weight', torch.float32), cin, cout, _dev(img, 'image', torch.uint8), _stream())
+    _lib.check(code, 'gd4d_dcn_weight_image_t')
+    return img
+
+
+def _dcn_bwd_args(name, dout, y, scale, x, offmask, cout, stride):
+    n, cin, h, w = _dcn_x(x, name)
+    ho, wo = dcn_out_hw(h, w, stride)
+    cout = int(cout)
+    if tuple(offmask.shape) != (n, DCN_OFFSET_CHANNELS, ho, wo):
+        raise ValueError(f'{name}: offmask must be ({n}, {DCN_OFFSET_CHANNELS}, {ho}, {wo}), got {tuple(offmask.shape)}')
+    if tuple(dout.shape) != (n, cout, ho, wo) or (y is not None and tuple(y.shape) != (n, cout, ho, wo)):
+        raise ValueError(f'{name}: dout (and y) must be ({n}, {cout}, {ho}, {wo})')
+    if scale is not None and tuple(scale.shape) != (cout,):
+        raise ValueError(f'{name}: scale must be ({cout},)')
+    return n, cin, cout, h, w, ho, wo
+
+
+def dcn_bwd_data(dout, x, offmask, image_t, cout, stride=1, y=None, scale=None, sigmoid_grad=False, dx=None, want_dx=True):
+    """gd4d_dcn_bwd_data: the input and offset / modulation gradients of dcn_fwd in one pass.  dout (N, cout, Ho, Wo); y: the forward's
+    output when it applied its ReLU (the mask y > 0), scale: the folded BatchNorm's, both optional; image_t = dcn_weight_image_t(weight).
+    Returns (dx (N, Cin, H, W) or None, doff (N, 27, Ho, Wo)): doff[:18] the offset gradient, doff[18:] the modulation's - times m (1 - m)
+    with sigmoid_grad (the gradient of conv_offset's raw output).  dx is ADDED into with float atomics (the one output whose last bits
+    depend on the run): a given dx must hold zeros (or what to add to); by default a zeroed one is made."""
+    lib = _lib.load()
+    f32 = torch.float32
+    n, cin, cout, h, w, ho, wo = _dcn_bwd_args('dcn_bwd_data', dout, y, scale, x, offmask, cout, stride)
+    if int(lib.gd4d_dcn_weight_image_t_bytes(cin, cout)) != image_t.numel() or image_t.numel() == 0:
+        raise _lib.Gd4dError(f'dcn_bwd_data: the image is not dcn_weight_image_t of a ({cout}, {cin}, 3, 3) weight the kernel takes')
+    if dx is None and want_dx:
+        dx = torch.zeros(n, cin, h, w, device=x.device, dtype=f32)
+    elif dx is not None and tuple(dx.shape) != (n, cin, h, w):
+        raise ValueError(f'dcn_bwd_data: dx must be ({n}, {cin}, {h}, {w})')
+    doff = torch.empty(n, DCN_OFFSET_CHANNELS, ho, wo, device=x.device, dtype=f32)
+    code = lib.gd4d_dcn_bwd_data(_dev(dout, 'dout', f32), None if y is None else _dev(y, 'y', f32),
+                                 None if scale is None else _dev(scale, 'scale', f32), _dev(x, 'x', f32), _dev(offmask, 'offmask', f32),
+                                 n, cin, cout, h, w, int(stride), _dev(image_t, 'image_t', torch.uint8), int(bool(sigmoid_grad)),
+                                 None if dx is None else _dev(dx, 'dx', f32), _dev(doff, 'doff', f32), _stream())
+    _lib.check(code, 'gd4d_dcn_bwd_data')
+    return dx, doff
+
+
+def _dcn_partitions(lib, dev, n, cin, h, w, stride, partitions, waves_per_block):
+    if dev.type != 'cuda':
+        raise _lib.Gd4dError('x must live on the GPU (no CPU fallback in graph-detr4d_amd)')
+    if partitions is None:
+        tiles = int(lib.gd4d_dcn_wgrad_tiles(n, h, w, int(stride)))
+        blocks = 2 * torch.cuda.get_device_properties(dev).multi_processor_count * (4 // waves_per_block)
+        partitions = max(1, min(tiles, blocks // (9 * cin // 32), 4096))
+    return int(partitions)
+
+
+def dcn_wgrad(dout, x, offmask, cout, stride=1, y=None, scale=None, partitions=None):
+    """gd4d_dcn_wgrad: (dW (cout, Cin, 3, 3), dbias (cout)) of dcn_fwd, the modulated samples recomputed as the forward forms them; y /
+    scale as dcn_bwd_data.  One launch plus the reduction over `partitions` partial sums (default: about two workgroups per compute
+    unit, at most one partition per 64-pixel tile)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    n, cin, cout, h, w, ho, wo = _dcn_bwd_args('dcn_wgrad', dout, y, scale, x, offmask, cout, stride)
+    partitions = _dcn_partitions(lib, x.device, n, cin, h, w, stride, partitions, 4)
+    nbytes = int(lib.gd4d_dcn_wgrad_workspace_bytes(cin, cout, partitions))
+    if nbytes == 0:
+        raise _lib.Gd4dError(f'dcn_wgrad: Cin = {cin}, Cout = {cout}, partitions = {partitions}: the kernel takes channels that are multiples '
+                             'of 64 in [64, 512] and 1..4096 partitions')
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=f32)
+    dw = torch.empty(cout, cin, 3, 3, device=x.device, dtype=f32)
+    db = torch.empty(cout, device=x.device, dtype=f32)
+    code = lib.gd4d_dcn_wgrad(_dev(dout, 'dout', f32), None if y is None else _dev(y, 'y', f32),
+                              None if scale is None else _dev(scale, 'scale', f32), _dev(x, 'x', f32), _dev(offmask, 'offmask', f32),
+                              n, cin, cout, h, w, int(stride), partitions, _dev(ws, 'workspace', f32), _dev(dw, 'dw', f32),
+                              _dev(db, 'dbias', f32), _stream())
+    _lib.check(code, 'gd4d_dcn_wgrad')
+    return dw, db
+
+
+def _dcn_doff(name, doff, x, stride):
+    n, cin, h, w = _dcn_x(x, name)
+    ho, wo = dcn_out_hw(h, w, stride)
+    if tuple(doff.shape) != (n, DCN_OFFSET_CHANNELS, ho, wo):
+        raise ValueError(f'{name}: doff must be ({n}, {DCN_OFFSET_CHANNELS}, {ho}, {wo}), got {tuple(doff.shape)}')
+    return n, cin, h, w
+
+
+def dcn_offset_conv_dgrad(doff, weight, dx, stride=1):
+    """gd4d_dcn_offset_conv_dgrad: dx (N, Cin, H, W) += conv_transpose3x3(doff (N, 27, Ho, Wo), weight (27, Cin, 3, 3); stride, pad 1), in
+    place: a plain read-modify-write (run it after dcn_bwd_data on the same stream).  Returns dx."""
+    lib = _lib.load()
+    f32 = torch.float32
+    n, cin, h, w = _dcn_doff('dcn_offset_conv_dgrad', doff, dx, stride)
+    if tuple(weight.shape) != (DCN_OFFSET_CHANNELS, cin, 3, 3):
+        raise ValueError(f'dcn_offset_conv_dgrad: weight must be ({DCN_OFFSET_CHANNELS}, {cin}, 3, 3)')
+    code = lib.gd4d_dcn_offset_conv_dgrad(_dev(doff, 'doff', f32), _dev(weight, 'weight', f32), n, cin, h, w, int(stride), _dev(dx, 'dx', f32),
+                                          _stream())
+    _lib.check(code, 'gd4d_dcn_offset_conv_dgrad')
+    return dx
+
+
+def dcn_offset_conv_wgrad(doff, x, stride=1, partitions=None):
+    """gd4d_dcn_offset_conv_wgrad: (dW (27, Cin, 3, 3), db (27)) of conv_offset from doff (N, 27, Ho, Wo) and its input x; `partitions` as
+    dcn_wgrad."""
+    lib = _lib.load()
+    f32 = torch.float32
+    n, cin, h, w = _dcn_doff('dcn_offset_conv_wgrad', doff, x, stride)
+    partitions = _dcn_partitions(lib, x.device, n, cin, h, w, stride, partitions, 1)
+    nbytes = int(lib.gd4d_dcn_offset_conv_wgrad_workspace_bytes(cin, partitions))
+    if nbytes == 0:
+        raise _lib.Gd4dError(f'dcn_offset_conv_wgrad: Cin = {cin}, partitions = {partitions}: the kernel takes Cin a multiple of 64 in '
+                             '[64, 512] and 1..4096 partitions')
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=f32)
+    dw = torch.empty(DCN_OFFSET_CHANNELS, cin, 3, 3, device=x.device, dtype=f32)
+    db = torch.empty(DCN_OFFSET_CHANNELS, device=x.device, dtype=f32)
+    code = lib.gd4d_dcn_offset_conv_wgrad(_dev(doff, 'doff', f32), _dev(x, 'x', f32), n, cin, h, w, int(stride), partitions,
+                                          _dev(ws, 'workspace', f32), _dev(dw, 'dw', f32), _dev(db, 'db', f32), _stream())
+    _lib.check(code, 'gd4d_dcn_offset_conv_wgrad')
+    return dw, db
+
+
 def _first_tensor(args):
     for a in args:
         if torch.is_tensor(a):

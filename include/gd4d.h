@@ -1500,7 +1500,7 @@ int gd4d_fpn_extra_conv_wgrad(const float* dy, const float* x, int n, int channe
 int gd4d_fpn_bias_grad(const float* g, int n, int channels, int h, int w, float* workspace, float* db, void* stream);
 
 /* DCNv2, the modulated deformable 3x3 convolution of the R50 / R101 backbones (mmcv 1.x ModulatedDeformConv2dPack with
- * deform_groups = groups = dilation = 1, padding 1), inference forward (gd4d_dcn.hip; additive exports, the ABI version stays).
+ * deform_groups = groups = dilation = 1, padding 1), forward (gd4d_dcn.hip; additive exports, the ABI version stays).
  * With s the stride, tap k = 3 ky + kx and o (N, 27, Ho, Wo) the offset / modulation map (channel 2 k: dy_k, 2 k + 1: dx_k, 18 + k: m_k,
  * already through the sigmoid):
  *     out[n, co, y, x] = sum_{ci, k} w[co, ci, k] m_k[n, y, x] bilinear0(x[n, ci], y s - 1 + ky + dy_k, x s - 1 + kx + dx_k)
@@ -1522,6 +1522,44 @@ int gd4d_dcn_offset_conv_fwd(const float* x, int n, int cin, int h, int w, int s
                              float* offmask, void* stream);
 int gd4d_dcn_fwd(const float* x, const float* offmask, int n, int cin, int cout, int h, int w, int stride, const void* image,
                  const float* scale, const float* shift, int relu, float* out, void* stream);
+
+/* DCNv2, training (gd4d_dcn_train.hip; additive exports, the ABI version stays).  Notation as above; m_k the modulation after the
+ * sigmoid, S[ci, k, p] the UNmodulated bilinear0 sample, wgt_j / v_j the weight / value of corner j (00, 01, 10, 11), ly / lx the
+ * fractions.  With dout (N, cout, Ho, Wo) the incoming gradient:
+ *     g[co, p]    = dout[co, p] * (y[co, p] > 0, when y is given: the forward's output where it applied its ReLU) * (scale[co], when given)
+ *     c[ci, k, p] = sum_co w[co, ci, k] g[co, p]                          (never written to memory)
+ *     doff[2 k]   = m_k sum_ci c ((1 - lx)(v10 - v00) + lx (v11 - v01))    doff[2 k + 1] = m_k sum_ci c ((1 - ly)(v01 - v00) + ly (v11 - v10))
+ *     doff[18 + k] = sum_ci c S, times m_k (1 - m_k) when sigmoid_grad != 0 (the gradient of conv_offset's raw output)
+ *     dx[ci, corner j of P_k(p)] += m_k wgt_j c                            dw[co, ci, k] = sum_{n, p} g m_k S,  dbias[co] = sum_{n, p} g
+ * Floor and fraction are taken of the offset, as in the forward: at an integer sample coordinate the offset gradient is the
+ * derivative from the right (mmcv's convention).
+ * gd4d_dcn_weight_image_t - the weight as the data kernel's A operand (rows (tap, ci), K = cout): gd4d_dcn_weight_image_t_bytes(cin,
+ *   cout) = 9 cin cout 4 bytes, 16-B aligned; cin and cout multiples of 64 in [64, 512], else 0 bytes / GD4D_EUNSUPPORTED.
+ * gd4d_dcn_bwd_data - doff (N, 27, Ho, Wo) and dx (N, cin, H, W) in one pass.  dx is ACCUMULATED with float atomics into a buffer the
+ *   caller zeroed: it is the one output whose last bits depend on the run; NULL: not wanted.  doff is written, every sum in a fixed order.
+ * gd4d_dcn_wgrad - dw (cout, cin, 3, 3) and dbias (cout): `partitions` (1..4096) partial sums over the gd4d_dcn_wgrad_tiles(n, h, w,
+ *   stride) 64-pixel tiles in a workspace of gd4d_dcn_wgrad_workspace_bytes(cin, cout, partitions) bytes (16-B aligned), added in
+ *   partition order by a second kernel; partitions beyond the tile count contribute zeros.  The samples are recomputed as the forward
+ *   forms them.  Fixed order: two runs give the same bits; another partition count is another order.
+ * gd4d_dcn_offset_conv_dgrad - dx (N, cin, H, W) += conv_transpose3x3(doff, weight (27, cin, 3, 3) fp32; stride, pad 1): a plain
+ *   read-modify-write, to run after gd4d_dcn_bwd_data on the same stream.
+ * gd4d_dcn_offset_conv_wgrad - dw (27, cin, 3, 3) = sum_{n, p} doff[j, p] x[ci, p s - 1 + tap], db (27) = sum doff: the same partition
+ *   scheme, gd4d_dcn_offset_conv_wgrad_workspace_bytes(cin, partitions) bytes.
+ * Limits and error codes as the forward's; partitions outside 1..4096 or sigmoid_grad other than 0 / 1: GD4D_EUNSUPPORTED (0 bytes);
+ * a NULL required pointer: GD4D_EINVAL; an image or workspace not 16-B aligned: GD4D_EALIGN.  y, scale (and dx of gd4d_dcn_bwd_data)
+ * may be NULL. */
+size_t gd4d_dcn_weight_image_t_bytes(int cin, int cout);
+int gd4d_dcn_weight_image_t(const float* weight, int cin, int cout, void* image, void* stream);
+int gd4d_dcn_bwd_data(const float* dout, const float* y, const float* scale, const float* x, const float* offmask, int n, int cin,
+                      int cout, int h, int w, int stride, const void* image_t, int sigmoid_grad, float* dx, float* doff, void* stream);
+long long gd4d_dcn_wgrad_tiles(int n, int h, int w, int stride);
+size_t gd4d_dcn_wgrad_workspace_bytes(int cin, int cout, int partitions);
+int gd4d_dcn_wgrad(const float* dout, const float* y, const float* scale, const float* x, const float* offmask, int n, int cin, int cout,
+                   int h, int w, int stride, int partitions, float* workspace, float* dw, float* dbias, void* stream);
+int gd4d_dcn_offset_conv_dgrad(const float* doff, const float* weight, int n, int cin, int h, int w, int stride, float* dx, void* stream);
+size_t gd4d_dcn_offset_conv_wgrad_workspace_bytes(int cin, int partitions);
+int gd4d_dcn_offset_conv_wgrad(const float* doff, const float* x, int n, int cin, int h, int w, int stride, int partitions,
+                               float* workspace, float* dw, float* db, void* stream);
 
 #ifdef __cplusplus
 }
