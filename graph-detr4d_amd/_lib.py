@@ -189,6 +189,15 @@ SIGNATURES = {
     'gd4d_dcn_offset_conv_dgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'gd4d_dcn_offset_conv_wgrad_workspace_bytes': (_c.c_size_t, [_i, _i]),
     'gd4d_dcn_offset_conv_wgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'gd4d_conv3x3_image_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_conv3x3_image': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_conv3x3_bn_relu_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
+    'gd4d_osa_concat_image_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_osa_concat_image': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_osa_concat_tiles': (_c.c_longlong, [_i, _i]),
+    'gd4d_osa_concat_conv_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    'gd4d_ese_gate_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'gd4d_ese_apply_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -15,12 +15,15 @@ differentiable grid_sample route), and so is `hip_train=True`: the same one call
 Scope: depth 50 / 101, style 'pytorch', the plain 7x7 stem, BatchNorm, `fallback_on_stride=False`; `num_stages`, `out_indices`,
 `strides`, `dilations`, `frozen_stages`, `norm_eval`, `dcn`, `stage_with_dcn`, `zero_init_residual`.  deep_stem, avg_down, plugins, other
 norms and `with_cp` are refused: nothing shipped uses them.
+
+The VoVNet configurations' backbone, `VoVNet` / `VoVNetCP`, is in vovnet.py and re-exported here.
 """
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
 from .registry import BACKBONES, build_conv_layer
+from .vovnet import VoVNet, VoVNetCP  # noqa: F401  (the VoVNet configurations' backbone: vovnet.py)
 
 
 def _norm(norm_cfg, channels):

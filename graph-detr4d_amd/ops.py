@@ -3537,6 +3537,154 @@ def dcn_offset_conv_wgrad(doff, x, stride=1, partitions=None):
     return dw, db
 
 
+# ---- VoVNet: 3x3 conv + frozen BN + ReLU, the OSA aggregation, eSE (gd4d_vovnet.hip) -------------------------------------------
+OSA_MAX_SOURCES = 6
+
+
+def conv3x3_image(weight):
+    """gd4d_conv3x3_image: a 3x3 weight (Cout, Cin, 3, 3) fp32 -> its bf16 hi / lo fragment image.  Cin a multiple of 32 in [32, 1024],
+    Cout a multiple of 32 in [32, 256].  Remake it when the weight changes."""
+    lib = _lib.load()
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise _lib.Gd4dError(f'conv3x3_image: weight {tuple(weight.shape)}; the kernel takes (Cout, Cin, 3, 3)')
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    nbytes = int(lib.gd4d_conv3x3_image_bytes(cin, cout))
+    if nbytes == 0:
+        raise _lib.Gd4dError(f'conv3x3_image: weight {tuple(weight.shape)}; the kernel takes Cin a multiple of 32 in [32, 1024] and Cout '
+                             'a multiple of 32 in [32, 256]')
+    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
+    code = lib.gd4d_conv3x3_image(_dev(weight.contiguous(), 'weight', torch.float32), cin, cout, _dev(img, 'image', torch.uint8), _stream())
+    _lib.check(code, 'gd4d_conv3x3_image')
+    return img
+
+
+def conv3x3_bn_relu(x, image, cout, scale, shift, stride=1, out=None, m_blocks=0):
+    """gd4d_conv3x3_bn_relu_fwd: x (N, Cin, H, W) fp32 NCHW -> relu(conv3x3(x; stride, pad 1) * scale + shift), (N, cout, Ho, Wo); image =
+    conv3x3_image(weight), scale / shift (cout) the folded frozen BatchNorm.  m_blocks: 0, or the M tiling to force (1, 2, 3, 4, 5 or 7
+    row blocks of 32 channels per workgroup, dividing cout / 32; the same bits either way)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    n, cin, h, w = _dcn_x(x, 'conv3x3_bn_relu')
+    cout = int(cout)
+    ho, wo = dcn_out_hw(h, w, stride)
+    for t, name in ((scale, 'scale'), (shift, 'shift')):
+        if tuple(t.shape) != (cout,):
+            raise ValueError(f'conv3x3_bn_relu: {name} must be ({cout},)')
+    nbytes = int(lib.gd4d_conv3x3_image_bytes(cin, cout))
+    if nbytes == 0 or nbytes != image.numel():
+        raise _lib.Gd4dError(f'conv3x3_bn_relu: the image is not conv3x3_image of a ({cout}, {cin}, 3, 3) weight the kernel takes '
+                             '(Cin a multiple of 32 in [32, 1024], Cout a multiple of 32 in [32, 256])')
+    if out is None:
+        out = torch.empty(n, cout, ho, wo, device=x.device, dtype=f32)
+    elif tuple(out.shape) != (n, cout, ho, wo):
+        raise ValueError(f'conv3x3_bn_relu: out must be ({n}, {cout}, {ho}, {wo})')
+    code = lib.gd4d_conv3x3_bn_relu_fwd(_dev(x, 'x', f32), n, cin, h, w, int(stride), _dev(image, 'image', torch.uint8), cout,
+                                        _dev(scale, 'scale', f32), _dev(shift, 'shift', f32), _dev(out, 'out', f32), int(m_blocks), _stream())
+    _lib.check(code, 'gd4d_conv3x3_bn_relu_fwd')
+    return out
+
+
+def osa_concat_image(weight):
+    """gd4d_osa_concat_image: the aggregation's weight (Cout, K) or (Cout, K, 1, 1) fp32 -> its fragment image.  K a multiple of 32 in
+    [32, 2304], Cout a multiple of 32 in [32, 1024]."""
+    lib = _lib.load()
+    if weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1):
+        weight = weight.reshape(weight.shape[0], weight.shape[1])
+    if weight.dim() != 2:
+        raise _lib.Gd4dError(f'osa_concat_image: weight {tuple(weight.shape)}; the kernel takes (Cout, K) or (Cout, K, 1, 1)')
+    cout, k = int(weight.shape[0]), int(weight.shape[1])
+    nbytes = int(lib.gd4d_osa_concat_image_bytes(k, cout))
+    if nbytes == 0:
+        raise _lib.Gd4dError(f'osa_concat_image: weight {tuple(weight.shape)}; the kernel takes K a multiple of 32 in [32, 2304] and Cout '
+                             'a multiple of 32 in [32, 1024]')
+    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
+    code = lib.gd4d_osa_concat_image(_dev(weight.contiguous(), 'weight', torch.float32), k, cout, _dev(img, 'image', torch.uint8), _stream())
+    _lib.check(code, 'gd4d_osa_concat_image')
+    return img
+
+
+def osa_concat_conv(sources, image, cout, scale, shift, out=None, partials=None, m_blocks=0):
+    """gd4d_osa_concat_conv_fwd: relu((W . concat(sources)) * scale + shift) for 1..6 separate NCHW fp32 maps of the same (N, H, W), each
+    with a multiple of 32 channels; the concatenation is never written.  Returns (out (N, cout, H, W), partials (N, tiles, cout)): each
+    128-pixel tile's per-channel sum of the outputs, what ese_gate averages.  m_blocks: as conv3x3_bn_relu's."""
+    lib = _lib.load()
+    f32 = torch.float32
+    sources = list(sources)
+    if not 1 <= len(sources) <= OSA_MAX_SOURCES:
+        raise _lib.Gd4dError(f'osa_concat_conv: {len(sources)} sources; the kernel takes 1 to {OSA_MAX_SOURCES}')
+    n, _, h, w = _dcn_x(sources[0], 'osa_concat_conv')
+    for s in sources:
+        if s.dim() != 4 or (int(s.shape[0]), int(s.shape[2]), int(s.shape[3])) != (n, h, w):
+            raise ValueError(f'osa_concat_conv: every source must be ({n}, C_i, {h}, {w}), got {tuple(s.shape)}')
+    chans = [int(s.shape[1]) for s in sources]
+    cout = int(cout)
+    for t, name in ((scale, 'scale'), (shift, 'shift')):
+        if tuple(t.shape) != (cout,):
+            raise ValueError(f'osa_concat_conv: {name} must be ({cout},)')
+    nbytes = int(lib.gd4d_osa_concat_image_bytes(sum(chans), cout))
+    if nbytes == 0 or nbytes != image.numel() or any(c % 32 for c in chans):
+        raise _lib.Gd4dError(f'osa_concat_conv: sources of {chans} channels -> {cout}: the kernel takes multiples of 32, K up to 2304 and '
+                             'Cout up to 1024, with image = osa_concat_image of the (Cout, K) weight')
+    tiles = int(lib.gd4d_osa_concat_tiles(h, w))
+    if out is None:
+        out = torch.empty(n, cout, h, w, device=sources[0].device, dtype=f32)
+    elif tuple(out.shape) != (n, cout, h, w):
+        raise ValueError(f'osa_concat_conv: out must be ({n}, {cout}, {h}, {w})')
+    if partials is None:
+        partials = torch.empty(n, tiles, cout, device=sources[0].device, dtype=f32)
+    elif tuple(partials.shape) != (n, tiles, cout):
+        raise ValueError(f'osa_concat_conv: partials must be ({n}, {tiles}, {cout})')
+    ptrs = (ctypes.c_void_p * len(sources))(*[_dev(s, 'sources', f32) for s in sources])
+    ch = (ctypes.c_int32 * len(sources))(*chans)
+    code = lib.gd4d_osa_concat_conv_fwd(ptrs, ch, len(sources), n, h, w, _dev(image, 'image', torch.uint8), cout,
+                                        _dev(scale, 'scale', f32), _dev(shift, 'shift', f32), _dev(out, 'out', f32),
+                                        _dev(partials, 'partials', f32), int(m_blocks), _stream())
+    _lib.check(code, 'gd4d_osa_concat_conv_fwd')
+    return out, partials
+
+
+def ese_gate(partials, hw, fc_weight, fc_bias, out=None):
+    """gd4d_ese_gate_fwd: partials (N, tiles, C) of osa_concat_conv, hw = H W -> gate (N, C) = relu6(fc_weight mean + fc_bias + 3) / 6;
+    fc_weight (C, C) or (C, C, 1, 1), C a multiple of 32 up to 1024."""
+    lib = _lib.load()
+    f32 = torch.float32
+    if partials.dim() != 3:
+        raise ValueError('ese_gate: partials (N, tiles, C) expected')
+    n, tiles, c = (int(v) for v in partials.shape)
+    if fc_weight.numel() != c * c or tuple(fc_weight.shape[:2]) != (c, c) or tuple(fc_bias.shape) != (c,):
+        raise ValueError(f'ese_gate: fc_weight ({c}, {c}[, 1, 1]) and fc_bias ({c},) expected')
+    if c % 32 or not 32 <= c <= 1024:
+        raise _lib.Gd4dError(f'ese_gate: C = {c}; the kernel takes a multiple of 32 in [32, 1024]')
+    if out is None:
+        out = torch.empty(n, c, device=partials.device, dtype=f32)
+    elif tuple(out.shape) != (n, c):
+        raise ValueError(f'ese_gate: out must be ({n}, {c})')
+    code = lib.gd4d_ese_gate_fwd(_dev(partials, 'partials', f32), n, tiles, c, int(hw), _dev(fc_weight, 'fc_weight', f32),
+                                 _dev(fc_bias, 'fc_bias', f32), _dev(out, 'out', f32), _stream())
+    _lib.check(code, 'gd4d_ese_gate_fwd')
+    return out
+
+
+def ese_apply(xt, gate, identity=None, out=None):
+    """gd4d_ese_apply_fwd: xt (N, C, H, W) * gate (N, C) (+ identity, xt's shape) -> out (a new tensor, or the one given: xt itself is
+    allowed)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    n, c, h, w = _dcn_x(xt, 'ese_apply')
+    if tuple(gate.shape) != (n, c):
+        raise ValueError(f'ese_apply: gate must be ({n}, {c})')
+    if identity is not None and identity.shape != xt.shape:
+        raise ValueError(f'ese_apply: identity must have xt\'s shape {tuple(xt.shape)}, got {tuple(identity.shape)}')
+    if out is None:
+        out = torch.empty_like(xt)
+    elif out.shape != xt.shape:
+        raise ValueError(f'ese_apply: out must have xt\'s shape {tuple(xt.shape)}')
+    code = lib.gd4d_ese_apply_fwd(_dev(xt, 'xt', f32), _dev(gate, 'gate', f32), None if identity is None else _dev(identity, 'identity', f32),
+                                  n, c, h * w, _dev(out, 'out', f32), _stream())
+    _lib.check(code, 'gd4d_ese_apply_fwd')
+    return out
+
+
 def _first_tensor(args):
     for a in args:
         if torch.is_tensor(a):

@@ -3,8 +3,8 @@
 Mirror of `Detr3D.extract_img_feat` / `extract_feat` (projects/mmdet3d_plugin/models/detectors/detr3d.py:39-72): the
 (B, N, 3, H, W) image batch is folded to (B*N, 3, H, W), pushed through the image backbone and neck, and every level is
 unfolded to (B, N, C, H_l, W_l) fp32 - the `value` list the attention modules take.  The backbone and neck are the
-caller's (mmdet's ResNet / VoVNet + FPN in the reference; PyTorch-ROCm modules here).  The backbone stays plain PyTorch (outside
-the hot path); for the neck the package has `FPN` / `CPFPN` on its own kernels (fpn.py).  `ResNet18FPN` is a small stand-in for BASELINE.json configs[0] ("DETR3D 1-layer
+caller's (mmdet's ResNet / VoVNet + FPN in the reference; PyTorch-ROCm modules here).  The package has both backbones the configs build - `ResNet` with DCNv2 (backbones.py, dcn.py)
+and `VoVNet` / `VoVNetCP` (vovnet.py), each with its hot convolutions on the library's kernels - and for the neck `FPN` / `CPFPN` on its own kernels (fpn.py).  `ResNet18FPN` is a small stand-in for BASELINE.json configs[0] ("DETR3D 1-layer
 decoder, 100 queries, 6 x (3 x 256 x 256) synthetic images, ResNet18 backbone on CPU"): a BasicBlock ResNet-18 with
 an FPN configured like the reference's necks (config detr3d_res50.py: start_level=1, add_extra_convs='on_output',
 num_outs=4, relu_before_extra_convs=True), giving strides 8 / 16 / 32 / 64.

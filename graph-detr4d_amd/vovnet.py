@@ -1,0 +1,399 @@
+"""VoVNet with eSE, the image backbone of the reference's VoVNet configurations (models/backbones/vovnet.py `VoVNet`, vovnetcp.py
+`VoVNetCP`; eight shipped configs, all `spec_name='V-99-eSE'`):
+    img_backbone=dict(type='VoVNetCP', spec_name='V-99-eSE', norm_eval=True, frozen_stages=-1, input_ch=3, out_features=('stage4', 'stage5'))
+`VoVNet.forward` returns a dict keyed by feature name, `VoVNetCP.forward` a list in stage order.  Both keep the reference's module
+tree, so the state-dict keys are its own (`stem.stem_1/conv.weight`, `stage3.OSA3_2.layers.4.OSA3_2_4/norm.running_var`,
+`stage2.OSA2_1.concat.OSA2_1_concat/conv.weight`, `stage5.OSA5_3.ese.fc.bias`) and a checkpoint's backbone slice loads with strict=True.
+
+The network: a stem of three conv3x3 + BN + ReLU (strides 2, 1, 2), then stages 2-5 of OSA modules, a MaxPool2d(3, 2, ceil_mode=True)
+in front of stages 3-5.  One OSA module (L layers of `stage_ch` channels, `concat_ch` outputs):
+    x_0 = input;  x_i = relu(bn_i(conv3x3_i(x_{i-1})))  (i = 1 .. L);  xt = relu(bn(conv1x1(cat(x_0 .. x_L))))
+    out = xt * relu6(fc(mean_{hw}(xt)) + 3) / 6  (+ input, in every module of a stage but its first)
+
+What runs where.  The default route is inference on the library's kernels (gd4d_vovnet.hip), eight launches per five-layer module:
+    ops.conv3x3_bn_relu   x L     the 3x3 convolutions, BatchNorm (folded: scale, shift) and ReLU in the epilogue; also stem_2 and stem_3
+    ops.osa_concat_conv           the aggregation reads the L + 1 maps where they lie: the concatenation is never written; its epilogue
+                                  also leaves each tile's per-channel sums for the pool
+    ops.ese_gate, ops.ese_apply   the (C x C) matvec per image, then xt * gate (+ input) in place
+Stock torch inside the kernel route, deliberately: `stem_1` (3 input channels, K = 27: F.conv2d, then the folded BatchNorm and ReLU)
+and the MaxPool2d in front of stages 3-5.  Inputs that are not fp32 contiguous NCHW are converted with `.float().contiguous()`.
+    torch_ops=False   True (or GD4D_TORCH_OPS=1 for the whole process): the reference's op sequence - differentiable, any device and
+                      dtype, `torch.utils.checkpoint` per OSA module for VoVNetCP (with_cp=True) in train() mode, and the route for the
+                      specs outside the kernels' limits.
+                      The switch lives on the stem and on each OSA module (they decide their route per call); the network's
+                      `torch_ops` attribute, and `with Fn.torch_ops_for(net):`, set all of them.
+The kernels' limits: plain (not depthwise) 3x3 layers, every channel count a multiple of 32, 3x3 inputs up to 1024 and outputs up to 256
+channels, at most five layers per module, concatenations up to 2304 and module outputs up to 1024 channels: V-19-eSE, V-39, V-57 and
+V-99.  The two depthwise specs and V-19-slim-eSE (80- and 112-channel layers) are refused AT CONSTRUCTION unless torch_ops=True.  The
+kernel route raises Gd4dError, naming `torch_ops=True`, in train() mode with a BatchNorm that is not frozen (norm_eval=False), when
+autograd wants a gradient (a parameter or the input requires grad and grad mode is on), and on CPU tensors.  There is no HIP backward yet.
+
+Kept state: per convolution its weight image and the folded (scale, shift) of its BatchNorm, each under ops._Stamp's validity rule and
+each at a FIXED device address (a changed parameter is rebuilt into the same buffer by the next eager call, or by `refresh_images()`).
+The maps, partials and gates are new tensors every call (torch's caching allocator).  So a forward can be captured in a hipGraph after
+one eager call; capturing with a missing or stale image raises instead of allocating.
+"""
+import warnings
+from collections import OrderedDict
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+import torch.utils.checkpoint as cp
+from torch.nn.modules.batchnorm import _BatchNorm
+
+from . import _lib
+from . import functional as Fn
+from . import ops
+from .registry import BACKBONES
+
+
+def _spec(stem, conv_ch, out_ch, layers, blocks, dw):
+    return dict(stem=stem, stage_conv_ch=conv_ch, stage_out_ch=out_ch, layer_per_block=layers, block_per_stage=blocks, eSE=True, dw=dw)
+
+
+_WIDE, _SLIM = ([128, 160, 192, 224], [256, 512, 768, 1024]), ([64, 80, 96, 112], [112, 256, 384, 512])
+_STAGE_SPECS = {
+    'V-19-slim-dw-eSE': _spec([64, 64, 64], *_SLIM, 3, [1, 1, 1, 1], True),
+    'V-19-dw-eSE': _spec([64, 64, 64], *_WIDE, 3, [1, 1, 1, 1], True),
+    'V-19-slim-eSE': _spec([64, 64, 128], *_SLIM, 3, [1, 1, 1, 1], False),
+    'V-19-eSE': _spec([64, 64, 128], *_WIDE, 3, [1, 1, 1, 1], False),
+    'V-39-eSE': _spec([64, 64, 128], *_WIDE, 5, [1, 1, 2, 2], False),
+    'V-57-eSE': _spec([64, 64, 128], *_WIDE, 5, [1, 1, 4, 3], False),
+    'V-99-eSE': _spec([64, 64, 128], *_WIDE, 5, [1, 3, 9, 3], False),
+}
+
+
+def _conv_bn_relu(cin, cout, name, kernel_size, stride=1):
+    """The reference's conv3x3 / conv1x1 triple: `<name>/conv` (no bias), `<name>/norm`, `<name>/relu`."""
+    return [(f'{name}/conv', nn.Conv2d(cin, cout, kernel_size=kernel_size, stride=stride, padding=kernel_size // 2, bias=False)),
+            (f'{name}/norm', nn.BatchNorm2d(cout)),
+            (f'{name}/relu', nn.ReLU(inplace=True))]
+
+
+def _dw_conv_bn_relu(cin, cout, name, stride=1):
+    """The reference's dw_conv3x3: a depthwise 3x3 (groups = out channels), a pointwise 1x1, one BatchNorm, ReLU."""
+    return [(f'{name}/dw_conv3x3', nn.Conv2d(cin, cout, kernel_size=3, stride=stride, padding=1, groups=cout, bias=False)),
+            (f'{name}/pw_conv1x1', nn.Conv2d(cin, cout, kernel_size=1, bias=False)),
+            (f'{name}/pw_norm', nn.BatchNorm2d(cout)),
+            (f'{name}/pw_relu', nn.ReLU(inplace=True))]
+
+
+class Hsigmoid(nn.Module):
+    """The hard sigmoid clamp(v + 3, 0, 6) / 6."""
+
+    def forward(self, v):
+        return torch.clamp(v + 3.0, min=0.0, max=6.0) / 6.0
+
+
+class eSEModule(nn.Module):
+    """Effective squeeze-excitation: x * hsigmoid(fc(mean over the pixels of x)), fc a 1x1 convolution C -> C with a bias (the only
+    parameters, so the keys are `ese.fc.weight` / `ese.fc.bias`)."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.fc = nn.Conv2d(channels, channels, 1)
+        self.avg_pool, self.hsigmoid = nn.AdaptiveAvgPool2d(1), Hsigmoid()
+
+    def forward(self, x):
+        return x * self.hsigmoid(self.fc(self.avg_pool(x)))
+
+
+def _f32(x):
+    return x if x.dtype == torch.float32 and x.is_contiguous() else x.float().contiguous()
+
+
+class _KernelRoute:
+    """What the stem and the OSA module share: the route decision and the values kept from parameters."""
+    torch_ops = False
+
+    def _init_route(self, torch_ops, limits):
+        self.torch_ops = bool(torch_ops)
+        self._kernel_limits = limits
+        self._kept = {}             # key -> (ops._Stamp, value at a fixed address)
+        # what the route decision reads on every call, listed once: the subtree is built in __init__ and never altered
+        self._norms = tuple(m for m in self.modules() if isinstance(m, _BatchNorm))
+        self._params = tuple(self.parameters())
+
+    def _route_name(self):
+        limits = f': {"; ".join(self._kernel_limits)}' if self._kernel_limits else ''
+        return f'{type(self).__name__}{limits}'
+
+    def _uses_torch_ops(self, x):
+        if Fn.torch_ops_route(self._route_name(), True, module=self):
+            return True
+        Fn.torch_ops_route(self._route_name(), not self._kernel_limits, module=self)     # raises when outside the limits
+        name = type(self).__name__
+        if any(m.training or m.running_mean is None for m in self._norms):
+            raise _lib.Gd4dError(f'{name} in train() mode with a BatchNorm that is not frozen: graph-detr4d_amd\'s VoVNet kernels fold the '
+                                 'running statistics into the convolutions and have no backward.  `torch_ops=True` (or GD4D_TORCH_OPS=1) '
+                                 'runs the reference\'s op sequence, trainable by autograd; norm_eval=True (every config) keeps the '
+                                 'BatchNorms in eval() mode.')
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._params)):
+            raise _lib.Gd4dError(f'{name}: autograd is on, and graph-detr4d_amd\'s VoVNet kernels have no backward.  Run inference under '
+                                 'torch.no_grad() (or freeze the parameters and the input), or choose the torch-op route '
+                                 '(`torch_ops=True` / GD4D_TORCH_OPS=1).')
+        Fn.require_gpu(x, 'inputs')
+        return False
+
+    def _keep(self, key, sources, build):
+        """build()'s value of `sources` under ops._Stamp's rule, at a fixed device address: a stale value is rebuilt INTO its buffer."""
+        ent = self._kept.get(key)
+        dev = sources[0].device
+        if ent is not None and ent[0].valid(sources) and ent[1].device == dev:
+            return ent[1]
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'{type(self).__name__} under hipGraph capture: call the module (or refresh_images) once eagerly first - '
+                               'its weight images are not on the device yet, or a parameter changed since they were made')
+        with torch.no_grad():
+            value = build()
+        if ent is not None and ent[1].device == value.device and ent[1].shape == value.shape:
+            ent[1].copy_(value)
+            value = ent[1]
+        self._kept[key] = (ops._Stamp(tuple(sources)), value)
+        return value
+
+    def _image(self, key, conv):
+        build = ops.conv3x3_image if conv.kernel_size == (3, 3) else ops.osa_concat_image
+        return self._keep(('image', key), (conv.weight,), lambda: build(conv.weight.detach().float()))
+
+    def _folded(self, key, bn):
+        """(2, C): scale = gamma / sqrt(var + eps) and shift = beta - mean scale of an eval()-mode BatchNorm2d."""
+        def build():
+            scale = torch.rsqrt(bn.running_var.detach().float() + bn.eps)
+            if bn.weight is not None:
+                scale = scale * bn.weight.detach().float()
+            shift = -bn.running_mean.detach().float() * scale
+            if bn.bias is not None:
+                shift = shift + bn.bias.detach().float()
+            return torch.stack((scale, shift)).contiguous()
+        return self._keep(('bn', key, float(bn.eps)), (bn.running_var, bn.running_mean, bn.weight, bn.bias), build)
+
+    def _conv3x3_hip(self, key, x, conv, bn):
+        scale, shift = self._folded(key, bn)
+        return ops.conv3x3_bn_relu(x, self._image(key, conv), conv.out_channels, scale, shift, stride=conv.stride[0])
+
+    def refresh_images(self):
+        """For the owner of a hipGraph captured over this module: after an in-place parameter edit, rebuild the changed images and
+        folded constants into the buffers the graph reads (outside the graph, before the replay).  Writes through `.data` need
+        ops.invalidate_chain_images() first, as everywhere."""
+        if not next(self.parameters()).is_cuda:
+            raise _lib.Gd4dError('refresh_images: the module is not on the GPU (no CPU fallback in graph-detr4d_amd)')
+        for key, conv, bn in self._kernel_layers():
+            self._image(key, conv)
+            self._folded(key, bn)
+
+
+def _channel_limits(name, cin, cout, k3=True):
+    why = []
+    lim_in, lim_out = (1024, 256) if k3 else (2304, 1024)
+    if cin % 32 or not 32 <= cin <= lim_in:
+        why.append(f'{name}: {cin} input channels (kernels: multiples of 32 in [32, {lim_in}])')
+    if cout % 32 or not 32 <= cout <= lim_out:
+        why.append(f'{name}: {cout} output channels (kernels: multiples of 32 in [32, {lim_out}])')
+    return why
+
+
+class _Stem(_KernelRoute, nn.Sequential):
+    """`stem`: stem_1 (stride 2), stem_2, stem_3 (stride 2).  On the kernel route stem_1 runs on F.conv2d (3 input channels)."""
+
+    def __init__(self, input_ch, stem_ch, depthwise, torch_ops):
+        conv_type = _dw_conv_bn_relu if depthwise else (lambda cin, cout, name, stride=1: _conv_bn_relu(cin, cout, name, 3, stride))
+        layers = _conv_bn_relu(input_ch, stem_ch[0], 'stem_1', 3, 2)
+        layers += conv_type(stem_ch[0], stem_ch[1], 'stem_2', 1)
+        layers += conv_type(stem_ch[1], stem_ch[2], 'stem_3', 2)
+        nn.Sequential.__init__(self, OrderedDict(layers))
+        limits = ['depthwise stem (kernels: plain 3x3 convolutions)'] if depthwise else \
+            _channel_limits('stem_2', stem_ch[0], stem_ch[1]) + _channel_limits('stem_3', stem_ch[1], stem_ch[2])
+        self._init_route(torch_ops, limits)
+
+    def _kernel_layers(self):
+        return [(i, getattr(self, f'stem_{i}/conv'), getattr(self, f'stem_{i}/norm')) for i in (1, 2, 3)]
+
+    def refresh_images(self):
+        (_, _, bn1), *rest = self._kernel_layers()
+        self._folded(1, bn1)
+        for key, conv, bn in rest:
+            self._image(key, conv)
+            self._folded(key, bn)
+
+    def forward(self, x):
+        if self._uses_torch_ops(x):
+            return nn.Sequential.forward(self, x)
+        with torch.no_grad():
+            (_, conv1, bn1), *rest = self._kernel_layers()
+            scale, shift = self._folded(1, bn1)
+            x = F.conv2d(_f32(x), conv1.weight.detach().float(), None, conv1.stride, conv1.padding)
+            x = x.mul_(scale.view(1, -1, 1, 1)).add_(shift.view(1, -1, 1, 1)).relu_()
+            for key, conv, bn in rest:
+                x = self._conv3x3_hip(key, x, conv, bn)
+            return x
+
+
+class _OSA_module(_KernelRoute, nn.Module):
+    """One-shot aggregation: `layers` (a chain of 3x3 conv + BN + ReLU), `concat` (the 1x1 over the input and every layer's output),
+    `ese`; `identity` adds the input (the modules of a stage after its first).  A depthwise module whose input is wider than its
+    layers narrows it first (`conv_reduction`)."""
+
+    def __init__(self, in_ch, stage_ch, concat_ch, num_layers, module_name, identity=False, depthwise=False, with_cp=False,
+                 torch_ops=False):
+        nn.Module.__init__(self)
+        self.module_name, self.identity, self.depthwise, self.with_cp = module_name, identity, depthwise, with_cp
+        self.reduced = depthwise and in_ch != stage_ch
+        if self.reduced:
+            self.conv_reduction = nn.Sequential(OrderedDict(_conv_bn_relu(in_ch, stage_ch, f'{module_name}_reduction_0', 1)))
+        widths = [stage_ch if depthwise else in_ch] + [stage_ch] * num_layers          # of the chain's maps
+        make = _dw_conv_bn_relu if depthwise else (lambda cin, cout, name: _conv_bn_relu(cin, cout, name, 3))
+        self.layers = nn.ModuleList(nn.Sequential(OrderedDict(make(widths[i], widths[i + 1], f'{module_name}_{i}')))
+                                    for i in range(num_layers))
+        k = in_ch + num_layers * stage_ch
+        self.concat = nn.Sequential(OrderedDict(_conv_bn_relu(k, concat_ch, f'{module_name}_concat', 1)))
+        self.ese = eSEModule(concat_ch)
+
+        limits = ['depthwise layers (kernels: plain 3x3 convolutions)'] if depthwise else \
+            [w for i in range(min(num_layers, 2)) for w in _channel_limits(f'{module_name}_{i}' + ('..' if i else ''), widths[i], stage_ch)]
+        if num_layers + 1 > ops.OSA_MAX_SOURCES:
+            limits.append(f'{num_layers} layers per module (kernels: up to {ops.OSA_MAX_SOURCES - 1})')
+        limits += _channel_limits(f'{module_name}_concat', k, concat_ch, k3=False)
+        self._init_route(torch_ops, limits)
+
+    def _kernel_layers(self):
+        n = self.module_name
+        layers = [(i, getattr(seq, f'{n}_{i}/conv'), getattr(seq, f'{n}_{i}/norm')) for i, seq in enumerate(self.layers)]
+        return layers + [('concat', getattr(self.concat, f'{n}_concat/conv'), getattr(self.concat, f'{n}_concat/norm'))]
+
+    def _torch(self, x):
+        """The torch-op route: the chain, torch.cat, the aggregation, eSE, the residual."""
+        maps = [x]
+        y = self.conv_reduction(x) if self.reduced else x
+        for layer in self.layers:
+            y = layer(y)
+            maps.append(y)
+        out = self.ese(self.concat(torch.cat(maps, dim=1)))
+        return out + x if self.identity else out
+
+    def _hip(self, x):
+        *layers, (ckey, cconv, cbn) = self._kernel_layers()
+        maps = [_f32(x)]
+        for key, conv, bn in layers:
+            maps.append(self._conv3x3_hip(key, maps[-1], conv, bn))
+        scale, shift = self._folded(ckey, cbn)
+        xt, partials = ops.osa_concat_conv(maps, self._image(ckey, cconv), cconv.out_channels, scale, shift)
+        gate = ops.ese_gate(partials, xt.shape[2] * xt.shape[3], self.ese.fc.weight.detach(), self.ese.fc.bias.detach())
+        return ops.ese_apply(xt, gate, identity=maps[0] if self.identity else None, out=xt)
+
+    def forward(self, x):
+        if self._uses_torch_ops(x):
+            if self.with_cp and self.training:
+                return cp.checkpoint(self._torch, x, use_reentrant=False)
+            return self._torch(x)
+        with torch.no_grad():
+            return self._hip(x)
+
+
+class _OSA_stage(nn.Sequential):
+    """`stage<n>`: `Pooling` (not in stage 2), then `OSA<n>_1` .. `OSA<n>_<blocks>`; every module but the first has the residual."""
+
+    def __init__(self, stage_num, in_ch, stage_ch, concat_ch, blocks, num_layers, depthwise=False, with_cp=False, torch_ops=False):
+        super().__init__()
+        if stage_num != 2:
+            self.add_module('Pooling', nn.MaxPool2d(kernel_size=3, stride=2, ceil_mode=True))
+        for b in range(1, blocks + 1):
+            name = f'OSA{stage_num}_{b}'
+            self.add_module(name, _OSA_module(in_ch if b == 1 else concat_ch, stage_ch, concat_ch, num_layers, name, identity=b > 1,
+                                              depthwise=depthwise, with_cp=with_cp, torch_ops=torch_ops))
+
+
+@BACKBONES.register_module()
+class VoVNet(nn.Module):
+    """The reference's VoVNet: forward returns {feature name: map} for the names in `out_features` ('stem', 'stage2' .. 'stage5').
+    `pretrained` / `init_cfg` are kept as attributes and not acted on: load the checkpoint slice with load_state_dict.
+    `net.torch_ops` is the route switch of the whole network: setting it (or `with Fn.torch_ops_for(net):`) sets it on the stem and on
+    every OSA module, which decide their route themselves (so a single stage can be switched too)."""
+    _with_cp = False
+
+    def __init__(self, spec_name, input_ch=3, out_features=None, frozen_stages=-1, norm_eval=True, pretrained=None, init_cfg=None,
+                 torch_ops=False):
+        super().__init__()
+        if spec_name not in _STAGE_SPECS:
+            raise KeyError(f'{type(self).__name__}: spec_name={spec_name!r}; known: {sorted(_STAGE_SPECS)}')
+        spec = _STAGE_SPECS[spec_name]
+        self.spec_name, self.frozen_stages, self.norm_eval = spec_name, frozen_stages, norm_eval
+        self._out_features = out_features
+        if isinstance(pretrained, str):
+            warnings.warn('VoVNet: `pretrained` is deprecated, use init_cfg=dict(type="Pretrained", checkpoint=...)', DeprecationWarning)
+            init_cfg = dict(type='Pretrained', checkpoint=pretrained)
+        self.init_cfg = init_cfg
+        stem_ch, widths = spec['stem'], [spec['stem'][2]] + list(spec['stage_out_ch'])
+        self.stem = _Stem(input_ch, stem_ch, spec['dw'], torch_ops)
+        self.stage_names = [f'stage{n}' for n in (2, 3, 4, 5)]
+        for i, name in enumerate(self.stage_names):
+            self.add_module(name, _OSA_stage(i + 2, widths[i], spec['stage_conv_ch'][i], widths[i + 1], spec['block_per_stage'][i],
+                                             spec['layer_per_block'], spec['dw'], with_cp=self._with_cp, torch_ops=torch_ops))
+        self._out_feature_channels = dict(zip(['stem'] + self.stage_names, widths))
+        self._out_feature_strides = dict(zip(['stem'] + self.stage_names, (4, 4, 8, 16, 32)))
+        self.torch_ops = torch_ops
+        limits = [w for m in self._routed() for w in m._kernel_limits]
+        if limits:      # refused here, not at the first forward; raises unless the torch-op route was chosen
+            Fn.torch_ops_route(f'{type(self).__name__}({spec_name!r}): {"; ".join(limits[:4])}'
+                               + (f' and {len(limits) - 4} more' if len(limits) > 4 else '')
+                               + ' - pass torch_ops=True for this spec', False, module=self)
+
+    def _routed(self):
+        return [m for m in self.modules() if isinstance(m, _KernelRoute)]
+
+    @property
+    def torch_ops(self):
+        return self._torch_ops
+
+    @torch_ops.setter
+    def torch_ops(self, value):
+        self._torch_ops = bool(value)
+        for m in self._routed():
+            m.torch_ops = self._torch_ops
+
+    def refresh_images(self):
+        """Rebuild every changed weight image and folded BatchNorm into the buffers a captured graph reads (see the module docstring)."""
+        for m in self._routed():
+            m.refresh_images()
+
+    def _features(self, x):
+        x = self.stem(x)
+        if 'stem' in self._out_features:
+            yield 'stem', x
+        for name in self.stage_names:
+            x = getattr(self, name)(x)
+            if name in self._out_features:
+                yield name, x
+
+    def forward(self, x):
+        return dict(self._features(x))
+
+    def _freeze_stages(self):
+        """frozen_stages = k >= 0 freezes the stem and stages 2 .. k + 1: eval() mode, no gradients."""
+        frozen = ['stem'] + self.stage_names[:self.frozen_stages] if self.frozen_stages >= 0 else []
+        for name in frozen:
+            getattr(self, name).eval().requires_grad_(False)
+
+    def train(self, mode=True):
+        """Training mode with the frozen stages and (norm_eval) every BatchNorm kept in eval() mode."""
+        super().train(mode)
+        self._freeze_stages()
+        if mode and self.norm_eval:
+            for m in self.modules():
+                if isinstance(m, _BatchNorm):
+                    m.eval()
+        return self
+
+
+@BACKBONES.register_module()
+class VoVNetCP(VoVNet):
+    """The reference's VoVNetCP: forward returns the list of the `out_features` maps in network order; on the torch-op route each
+    OSA module runs under torch.utils.checkpoint in train() mode unless with_cp=False (ignored on the kernel route)."""
+
+    def __init__(self, *args, with_cp=True, **kwargs):
+        self._with_cp = bool(with_cp)
+        super().__init__(*args, **kwargs)
+
+    def forward(self, x):
+        return [m for _, m in self._features(x)]

@@ -1561,6 +1561,39 @@ size_t gd4d_dcn_offset_conv_wgrad_workspace_bytes(int cin, int partitions);
 int gd4d_dcn_offset_conv_wgrad(const float* doff, const float* x, int n, int cin, int h, int w, int stride, int partitions,
                                float* workspace, float* dw, float* db, void* stream);
 
+/* VoVNet (V-39 / V-57 / V-99 eSE), inference with frozen BatchNorm (gd4d_vovnet.hip; additive exports, the ABI version stays).  All maps
+ * contiguous NCHW fp32; split-bf16 x 3 products, fp32 sums in a fixed order, no atomics: two runs give the same bits.
+ * gd4d_conv3x3_image - a (cout, cin, 3, 3) fp32 weight split into bf16 hi / lo MFMA fragments, per block of 32 output channels; image: gd4d_conv3x3_image_bytes(cin, cout) bytes, 16-B aligned.  cin a multiple of 32 in [32, 1024], cout a
+ *   multiple of 32 in [32, 256]; anything else: 0 bytes / GD4D_EUNSUPPORTED.  Remake it when the weight changes.
+ * gd4d_conv3x3_bn_relu_fwd - out (N, cout, Ho, Wo) = relu(conv3x3(x; stride 1 or 2, pad 1, no bias) * scale[co] + shift[co]); the folded
+ *   frozen BatchNorm is scale = gamma / sqrt(var + eps), shift = beta - mean scale.  Ho = (H - 1) / stride + 1, Wo likewise.
+ * gd4d_osa_concat_image - the (cout, K) fp32 weight of the OSA aggregation (a 1x1 convolution over the concatenation), likewise; K a
+ *   multiple of 32 in [32, 2304], cout a multiple of 32 in [32, 1024]; gd4d_osa_concat_image_bytes(k, cout) bytes.
+ * gd4d_osa_concat_conv_fwd - out (N, cout, h, w) = relu((W . concat(src_0 .. src_{n_src - 1})) * scale + shift) for 1 <= n_src <= 6
+ *   separate maps (N, src_channels[i], h, w), each channel count a multiple of 32; the concatenation is never written.  partials
+ *   (N, gd4d_osa_concat_tiles(h, w), cout): each 128-pixel tile's per-channel sum of the outputs, all written.
+ * gd4d_ese_gate_fwd - gate (N, channels) = relu6(fc_w mean + fc_b + 3) / 6 with mean[n, c] = (sum over the tiles, in order, of
+ *   partials[n, t, c]) / hw; fc_w (channels, channels) row-major, 16-B aligned; channels a multiple of 32 in [32, 1024].
+ * gd4d_ese_apply_fwd - out = xt * gate[n, c] (+ identity when not NULL), (N, channels, hw) each; hw need not be a multiple of 4; xt, out
+ *   and identity 16-B aligned; out may be xt.
+ * m_blocks - the M tiling of the two GEMMs: 0 lets the library choose (the largest count of 32-channel row blocks per workgroup where
+ *   the pixel tiles fill the CUs, a smaller one where they do not); 1, 2, 3, 4, 5 or 7 dividing cout / 32 forces it (anything else: GD4D_EUNSUPPORTED).  The result's
+ *   bits do not depend on it.
+ * A NULL required pointer (a NULL entry of src included): GD4D_EINVAL; sizes outside the limits, N / h / w <= 0, more than 2^30 pixels in
+ *   one plane: GD4D_EUNSUPPORTED; a misaligned image, fc_w or map of gd4d_ese_apply_fwd: GD4D_EALIGN. */
+size_t gd4d_conv3x3_image_bytes(int cin, int cout);
+int gd4d_conv3x3_image(const float* weight, int cin, int cout, void* image, void* stream);
+int gd4d_conv3x3_bn_relu_fwd(const float* x, int n, int cin, int h, int w, int stride, const void* image, int cout, const float* scale,
+                             const float* shift, float* out, int m_blocks, void* stream);
+size_t gd4d_osa_concat_image_bytes(int k, int cout);
+int gd4d_osa_concat_image(const float* weight, int k, int cout, void* image, void* stream);
+long long gd4d_osa_concat_tiles(int h, int w);
+int gd4d_osa_concat_conv_fwd(const float* const* src, const int32_t* src_channels, int n_src, int n, int h, int w, const void* image,
+                             int cout, const float* scale, const float* shift, float* out, float* partials, int m_blocks, void* stream);
+int gd4d_ese_gate_fwd(const float* partials, int n, int tiles, int channels, int hw, const float* fc_w, const float* fc_b, float* gate,
+                      void* stream);
+int gd4d_ese_apply_fwd(const float* xt, const float* gate, const float* identity, int n, int channels, int hw, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

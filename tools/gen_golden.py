@@ -849,6 +849,68 @@ def case_fpn_cp(name, *, seed, num_cams=2, in_channels=(32, 64, 96, 128), levels
     save(name, meta, **arrays)
 
 
+def case_vovnet(name, *, seed, num_cams=2, img_hw=(52, 84), weight_keep=0.1, chan_stride=2):
+    """The reference's VoVNetCP.eval() (models/backbones/vovnetcp.py) on a tiny spec of V-99's PATTERN, inserted into the loaded module's
+    _STAGE_SPECS at run time: two layers per OSA module, one stage of two modules (so the identity path runs), every channel count a
+    multiple of 32.  Records the input, the state dict, the stem's output and the four stage outputs, and asserts that VoVNet's dict
+    carries the same tensors.  BatchNorm statistics and affine terms are random and non-trivial; some eSE biases are +-8, so gates of
+    exactly 0 and exactly 1 occur.  Input on the k/32 grid; weights sparse on a grid of 1/64 (they compress); the stem's and stage 2's
+    maps are kept for every chan_stride-th channel only: the file stays within the size limit for a committed fixture."""
+    vov, vovcp = refstub.load_vovnet()
+    spec = dict(stem=[32, 32, 64], stage_conv_ch=[32, 64, 32, 64], stage_out_ch=[64, 96, 128, 160], layer_per_block=2,
+                block_per_stage=[1, 2, 1, 1], eSE=True, dw=False)
+    spec_name = 'V-tiny-eSE'
+    feats = ('stem', 'stage2', 'stage3', 'stage4', 'stage5')
+    nets = []
+    for mod, cls in ((vovcp, 'VoVNetCP'), (vov, 'VoVNet')):
+        mod._STAGE_SPECS[spec_name] = spec
+        nets.append(getattr(mod, cls)(spec_name, out_features=feats))
+        nets[-1].eval()                       # (the reference's train() returns None, and so does its eval())
+    net, net_dict = nets
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for p_name, p in net.named_parameters():
+            if p.dim() == 1:                                                      # BatchNorm affine terms, eSE biases
+                p.copy_(torch.randint(-16, 17, p.shape, generator=g) / 64.)
+                if p_name.endswith('norm.weight'):
+                    p.add_(1.0)
+                if p_name.endswith('ese.fc.bias'):
+                    p[0::7] = 8.0
+                    p[3::7] = -8.0
+            else:
+                keep = torch.rand(p.shape, generator=g) < (weight_keep if p.shape[-1] == 3 else 0.5)
+                p.copy_(torch.randint(-8, 9, p.shape, generator=g) / 64. * keep)
+        for b_name, b in net.named_buffers():
+            if b_name.endswith('running_mean'):
+                b.copy_(torch.randint(-16, 17, b.shape, generator=g) / 64.)
+            elif b_name.endswith('running_var'):
+                b.copy_(torch.randint(32, 129, b.shape, generator=g) / 64.)
+    net_dict.load_state_dict(net.state_dict(), strict=True)
+    q = torch.round(torch.randn(num_cams, 3, *img_hw, generator=g) * FEAT_SCALE).clamp(-127, 127)
+    x = q / FEAT_SCALE
+    gates = {}
+    handles = [m.hsigmoid.register_forward_hook(lambda mod, inp, out, n=n: gates.__setitem__(n, out.detach().clone()))
+               for n, m in net.named_modules() if type(m).__name__ == 'eSEModule']
+    with torch.no_grad():
+        outs = net(x.clone())
+        outs_dict = net_dict(x.clone())
+    for h in handles:
+        h.remove()
+    assert len(outs) == len(feats) and list(outs_dict) == list(feats)
+    assert all(torch.equal(o, outs_dict[f]) for f, o in zip(feats, outs))
+    allg = torch.cat([v.flatten() for v in gates.values()])
+    assert (allg == 0).any() and (allg == 1).any() and ((allg > 0) & (allg < 1)).any()
+    arrays = {'img': q.to(torch.int8)}
+    for f, o in zip(feats, outs):
+        assert o.abs().max() > 1e-2 and torch.isfinite(o).all(), f
+        arrays[f] = (o[:, ::chan_stride] if f in ('stem', 'stage2') else o).contiguous()
+    arrays.update(pack_state(net))
+    meta = dict(kind='vovnet', spec_name=spec_name, spec=spec, out_features=list(feats), num_cams=num_cams, img_hw=list(img_hw),
+                seed=seed, feat_scale=FEAT_SCALE, w_scale=W_SCALE, chan_stride=chan_stride, keys=list(net.state_dict()),
+                shapes={f: list(o.shape) for f, o in zip(feats, outs)})
+    save(name, meta, **arrays)
+
+
 def case_detr4d_distill(name, *, num_student, num_teacher, batch, seed, num_layers=2, reweight_score=False, loss_cls_weight=1.0,
                         loss_reg_weight=0.25, degenerate=False):
     """Detr4D_Distiller.get_instance_distill_loss (distillation/distillers/detr4d_distiller.py:143-168), called unbound on a shell whose
@@ -977,6 +1039,7 @@ def main():
     case_feat_distill('feat_distill_vanilla', kind='vanilla', seed=1001)
     case_feat_distill('feat_distill_attention', kind='attention', seed=1002)
     case_fpn_cp('fpn_cp', seed=1101)
+    case_vovnet('vovnet_tiny', seed=1201)
 
 
 if __name__ == '__main__':

@@ -730,3 +730,32 @@ def load_cp_fpn():
             warnings.simplefilter('ignore')
             spec.loader.exec_module(mod)
     return sys.modules[full]
+
+
+# --------------------------------------------------------------------------------------
+# VoVNet / VoVNetCP: the reference's own backbone
+# --------------------------------------------------------------------------------------
+def load_vovnet():
+    """Import the reference's models/backbones/vovnet.py and vovnetcp.py unmodified (by path: the package's __init__ is not run) and
+    return the two modules.  BaseModule and the BACKBONES registry are stand-ins."""
+    install_stubs()
+    sys.modules['mmcv.runner'].BaseModule = BaseModule
+    if 'mmdet.models.builder' not in sys.modules:
+        _mod('mmdet.models.builder')
+    if not hasattr(sys.modules['mmdet.models.builder'], 'BACKBONES'):
+        sys.modules['mmdet.models.builder'].BACKBONES = Registry('backbone')
+    mods = []
+    for stem in ('vovnet', 'vovnetcp'):
+        full = f'_gd4d_ref_{stem}'
+        if full not in sys.modules:
+            path = os.path.join(REFERENCE_ROOT, f'projects/mmdet3d_plugin/models/backbones/{stem}.py')
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f'reference not present at {path} (build container only)')
+            spec = importlib.util.spec_from_file_location(full, path)
+            mod = importlib.util.module_from_spec(spec)
+            sys.modules[full] = mod
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore')
+                spec.loader.exec_module(mod)
+        mods.append(sys.modules[full])
+    return tuple(mods)
