@@ -55,6 +55,13 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
   return static_cast<uint16_t>(u >> 16);
 }
 
+// the sum over the 32 lanes of a wave's half, by an xor butterfly: every lane of the half gets the same bits
+__device__ __forceinline__ float half_wave_sum(float s) {
+#pragma unroll
+  for (int m = 1; m < 32; m <<= 1) s += __shfl_xor(s, m);
+  return s;
+}
+
 // inverse_sigmoid of the reference (deform3d_cross_attn.py:16-31), eps = 1e-5
 __device__ __forceinline__ float inv_sigmoid(float x) {
   x = fminf(fmaxf(x, 0.f), 1.f);

@@ -54,39 +54,12 @@
 // gd4d_dcn_train.hip; what both share is gd4d_dcn_common.h.
 #include "gd4d_common.h"
 #include "gd4d_bf16x3.h"
+#include "gd4d_conv_common.h"
 #include "gd4d_dcn_common.h"
 
 #include <type_traits>
 
 namespace gd4d {
-
-// ---- weight image ---------------------------------------------------------------------------------------------------------
-// item i = (((tap * chunks + chunk) * 2 + plane) * (KC / 8) + k-group) * Mpad + out channel, 16 bytes each
-__global__ __launch_bounds__(256) void dcn_image_kernel(const float* __restrict__ w, char* __restrict__ image, const int cin,
-                                                        const int cout, const int mpad, const int kc) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= DCN_TAPS * cin / 4 * mpad) return;                     // 9 (Cin / KC) 2 (KC / 8) Mpad items
-  const int kgs = kc / 8;
-  const int oc = i % mpad;
-  int r = i / mpad;
-  const int kgrp = r % kgs;
-  r /= kgs;
-  const int plane = r & 1, s = r >> 1;
-  const int chunks = cin / kc;
-  const int tap = s / chunks, chunk = s % chunks;
-  uint16_t e[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int ci = chunk * kc + kgrp * 8 + j;
-    const float v = oc < cout ? w[((size_t)oc * cin + ci) * DCN_TAPS + tap] : 0.f;   // (out, in, ky, kx): tap = 3 ky + kx
-    const uint16_t h = f32_to_bf16(v);
-    e[j] = plane ? f32_to_bf16(v - bf16_to_f32(h)) : h;
-  }
-  u32x4 o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = (unsigned)e[2 * j] | ((unsigned)e[2 * j + 1] << 16);
-  *reinterpret_cast<u32x4*>(image + (size_t)i * 16) = o;
-}
 
 // ---- conv_offset: the 27-channel convolution ---------------------------------------------------------------------------------
 struct DcnOffsetParams {
@@ -400,10 +373,8 @@ extern "C" int gd4d_dcn_weight_image(const float* weight, int cin, int cout, voi
   int mpad, kc;
   if (!dcn_cin_ok(cin) || !dcn_geometry(cout, mpad, kc)) return GD4D_EUNSUPPORTED;
   if (!aligned16(image)) return GD4D_EALIGN;
-  const int items = DCN_TAPS * cin / 4 * mpad;
-  hipLaunchKernelGGL(dcn_image_kernel, dim3((items + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), weight,
-                     static_cast<char*>(image), cin, cout, mpad, kc);
-  return check_launch();
+  const ConvImage d{cin, cout, DCN_TAPS, mpad, kc, mpad, 1, 0, 0};
+  return pack_conv_image(d, weight, image, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int gd4d_dcn_offset_conv_fwd(const float* x, int n, int cin, int h, int w, int stride, const void* image, const float* bias,

@@ -44,6 +44,7 @@
 // conv_offset kernels into these.
 #include "gd4d_common.h"
 #include "gd4d_bf16x3.h"
+#include "gd4d_conv_common.h"
 #include "gd4d_dcn_common.h"
 
 namespace gd4d {
@@ -51,33 +52,6 @@ namespace gd4d {
 constexpr int DT_THREADS = 512, DT_WAVES = 8, DT_ROWS = 32;      // data kernel: 8 waves, items of 32 (tap, ci) rows
 constexpr int DW_THREADS = 256, DW_PX = 64, DW_NC = 32;          // weight gradients: 64-pixel tiles, 32 input channels per item
 constexpr int DCN_MAX_PARTITIONS = 4096;
-
-// ---- transposed weight image ------------------------------------------------------------------------------------------------
-// item i = (((tap * (Cin / 32) + chunk) * 2 + plane) * (Cout / 8) + k-group) * 32 + row, 16 bytes each
-__global__ __launch_bounds__(256) void dcn_image_t_kernel(const float* __restrict__ w, char* __restrict__ image, const int cin,
-                                                          const int cout) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= DCN_TAPS * cin * (cout / 4)) return;
-  const int kgs = cout / 8, chunks = cin / DT_ROWS;
-  const int row = i & 31;
-  int q = i >> 5;
-  const int kgrp = q % kgs;
-  q /= kgs;
-  const int plane = q & 1, item = q >> 1;
-  const int tap = item / chunks, chunk = item - tap * chunks;
-  const int ci = chunk * DT_ROWS + row;
-  uint16_t e[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float v = w[((size_t)(kgrp * 8 + j) * cin + ci) * DCN_TAPS + tap];
-    const uint16_t h = f32_to_bf16(v);
-    e[j] = plane ? f32_to_bf16(v - bf16_to_f32(h)) : h;
-  }
-  u32x4 o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = (unsigned)e[2 * j] | ((unsigned)e[2 * j + 1] << 16);
-  *reinterpret_cast<u32x4*>(image + (size_t)i * 16) = o;
-}
 
 // g of one element: dout, masked by the forward's ReLU (y > 0) and scaled by the folded BatchNorm
 __device__ __forceinline__ float dcn_g(const float* __restrict__ dout, const float* __restrict__ y, size_t i, float scale) {
@@ -344,23 +318,6 @@ __global__ __launch_bounds__(DW_THREADS) void dcn_wgrad_kernel(const DcnWgradPar
   }
 }
 
-// dw (total) and db (nb) = the partitions' partials added in order
-__global__ __launch_bounds__(256) void dcn_partial_sum_kernel(const float* __restrict__ ws, const float* __restrict__ ws_b,
-                                                              const int partitions, const int total, const int nb,
-                                                              float* __restrict__ dw, float* __restrict__ db) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < total) {
-    float s = 0.f;
-    for (int q = 0; q < partitions; ++q) s += ws[(size_t)q * total + i];
-    dw[i] = s;
-  }
-  if (i < nb) {
-    float s = 0.f;
-    for (int q = 0; q < partitions; ++q) s += ws_b[(size_t)q * nb + i];
-    db[i] = s;
-  }
-}
-
 // ---- conv_offset: input gradient ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void dcn_offset_dgrad_kernel(const float* __restrict__ doff, const float* __restrict__ woff,
                                                                float* __restrict__ dx, const long long total, const int cin, const int H,
@@ -482,10 +439,8 @@ extern "C" int gd4d_dcn_weight_image_t(const float* weight, int cin, int cout, v
   int mpad, kc;
   if (!dcn_cin_ok(cin) || cout == DCN_OFF_C || !dcn_geometry(cout, mpad, kc)) return GD4D_EUNSUPPORTED;
   if (!aligned16(image)) return GD4D_EALIGN;
-  const int items = DCN_TAPS * cin * (cout / 4);
-  hipLaunchKernelGGL(dcn_image_t_kernel, dim3((items + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), weight,
-                     static_cast<char*>(image), cin, cout);
-  return check_launch();
+  const ConvImage d{cin, cout, DCN_TAPS, DT_ROWS, cout, cin, 1, 1, 0};
+  return pack_conv_image(d, weight, image, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int gd4d_dcn_bwd_data(const float* dout, const float* y, const float* scale, const float* x, const float* offmask, int n, int cin,
@@ -531,8 +486,7 @@ extern "C" int gd4d_dcn_wgrad(const float* dout, const float* y, const float* sc
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(dcn_wgrad_kernel, dim3((unsigned)(DCN_TAPS * p.chunks * partitions)), dim3(DW_THREADS), 0, s, p);
   const int total = cout * cin * DCN_TAPS;
-  hipLaunchKernelGGL(dcn_partial_sum_kernel, dim3((total + 255) / 256), dim3(256), 0, s, p.ws, p.ws_b, partitions, total, cout, dw, dbias);
-  return check_launch();
+  return sum_partitions(p.ws, p.ws_b, partitions, total, cout, dw, dbias, s);
 }
 
 extern "C" int gd4d_dcn_offset_conv_dgrad(const float* doff, const float* weight, int n, int cin, int h, int w, int stride, float* dx,
@@ -568,6 +522,5 @@ extern "C" int gd4d_dcn_offset_conv_wgrad(const float* doff, const float* x, int
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(dcn_offset_wgrad_kernel, dim3((unsigned)(DCN_TAPS * p.chunks * partitions)), dim3(64), 0, s, p);
   const int total = DCN_OFF_C * cin * DCN_TAPS;
-  hipLaunchKernelGGL(dcn_partial_sum_kernel, dim3((total + 255) / 256), dim3(256), 0, s, p.ws, p.ws_b, partitions, total, DCN_OFF_C, dw, db);
-  return check_launch();
+  return sum_partitions(p.ws, p.ws_b, partitions, total, DCN_OFF_C, dw, db, s);
 }

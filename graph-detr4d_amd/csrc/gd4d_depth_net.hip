@@ -48,6 +48,7 @@
 // Left off: padding the stages, two workgroups per CU, fusing the epilogue into the position embedding's gate / fuse kernel.
 #include "gd4d_common.h"
 #include "gd4d_bf16x3.h"
+#include "gd4d_conv_common.h"
 
 namespace gd4d {
 
@@ -66,31 +67,6 @@ constexpr size_t DN_IMAGE_BYTES = (size_t)DN_STEPS * DN_W_STAGE;             // 
 constexpr int DN_MAX_LEVELS = 4;
 
 static_assert(DN_LDS <= 160 * 1024, "LDS budget of a CU");
-
-// ---- weight image ---------------------------------------------------------------------------------------------------------
-// item i = ((step * 2 + plane) * 4 + k-group) * 256 + out channel, 16 bytes each: byte offset 16 i
-// transposed (the input gradient's image): the weight w'[ic, oc, 2 - ky, 2 - kx] = w[oc, ic, ky, kx] is laid out instead, so the same
-// kernel run on dy gives dx
-__global__ __launch_bounds__(256) void depth_net_image_kernel(const float* __restrict__ w, char* __restrict__ image,
-                                                              const int transposed) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= DN_STEPS * 2 * 4 * DN_C) return;
-  const int oc = i & 255, kgrp = (i >> 8) & 3, plane = (i >> 10) & 1, s = i >> 11;
-  const int chunk = s / DN_TAPS, tap = s % DN_TAPS;
-  uint16_t e[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int ci = chunk * DN_KC + kgrp * 8 + j;
-    const float v = transposed ? w[((size_t)ci * DN_C + oc) * 9 + (DN_TAPS - 1 - tap)]
-                               : w[((size_t)oc * DN_C + ci) * 9 + tap];   // (out, in, ky, kx): tap = 3 ky + kx
-    const uint16_t h = f32_to_bf16(v);
-    e[j] = plane ? f32_to_bf16(v - bf16_to_f32(h)) : h;
-  }
-  u32x4 o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = (unsigned)e[2 * j] | ((unsigned)e[2 * j + 1] << 16);
-  *reinterpret_cast<u32x4*>(image + (size_t)i * 16) = o;
-}
 
 // ---- camera gate ------------------------------------------------------------------------------------------------------------
 struct CamGateParams {
@@ -191,12 +167,6 @@ struct DepthConvParams {
 // butterfly, then the four pixel waves).  PLAIN: stores conv (+ bias when given): the frozen-BatchNorm forward and the input gradient.
 // LEVELS / LEVELS_CL (the FPN neck's output convolutions): PLAIN with the level's own image and bias, stored NCHW / channels-last.
 enum { DN_EPI_INFER = 0, DN_EPI_STATS = 1, DN_EPI_PLAIN = 2, DN_EPI_LEVELS = 3, DN_EPI_LEVELS_CL = 4 };
-
-__device__ __forceinline__ float dn_half_wave_sum(float s) {
-#pragma unroll
-  for (int m = 1; m < 32; m <<= 1) s += __shfl_xor(s, m);
-  return s;
-}
 
 template <int EPI>
 __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvParams p) {
@@ -416,7 +386,7 @@ __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvP
           }
         }
         if (EPI == DN_EPI_STATS) {
-          s = dn_half_wave_sum(s);
+          s = half_wave_sum(s);
           if (l32 == 0) red[wn * DN_C + c] = s;
         }
       }
@@ -437,7 +407,7 @@ __global__ __launch_bounds__(DN_THREADS) void depth_conv_kernel(const DepthConvP
             const float d = acc[mi][ni][r] - m;
             if (ok[ni]) s += d * d;
           }
-          s = dn_half_wave_sum(s);
+          s = half_wave_sum(s);
           if (l32 == 0) red[wn * DN_C + c] = s;                 // (tmean is read above, red's sums were consumed before the barrier)
         }
       __syncthreads();
@@ -459,10 +429,9 @@ extern "C" int gd4d_depth_net_image_mode(const float* conv_w, int channels, int 
   if (!conv_w || !image) return GD4D_EINVAL;
   if (channels != DN_C || (transposed != 0 && transposed != 1)) return GD4D_EUNSUPPORTED;
   if (!aligned16(image)) return GD4D_EALIGN;
-  const int items = DN_STEPS * 2 * 4 * DN_C;
-  hipLaunchKernelGGL(depth_net_image_kernel, dim3((items + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), conv_w,
-                     static_cast<char*>(image), transposed);
-  return check_launch();
+  // transposed (the input gradient's image): w'[ic, oc, 2 - ky, 2 - kx] = w[oc, ic, ky, kx], so the same kernel run on dy gives dx
+  const ConvImage d{DN_C, DN_C, DN_TAPS, DN_C, DN_KC, DN_C, 0, transposed, transposed};
+  return pack_conv_image(d, conv_w, image, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int gd4d_depth_net_image(const float* conv_w, int channels, void* image, void* stream) {

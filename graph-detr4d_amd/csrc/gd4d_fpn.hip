@@ -40,6 +40,7 @@
 // Arithmetic: split-bf16 x 3 on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (gd4d_bf16x3.h).  No atomics: two runs give the same bits.
 #include "gd4d_bf16x3.h"
 #include "gd4d_common.h"
+#include "gd4d_conv_common.h"
 #include "gd4d_fpn_index.h"
 
 namespace gd4d {
@@ -54,35 +55,6 @@ constexpr int FPN_W_ARR = 4 * FPN_C * 16;            // bytes of one plane of a 
 constexpr int FPN_W_STEP = 2 * FPN_W_ARR;            // hi + lo
 constexpr int FPN_MAX_CIN = 2048;
 constexpr int FPN_TAPS = 9;
-
-// item i = ((chunk * 2 + plane) * 4 + k-group) * 256 + out channel, 16 bytes each
-__global__ __launch_bounds__(256) void fpn_lateral_image_kernel(const float* __restrict__ w, char* __restrict__ image, const int cin) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= (cin / FPN_KC) * 2 * 4 * FPN_C) return;
-  const int oc = i & 255, kgrp = (i >> 8) & 3, plane = (i >> 10) & 1, chunk = i >> 11;
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = w[(size_t)oc * cin + chunk * FPN_KC + kgrp * 8 + j];
-  u32x4 hi, lo;
-  split8(v, hi, lo);
-  *reinterpret_cast<u32x4*>(image + (size_t)i * 16) = plane ? lo : hi;
-}
-
-// the input gradient's image, W^T: output channels = the lateral's input channels in blocks of 256 (zeros beyond cin), K = its 256
-// output channels.  item i = (((block * 8 + chunk) * 2 + plane) * 4 + k-group) * 256 + channel of the block
-__global__ __launch_bounds__(256) void fpn_lateral_image_t_kernel(const float* __restrict__ w, char* __restrict__ image, const int cin,
-                                                                  const int blocks) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= blocks * (FPN_C / FPN_KC) * 2 * 4 * FPN_C) return;
-  const int ocl = i & 255, kgrp = (i >> 8) & 3, plane = (i >> 10) & 1, chunk = (i >> 11) & 7, block = i >> 14;
-  const int oc = block * FPN_C + ocl;
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = oc < cin ? w[(size_t)(chunk * FPN_KC + kgrp * 8 + j) * cin + oc] : 0.f;
-  u32x4 hi, lo;
-  split8(v, hi, lo);
-  *reinterpret_cast<u32x4*>(image + (size_t)i * 16) = plane ? lo : hi;
-}
 
 struct FpnGemmParams {
   const float* x;          // LATERAL: (N, Cin, H, W); EXTRA: (N, 256, H, W), NCHW or channels-last (x_cs / x_ps)
@@ -263,11 +235,9 @@ extern "C" int gd4d_fpn_lateral_image_mode(const float* weight, int cin, int out
   if (!weight || !image) return GD4D_EINVAL;
   if (out_channels != FPN_C || transposed != 1 || gd4d_fpn_lateral_image_bytes(cin) == 0) return GD4D_EUNSUPPORTED;
   if (!aligned16(image)) return GD4D_EALIGN;
-  const int blocks = (cin + FPN_C - 1) / FPN_C;
-  const int items = blocks * (FPN_C / FPN_KC) * 2 * 4 * FPN_C;
-  hipLaunchKernelGGL(fpn_lateral_image_t_kernel, dim3((items + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), weight,
-                     static_cast<char*>(image), cin, blocks);
-  return check_launch();
+  // W^T: rows = the lateral's input channels in blocks of 256 (zeros beyond cin), K = its 256 output channels
+  const ConvImage d{cin, FPN_C, 1, FPN_C, FPN_KC, (cin + FPN_C - 1) / FPN_C * FPN_C, 0, 1, 0};
+  return pack_conv_image(d, weight, image, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int gd4d_fpn_lateral_image(const float* weight, int cin, int out_channels, void* image, void* stream) {
@@ -275,10 +245,8 @@ extern "C" int gd4d_fpn_lateral_image(const float* weight, int cin, int out_chan
   if (!weight || !image) return GD4D_EINVAL;
   if (out_channels != FPN_C || gd4d_fpn_lateral_image_bytes(cin) == 0) return GD4D_EUNSUPPORTED;
   if (!aligned16(image)) return GD4D_EALIGN;
-  const int items = (cin / FPN_KC) * 2 * 4 * FPN_C;
-  hipLaunchKernelGGL(fpn_lateral_image_kernel, dim3((items + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), weight,
-                     static_cast<char*>(image), cin);
-  return check_launch();
+  const ConvImage d{cin, FPN_C, 1, FPN_C, FPN_KC, FPN_C, 0, 0, 0};
+  return pack_conv_image(d, weight, image, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int gd4d_fpn_lateral_fwd(const float* x, int n, int cin, int h, int w, const void* image, const float* bias, const float* up,

@@ -26,6 +26,7 @@
 // No atomics: every sum runs in a fixed order, two runs give the same bits.
 #include "gd4d_bf16x3.h"
 #include "gd4d_common.h"
+#include "gd4d_conv_common.h"
 #include "gd4d_fpn_index.h"
 
 namespace gd4d {
@@ -135,24 +136,6 @@ __global__ __launch_bounds__(LW_THREADS) void fpn_lateral_wgrad_kernel(const Lat
       const float other = __shfl_xor(bsum[i], 32);
       if (kg == 0) p.ws_b[(size_t)part * FT_C + 64 * wave + 32 * i + l32] = bsum[i] + other;   // pixels 0-7 of a step, then 8-15
     }
-  }
-}
-
-// dW (256, Cin) and db (256) = the partitions' partials added in order
-__global__ __launch_bounds__(256) void fpn_lateral_wgrad_sum_kernel(const float* __restrict__ ws, const float* __restrict__ ws_b,
-                                                                    int partitions, int cin, float* __restrict__ dw,
-                                                                    float* __restrict__ db) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const int total = FT_C * cin;
-  if (i < total) {
-    float s = 0.f;
-    for (int q = 0; q < partitions; ++q) s += ws[(size_t)q * total + i];
-    dw[i] = s;
-  }
-  if (i < FT_C) {
-    float s = 0.f;
-    for (int q = 0; q < partitions; ++q) s += ws_b[(size_t)q * FT_C + i];
-    db[i] = s;
   }
 }
 
@@ -312,8 +295,7 @@ extern "C" int gd4d_fpn_lateral_wgrad(const float* g, const float* x, int n, int
   p.chunks = (cin + LW_IC - 1) / LW_IC;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(fpn_lateral_wgrad_kernel, dim3((unsigned)(p.chunks * partitions)), dim3(LW_THREADS), 0, s, p);
-  hipLaunchKernelGGL(fpn_lateral_wgrad_sum_kernel, dim3((FT_C * cin + 255) / 256), dim3(256), 0, s, p.ws, p.ws_b, partitions, cin, dw, db);
-  return check_launch();
+  return sum_partitions(p.ws, p.ws_b, partitions, FT_C * cin, FT_C, dw, db, s);   // dW (256, Cin) and db (256)
 }
 
 extern "C" int gd4d_fpn_topdown_bwd(const float* g_fine, int n, int channels, int h, int w, float* g_coarse, int coarse_h, int coarse_w,

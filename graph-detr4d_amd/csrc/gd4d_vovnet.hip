@@ -47,11 +47,13 @@
 //     3      128 +  48,  70 656, 2    256 +  72,  96 384, 1      92 +  48, 57 344, 3
 //     2      124 +  32,  62 464, 3    256 +  48,  88 192, 1      84 +  32, 49 152, 4
 //     1      120 +  16,  54 272, 3    256 +  26,  80 000, 1      80 +  16, 40 960, 5
-// vv_image_kernel 17 VGPRs, vv_ese_gate_kernel 62 (4 KB of static LDS), vv_ese_apply_kernel 18; no scratch.
+// vv_ese_gate_kernel 62 VGPRs (4 KB of static LDS), vv_ese_apply_kernel 18; no scratch.  The weight images are packed by
+// pack_conv_image (gd4d_conv_common.h has the format).
 // Left off: a 2 x 2 register tile per wave (halves the A reads from LDS), a double-buffered stride-2 halo, fusing the gate's matvec
 // into the last aggregation tile, NHWC.
 #include "gd4d_common.h"
 #include "gd4d_bf16x3.h"
+#include "gd4d_conv_common.h"
 
 namespace gd4d {
 
@@ -105,31 +107,6 @@ static inline bool vv_mt_ok(int cout, int m_blocks) {
   return m_blocks == 0 || ((m_blocks == 7 || (m_blocks >= 1 && m_blocks <= 5)) && (cout / 32) % m_blocks == 0);
 }
 
-// ---- weight image --------------------------------------------------------------------------------------------------------
-// item i = ((((row block * steps + step) * 2 + plane) * 4 + k-group) * 32 + row), 16 bytes each; step = chunk * taps + tap: one
-// (row block of 32 output channels, step) is 4 KB, and the image does not depend on the M tiling.  w (cout, cin, taps) row-major
-__global__ __launch_bounds__(256) void vv_image_kernel(const float* __restrict__ w, char* __restrict__ image, const int cin, const int taps,
-                                                       const long long items) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= items) return;
-  const int steps = (cin / VV_KC) * taps;
-  const int row = (int)(i & 31), kgrp = (int)((i >> 5) & 3), plane = (int)((i >> 7) & 1);
-  const int s = (int)((i >> 8) % steps), blk = (int)((i >> 8) / steps);
-  const int oc = blk * 32 + row, chunk = s / taps, tap = s % taps;
-  uint16_t e[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int ci = chunk * VV_KC + kgrp * 8 + j;
-    const float v = w[((size_t)oc * cin + ci) * taps + tap];
-    const uint16_t h = f32_to_bf16(v);
-    e[j] = plane ? f32_to_bf16(v - bf16_to_f32(h)) : h;
-  }
-  u32x4 o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = (unsigned)e[2 * j] | ((unsigned)e[2 * j + 1] << 16);
-  *reinterpret_cast<u32x4*>(image + (size_t)i * 16) = o;
-}
-
 // ---- the GEMM ---------------------------------------------------------------------------------------------------------------
 struct VvParams {
   const float* src[VV_MAX_SRC];   // NCHW maps of the same N, H, W; the convolutions have one
@@ -143,12 +120,6 @@ struct VvParams {
   float* out;
   float* partials;                // OSA: (N, tiles_img, cout)
 };
-
-__device__ __forceinline__ float vv_half_wave_sum(float s) {
-#pragma unroll
-  for (int m = 1; m < 32; m <<= 1) s += __shfl_xor(s, m);
-  return s;
-}
 
 template <int MT, int MODE>
 __global__ __launch_bounds__(VV_THREADS) void vv_gemm_kernel(const VvParams p) {
@@ -314,7 +285,7 @@ __global__ __launch_bounds__(VV_THREADS) void vv_gemm_kernel(const VvParams p) {
       const float v = fmaxf(acc[mi][r] * p.scale[crow0 + cl] + p.shift[crow0 + cl], 0.f);
       if (ok) outp[(size_t)cl * plane] = v;
       if (MODE == VV_OSA) {
-        const float s = vv_half_wave_sum(ok ? v : 0.f);
+        const float s = half_wave_sum(ok ? v : 0.f);
         if (l32 == 0) red[wave * ROWS + cl] = s;
       }
     }
@@ -420,13 +391,11 @@ static bool vv_osa_channels(int k, int cout) {
   return k % 32 == 0 && k >= 32 && k <= 2304 && cout % 32 == 0 && cout >= 32 && cout <= 1024;
 }
 
+// w (cout, cin, taps): a (row block of 32 output channels, step = chunk * taps + tap) is 4 KB; the image does not depend on the M tiling
 static int vv_image(const float* weight, int cin, int cout, int taps, void* image, void* stream) {
-  if (!weight || !image) return GD4D_EINVAL;
   if (!aligned16(image)) return GD4D_EALIGN;
-  const long long items = (long long)cout * cin * taps / 4;   // 2 planes x (cout cin taps / 8) groups of 8
-  hipLaunchKernelGGL(vv_image_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), weight,
-                     static_cast<char*>(image), cin, taps, items);
-  return check_launch();
+  const ConvImage d{cin, cout, taps, 32, VV_KC, cout, 0, 0, 0};
+  return pack_conv_image(d, weight, image, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace gd4d

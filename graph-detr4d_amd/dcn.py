@@ -240,21 +240,7 @@ class ModulatedDeformConv2d(nn.Module):
 
     # ---- kept values ----------------------------------------------------------------------------------------------------
     def _keep(self, key, sources, build):
-        """build()'s value of `sources` under ops._Stamp's rule, at a fixed device address: a stale value is rebuilt INTO its buffer."""
-        ent = self._kept.get(key)
-        dev = next(s for s in sources if s is not None).device
-        if ent is not None and ent[0].valid(sources) and ent[1].device == dev:
-            return ent[1]
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f'{type(self).__name__} under hipGraph capture: call the module (or refresh_images) once eagerly first - '
-                               'its weight images are not on the device yet, or a parameter changed since they were made')
-        with torch.no_grad():
-            value = build()
-        if ent is not None and ent[1].device == value.device and ent[1].shape == value.shape:
-            ent[1].copy_(value)
-            value = ent[1]
-        self._kept[key] = (ops._Stamp(tuple(sources)), value)
-        return value
+        return ops.kept_in_place(self._kept, key, sources, build, self)
 
     def _weight_image(self):
         return self._keep('weight', (self.weight,), lambda: ops.dcn_weight_image(self.weight.detach().float()))
@@ -266,18 +252,7 @@ class ModulatedDeformConv2d(nn.Module):
         """(2, Cout): scale = gamma / sqrt(var + eps) and shift = beta + (bias - mean) scale of an eval()-mode BatchNorm2d behind the
         convolution's bias."""
         sources = (bn.weight, bn.bias, bn.running_mean, bn.running_var, self.bias)
-
-        def build():
-            var, mean = bn.running_var.detach().float(), bn.running_mean.detach().float()
-            scale = torch.rsqrt(var + bn.eps)
-            if bn.weight is not None:
-                scale = scale * bn.weight.detach().float()
-            shift = -mean if self.bias is None else self.bias.detach().float() - mean
-            shift = shift * scale
-            if bn.bias is not None:
-                shift = shift + bn.bias.detach().float()
-            return torch.stack((scale, shift)).contiguous()
-        return self._keep(('bn', id(bn), float(bn.eps)), sources, build)
+        return self._keep(('bn', id(bn), float(bn.eps)), sources, lambda: Fn.folded_batchnorm(bn, self.bias))
 
     def refresh_images(self):
         """For the owner of a hipGraph captured over this module: after an in-place weight edit, re-image the changed weights into

@@ -303,19 +303,7 @@ class FPN(nn.Module):
 
     # ---- kernel route -------------------------------------------------------------------------------------------------
     def _image(self, key, weight, build):
-        """The weight's fragment image under ops._Stamp's rule, at a fixed device address: a stale image is rebuilt INTO its buffer."""
-        ent = self._images.get(key)
-        if ent is not None and ent[0].valid((weight,)) and ent[1].device == weight.device:
-            return ent[1]
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f'{type(self).__name__} under hipGraph capture: call the module (or refresh_images) once eagerly first - '
-                               'its weight images are not on the device yet, or a weight changed since they were made')
-        img = build(weight.detach())
-        if ent is not None and ent[1].device == img.device and ent[1].shape == img.shape:
-            ent[1].copy_(img)
-            img = ent[1]
-        self._images[key] = (ops._Stamp((weight,)), img)
-        return img
+        return ops.kept_in_place(self._images, key, (weight,), lambda: build(weight.detach()), self, changed='weight')
 
     def _all_images(self):
         lat = [self._image(('lateral', i), m.conv.weight, ops.fpn_lateral_image) for i, m in enumerate(self.lateral_convs)]

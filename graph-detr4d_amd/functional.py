@@ -174,6 +174,20 @@ def require_gpu(t, name):
                              '(no CPU fallback)')
 
 
+def folded_batchnorm(bn, bias=None):
+    """(2, C): scale = gamma / sqrt(var + eps) and shift = beta + (bias - mean) scale of an eval()-mode BatchNorm2d behind a
+    convolution's bias (None: no bias), in fp32."""
+    var, mean = bn.running_var.detach().float(), bn.running_mean.detach().float()
+    scale = torch.rsqrt(var + bn.eps)
+    if bn.weight is not None:
+        scale = scale * bn.weight.detach().float()
+    shift = -mean if bias is None else bias.detach().float() - mean
+    shift = shift * scale
+    if bn.bias is not None:
+        shift = shift + bn.bias.detach().float()
+    return torch.stack((scale, shift)).contiguous()
+
+
 def inverse_sigmoid(x, eps=1e-5):
     """Reference: deform3d_cross_attn.py:16-31 / detr3d_transformer.py:28-43."""
     x = x.clamp(min=0, max=1)

@@ -2013,6 +2013,29 @@ def _kept(table, key, sources, build):
     return value
 
 
+def kept_in_place(table, key, sources, build, owner, changed='parameter'):
+    """_kept at a fixed address, for values a captured hipGraph reads (the weight images and folded constants of FPN, DCNv2, VoVNet):
+    table[key] is served while its stamp holds and it lives on the device of the first source that is not None.  Otherwise build()
+    runs under torch.no_grad() and, where an earlier value of the same device and shape is kept, is copied INTO that buffer, so a
+    captured graph sees the new weights; under hipGraph capture it raises instead, in `owner`'s name.  The entry outlives its
+    sources: the address is the point."""
+    sources = tuple(sources)
+    ent = table.get(key)
+    dev = next(t for t in sources if t is not None).device
+    if ent is not None and ent[0].valid(sources) and ent[1].device == dev:
+        return ent[1]
+    if dev.type == 'cuda' and torch.cuda.is_current_stream_capturing():       # (never asked of CPU tensors: there may be no GPU)
+        raise RuntimeError(f'{type(owner).__name__} under hipGraph capture: call the module (or refresh_images) once eagerly first - '
+                           f'its weight images are not on the device yet, or a {changed} changed since they were made')
+    with torch.no_grad():
+        value = build()
+    if ent is not None and ent[1].device == value.device and ent[1].shape == value.shape:
+        ent[1].copy_(value)
+        value = ent[1]
+    table[key] = (_Stamp(sources), value)
+    return value
+
+
 def chain_weight_image(weight, exact=False):
     """The bf16 hi / lo (exact: hi / mid / lo) MFMA-fragment image of a (N, K) fp32 weight (gd4d_chain_weight_image[_exact]),
     kept while the weight does not change (invalidate_chain_images) - one small launch after a load_state_dict or an optimizer
@@ -2846,18 +2869,24 @@ def copy_into(dst, src):
     return dst
 
 
+def _weight_image(entry, nbytes, unsupported, weight, *dims, name='weight'):
+    """The common tail of the convolutions' weight-image wrappers: nbytes (the entry's *_bytes; 0: a weight the kernel does not take, which
+    raises `unsupported`) of device memory, filled by lib.<entry>(weight, *dims, image, stream)."""
+    if nbytes == 0:
+        raise _lib.Gd4dError(unsupported)
+    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
+    code = getattr(_lib.load(), entry)(_dev(weight.contiguous(), name, torch.float32), *dims, _dev(img, 'image', torch.uint8), _stream())
+    _lib.check(code, entry)
+    return img
+
+
 def depth_net_image(conv_w):
     """gd4d_depth_net_image: the camera-aware DepthNet's 3x3 weight (256, 256, 3, 3) fp32 -> its bf16 hi / lo fragment image for
     depth_conv_fwd (2.25 MB; remake it when the weight changes)."""
-    lib = _lib.load()
-    c = conv_w.shape[0]
-    nbytes = int(lib.gd4d_depth_net_image_bytes(int(c)))
-    if nbytes == 0 or tuple(conv_w.shape) != (c, c, 3, 3):
-        raise _lib.Gd4dError(f'depth_net_image: weight {tuple(conv_w.shape)}; the kernel takes (256, 256, 3, 3)')
-    img = torch.empty(nbytes, device=conv_w.device, dtype=torch.uint8)
-    code = lib.gd4d_depth_net_image(_dev(conv_w.contiguous(), 'conv_w', torch.float32), int(c), _dev(img, 'image', torch.uint8), _stream())
-    _lib.check(code, 'gd4d_depth_net_image')
-    return img
+    c = int(conv_w.shape[0])
+    nbytes = int(_lib.load().gd4d_depth_net_image_bytes(c)) if tuple(conv_w.shape) == (c, c, 3, 3) else 0
+    return _weight_image('gd4d_depth_net_image', nbytes, f'depth_net_image: weight {tuple(conv_w.shape)}; the kernel takes (256, 256, 3, 3)',
+                         conv_w, c, name='conv_w')
 
 
 def cam_gate_fwd(intrinsics, ida00, fc1_w, fc1_b, fc2_w, fc2_b, se_reduce_w, se_reduce_b, se_expand_w, se_expand_b,
@@ -2929,16 +2958,10 @@ def _depth_ptrs(tensors, name):
 def depth_net_image_t(conv_w):
     """gd4d_depth_net_image_mode(transposed = 1): the image of w'[ic, oc, 2 - ky, 2 - kx] = w[oc, ic, ky, kx], with which depth_conv_raw run
     on dy gives the input gradient (remake it when the weight changes, as depth_net_image)."""
-    lib = _lib.load()
-    c = conv_w.shape[0]
-    nbytes = int(lib.gd4d_depth_net_image_bytes(int(c)))
-    if nbytes == 0 or tuple(conv_w.shape) != (c, c, 3, 3):
-        raise _lib.Gd4dError(f'depth_net_image_t: weight {tuple(conv_w.shape)}; the kernel takes (256, 256, 3, 3)')
-    img = torch.empty(nbytes, device=conv_w.device, dtype=torch.uint8)
-    code = lib.gd4d_depth_net_image_mode(_dev(conv_w.contiguous(), 'conv_w', torch.float32), int(c), 1, _dev(img, 'image', torch.uint8),
-                                         _stream())
-    _lib.check(code, 'gd4d_depth_net_image_mode')
-    return img
+    c = int(conv_w.shape[0])
+    nbytes = int(_lib.load().gd4d_depth_net_image_bytes(c)) if tuple(conv_w.shape) == (c, c, 3, 3) else 0
+    return _weight_image('gd4d_depth_net_image_mode', nbytes,
+                         f'depth_net_image_t: weight {tuple(conv_w.shape)}; the kernel takes (256, 256, 3, 3)', conv_w, c, 1, name='conv_w')
 
 
 def depth_conv_tiles(level_hw, n):
@@ -3071,21 +3094,20 @@ def _fpn_map(t, name):
     raise ValueError(f'{name} must be contiguous NCHW or channels-last')
 
 
+def _fpn_lateral_image(name, weight, transposed):
+    w = weight.reshape(weight.shape[0], -1)
+    cout, cin = (int(v) for v in w.shape)
+    ok = cout == 256 and (weight.dim() != 4 or tuple(weight.shape[2:]) == (1, 1))
+    nbytes = int(_lib.load().gd4d_fpn_lateral_image_mode_bytes(cin, transposed)) if ok else 0
+    entry, mode = ('gd4d_fpn_lateral_image_mode', (1,)) if transposed else ('gd4d_fpn_lateral_image', ())
+    return _weight_image(entry, nbytes, f'{name}: weight {tuple(weight.shape)}; the kernel takes (256, Cin, 1, 1), Cin a multiple of 32 '
+                         'in [32, 2048]', w, cin, cout, *mode)
+
+
 def fpn_lateral_image(weight):
     """gd4d_fpn_lateral_image: a lateral's 1x1 weight (256, Cin[, 1, 1]) fp32 -> its bf16 hi / lo fragment image for fpn_lateral_fwd
     (Cin a multiple of 32 in [32, 2048]; remake it when the weight changes)."""
-    lib = _lib.load()
-    w = weight.reshape(weight.shape[0], -1)
-    cout, cin = w.shape
-    nbytes = int(lib.gd4d_fpn_lateral_image_bytes(int(cin)))
-    if nbytes == 0 or cout != 256 or weight.numel() != cout * cin or (weight.dim() == 4 and tuple(weight.shape[2:]) != (1, 1)):
-        raise _lib.Gd4dError(f'fpn_lateral_image: weight {tuple(weight.shape)}; the kernel takes (256, Cin, 1, 1), Cin a multiple of 32 '
-                             'in [32, 2048]')
-    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
-    code = lib.gd4d_fpn_lateral_image(_dev(w.contiguous(), 'weight', torch.float32), int(cin), int(cout), _dev(img, 'image', torch.uint8),
-                                      _stream())
-    _lib.check(code, 'gd4d_fpn_lateral_image')
-    return img
+    return _fpn_lateral_image('fpn_lateral_image', weight, 0)
 
 
 def fpn_lateral_fwd(x, image, bias, up=None, out=None, channels_last_out=False):
@@ -3164,18 +3186,7 @@ def fpn_extra_conv_fwd(x, image, bias=None, relu_in=False, out=None, channels_la
 def fpn_lateral_image_t(weight):
     """gd4d_fpn_lateral_image_mode(transposed = 1): a lateral's (256, Cin[, 1, 1]) weight -> the image of W^T with which fpn_lateral_dgrad
     gives the input gradient (the Cin output channels in blocks of 256, zeros beyond Cin; remake it when the weight changes)."""
-    lib = _lib.load()
-    w = weight.reshape(weight.shape[0], -1)
-    cout, cin = w.shape
-    nbytes = int(lib.gd4d_fpn_lateral_image_mode_bytes(int(cin), 1))
-    if nbytes == 0 or cout != 256 or (weight.dim() == 4 and tuple(weight.shape[2:]) != (1, 1)):
-        raise _lib.Gd4dError(f'fpn_lateral_image_t: weight {tuple(weight.shape)}; the kernel takes (256, Cin, 1, 1), Cin a multiple of 32 '
-                             'in [32, 2048]')
-    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
-    code = lib.gd4d_fpn_lateral_image_mode(_dev(w.contiguous(), 'weight', torch.float32), int(cin), int(cout), 1,
-                                           _dev(img, 'image', torch.uint8), _stream())
-    _lib.check(code, 'gd4d_fpn_lateral_image_mode')
-    return img
+    return _fpn_lateral_image('fpn_lateral_image_t', weight, 1)
 
 
 def _fpn_grad_map(t, name, channels=256):
@@ -3342,21 +3353,20 @@ def dcn_out_hw(h, w, stride):
     return (int(h) - 1) // int(stride) + 1, (int(w) - 1) // int(stride) + 1
 
 
+def _conv3x3_weight_image(name, entry, weight, takes, limits):
+    """A (Cout, Cin, 3, 3) weight's image by lib.<entry>(weight, cin, cout, image, stream), sized by lib.<entry>_bytes(cin, cout)."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise _lib.Gd4dError(f'{name}: weight {tuple(weight.shape)}; {takes} (Cout, Cin, 3, 3)')
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    nbytes = int(getattr(_lib.load(), entry + '_bytes')(cin, cout))
+    return _weight_image(entry, nbytes, f'{name}: weight {tuple(weight.shape)}; {takes} {limits}', weight, cin, cout)
+
+
 def dcn_weight_image(weight):
     """gd4d_dcn_weight_image: a 3x3 weight (Cout, Cin, 3, 3) fp32 -> its bf16 hi / lo fragment image.  Cin a multiple of 64 in [64, 512];
     Cout a multiple of 64 in [64, 512] (dcn_fwd) or 27 (dcn_offset_conv_fwd).  Remake it when the weight changes."""
-    lib = _lib.load()
-    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
-        raise _lib.Gd4dError(f'dcn_weight_image: weight {tuple(weight.shape)}; the kernels take (Cout, Cin, 3, 3)')
-    cout, cin = int(weight.shape[0]), int(weight.shape[1])
-    nbytes = int(lib.gd4d_dcn_weight_image_bytes(cin, cout))
-    if nbytes == 0:
-        raise _lib.Gd4dError(f'dcn_weight_image: weight {tuple(weight.shape)}; the kernels take Cin a multiple of 64 in [64, 512] and Cout '
-                             'a multiple of 64 in [64, 512] (or 27, conv_offset)')
-    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
-    code = lib.gd4d_dcn_weight_image(_dev(weight.contiguous(), 'weight', torch.float32), cin, cout, _dev(img, 'image', torch.uint8), _stream())
-    _lib.check(code, 'gd4d_dcn_weight_image')
-    return img
+    return _conv3x3_weight_image('dcn_weight_image', 'gd4d_dcn_weight_image', weight, 'the kernels take',
+                                 'Cin a multiple of 64 in [64, 512] and Cout a multiple of 64 in [64, 512] (or 27, conv_offset)')
 
 
 def _dcn_x(x, name):
@@ -3412,17 +3422,8 @@ def dcn_fwd(x, offmask, image, cout, stride=1, scale=None, shift=None, relu=Fals
 def dcn_weight_image_t(weight):
     """gd4d_dcn_weight_image_t: a 3x3 weight (Cout, Cin, 3, 3) fp32 -> the transposed bf16 hi / lo fragment image dcn_bwd_data reads
     (rows (tap, ci), K = Cout).  Cin and Cout multiples of 64 in [64, 512].  Remake it when the weight changes."""
-    lib = _lib.load()
-    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
-        raise _lib.Gd4dError(f'dcn_weight_image_t: weight {tuple(weight.shape)}; the kernels take (Cout, Cin, 3, 3)')
-    cout, cin = int(weight.shape[0]), int(weight.shape[1])
-    nbytes = int(lib.gd4d_dcn_weight_image_t_bytes(cin, cout))
-    if nbytes == 0:
-        raise _lib.Gd4dError(f'dcn_weight_image_t: weight {tuple(weight.shape)}; the kernels take Cin and Cout multiples of 64 in [64, 512]')
-    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
-    code = lib.gd4d_dcn_weight_image_t(_dev(weight.contiguous(), 'weight', torch.float32), cin, cout, _dev(img, 'image', torch.uint8), _stream())
-    _lib.check(code, 'gd4d_dcn_weight_image_t')
-    return img
+    return _conv3x3_weight_image('dcn_weight_image_t', 'gd4d_dcn_weight_image_t', weight, 'the kernels take',
+                                 'Cin and Cout multiples of 64 in [64, 512]')
 
 
 def _dcn_bwd_args(name, dout, y, scale, x, offmask, cout, stride):
@@ -3544,18 +3545,8 @@ OSA_MAX_SOURCES = 6
 def conv3x3_image(weight):
     """gd4d_conv3x3_image: a 3x3 weight (Cout, Cin, 3, 3) fp32 -> its bf16 hi / lo fragment image.  Cin a multiple of 32 in [32, 1024],
     Cout a multiple of 32 in [32, 256].  Remake it when the weight changes."""
-    lib = _lib.load()
-    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
-        raise _lib.Gd4dError(f'conv3x3_image: weight {tuple(weight.shape)}; the kernel takes (Cout, Cin, 3, 3)')
-    cout, cin = int(weight.shape[0]), int(weight.shape[1])
-    nbytes = int(lib.gd4d_conv3x3_image_bytes(cin, cout))
-    if nbytes == 0:
-        raise _lib.Gd4dError(f'conv3x3_image: weight {tuple(weight.shape)}; the kernel takes Cin a multiple of 32 in [32, 1024] and Cout '
-                             'a multiple of 32 in [32, 256]')
-    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
-    code = lib.gd4d_conv3x3_image(_dev(weight.contiguous(), 'weight', torch.float32), cin, cout, _dev(img, 'image', torch.uint8), _stream())
-    _lib.check(code, 'gd4d_conv3x3_image')
-    return img
+    return _conv3x3_weight_image('conv3x3_image', 'gd4d_conv3x3_image', weight, 'the kernel takes',
+                                 'Cin a multiple of 32 in [32, 1024] and Cout a multiple of 32 in [32, 256]')
 
 
 def conv3x3_bn_relu(x, image, cout, scale, shift, stride=1, out=None, m_blocks=0):
@@ -3587,20 +3578,14 @@ def conv3x3_bn_relu(x, image, cout, scale, shift, stride=1, out=None, m_blocks=0
 def osa_concat_image(weight):
     """gd4d_osa_concat_image: the aggregation's weight (Cout, K) or (Cout, K, 1, 1) fp32 -> its fragment image.  K a multiple of 32 in
     [32, 2304], Cout a multiple of 32 in [32, 1024]."""
-    lib = _lib.load()
     if weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1):
         weight = weight.reshape(weight.shape[0], weight.shape[1])
     if weight.dim() != 2:
         raise _lib.Gd4dError(f'osa_concat_image: weight {tuple(weight.shape)}; the kernel takes (Cout, K) or (Cout, K, 1, 1)')
     cout, k = int(weight.shape[0]), int(weight.shape[1])
-    nbytes = int(lib.gd4d_osa_concat_image_bytes(k, cout))
-    if nbytes == 0:
-        raise _lib.Gd4dError(f'osa_concat_image: weight {tuple(weight.shape)}; the kernel takes K a multiple of 32 in [32, 2304] and Cout '
-                             'a multiple of 32 in [32, 1024]')
-    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
-    code = lib.gd4d_osa_concat_image(_dev(weight.contiguous(), 'weight', torch.float32), k, cout, _dev(img, 'image', torch.uint8), _stream())
-    _lib.check(code, 'gd4d_osa_concat_image')
-    return img
+    return _weight_image('gd4d_osa_concat_image', int(_lib.load().gd4d_osa_concat_image_bytes(k, cout)),
+                         f'osa_concat_image: weight {tuple(weight.shape)}; the kernel takes K a multiple of 32 in [32, 2304] and Cout '
+                         'a multiple of 32 in [32, 1024]', weight, k, cout)
 
 
 def osa_concat_conv(sources, image, cout, scale, shift, out=None, partials=None, m_blocks=0):
@@ -3708,7 +3693,7 @@ def _on_tensor_device(fn):
     return wrapped
 
 
-_HOST_ONLY = {'linear_sum_assignment_batch', 'cross_attn_plan_bytes', 'invalidate_chain_images', 'chain_load', 'chain_gemm', 'chain_small_linear', 'chain_layernorm',
+_HOST_ONLY = {'linear_sum_assignment_batch', 'cross_attn_plan_bytes', 'invalidate_chain_images', 'kept_in_place', 'chain_load', 'chain_gemm', 'chain_small_linear', 'chain_layernorm',
               'chain_add', 'chain_refine', 'row_chain_fwd', 'chain_weight_image', 'chain_layernorm_bwd'}
 for _name, _fn in list(globals().items()):
     if inspect.isfunction(_fn) and _fn.__module__ == __name__ and not _name.startswith('_') and _name not in _HOST_ONLY:

@@ -137,21 +137,7 @@ class _KernelRoute:
         return False
 
     def _keep(self, key, sources, build):
-        """build()'s value of `sources` under ops._Stamp's rule, at a fixed device address: a stale value is rebuilt INTO its buffer."""
-        ent = self._kept.get(key)
-        dev = sources[0].device
-        if ent is not None and ent[0].valid(sources) and ent[1].device == dev:
-            return ent[1]
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f'{type(self).__name__} under hipGraph capture: call the module (or refresh_images) once eagerly first - '
-                               'its weight images are not on the device yet, or a parameter changed since they were made')
-        with torch.no_grad():
-            value = build()
-        if ent is not None and ent[1].device == value.device and ent[1].shape == value.shape:
-            ent[1].copy_(value)
-            value = ent[1]
-        self._kept[key] = (ops._Stamp(tuple(sources)), value)
-        return value
+        return ops.kept_in_place(self._kept, key, sources, build, self)
 
     def _image(self, key, conv):
         build = ops.conv3x3_image if conv.kernel_size == (3, 3) else ops.osa_concat_image
@@ -159,15 +145,8 @@ class _KernelRoute:
 
     def _folded(self, key, bn):
         """(2, C): scale = gamma / sqrt(var + eps) and shift = beta - mean scale of an eval()-mode BatchNorm2d."""
-        def build():
-            scale = torch.rsqrt(bn.running_var.detach().float() + bn.eps)
-            if bn.weight is not None:
-                scale = scale * bn.weight.detach().float()
-            shift = -bn.running_mean.detach().float() * scale
-            if bn.bias is not None:
-                shift = shift + bn.bias.detach().float()
-            return torch.stack((scale, shift)).contiguous()
-        return self._keep(('bn', key, float(bn.eps)), (bn.running_var, bn.running_mean, bn.weight, bn.bias), build)
+        sources = (bn.running_var, bn.running_mean, bn.weight, bn.bias)
+        return self._keep(('bn', key, float(bn.eps)), sources, lambda: Fn.folded_batchnorm(bn))
 
     def _conv3x3_hip(self, key, x, conv, bn):
         scale, shift = self._folded(key, bn)

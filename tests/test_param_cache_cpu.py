@@ -102,3 +102,66 @@ def test_a_copied_module_never_validates():
         assert torch.equal(value, m.keep[1])
         assert not stamp.valid([twin.lin.weight, twin.lin.bias]) and not stamp.valid([m.lin.weight, m.lin.bias])
     assert m.keep[0].valid([m.lin.weight, m.lin.bias])
+
+
+class InPlace:
+    """A cache in the form of ops.kept_in_place: the value is a tensor built from the sources, kept at a fixed address."""
+
+    def __init__(self):
+        self.table, self.builds = {}, 0
+
+    def __call__(self, *sources, key='k'):
+        def build():
+            self.builds += 1
+            assert not torch.is_grad_enabled()
+            return sum(t.sum() for t in sources if t is not None) + torch.zeros(sources[0].shape[0])
+        return ops.kept_in_place(self.table, key, sources, build, self)
+
+
+def test_kept_in_place_hit_serves_the_same_object():
+    w = torch.nn.Parameter(torch.randn(4, 8))
+    c = InPlace()
+    v = c(w)
+    assert c(w) is v and c.builds == 1 and not v.requires_grad
+
+
+def test_kept_in_place_rebuilds_into_the_same_buffer_after_an_in_place_edit():
+    w = torch.randn(4, 8)
+    c = InPlace()
+    v = c(w)
+    ptr, old = v.data_ptr(), v.clone()
+    w.add_(1)
+    v2 = c(w)
+    assert v2 is v and v2.data_ptr() == ptr and c.builds == 2
+    assert torch.equal(v2, w.sum() + torch.zeros(4)) and not torch.equal(v2, old)
+    assert c(w) is v and c.builds == 2
+
+
+def test_kept_in_place_a_shape_change_replaces_the_buffer():
+    c = InPlace()
+    v = c(torch.randn(4, 8))
+    w2 = torch.randn(6, 8)
+    v2 = c(w2)
+    assert v2 is not v and v2.shape == (6,) and v.shape == (4,) and c.builds == 2
+    assert c(w2) is v2
+
+
+def test_kept_in_place_invalidate_forces_a_rebuild():
+    w = torch.nn.Parameter(torch.randn(4, 8))
+    c = InPlace()
+    v = c(w)
+    w.data.copy_(torch.randn(4, 8))
+    assert c(w) is v and c.builds == 1
+    ops.invalidate_chain_images()
+    v2 = c(w)
+    assert v2 is v and c.builds == 2 and torch.equal(v2, w.detach().sum() + torch.zeros(4))
+
+
+def test_kept_in_place_accepts_an_absent_source():
+    w, b = torch.randn(4, 8), torch.randn(4)
+    c = InPlace()
+    v = c(w, None)
+    assert c(w, None) is v and c.builds == 1
+    assert c(w, b) is v and c.builds == 2 and torch.equal(v, w.sum() + b.sum() + torch.zeros(4))
+    first_absent = ops.kept_in_place({}, 'k', (None, w), lambda: w.sum(0), c)           # the device comes from the first tensor present
+    assert torch.equal(first_absent, w.sum(0))
