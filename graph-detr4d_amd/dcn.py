@@ -22,8 +22,7 @@ config (norm_eval=True, frozen).  Inputs that are not fp32 contiguous NCHW are c
                       grad, the call is ONE autograd node (_DcnTrainFunction): its forward is the two launches above (the same bits),
                       its backward gd4d_dcn_train.hip's kernels (below).  `torch_ops=True` wins over it.
 The kernels' limits: kernel size 3, padding 1, dilation 1, groups = deform_groups = 1, stride 1 or 2, in / out channels multiples of 64
-in [64, 512].  The default route raises Gd4dError outside them, in train() mode, under autograd (a parameter or an input that
-requires grad), and on CPU tensors; the message names the switches.  Without `hip_train` there is no HIP backward.
+in [64, 512].  The route of a call follows kernel_route.py's rule, the limits checked per call.
 
 The backward (hip_train=True).  The node keeps x (fp32), the 27-channel offset map and - when the ReLU ran - the output (its mask).
     gd4d_dcn_bwd_data            the offset / modulation gradients and dX in one pass: c = W^T g (g = dout x ReLU mask x BatchNorm scale)
@@ -43,10 +42,8 @@ arithmetic gives.  The torch-op route's `grid_sample` normalises the coordinate 
 the LEFT derivative there: on exactly-integer offsets the two routes' offset gradients differ (by as much as the gradient itself); on
 any other offsets they agree to rounding.  The arbiter is the floor-based fp64 form, never grid_sample.
 
-Kept state: the two weight images and the folded (scale, shift) of a BatchNorm, each under ops._Stamp's validity rule and each at a
-FIXED device address (a changed source is rebuilt into the same buffer).  The outputs and the offset map are new tensors every call
-(torch's caching allocator).  So a forward can be captured in a hipGraph; a replay after an in-place weight edit shows the new weights
-once `refresh_images()` (or any eager forward) has run outside the graph.
+Kept state (kernel_route.py): the two weight images and the folded (scale, shift) of a BatchNorm.  The outputs and the offset map
+are new tensors every call (torch's caching allocator).
 """
 import math
 
@@ -57,6 +54,7 @@ import torch.nn.functional as F
 from . import _lib
 from . import functional as Fn
 from . import ops
+from .kernel_route import KernelRoute, f32
 from .registry import CONV_LAYERS
 
 
@@ -107,9 +105,9 @@ class _DcnTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, bn, relu, x, offset, mask, weight, bias, off_weight, off_bias):
-        xf = module._f32(x)
+        xf = f32(x)
         pack = offset is None
-        offmask = module._offmask_hip(xf) if pack else torch.cat((module._f32(offset), module._f32(mask)), dim=1)
+        offmask = module._offmask_hip(xf) if pack else torch.cat((f32(offset), f32(mask)), dim=1)
         out = module._hip(xf, offmask, bn, relu=relu)
         ctx.module, ctx.bn, ctx.relu, ctx.pack = module, bn, relu, pack
         ctx.dtypes = [None if t is None else t.dtype for t in (x, offset, mask, weight, bias, off_weight, off_bias)]
@@ -145,10 +143,11 @@ class _DcnTrainFunction(torch.autograd.Function):
 
 
 @CONV_LAYERS.register_module('ModulatedDeformConv2d')
-class ModulatedDeformConv2d(nn.Module):
+class ModulatedDeformConv2d(KernelRoute, nn.Module):
     """mmcv.ops.ModulatedDeformConv2d: forward(x, offset, mask) with the offset (N, 18, Ho, Wo) and the mask (N, 9, Ho, Wo, already
     through the sigmoid) from the caller."""
     _version = 2
+    _kernels = 'deformable-convolution kernels have no backward unless asked (a frozen layer belongs in eval() mode)'
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, deform_groups=1, bias=True,
                  torch_ops=False, hip_train=False):
@@ -158,17 +157,15 @@ class ModulatedDeformConv2d(nn.Module):
         self.stride, self.padding, self.dilation = _pair(stride), _pair(padding), _pair(dilation)
         self.groups, self.deform_groups = int(groups), int(deform_groups)
         self.transposed, self.output_padding = False, (0, 0)
-        self.torch_ops = bool(torch_ops)
         self.hip_train = bool(hip_train)
         self.weight = nn.Parameter(torch.empty(self.out_channels, self.in_channels // self.groups, *self.kernel_size))
         if bias:
             self.bias = nn.Parameter(torch.empty(self.out_channels))
         else:
             self.register_parameter('bias', None)
-        self._kept = {}             # key -> (ops._Stamp, value at a fixed address)
         self._bns = {}              # id -> the BatchNorm2d modules forward_bn_relu has folded (refresh_images re-folds them)
         self.init_weights()
-        self._kernel_limits = self._outside_kernel_limits()
+        self._init_route(torch_ops, self._outside_kernel_limits())
 
     def init_weights(self):
         n = self.in_channels
@@ -201,30 +198,12 @@ class ModulatedDeformConv2d(nn.Module):
         return why
 
     def _route_name(self):
-        limits = f': {"; ".join(self._kernel_limits)}' if self._kernel_limits else ''
-        return f'{type(self).__name__}({self.in_channels}, {self.out_channels}){limits}'
+        return f'{type(self).__name__}({self.in_channels}, {self.out_channels})'
 
-    def _uses_torch_ops(self, *inputs):
-        if Fn.torch_ops_route(self._route_name(), True, module=self):
-            return True
-        Fn.torch_ops_route(self._route_name(), not self._kernel_limits, module=self)     # raises when outside the limits
-        name = type(self).__name__
-        if self.training and not self.hip_train:
-            raise _lib.Gd4dError(f'{name} in train() mode: graph-detr4d_amd\'s deformable-convolution kernels have no backward.  '
-                                 '`torch_ops=True` (or GD4D_TORCH_OPS=1) runs the module through grid_sample and einsum, trainable by '
-                                 'autograd; a frozen layer belongs in eval() mode.  `hip_train=True` trains the layer on the library\'s '
-                                 'own forward and backward kernels.')
-        if Fn.wants_grad(self, *inputs) and not self.hip_train:
-            raise _lib.Gd4dError(f'{name}: autograd is on, and graph-detr4d_amd\'s deformable-convolution kernels have no backward.  Run '
-                                 'inference under torch.no_grad() (or freeze the parameters and the input), or choose the torch-op route '
-                                 '(`torch_ops=True` / GD4D_TORCH_OPS=1).  `hip_train=True` makes the kernel route differentiable.')
-        for x in inputs:
-            Fn.require_gpu(x, 'inputs')
-        return False
-
-    def _trains(self, *inputs):
-        """The call must be an autograd node: hip_train, and train() mode or something that requires grad."""
-        return self.hip_train and torch.is_grad_enabled() and (self.training or Fn.wants_grad(self, *inputs))
+    def _route(self, *inputs):
+        route = KernelRoute._route(self, *inputs)
+        # under torch.no_grad() the training node would record nothing, and its forward IS the inference launches: take those
+        return 'infer' if route == 'train' and not torch.is_grad_enabled() else route
 
     def _train_node(self, x, offset, mask, bn, relu):
         if bn is not None and any(p is not None and p.requires_grad for p in (bn.weight, bn.bias)):
@@ -239,9 +218,6 @@ class ModulatedDeformConv2d(nn.Module):
         return _DcnTrainFunction.apply(self, bn, relu, x, offset, mask, self.weight, self.bias, off_weight, off_bias)
 
     # ---- kept values ----------------------------------------------------------------------------------------------------
-    def _keep(self, key, sources, build):
-        return ops.kept_in_place(self._kept, key, sources, build, self)
-
     def _weight_image(self):
         return self._keep('weight', (self.weight,), lambda: ops.dcn_weight_image(self.weight.detach().float()))
 
@@ -254,21 +230,12 @@ class ModulatedDeformConv2d(nn.Module):
         sources = (bn.weight, bn.bias, bn.running_mean, bn.running_var, self.bias)
         return self._keep(('bn', id(bn), float(bn.eps)), sources, lambda: Fn.folded_batchnorm(bn, self.bias))
 
-    def refresh_images(self):
-        """For the owner of a hipGraph captured over this module: after an in-place weight edit, re-image the changed weights into
-        the buffers the graph reads (outside the graph, before the replay).  Writes through `.data` need
-        ops.invalidate_chain_images() first, as everywhere."""
-        if not self.weight.is_cuda:
-            raise _lib.Gd4dError('refresh_images: the module is not on the GPU (no CPU fallback in graph-detr4d_amd)')
+    def _kept_values(self):
         self._weight_image()
         for bn in self._bns.values():
             self._folded(bn)
 
     # ---- forward --------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _f32(x):
-        return x if x.dtype == torch.float32 and x.is_contiguous() else x.float().contiguous()
-
     def _check_bn(self, bn):
         if not isinstance(bn, nn.BatchNorm2d) or bn.num_features != self.out_channels:
             raise ValueError(f'forward_bn_relu: a BatchNorm2d of {self.out_channels} features expected')
@@ -289,22 +256,24 @@ class ModulatedDeformConv2d(nn.Module):
                                              self.groups, self.deform_groups)
 
     def forward(self, x, offset, mask):
-        if self._uses_torch_ops(x, offset, mask):
+        route = self._route(x, offset, mask)
+        if route == 'torch':
             return self._torch(x, offset, mask)
-        if self._trains(x, offset, mask):
+        if route == 'train':
             return self._train_node(x, offset, mask, None, False)
         with torch.no_grad():
-            return self._hip(self._f32(x), torch.cat((self._f32(offset), self._f32(mask)), dim=1))
+            return self._hip(f32(x), torch.cat((f32(offset), f32(mask)), dim=1))
 
     def forward_bn_relu(self, x, offset, mask, bn):
         """relu(bn(forward(x, offset, mask))) for an eval()-mode BatchNorm2d, folded into the kernel's epilogue."""
         self._check_bn(bn)
-        if self._uses_torch_ops(x, offset, mask):
+        route = self._route(x, offset, mask)
+        if route == 'torch':
             return F.relu(bn(self._torch(x, offset, mask)))
-        if self._trains(x, offset, mask):
+        if route == 'train':
             return self._train_node(x, offset, mask, bn, True)
         with torch.no_grad():
-            return self._hip(self._f32(x), torch.cat((self._f32(offset), self._f32(mask)), dim=1), bn, relu=True)
+            return self._hip(f32(x), torch.cat((f32(offset), f32(mask)), dim=1), bn, relu=True)
 
 
 @CONV_LAYERS.register_module('DCNv2')
@@ -332,8 +301,8 @@ class ModulatedDeformConv2dPack(ModulatedDeformConv2d):
     def _offset_image(self):
         return self._keep('conv_offset', (self.conv_offset.weight,), lambda: ops.dcn_weight_image(self.conv_offset.weight.detach().float()))
 
-    def refresh_images(self):
-        super().refresh_images()
+    def _kept_values(self):
+        super()._kept_values()
         self._offset_image()
 
     def offsets_torch(self, x):
@@ -345,23 +314,25 @@ class ModulatedDeformConv2dPack(ModulatedDeformConv2d):
         return ops.dcn_offset_conv_fwd(x, self._offset_image(), self.conv_offset.bias.detach(), stride=self.stride[0])
 
     def forward(self, x):
-        if self._uses_torch_ops(x):
+        route = self._route(x)
+        if route == 'torch':
             return self._torch(x, *self.offsets_torch(x))
-        if self._trains(x):
+        if route == 'train':
             return self._train_node(x, None, None, None, False)
         with torch.no_grad():
-            x = self._f32(x)
+            x = f32(x)
             return self._hip(x, self._offmask_hip(x))
 
     def forward_bn_relu(self, x, bn):
         """relu(bn(forward(x))) for an eval()-mode BatchNorm2d: the bottleneck's relu(bn2(conv2(x))), folded into the kernel's epilogue."""
         self._check_bn(bn)
-        if self._uses_torch_ops(x):
+        route = self._route(x)
+        if route == 'torch':
             return F.relu(bn(self._torch(x, *self.offsets_torch(x))))
-        if self._trains(x):
+        if route == 'train':
             return self._train_node(x, None, None, bn, True)
         with torch.no_grad():
-            x = self._f32(x)
+            x = f32(x)
             return self._hip(x, self._offmask_hip(x), bn, relu=True)
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):

@@ -12,8 +12,9 @@ the reference (`forward` returns x); it is not computed here, its parameters are
 What runs where (inference): the gate is one kernel (ops.cam_gate_fwd) reading the intrinsics / ida scales from a persistent device
 buffer (a captured graph serves new cameras after refresh_matrices), the 3x3 convolution with bias, BatchNorm (running statistics),
 ReLU and the gate as its epilogue is ONE launch over all levels (ops.depth_conv_fwd, split-bf16 x 3 on the bf16 matrix cores).
-Training (BatchNorm on batch statistics) and shapes the kernels do not take run on the torch-op route, when chosen
-(`torch_ops=True` or GD4D_TORCH_OPS=1): the module's own nn.Conv2d / BatchNorm2d / MLP / SE, the reference arithmetic.
+The route of a call follows kernel_route.py's rule (limits per call: 256 channels, float32 maps); the torch-op route is the module's
+own nn.Conv2d / BatchNorm2d / MLP / SE, the reference arithmetic.  CPU maps are refused on every route.  The two weight images
+(the forward's, and the input gradient's) are kept values of that file: fixed addresses, `refresh_images()`.
 
 Training on the kernels is opt-in (`hip_train=True`; `torch_ops=True` wins over it): one autograd node per call over all levels
 (_DepthNetTrainFunction).  Forward: the same implicit GEMM with a plain-store epilogue keeps y = conv + bias and emits per-tile
@@ -31,9 +32,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
 from . import functional as Fn
 from . import ops
+from .kernel_route import KernelRoute, f32
 
 MAX_LEVELS_PER_LAUNCH = 4
 
@@ -102,7 +103,7 @@ class _DepthNetTrainFunction(torch.autograd.Function):
         gate = gate_value
         bn = module.reduce_conv[1]
         image = module._image()
-        feats = [f.contiguous() for f in feats]
+        feats = [f32(f) for f in feats]
         gate, bias, gamma, beta = (t.detach().contiguous() for t in (gate, bias, gamma, beta))
         n = feats[0].shape[0]
         ys, stats, outs = [], [], []
@@ -153,7 +154,10 @@ class _DepthNetTrainFunction(torch.autograd.Function):
                 dbeta if need[7] else None, *dxs)
 
 
-class DepthNet(nn.Module):
+class DepthNet(KernelRoute, nn.Module):
+    _kernels = ('kernels run this stage\'s BatchNorm on its running statistics and give the 3x3 convolution a backward only on '
+                'request (train() mode normalises with batch statistics)')
+
     def __init__(self, in_channels, mid_channels, context_channels, torch_ops=False, hip_train=False):
         """torch_ops (not a keyword of the reference): run the module's own torch layers (the reference arithmetic, trainable) instead
         of the library's kernels - the only route for shapes the kernels do not take.  hip_train (neither): make the kernel route
@@ -168,42 +172,26 @@ class DepthNet(nn.Module):
         self.context_conv = nn.Conv2d(mid_channels, context_channels, kernel_size=1, stride=1, padding=0)
         self.mlp = Mlp(1, mid_channels, mid_channels)
         self.se = SELayer(mid_channels)
-        self.torch_ops = bool(torch_ops)
         self.hip_train = bool(hip_train)
-        self._image_t_cache = None  # (ops._Stamp, transposed weight image of reduce_conv[0]: the input gradient's)
-        self._image_cache = None    # (ops._Stamp, weight image of reduce_conv[0])
+        self._init_route(torch_ops)
         self._mats = {}             # (device, request slot, N) -> [host intrinsics, host ida00 (N), device buffer]
 
     # ---- routes ---------------------------------------------------------------------------------------------------------
-    def _route_name(self, x):
-        return (f'camera-aware DepthNet with in / mid channels {self.reduce_conv[0].in_channels} / {self.reduce_conv[0].out_channels}, '
-                f'{x.shape[-3]}-channel {x.dtype} maps (kernels: 256 channels, float32, eval mode)')
+    def _route_name(self):
+        return f'camera-aware DepthNet({self.reduce_conv[0].in_channels}, {self.reduce_conv[0].out_channels})'
 
-    def _uses_torch_ops(self, feats):
-        """True for the torch-op route; raises where the kernels cannot serve and that route was not chosen."""
-        for f in feats:
-            Fn.require_gpu(f, 'mlvl_feats')
-        if Fn.torch_ops_route(self._route_name(feats[0]), True, module=self):
-            return True
-        if self.training and not self.hip_train:
-            raise _lib.Gd4dError('DepthNet in train() mode: BatchNorm then normalises with batch statistics and the 3x3 convolution '
-                                 'needs a backward, which graph-detr4d_amd\'s kernels do not provide.  `torch_ops=True` (or '
-                                 'GD4D_TORCH_OPS=1) runs the module\'s own torch layers, the reference arithmetic, trainable by autograd.  '
-                                 '`hip_train=True` trains the stage on the library\'s own forward and backward kernels.')
-        conv = self.reduce_conv[0]
-        ok = conv.in_channels == 256 and conv.out_channels == 256 and all(f.shape[-3] == 256 and f.dtype == torch.float32 for f in feats)
-        Fn.torch_ops_route(self._route_name(feats[0]), ok, module=self)       # raises when not ok
-        if self.hip_train:
-            bn = self.reduce_conv[1]
-            if self.training and (bn.momentum is None or not bn.track_running_stats):
-                raise _lib.Gd4dError('DepthNet(hip_train=True): BatchNorm2d with momentum=None or track_running_stats=False is outside '
-                                     'the kernels\' limits; `torch_ops=True` (or GD4D_TORCH_OPS=1) runs the module\'s own torch layers.')
-            return False
-        if Fn.wants_grad(self, *feats):
-            raise _lib.Gd4dError('DepthNet: autograd is on, and graph-detr4d_amd\'s kernels have no backward for this stage.  Run '
-                                 'inference under torch.no_grad(), or choose the torch-op route (`torch_ops=True` / GD4D_TORCH_OPS=1).  '
-                                 '`hip_train=True` makes the kernel route differentiable.')
-        return False
+    def _limits(self, *feats):
+        """Per call: the maps' channels and dtype are limits too."""
+        conv, bn = self.reduce_conv[0], self.reduce_conv[1]
+        why = []
+        if conv.in_channels != 256 or conv.out_channels != 256:
+            why.append(f'in / mid channels {conv.in_channels} / {conv.out_channels} (kernels: 256)')
+        bad = next((f for f in feats if f.shape[-3] != 256 or f.dtype != torch.float32), None)
+        if bad is not None:
+            why.append(f'{bad.shape[-3]}-channel {bad.dtype} maps (kernels: 256 channels, float32)')
+        if self.hip_train and self.training and (bn.momentum is None or not bn.track_running_stats):
+            why.append('hip_train with a BatchNorm2d of momentum=None or track_running_stats=False (kernels: a running average)')
+        return why
 
     @staticmethod
     def _squeeze_batch(x):
@@ -231,18 +219,17 @@ class DepthNet(nn.Module):
 
     # ---- kernel route -------------------------------------------------------------------------------------------------
     def _image(self):
-        """The 3x3 weight's fragment image, remade when the weight changes (ops.invalidate_chain_images states when)."""
+        """The 3x3 weight's fragment image."""
         w = self.reduce_conv[0].weight
-        if self._image_cache is None or not self._image_cache[0].valid((w,)):
-            self._image_cache = (ops._Stamp((w,)), ops.depth_net_image(w.detach()))
-        return self._image_cache[1]
+        return self._keep('image', (w,), lambda: ops.depth_net_image(w.detach()))
 
     def _image_t(self):
-        """The transposed, tap-flipped weight's image (the input gradient's GEMM), under the same validity rule as _image."""
+        """The transposed, tap-flipped weight's image (the input gradient's GEMM)."""
         w = self.reduce_conv[0].weight
-        if self._image_t_cache is None or not self._image_t_cache[0].valid((w,)):
-            self._image_t_cache = (ops._Stamp((w,)), ops.depth_net_image_t(w.detach()))
-        return self._image_t_cache[1]
+        return self._keep('image_t', (w,), lambda: ops.depth_net_image_t(w.detach()))
+
+    def _kept_values(self):
+        self._image()
 
     def _matrices_device(self, intrin, ida00, dev, capturing=False):
         """The intrinsics (N, 4, 4) and ida scales (N) on the device: ONE persistent buffer per (device, request slot, N),
@@ -281,11 +268,10 @@ class DepthNet(nn.Module):
                                 scale_depth_factor)
 
     def _forward_hip(self, feats, intrin, ida00, scale_depth_factor):
-        dev = feats[0].device
-        gate = self._gate(intrin, ida00, scale_depth_factor, dev)
+        image = self._image()                   # first: a stale image under capture raises before anything is recorded
+        gate = self._gate(intrin, ida00, scale_depth_factor, feats[0].device)
         conv, bn = self.reduce_conv[0], self.reduce_conv[1]
-        image = self._image()
-        feats = [f.contiguous() for f in feats]
+        feats = [f32(f) for f in feats]
         outs = []
         for i in range(0, len(feats), MAX_LEVELS_PER_LAUNCH):
             outs += ops.depth_conv_fwd(feats[i:i + MAX_LEVELS_PER_LAUNCH], image, conv.bias.detach(), bn.running_mean, bn.running_var,
@@ -321,9 +307,13 @@ class DepthNet(nn.Module):
     def _run(self, feats, intrin, ida00, scale_depth_factor):
         if len({f.shape[0] for f in feats}) != 1:
             raise ValueError('DepthNet: every level must hold the same cameras')
-        if self._uses_torch_ops(feats):
+        for f in feats:
+            Fn.require_gpu(f, 'mlvl_feats')         # on every route, as this stage always has: its torch-op route is no CPU fallback
+        route = self._route(*feats)
+        if route == 'torch':
             return self._forward_torch(feats, intrin, ida00, scale_depth_factor)
-        if self.hip_train and (self.training or Fn.wants_grad(self, *feats)):
+        if route == 'train':
+            # also in train() mode under torch.no_grad(): BatchNorm must take (and move) batch statistics, which only this forward does
             return self._forward_hip_train(feats, intrin, ida00, scale_depth_factor)
         with torch.no_grad():
             return self._forward_hip(feats, intrin, ida00, scale_depth_factor)

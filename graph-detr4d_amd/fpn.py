@@ -24,8 +24,7 @@ Two keywords are not the reference's:
     hip_train=False          True: the kernel route trains.  In train() mode, or with autograd on and a parameter or an input that
                              requires grad, the call runs as ONE autograd node (_FpnTrainFunction): its forward is the launches
                              above (the same bits), its backward the library's kernels (below).  `torch_ops=True` wins over it.
-Without `hip_train` the kernel route has no backward: train() mode, or autograd on with a parameter or an input that requires grad,
-raises Gd4dError unless the torch-op route was chosen.
+The route of a call follows kernel_route.py's rule; a configuration outside the kernels' limits is refused at construction.
 
 The backward (hip_train=True), with dout_k the gradient of output k and gl_i the gradient of lateral i:
     extras     last to first: g(outs[k-1]) = dout_{k-1} + [outs[k-1] > 0]? dgrad_stride2(g(outs[k])) (gd4d_fpn_extra_conv_dgrad, the mask
@@ -40,13 +39,9 @@ that do not require grad (a frozen backbone, a teacher, the levels below start_l
 On this route the laterals are new tensors every call (the node keeps them until its backward; the kept per-slot buffers would be
 overwritten by the next call).  All sums run in a fixed order: two runs give the same bits.
 
-Kept state: the weights' fragment images, each under ops._Stamp's validity rule and each at a FIXED device address (a changed weight
-is re-imaged into the same buffer), and the intermediate laterals, per (device, request slot, shapes).  The outputs are new tensors
-every call.  So a forward can be captured in a hipGraph; a replay after an in-place weight edit shows the new weights once
-`refresh_images()` (or any eager forward) has run outside the graph.
+Kept state: the weights' fragment images (kernel_route.py), and the intermediate laterals, per (device, request slot, shapes).  The
+outputs are new tensors every call.
 """
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -54,6 +49,7 @@ import torch.nn.functional as F
 from . import _lib
 from . import functional as Fn
 from . import ops
+from .kernel_route import KernelRoute, f32, refuse_outside_limits
 from .registry import NECKS
 
 OUT_CHANNELS = 256
@@ -148,9 +144,10 @@ class _ConvModule(nn.Module):
 
 
 @NECKS.register_module()
-class FPN(nn.Module):
+class FPN(KernelRoute, nn.Module):
     """mmdet.models.necks.FPN (the shipped config: in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1,
     add_extra_convs='on_output', num_outs=4, relu_before_extra_convs=True)."""
+    _kernels = 'kernels give the neck\'s convolutions a backward only on request'
 
     def __init__(self, in_channels, out_channels, num_outs, start_level=0, end_level=-1, add_extra_convs=False,
                  relu_before_extra_convs=False, no_norm_on_lateral=False, conv_cfg=None, norm_cfg=None, act_cfg=None,
@@ -165,7 +162,6 @@ class FPN(nn.Module):
         self.relu_before_extra_convs = relu_before_extra_convs
         self.no_norm_on_lateral = no_norm_on_lateral
         self.upsample_cfg = dict(upsample_cfg)
-        self.torch_ops = bool(torch_ops)
         self.channels_last_out = bool(channels_last_out)
         self.hip_train = bool(hip_train)
         if end_level == -1:
@@ -188,11 +184,8 @@ class FPN(nn.Module):
         if built:
             raise _lib.Gd4dError(f'{type(self).__name__}: {", ".join(built)} given; this module builds plain nn.Conv2d layers with a bias '
                                  '(what every shipped config uses), on the kernels and on the `torch_ops=True` route alike')
-        self._kernel_limits = self._outside_kernel_limits()
-        if self._kernel_limits and not (self.torch_ops or os.environ.get('GD4D_TORCH_OPS') == '1'):
-            raise _lib.Gd4dError(f'{type(self).__name__}: {"; ".join(self._kernel_limits)} - outside the limits of graph-detr4d_amd\'s '
-                                 'kernels.  `torch_ops=True` (or GD4D_TORCH_OPS=1) runs the module\'s own torch layers instead (an '
-                                 'explicit choice, not a fallback).')
+        self._init_route(torch_ops, self._outside_kernel_limits())
+        refuse_outside_limits(self, type(self).__name__, self._kernel_limits)      # here, not at the first forward
 
         self.lateral_convs = nn.ModuleList()
         self.fpn_convs = nn.ModuleList()
@@ -207,7 +200,6 @@ class FPN(nn.Module):
                 cin = self.in_channels[self.backbone_end_level - 1] if i == 0 and self.add_extra_convs == 'on_input' else out_channels
                 self.fpn_convs.append(_ConvModule(cin, out_channels, 3, stride=2, padding=1))
         self._init_weights(init_cfg)
-        self._images = {}           # key -> (ops._Stamp, weight image at a fixed address)
         self._laterals = {}         # (device, request slot, shapes) -> the intermediate laterals
 
     # ---- construction ---------------------------------------------------------------------------------------------------
@@ -248,31 +240,6 @@ class FPN(nn.Module):
                     nn.init.xavier_normal_(m.weight, gain=init_cfg.get('gain', 1))
                 nn.init.constant_(m.bias, init_cfg.get('bias', 0))
 
-    # ---- routes ---------------------------------------------------------------------------------------------------------
-    def _route_name(self):
-        return (f'{type(self).__name__} neck, in_channels {self.in_channels}, out_channels {self.out_channels} (kernels: 256 output '
-                'channels, float32, inference)')
-
-    def _uses_torch_ops(self, inputs):
-        if Fn.torch_ops_route(self._route_name(), True, module=self):
-            return True
-        Fn.torch_ops_route(self._route_name(), not self._kernel_limits, module=self)     # raises when outside the limits
-        for x in inputs:
-            Fn.require_gpu(x, 'inputs')
-        name = type(self).__name__
-        if self.hip_train:
-            return False
-        if self.training:
-            raise _lib.Gd4dError(f'{name} in train() mode: the neck\'s convolutions need a backward, which graph-detr4d_amd\'s kernels '
-                                 'provide only on request.  `torch_ops=True` (or GD4D_TORCH_OPS=1) runs the module\'s own torch layers, the '
-                                 'reference arithmetic, trainable by autograd; `hip_train=True` trains the stage on the library\'s own '
-                                 'forward and backward kernels.')
-        if Fn.wants_grad(self, *inputs):
-            raise _lib.Gd4dError(f'{name}: autograd is on, and graph-detr4d_amd\'s kernels have no backward for this stage unless asked.  '
-                                 'Run inference under torch.no_grad(), choose the torch-op route (`torch_ops=True` / GD4D_TORCH_OPS=1), or '
-                                 'make the kernel route differentiable with `hip_train=True`.')
-        return False
-
     # ---- torch-op route: the reference's op sequence -------------------------------------------------------------------
     def _forward_torch(self, inputs):
         laterals = [conv(inputs[i + self.start_level]) for i, conv in enumerate(self.lateral_convs)]               # :162-165
@@ -303,7 +270,7 @@ class FPN(nn.Module):
 
     # ---- kernel route -------------------------------------------------------------------------------------------------
     def _image(self, key, weight, build):
-        return ops.kept_in_place(self._images, key, (weight,), lambda: build(weight.detach()), self, changed='weight')
+        return self._keep(key, (weight,), lambda: build(weight.detach()))
 
     def _all_images(self):
         lat = [self._image(('lateral', i), m.conv.weight, ops.fpn_lateral_image) for i, m in enumerate(self.lateral_convs)]
@@ -316,14 +283,8 @@ class FPN(nn.Module):
         conv = [self._image(('conv_t', i), m.conv.weight, ops.depth_net_image_t) for i, m in enumerate(self.fpn_convs)]
         return lat, conv
 
-    def refresh_images(self):
-        """For the owner of a hipGraph captured over this module: after an in-place weight edit, re-image the changed weights into
-        the buffers the graph reads (outside the graph, before the replay).  Writes through `.data` need
-        ops.invalidate_chain_images() first, as everywhere."""
-        if not any(p.is_cuda for p in self.parameters()):
-            raise _lib.Gd4dError('refresh_images: the module is not on the GPU (no CPU fallback in graph-detr4d_amd)')
-        with torch.no_grad():
-            self._all_images()
+    def _kept_values(self):
+        self._all_images()
 
     def _lateral_buffers(self, shapes, layouts, dev):
         key = (str(dev), Fn.slot_key(dev), tuple(shapes), tuple(layouts))
@@ -339,7 +300,7 @@ class FPN(nn.Module):
         call returns (outs, laterals, the fp32 contiguous inputs)."""
         used = len(self.lateral_convs)
         xs = list(inputs) if used_inputs else [inputs[i + self.start_level] for i in range(used)]
-        xs = [x if x.dtype == torch.float32 and x.is_contiguous() else x.float().contiguous() for x in xs]
+        xs = [f32(x) for x in xs]
         if any(x.dim() != 4 or x.shape[0] != xs[0].shape[0] for x in xs):
             raise ValueError(f'{type(self).__name__}: (N, C, H, W) maps of the same N expected')
         for x, m in zip(xs, self.lateral_convs):
@@ -377,9 +338,10 @@ class FPN(nn.Module):
         """inputs: the backbone's len(in_channels) maps (N, C_i, H_i, W_i) -> the tuple of num_outs maps (N, 256, H_l, W_l)."""
         assert len(inputs) == len(self.in_channels)
         inputs = list(inputs)
-        if self._uses_torch_ops(inputs):
+        route = self._route(*inputs)
+        if route == 'torch':
             return self._forward_torch(inputs)
-        if self.hip_train and (self.training or Fn.wants_grad(self, *inputs)):
+        if route == 'train':
             used = len(self.lateral_convs)
             params = [t for m in list(self.lateral_convs) + list(self.fpn_convs) for t in (m.conv.weight, m.conv.bias)]
             return _FpnTrainFunction.apply(self, *params, *inputs[self.start_level:self.start_level + used])

@@ -25,13 +25,11 @@ and the MaxPool2d in front of stages 3-5.  Inputs that are not fp32 contiguous N
 The kernels' limits: plain (not depthwise) 3x3 layers, every channel count a multiple of 32, 3x3 inputs up to 1024 and outputs up to 256
 channels, at most five layers per module, concatenations up to 2304 and module outputs up to 1024 channels: V-19-eSE, V-39, V-57 and
 V-99.  The two depthwise specs and V-19-slim-eSE (80- and 112-channel layers) are refused AT CONSTRUCTION unless torch_ops=True.  The
-kernel route raises Gd4dError, naming `torch_ops=True`, in train() mode with a BatchNorm that is not frozen (norm_eval=False), when
-autograd wants a gradient (a parameter or the input requires grad and grad mode is on), and on CPU tensors.  There is no HIP backward yet.
+route of a call follows kernel_route.py's rule; "train mode" is here a BatchNorm that is not frozen (norm_eval=False).  There is no
+HIP backward yet, so no `hip_train` switch.
 
-Kept state: per convolution its weight image and the folded (scale, shift) of its BatchNorm, each under ops._Stamp's validity rule and
-each at a FIXED device address (a changed parameter is rebuilt into the same buffer by the next eager call, or by `refresh_images()`).
-The maps, partials and gates are new tensors every call (torch's caching allocator).  So a forward can be captured in a hipGraph after
-one eager call; capturing with a missing or stale image raises instead of allocating.
+Kept state (kernel_route.py): per convolution its weight image and the folded (scale, shift) of its BatchNorm.  The maps, partials
+and gates are new tensors every call (torch's caching allocator).
 """
 import warnings
 from collections import OrderedDict
@@ -42,9 +40,9 @@ import torch.nn.functional as F
 import torch.utils.checkpoint as cp
 from torch.nn.modules.batchnorm import _BatchNorm
 
-from . import _lib
 from . import functional as Fn
 from . import ops
+from .kernel_route import KernelRoute, f32, refuse_outside_limits
 from .registry import BACKBONES
 
 
@@ -99,45 +97,19 @@ class eSEModule(nn.Module):
         return x * self.hsigmoid(self.fc(self.avg_pool(x)))
 
 
-def _f32(x):
-    return x if x.dtype == torch.float32 and x.is_contiguous() else x.float().contiguous()
-
-
-class _KernelRoute:
-    """What the stem and the OSA module share: the route decision and the values kept from parameters."""
-    torch_ops = False
+class _KernelRoute(KernelRoute):
+    """What the stem and the OSA module add to the skeleton: their BatchNorms decide what train mode is, and every kept value is a
+    convolution's weight image or the folded constants of the BatchNorm behind it."""
+    _kernels = ('VoVNet kernels fold the BatchNorms\' running statistics into the convolutions (so every BatchNorm must be frozen: '
+                'eval() mode with running statistics, what norm_eval=True keeps in every config) and have no backward')
 
     def _init_route(self, torch_ops, limits):
-        self.torch_ops = bool(torch_ops)
-        self._kernel_limits = limits
-        self._kept = {}             # key -> (ops._Stamp, value at a fixed address)
+        KernelRoute._init_route(self, torch_ops, limits)
         # what the route decision reads on every call, listed once: the subtree is built in __init__ and never altered
         self._norms = tuple(m for m in self.modules() if isinstance(m, _BatchNorm))
-        self._params = tuple(self.parameters())
 
-    def _route_name(self):
-        limits = f': {"; ".join(self._kernel_limits)}' if self._kernel_limits else ''
-        return f'{type(self).__name__}{limits}'
-
-    def _uses_torch_ops(self, x):
-        if Fn.torch_ops_route(self._route_name(), True, module=self):
-            return True
-        Fn.torch_ops_route(self._route_name(), not self._kernel_limits, module=self)     # raises when outside the limits
-        name = type(self).__name__
-        if any(m.training or m.running_mean is None for m in self._norms):
-            raise _lib.Gd4dError(f'{name} in train() mode with a BatchNorm that is not frozen: graph-detr4d_amd\'s VoVNet kernels fold the '
-                                 'running statistics into the convolutions and have no backward.  `torch_ops=True` (or GD4D_TORCH_OPS=1) '
-                                 'runs the reference\'s op sequence, trainable by autograd; norm_eval=True (every config) keeps the '
-                                 'BatchNorms in eval() mode.')
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._params)):
-            raise _lib.Gd4dError(f'{name}: autograd is on, and graph-detr4d_amd\'s VoVNet kernels have no backward.  Run inference under '
-                                 'torch.no_grad() (or freeze the parameters and the input), or choose the torch-op route '
-                                 '(`torch_ops=True` / GD4D_TORCH_OPS=1).')
-        Fn.require_gpu(x, 'inputs')
-        return False
-
-    def _keep(self, key, sources, build):
-        return ops.kept_in_place(self._kept, key, sources, build, self)
+    def _in_train_mode(self):
+        return any(m.training or m.running_mean is None for m in self._norms)
 
     def _image(self, key, conv):
         build = ops.conv3x3_image if conv.kernel_size == (3, 3) else ops.osa_concat_image
@@ -152,12 +124,7 @@ class _KernelRoute:
         scale, shift = self._folded(key, bn)
         return ops.conv3x3_bn_relu(x, self._image(key, conv), conv.out_channels, scale, shift, stride=conv.stride[0])
 
-    def refresh_images(self):
-        """For the owner of a hipGraph captured over this module: after an in-place parameter edit, rebuild the changed images and
-        folded constants into the buffers the graph reads (outside the graph, before the replay).  Writes through `.data` need
-        ops.invalidate_chain_images() first, as everywhere."""
-        if not next(self.parameters()).is_cuda:
-            raise _lib.Gd4dError('refresh_images: the module is not on the GPU (no CPU fallback in graph-detr4d_amd)')
+    def _kept_values(self):
         for key, conv, bn in self._kernel_layers():
             self._image(key, conv)
             self._folded(key, bn)
@@ -189,20 +156,20 @@ class _Stem(_KernelRoute, nn.Sequential):
     def _kernel_layers(self):
         return [(i, getattr(self, f'stem_{i}/conv'), getattr(self, f'stem_{i}/norm')) for i in (1, 2, 3)]
 
-    def refresh_images(self):
+    def _kept_values(self):
         (_, _, bn1), *rest = self._kernel_layers()
-        self._folded(1, bn1)
+        self._folded(1, bn1)                    # (stem_1 runs on F.conv2d: no weight image)
         for key, conv, bn in rest:
             self._image(key, conv)
             self._folded(key, bn)
 
     def forward(self, x):
-        if self._uses_torch_ops(x):
+        if self._route(x) == 'torch':
             return nn.Sequential.forward(self, x)
         with torch.no_grad():
             (_, conv1, bn1), *rest = self._kernel_layers()
             scale, shift = self._folded(1, bn1)
-            x = F.conv2d(_f32(x), conv1.weight.detach().float(), None, conv1.stride, conv1.padding)
+            x = F.conv2d(f32(x), conv1.weight.detach().float(), None, conv1.stride, conv1.padding)
             x = x.mul_(scale.view(1, -1, 1, 1)).add_(shift.view(1, -1, 1, 1)).relu_()
             for key, conv, bn in rest:
                 x = self._conv3x3_hip(key, x, conv, bn)
@@ -253,7 +220,7 @@ class _OSA_module(_KernelRoute, nn.Module):
 
     def _hip(self, x):
         *layers, (ckey, cconv, cbn) = self._kernel_layers()
-        maps = [_f32(x)]
+        maps = [f32(x)]
         for key, conv, bn in layers:
             maps.append(self._conv3x3_hip(key, maps[-1], conv, bn))
         scale, shift = self._folded(ckey, cbn)
@@ -262,7 +229,7 @@ class _OSA_module(_KernelRoute, nn.Module):
         return ops.ese_apply(xt, gate, identity=maps[0] if self.identity else None, out=xt)
 
     def forward(self, x):
-        if self._uses_torch_ops(x):
+        if self._route(x) == 'torch':
             if self.with_cp and self.training:
                 return cp.checkpoint(self._torch, x, use_reentrant=False)
             return self._torch(x)
@@ -312,11 +279,8 @@ class VoVNet(nn.Module):
         self._out_feature_channels = dict(zip(['stem'] + self.stage_names, widths))
         self._out_feature_strides = dict(zip(['stem'] + self.stage_names, (4, 4, 8, 16, 32)))
         self.torch_ops = torch_ops
-        limits = [w for m in self._routed() for w in m._kernel_limits]
-        if limits:      # refused here, not at the first forward; raises unless the torch-op route was chosen
-            Fn.torch_ops_route(f'{type(self).__name__}({spec_name!r}): {"; ".join(limits[:4])}'
-                               + (f' and {len(limits) - 4} more' if len(limits) > 4 else '')
-                               + ' - pass torch_ops=True for this spec', False, module=self)
+        # refused here, not at the first forward
+        refuse_outside_limits(self, f'{type(self).__name__}({spec_name!r})', [w for m in self._routed() for w in m._kernel_limits])
 
     def _routed(self):
         return [m for m in self.modules() if isinstance(m, _KernelRoute)]

@@ -224,6 +224,62 @@ def test_graph_captured_on_a_serves_b_after_refresh_matrices():
             assert not torch.equal(e, e_a)                                 # B's cameras differ from A's
 
 
+def _small_capture_case(seed):
+    """One level, 2 cameras, a 17 x 18 map: 2 x 2 tiles of 16 x 16, ragged on both edges.  (module, metas, inputs A, inputs B)."""
+    mod = _random_module(seed)
+    six = _rig_metas(6, seed)[0]
+    metas = [dict(intrinsics=six['intrinsics'][:2], ida_mats=six['ida_mats'])]
+    gen = torch.Generator().manual_seed(seed)
+    a, b = (torch.randn(1, 2, 256, 17, 18, generator=gen).to(DEV) for _ in range(2))
+    return mod, metas, a, b
+
+
+def test_graph_replay_follows_refresh_images_at_the_same_address():
+    """A hipGraph captured on inputs A and replayed on inputs B equals the eager call on B; after an in-place weight edit,
+    refresh_images() (outside the graph) makes the replay show the new weight - the image keeps its address."""
+    from graph_detr4d_amd import functional as Fn
+    mod, metas, a, b = _small_capture_case(21)
+    static = a.clone()
+    with torch.no_grad(), Fn.request_slot(3):
+        mod.forward_levels([static], metas)                                # eager once: matrices and image on the device
+        torch.cuda.synchronize()
+        address = mod._image().data_ptr()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+            out, = mod.forward_levels([static], metas)
+        static.copy_(b)
+        graph.replay()
+        eager, = mod.forward_levels([b], metas)
+        assert torch.equal(out, eager)
+        before = out.clone()
+        mod.reduce_conv[0].weight.mul_(0.5)                                # in place: the version counter moves
+        mod.refresh_images()
+        graph.replay()
+        eager, = mod.forward_levels([b], metas)
+        assert torch.equal(out, eager) and not torch.equal(out, before)
+        assert mod._image().data_ptr() == address
+    torch.cuda.synchronize()
+
+
+def test_a_stale_image_is_refused_under_capture():
+    """After an in-place weight edit without refresh_images(), a capture raises instead of re-imaging inside the graph; a later eager
+    call works (and re-images)."""
+    from graph_detr4d_amd import functional as Fn
+    mod, metas, a, _ = _small_capture_case(22)
+    with torch.no_grad(), Fn.request_slot(3):
+        first, = mod.forward_levels([a], metas)
+        mod.reduce_conv[0].weight.mul_(0.5)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with pytest.raises(RuntimeError, match='once eagerly'):
+            with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+                mod.forward_levels([a], metas)
+        torch.cuda.synchronize()
+        second, = mod.forward_levels([a], metas)
+        assert torch.isfinite(second).all() and not torch.equal(first, second)
+    torch.cuda.synchronize()
+
+
 def test_output_follows_new_weights():
     """(e) load_state_dict, or an in-place change of a parameter: the next call uses the new weights."""
     n = 6
