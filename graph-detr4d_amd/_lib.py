@@ -8,8 +8,10 @@ import ctypes
 import os
 import threading
 
+from . import switches
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('GD4D_LIB_PATH') or os.path.join(_HERE, 'libgd4d.so')   # env override: dev A/B builds
+LIB_PATH = switches.path('GD4D_LIB_PATH') or os.path.join(_HERE, 'libgd4d.so')   # dev A/B builds; an import-time read
 ABI_VERSION = 56
 PIXEL_MAJOR, HEAD_MAJOR = 0, 1
 

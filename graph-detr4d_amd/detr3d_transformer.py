@@ -5,13 +5,13 @@ Drop-ins for the reference classes of the same names in
 projects/mmdet3d_plugin/models/utils/detr3d_transformer.py (:46, :153, :229, :397): same registry
 type names, constructor keywords, state-dict keys and call signatures.
 """
-import os
 
 import torch
 import torch.nn as nn
 
 from . import functional as Fn
 from . import ops
+from . import switches
 from .deform3d_cross_attn import Deform3DCrossAttn
 from .registry import (ATTENTION, TRANSFORMER, TRANSFORMER_LAYER_SEQUENCE,
                        build_transformer_layer_sequence)
@@ -325,7 +325,7 @@ class Detr3DTransformerDecoder(TransformerLayerSequence):
           'stream' - = 'g1,1,...': the round-1 per-layer pipeline (two value tensors alive)
           '0'      - off: every layer projects when it runs (the reference's order)
         Returns (kwargs, pipeline or None)."""
-        mode = os.environ.get('GD4D_PREPROJECT', 'auto')
+        mode = switches.spec('GD4D_PREPROJECT')
         value = kwargs.get('value')
         if kwargs.get(Fn.VALUE_CACHE_KEY) is not None:       # the caller projected already (Detr3DTransformer.forward_shared)
             return kwargs, None

@@ -1,10 +1,9 @@
 """Host-side helpers shared by the attention modules (GPU only; no CPU fallback)."""
 import numpy as np
-import os
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, switches
 
 
 def wants_grad(module, *tensors):
@@ -125,7 +124,7 @@ def torch_ops_route(what, supported, module=None):
     the kernels cover run on them unless the torch-op route was CHOSEN - per module (`module.torch_ops = True`, the constructor
     keyword `torch_ops=True` where a module has one, or `with Fn.torch_ops_for(module):`) or for the whole process
     (GD4D_TORCH_OPS=1, which the tests compare against); shapes they do not cover raise, naming the switches."""
-    if os.environ.get('GD4D_TORCH_OPS') == '1' or (module is not None and getattr(module, 'torch_ops', False)):
+    if switches.flag('GD4D_TORCH_OPS') or (module is not None and getattr(module, 'torch_ops', False)):
         return True
     if supported:
         return False
@@ -330,9 +329,8 @@ def use_head_major(value_dtype):
     """Value layout policy: head-major planes (B*N, Hh, S, Dh) pay off for bf16 storage (two
     x-adjacent corners = one 128-byte line: gather 42.9 -> 38.7 us); for fp32 the layouts tie, so the
     mmcv-compatible pixel-major layout is kept.  GD4D_VALUE_LAYOUT=pixel|head overrides (dev A/B)."""
-    import os
-    o = os.environ.get('GD4D_VALUE_LAYOUT')
-    if o in ('pixel', 'head'):
+    o = switches.choice('GD4D_VALUE_LAYOUT')
+    if o is not None:
         return o == 'head'
     return value_dtype == torch.bfloat16
 
@@ -427,7 +425,7 @@ def head_outputs(hs, init_reference, inter_references, cls_branches, reg_branche
         boxes = BoxHeadFunction.apply(torch.stack(tmps), refs, pc_range, 1.0 if depth_factor is None else float(depth_factor))
         return {'all_cls_scores': torch.stack(classes), 'all_bbox_preds': boxes,
                 'enc_cls_scores': None, 'enc_bbox_preds': None}
-    chains = hs.is_cuda and hs.dtype == torch.float32 and os.environ.get('GD4D_HEAD_CHAINS', '1') != '0'
+    chains = hs.is_cuda and hs.dtype == torch.float32 and switches.flag('GD4D_HEAD_CHAINS')
     for lvl in range(hs.shape[0]):
         reference = init_reference if lvl == 0 else inter_references[lvl - 1]
         x = hs[lvl].contiguous()
@@ -490,7 +488,7 @@ def raw_pyramid_for_training(modules, value):
     after the last layer's backward.  Returns the dict handed to the layers through kwargs[VALUE_CACHE_KEY]:
     {id(module): (None, shapes, value, (RawPyramid, token))}, or None when the path does not apply (bf16 values, channels-last
     levels, shapes outside the kernels' limits)."""
-    if os.environ.get('GD4D_TRAIN_VALUES', 'raw') != 'raw' or not LateValues.applicable(modules, value, ignore_mode=True):
+    if switches.choice('GD4D_TRAIN_VALUES') != 'raw' or not LateValues.applicable(modules, value, ignore_mode=True):
         return None
     if any(v.dtype != torch.float32 for v in value):
         return None
@@ -519,7 +517,7 @@ def project_values_for_layers_autograd(modules, value):
         with torch.no_grad():
             # (a PyramidView: the channel-sliced gather reads it; GD4D_AGG=rows keeps the pixel-major copy + gd4d_cross_attn_agg_fwd)
             src = [v.detach().contiguous() for v in value]
-            if os.environ.get('GD4D_AGG', AGG_DEFAULT) == 'sliced':
+            if switches.choice('GD4D_AGG') == 'sliced':
                 sp, hw = ops.pyramid_slice_planar_fwd(src)
                 cl = ops.PyramidView.slice_planar(sp, hw)
             else:
@@ -551,7 +549,7 @@ def aux_stream(device):
     """Second-branch HIP stream for query-side work that is off the layer's critical path (position_encoder of the
     reference points, the reg branch + refinement between layers).  Those kernels are tiny and latency-bound; run
     next to the main chain they cost nothing.  None when disabled (GD4D_AUX_STREAM=0)."""
-    if os.environ.get('GD4D_AUX_STREAM', '1') == '0':
+    if not switches.flag('GD4D_AUX_STREAM'):
         return None
     return _companion_stream(_AUX_STREAMS, device)
 
@@ -594,9 +592,9 @@ class ValuePipeline:
     # are 57 workgroups at 900 queries and want one round): 3/4 of the device.  MI355X, groups of two layers, fused
     # decoder: 144: 345, 160: 352, 176: 365, 192: 373, 224: 356 samples/s.  GD4D_PIPELINE_CUS overrides.
     def _cu_share(self, group_size):
-        env = os.environ.get('GD4D_PIPELINE_CUS')
-        if env:
-            return int(env)
+        env = switches.integer('GD4D_PIPELINE_CUS')
+        if env is not None:
+            return env
         cus = torch.cuda.get_device_properties(self.value[0].device).multi_processor_count
         return max(8, (cus * 3 // 4) // 8 * 8)
 
@@ -671,7 +669,6 @@ def _wait_event(stream, event):
 
 
 LATE_VALUES_KEY = '_gd4d_late_values'
-AGG_DEFAULT = 'sliced'
 
 
 class LateValues:
@@ -685,7 +682,7 @@ class LateValues:
         """dtype: storage type of the channels-last copy - torch.bfloat16 for modules built with value_dtype='bf16' (half the
         bytes to copy and to gather, bf16-rounded features, fp32 accumulation).
 
-        Three sources for the gather (GD4D_AGG=rows|sliced, default AGG_DEFAULT):
+        Three sources for the gather (GD4D_AGG=rows|sliced, default sliced):
           rows    gd4d_pyramid_channels_last_fwd -> (R, S, 256), gd4d_cross_attn_agg_fwd (one workgroup per query, value_proj
                   in its epilogue); batch 1 only
           sliced  gd4d_pyramid_slice_planar_fwd -> (8, R, S, 32), gd4d_cross_attn_plan_fwd + gd4d_cross_attn_agg_sliced_fwd
@@ -719,7 +716,7 @@ class LateValues:
                     self.event = _record_event(self.side)
                 self.coarse.rows.record_stream(self.main)
             return
-        self.mode = os.environ.get('GD4D_AGG', AGG_DEFAULT)
+        self.mode = switches.choice('GD4D_AGG')
         if self.mode == 'rows' and value[0].shape[0] != 1:
             self.mode = 'sliced'                     # B > 1: the row % B pairing lives in the plan kernel
         self.side = _companion_stream(_SIDE_STREAMS, dev)
@@ -728,9 +725,9 @@ class LateValues:
             # GD4D_COPY_CUS: compute units of the persistent copy (default 3/4 of the device: the query side of the first layer and the
             # first projection of the coarse levels run on the rest, underneath it - round 6, samples/s one request / two in flight:
             # 160: 646 / 798, 192: 656-658 / 807-810, 224: 657-659 / 785-789, 256: 659 / 778); 0 = the plain one-workgroup-per-tile copy
-            env = os.environ.get('GD4D_COPY_CUS')
+            env = switches.integer('GD4D_COPY_CUS')
             cus = torch.cuda.get_device_properties(dev).multi_processor_count
-            copy_cus = int(env) if env else max(8, (cus * 3 // 4) // 8 * 8)
+            copy_cus = env if env is not None else max(8, (cus * 3 // 4) // 8 * 8)
             src = [v.contiguous() for v in value]
             self.src, self.copy_cus, self.copy_dtype = src, copy_cus, dtype
             if self.mode == 'sliced':
@@ -738,7 +735,7 @@ class LateValues:
                     # The first layer's projection of the coarse levels: on the MAIN stream behind plan 0 (aggregate), where that
                     # stream would otherwise only wait for the copy - in front of the copy it was 19-26 us of the request's critical
                     # path (one request at a time: 667 against 658 samples/s; two in flight: 786 against 808 - GD4D_FIRST_PROJ=side).
-                    if os.environ.get('GD4D_FIRST_PROJ', 'main') == 'main':
+                    if switches.choice('GD4D_FIRST_PROJ') == 'main':
                         self.coarse_first, self.project_late = coarse_for[0], True
                     else:
                         self._project_first(coarse_for[0])
@@ -781,7 +778,7 @@ class LateValues:
 
     @staticmethod
     def applicable(modules, value, ignore_mode=False):
-        if (not ignore_mode and os.environ.get('GD4D_PROJECT', 'late') != 'late') or not modules \
+        if (not ignore_mode and switches.choice('GD4D_PROJECT') != 'late') or not modules \
                 or not isinstance(value, (list, tuple)):
             return False
         in_place = all(torch.is_tensor(v) and ops.PyramidView.is_channels_last_level(v) for v in value)
@@ -803,7 +800,7 @@ class LateValues:
         were a third of the gather.  Returns whether it applies: 4 levels, 8 heads, fp32 source levels (GD4D_COARSE=0: off)."""
         if self.coarse is not None:
             return True
-        if os.environ.get('GD4D_COARSE', '1') == '0' or self.mode != 'sliced' or len(self.shapes) != 4 or not modules:
+        if not switches.flag('GD4D_COARSE') or self.mode != 'sliced' or len(self.shapes) != 4 or not modules:
             return False
         if any(m.num_heads != 8 or m.embed_dims != 256 for m in modules) or self.value[0].dtype != torch.float32:
             return False
@@ -814,7 +811,7 @@ class LateValues:
         s23 = sum(h * w for h, w in self.shapes[2:])
         # The projection must fit the window it hides in: ~30 us for the 43 800 rows of the R50 pyramid at 24 cameras beside a 55-us
         # chain; the VoVNet-99 pyramid's coarse levels are 4 x that while its gather gains the same ~30 us (GD4D_COARSE_MAX_ROWS).
-        if rows * s23 > int(os.environ.get('GD4D_COARSE_MAX_ROWS', '65536')):
+        if rows * s23 > switches.integer('GD4D_COARSE_MAX_ROWS'):
             return False
         buf = torch.empty(rows, s23, 256, device=src[0].device, dtype=torch.float32)
         self.coarse_src, self.coarse = src, ops.CoarseValues(buf, self.shapes[2:])
@@ -854,7 +851,7 @@ class LateValues:
         if self.mode == 'sliced':
             # (the plan needs nothing from the pyramid but its strides: layer 0's runs underneath the copy)
             # GD4D_PLAN=pairs: the 128-bytes-per-item form the training kernels read
-            items = coarse or os.environ.get('GD4D_PLAN', 'items') != 'pairs'     # (the coarse-projected gather walks items)
+            items = coarse or switches.choice('GD4D_PLAN') != 'pairs'     # (the coarse-projected gather walks items)
             plan = ops.cross_attn_plan_fwd(self.pyramid, ref.contiguous(), offsets.contiguous(), attn_logits.contiguous(),
                                            cam_logits.contiguous(), lidar2img, module.pc_range, img_h, img_w, module.num_heads,
                                            query_order=order, items=items, raw_cam_weights=raw_cam_weights)
@@ -918,7 +915,7 @@ def query_order(reference_points, pc_range):
 
 def query_order_enabled(reference_points):
     """gd4d_query_order_fwd sorts in one workgroup: up to 4096 queries per call; beyond that run unordered."""
-    return os.environ.get('GD4D_QUERY_ORDER', '1') != '0' and reference_points.is_cuda and \
+    return switches.flag('GD4D_QUERY_ORDER') and reference_points.is_cuda and \
         reference_points.shape[0] * reference_points.shape[1] <= 4096 and reference_points.shape[0] <= 512
 
 

@@ -16,7 +16,6 @@ reductions only.  Used by Detr3DTransformerDecoder.forward when every layer has 
 (GD4D_FUSED_DECODER=0 disables it); anything else takes the generic path.
 """
 import ctypes
-import os
 import weakref
 
 import torch
@@ -25,6 +24,7 @@ import torch.nn as nn
 from . import _lib
 from . import functional as Fn
 from . import ops
+from . import switches
 from .deform3d_cross_attn import Deform3DCrossAttn
 from .transformer_layers import FFN, MultiheadAttention
 
@@ -54,7 +54,7 @@ def applicable(decoder, query, value, reference_points, reg_branches, attn_masks
     """The forward-only fused loop must not be taken when autograd has to see the call: a parameter, the queries, the
     reference points OR THE FEATURE MAPS (a frozen decoder on a backbone that is being fine-tuned, input-gradient
     analysis) requiring grad sends the call down the generic path, whose modules build the autograd graph."""
-    if os.environ.get('GD4D_FUSED_DECODER', '1') == '0' or Fn.wants_grad(
+    if not switches.flag('GD4D_FUSED_DECODER') or Fn.wants_grad(
             decoder, query, query_pos, reference_points, *(value if isinstance(value, (list, tuple)) else ())):
         return False
     if not query.is_cuda or query.dtype != torch.float32 or query.dim() != 3 or query.shape[1] != 1:
@@ -109,7 +109,7 @@ def _kv_planes(layers, q, c, attn_mask, dev):
     """The K / V planes of run_single's attention launches, or None: one pair for all layers (a layer's attention core has read
     them before the in-projection of the next writes them - one stream).  Needs the one-operation in-projection, 256 channels
     (H-DETR's 2-D mask rides along)."""
-    if c != 256 or (attn_mask is not None and attn_mask.dim() != 2) or os.environ.get('GD4D_MHA_FP32') == '1':
+    if c != 256 or (attn_mask is not None and attn_mask.dim() != 2) or switches.flag('GD4D_MHA_FP32'):
         return None
     if layers[0].attentions[0].num_heads != 8:
         return None
@@ -133,7 +133,7 @@ def initial_reference(linear, query_pos):
 
 def fast_input(module, query_embed, mlvl_feats):
     """The conditions under which Detr3DTransformer hands strided views to the decoder and uses initial_reference."""
-    return (os.environ.get('GD4D_FUSED_DECODER', '1') != '0' and query_embed.is_cuda and query_embed.dtype == torch.float32
+    return (switches.flag('GD4D_FUSED_DECODER') and query_embed.is_cuda and query_embed.dtype == torch.float32
             and mlvl_feats[0].size(0) == 1 and query_embed.dim() == 2 and query_embed.stride(1) == 1
             and query_embed.shape[1] % 8 == 0 and (query_embed.shape[1] // 2) % 128 == 0
             and not Fn.wants_grad(module, query_embed, *mlvl_feats))
@@ -510,16 +510,13 @@ def run(decoder, query, query_pos, value, reference_points, reg_branches, img_me
 
 
 # ---- the request program: one host call per eager request -------------------------------------------------------------------
-# Switches that select the schedule run_single / LateValues build: part of a program's key.
-ROUTE_SWITCHES = ('GD4D_POS_ENCODER', 'GD4D_COARSE', 'GD4D_FIRST_PROJ', 'GD4D_MHA_FP32', 'GD4D_AGG', 'GD4D_PLAN', 'GD4D_PROJECT',
-                  'GD4D_COPY_CUS', 'GD4D_COARSE_MAX_ROWS', 'GD4D_QUERY_ORDER')
 _PROGRAMS = weakref.WeakKeyDictionary()          # decoder -> {key: RequestProgram}
 _B_QUERY, _B_POS, _B_REF, _B_L2I, _B_IMG_H, _B_IMG_W, _B_MASK, _B_OUT, _B_REFS, _B_LEVEL0 = range(10)
 
 
 def request_enabled():
     """GD4D_REQUEST=1 (default 0) and no capture in progress: a captured graph keeps the launches of the Python loop, one by one."""
-    return os.environ.get('GD4D_REQUEST', '0') == '1' and _lib.recorder() is None and not torch.cuda.is_current_stream_capturing()
+    return switches.flag('GD4D_REQUEST') and _lib.recorder() is None and not torch.cuda.is_current_stream_capturing()
 
 
 class RequestProgram:
@@ -535,7 +532,7 @@ class RequestProgram:
     slice-planar copy, the coarse rows - lives in the program's private memory pool.
 
     One program serves ONE request at a time on ONE stream: it is keyed by (device, stream, request slot - functional.slot_key -, shapes
-    and strides, level layout, mask, route switches - the environment ones and ops.ALL_EXACT, hand-offs in use, value storage type),
+    and strides, level layout, mask, route switches - switches.schedule_key() and ops.ALL_EXACT, hand-offs in use, value storage type),
     so a second stream or slot gets a program (and intermediates) of its own; recording is per thread (_lib.recording).  It
     holds values derived from parameters (weight images, stacked weights, value_proj images): it stands under the one rule of
     ops.invalidate_chain_images (an ops._Stamp over the decoder's and the reg branches' parameters) and is recorded again before
@@ -561,8 +558,9 @@ class RequestProgram:
         kwargs = dict(key=None, value=value, query_pos=query_pos, img_metas=img_metas)
         if mask is not None:
             kwargs['attn_masks'] = [mask, None]
-        with torch.cuda.use_mem_pool(self.pool, device=dev), _lib.recording(rec):
+        with torch.cuda.use_mem_pool(self.pool, device=dev), switches.read_log() as read, _lib.recording(rec):
             outs, refs = decoder(query, reference_points=reference_points, reg_branches=reg_branches, **kwargs)
+        self.switches_read = frozenset(read)           # what the recorded code asked the environment: all in switches.SCHEDULE (tested)
         lead = () if decoder.return_intermediate else (1,)           # (forward hands out [0] of the stacked outputs then)
         self.out_shape, self.ref_shape = lead + tuple(outs.shape), lead + tuple(refs.shape)
         tensors = {_B_QUERY: query, _B_POS: query_pos, _B_REF: reference_points, _B_OUT: outs, _B_REFS: refs}
@@ -673,7 +671,7 @@ def request_forward(decoder, query, reference_points, reg_branches, kwargs):
     # steps use hand-offs (a time-out turns them off: ops.check_handoff), the value storage type of the cross-attention modules
     key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, Fn.slot_key(dev), tuple(query.shape), query.stride(), query_pos.stride(),
            tuple((tuple(v.shape), v.stride(), v.dtype) for v in value), None if mask is None else (tuple(mask.shape), mask.dtype),
-           reg_branches is None, decoder.return_intermediate, len(img_metas), tuple(os.environ.get(k) for k in ROUTE_SWITCHES),
+           reg_branches is None, decoder.return_intermediate, len(img_metas), switches.schedule_key(),
            bool(ops.ALL_EXACT[0]), ops.handoff_enabled(dev, 'GD4D_POS_ENCODER'), decoder.layers[0].attentions[1].value_dtype)
     table = _PROGRAMS.get(decoder)
     if table is None:

@@ -24,13 +24,13 @@ Reference: utils/detr3d_transformer.py:153-225 (loop, refinement, detach), utils
 BaseTransformerLayer / MultiheadAttention / FFN (config ...ceph.py:71-89); what is computed is autograd of exactly those.
 GD4D_TRAIN_CHAINS=0 keeps the generic path.
 """
-import os
 import weakref
 
 import torch
 
 from . import functional as Fn
 from . import ops
+from . import switches
 from .deform3d_cross_attn import Deform3DCrossAttn
 from .fused_decoder import ORDER, _plain_reg_branch
 from .transformer_layers import FFN, MultiheadAttention
@@ -60,7 +60,7 @@ def _dropouts(layer):
 
 
 def applicable(decoder, query, query_pos, value, reference_points, reg_branches, attn_masks, raw_entry, args, kwargs):
-    if os.environ.get('GD4D_TRAIN_CHAINS', '1') == '0' or not torch.is_grad_enabled() or args:
+    if not switches.flag('GD4D_TRAIN_CHAINS') or not torch.is_grad_enabled() or args:
         return False
     if raw_entry is None or not isinstance(raw_entry, dict) or query_pos is None or 'img_metas' not in kwargs:
         return False
@@ -221,7 +221,7 @@ class DecoderTrainFunction(torch.autograd.Function):
         # before the next in-projection writes them); the fp32 rows stay for the attention backward
         kv = None
         if (c == 256 and layers[0].attentions[0].num_heads == 8 and (mask is None or mask.dim() == 2)
-                and os.environ.get('GD4D_MHA_FP32') != '1'):
+                and not switches.flag('GD4D_MHA_FP32')):
             kv = ops.KVPlanes(q, c, dev, heads=8)
         ops.row_chain_fwd([ops.chain_load(0, x, pos, out=xp), ops.chain_load(1, x),
                            ops.chain_gemm_two_sources(0, 1, 2 * c, im0['inproj'], p0['in_b'], qkv.view(q, -1), kv=kv, keep_fp32=True)], q)
@@ -386,7 +386,7 @@ class DecoderTrainFunction(torch.autograd.Function):
         g_next = None                        # gradient of a layer's OUTPUT coming from the layer after it
         gpos = None                          # running gradient of query_pos
         g_ref0 = padz = carry = carry_keep = None
-        fills_in = os.environ.get('GD4D_FILLS_RIDE', 'chain')               # 'chain' | 'mha': which launches carry the record fills
+        fills_in = switches.choice('GD4D_FILLS_RIDE')               # 'chain' | 'mha': which launches carry the record fills
         if want_pyramid:
             # the pyramid gradient's record fills ride as guests of every layer's first backward chain (57 of the 256 compute units
             # busy for 50-70 us); until round 6: of the attention backward's dk / dv launches, which they made 20-38 us longer

@@ -11,7 +11,6 @@ ops.sine_pe3d_fwd, ops.se_fuse_fwd); the 1x1 convolutions are plain library GEMM
 padding masks only, so its result is cached while the masks do not change (every sample of a dataset shares them).
 """
 import math
-import os
 
 import numpy as np
 import torch
@@ -20,6 +19,7 @@ import torch.nn.functional as F
 
 from . import functional as Fn
 from . import ops
+from . import switches
 
 
 class SELayer(nn.Module):
@@ -274,7 +274,7 @@ class FeaturePositionEmbedding(nn.Module):
             # ... and with the frustum coordinates generated in its prologue (gd4d_mlp2_frustum_fwd; GD4D_PE_FRUSTUM=0: the two kernels)
             cache['pe_mlp_fr'] = ops.mlp2_frustum_image(flat(pe0), pe0.bias.detach(), flat(pe2)) \
                 if cache['pe_mlp'] is not None and pe0.in_channels == 192 and self.depth_num == 64 and len(self.pc_range) == 6 \
-                and os.environ.get('GD4D_PE_FRUSTUM', '1') != '0' else None
+                and switches.flag('GD4D_PE_FRUSTUM') else None
             # the SE gate's two convolutions (and the fuse behind them) as one kernel too: gd4d_mlp2_se_fuse_fwd
             ce = convs['se1']
             cache['se_mlp'] = ops.mlp2_image(flat(cr), cr.bias.detach(), flat(ce)) \
@@ -322,7 +322,7 @@ class FeaturePositionEmbedding(nn.Module):
         # from sample to sample (the past frames' matrices carry the ego motion and change every time).
         pkey = (str(dev), tuple(shapes), tuple(pad_hw), r, sw['stamp'])
         if self.channels_last_out and sw.get('se_mlp') is not None and sw.get('pe_mlp_fr') is not None and len(feats) <= 4 \
-                and os.environ.get('GD4D_PE_FUSED', '1') != '0':
+                and switches.flag('GD4D_PE_FUSED'):
             return self._forward_one_kernel(feats, mats, sw, sine, shapes, starts, s_tot, pad_hw, pkey)
         c = self._pe_cache if self.cache_position_embedding else None
         if c is not None and c[0] == pkey:

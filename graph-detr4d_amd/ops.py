@@ -6,12 +6,11 @@ path has no CPU fallback.
 import ctypes
 import functools
 import inspect
-import os
 import weakref
 
 import torch
 
-from . import _lib
+from . import _lib, switches
 
 
 def _dev(t, name, dtype=None):
@@ -2172,7 +2171,7 @@ def chain_dropmask(src, dst, n, seed, p, out=None):
 # Measurement switch (bench.py's `exact_gemms` figure; `with ops.all_exact():`): EVERY GEMM operation of the chains built while it is
 # on uses six bf16 products (GD4D_CHAIN_EXACT, ~2^-24) - what fp32-class arithmetic on the query side costs.  HEADGEMM (value_proj
 # of the aggregates) and the attention core's two products stay on three.
-ALL_EXACT = [os.environ.get('GD4D_CHAIN_ALL_EXACT') == '1']
+ALL_EXACT = [switches.flag('GD4D_CHAIN_ALL_EXACT')]          # (an import-time read: switches.py)
 
 
 class all_exact:
@@ -2465,11 +2464,10 @@ def handoff_placement_ok(device):
     return st['placement']
 
 
-def handoff_enabled(device, env):
-    """Whether a step may use hand-offs: the switch `env` (GD4D_POS_ENCODER=dual / GD4D_TRAIN_REG_BESIDE=0 turn them off) and the
+def handoff_enabled(device, switch):
+    """Whether a step may use hand-offs: the flag `switch` (GD4D_POS_ENCODER=dual / GD4D_TRAIN_REG_BESIDE=0 turn them off) and the
     placement self-test."""
-    import os
-    if os.environ.get(env, '1') in ('0', 'dual'):
+    if not switches.flag(switch):
         return False
     return handoff_placement_ok(device)
 

@@ -96,6 +96,23 @@ def test_request_equals_eager_under_route_switch(scene, monkeypatch, switch, val
     _same(monkeypatch, scene['tr'], scene['feats'], scene['qe'], scene['regs'], scene['metas'])
 
 
+def test_a_recording_reads_schedule_switches_only(scene, monkeypatch):
+    """The program's key holds the raw values of switches.SCHEDULE; the read log of a recording (RequestProgram.switches_read: every
+    switch the recorded code asked the environment) must lie inside that set - a switch read there and missing from the key would
+    let a recorded launch sequence be replayed after the switch changed."""
+    from graph_detr4d_amd import fused_decoder, switches
+    programs = []
+    orig = fused_decoder.RequestProgram.__init__
+    monkeypatch.setattr(fused_decoder.RequestProgram, '__init__', lambda self, *a: (orig(self, *a), programs.append(self))[0])
+    monkeypatch.setenv('GD4D_COPY_CUS', '200')             # (a key no other test of this file uses: this call records)
+    _call(monkeypatch, True, scene['tr'], scene['feats'], scene['qe'], scene['regs'], scene['metas'])
+    assert len(programs) == 1
+    read = programs[0].switches_read
+    print('switches read while recording:', sorted(read))
+    assert read and read <= set(switches.SCHEDULE), sorted(read - set(switches.SCHEDULE))
+    assert {'GD4D_AGG', 'GD4D_COPY_CUS', 'GD4D_POS_ENCODER', 'GD4D_MHA_FP32'} <= read      # (LateValues and run_single were recorded)
+
+
 def test_all_exact_is_part_of_the_program_key(scene, monkeypatch):
     """`with ops.all_exact():` selects other chain descriptors without touching the environment: a request inside it must not be
     served by the program recorded outside it."""

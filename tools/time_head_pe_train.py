@@ -1,5 +1,7 @@
-"""Forward + backward of FeaturePositionEmbedding at the VoVNet / 24-camera size on both routes (GD4D_HEAD_PE_BWD=hip|torch):
-milliseconds per call, and the largest difference between the two routes' gradients."""
+"""Forward + backward of FeaturePositionEmbedding at the VoVNet / 24-camera size on both routes: milliseconds per call, and the
+largest difference between the two routes' gradients.  The routes are selected by GD4D_TORCH_OPS, the switch the module reads
+(`hip`: 0, the library's GEMMs forward and backward; `torch`: 1, the 1x1 convolutions as torch ops).  The tool used to set
+GD4D_HEAD_PE_BWD, a name nothing reads, and so timed one route twice; it now drives the real switch."""
 import os
 import sys
 import time
@@ -24,7 +26,7 @@ def main():
     probes = [torch.randn_like(f) for f in feats0]
     res = {}
     for route in ('hip', 'torch', 'hip', 'torch'):
-        os.environ['GD4D_HEAD_PE_BWD'] = route
+        os.environ['GD4D_TORCH_OPS'] = '1' if route == 'torch' else '0'
         times = []
         for it in range(4):
             mod.zero_grad(set_to_none=True)
