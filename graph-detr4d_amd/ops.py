@@ -2,6 +2,20 @@
 
 Every function requires CUDA(HIP)-resident, contiguous tensors and raises otherwise - the product
 path has no CPU fallback.
+
+The wrapper convention, stated once.  A wrapper checks shapes, allocates what it returns, marshals, and launches with _call:
+  _call(entry, *args)   looks `entry` up on _lib.load() AT CALL TIME (so a StepRecorder or any other _lib.recording stand-in takes
+                        the call), passes args and the current stream of the current device as the last argument, and raises
+                        Gd4dError in the entry's name unless the code is 0.  Entries without a trailing stream, size queries
+                        (*_bytes, *_tiles) and the one wrapper that looks at the code before it is checked are written out.
+  _dev(t, name, dtype)  the pointer argument of a tensor: Gd4dError unless it lives on the GPU, TypeError unless it has `dtype`
+                        (None: any), ValueError unless it is contiguous - in that order.  _opt is _dev that hands None through as
+                        a null pointer (dtype defaults to F32); _order_ptr does the same for a query order.
+  _out(out, shape, ..)  the tensor to write: a new one, or the caller's after a ValueError if its shape is not `shape` (its device,
+                        dtype and layout are _dev's business when it is passed).
+  _levels / _range6 / _ptrs  the tables: c_int32[2 L] of (H, W) per level from pairs or from tensors' last two dimensions,
+                        c_double[6], and c_void_p[n] with every entry checked by _dev (a None entry is a null only with
+                        optional=True).  They are ctypes arrays; StepRecorder.steps takes bytes() of them.
 """
 import ctypes
 import functools
@@ -11,6 +25,8 @@ import weakref
 import torch
 
 from . import _lib, switches
+
+F32, I32, U8 = torch.float32, torch.int32, torch.uint8
 
 
 def _dev(t, name, dtype=None):
@@ -23,12 +39,54 @@ def _dev(t, name, dtype=None):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _opt(t, name, dtype=F32):
+    return None if t is None else _dev(t, name, dtype)
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _call(entry, *args):
+    _lib.check(getattr(_lib.load(), entry)(*args, _stream()), entry)
+
+
+def _out(out, shape, device, what, dtype=F32):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f'{what} must be {tuple(shape)}, got {tuple(out.shape)}')
+    return out
+
+
+def _levels(seq):
+    flat = [int(x) for e in seq for x in (e.shape[-2:] if torch.is_tensor(e) else e)]
+    return (ctypes.c_int32 * len(flat))(*flat)
+
+
+def _range6(pc_range):
+    return (ctypes.c_double * 6)(*[float(x) for x in pc_range])
+
+
+def _ptrs(tensors, name, dtype=F32, optional=False):
+    vals = [None if optional and t is None else _dev(t, f'{name}[{i}]', dtype).value for i, t in enumerate(tensors)]
+    return (ctypes.c_void_p * len(vals))(*vals)
+
+
+def _camera_args(ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w):
+    """The run of arguments the cross-attention entry points share, for *-splicing."""
+    return (_dev(ref, 'ref', F32), _dev(offsets, 'offsets', F32), _dev(attn_logits, 'attn_logits', F32),
+            _dev(cam_logits, 'cam_logits', F32), _dev(lidar2img, 'lidar2img', F32), _range6(pc_range), float(img_h), float(img_w))
+
+
+def _asked(res, *optional, bare=True):
+    """res (a tuple) + the optional results that were asked for (the others are None); bare: a lone result is not wrapped."""
+    res += tuple(o for o in optional if o is not None)
+    return res[0] if bare and len(res) == 1 else res
+
+
 def _value_dtype(t):
-    if t.dtype == torch.float32:
+    if t.dtype == F32:
         return _lib.F32
     if t.dtype == torch.bfloat16:
         return _lib.BF16
@@ -43,7 +101,6 @@ def cross_attn_fwd(value, level_hw, ref, offsets, attn_logits, cam_logits, lidar
     attn_logits (B,Q,Hh,L,P) (or (B,Q,Hh,L*P)); cam_logits (B,Q,N); lidar2img (B,N,4,4).
     query_order: optional int32 permutation of [0, B*Q) from query_order_fwd (scheduling only, same result).
     Returns out (B,Q,Hh*Dh) [, mask (B,N,Q,Hh,P) uint8] [, uv (B,N,Q,Hh,P,2)]."""
-    lib = _lib.load()
     b, q = ref.shape[0], ref.shape[1]
     n = lidar2img.shape[1]
     hh, dh = (value.shape[1], value.shape[3]) if head_major else (value.shape[2], value.shape[3])
@@ -55,26 +112,14 @@ def cross_attn_fwd(value, level_hw, ref, offsets, attn_logits, cam_logits, lidar
     if attn_logits.numel() != b * q * hh * nl * p or cam_logits.numel() != b * q * n:
         raise ValueError('attn_logits / cam_logits have the wrong number of elements')
     if out is None:
-        out = torch.empty(b, q, hh * dh, device=ref.device, dtype=torch.float32)
-    mask = torch.empty(b, n, q, hh, p, device=ref.device, dtype=torch.uint8) if want_mask else None
-    uv = torch.empty(b, n, q, hh, p, 2, device=ref.device, dtype=torch.float32) if want_uv else None
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for hw in level_hw for x in hw])
-    rng = (ctypes.c_double * 6)(*[float(x) for x in pc_range])
-    f32 = torch.float32
-    code = lib.gd4d_cross_attn_fwd(
-        _dev(value, 'value'), lv, _dev(ref, 'ref', f32), _dev(offsets, 'offsets', f32),
-        _dev(attn_logits, 'attn_logits', f32), _dev(cam_logits, 'cam_logits', f32),
-        _dev(lidar2img, 'lidar2img', f32), rng, float(img_h), float(img_w), _dev(out, 'out', f32),
-        _dev(mask, 'mask') if want_mask else None, _dev(uv, 'uv') if want_uv else None,
-        b, n, q, hh, dh, nl, p, _value_dtype(value), _lib.HEAD_MAJOR if head_major else _lib.PIXEL_MAJOR,
-        1 if raw_cam_weights else 0, None if query_order is None else _order_ptr(query_order, b * q), _stream())
-    _lib.check(code, 'gd4d_cross_attn_fwd')
-    res = (out,)
-    if want_mask:
-        res += (mask,)
-    if want_uv:
-        res += (uv,)
-    return res if len(res) > 1 else out
+        out = torch.empty(b, q, hh * dh, device=ref.device, dtype=F32)
+    mask = torch.empty(b, n, q, hh, p, device=ref.device, dtype=U8) if want_mask else None
+    uv = torch.empty(b, n, q, hh, p, 2, device=ref.device, dtype=F32) if want_uv else None
+    _call('gd4d_cross_attn_fwd', _dev(value, 'value'), _levels(level_hw),
+          *_camera_args(ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w), _dev(out, 'out', F32),
+          _opt(mask, 'mask', None), _opt(uv, 'uv', None), b, n, q, hh, dh, nl, p, _value_dtype(value),
+          _lib.HEAD_MAJOR if head_major else _lib.PIXEL_MAJOR, 1 if raw_cam_weights else 0, _order_ptr(query_order, b * q))
+    return _asked((out,), mask, uv)
 
 
 def pyramid_channels_last_fwd(feats, out=None, max_cus=0, out_dtype=torch.float32):
@@ -82,7 +127,6 @@ def pyramid_channels_last_fwd(feats, out=None, max_cus=0, out_dtype=torch.float3
     max_cus > 0: one persistent workgroup on each of that many compute units (the rest stays free for another stream).
     out_dtype torch.bfloat16: bf16 storage of the copy (reduced precision; the aggregate kernel accumulates in fp32).
     Returns (cl (R, S, 256), level_hw)."""
-    lib = _lib.load()
     fl = [f.reshape(-1, *f.shape[-3:]) for f in feats]
     r, c = fl[0].shape[0], fl[0].shape[1]
     level_hw = [(int(f.shape[-2]), int(f.shape[-1])) for f in fl]
@@ -91,11 +135,9 @@ def pyramid_channels_last_fwd(feats, out=None, max_cus=0, out_dtype=torch.float3
         raise ValueError('feature levels disagree in rows / channels')
     if out is None:
         out = torch.empty(r, s, c, device=fl[0].device, dtype=out_dtype)
-    ptrs = (ctypes.c_void_p * len(fl))(*[_dev(f, 'feats', torch.float32).value for f in fl])
-    lv = (ctypes.c_int32 * (2 * len(fl)))(*[int(x) for hw in level_hw for x in hw])
-    code = lib.gd4d_pyramid_channels_last_fwd(ptrs, lv, _dev(out, 'out'), r, c, len(fl), _lib.F32, _value_dtype(out), int(max_cus),
-                                              _stream())
-    _lib.check(code, 'gd4d_pyramid_channels_last_fwd')
+    ptrs = _ptrs(fl, 'feats')
+    lv = _levels(level_hw)
+    _call('gd4d_pyramid_channels_last_fwd', ptrs, lv, _dev(out, 'out'), r, c, len(fl), _lib.F32, _value_dtype(out), int(max_cus))
     return out, level_hw
 
 
@@ -105,7 +147,6 @@ def cross_attn_agg_fwd(feats_cl, level_hw, ref, offsets, attn_logits, cam_logits
     """gd4d_cross_attn_agg_fwd.  feats_cl (B*N, S, 256) fp32 channels-last pyramid; the other arguments as cross_attn_fwd.
     Returns agg (B, Q, Hh, 256), wsum (B, Q, Hh) [, mask] [, uv]; with vp_weight (256, 256) [, vp_bias]: value_proj of the
     aggregates applied in the kernel's epilogue - returns out (B, Q, 256) [, mask] [, uv] instead."""
-    lib = _lib.load()
     b, q = ref.shape[0], ref.shape[1]
     n = lidar2img.shape[1]
     hh, p = num_heads, offsets.shape[3]
@@ -115,38 +156,24 @@ def cross_attn_agg_fwd(feats_cl, level_hw, ref, offsets, attn_logits, cam_logits
         raise ValueError(f'feats_cl shape {tuple(feats_cl.shape)} inconsistent with B*N={b * n}, levels {level_hw}')
     if offsets.numel() != b * q * hh * p * 3 or attn_logits.numel() != b * q * hh * nl * p or cam_logits.numel() != b * q * n:
         raise ValueError('offsets / attn_logits / cam_logits have the wrong number of elements')
-    f32 = torch.float32
     fused = vp_weight is not None
-    agg = None if fused else torch.empty(b, q, hh, c, device=ref.device, dtype=f32)
-    wsum = None if fused else torch.empty(b, q, hh, device=ref.device, dtype=f32)
-    out = torch.empty(b, q, c, device=ref.device, dtype=f32) if fused else None
-    mask = torch.empty(b, n, q, hh, p, device=ref.device, dtype=torch.uint8) if want_mask else None
-    uv = torch.empty(b, n, q, hh, p, 2, device=ref.device, dtype=f32) if want_uv else None
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for hw in level_hw for x in hw])
-    rng = (ctypes.c_double * 6)(*[float(x) for x in pc_range])
-    code = lib.gd4d_cross_attn_agg_fwd(
-        _dev(feats_cl, 'feats_cl'), lv, _dev(ref, 'ref', f32), _dev(offsets, 'offsets', f32),
-        _dev(attn_logits, 'attn_logits', f32), _dev(cam_logits, 'cam_logits', f32), _dev(lidar2img, 'lidar2img', f32),
-        rng, float(img_h), float(img_w), None if fused else _dev(agg, 'agg'), None if fused else _dev(wsum, 'wsum'),
-        _dev(mask, 'mask') if want_mask else None, _dev(uv, 'uv') if want_uv else None,
-        b, n, q, hh, c, nl, p, _value_dtype(feats_cl), 1 if raw_cam_weights else 0,
-        None if query_order is None else _order_ptr(query_order, b * q),
-        _dev(vp_weight, 'vp_weight', f32) if fused else None, _opt(vp_bias, 'vp_bias') if fused else None,
-        _dev(out, 'out') if fused else None, _stream())
-    _lib.check(code, 'gd4d_cross_attn_agg_fwd')
-    res = (out,) if fused else (agg, wsum)
-    if want_mask:
-        res += (mask,)
-    if want_uv:
-        res += (uv,)
-    return res
+    agg = None if fused else torch.empty(b, q, hh, c, device=ref.device, dtype=F32)
+    wsum = None if fused else torch.empty(b, q, hh, device=ref.device, dtype=F32)
+    out = torch.empty(b, q, c, device=ref.device, dtype=F32) if fused else None
+    mask = torch.empty(b, n, q, hh, p, device=ref.device, dtype=U8) if want_mask else None
+    uv = torch.empty(b, n, q, hh, p, 2, device=ref.device, dtype=F32) if want_uv else None
+    _call('gd4d_cross_attn_agg_fwd', _dev(feats_cl, 'feats_cl'), _levels(level_hw),
+          *_camera_args(ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w), _opt(agg, 'agg', None),
+          _opt(wsum, 'wsum', None), _opt(mask, 'mask', None), _opt(uv, 'uv', None), b, n, q, hh, c, nl, p, _value_dtype(feats_cl),
+          1 if raw_cam_weights else 0, _order_ptr(query_order, b * q), _opt(vp_weight, 'vp_weight'),
+          _opt(vp_bias, 'vp_bias') if fused else None, _opt(out, 'out', None))
+    return _asked((out,) if fused else (agg, wsum), mask, uv, bare=False)
 
 
 def pyramid_slice_planar_fwd(feats, out=None, max_cus=0, out_dtype=torch.float32):
     """gd4d_pyramid_slice_planar_fwd.  feats as pyramid_channels_last_fwd.  Returns (sp (8, R, S, 32), level_hw): the
     channels-last pyramid with the channel axis cut into 8 planes of 32 (the layout gd4d_cross_attn_agg_sliced_fwd
     gathers from when it has to make its own copy)."""
-    lib = _lib.load()
     fl = [f.reshape(-1, *f.shape[-3:]) for f in feats]
     r, c = fl[0].shape[0], fl[0].shape[1]
     level_hw = [(int(f.shape[-2]), int(f.shape[-1])) for f in fl]
@@ -157,11 +184,9 @@ def pyramid_slice_planar_fwd(feats, out=None, max_cus=0, out_dtype=torch.float32
         raise ValueError('the slice-planar copy is built for 256 channels')
     if out is None:
         out = torch.empty(8, r, s, 32, device=fl[0].device, dtype=out_dtype)
-    ptrs = (ctypes.c_void_p * len(fl))(*[_dev(f, 'feats', torch.float32).value for f in fl])
-    lv = (ctypes.c_int32 * (2 * len(fl)))(*[int(x) for hw in level_hw for x in hw])
-    code = lib.gd4d_pyramid_slice_planar_fwd(ptrs, lv, _dev(out, 'out'), r, c, len(fl), _lib.F32, _value_dtype(out), int(max_cus),
-                                             _stream())
-    _lib.check(code, 'gd4d_pyramid_slice_planar_fwd')
+    ptrs = _ptrs(fl, 'feats')
+    lv = _levels(level_hw)
+    _call('gd4d_pyramid_slice_planar_fwd', ptrs, lv, _dev(out, 'out'), r, c, len(fl), _lib.F32, _value_dtype(out), int(max_cus))
     return out, level_hw
 
 
@@ -269,7 +294,6 @@ def cross_attn_plan_fwd(pyramid, ref, offsets, attn_logits, cam_logits, lidar2im
     which then also fills wsum).  both: pairs AND items in one launch (a training step: the forward gather reads the items, the
     backward kernels the pairs).
     Returns Plan [, mask (B, N, Q, Hh, P) uint8] [, uv (B, N, Q, Hh, P, 2)]."""
-    lib = _lib.load()
     b, q = ref.shape[0], ref.shape[1]
     n = lidar2img.shape[1]
     hh, p, nl = num_heads, offsets.shape[3], len(pyramid.level_hw)
@@ -277,32 +301,21 @@ def cross_attn_plan_fwd(pyramid, ref, offsets, attn_logits, cam_logits, lidar2im
         raise ValueError(f'pyramid has {pyramid.rows} camera rows, expected B*N = {b * n}')
     if offsets.numel() != b * q * hh * p * 3 or attn_logits.numel() != b * q * hh * nl * p or cam_logits.numel() != b * q * n:
         raise ValueError('offsets / attn_logits / cam_logits have the wrong number of elements')
-    f32 = torch.float32
     nbytes = cross_attn_plan_bytes(b, n, q, hh, p)
     if both and (items or plan is not None):
         raise ValueError('both=True excludes items / plan')
-    buf = torch.empty(2 * nbytes if both else nbytes, device=ref.device, dtype=torch.uint8) if plan is None else plan.buf
-    wsum = torch.empty(b, q, hh, device=ref.device, dtype=f32) if plan is None else plan.wsum
+    buf = torch.empty(2 * nbytes if both else nbytes, device=ref.device, dtype=U8) if plan is None else plan.buf
+    wsum = torch.empty(b, q, hh, device=ref.device, dtype=F32) if plan is None else plan.wsum
     plan = Plan(buf, query_order, pyramid, b, q, hh, wsum, items=items, points=p, items_buf=buf[nbytes:] if both else None)
-    mask = torch.empty(b, n, q, hh, p, device=ref.device, dtype=torch.uint8) if want_mask else None
-    uv = torch.empty(b, n, q, hh, p, 2, device=ref.device, dtype=f32) if want_uv else None
-    rng = (ctypes.c_double * 6)(*[float(x) for x in pc_range])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for hw in pyramid.level_hw for x in hw])
+    mask = torch.empty(b, n, q, hh, p, device=ref.device, dtype=U8) if want_mask else None
+    uv = torch.empty(b, n, q, hh, p, 2, device=ref.device, dtype=F32) if want_uv else None
     cs = (ctypes.c_int64 * nl)(*pyramid.cam_stride)
-    code = lib.gd4d_cross_attn_plan_fwd(
-        _dev(ref, 'ref', f32), _dev(offsets, 'offsets', f32), _dev(attn_logits, 'attn_logits', f32),
-        _dev(cam_logits, 'cam_logits', f32), _dev(lidar2img, 'lidar2img', f32), rng, float(img_h), float(img_w),
-        lv, cs, pyramid.pix_stride, _dev(buf, 'plan', torch.uint8), buf.numel(), _dev(wsum, 'wsum', f32),
-        _dev(mask, 'mask') if want_mask else None, _dev(uv, 'uv') if want_uv else None, b, n, q, hh, nl, p,
-        (CA_RAW_CAM_WEIGHTS if raw_cam_weights else 0) | (CA_PLAN_ITEMS if items else 0) | (CA_PLAN_BOTH if both else 0),
-        None if query_order is None else _order_ptr(query_order, b * q), _stream())
-    _lib.check(code, 'gd4d_cross_attn_plan_fwd')
-    res = (plan,)
-    if want_mask:
-        res += (mask,)
-    if want_uv:
-        res += (uv,)
-    return res if len(res) > 1 else plan
+    _call('gd4d_cross_attn_plan_fwd', *_camera_args(ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w),
+          _levels(pyramid.level_hw), cs, pyramid.pix_stride, _dev(buf, 'plan', U8), buf.numel(), _dev(wsum, 'wsum', F32),
+          _opt(mask, 'mask', None), _opt(uv, 'uv', None), b, n, q, hh, nl, p,
+          (CA_RAW_CAM_WEIGHTS if raw_cam_weights else 0) | (CA_PLAN_ITEMS if items else 0) | (CA_PLAN_BOTH if both else 0),
+          _order_ptr(query_order, b * q))
+    return _asked((plan,), mask, uv)
 
 
 def cross_attn_agg_sliced_fwd(plan, slices=(0, 8), agg=None, count=None):
@@ -317,12 +330,11 @@ def cross_attn_agg_sliced_fwd(plan, slices=(0, 8), agg=None, count=None):
     if not plan.buf.is_cuda or plan.buf.device != dev:
         raise _lib.Gd4dError('plan must live on the pyramid\'s GPU (no CPU fallback in graph-detr4d_amd)')
     nl = len(pyramid.level_hw)
-    f32 = torch.float32
     if agg is None:
-        agg = torch.empty(b, q, hh, 256, device=dev, dtype=f32)
+        agg = torch.empty(b, q, hh, 256, device=dev, dtype=F32)
     ptrs = (ctypes.c_void_p * nl)(*pyramid.ptrs)
     if plan.items or plan.items_buf is not None:
-        lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for hw in pyramid.level_hw for x in hw])
+        lv = _levels(pyramid.level_hw)
         cs = (ctypes.c_int64 * nl)(*pyramid.cam_stride)
         if count is not None:
             sink, layer = count
@@ -330,30 +342,25 @@ def cross_attn_agg_sliced_fwd(plan, slices=(0, 8), agg=None, count=None):
                 raise _lib.Gd4dError('gather + record count in one launch: a plan in both forms, all slices')
             slots, slot_bytes = sink.begin_layer(layer, plan)
             code = lib.gd4d_cross_attn_agg_items_count_fwd(
-                ptrs, lv, cs, pyramid.pix_stride, pyramid.slice_stride, _dev(plan.items_buf, 'plan', torch.uint8), _dev(agg, 'agg', f32),
-                _dev(plan.wsum, 'wsum', f32), b, pyramid.rows // b, q, hh, 256, nl, plan.points,
-                _lib.F32 if pyramid.dtype == torch.float32 else _lib.BF16,
-                None if query_order is None else _order_ptr(query_order, b * q), _dev(plan.buf, 'plan', torch.uint8),
-                _dev(sink.count, 'count', torch.int32), _dev(slots, 'slots'), ctypes.c_size_t(slot_bytes), _stream())
+                ptrs, lv, cs, pyramid.pix_stride, pyramid.slice_stride, _dev(plan.items_buf, 'plan', U8), _dev(agg, 'agg', F32),
+                _dev(plan.wsum, 'wsum', F32), b, pyramid.rows // b, q, hh, 256, nl, plan.points,
+                _lib.F32 if pyramid.dtype == F32 else _lib.BF16,
+                _order_ptr(query_order, b * q), _dev(plan.buf, 'plan', U8),
+                _dev(sink.count, 'count', I32), _dev(slots, 'slots'), ctypes.c_size_t(slot_bytes), _stream())
             if code == -2:                               # GD4D_EUNSUPPORTED (e.g. a pyramid of 4 GiB or more): the caller launches the two
                 return None
             _lib.check(code, 'gd4d_cross_attn_agg_items_count_fwd')
             sink.plans.append((int(layer), plan, slots))
             return agg
-        items_buf = _dev(plan.buf if plan.items else plan.items_buf, 'plan', torch.uint8)
-        dt = _lib.F32 if pyramid.dtype == torch.float32 else _lib.BF16
-        order_p = None if query_order is None else _order_ptr(query_order, b * q)
-        code = lib.gd4d_cross_attn_agg_items_fwd(
-            ptrs, lv, cs, pyramid.pix_stride, pyramid.slice_stride, items_buf, _dev(agg, 'agg', f32),
-            _dev(plan.wsum, 'wsum', f32), b, pyramid.rows // b, q, hh, 256, nl, plan.points, dt, order_p,
-            int(slices[0]), int(slices[1]), _stream())
-        _lib.check(code, 'gd4d_cross_attn_agg_items_fwd')
+        items_buf = _dev(plan.buf if plan.items else plan.items_buf, 'plan', U8)
+        dt = _lib.F32 if pyramid.dtype == F32 else _lib.BF16
+        order_p = _order_ptr(query_order, b * q)
+        _call('gd4d_cross_attn_agg_items_fwd', ptrs, lv, cs, pyramid.pix_stride, pyramid.slice_stride, items_buf, _dev(agg, 'agg', F32),
+              _dev(plan.wsum, 'wsum', F32), b, pyramid.rows // b, q, hh, 256, nl, plan.points, dt, order_p, int(slices[0]), int(slices[1]))
         return agg
-    code = lib.gd4d_cross_attn_agg_sliced_fwd(
-        ptrs, pyramid.slice_stride, _dev(plan.buf, 'plan', torch.uint8), _dev(agg, 'agg', f32), b, pyramid.rows // b, q, hh,
-        256, nl, plan.points, _lib.F32 if pyramid.dtype == torch.float32 else _lib.BF16,
-        None if query_order is None else _order_ptr(query_order, b * q), int(slices[0]), int(slices[1]), _stream())
-    _lib.check(code, 'gd4d_cross_attn_agg_sliced_fwd')
+    _call('gd4d_cross_attn_agg_sliced_fwd', ptrs, pyramid.slice_stride, _dev(plan.buf, 'plan', U8), _dev(agg, 'agg', F32), b,
+          pyramid.rows // b, q, hh, 256, nl, plan.points, _lib.F32 if pyramid.dtype == F32 else _lib.BF16, _order_ptr(query_order, b * q),
+          int(slices[0]), int(slices[1]))
     return agg
 
 
@@ -363,7 +370,7 @@ class CoarseValues:
 
     def __init__(self, rows, level_hw):
         (h2, w2), (h3, w3) = level_hw
-        if rows.dim() != 3 or rows.shape[1] != h2 * w2 + h3 * w3 or rows.shape[2] != 256 or rows.dtype != torch.float32 \
+        if rows.dim() != 3 or rows.shape[1] != h2 * w2 + h3 * w3 or rows.shape[2] != 256 or rows.dtype != F32 \
                 or not rows.is_contiguous():
             raise ValueError(f'projected coarse levels {tuple(rows.shape)} inconsistent with {level_hw}')
         self.rows, self.level_hw = rows, [(int(h2), int(w2)), (int(h3), int(w3))]
@@ -380,7 +387,6 @@ def cross_attn_agg_coarse_fwd(plan, coarse, agg=None, pagg=None):
     """gd4d_cross_attn_agg_items_coarse_fwd: levels 0, 1 gathered raw from the Plan's pyramid, levels 2, 3 from `coarse`
     (CoarseValues of THIS layer's value_proj).  Returns agg (B, Q, 8, 256), pagg (B, Q, 256); plan.wsum holds the fine levels'
     weight sums: value_proj_heads_fwd(agg, plan.wsum, W, b) + pagg is the layer's sampled value."""
-    lib = _lib.load()
     pyramid = plan.pyramid
     dev = pyramid.device
     b, q, hh, query_order = plan.b, plan.q, plan.num_heads, plan.order
@@ -389,53 +395,43 @@ def cross_attn_agg_coarse_fwd(plan, coarse, agg=None, pagg=None):
     if list(coarse.level_hw) != [tuple(x) for x in pyramid.level_hw[2:]] or coarse.rows.shape[0] != pyramid.rows \
             or coarse.rows.device != dev:
         raise ValueError('projected coarse levels do not belong to this pyramid')
-    f32 = torch.float32
     if agg is None:
-        agg = torch.empty(b, q, hh, 256, device=dev, dtype=f32)
+        agg = torch.empty(b, q, hh, 256, device=dev, dtype=F32)
     if pagg is None:
-        pagg = torch.empty(b, q, 256, device=dev, dtype=f32)
+        pagg = torch.empty(b, q, 256, device=dev, dtype=F32)
     ptrs = (ctypes.c_void_p * 4)(*pyramid.ptrs)
-    lv = (ctypes.c_int32 * 8)(*[int(x) for hw in pyramid.level_hw for x in hw])
+    lv = _levels(pyramid.level_hw)
     cs = (ctypes.c_int64 * 4)(*pyramid.cam_stride)
     pp = (ctypes.c_void_p * 2)(*coarse.ptrs)
     pcs = (ctypes.c_int64 * 2)(*coarse.cam_stride)
-    code = lib.gd4d_cross_attn_agg_items_coarse_fwd(
-        ptrs, lv, cs, pyramid.pix_stride, pyramid.slice_stride, pp, pcs, _dev(plan.buf, 'plan', torch.uint8), _dev(agg, 'agg', f32),
-        _dev(plan.wsum, 'wsum', f32), _dev(pagg, 'pagg', f32), b, pyramid.rows // b, q, hh, 256, 4, plan.points,
-        _lib.F32 if pyramid.dtype == torch.float32 else _lib.BF16,
-        None if query_order is None else _order_ptr(query_order, b * q), _stream())
-    _lib.check(code, 'gd4d_cross_attn_agg_items_coarse_fwd')
+    _call('gd4d_cross_attn_agg_items_coarse_fwd', ptrs, lv, cs, pyramid.pix_stride, pyramid.slice_stride, pp, pcs,
+          _dev(plan.buf, 'plan', U8), _dev(agg, 'agg', F32), _dev(plan.wsum, 'wsum', F32), _dev(pagg, 'pagg', F32), b, pyramid.rows // b, q,
+          hh, 256, 4, plan.points, _lib.F32 if pyramid.dtype == F32 else _lib.BF16, _order_ptr(query_order, b * q))
     return agg, pagg
 
 
 def value_proj_heads_fwd(agg, wsum, weight, bias=None, out=None):
     """gd4d_value_proj_heads_fwd: agg (..., Hh, 256), wsum (..., Hh) -> out (..., 256) = value_proj of the aggregates."""
-    lib = _lib.load()
     hh, c = agg.shape[-2], agg.shape[-1]
     m = agg.numel() // (hh * c)
-    f32 = torch.float32
     if out is None:
-        out = torch.empty(*agg.shape[:-2], c, device=agg.device, dtype=f32)
-    code = lib.gd4d_value_proj_heads_fwd(_dev(agg, 'agg', f32), _dev(wsum, 'wsum', f32), _dev(weight, 'weight', f32),
-                                         _opt(bias, 'bias'), _dev(out, 'out', f32), m, hh, c, _stream())
-    _lib.check(code, 'gd4d_value_proj_heads_fwd')
+        out = torch.empty(*agg.shape[:-2], c, device=agg.device, dtype=F32)
+    _call('gd4d_value_proj_heads_fwd', _dev(agg, 'agg', F32), _dev(wsum, 'wsum', F32), _dev(weight, 'weight', F32), _opt(bias, 'bias'),
+          _dev(out, 'out', F32), m, hh, c)
     return out
 
 
 def value_proj_heads_bwd(grad_out, weight, bias=None, num_heads=8, grad_agg=None, beta=None):
     """gd4d_value_proj_heads_bwd: grad_out (..., 256) -> grad_agg (..., Hh, 256) = W_h^T grad_out[.., h], beta (..., Hh) =
     <b_h, grad_out[.., h]> (zeros without a bias): the gradient of value_proj_heads_fwd w.r.t. agg and wsum."""
-    lib = _lib.load()
     c = grad_out.shape[-1]
     m = grad_out.numel() // c
-    f32 = torch.float32
     if grad_agg is None:
-        grad_agg = torch.empty(*grad_out.shape[:-1], num_heads, c, device=grad_out.device, dtype=f32)
+        grad_agg = torch.empty(*grad_out.shape[:-1], num_heads, c, device=grad_out.device, dtype=F32)
     if beta is None:
-        beta = torch.empty(*grad_out.shape[:-1], num_heads, device=grad_out.device, dtype=f32)
-    code = lib.gd4d_value_proj_heads_bwd(_dev(grad_out, 'grad_out', f32), _dev(weight, 'weight', f32), _opt(bias, 'bias'),
-                                         _dev(grad_agg, 'grad_agg', f32), _dev(beta, 'beta', f32), m, num_heads, c, _stream())
-    _lib.check(code, 'gd4d_value_proj_heads_bwd')
+        beta = torch.empty(*grad_out.shape[:-1], num_heads, device=grad_out.device, dtype=F32)
+    _call('gd4d_value_proj_heads_bwd', _dev(grad_out, 'grad_out', F32), _dev(weight, 'weight', F32), _opt(bias, 'bias'),
+          _dev(grad_agg, 'grad_agg', F32), _dev(beta, 'beta', F32), m, num_heads, c)
     return grad_agg, beta
 
 
@@ -444,21 +440,18 @@ def value_proj_heads_bwd_weight(grad_out, agg, wsum=None, want_bias=True, into=N
     grad_bias (256) or None): value_proj's gradients from the per-head aggregates of the forward pass.  into=(w_buf, b_buf):
     added to these instead."""
     lib = _lib.load()
-    f32 = torch.float32
     hh, c = agg.shape[-2], agg.shape[-1]
     m = grad_out.numel() // c
     if into is None:
-        gw = torch.empty(c, c, device=grad_out.device, dtype=f32)
-        gb = torch.empty(c, device=grad_out.device, dtype=f32) if want_bias else None
+        gw = torch.empty(c, c, device=grad_out.device, dtype=F32)
+        gb = torch.empty(c, device=grad_out.device, dtype=F32) if want_bias else None
     else:
         gw, gb = into[0], (into[1] if want_bias else None)
     wsb = int(lib.gd4d_value_proj_heads_bwd_weight_workspace_bytes())
-    ws = torch.empty(wsb, device=grad_out.device, dtype=torch.uint8)
-    code = lib.gd4d_value_proj_heads_bwd_weight(_dev(grad_out, 'grad_out', f32), _dev(agg, 'agg', f32),
-                                                _dev(wsum, 'wsum', f32) if want_bias else None, _dev(gw, 'grad_weight', f32),
-                                                _dev(gb, 'grad_bias', f32) if want_bias else None, _dev(ws, 'workspace'),
-                                                ctypes.c_size_t(wsb), m, hh, c, 0 if into is None else 1, _stream())
-    _lib.check(code, 'gd4d_value_proj_heads_bwd_weight')
+    ws = torch.empty(wsb, device=grad_out.device, dtype=U8)
+    _call('gd4d_value_proj_heads_bwd_weight', _dev(grad_out, 'grad_out', F32), _dev(agg, 'agg', F32),
+          _dev(wsum, 'wsum', F32) if want_bias else None, _dev(gw, 'grad_weight', F32), _dev(gb, 'grad_bias', F32) if want_bias else None,
+          _dev(ws, 'workspace'), ctypes.c_size_t(wsb), m, hh, c, 0 if into is None else 1)
     return gw, gb
 
 
@@ -467,20 +460,16 @@ def value_proj_heads_bwd_weight_group(problems, accumulate=True):
     grad_weight (256, 256), grad_bias (256) or None) - value_proj's gradients of several layers in one pair of launches, added to
     (accumulate) or written into the targets."""
     lib = _lib.load()
-    f32 = torch.float32
     n = len(problems)
     hh, c = problems[0][1].shape[-2], problems[0][1].shape[-1]
     dev = problems[0][0].device
     nbytes = n * int(lib.gd4d_value_proj_heads_bwd_weight_workspace_bytes())
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)             # (scratch of this call only: see _vp_workspace)
-    arr = lambda v: (ctypes.c_void_p * n)(*v)          # noqa: E731
-    rows = (ctypes.c_int32 * n)(*[int(g.numel() // c) for g, _, _, _, _ in problems])
-    code = lib.gd4d_value_proj_heads_bwd_weight_group(
-        arr([_dev(g, 'grad_out', f32).value for g, _, _, _, _ in problems]), arr([_dev(a, 'agg', f32).value for _, a, _, _, _ in problems]),
-        arr([_dev(w, 'wsum', f32).value for _, _, w, _, _ in problems]), arr([_dev(gw, 'grad_weight', f32).value for _, _, _, gw, _ in problems]),
-        arr([None if gb is None else _dev(gb, 'grad_bias', f32).value for _, _, _, _, gb in problems]), rows, n,
-        _dev(ws, 'workspace'), ctypes.c_size_t(nbytes), hh, c, 1 if accumulate else 0, _stream())
-    _lib.check(code, 'gd4d_value_proj_heads_bwd_weight_group')
+    ws = torch.empty(nbytes, device=dev, dtype=U8)             # (scratch of this call only: see _vp_workspace)
+    gos, aggs, wsums, gws, gbs = zip(*problems)
+    rows = (ctypes.c_int32 * n)(*[int(g.numel() // c) for g in gos])
+    _call('gd4d_value_proj_heads_bwd_weight_group', _ptrs(gos, 'grad_out'), _ptrs(aggs, 'agg'), _ptrs(wsums, 'wsum'),
+          _ptrs(gws, 'grad_weight'), _ptrs(gbs, 'grad_bias', optional=True), rows, n, _dev(ws, 'workspace'), ctypes.c_size_t(nbytes), hh, c,
+          1 if accumulate else 0)
 
 
 def cross_attn_dot_bytes(b, n, q, num_heads, points=4):
@@ -489,19 +478,17 @@ def cross_attn_dot_bytes(b, n, q, num_heads, points=4):
 
 def _wgrad_arrays(problems):
     """The C arrays of gd4d_linear_bwd_weight_group for problems = [(x (M, K), grad_y (M, N), grad_w (N, K), grad_b (N) or None)]."""
-    f32 = torch.float32
     n = len(problems)
-    xs, gys, gws, gbs, dims = [], [], [], [], []
+    dims = []
     for x, gy, gw, gb in problems:
         k, nn_ = x.shape[-1], gy.shape[-1]
         m = x.numel() // k
         if gy.numel() // nn_ != m or tuple(gw.shape) != (nn_, k) or (gb is not None and gb.numel() != nn_):
             raise ValueError('weight-gradient group: inconsistent shapes')
-        xs.append(_dev(x, 'x', f32).value); gys.append(_dev(gy, 'grad_y', f32).value); gws.append(_dev(gw, 'grad_w', f32).value)
-        gbs.append(_dev(gb, 'grad_b', f32).value if gb is not None else None)
         dims += [m, k, nn_, k, nn_]
-    arr = lambda v: (ctypes.c_void_p * n)(*v)          # noqa: E731
-    return arr(xs), arr(gys), arr(gws), arr(gbs), (ctypes.c_int32 * (5 * n))(*dims), n
+    xs, gys, gws, gbs = zip(*problems) if n else [()] * 4
+    return (_ptrs(xs, 'x'), _ptrs(gys, 'grad_y'), _ptrs(gws, 'grad_w'), _ptrs(gbs, 'grad_b', optional=True),
+            (ctypes.c_int32 * (5 * n))(*dims), n)
 
 
 def cross_attn_dot_sliced(plan, grad_agg, dpart=None, wgrads=None):
@@ -517,29 +504,23 @@ def cross_attn_dot_sliced(plan, grad_agg, dpart=None, wgrads=None):
     nl = len(pyramid.level_hw)
     nbytes = int(lib.gd4d_cross_attn_dot_bytes(b, n, q, hh, plan.points))
     if dpart is None:
-        dpart = torch.empty(nbytes, device=pyramid.device, dtype=torch.uint8)
+        dpart = torch.empty(nbytes, device=pyramid.device, dtype=U8)
     ptrs = (ctypes.c_void_p * nl)(*pyramid.ptrs)
     if wgrads:
         xs, gys, gws, gbs, dims, cnt = _wgrad_arrays(wgrads)
-        code = lib.gd4d_cross_attn_dot_sliced_wgrad(
-            ptrs, pyramid.slice_stride, _dev(plan.buf, 'plan', torch.uint8), _dev(grad_agg, 'grad_agg', torch.float32),
-            _dev(dpart, 'dpart', torch.uint8), dpart.numel(), b, n, q, hh, 256, nl, plan.points,
-            _lib.F32 if pyramid.dtype == torch.float32 else _lib.BF16,
-            None if plan.order is None else _order_ptr(plan.order, b * q), xs, gys, gws, gbs, dims, cnt, 1, _stream())
-        _lib.check(code, 'gd4d_cross_attn_dot_sliced_wgrad')
+        _call('gd4d_cross_attn_dot_sliced_wgrad', ptrs, pyramid.slice_stride, _dev(plan.buf, 'plan', U8), _dev(grad_agg, 'grad_agg', F32),
+              _dev(dpart, 'dpart', U8), dpart.numel(), b, n, q, hh, 256, nl, plan.points, _lib.F32 if pyramid.dtype == F32 else _lib.BF16,
+              _order_ptr(plan.order, b * q), xs, gys, gws, gbs, dims, cnt, 1)
         return dpart
-    code = lib.gd4d_cross_attn_dot_sliced(
-        ptrs, pyramid.slice_stride, _dev(plan.buf, 'plan', torch.uint8), _dev(grad_agg, 'grad_agg', torch.float32),
-        _dev(dpart, 'dpart', torch.uint8), dpart.numel(), b, n, q, hh, 256, nl, plan.points,
-        _lib.F32 if pyramid.dtype == torch.float32 else _lib.BF16,
-        None if plan.order is None else _order_ptr(plan.order, b * q), _stream())
-    _lib.check(code, 'gd4d_cross_attn_dot_sliced')
+    _call('gd4d_cross_attn_dot_sliced', ptrs, pyramid.slice_stride, _dev(plan.buf, 'plan', U8), _dev(grad_agg, 'grad_agg', F32),
+          _dev(dpart, 'dpart', U8), dpart.numel(), b, n, q, hh, 256, nl, plan.points, _lib.F32 if pyramid.dtype == F32 else _lib.BF16,
+          _order_ptr(plan.order, b * q))
     return dpart
 
 
 def wgrads_ride_with(plan):
     """Whether cross_attn_dot_sliced(plan, ..., wgrads=...) has a launch for this plan's shape."""
-    return plan.num_heads == 8 and len(plan.pyramid.level_hw) == 4 and plan.pyramid.dtype == torch.float32
+    return plan.num_heads == 8 and len(plan.pyramid.level_hw) == 4 and plan.pyramid.dtype == F32
 
 
 def cross_attn_plan_bwd(plan, dpart, beta, ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w,
@@ -548,30 +529,23 @@ def cross_attn_plan_bwd(plan, dpart, beta, ref, offsets, attn_logits, cam_logits
     Returns (grad_ref, grad_offsets, grad_attn_logits, grad_cam_logits) - what cross_attn_bwd returns after grad_value."""
     lib = _lib.load()
     plan.need_pairs('gd4d_cross_attn_plan_bwd')
-    f32 = torch.float32
     b, q, hh = plan.b, plan.q, plan.num_heads
     n = lidar2img.shape[1]
     p = offsets.shape[3]
     level_hw = plan.pyramid.level_hw
     nl = len(level_hw)
     dev = ref.device
-    gr = torch.empty(b, q, 3, device=dev, dtype=f32)
-    go = torch.empty(b, q, hh, p, 3, device=dev, dtype=f32)
-    ga = torch.empty(b, q, hh, nl, p, device=dev, dtype=f32)
-    gc = torch.empty(b, q, n, device=dev, dtype=f32)
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for hw in level_hw for x in hw])
-    rng = (ctypes.c_double * 6)(*[float(x) for x in pc_range])
+    gr = torch.empty(b, q, 3, device=dev, dtype=F32)
+    go = torch.empty(b, q, hh, p, 3, device=dev, dtype=F32)
+    ga = torch.empty(b, q, hh, nl, p, device=dev, dtype=F32)
+    gc = torch.empty(b, q, n, device=dev, dtype=F32)
     nbytes = lib.gd4d_cross_attn_bwd_workspace_bytes(b, q, hh, nl, p)
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
-    code = lib.gd4d_cross_attn_plan_bwd(
-        _dev(ref, 'ref', f32), _dev(offsets, 'offsets', f32), _dev(attn_logits, 'attn_logits', f32),
-        _dev(cam_logits, 'cam_logits', f32), _dev(lidar2img, 'lidar2img', f32), rng, float(img_h), float(img_w), lv,
-        _dev(plan.buf, 'plan', torch.uint8), _dev(dpart, 'dpart', torch.uint8), _opt(beta, 'beta'), _dev(gr, 'grad_ref'),
-        _dev(go, 'grad_offsets'), _dev(ga, 'grad_attn_logits'), _dev(gc, 'grad_cam_logits'),
-        None if ws is None else _dev(ws, 'workspace'), ctypes.c_size_t(nbytes),
-        None if status is None else _dev(status, 'status', torch.int32), b, n, q, hh, nl, p, 1 if raw_cam_weights else 0,
-        None if plan.order is None else _order_ptr(plan.order, b * q), _stream())
-    _lib.check(code, 'gd4d_cross_attn_plan_bwd')
+    ws = torch.empty(nbytes, device=dev, dtype=U8) if nbytes else None
+    _call('gd4d_cross_attn_plan_bwd', *_camera_args(ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w),
+          _levels(level_hw), _dev(plan.buf, 'plan', U8), _dev(dpart, 'dpart', U8), _opt(beta, 'beta'), _dev(gr, 'grad_ref'),
+          _dev(go, 'grad_offsets'), _dev(ga, 'grad_attn_logits'), _dev(gc, 'grad_cam_logits'), _opt(ws, 'workspace', None),
+          ctypes.c_size_t(nbytes), _opt(status, 'status', I32), b, n, q, hh, nl, p, 1 if raw_cam_weights else 0,
+          _order_ptr(plan.order, b * q))
     return gr, go, ga, gc
 
 
@@ -591,7 +565,7 @@ def _chunk_walk(level_hw, rows, device, regions=(6, 10)):
         return hit
     lib = _lib.load()
     nl = len(level_hw)
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for hw in level_hw for x in hw])
+    lv = _levels(level_hw)
     geo = (ctypes.c_int32 * (5 * nl))()
     _lib.check(lib.gd4d_pyramid_grad_chunk_geometry(lv, int(rows), nl, geo), 'gd4d_pyramid_grad_chunk_geometry')
     keys, ids = [], []
@@ -626,12 +600,12 @@ class PyramidGrad:
         lib = _lib.load()
         self.n = pyramid.rows // self.b
         nl = len(pyramid.level_hw)
-        self._lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for hw in pyramid.level_hw for x in hw])
+        self._lv = _levels(pyramid.level_hw)
         self._cs = (ctypes.c_int64 * nl)(*pyramid.cam_stride)
         self.chunks = int(lib.gd4d_pyramid_grad_chunks(self._lv, pyramid.rows, nl))
         if self.chunks <= 0:
             raise _lib.Gd4dError('gd4d_pyramid_grad_chunks: unsupported pyramid')
-        self.count = torch.zeros(self.chunks, device=dev, dtype=torch.int32)
+        self.count = torch.zeros(self.chunks, device=dev, dtype=I32)
         self._scanned, self._riding = None, []
         self.table, self.layer_q = None, {}
         if self.layers > 0:
@@ -655,7 +629,7 @@ class PyramidGrad:
             self.row_base.append(self.row_base[-1] + self.b * q * self.hh)
         if self.row_base[-1] >= 1 << 26:
             raise _lib.Gd4dError('PyramidGrad: more than 2^26 table rows (a record keeps its row in 26 bits)')
-        self.table = torch.zeros(max(self.row_base[-1], 1), 256, device=self.pyramid.device, dtype=torch.float32)
+        self.table = torch.zeros(max(self.row_base[-1], 1), 256, device=self.pyramid.device, dtype=F32)
 
     def grad_agg_rows(self, layer):
         """(B, Q_layer, Hh, 256) view of the table: where layer `layer`'s gd4d_value_proj_heads_bwd writes."""
@@ -665,13 +639,11 @@ class PyramidGrad:
         """Hand every record of `plan` its slot (the plan is kept until finish(): its buffer must not be overwritten).  The
         plan's own (B, Q, Hh) say where its pairs are; B and Hh must be the sink's (they fix the pyramid rows / the table's
         row width), Q is per layer."""
-        lib = _lib.load()
         slots, slot_bytes = self.begin_layer(layer, plan)
         layer = int(layer)
-        code = lib.gd4d_pyramid_grad_count(_dev(plan.buf, 'plan', torch.uint8), self._lv, self._cs, self.pyramid.pix_stride,
-                                           _dev(self.count, 'count', torch.int32), _dev(slots, 'slots'), ctypes.c_size_t(slot_bytes),
-                                           self.b, self.n, plan.q, self.hh, len(self.pyramid.level_hw), plan.points, _stream())
-        _lib.check(code, 'gd4d_pyramid_grad_count')
+        _call('gd4d_pyramid_grad_count', _dev(plan.buf, 'plan', U8), self._lv, self._cs, self.pyramid.pix_stride,
+              _dev(self.count, 'count', I32), _dev(slots, 'slots'), ctypes.c_size_t(slot_bytes), self.b, self.n, plan.q, self.hh,
+              len(self.pyramid.level_hw), plan.points)
         self.plans.append((layer, plan, slots))
 
     def begin_layer(self, layer, plan):
@@ -687,11 +659,10 @@ class PyramidGrad:
             raise _lib.Gd4dError(f'PyramidGrad: layer {layer} has {plan.q} queries, the table was made for '
                                  f'{self.table_q[layer] if layer < self.layers else "fewer layers"}')
         self.layer_q[layer] = plan.q
-        lib = _lib.load()
         if plan.points != self.points:
             raise _lib.Gd4dError(f'PyramidGrad: a plan with {plan.points} points per head handed to a sink made for {self.points}')
         slot_bytes = int(lib.gd4d_pyramid_grad_slots_bytes(self.b, self.n, plan.q, self.hh, plan.points))
-        slots = torch.empty(slot_bytes, device=self.pyramid.device, dtype=torch.uint8)
+        slots = torch.empty(slot_bytes, device=self.pyramid.device, dtype=U8)
         return slots, slot_bytes
 
     def prepare(self):
@@ -706,17 +677,15 @@ class PyramidGrad:
         mha_core_bwd(fills=...)); finish_prepare() launches whatever is left of them, and the sort."""
         lib = _lib.load()
         dev = self.pyramid.device
-        i32 = torch.int32
-        start = torch.empty(self.chunks, device=dev, dtype=i32)
+        start = torch.empty(self.chunks, device=dev, dtype=I32)
         wsb = int(lib.gd4d_pyramid_grad_scan_workspace_bytes(self.chunks))
-        ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
-        code = lib.gd4d_pyramid_grad_scan(_dev(self.count, 'count', i32), _dev(start, 'start', i32), _dev(ws, 'workspace'),
-                                          ctypes.c_size_t(wsb), self.chunks, _stream())
-        _lib.check(code, 'gd4d_pyramid_grad_scan')
+        ws = torch.empty(wsb, device=dev, dtype=U8)
+        _call('gd4d_pyramid_grad_scan', _dev(self.count, 'count', I32), _dev(start, 'start', I32), _dev(ws, 'workspace'),
+              ctypes.c_size_t(wsb), self.chunks)
         if self.table is None:
             raise _lib.Gd4dError('PyramidGrad.prepare: alloc_table() first (the records carry table rows)')
         nbytes = max(sum(slots.numel() for _, _, slots in self.plans), self.slot_bytes)
-        self._scanned = (start, torch.empty(nbytes, device=dev, dtype=torch.uint8), nbytes)
+        self._scanned = (start, torch.empty(nbytes, device=dev, dtype=U8), nbytes)
         for layer, plan, slots in self.plans:
             if layer >= self.layers or self.table_q[layer] != plan.q:
                 raise _lib.Gd4dError(f'PyramidGrad: layer {layer} ({plan.q} queries) does not match the table')
@@ -734,21 +703,16 @@ class PyramidGrad:
         return jobs, start, records, self.b, self.n, self.hh
 
     def finish_prepare(self):
-        lib = _lib.load()
         dev = self.pyramid.device
-        i32 = torch.int32
         start, records, nbytes = self._scanned
         for layer, plan, slots in self.plans:
-            code = lib.gd4d_pyramid_grad_fill(
-                _dev(plan.buf, 'plan', torch.uint8), _dev(slots, 'slots'), _dev(start, 'start', i32), _dev(records, 'records'),
-                self.row_base[layer], None if plan.order is None else _order_ptr(plan.order, self.b * plan.q),
-                self.b, self.n, plan.q, self.hh, plan.points, _stream())
-            _lib.check(code, 'gd4d_pyramid_grad_fill')
-        sorted_ = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        pxoff = torch.empty(self.chunks, 65, device=dev, dtype=i32)
-        code = lib.gd4d_pyramid_grad_sort(_dev(self.count, 'count', i32), _dev(start, 'start', i32), _dev(records, 'records'),
-                                          _dev(sorted_, 'sorted'), _dev(pxoff, 'pxoff', i32), self.chunks, _stream())
-        _lib.check(code, 'gd4d_pyramid_grad_sort')
+            _call('gd4d_pyramid_grad_fill', _dev(plan.buf, 'plan', U8), _dev(slots, 'slots'), _dev(start, 'start', I32),
+                  _dev(records, 'records'), self.row_base[layer], _order_ptr(plan.order, self.b * plan.q), self.b, self.n, plan.q, self.hh,
+                  plan.points)
+        sorted_ = torch.empty(nbytes, device=dev, dtype=U8)
+        pxoff = torch.empty(self.chunks, 65, device=dev, dtype=I32)
+        _call('gd4d_pyramid_grad_sort', _dev(self.count, 'count', I32), _dev(start, 'start', I32), _dev(records, 'records'),
+              _dev(sorted_, 'sorted'), _dev(pxoff, 'pxoff', I32), self.chunks)
         self.prepared = (start, pxoff, sorted_)
         self.plans = []
         self._riding = []
@@ -758,22 +722,16 @@ class PyramidGrad:
         """-> L tensors (R, 256, H_l, W_l) fp32: the pyramid's gradient summed over the layers (prepare() first; the table
         rows of every layer must have been written).  channels_last: the tensors are stored (R, H_l, W_l, 256) - the layout of
         levels the gather read in place - and returned as (R, 256, H_l, W_l) views of that memory."""
-        lib = _lib.load()
         py = self.pyramid
         nl = len(py.level_hw)
-        i32 = torch.int32
         start, pxoff, sorted_ = self.prepared
         if grads is None:
-            grads = [torch.empty((py.rows, h, w, 256) if channels_last else (py.rows, 256, h, w), device=py.device, dtype=torch.float32)
+            grads = [torch.empty((py.rows, h, w, 256) if channels_last else (py.rows, 256, h, w), device=py.device, dtype=F32)
                      for h, w in py.level_hw]
-        for g in grads:
-            _dev(g, 'grads', torch.float32)
-        ptrs = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in grads])
-        code = lib.gd4d_pyramid_grad_reduce(_dev(start, 'start', i32), _dev(pxoff, 'pxoff', i32), _dev(sorted_, 'sorted'),
-                                            _dev(self.table, 'table', torch.float32), ptrs, self._lv,
-                                            None if self.order is None else _dev(self.order, 'chunk_order', i32), py.rows, 256, nl,
-                                            1 if channels_last else 0, _stream())
-        _lib.check(code, 'gd4d_pyramid_grad_reduce')
+        ptrs = _ptrs(grads, 'grads')
+        _call('gd4d_pyramid_grad_reduce', _dev(start, 'start', I32), _dev(pxoff, 'pxoff', I32), _dev(sorted_, 'sorted'),
+              _dev(self.table, 'table', F32), ptrs, self._lv, _opt(self.order, 'chunk_order', I32), py.rows, 256, nl,
+              1 if channels_last else 0)
         self.prepared = None
         return [g.permute(0, 3, 1, 2) for g in grads] if channels_last else grads
 
@@ -783,21 +741,27 @@ class PyramidGrad:
 
 
 def _order_ptr(order, count):
-    if order.dtype != torch.int32 or order.numel() != count:
+    if order is None:
+        return None
+    if order.dtype != I32 or order.numel() != count:
         raise ValueError(f'query_order must be an int32 permutation of {count} entries')
     return _dev(order, 'query_order')
 
 
 def query_order_fwd(ref, pc_range, out=None):
     """gd4d_query_order_fwd: ref (B,Q,3) in [0,1] -> int32 (B*Q) locality order for cross_attn_fwd(query_order=)."""
-    lib = _lib.load()
     b, q = ref.shape[0], ref.shape[1]
     if out is None:
-        out = torch.empty(b * q, device=ref.device, dtype=torch.int32)
-    rng = (ctypes.c_double * 6)(*[float(x) for x in pc_range])
-    code = lib.gd4d_query_order_fwd(_dev(ref, 'ref', torch.float32), rng, _order_ptr(out, b * q), b, q, _stream())
-    _lib.check(code, 'gd4d_query_order_fwd')
+        out = torch.empty(b * q, device=ref.device, dtype=I32)
+    _call('gd4d_query_order_fwd', _dev(ref, 'ref', F32), _range6(pc_range), _order_ptr(out, b * q), b, q)
     return out
+
+
+def _detr3d_args(feats, ref, attn_logits, lidar2img, pc_range, img_h, img_w, offsets=None):
+    """The leading arguments the four detr3d entry points share (offsets: the v2 pair's, after attn_logits), for *-splicing."""
+    off = () if offsets is None else (_dev(offsets, 'offsets', F32),)
+    return (_ptrs(feats, 'feats'), _levels(feats), _dev(ref, 'ref', F32), _dev(attn_logits, 'attn_logits', F32), *off,
+            _dev(lidar2img, 'lidar2img', F32), _range6(pc_range), float(img_h), float(img_w))
 
 
 def detr3d_fwd(feats, ref, attn_logits, lidar2img, pc_range, img_h, img_w, want_out=True,
@@ -806,71 +770,46 @@ def detr3d_fwd(feats, ref, attn_logits, lidar2img, pc_range, img_h, img_w, want_
     ref (B,Q,3); attn_logits (B,Q,N,1,L) (any shape with B*Q*N*L elements in that order).
     Returns a dict with the requested 'out' (B,Q,C), 'mask' (B,N,Q) uint8,
     'sampled' (B,C,Q,N,1,L)."""
-    lib = _lib.load()
     b, n, c = feats[0].shape[:3]
     q = ref.shape[1]
     nl = len(feats)
     if attn_logits.numel() != b * q * n * nl:
         raise ValueError('attn_logits must have B*Q*N*L elements (num_points must be 1)')
-    f32 = torch.float32
-    ptrs = (ctypes.c_void_p * nl)(*[_dev(f, f'feats[{i}]', f32).value for i, f in enumerate(feats)])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in feats for x in f.shape[-2:]])
-    rng = (ctypes.c_double * 6)(*[float(x) for x in pc_range])
     dev = ref.device
-    out = torch.empty(b, q, c, device=dev, dtype=f32) if want_out else None
-    mask = torch.empty(b, n, q, device=dev, dtype=torch.uint8) if want_mask else None
-    sampled = torch.empty(b, c, q, n, 1, nl, device=dev, dtype=f32) if want_sampled else None
-    code = lib.gd4d_detr3d_fwd(
-        ptrs, lv, _dev(ref, 'ref', f32), _dev(attn_logits, 'attn_logits', f32),
-        _dev(lidar2img, 'lidar2img', f32), rng, float(img_h), float(img_w),
-        _dev(out, 'out') if want_out else None, _dev(mask, 'mask') if want_mask else None,
-        _dev(sampled, 'sampled') if want_sampled else None, b, n, q, c, nl, 1, _stream())
-    _lib.check(code, 'gd4d_detr3d_fwd')
+    out = torch.empty(b, q, c, device=dev, dtype=F32) if want_out else None
+    mask = torch.empty(b, n, q, device=dev, dtype=U8) if want_mask else None
+    sampled = torch.empty(b, c, q, n, 1, nl, device=dev, dtype=F32) if want_sampled else None
+    _call('gd4d_detr3d_fwd', *_detr3d_args(feats, ref, attn_logits, lidar2img, pc_range, img_h, img_w), _opt(out, 'out', None),
+          _opt(mask, 'mask', None), _opt(sampled, 'sampled', None), b, n, q, c, nl, 1)
     return dict(out=out, mask=mask, sampled=sampled)
 
 
 def detr3d_bwd(feats, ref, attn_logits, lidar2img, pc_range, img_h, img_w, grad_out, want_feats=True, want_ref=True):
     """gd4d_detr3d_bwd: gradients of detr3d_fwd(...)['out'].  Returns (grad_feats: list like feats or None,
     grad_logits like attn_logits, grad_ref (B, Q, 3) or None)."""
-    lib = _lib.load()
     b, n, c = feats[0].shape[:3]
     q = ref.shape[1]
     nl = len(feats)
-    f32 = torch.float32
-    ptrs = (ctypes.c_void_p * nl)(*[_dev(f, f'feats[{i}]', f32).value for i, f in enumerate(feats)])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in feats for x in f.shape[-2:]])
-    rng = (ctypes.c_double * 6)(*[float(x) for x in pc_range])
     gf = [torch.zeros_like(f) for f in feats] if want_feats else None
-    gptrs = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gf]) if want_feats else None
-    gl = torch.empty(b * q * n * nl, device=ref.device, dtype=f32).view_as(attn_logits)
-    gr = torch.empty(b, q, 3, device=ref.device, dtype=f32) if want_ref else None
-    code = lib.gd4d_detr3d_bwd(ptrs, lv, _dev(ref, 'ref', f32), _dev(attn_logits, 'attn_logits', f32),
-                               _dev(lidar2img, 'lidar2img', f32), rng, float(img_h), float(img_w), _dev(grad_out, 'grad_out', f32),
-                               gptrs, _dev(gl, 'grad_logits'), _dev(gr, 'grad_ref') if want_ref else None, b, n, q, c, nl, 1, _stream())
-    _lib.check(code, 'gd4d_detr3d_bwd')
+    gl = torch.empty(b * q * n * nl, device=ref.device, dtype=F32).view_as(attn_logits)
+    gr = torch.empty(b, q, 3, device=ref.device, dtype=F32) if want_ref else None
+    _call('gd4d_detr3d_bwd', *_detr3d_args(feats, ref, attn_logits, lidar2img, pc_range, img_h, img_w), _dev(grad_out, 'grad_out', F32),
+          _ptrs(gf, 'grad_feats') if want_feats else None, _dev(gl, 'grad_logits'), _opt(gr, 'grad_ref', None), b, n, q, c, nl, 1)
     return gf, gl, gr
 
 
 def detr3d_v2_fwd(feats, ref, attn_logits, offsets, lidar2img, pc_range, img_h, img_w, num_heads, want_mask=False):
     """gd4d_detr3d_v2_fwd.  feats: list of L tensors (B, N, C, H_l, W_l) fp32; attn_logits (B, Q, N, Hh, L*P);
     offsets (B, Q, N, Hh, L, P, 2), P == L.  Returns out (B, Q, C) [, mask (B, N, Q) uint8]."""
-    lib = _lib.load()
     b, n, c = feats[0].shape[:3]
     q = ref.shape[1]
     nl = len(feats)
     if attn_logits.numel() != b * q * n * num_heads * nl * nl or offsets.numel() != 2 * attn_logits.numel():
         raise ValueError('attn_logits / offsets must be (B, Q, N, heads, L*P) / (..., L, P, 2) with P == L')
-    f32 = torch.float32
-    ptrs = (ctypes.c_void_p * nl)(*[_dev(f, f'feats[{i}]', f32).value for i, f in enumerate(feats)])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in feats for x in f.shape[-2:]])
-    rng = (ctypes.c_double * 6)(*[float(x) for x in pc_range])
-    out = torch.empty(b, q, c, device=ref.device, dtype=f32)
-    mask = torch.empty(b, n, q, device=ref.device, dtype=torch.uint8) if want_mask else None
-    code = lib.gd4d_detr3d_v2_fwd(ptrs, lv, _dev(ref, 'ref', f32), _dev(attn_logits, 'attn_logits', f32),
-                                  _dev(offsets, 'offsets', f32), _dev(lidar2img, 'lidar2img', f32), rng, float(img_h),
-                                  float(img_w), _dev(out, 'out'), _dev(mask, 'mask') if want_mask else None,
-                                  b, n, q, c, int(num_heads), nl, nl, _stream())
-    _lib.check(code, 'gd4d_detr3d_v2_fwd')
+    out = torch.empty(b, q, c, device=ref.device, dtype=F32)
+    mask = torch.empty(b, n, q, device=ref.device, dtype=U8) if want_mask else None
+    _call('gd4d_detr3d_v2_fwd', *_detr3d_args(feats, ref, attn_logits, lidar2img, pc_range, img_h, img_w, offsets), _dev(out, 'out'),
+          _opt(mask, 'mask', None), b, n, q, c, int(num_heads), nl, nl)
     return (out, mask) if want_mask else out
 
 
@@ -878,24 +817,16 @@ def detr3d_v2_bwd(feats, ref, attn_logits, offsets, lidar2img, pc_range, img_h, 
                   want_ref=True):
     """gd4d_detr3d_v2_bwd: the gradients of detr3d_v2_fwd's `out`.  Returns (grad_feats list or None, grad_attn_logits
     (B, Q, N, Hh, L*P), grad_offsets (B, Q, N, Hh, L, P, 2), grad_ref (B, Q, 3) or None).  C <= 256."""
-    lib = _lib.load()
     b, n, c = feats[0].shape[:3]
     q = ref.shape[1]
     nl = len(feats)
-    f32 = torch.float32
-    ptrs = (ctypes.c_void_p * nl)(*[_dev(f, f'feats[{i}]', f32).value for i, f in enumerate(feats)])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in feats for x in f.shape[-2:]])
-    rng = (ctypes.c_double * 6)(*[float(x) for x in pc_range])
     gfeats = [torch.zeros_like(f) for f in feats] if want_feats else None
-    gptrs = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gfeats]) if want_feats else None
-    gl = torch.empty(b, q, n, num_heads, nl * nl, device=ref.device, dtype=f32)
-    go = torch.empty(b, q, n, num_heads, nl, nl, 2, device=ref.device, dtype=f32)
-    gr = torch.empty(b, q, 3, device=ref.device, dtype=f32) if want_ref else None
-    code = lib.gd4d_detr3d_v2_bwd(ptrs, lv, _dev(ref, 'ref', f32), _dev(attn_logits, 'attn_logits', f32),
-                                  _dev(offsets, 'offsets', f32), _dev(lidar2img, 'lidar2img', f32), rng, float(img_h), float(img_w),
-                                  _dev(grad_out, 'grad_out', f32), gptrs, _dev(gl, 'grad_logits'), _dev(go, 'grad_offsets'),
-                                  _dev(gr, 'grad_ref') if want_ref else None, b, n, q, c, nl, int(num_heads), _stream())
-    _lib.check(code, 'gd4d_detr3d_v2_bwd')
+    gl = torch.empty(b, q, n, num_heads, nl * nl, device=ref.device, dtype=F32)
+    go = torch.empty(b, q, n, num_heads, nl, nl, 2, device=ref.device, dtype=F32)
+    gr = torch.empty(b, q, 3, device=ref.device, dtype=F32) if want_ref else None
+    _call('gd4d_detr3d_v2_bwd', *_detr3d_args(feats, ref, attn_logits, lidar2img, pc_range, img_h, img_w, offsets),
+          _dev(grad_out, 'grad_out', F32), _ptrs(gfeats, 'grad_feats') if want_feats else None, _dev(gl, 'grad_logits'),
+          _dev(go, 'grad_offsets'), _opt(gr, 'grad_ref', None), b, n, q, c, nl, int(num_heads))
     return gfeats, gl, go, gr
 
 
@@ -903,7 +834,7 @@ def _vp_workspace(nlayers, device):
     """Scratch for the weight fragments of a value_proj launch (rewritten by every call: stream-ordered, so a fresh
     tensor per call keeps concurrent launches on different streams apart; the caching allocator makes it free)."""
     nbytes = _lib.load().gd4d_value_proj_workspace_bytes(int(nlayers))
-    return torch.empty(nbytes, device=device, dtype=torch.uint8), nbytes
+    return torch.empty(nbytes, device=device, dtype=U8), nbytes
 
 
 def value_proj_fwd(feats, weight, bias, out_dtype=torch.float32, out=None, num_heads=8, head_major=False,
@@ -920,8 +851,6 @@ def value_proj_multi_fwd(feats, weights, biases, out_dtype=torch.float32, num_he
                          bf16_math=False, max_cus=0, outs=None):
     """gd4d_value_proj_multi_fwd: project the same pyramid with NL (weight, bias) pairs in one
     launch.  Returns a list of NL tensors (R, S, C) (or (R, Hh, S, C/Hh) with head_major=True)."""
-    lib = _lib.load()
-    f32 = torch.float32
     nlayers = len(weights)
     c = weights[0].shape[0]
     r = feats[0].numel() // (c * feats[0].shape[-1] * feats[0].shape[-2])
@@ -931,18 +860,14 @@ def value_proj_multi_fwd(feats, weights, biases, out_dtype=torch.float32, num_he
     if outs is None:
         outs = [torch.empty(*shape, device=weights[0].device, dtype=out_dtype) for _ in range(nlayers)]
     ws, nbytes = _vp_workspace(nlayers, weights[0].device)
-    ptrs = (ctypes.c_void_p * nl)(*[_dev(f, f'feats[{i}]', f32).value for i, f in enumerate(feats)])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in feats for x in f.shape[-2:]])
-    wp = (ctypes.c_void_p * nlayers)(*[_dev(w, 'weight', f32).value for w in weights])
-    bp = (ctypes.c_void_p * nlayers)(*[(_dev(b, 'bias', f32).value if b is not None else None)
-                                       for b in biases])
-    op = (ctypes.c_void_p * nlayers)(*[_dev(o, 'out').value for o in outs])
-    code = lib.gd4d_value_proj_multi_fwd(ptrs, lv, wp, bp, op, r, c, nl, nlayers, num_heads, _lib.F32,
-                                         _value_dtype(outs[0]),
-                                         _lib.HEAD_MAJOR if head_major else _lib.PIXEL_MAJOR,
-                                         int(bool(bf16_math)), _dev(ws, 'workspace'), ctypes.c_size_t(nbytes),
-                                         int(max_cus), _stream())
-    _lib.check(code, 'gd4d_value_proj_multi_fwd')
+    ptrs = _ptrs(feats, 'feats')
+    lv = _levels(feats)
+    wp = _ptrs(weights, 'weight')
+    bp = _ptrs(biases, 'bias', optional=True)
+    op = _ptrs(outs, 'out', None)
+    _call('gd4d_value_proj_multi_fwd', ptrs, lv, wp, bp, op, r, c, nl, nlayers, num_heads, _lib.F32, _value_dtype(outs[0]),
+          _lib.HEAD_MAJOR if head_major else _lib.PIXEL_MAJOR, int(bool(bf16_math)), _dev(ws, 'workspace'), ctypes.c_size_t(nbytes),
+          int(max_cus))
     return outs
 
 
@@ -950,54 +875,45 @@ def linear_bwd_weight(x, grad_y, want_bias=True, into=None):
     """gd4d_linear_bwd_weight.  x (..., K), grad_y (..., N) fp32 with the same leading shape (contiguous rows).
     Returns (grad_w (N, K), grad_b (N) or None).  into=(w_buf, b_buf or None): the sums are ADDED to these tensors (views
     of a flat gradient buffer) and returned."""
-    lib = _lib.load()
-    f32 = torch.float32
     k, n = x.shape[-1], grad_y.shape[-1]
     m = x.numel() // k
     if grad_y.numel() // n != m:
         raise ValueError('x and grad_y must have the same number of rows')
     if into is None:
-        gw = torch.empty(n, k, device=x.device, dtype=f32)
-        gb = torch.empty(n, device=x.device, dtype=f32) if want_bias else None
+        gw = torch.empty(n, k, device=x.device, dtype=F32)
+        gb = torch.empty(n, device=x.device, dtype=F32) if want_bias else None
     else:
         gw, gb = into
         if tuple(gw.shape) != (n, k) or (want_bias and (gb is None or gb.numel() != n)):
             raise ValueError('linear_bwd_weight: the accumulation targets do not match the gradient shapes')
         gb = gb if want_bias else None
-    code = lib.gd4d_linear_bwd_weight(_dev(x, 'x', f32), _dev(grad_y, 'grad_y', f32), _dev(gw, 'grad_w', f32),
-                                      _dev(gb, 'grad_b', f32) if gb is not None else None, m, k, n, k, n, 0 if into is None else 1,
-                                      _stream())
-    _lib.check(code, 'gd4d_linear_bwd_weight')
+    _call('gd4d_linear_bwd_weight', _dev(x, 'x', F32), _dev(grad_y, 'grad_y', F32), _dev(gw, 'grad_w', F32), _opt(gb, 'grad_b'), m, k, n, k,
+          n, 0 if into is None else 1)
     return gw, gb
 
 
 def linear_bwd_weight_group(problems, accumulate=True):
     """gd4d_linear_bwd_weight_group: problems = list (<= 16) of (x (M, K), grad_y (M, N), grad_w (N, K), grad_b (N) or None);
     the sums are added to (accumulate) or written into grad_w / grad_b.  One launch for all of them."""
-    lib = _lib.load()
     xs, gys, gws, gbs, dims, n = _wgrad_arrays(problems)
-    code = lib.gd4d_linear_bwd_weight_group(xs, gys, gws, gbs, dims, n, 1 if accumulate else 0, _stream())
-    _lib.check(code, 'gd4d_linear_bwd_weight_group')
+    _call('gd4d_linear_bwd_weight_group', xs, gys, gws, gbs, dims, n, 1 if accumulate else 0)
 
 
 def value_proj_bwd_input(grad_out, weight, shapes, grads=None, accumulate=False):
     """gd4d_value_proj_bwd_input.  grad_out (R, S, C) fp32; weight (C, C); shapes: per level (H_l, W_l).
     Returns the list of L gradients (R, C, H_l, W_l); with `grads` given they are written (accumulate=False) or added
     to (accumulate=True) in place."""
-    lib = _lib.load()
-    f32 = torch.float32
     c = weight.shape[0]
     r = grad_out.numel() // (c * sum(h * w for h, w in shapes))
     nl = len(shapes)
     if grads is None:
         if accumulate:
             raise ValueError('accumulate=True needs the tensors to add to')
-        grads = [torch.empty(r, c, h, w, device=grad_out.device, dtype=f32) for h, w in shapes]
-    ptrs = (ctypes.c_void_p * nl)(*[_dev(g, f'grads[{i}]', f32).value for i, g in enumerate(grads)])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for hw in shapes for x in hw])
-    code = lib.gd4d_value_proj_bwd_input(_dev(grad_out, 'grad_out', f32), _dev(weight, 'weight', f32), ptrs, lv,
-                                         r, c, nl, int(bool(accumulate)), _stream())
-    _lib.check(code, 'gd4d_value_proj_bwd_input')
+        grads = [torch.empty(r, c, h, w, device=grad_out.device, dtype=F32) for h, w in shapes]
+    ptrs = _ptrs(grads, 'grads')
+    lv = _levels(shapes)
+    _call('gd4d_value_proj_bwd_input', _dev(grad_out, 'grad_out', F32), _dev(weight, 'weight', F32), ptrs, lv, r, c, nl,
+          int(bool(accumulate)))
     return grads
 
 
@@ -1005,26 +921,19 @@ def value_proj_bwd_weight(grad_out, feats, want_bias=True):
     """gd4d_value_proj_bwd_weight.  grad_out (R, S, C) fp32; feats: the L NCHW levels the forward read.
     Returns (grad_weight (C, C), grad_bias (C) or None)."""
     lib = _lib.load()
-    f32 = torch.float32
     c = feats[0].shape[-3]
     nl = len(feats)
     r = feats[0].numel() // (c * feats[0].shape[-1] * feats[0].shape[-2])
     dev = grad_out.device
     nbytes = lib.gd4d_value_proj_bwd_weight_workspace_bytes()
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)             # (scratch of this call only: see _vp_workspace)
-    gw = torch.empty(c, c, device=dev, dtype=f32)
-    gb = torch.empty(c, device=dev, dtype=f32) if want_bias else None
-    ptrs = (ctypes.c_void_p * nl)(*[_dev(f, f'feats[{i}]', f32).value for i, f in enumerate(feats)])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in feats for x in f.shape[-2:]])
-    code = lib.gd4d_value_proj_bwd_weight(_dev(grad_out, 'grad_out', f32), ptrs, lv, _dev(gw, 'grad_weight'),
-                                          _dev(gb, 'grad_bias') if want_bias else None, _dev(ws, 'workspace'),
-                                          ctypes.c_size_t(nbytes), r, c, nl, _stream())
-    _lib.check(code, 'gd4d_value_proj_bwd_weight')
+    ws = torch.empty(nbytes, device=dev, dtype=U8)             # (scratch of this call only: see _vp_workspace)
+    gw = torch.empty(c, c, device=dev, dtype=F32)
+    gb = torch.empty(c, device=dev, dtype=F32) if want_bias else None
+    ptrs = _ptrs(feats, 'feats')
+    lv = _levels(feats)
+    _call('gd4d_value_proj_bwd_weight', _dev(grad_out, 'grad_out', F32), ptrs, lv, _dev(gw, 'grad_weight'), _opt(gb, 'grad_bias', None),
+          _dev(ws, 'workspace'), ctypes.c_size_t(nbytes), r, c, nl)
     return gw, gb
-
-
-def _opt(t, name):
-    return _dev(t, name, torch.float32) if t is not None else None
 
 
 def linear_fwd(x, weight, bias=None, x2=None, n_split=None, relu=False, r1=None, r2=None, out=None,
@@ -1032,7 +941,6 @@ def linear_fwd(x, weight, bias=None, x2=None, n_split=None, relu=False, r1=None,
     """gd4d_linear_fwd on the last dimension: y = act((x [+ x2 for cols < n_split]) W^T + b) [+r1] [+r2].
     x (..., K) contiguous - or 2-D with a row stride (a column slice of a wider buffer, e.g. the q|k part of a packed
     gradient); weight (N, K); residuals (..., N) contiguous.  Returns (..., N); with want_xsum (needs x2): (y, x + x2)."""
-    lib = _lib.load()
     k = x.shape[-1]
     n = weight.shape[1] if weight_kn else weight.shape[0]      # weight_kn: weight is (K, N) - y = x W (a Linear's dgrad)
     if weight_kn and weight.shape[0] != k:
@@ -1044,26 +952,23 @@ def linear_fwd(x, weight, bias=None, x2=None, n_split=None, relu=False, r1=None,
             raise ValueError('x must be contiguous, or 2-D with unit column stride (and no x2)')
         ldx = x.stride(0)
     if out is None:
-        out = torch.empty(*x.shape[:-1], n, device=x.device, dtype=torch.float32)
+        out = torch.empty(*x.shape[:-1], n, device=x.device, dtype=F32)
     if x2 is not None and x2.shape != x.shape:
         raise ValueError('x2 must have the shape of x')
     xsum = None
     if want_xsum:
         if x2 is None:
             raise ValueError('want_xsum needs x2')
-        xsum = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-    xptr = _dev(x, 'x', torch.float32) if ldx == k else _devptr_strided(x, 'x')
-    code = lib.gd4d_linear_fwd(xptr, _opt(x2, 'x2'), _dev(weight, 'weight', torch.float32),
-                               _opt(bias, 'bias'), _opt(r1, 'r1'), _opt(r2, 'r2'), _dev(out, 'out'),
-                               m, k, n, n if n_split is None else int(n_split),
-                               int(bool(relu)) | (2 if inv_sigmoid_in else 0) | (8 if weight_kn else 0),
-                               ldx, n, n, n, None if xsum is None else _dev(xsum, 'xsum'), _stream())
-    _lib.check(code, 'gd4d_linear_fwd')
+        xsum = torch.empty(x.shape, device=x.device, dtype=F32)
+    xptr = _dev(x, 'x', F32) if ldx == k else _devptr_strided(x, 'x')
+    _call('gd4d_linear_fwd', xptr, _opt(x2, 'x2'), _dev(weight, 'weight', F32), _opt(bias, 'bias'), _opt(r1, 'r1'), _opt(r2, 'r2'),
+          _dev(out, 'out'), m, k, n, n if n_split is None else int(n_split),
+          int(bool(relu)) | (2 if inv_sigmoid_in else 0) | (8 if weight_kn else 0), ldx, n, n, n, _opt(xsum, 'xsum', None))
     return (out, xsum) if want_xsum else out
 
 
 def _devptr_strided(t, name):
-    if not t.is_cuda or t.dtype != torch.float32:
+    if not t.is_cuda or t.dtype != F32:
         raise _lib.Gd4dError(f'{name}: fp32 device tensor expected, got {t.dtype} on {t.device}')
     return ctypes.c_void_p(t.data_ptr())
 
@@ -1071,7 +976,6 @@ def _devptr_strided(t, name):
 def linear_group_fwd(x, weights, biases, x2=None, want_xsum=False):
     """gd4d_linear_group_fwd: [(x + x2) W_g^T + b_g for g] in one launch.  x (..., K) contiguous; returns a list
     (want_xsum, needs x2: (list, x + x2))."""
-    lib = _lib.load()
     g = len(weights)
     k = x.shape[-1]
     m = x.numel() // k
@@ -1079,60 +983,44 @@ def linear_group_fwd(x, weights, biases, x2=None, want_xsum=False):
         raise ValueError('x2 must have the shape of x')
     if want_xsum and x2 is None:
         raise ValueError('want_xsum needs x2')
-    outs = [torch.empty(*x.shape[:-1], w.shape[0], device=x.device, dtype=torch.float32) for w in weights]
-    xsum = torch.empty(x.shape, device=x.device, dtype=torch.float32) if want_xsum else None
-    vp = ctypes.c_void_p
-    warr = (vp * g)(*[_dev(w, 'weight', torch.float32).value for w in weights])
-    barr = (vp * g)(*[None if b is None else _dev(b, 'bias', torch.float32).value for b in biases])
-    yarr = (vp * g)(*[o.data_ptr() for o in outs])
+    outs = [torch.empty(*x.shape[:-1], w.shape[0], device=x.device, dtype=F32) for w in weights]
+    xsum = torch.empty(x.shape, device=x.device, dtype=F32) if want_xsum else None
     narr = (ctypes.c_int32 * g)(*[w.shape[0] for w in weights])
-    code = lib.gd4d_linear_group_fwd(_dev(x, 'x', torch.float32), _opt(x2, 'x2'), warr, barr, yarr, narr, g, m, k, k,
-                                     None if xsum is None else _dev(xsum, 'xsum'), _stream())
-    _lib.check(code, 'gd4d_linear_group_fwd')
+    _call('gd4d_linear_group_fwd', _dev(x, 'x', F32), _opt(x2, 'x2'), _ptrs(weights, 'weight'), _ptrs(biases, 'bias', optional=True),
+          _ptrs(outs, 'out'), narr, g, m, k, k, _opt(xsum, 'xsum', None))
     return (outs, xsum) if want_xsum else outs
 
 
 def layernorm_fwd(x, gamma, beta, eps=1e-5, res=None, relu=False):
     """gd4d_layernorm_fwd over the last dimension of a contiguous tensor."""
-    lib = _lib.load()
     c = x.shape[-1]
     out = torch.empty_like(x)
-    code = lib.gd4d_layernorm_fwd(_dev(x, 'x', torch.float32), _opt(res, 'res'), _dev(gamma, 'gamma', torch.float32),
-                                  _dev(beta, 'beta', torch.float32), _dev(out, 'out'), x.numel() // c, c,
-                                  float(eps), int(bool(relu)), _stream())
-    _lib.check(code, 'gd4d_layernorm_fwd')
+    _call('gd4d_layernorm_fwd', _dev(x, 'x', F32), _opt(res, 'res'), _dev(gamma, 'gamma', F32), _dev(beta, 'beta', F32), _dev(out, 'out'),
+          x.numel() // c, c, float(eps), int(bool(relu)))
     return out
 
 
 def linear_ln_fwd(x, weight, bias=None, gamma=None, beta=None, eps=1e-5, x2=None, n_split=None, relu=False, r1=None,
                   r2=None, relu_after_ln=False, out=None):
     """gd4d_linear_ln_fwd: y = [ReLU] LN(act((x [+ x2]) W^T + b) + r1 + r2); gamma=None: no LayerNorm."""
-    lib = _lib.load()
     k, n = x.shape[-1], weight.shape[0]
     m = x.numel() // k
     if out is None:
-        out = torch.empty(*x.shape[:-1], n, device=x.device, dtype=torch.float32)
+        out = torch.empty(*x.shape[:-1], n, device=x.device, dtype=F32)
     if x2 is not None and x2.shape != x.shape:
         raise ValueError('x2 must have the shape of x')
-    code = lib.gd4d_linear_ln_fwd(_dev(x, 'x', torch.float32), _opt(x2, 'x2'), _dev(weight, 'weight', torch.float32),
-                                  _opt(bias, 'bias'), _opt(r1, 'r1'), _opt(r2, 'r2'), _opt(gamma, 'gamma'),
-                                  _opt(beta, 'beta'), _dev(out, 'out'), m, k, n, n if n_split is None else int(n_split),
-                                  int(bool(relu)) | (4 if relu_after_ln else 0), float(eps), k, n, n, n, _stream())
-    _lib.check(code, 'gd4d_linear_ln_fwd')
+    _call('gd4d_linear_ln_fwd', _dev(x, 'x', F32), _opt(x2, 'x2'), _dev(weight, 'weight', F32), _opt(bias, 'bias'), _opt(r1, 'r1'),
+          _opt(r2, 'r2'), _opt(gamma, 'gamma'), _opt(beta, 'beta'), _dev(out, 'out'), m, k, n, n if n_split is None else int(n_split),
+          int(bool(relu)) | (4 if relu_after_ln else 0), float(eps), k, n, n, n)
     return out
 
 
 def small_linear_layernorm_fwd(x, weight, bias, gamma, beta, eps=1e-5, relu=False, inv_sigmoid_in=False):
     """gd4d_small_linear_layernorm_fwd: [ReLU] LN(f(x) W^T + b) with x (..., K <= 4) -> (..., C)."""
-    lib = _lib.load()
     k, c = x.shape[-1], weight.shape[0]
-    out = torch.empty(*x.shape[:-1], c, device=x.device, dtype=torch.float32)
-    code = lib.gd4d_small_linear_layernorm_fwd(_dev(x, 'x', torch.float32), _dev(weight, 'weight', torch.float32),
-                                               _opt(bias, 'bias'), _dev(gamma, 'gamma', torch.float32),
-                                               _dev(beta, 'beta', torch.float32), _dev(out, 'out'), x.numel() // k, k,
-                                               c, float(eps), int(bool(relu)) | (2 if inv_sigmoid_in else 0),
-                                               _stream())
-    _lib.check(code, 'gd4d_small_linear_layernorm_fwd')
+    out = torch.empty(*x.shape[:-1], c, device=x.device, dtype=F32)
+    _call('gd4d_small_linear_layernorm_fwd', _dev(x, 'x', F32), _dev(weight, 'weight', F32), _opt(bias, 'bias'), _dev(gamma, 'gamma', F32),
+          _dev(beta, 'beta', F32), _dev(out, 'out'), x.numel() // k, k, c, float(eps), int(bool(relu)) | (2 if inv_sigmoid_in else 0))
     return out
 
 
@@ -1142,7 +1030,7 @@ def _mha_args(q, k, v, num_heads, attn_mask):
     d = c // num_heads
 
     def ld(t, name):
-        if not t.is_cuda or t.dtype != torch.float32:
+        if not t.is_cuda or t.dtype != F32:
             raise _lib.Gd4dError(f'{name} must be a float32 GPU tensor')
         if t.stride(2) != 1 or t.stride(0) != t.stride(1) * t.shape[1]:
             raise ValueError(f'{name} must be row-strided (L, B, C)')
@@ -1151,8 +1039,8 @@ def _mha_args(q, k, v, num_heads, attn_mask):
     if attn_mask is not None:
         if attn_mask.dim() != 2:
             raise NotImplementedError('only 2-D (Lq, Lk) attention masks are supported')
-        if attn_mask.dtype in (torch.bool, torch.uint8):
-            attn_mask, kind = attn_mask.to(torch.uint8), 1
+        if attn_mask.dtype in (torch.bool, U8):
+            attn_mask, kind = attn_mask.to(U8), 1
         else:
             attn_mask, kind = attn_mask.float(), 2
         attn_mask = attn_mask.contiguous()
@@ -1201,17 +1089,13 @@ def mha_core_fwd(q, k, v, num_heads, attn_mask=None, want_lse=False, dropout_p=0
     (L, B, 3C) in-projection buffer.  attn_mask: None, bool/uint8 (Lq, Lk) (nonzero = masked) or float
     additive (Lq, Lk).  Returns (Lq, B, C) [, lse (Lq, B, heads) with want_lse - what mha_core_bwd needs].
     dropout_p, seed (mha_dropout_seed): dropout of the probabilities, as nn.MultiheadAttention in training."""
-    lib = _lib.load()
     lq, lk, b, c, d, ld, kind, mptr, keep = _mha_args(q, k, v, num_heads, attn_mask)
     sptr = _mha_seed(dropout_p, seed, q.device)
-    out = torch.empty(lq, b, c, device=q.device, dtype=torch.float32)
-    lse = torch.empty(lq, b, num_heads, device=q.device, dtype=torch.float32) if want_lse else None
-    code = lib.gd4d_mha_core_fwd(ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(k.data_ptr()),
-                                 ctypes.c_void_p(v.data_ptr()), mptr, _dev(out, 'out'), lq, lk, b,
-                                 num_heads, d, ld(q, 'q'), ld(k, 'k'), ld(v, 'v'), c, kind,
-                                 1.0 / (d ** 0.5), None if lse is None else _dev(lse, 'lse'), float(dropout_p), sptr,
-                                 _stream())
-    _lib.check(code, 'gd4d_mha_core_fwd')
+    out = torch.empty(lq, b, c, device=q.device, dtype=F32)
+    lse = torch.empty(lq, b, num_heads, device=q.device, dtype=F32) if want_lse else None
+    _call('gd4d_mha_core_fwd', ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(v.data_ptr()), mptr,
+          _dev(out, 'out'), lq, lk, b, num_heads, d, ld(q, 'q'), ld(k, 'k'), ld(v, 'v'), c, kind, 1.0 / (d ** 0.5), _opt(lse, 'lse', None),
+          float(dropout_p), sptr)
     return (out, lse) if want_lse else out
 
 
@@ -1221,44 +1105,38 @@ class FillJob(ctypes.Structure):
                 ('id_base', ctypes.c_uint32), ('Q', ctypes.c_int32)]
 
 
+def _fill_args(fills):
+    """What a launch that carries `fills` (PyramidGrad.take_fills) takes for them: the job table, its length, start, records, B, N, Hh,
+    points per head."""
+    jobs, start, records, fb, fn, fhh = fills
+    arr = (FillJob * len(jobs))(*[FillJob(_dev(pl.buf, 'plan', U8).value, _dev(sl, 'slots').value,
+                                          _addr(_order_ptr(pl.order, fb * pl.q)) or None, int(base), int(pl.q)) for pl, sl, base in jobs])
+    return arr, len(jobs), _dev(start, 'start', I32), _dev(records, 'records'), fb, fn, fhh, int(jobs[0][0].points)
+
+
 def mha_core_bwd(q, k, v, out, grad_out, lse, num_heads, attn_mask=None, packed_qk=False, dropout_p=0., seed=None, fills=None):
     """gd4d_mha_core_bwd.  Returns (dq, dk, dv), each (L, B, C) contiguous; packed_qk (self-attention, q and k the two halves
     of one (L, B, 2C) projection): (dqk (L, B, 2C), dv) - the kernel writes both halves of one buffer.  dropout_p / seed:
     the forward's.  fills: what PyramidGrad.take_fills returned - one or two layers' record fills of the pyramid gradient ride
     in the dk / dv launch (gd4d_mha_core_bwd_fill)."""
-    lib = _lib.load()
     lq, lk, b, c, d, ld, kind, mptr, keep = _mha_args(q, k, v, num_heads, attn_mask)
     sptr = _mha_seed(dropout_p, seed, q.device)
-    f32 = torch.float32
     if packed_qk:
         if lq != lk:
             raise ValueError('packed_qk needs as many queries as keys')
-        dqk = torch.empty(lq, b, 2 * c, device=q.device, dtype=f32)
+        dqk = torch.empty(lq, b, 2 * c, device=q.device, dtype=F32)
         dq, dk, ldd = dqk[..., :c], dqk[..., c:], 2 * c
     else:
-        dq = torch.empty(lq, b, c, device=q.device, dtype=f32)
-        dk = torch.empty(lk, b, c, device=q.device, dtype=f32)
+        dq = torch.empty(lq, b, c, device=q.device, dtype=F32)
+        dk = torch.empty(lk, b, c, device=q.device, dtype=F32)
         ldd = c
-    dv = torch.empty(lk, b, c, device=q.device, dtype=f32)
-    dsum = torch.empty(lq, b, num_heads, device=q.device, dtype=f32)
+    dv = torch.empty(lk, b, c, device=q.device, dtype=F32)
+    dsum = torch.empty(lq, b, num_heads, device=q.device, dtype=F32)
     vp = lambda t: ctypes.c_void_p(t.data_ptr())    # noqa: E731
-    if fills is not None:
-        jobs, start, records, fb, fn, fhh = fills
-        arr = (FillJob * len(jobs))(*[FillJob(_dev(pl.buf, 'plan', torch.uint8).value, _dev(sl, 'slots').value,
-                                               None if pl.order is None else _order_ptr(pl.order, fb * pl.q).value, int(base), int(pl.q))
-                                       for pl, sl, base in jobs])
-        code = lib.gd4d_mha_core_bwd_fill(vp(q), vp(k), vp(v), _dev(out, 'out', f32), _dev(grad_out, 'grad_out', f32),
-                                          mptr, _dev(lse, 'lse', f32), _dev(dsum, 'dsum'), vp(dq), vp(dk),
-                                          _dev(dv, 'dv'), lq, lk, b, num_heads, d, ld(q, 'q'), ld(k, 'k'), ld(v, 'v'), c, c, ldd, ldd, c,
-                                          kind, 1.0 / (d ** 0.5), float(dropout_p), sptr, arr, len(jobs),
-                                          _dev(start, 'start', torch.int32), _dev(records, 'records'), fb, fn, fhh, int(jobs[0][0].points), _stream())
-        _lib.check(code, 'gd4d_mha_core_bwd_fill')
-        return (dqk, dv) if packed_qk else (dq, dk, dv)
-    code = lib.gd4d_mha_core_bwd(vp(q), vp(k), vp(v), _dev(out, 'out', f32), _dev(grad_out, 'grad_out', f32),
-                                 mptr, _dev(lse, 'lse', f32), _dev(dsum, 'dsum'), vp(dq), vp(dk),
-                                 _dev(dv, 'dv'), lq, lk, b, num_heads, d, ld(q, 'q'), ld(k, 'k'), ld(v, 'v'), c, c, ldd, ldd, c,
-                                 kind, 1.0 / (d ** 0.5), float(dropout_p), sptr, _stream())
-    _lib.check(code, 'gd4d_mha_core_bwd')
+    fargs = () if fills is None else _fill_args(fills)
+    _call('gd4d_mha_core_bwd' if fills is None else 'gd4d_mha_core_bwd_fill', vp(q), vp(k), vp(v), _dev(out, 'out', F32),
+          _dev(grad_out, 'grad_out', F32), mptr, _dev(lse, 'lse', F32), _dev(dsum, 'dsum'), vp(dq), vp(dk), _dev(dv, 'dv'), lq, lk, b,
+          num_heads, d, ld(q, 'q'), ld(k, 'k'), ld(v, 'v'), c, c, ldd, ldd, c, kind, 1.0 / (d ** 0.5), float(dropout_p), sptr, *fargs)
     return (dqk, dv) if packed_qk else (dq, dk, dv)
 
 
@@ -1267,61 +1145,45 @@ def layernorm_bwd(x, gamma, beta, grad_y, eps=1e-5, res=None, relu=False, into=N
     defer=True: only dx and the partial column sums are computed - returns (dx, workspace, (M, C)) for
     layernorm_bwd_reduce_group."""
     lib = _lib.load()
-    f32 = torch.float32
     c = x.shape[-1]
     m = x.numel() // c
     dx = torch.empty_like(x)
     dg, db = (None, None) if defer else ((torch.empty_like(gamma), torch.empty_like(gamma)) if into is None else into)
     nbytes = lib.gd4d_layernorm_bwd_workspace_bytes(m, c)
-    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-    code = lib.gd4d_layernorm_bwd(_dev(x, 'x', f32), _opt(res, 'res'), _dev(gamma, 'gamma', f32), _opt(beta, 'beta'),
-                                  _dev(grad_y, 'grad_y', f32), _dev(dx, 'dx'), None if defer else _dev(dg, 'dgamma', f32),
-                                  None if defer else _dev(db, 'dbeta', f32), _dev(ws, 'workspace'), ctypes.c_size_t(nbytes), m, c,
-                                  float(eps), (1 if relu else 0) | (0 if into is None else 2) | (4 if defer else 0), _stream())
-    _lib.check(code, 'gd4d_layernorm_bwd')
+    ws = torch.empty(nbytes, device=x.device, dtype=U8)
+    _call('gd4d_layernorm_bwd', _dev(x, 'x', F32), _opt(res, 'res'), _dev(gamma, 'gamma', F32), _opt(beta, 'beta'),
+          _dev(grad_y, 'grad_y', F32), _dev(dx, 'dx'), _opt(dg, 'dgamma'), _opt(db, 'dbeta'), _dev(ws, 'workspace'),
+          ctypes.c_size_t(nbytes), m, c, float(eps), (1 if relu else 0) | (0 if into is None else 2) | (4 if defer else 0))
     return (dx, ws, (m, c)) if defer else (dx, dg, db)
 
 
 def layernorm_bwd_reduce_group(problems, accumulate=True):
     """gd4d_layernorm_bwd_reduce_group: problems = list (<= 32) of (workspace, (M, C), dgamma, dbeta) from layernorm_bwd(defer=True)."""
-    lib = _lib.load()
     n = len(problems)
-    f32 = torch.float32
-    arr = lambda v: (ctypes.c_void_p * n)(*v)          # noqa: E731
-    dims = [int(v) for _, mc, _, _ in problems for v in mc]
-    code = lib.gd4d_layernorm_bwd_reduce_group(arr([_dev(w, 'workspace').value for w, _, _, _ in problems]),
-                                               arr([_dev(g, 'dgamma', f32).value for _, _, g, _ in problems]),
-                                               arr([_dev(b, 'dbeta', f32).value for _, _, _, b in problems]),
-                                               (ctypes.c_int32 * (2 * n))(*dims), n, 1 if accumulate else 0, _stream())
-    _lib.check(code, 'gd4d_layernorm_bwd_reduce_group')
+    wss, mcs, dgs, dbs = zip(*problems) if n else [()] * 4
+    dims = [int(v) for mc in mcs for v in mc]
+    _call('gd4d_layernorm_bwd_reduce_group', _ptrs(wss, 'workspace', None), _ptrs(dgs, 'dgamma'), _ptrs(dbs, 'dbeta'),
+          (ctypes.c_int32 * (2 * n))(*dims), n, 1 if accumulate else 0)
 
 
 def inverse_sigmoid_fwd(x):
     """gd4d_inverse_sigmoid_fwd: the reference's inverse_sigmoid (eps = 1e-5) as one launch; no autograd."""
-    lib = _lib.load()
     y = torch.empty_like(x)
-    code = lib.gd4d_inverse_sigmoid_fwd(_dev(x, 'x', torch.float32), _dev(y, 'y'), x.numel(), _stream())
-    _lib.check(code, 'gd4d_inverse_sigmoid_fwd')
+    _call('gd4d_inverse_sigmoid_fwd', _dev(x, 'x', F32), _dev(y, 'y'), x.numel())
     return y
 
 
 def inverse_sigmoid_bwd(x, grad_y, add=None):
     """gd4d_inverse_sigmoid_bwd: grad_y * d inverse_sigmoid(x) / dx (+ add)."""
-    lib = _lib.load()
     gx = torch.empty_like(x)
-    code = lib.gd4d_inverse_sigmoid_bwd(_dev(x, 'x', torch.float32), _dev(grad_y, 'grad_y', torch.float32), _opt(add, 'add'),
-                                        _dev(gx, 'grad_x'), x.numel(), _stream())
-    _lib.check(code, 'gd4d_inverse_sigmoid_bwd')
+    _call('gd4d_inverse_sigmoid_bwd', _dev(x, 'x', F32), _dev(grad_y, 'grad_y', F32), _opt(add, 'add'), _dev(gx, 'grad_x'), x.numel())
     return gx
 
 
 def refine_reference_fwd(tmp, ref):
     """gd4d_refine_reference_fwd: tmp (..., >=5) regression deltas, ref (..., 3) in [0,1] -> new ref."""
-    lib = _lib.load()
     out = torch.empty_like(ref)
-    code = lib.gd4d_refine_reference_fwd(_dev(tmp, 'tmp', torch.float32), _dev(ref, 'ref', torch.float32),
-                                         _dev(out, 'out'), ref.numel() // 3, tmp.shape[-1], _stream())
-    _lib.check(code, 'gd4d_refine_reference_fwd')
+    _call('gd4d_refine_reference_fwd', _dev(tmp, 'tmp', F32), _dev(ref, 'ref', F32), _dev(out, 'out'), ref.numel() // 3, tmp.shape[-1])
     return out
 
 
@@ -1329,23 +1191,19 @@ def frustum_pe_input_fwd(img2lidar, feat_hw, pad_hw, depth_num, depth_start, pc_
     """gd4d_frustum_pe_input_fwd.  img2lidar (R, 4, 4) fp32 -> (x, outside (R, H, W) bool).  Without `out`: x is a new
     NCHW (R, 3*D, H, W) tensor; with `out` (R, S, 3*D) the level is written channels-last at pixels
     [row_start, row_start + H*W) of every row."""
-    lib = _lib.load()
     r = img2lidar.shape[0]
     h, w = feat_hw
     row_pixels = 0
     if out is None:
-        out = torch.empty(r, 3 * depth_num, h, w, device=img2lidar.device, dtype=torch.float32)
+        out = torch.empty(r, 3 * depth_num, h, w, device=img2lidar.device, dtype=F32)
     else:
         row_pixels = out.shape[1]
         if out.shape != (r, row_pixels, 3 * depth_num):
             raise ValueError('out must be (R, S, 3*D)')
-    outside = torch.empty(r, h, w, device=img2lidar.device, dtype=torch.uint8)
-    rng = (ctypes.c_double * 6)(*[float(v) for v in pc_range])
-    code = lib.gd4d_frustum_pe_input_fwd(_dev(img2lidar, 'img2lidar', torch.float32), _dev(out, 'out', torch.float32),
-                                         _dev(outside, 'outside'), r, h, w, int(depth_num), float(pad_hw[0]),
-                                         float(pad_hw[1]), float(depth_start), rng, int(row_pixels), int(row_start),
-                                         _stream())
-    _lib.check(code, 'gd4d_frustum_pe_input_fwd')
+    outside = torch.empty(r, h, w, device=img2lidar.device, dtype=U8)
+    rng = _range6(pc_range)
+    _call('gd4d_frustum_pe_input_fwd', _dev(img2lidar, 'img2lidar', F32), _dev(out, 'out', F32), _dev(outside, 'outside'), r, h, w,
+          int(depth_num), float(pad_hw[0]), float(pad_hw[1]), float(depth_start), rng, int(row_pixels), int(row_start))
     return out, outside.bool()
 
 
@@ -1353,84 +1211,64 @@ def se_fuse_chlast_fwd(feat, gate, pe, sine, row_start, out=None, out_channels_l
     """gd4d_se_fuse_chlast_fwd: feat (R, C, H, W) NCHW, gate / pe (R, S, C) channels-last, sine NCHW like feat or
     channels-last like gate -> (R, C, H, W).  out_channels_last: the result's MEMORY is (R, H, W, C) - returned as its
     (R, C, H, W) view, the same values; what PyramidView.is_channels_last_level recognises and the gathers read in place."""
-    lib = _lib.load()
     r, c, h, w = feat.shape
     if out is None:
-        out = torch.empty((r, h, w, c) if out_channels_last else (r, c, h, w), device=feat.device, dtype=torch.float32)
-    code = lib.gd4d_se_fuse_chlast_fwd(_dev(feat, 'feat', torch.float32), _dev(gate, 'gate', torch.float32),
-                                       _dev(pe, 'pe', torch.float32), _dev(sine, 'sine', torch.float32), _dev(out, 'out'),
-                                       r, c, h * w, gate.shape[1], int(row_start), int(sine.dim() == 3),
-                                       1 if out_channels_last else 0, _stream())
-    _lib.check(code, 'gd4d_se_fuse_chlast_fwd')
+        out = torch.empty((r, h, w, c) if out_channels_last else (r, c, h, w), device=feat.device, dtype=F32)
+    _call('gd4d_se_fuse_chlast_fwd', _dev(feat, 'feat', F32), _dev(gate, 'gate', F32), _dev(pe, 'pe', F32), _dev(sine, 'sine', F32),
+          _dev(out, 'out'), r, c, h * w, gate.shape[1], int(row_start), int(sine.dim() == 3), 1 if out_channels_last else 0)
     return out.permute(0, 3, 1, 2) if out_channels_last else out
 
 
 def sine_pe3d_fwd(n_embed, y_embed, x_embed, dim_t, out=None, row_start=0):
     """gd4d_sine_pe3d_fwd.  embeds (R, H, W) fp32, dim_t (F) -> (R, 3*F, H, W); with `out` (R, S, 3*F) the level is
     written channels-last at pixels [row_start, row_start + H*W) of every row."""
-    lib = _lib.load()
     r, h, w = n_embed.shape
     f = dim_t.numel()
     row_pixels = 0
     if out is None:
-        out = torch.empty(r, 3 * f, h, w, device=n_embed.device, dtype=torch.float32)
+        out = torch.empty(r, 3 * f, h, w, device=n_embed.device, dtype=F32)
     else:
         row_pixels = out.shape[1]
-    code = lib.gd4d_sine_pe3d_fwd(_dev(n_embed, 'n_embed', torch.float32), _dev(y_embed, 'y_embed', torch.float32),
-                                  _dev(x_embed, 'x_embed', torch.float32), _dev(dim_t, 'dim_t', torch.float32),
-                                  _dev(out, 'out', torch.float32), r, h * w, f, int(row_pixels), int(row_start), _stream())
-    _lib.check(code, 'gd4d_sine_pe3d_fwd')
+    _call('gd4d_sine_pe3d_fwd', _dev(n_embed, 'n_embed', F32), _dev(y_embed, 'y_embed', F32), _dev(x_embed, 'x_embed', F32),
+          _dev(dim_t, 'dim_t', F32), _dev(out, 'out', F32), r, h * w, f, int(row_pixels), int(row_start))
     return out
 
 
 def se_fuse_chlast_bwd(grad_out, gate, pe, grad_sine, row_start):
     """gd4d_se_fuse_chlast_bwd for one level: grad_out (R, C, H, W); gate / pe (R, S, C) are REPLACED by their gradients on
     the level's rows, grad_sine (R, S, C) receives grad_out channels-last."""
-    lib = _lib.load()
     r, c, h, w = grad_out.shape
-    code = lib.gd4d_se_fuse_chlast_bwd(_dev(grad_out, 'grad_out', torch.float32), _dev(gate, 'gate', torch.float32),
-                                       _dev(pe, 'pe', torch.float32), _dev(gate, 'gate'), _dev(pe, 'pe'),
-                                       _dev(grad_sine, 'grad_sine', torch.float32), r, c, h * w, gate.shape[1],
-                                       int(row_start), _stream())
-    _lib.check(code, 'gd4d_se_fuse_chlast_bwd')
+    _call('gd4d_se_fuse_chlast_bwd', _dev(grad_out, 'grad_out', F32), _dev(gate, 'gate', F32), _dev(pe, 'pe', F32), _dev(gate, 'gate'),
+          _dev(pe, 'pe'), _dev(grad_sine, 'grad_sine', F32), r, c, h * w, gate.shape[1], int(row_start))
 
 
 def se_fuse_fwd(feat, gate, pe, sine, out=None):
     """gd4d_se_fuse_fwd: feat + (pe * sigmoid(gate) + sine), all the same shape."""
-    lib = _lib.load()
     out = torch.empty_like(feat) if out is None else out
-    code = lib.gd4d_se_fuse_fwd(_dev(feat, 'feat', torch.float32), _dev(gate, 'gate', torch.float32),
-                                _dev(pe, 'pe', torch.float32), _dev(sine, 'sine', torch.float32), _dev(out, 'out'),
-                                ctypes.c_size_t(feat.numel()), _stream())
-    _lib.check(code, 'gd4d_se_fuse_fwd')
+    _call('gd4d_se_fuse_fwd', _dev(feat, 'feat', F32), _dev(gate, 'gate', F32), _dev(pe, 'pe', F32), _dev(sine, 'sine', F32),
+          _dev(out, 'out'), ctypes.c_size_t(feat.numel()))
     return out
 
 
 def split_bf16_fwd(w):
     """gd4d_split_bf16_fwd: fp32 tensor -> (hi, lo) bf16 tensors of the same shape with w ~= hi + lo."""
-    lib = _lib.load()
     hi = torch.empty(w.shape, device=w.device, dtype=torch.bfloat16)
     lo = torch.empty(w.shape, device=w.device, dtype=torch.bfloat16)
-    code = lib.gd4d_split_bf16_fwd(_dev(w, 'w', torch.float32), _dev(hi, 'hi'), _dev(lo, 'lo'),
-                                   ctypes.c_size_t(w.numel()), _stream())
-    _lib.check(code, 'gd4d_split_bf16_fwd')
+    _call('gd4d_split_bf16_fwd', _dev(w, 'w', F32), _dev(hi, 'hi'), _dev(lo, 'lo'), ctypes.c_size_t(w.numel()))
     return hi, lo
 
 
 def gemm_bf16x3_fwd(a, w_hi, w_lo, bias=None, relu=False, out=None, relu_in=False, mask_out=False):
     """gd4d_gemm_bf16x3_fwd: a (M, K) fp32 row-major, w_hi / w_lo (N, K) bf16 -> act(a W^T + b) (M, N) fp32.
     mask_out: `out` holds a ReLU's forward output and is replaced by the result where it was > 0, by 0 elsewhere."""
-    lib = _lib.load()
     m, k = a.shape
     n = w_hi.shape[0]
     if out is None:
         if mask_out:
             raise ValueError('mask_out=True needs `out` = the activations of the forward')
-        out = torch.empty(m, n, device=a.device, dtype=torch.float32)
-    code = lib.gd4d_gemm_bf16x3_fwd(_dev(a, 'a', torch.float32), _dev(w_hi, 'w_hi', torch.bfloat16),
-                                    _dev(w_lo, 'w_lo', torch.bfloat16), _opt(bias, 'bias'), _dev(out, 'out'), m, n, k, k, n,
-                                    int(bool(relu)) | (16 if relu_in else 0) | (32 if mask_out else 0), _stream())
-    _lib.check(code, 'gd4d_gemm_bf16x3_fwd')
+        out = torch.empty(m, n, device=a.device, dtype=F32)
+    _call('gd4d_gemm_bf16x3_fwd', _dev(a, 'a', F32), _dev(w_hi, 'w_hi', torch.bfloat16), _dev(w_lo, 'w_lo', torch.bfloat16),
+          _opt(bias, 'bias'), _dev(out, 'out'), m, n, k, k, n, int(bool(relu)) | (16 if relu_in else 0) | (32 if mask_out else 0))
     return out
 
 
@@ -1442,10 +1280,9 @@ def mlp2_image(w1, b1, w2):
     nbytes = int(lib.gd4d_mlp2_image_bytes(k1, h, n2))
     if nbytes == 0 or w2.shape[1] != h:
         raise _lib.Gd4dError(f'mlp2: K1 = {k1} (a multiple of 16, <= 256), H = {h} (a multiple of 32), N2 = {n2} (256) are the kernel\'s limits')
-    img = torch.empty(nbytes, device=w1.device, dtype=torch.uint8)
-    code = lib.gd4d_mlp2_image(_dev(w1.contiguous(), 'w1', torch.float32), None if b1 is None else _dev(b1.contiguous(), 'b1', torch.float32),
-                               _dev(w2.contiguous(), 'w2', torch.float32), k1, h, n2, _dev(img, 'image', torch.uint8), _stream())
-    _lib.check(code, 'gd4d_mlp2_image')
+    img = torch.empty(nbytes, device=w1.device, dtype=U8)
+    _call('gd4d_mlp2_image', _dev(w1.contiguous(), 'w1', F32), None if b1 is None else _dev(b1.contiguous(), 'b1', F32),
+          _dev(w2.contiguous(), 'w2', F32), k1, h, n2, _dev(img, 'image', U8))
     img.shape_khn = (k1, h, n2)
     return img
 
@@ -1456,16 +1293,13 @@ def mlp2_supported(k1, h, n2):
 
 def mlp2_bf16x3_fwd(x, image, b2=None, out=None):
     """gd4d_mlp2_bf16x3_fwd: x (M, K1) fp32 -> relu(x W1^T + b1) W2^T + b2 (M, N2), the hidden activation never stored."""
-    lib = _lib.load()
     k1, h, n2 = image.shape_khn
     m = x.shape[0]
     if x.shape[1] != k1:
         raise ValueError(f'mlp2_bf16x3_fwd: x has {x.shape[1]} columns, the image was made for {k1}')
     if out is None:
-        out = torch.empty(m, n2, device=x.device, dtype=torch.float32)
-    code = lib.gd4d_mlp2_bf16x3_fwd(_dev(x, 'x', torch.float32), _dev(image, 'image', torch.uint8), _opt(b2, 'b2'),
-                                    _dev(out, 'out', torch.float32), m, k1, h, n2, k1, n2, _stream())
-    _lib.check(code, 'gd4d_mlp2_bf16x3_fwd')
+        out = torch.empty(m, n2, device=x.device, dtype=F32)
+    _call('gd4d_mlp2_bf16x3_fwd', _dev(x, 'x', F32), _dev(image, 'image', U8), _opt(b2, 'b2'), _dev(out, 'out', F32), m, k1, h, n2, k1, n2)
     return out
 
 
@@ -1475,8 +1309,6 @@ def mlp2_pe_se_fwd(img2lidar, feats, pad_hw, depth_num, depth_start, pc_range, p
     the (R, S, 256) embedding between them.  feats: L levels (R, 256, H_l, W_l) NCHW of the cameras of img2lidar (R, 4, 4); sine
     (R, S, 256); outs: L (R, H_l, W_l, 256) tensors to write (made when None); pe_out (R, S, 256): store the embedding as well.
     Returns the levels as (R, 256, H_l, W_l) views of channels-last memory."""
-    lib = _lib.load()
-    f32 = torch.float32
     k1, pe_h, n2 = pe_image.shape_khn
     sk, se_h, sn = se_image.shape_khn
     nl = len(feats)
@@ -1487,18 +1319,16 @@ def mlp2_pe_se_fwd(img2lidar, feats, pad_hw, depth_num, depth_start, pc_range, p
     if sine.numel() != r * s_tot * 256 or (pe_out is not None and pe_out.numel() != r * s_tot * 256):
         raise ValueError(f'mlp2_pe_se_fwd: sine / pe_out must hold ({r}, {s_tot}, 256)')
     if outs is None:
-        outs = [torch.empty(r, f.shape[2], f.shape[3], 256, device=f.device, dtype=f32) for f in feats]
+        outs = [torch.empty(r, f.shape[2], f.shape[3], 256, device=f.device, dtype=F32) for f in feats]
     elif any(tuple(o.shape) != (r, f.shape[2], f.shape[3], 256) for o, f in zip(outs, feats)):
         raise ValueError('mlp2_pe_se_fwd: outs must be (R, H_l, W_l, 256) per level')
-    fp = (ctypes.c_void_p * nl)(*[_dev(f, 'feats', f32).value for f in feats])
-    op = (ctypes.c_void_p * nl)(*[_dev(o, 'outs', f32).value for o in outs])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in feats for x in f.shape[2:]])
-    rng = (ctypes.c_double * 6)(*[float(v) for v in pc_range])
-    code = lib.gd4d_mlp2_pe_se_fwd(_dev(img2lidar, 'img2lidar', f32), fp, lv, nl, r, float(pad_hw[0]), float(pad_hw[1]), int(depth_num),
-                                   float(depth_start), rng, _dev(pe_image, 'pe_image', torch.uint8), _opt(pe_b2, 'pe_b2'), pe_h,
-                                   _dev(se_image, 'se_image', torch.uint8), _opt(se_b2, 'se_b2'), se_h, _dev(sine, 'sine', f32), op,
-                                   None if pe_out is None else _dev(pe_out, 'pe_out', f32), _stream())
-    _lib.check(code, 'gd4d_mlp2_pe_se_fwd')
+    fp = _ptrs(feats, 'feats')
+    op = _ptrs(outs, 'outs')
+    lv = _levels(feats)
+    rng = _range6(pc_range)
+    _call('gd4d_mlp2_pe_se_fwd', _dev(img2lidar, 'img2lidar', F32), fp, lv, nl, r, float(pad_hw[0]), float(pad_hw[1]), int(depth_num),
+          float(depth_start), rng, _dev(pe_image, 'pe_image', U8), _opt(pe_b2, 'pe_b2'), pe_h, _dev(se_image, 'se_image', U8),
+          _opt(se_b2, 'se_b2'), se_h, _dev(sine, 'sine', F32), op, _opt(pe_out, 'pe_out'))
     return [o.permute(0, 3, 1, 2) for o in outs]
 
 
@@ -1507,26 +1337,23 @@ def mlp2_se_fuse_fwd(feats, image, b2, pe, sine, outs=None):
     conv_expand.weight), b2 = conv_expand.bias, pe / sine (R, S, 256) channels-last rows of all levels side by side ->
     L tensors feat + (pe * sigmoid(gate) + sine) as (R, 256, H_l, W_l) VIEWS of (R, H_l, W_l, 256) memory (channels-last levels;
     outs: the L (R, H_l, W_l, 256) tensors to write)."""
-    lib = _lib.load()
     k1, h, n2 = image.shape_khn
     nl = len(feats)
     r = feats[0].shape[0]
-    f32 = torch.float32
     if k1 != 256 or n2 != 256 or any(f.shape[0] != r or f.shape[1] != 256 or f.dim() != 4 for f in feats):
         raise ValueError('mlp2_se_fuse_fwd: (R, 256, H, W) levels and a 256 -> H -> 256 image expected')
     s_tot = sum(f.shape[2] * f.shape[3] for f in feats)
     if tuple(pe.shape) != (r, s_tot, 256) or tuple(sine.shape) != (r, s_tot, 256):
         raise ValueError(f'mlp2_se_fuse_fwd: pe / sine must be ({r}, {s_tot}, 256)')
     if outs is None:
-        outs = [torch.empty(r, f.shape[2], f.shape[3], 256, device=f.device, dtype=f32) for f in feats]
+        outs = [torch.empty(r, f.shape[2], f.shape[3], 256, device=f.device, dtype=F32) for f in feats]
     elif any(tuple(o.shape) != (r, f.shape[2], f.shape[3], 256) for o, f in zip(outs, feats)):
         raise ValueError('mlp2_se_fuse_fwd: outs must be (R, H_l, W_l, 256) per level')
-    fp = (ctypes.c_void_p * nl)(*[_dev(f, 'feats', f32).value for f in feats])
-    op = (ctypes.c_void_p * nl)(*[_dev(o, 'outs', f32).value for o in outs])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in feats for x in f.shape[2:]])
-    code = lib.gd4d_mlp2_se_fuse_fwd(fp, lv, nl, r, _dev(image, 'image', torch.uint8), _opt(b2, 'b2'), _dev(pe, 'pe', f32),
-                                     _dev(sine, 'sine', f32), op, 256, h, _stream())
-    _lib.check(code, 'gd4d_mlp2_se_fuse_fwd')
+    fp = _ptrs(feats, 'feats')
+    op = _ptrs(outs, 'outs')
+    lv = _levels(feats)
+    _call('gd4d_mlp2_se_fuse_fwd', fp, lv, nl, r, _dev(image, 'image', U8), _opt(b2, 'b2'), _dev(pe, 'pe', F32), _dev(sine, 'sine', F32),
+          op, 256, h)
     return [o.permute(0, 3, 1, 2) for o in outs]
 
 
@@ -1543,7 +1370,6 @@ def mlp2_frustum_image(w1, b1, w2):
 def mlp2_frustum_fwd(img2lidar, level_hw, pad_hw, depth_num, depth_start, pc_range, image, b2=None, out=None):
     """gd4d_mlp2_frustum_fwd: img2lidar (R, 4, 4) -> position_encoder(frustum coordinates) (R, S, 256), S = the pixels of `level_hw`'s
     levels side by side; image: mlp2_frustum_image.  No (R, S, 192) frustum tensor is written or read."""
-    lib = _lib.load()
     k1, h, n2 = image.shape_khn
     r = img2lidar.shape[0]
     nl = len(level_hw)
@@ -1551,15 +1377,13 @@ def mlp2_frustum_fwd(img2lidar, level_hw, pad_hw, depth_num, depth_start, pc_ran
     if k1 != 3 * depth_num or n2 != 256:
         raise ValueError(f'mlp2_frustum_fwd: the image is {k1} -> {h} -> {n2}, the frustum has {3 * depth_num} channels')
     if out is None:
-        out = torch.empty(r, s_tot, n2, device=img2lidar.device, dtype=torch.float32)
+        out = torch.empty(r, s_tot, n2, device=img2lidar.device, dtype=F32)
     elif out.numel() != r * s_tot * n2:
         raise ValueError('mlp2_frustum_fwd: out must hold (R, S, 256)')
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for hw in level_hw for x in hw])
-    rng = (ctypes.c_double * 6)(*[float(v) for v in pc_range])
-    code = lib.gd4d_mlp2_frustum_fwd(_dev(img2lidar, 'img2lidar', torch.float32), lv, nl, r, float(pad_hw[0]), float(pad_hw[1]),
-                                     int(depth_num), float(depth_start), rng, _dev(image, 'image', torch.uint8), _opt(b2, 'b2'),
-                                     _dev(out, 'out', torch.float32), h, n2, _stream())
-    _lib.check(code, 'gd4d_mlp2_frustum_fwd')
+    lv = _levels(level_hw)
+    rng = _range6(pc_range)
+    _call('gd4d_mlp2_frustum_fwd', _dev(img2lidar, 'img2lidar', F32), lv, nl, r, float(pad_hw[0]), float(pad_hw[1]), int(depth_num),
+          float(depth_start), rng, _dev(image, 'image', U8), _opt(b2, 'b2'), _dev(out, 'out', F32), h, n2)
     return out.view(r, s_tot, n2)
 
 
@@ -1573,86 +1397,70 @@ def gemm_tn_bf16x3(a, b, relu_b=False, want_colsum=True):
         raise ValueError(f'gemm_tn_bf16x3: {tuple(a.shape)} against {tuple(b.shape)}')
     dev = a.device
     nbytes = lib.gd4d_gemm_tn_bf16x3_workspace_bytes(r, m, n)
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)             # (scratch of this call only: see _vp_workspace)
-    c = torch.empty(m, n, device=dev, dtype=torch.float32)
-    col = torch.empty(m, device=dev, dtype=torch.float32) if want_colsum else None
-    code = lib.gd4d_gemm_tn_bf16x3(_dev(a, 'a', torch.float32), _dev(b, 'b', torch.float32), _dev(c, 'c'), _opt(col, 'colsum'),
-                                   _dev(ws, 'workspace'), r, m, n, m, n, 16 if relu_b else 0, _stream())
-    _lib.check(code, 'gd4d_gemm_tn_bf16x3')
+    ws = torch.empty(nbytes, device=dev, dtype=U8)             # (scratch of this call only: see _vp_workspace)
+    c = torch.empty(m, n, device=dev, dtype=F32)
+    col = torch.empty(m, device=dev, dtype=F32) if want_colsum else None
+    _call('gd4d_gemm_tn_bf16x3', _dev(a, 'a', F32), _dev(b, 'b', F32), _dev(c, 'c'), _opt(col, 'colsum'), _dev(ws, 'workspace'), r, m, n, m,
+          n, 16 if relu_b else 0)
     return c, col
 
 
 def knn_farthest_fwd(x, k):
     """gd4d_knn_farthest_fwd: x (B, N, C) fp32 -> (B, N, K) int32 indices of the K farthest rows of the same sample."""
-    lib = _lib.load()
     b, n, c = x.shape
-    idx = torch.empty(b, n, k, device=x.device, dtype=torch.int32)
-    code = lib.gd4d_knn_farthest_fwd(_dev(x, 'x', torch.float32), _dev(idx, 'idx'), b, n, c, int(k), _stream())
-    _lib.check(code, 'gd4d_knn_farthest_fwd')
+    idx = torch.empty(b, n, k, device=x.device, dtype=I32)
+    _call('gd4d_knn_farthest_fwd', _dev(x, 'x', F32), _dev(idx, 'idx'), b, n, c, int(k))
     return idx
 
 
 def edge_conv_max_fwd(ab, idx, scale, shift):
     """gd4d_edge_conv_max_fwd: ab (B, N, 2C) = [W_a x | W_b x], idx (B, N, K) int32, scale / shift (C) -> (B, N, C)."""
-    lib = _lib.load()
     b, n, c2 = ab.shape
     c = c2 // 2
-    out = torch.empty(b, n, c, device=ab.device, dtype=torch.float32)
-    base = _dev(ab, 'ab', torch.float32)
-    code = lib.gd4d_edge_conv_max_fwd(base, ctypes.c_void_p(ab.data_ptr() + 4 * c), _dev(idx, 'idx', torch.int32),
-                                      _dev(scale, 'scale', torch.float32), _dev(shift, 'shift', torch.float32),
-                                      _dev(out, 'out'), b, n, c, idx.shape[-1], c2, _stream())
-    _lib.check(code, 'gd4d_edge_conv_max_fwd')
+    out = torch.empty(b, n, c, device=ab.device, dtype=F32)
+    base = _dev(ab, 'ab', F32)
+    _call('gd4d_edge_conv_max_fwd', base, ctypes.c_void_p(ab.data_ptr() + 4 * c), _dev(idx, 'idx', I32), _dev(scale, 'scale', F32),
+          _dev(shift, 'shift', F32), _dev(out, 'out'), b, n, c, idx.shape[-1], c2)
     return out
 
 
 def box_head_fwd(tmp, ref, pc_range, scale=1.0, out=None):
     """gd4d_box_head_fwd: tmp (..., code) raw regression output, ref (..., 3) in [0,1] -> bbox_preds."""
-    lib = _lib.load()
     out = torch.empty_like(tmp) if out is None else out
-    rng = (ctypes.c_double * 6)(*[float(v) for v in pc_range])
-    code = lib.gd4d_box_head_fwd(_dev(tmp, 'tmp', torch.float32), _dev(ref, 'ref', torch.float32), rng,
-                                 float(scale), _dev(out, 'out', torch.float32), ref.numel() // 3, tmp.shape[-1],
-                                 _stream())
-    _lib.check(code, 'gd4d_box_head_fwd')
+    rng = _range6(pc_range)
+    _call('gd4d_box_head_fwd', _dev(tmp, 'tmp', F32), _dev(ref, 'ref', F32), rng, float(scale), _dev(out, 'out', F32), ref.numel() // 3,
+          tmp.shape[-1])
     return out
 
 
 def nms_free_decode_fwd(cls_scores, bbox_preds, post_center_range, max_num, score_threshold=None):
     """gd4d_nms_free_decode_fwd.  cls_scores (B, Q, C) logits, bbox_preds (B, Q, code).
     Returns boxes (B, K, 9|7), scores (B, K), labels (B, K) int32, keep (B, K) bool, all sorted by score."""
-    lib = _lib.load()
     b, q, c = cls_scores.shape
     code_size = bbox_preds.shape[-1]
     k = int(max_num)
     if k > q * c:
         raise RuntimeError('selected index k out of range')        # what torch.topk raises in the reference
     dev = cls_scores.device
-    boxes = torch.empty(b, k, 9 if code_size > 8 else 7, device=dev, dtype=torch.float32)
-    scores = torch.empty(b, k, device=dev, dtype=torch.float32)
-    labels = torch.empty(b, k, device=dev, dtype=torch.int32)
-    keep = torch.empty(b, k, device=dev, dtype=torch.uint8)
+    boxes = torch.empty(b, k, 9 if code_size > 8 else 7, device=dev, dtype=F32)
+    scores = torch.empty(b, k, device=dev, dtype=F32)
+    labels = torch.empty(b, k, device=dev, dtype=I32)
+    keep = torch.empty(b, k, device=dev, dtype=U8)
     rng = (ctypes.c_float * 6)(*[float(v) for v in post_center_range])
     thr = -1.0 if score_threshold is None else float(score_threshold)
-    code = lib.gd4d_nms_free_decode_fwd(_dev(cls_scores, 'cls_scores', torch.float32),
-                                        _dev(bbox_preds, 'bbox_preds', torch.float32), rng, thr, _dev(boxes, 'boxes'),
-                                        _dev(scores, 'scores'), _dev(labels, 'labels'), _dev(keep, 'keep'),
-                                        b, q, c, code_size, k, _stream())
-    _lib.check(code, 'gd4d_nms_free_decode_fwd')
+    _call('gd4d_nms_free_decode_fwd', _dev(cls_scores, 'cls_scores', F32), _dev(bbox_preds, 'bbox_preds', F32), rng, thr,
+          _dev(boxes, 'boxes'), _dev(scores, 'scores'), _dev(labels, 'labels'), _dev(keep, 'keep'), b, q, c, code_size, k)
     return boxes, scores, labels, keep.bool()
 
 
 def refine_reference_order_fwd(tmp, ref, pc_range):
     """gd4d_refine_reference_order_fwd: tmp (B, Q, >=5), ref (B, Q, 3) -> (new ref, int32 locality order of it)."""
-    lib = _lib.load()
     b, q = ref.shape[0], ref.shape[1]
     out = torch.empty_like(ref)
-    order = torch.empty(b * q, device=ref.device, dtype=torch.int32)
-    rng = (ctypes.c_double * 6)(*[float(x) for x in pc_range])
-    code = lib.gd4d_refine_reference_order_fwd(_dev(tmp, 'tmp', torch.float32), _dev(ref, 'ref', torch.float32),
-                                               _dev(out, 'out'), rng, _dev(order, 'order'), b, q, tmp.shape[-1],
-                                               _stream())
-    _lib.check(code, 'gd4d_refine_reference_order_fwd')
+    order = torch.empty(b * q, device=ref.device, dtype=I32)
+    rng = _range6(pc_range)
+    _call('gd4d_refine_reference_order_fwd', _dev(tmp, 'tmp', F32), _dev(ref, 'ref', F32), _dev(out, 'out'), rng, _dev(order, 'order'), b,
+          q, tmp.shape[-1])
     return out, order
 
 
@@ -1660,30 +1468,23 @@ def cross_attn_bwd(value, level_hw, ref, offsets, attn_logits, cam_logits, lidar
                    grad_out, query_order=None, raw_cam_weights=False):
     """gd4d_cross_attn_bwd.  Returns (grad_value, grad_ref, grad_offsets, grad_attn_logits, grad_cam_logits)."""
     lib = _lib.load()
-    f32 = torch.float32
     b, q = ref.shape[0], ref.shape[1]
     n = lidar2img.shape[1]
     hh, dh = value.shape[2], value.shape[3]
     p = offsets.shape[3]
     nl = len(level_hw)
-    gv = torch.zeros_like(value, dtype=f32)
+    gv = torch.zeros_like(value, dtype=F32)
     gr = torch.empty_like(ref)
-    go = torch.empty(b, q, hh, p, 3, device=ref.device, dtype=f32)
-    ga = torch.empty(b, q, hh, nl, p, device=ref.device, dtype=f32)
-    gc = torch.empty(b, q, n, device=ref.device, dtype=f32)
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for hw in level_hw for x in hw])
-    rng = (ctypes.c_double * 6)(*[float(x) for x in pc_range])
+    go = torch.empty(b, q, hh, p, 3, device=ref.device, dtype=F32)
+    ga = torch.empty(b, q, hh, nl, p, device=ref.device, dtype=F32)
+    gc = torch.empty(b, q, n, device=ref.device, dtype=F32)
     nbytes = lib.gd4d_cross_attn_bwd_workspace_bytes(b, q, hh, nl, p)          # B > 1: partial logit gradients per sample
-    ws = torch.empty(nbytes, device=ref.device, dtype=torch.uint8) if nbytes else None
-    code = lib.gd4d_cross_attn_bwd(
-        _dev(value, 'value', f32), lv, _dev(ref, 'ref', f32), _dev(offsets, 'offsets', f32),
-        _dev(attn_logits, 'attn_logits', f32), _dev(cam_logits, 'cam_logits', f32),
-        _dev(lidar2img, 'lidar2img', f32), rng, float(img_h), float(img_w), _dev(grad_out, 'grad_out', f32),
-        _dev(gv, 'grad_value'), _dev(gr, 'grad_ref'), _dev(go, 'grad_offsets'), _dev(ga, 'grad_attn_logits'),
-        _dev(gc, 'grad_cam_logits'), b, n, q, hh, dh, nl, p, _lib.F32, _lib.PIXEL_MAJOR, 1 if raw_cam_weights else 0,
-        None if query_order is None else _order_ptr(query_order, b * q),
-        None if ws is None else _dev(ws, 'workspace'), ctypes.c_size_t(nbytes), _stream())
-    _lib.check(code, 'gd4d_cross_attn_bwd')
+    ws = torch.empty(nbytes, device=ref.device, dtype=U8) if nbytes else None
+    _call('gd4d_cross_attn_bwd', _dev(value, 'value', F32), _levels(level_hw),
+          *_camera_args(ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w), _dev(grad_out, 'grad_out', F32),
+          _dev(gv, 'grad_value'), _dev(gr, 'grad_ref'), _dev(go, 'grad_offsets'), _dev(ga, 'grad_attn_logits'), _dev(gc, 'grad_cam_logits'),
+          b, n, q, hh, dh, nl, p, _lib.F32, _lib.PIXEL_MAJOR, 1 if raw_cam_weights else 0, _order_ptr(query_order, b * q),
+          _opt(ws, 'workspace', None), ctypes.c_size_t(nbytes))
     return gv, gr, go, ga, gc
 
 
@@ -1691,34 +1492,25 @@ def match_cost_fwd(cls, box, gt_boxes, gt_labels, gt_start, max_gt, cls_weight=2
     """gd4d_match_cost_fwd.  cls (NL, B, Q, C), box (NL, B, Q, code) fp32; gt_boxes (sumG, 7..9) fp32, gt_labels (sumG)
     int32, gt_start (B + 1) int32 - all on the GPU; max_gt = largest per-sample count.  Returns the flat cost buffer
     (NL * Q * sumG): block (l, b) at Q * (l * sumG + gt_start[b]), shape (Q, G_b)."""
-    lib = _lib.load()
-    f32, i32 = torch.float32, torch.int32
     nl, b, q, c = cls.shape
     sum_gt = gt_boxes.shape[0]
-    cost = torch.empty(nl * q * sum_gt, device=cls.device, dtype=f32)
-    code = lib.gd4d_match_cost_fwd(_dev(cls, 'cls', f32), _dev(box, 'box', f32), _dev(gt_boxes, 'gt_boxes', f32),
-                                   _dev(gt_labels, 'gt_labels', i32), _dev(gt_start, 'gt_start', i32),
-                                   _dev(cost, 'cost'), nl, b, q, c, box.shape[-1], gt_boxes.shape[-1], sum_gt,
-                                   int(max_gt), float(cls_weight), float(reg_weight), float(alpha), _stream())
-    _lib.check(code, 'gd4d_match_cost_fwd')
+    cost = torch.empty(nl * q * sum_gt, device=cls.device, dtype=F32)
+    _call('gd4d_match_cost_fwd', _dev(cls, 'cls', F32), _dev(box, 'box', F32), _dev(gt_boxes, 'gt_boxes', F32),
+          _dev(gt_labels, 'gt_labels', I32), _dev(gt_start, 'gt_start', I32), _dev(cost, 'cost'), nl, b, q, c, box.shape[-1],
+          gt_boxes.shape[-1], sum_gt, int(max_gt), float(cls_weight), float(reg_weight), float(alpha))
     return cost
 
 
 def head_loss_fwd_bwd(cls, box, assigned, gt_boxes, gt_labels, code_weights, avg_factors, alpha=0.25,
                       loss_cls_weight=2.0, loss_bbox_weight=0.25):
     """gd4d_head_loss_fwd_bwd.  Returns (loss (NL, 2), grad_cls like cls, grad_box like box)."""
-    lib = _lib.load()
-    f32, i32 = torch.float32, torch.int32
     nl, b, q, c = cls.shape
-    loss = torch.empty(nl, 2, device=cls.device, dtype=f32)
+    loss = torch.empty(nl, 2, device=cls.device, dtype=F32)
     gcls, gbox = torch.empty_like(cls), torch.empty_like(box)
-    code = lib.gd4d_head_loss_fwd_bwd(_dev(cls, 'cls', f32), _dev(box, 'box', f32), _dev(assigned, 'assigned', i32),
-                                      _dev(gt_boxes, 'gt_boxes', f32), _dev(gt_labels, 'gt_labels', i32),
-                                      _dev(code_weights, 'code_weights', f32), _dev(avg_factors, 'avg_factors', f32),
-                                      _dev(loss, 'loss'), _dev(gcls, 'grad_cls'), _dev(gbox, 'grad_box'), nl, b, q, c,
-                                      box.shape[-1], gt_boxes.shape[-1], gt_boxes.shape[0], float(alpha),
-                                      float(loss_cls_weight), float(loss_bbox_weight), _stream())
-    _lib.check(code, 'gd4d_head_loss_fwd_bwd')
+    _call('gd4d_head_loss_fwd_bwd', _dev(cls, 'cls', F32), _dev(box, 'box', F32), _dev(assigned, 'assigned', I32),
+          _dev(gt_boxes, 'gt_boxes', F32), _dev(gt_labels, 'gt_labels', I32), _dev(code_weights, 'code_weights', F32),
+          _dev(avg_factors, 'avg_factors', F32), _dev(loss, 'loss'), _dev(gcls, 'grad_cls'), _dev(gbox, 'grad_box'), nl, b, q, c,
+          box.shape[-1], gt_boxes.shape[-1], gt_boxes.shape[0], float(alpha), float(loss_cls_weight), float(loss_bbox_weight))
     return loss, gcls, gbox
 
 
@@ -1747,20 +1539,22 @@ def hungarian_assign_fwd(cost, gt_start, nl, b, q, sum_gt, max_gt, assigned=None
     """gd4d_hungarian_assign_fwd: the assignment of every (layer, sample) block of match_cost_fwd's buffer on the device.  Returns
     (assigned (NL, B, Q) int32: index into the packed ground truth or -1, status (NL * B) int32: 0 solved / 1 NaN cost (bad label) /
     2 infeasible).  No host synchronisation."""
-    lib = _lib.load()
+    return _assign_fwd('gd4d_hungarian_assign', cost, gt_start, nl, b, q, sum_gt, max_gt, assigned, status, workspace)
+
+
+def _assign_fwd(stem, cost, gt_start, nl, b, q, sum_gt, max_gt, assigned, status, workspace):
+    """hungarian_assign_fwd and lsa_dense_fwd: one contract, two kernels - lib.<stem>_fwd, its scratch sized by lib.<stem>_workspace_bytes."""
     dev = cost.device
-    i32 = torch.int32
     if assigned is None:
-        assigned = torch.empty(nl, b, q, device=dev, dtype=i32)
+        assigned = torch.empty(nl, b, q, device=dev, dtype=I32)
     if status is None:
-        status = torch.empty(nl * b, device=dev, dtype=i32)
-    nbytes = int(lib.gd4d_hungarian_assign_workspace_bytes(nl, b, q, max(int(max_gt), 1)))
+        status = torch.empty(nl * b, device=dev, dtype=I32)
+    nbytes = int(getattr(_lib.load(), stem + '_workspace_bytes')(nl, b, q, max(int(max_gt), 1)))
     if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    code = lib.gd4d_hungarian_assign_fwd(_dev(cost, 'cost', torch.float32), _dev(gt_start, 'gt_start', i32), _dev(assigned, 'assigned', i32),
-                                         _dev(status, 'status', i32), _dev(workspace, 'workspace', torch.uint8), workspace.numel(),
-                                         int(nl), int(b), int(q), int(sum_gt), int(max_gt), _stream())
-    _lib.check(code, 'gd4d_hungarian_assign_fwd')
+        workspace = torch.empty(nbytes, device=dev, dtype=U8)
+    _call(stem + '_fwd', _dev(cost, 'cost', F32), _dev(gt_start, 'gt_start', I32), _dev(assigned, 'assigned', I32),
+          _dev(status, 'status', I32), _dev(workspace, 'workspace', U8), workspace.numel(), int(nl), int(b), int(q), int(sum_gt),
+          int(max_gt))
     return assigned, status
 
 
@@ -1772,82 +1566,55 @@ def hungarian_assign_branches_fwd(costs, gt_start, nl, b, qs, ks, sum_gt, max_gt
     want_copy), status (2, NL, B) int32 (0 solved / 1 NaN cost / 2 infeasible).  No host synchronisation."""
     lib = _lib.load()
     dev = gt_start.device
-    i32 = torch.int32
     qs, ks = [int(x) for x in qs], [int(x) for x in ks]
-    assigned = [torch.empty(nl, b, q, device=dev, dtype=i32) if q else None for q in qs]
-    copies = [torch.empty(nl, b, q, device=dev, dtype=i32) if q and want_copy else None for q in qs]
+    assigned = [torch.empty(nl, b, q, device=dev, dtype=I32) if q else None for q in qs]
+    copies = [torch.empty(nl, b, q, device=dev, dtype=I32) if q and want_copy else None for q in qs]
     if status is None:
-        status = torch.zeros(2, nl, b, device=dev, dtype=i32)
+        status = torch.zeros(2, nl, b, device=dev, dtype=I32)
     nbytes = int(lib.gd4d_hungarian_assign_branches_workspace_bytes(nl, b, qs[0], qs[1], max(int(max_gt), 1)))
     if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    opt = lambda t, name, dtype=None: None if t is None else _dev(t, name, dtype)  # noqa: E731
-    code = lib.gd4d_hungarian_assign_branches_fwd(
-        opt(costs[0], 'cost0', torch.float32), opt(costs[1], 'cost1', torch.float32), _dev(gt_start, 'gt_start', i32),
-        opt(assigned[0], 'assigned0'), opt(assigned[1], 'assigned1'), opt(copies[0], 'copy0'), opt(copies[1], 'copy1'),
-        _dev(status, 'status', i32), _dev(workspace, 'workspace', torch.uint8), workspace.numel(), int(nl), int(b), qs[0], qs[1],
-        ks[0], ks[1], int(sum_gt), int(max_gt), _stream())
-    _lib.check(code, 'gd4d_hungarian_assign_branches_fwd')
+        workspace = torch.empty(nbytes, device=dev, dtype=U8)
+    _call('gd4d_hungarian_assign_branches_fwd', _opt(costs[0], 'cost0'), _opt(costs[1], 'cost1'), _dev(gt_start, 'gt_start', I32),
+          _opt(assigned[0], 'assigned0', None), _opt(assigned[1], 'assigned1', None), _opt(copies[0], 'copy0', None),
+          _opt(copies[1], 'copy1', None), _dev(status, 'status', I32), _dev(workspace, 'workspace', U8), workspace.numel(), int(nl), int(b),
+          qs[0], qs[1], ks[0], ks[1], int(sum_gt), int(max_gt))
     return assigned, copies, status
-
 
 
 def distill_match_cost_fwd(s_cls, s_box, t_cls, t_box, cls_weight=1.0, reg_weight=0.25, pseudo_gt=False):
     """gd4d_distill_match_cost_fwd.  s_cls (NL, B, Qs, C), s_box (NL, B, Qs, code), t_cls (NL, B, Qt, C), t_box (NL, B, Qt, 10) fp32 on
     the GPU: the teacher head's logits and box codes.  pseudo_gt=True: t_cls the soft labels per sample, t_box (NL, B, Qt, 9) the
     denormalised boxes.  Returns the flat cost buffer (NL * B * Qs * Qt): block (l, b) at Qs * (l * B * Qt + b * Qt), shape (Qs, Qt)."""
-    lib = _lib.load()
-    f32 = torch.float32
     nl, b, qs, c = s_cls.shape
     qt = t_cls.shape[2]
     if tuple(s_box.shape[:3]) != (nl, b, qs) or tuple(t_cls.shape) != (nl, b, qt, c) or tuple(t_box.shape) != (nl, b, qt, 9 if pseudo_gt else 10):
         raise ValueError('distill_match_cost_fwd: s_cls / s_box / t_cls / t_box shapes disagree')
-    cost = torch.empty(nl * b * qs * qt, device=s_cls.device, dtype=f32)
-    code = lib.gd4d_distill_match_cost_fwd(_dev(s_cls, 's_cls', f32), _dev(s_box, 's_box', f32), _dev(t_cls, 't_cls', f32),
-                                           _dev(t_box, 't_box', f32), _dev(cost, 'cost'), nl, b, qs, qt, c, s_box.shape[-1],
-                                           1 if pseudo_gt else 0, float(cls_weight), float(reg_weight), _stream())
-    _lib.check(code, 'gd4d_distill_match_cost_fwd')
+    cost = torch.empty(nl * b * qs * qt, device=s_cls.device, dtype=F32)
+    _call('gd4d_distill_match_cost_fwd', _dev(s_cls, 's_cls', F32), _dev(s_box, 's_box', F32), _dev(t_cls, 't_cls', F32),
+          _dev(t_box, 't_box', F32), _dev(cost, 'cost'), nl, b, qs, qt, c, s_box.shape[-1], 1 if pseudo_gt else 0, float(cls_weight),
+          float(reg_weight))
     return cost
 
 
 def lsa_dense_fwd(cost, gt_start, nl, b, q, sum_gt, max_gt, assigned=None, status=None, workspace=None):
     """gd4d_lsa_dense_fwd: hungarian_assign_fwd's contract (same buffers, same outputs and status words) solved by the dense-problem
     kernel.  Returns (assigned (NL, B, Q) int32, status (NL * B) int32).  No host synchronisation."""
-    lib = _lib.load()
-    dev = cost.device
-    i32 = torch.int32
-    if assigned is None:
-        assigned = torch.empty(nl, b, q, device=dev, dtype=i32)
-    if status is None:
-        status = torch.empty(nl * b, device=dev, dtype=i32)
-    nbytes = int(lib.gd4d_lsa_dense_workspace_bytes(nl, b, q, max(int(max_gt), 1)))
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    code = lib.gd4d_lsa_dense_fwd(_dev(cost, 'cost', torch.float32), _dev(gt_start, 'gt_start', i32), _dev(assigned, 'assigned', i32),
-                                  _dev(status, 'status', i32), _dev(workspace, 'workspace', torch.uint8), workspace.numel(),
-                                  int(nl), int(b), int(q), int(sum_gt), int(max_gt), _stream())
-    _lib.check(code, 'gd4d_lsa_dense_fwd')
-    return assigned, status
+    return _assign_fwd('gd4d_lsa_dense', cost, gt_start, nl, b, q, sum_gt, max_gt, assigned, status, workspace)
 
 
 def distill_loss_fwd_bwd(s_cls, s_box, t_cls, t_box, assigned, code_weights, avg_factors, reweight_score=False,
                          loss_cls_weight=1.0, loss_reg_weight=1.0):
     """gd4d_distill_loss_fwd_bwd.  Returns (loss (NL, 2), grad_s_cls like s_cls, grad_s_box like s_box)."""
-    lib = _lib.load()
-    f32, i32 = torch.float32, torch.int32
     nl, b, qs, c = s_cls.shape
     qt = t_cls.shape[2]
     if tuple(assigned.shape) != (nl, b, qs) or tuple(t_box.shape) != (nl, b, qt, 10) or tuple(t_cls.shape) != (nl, b, qt, c):
         raise ValueError('distill_loss_fwd_bwd: shapes disagree')
-    loss = torch.empty(nl, 2, device=s_cls.device, dtype=f32)
+    loss = torch.empty(nl, 2, device=s_cls.device, dtype=F32)
     gcls, gbox = torch.empty_like(s_cls), torch.empty_like(s_box)
-    code = lib.gd4d_distill_loss_fwd_bwd(_dev(s_cls, 's_cls', f32), _dev(s_box, 's_box', f32), _dev(t_cls, 't_cls', f32),
-                                         _dev(t_box, 't_box', f32), _dev(assigned, 'assigned', i32),
-                                         _dev(code_weights, 'code_weights', f32), _dev(avg_factors, 'avg_factors', f32),
-                                         _dev(loss, 'loss'), _dev(gcls, 'grad_cls'), _dev(gbox, 'grad_box'), nl, b, qs, qt, c,
-                                         s_box.shape[-1], 1 if reweight_score else 0, float(loss_cls_weight), float(loss_reg_weight),
-                                         _stream())
-    _lib.check(code, 'gd4d_distill_loss_fwd_bwd')
+    _call('gd4d_distill_loss_fwd_bwd', _dev(s_cls, 's_cls', F32), _dev(s_box, 's_box', F32), _dev(t_cls, 't_cls', F32),
+          _dev(t_box, 't_box', F32), _dev(assigned, 'assigned', I32), _dev(code_weights, 'code_weights', F32),
+          _dev(avg_factors, 'avg_factors', F32), _dev(loss, 'loss'), _dev(gcls, 'grad_cls'), _dev(gbox, 'grad_box'), nl, b, qs, qt, c,
+          s_box.shape[-1], 1 if reweight_score else 0, float(loss_cls_weight), float(loss_reg_weight))
     return loss, gcls, gbox
 
 
@@ -1858,10 +1625,7 @@ def _feat_distill_levels(levels, name, like=None):
         raise ValueError(f'{name}: levels (R, C, H_l, W_l) with the same R and C expected')
     if like is not None and [tuple(t.shape) for t in levels] != [tuple(t.shape) for t in like]:
         raise ValueError(f'{name}: the levels\' shapes differ from the other pyramid\'s')
-    nl = len(levels)
-    ptrs = (ctypes.c_void_p * nl)(*[_dev(t, name, torch.float32).value for t in levels])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for t in levels for x in t.shape[2:]])
-    return ptrs, lv, int(levels[0].shape[0])
+    return _ptrs(levels, name), _levels(levels), int(levels[0].shape[0])
 
 
 def feat_distill_stats_fwd(teacher, temperature=0.5):
@@ -1869,17 +1633,14 @@ def feat_distill_stats_fwd(teacher, temperature=0.5):
     'attention' type (mix_distill.py:131-135), one pass over each level: a_c[l] (R, H_l W_l) = 256 softmax_p(mean_c |t| / T) and
     a_s[l] (R, 256) = H W softmax_c(mean_p |t| / T)."""
     lib = _lib.load()
-    f32 = torch.float32
     tp, lv, r = _feat_distill_levels(teacher, 'teacher')
     nl, c, dev = len(teacher), int(teacher[0].shape[1]), teacher[0].device
-    a_c = [torch.empty(r, t.shape[2] * t.shape[3], device=dev, dtype=f32) for t in teacher]
-    a_s = [torch.empty(r, c, device=dev, dtype=f32) for t in teacher]
-    ws = torch.empty(max(int(lib.gd4d_feat_distill_stats_workspace_bytes(lv, nl, r)), 16), device=dev, dtype=torch.uint8)
-    cp = (ctypes.c_void_p * nl)(*[_dev(t, 'a_c', f32).value for t in a_c])
-    sp = (ctypes.c_void_p * nl)(*[_dev(t, 'a_s', f32).value for t in a_s])
-    code = lib.gd4d_feat_distill_stats_fwd(tp, lv, nl, r, c, float(temperature), cp, sp, _dev(ws, 'workspace', torch.uint8), ws.numel(),
-                                           _stream())
-    _lib.check(code, 'gd4d_feat_distill_stats_fwd')
+    a_c = [torch.empty(r, t.shape[2] * t.shape[3], device=dev, dtype=F32) for t in teacher]
+    a_s = [torch.empty(r, c, device=dev, dtype=F32) for t in teacher]
+    ws = torch.empty(max(int(lib.gd4d_feat_distill_stats_workspace_bytes(lv, nl, r)), 16), device=dev, dtype=U8)
+    cp = _ptrs(a_c, 'a_c')
+    sp = _ptrs(a_s, 'a_s')
+    _call('gd4d_feat_distill_stats_fwd', tp, lv, nl, r, c, float(temperature), cp, sp, _dev(ws, 'workspace', U8), ws.numel())
     return a_c, a_s
 
 
@@ -1889,7 +1650,6 @@ def feat_distill_fwd(student, teacher, weight, bias, loss_weight, a_c=None, a_s=
     loss = loss_weight / L * sum_l mean(a_c a_s (conv_l(student_l) - teacher_l)^2); a_c / a_s from feat_distill_stats_fwd, or None for
     the vanilla type (plain mse).  The converted student map is never materialised."""
     lib = _lib.load()
-    f32 = torch.float32
     sp, lv, r = _feat_distill_levels(student, 'student')
     tp, _, _ = _feat_distill_levels(teacher, 'teacher', like=student)
     nl, c, dev = len(student), int(student[0].shape[1]), student[0].device
@@ -1902,17 +1662,15 @@ def feat_distill_fwd(student, teacher, weight, bias, loss_weight, a_c=None, a_s=
         if len(a_c) != nl or len(a_s) != nl or any(tuple(m.shape) != (r, s.shape[2] * s.shape[3]) for m, s in zip(a_c, student)) or \
                 any(tuple(m.shape) != (r, c) for m in a_s):
             raise ValueError('feat_distill_fwd: a_c[l] (R, H_l W_l) and a_s[l] (R, C) expected')
-        cp = (ctypes.c_void_p * nl)(*[_dev(t, 'a_c', f32).value for t in a_c])
-        ap = (ctypes.c_void_p * nl)(*[_dev(t, 'a_s', f32).value for t in a_s])
-    loss = torch.empty(1, device=dev, dtype=f32)
+        cp = _ptrs(a_c, 'a_c')
+        ap = _ptrs(a_s, 'a_s')
+    loss = torch.empty(1, device=dev, dtype=F32)
     gx = [torch.empty_like(s) for s in student]
     gw, gb = torch.empty_like(weight), torch.empty_like(bias)
-    gp = (ctypes.c_void_p * nl)(*[_dev(t, 'grad_student', f32).value for t in gx])
-    ws = torch.empty(max(int(lib.gd4d_feat_distill_workspace_bytes(lv, nl, r)), 16), device=dev, dtype=torch.uint8)
-    code = lib.gd4d_feat_distill_fwd(sp, tp, lv, nl, r, c, _dev(weight, 'weight', f32), _dev(bias, 'bias', f32), cp, ap, float(loss_weight),
-                                     _dev(loss, 'loss', f32), gp, _dev(gw, 'grad_weight', f32), _dev(gb, 'grad_bias', f32),
-                                     _dev(ws, 'workspace', torch.uint8), ws.numel(), _stream())
-    _lib.check(code, 'gd4d_feat_distill_fwd')
+    gp = _ptrs(gx, 'grad_student')
+    ws = torch.empty(max(int(lib.gd4d_feat_distill_workspace_bytes(lv, nl, r)), 16), device=dev, dtype=U8)
+    _call('gd4d_feat_distill_fwd', sp, tp, lv, nl, r, c, _dev(weight, 'weight', F32), _dev(bias, 'bias', F32), cp, ap, float(loss_weight),
+          _dev(loss, 'loss', F32), gp, _dev(gw, 'grad_weight', F32), _dev(gb, 'grad_bias', F32), _dev(ws, 'workspace', U8), ws.numel())
     return loss, gx, gw, gb
 
 
@@ -1937,7 +1695,7 @@ def _rows(t, name):
     dimensions collapse to rows of one stride (a contiguous tensor or a last-dim slice of one)."""
     if t is None:
         return None, 0
-    if not t.is_cuda or t.dtype != torch.float32:
+    if not t.is_cuda or t.dtype != F32:
         raise _lib.Gd4dError(f'{name} must be a float32 GPU tensor')
     if t.dim() == 1:
         return t.data_ptr(), 0
@@ -2039,7 +1797,7 @@ def chain_weight_image(weight, exact=False):
     """The bf16 hi / lo (exact: hi / mid / lo) MFMA-fragment image of a (N, K) fp32 weight (gd4d_chain_weight_image[_exact]),
     kept while the weight does not change (invalidate_chain_images) - one small launch after a load_state_dict or an optimizer
     step, none in steady-state inference."""
-    if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 2 or weight.stride(1) != 1 \
+    if not weight.is_cuda or weight.dtype != F32 or weight.dim() != 2 or weight.stride(1) != 1 \
             or weight.stride(0) != weight.shape[1]:
         raise ValueError('chain weights must be dense (N, K) float32 GPU tensors')
 
@@ -2049,11 +1807,10 @@ def chain_weight_image(weight, exact=False):
         nbytes = (lib.gd4d_chain_weight_image_exact_bytes if exact else lib.gd4d_chain_weight_image_bytes)(n, k)
         if nbytes == 0:
             raise _lib.Gd4dError(f'chain GEMM: K = {k} must be a multiple of 64')
-        img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
+        img = torch.empty(nbytes, device=weight.device, dtype=U8)
         with torch.cuda.device(weight.device):
-            fn = lib.gd4d_chain_weight_image_exact if exact else lib.gd4d_chain_weight_image
-            code = fn(ctypes.c_void_p(weight.data_ptr()), n, k, ctypes.c_void_p(img.data_ptr()), _stream())
-        _lib.check(code, 'gd4d_chain_weight_image')
+            _call('gd4d_chain_weight_image_exact' if exact else 'gd4d_chain_weight_image', ctypes.c_void_p(weight.data_ptr()), n, k,
+                  ctypes.c_void_p(img.data_ptr()))
         return img
     return _kept(_CHAIN_IMAGES, (weight.data_ptr(), tuple(weight.shape), bool(exact)), (weight,), build)
 
@@ -2087,7 +1844,7 @@ class ImageSet:
             raise ValueError('an image stacks one to three row blocks')
         seg, rows = (ctypes.c_void_p * 3)(), (ctypes.c_int32 * 3)()
         for i, t in enumerate(tensors):
-            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() % cols:
+            if not t.is_cuda or t.dtype != F32 or not t.is_contiguous() or t.numel() % cols:
                 raise ValueError('image sources must be dense float32 GPU tensors of `cols` columns')
             seg[i], rows[i] = t.data_ptr(), t.numel() // cols
             self.sources.append(t)
@@ -2101,7 +1858,7 @@ class ImageSet:
         kp = (k + 63) // 64 * 64
         planes = 3 if exact else 2
         frags = (n + 15) // 16 * (kp // 32)
-        img = torch.empty(frags * planes * 1024, device=self.device, dtype=torch.uint8)
+        img = torch.empty(frags * planes * 1024, device=self.device, dtype=U8)
         self._jobs.append(ImageJob(seg=seg, rows=rows, cols=cols, transposed=int(transposed), planes=planes, frag0=self._frags,
                                    image=img.data_ptr()))
         self._frags += frags
@@ -2111,7 +1868,7 @@ class ImageSet:
     def add_concat(self, vectors):
         """fp32 concatenation of 1-D tensors (a stacked bias), refreshed with the images."""
         seg, rows, r = self._segments(vectors, 1)
-        out = torch.empty(r, device=self.device, dtype=torch.float32)
+        out = torch.empty(r, device=self.device, dtype=F32)
         self._jobs.append(ImageJob(seg=seg, rows=rows, cols=1, transposed=0, planes=0, frag0=self._frags, image=out.data_ptr()))
         self._frags += (r + 63) // 64
         self._table = None
@@ -2124,17 +1881,15 @@ class ImageSet:
         """Upload the job table (a host-to-device copy: call it outside a graph capture; refresh() does it on first use)."""
         if self._table is None:
             arr = (ImageJob * len(self._jobs))(*self._jobs)
-            raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+            raw = torch.frombuffer(bytearray(bytes(arr)), dtype=U8)
             self._table = raw.to(self.device)
 
     def refresh(self):
-        lib = _lib.load()
         self.finalize()
         if len(self._jobs) > 1024:
             raise _lib.Gd4dError('ImageSet: more than 1024 jobs (GD4D_IMAGE_JOBS_MAX) - split the set')
         with torch.cuda.device(self.device):
-            code = lib.gd4d_chain_weight_image_group(ctypes.c_void_p(self._table.data_ptr()), len(self._jobs), self._frags, _stream())
-        _lib.check(code, 'gd4d_chain_weight_image_group')
+            _call('gd4d_chain_weight_image_group', ctypes.c_void_p(self._table.data_ptr()), len(self._jobs), self._frags)
 
 
 def _image_of(weight, exact=False):
@@ -2300,8 +2055,8 @@ def chain_headgemm(agg, wsum, weight, bias=None, dst=-1, res=-1, out=None, adden
     g, ldg = _rows(out if addend is None else addend, 'out')
     return ChainOp(kind=CHAIN_HEADGEMM, src=-1, dst=dst, res=res, K=k, N=n, ld0=heads, ldg=ldg, p0=img,
                    flags=CHAIN_ADD_GOUT if addend is not None else 0,
-                   p1=None if bias is None else bias.data_ptr(), p2=_dev(agg, 'agg', torch.float32).value,
-                   p3=_dev(wsum, 'wsum', torch.float32).value, gout=g)
+                   p1=None if bias is None else bias.data_ptr(), p2=_dev(agg, 'agg', F32).value,
+                   p3=_dev(wsum, 'wsum', F32).value, gout=g)
 
 
 def chain_small_linear(src, weight, bias, dst, relu=False, inv_sigmoid=False, out=None):
@@ -2320,7 +2075,7 @@ def chain_layernorm_bwd(src, x_buf, norm, dst=-1, relu=False, out=None, part=Non
     p3, ld3 = (None, 0) if isinstance(x_buf, int) else _rows(x_buf, 'x')
     return ChainOp(kind=CHAIN_LN_BWD, src=src, dst=dst, res=x_buf if isinstance(x_buf, int) else -1, N=norm.weight.shape[0],
                    eps=float(norm.eps), flags=CHAIN_RELU if relu else 0, ldg=ldg, ld1=ld3, p0=norm.weight.data_ptr(),
-                   p1=norm.bias.data_ptr(), p2=None if part is None else _dev(part, 'part', torch.float32).value, gout=g, p3=p3)
+                   p1=norm.bias.data_ptr(), p2=None if part is None else _dev(part, 'part', F32).value, gout=g, p3=p3)
 
 
 def chain_layernorm(src, norm, dst=-1, relu=False, out=None, dst2=-1, add=None):
@@ -2351,7 +2106,7 @@ def chain_refine(src, ref, out, dst=-1):
 def chain_signal(flags):
     """Two-program launches: publish this program's global outputs of its 16 rows to the other program (flags: int32 tensor
     of >= ceil(M / 16) zeros, one per row block)."""
-    return ChainOp(kind=CHAIN_SIGNAL, src=-1, dst=-1, res=-1, gout=_dev(flags, 'flags', torch.int32).value)
+    return ChainOp(kind=CHAIN_SIGNAL, src=-1, dst=-1, res=-1, gout=_dev(flags, 'flags', I32).value)
 
 
 _HANDOFF = {}       # device index -> {'word': int32[1] on the device, 'pinned': int32[1] host, 'event': Event or None, 'placement': bool}
@@ -2373,7 +2128,7 @@ def handoff_error_word(device):
     one, and check_handoff() / poll_handoff() turn it into an exception."""
     st = _handoff_state(device)
     if st['word'] is None:
-        st['word'] = torch.zeros(1, device=st['dev'], dtype=torch.int32)
+        st['word'] = torch.zeros(1, device=st['dev'], dtype=I32)
     return st['word']
 
 
@@ -2389,8 +2144,8 @@ def handoff_flags(device, rows, cols, slot_key):
     buf = _HANDOFF_FLAGS.get(key)
     if buf is None:
         if torch.cuda.is_current_stream_capturing():
-            return torch.zeros(rows, cols, device=device, dtype=torch.int32)       # (first use inside a capture: this graph's own, filled per replay)
-        buf = _HANDOFF_FLAGS[key] = torch.zeros(rows, cols, device=device, dtype=torch.int32)
+            return torch.zeros(rows, cols, device=device, dtype=I32)       # (first use inside a capture: this graph's own, filled per replay)
+        buf = _HANDOFF_FLAGS[key] = torch.zeros(rows, cols, device=device, dtype=I32)
     return buf
 
 
@@ -2429,7 +2184,7 @@ def poll_handoff(device):
             check_handoff(device)
     if st['event'] is None:
         if st['pinned'] is None:
-            st['pinned'] = torch.zeros(1, dtype=torch.int32).pin_memory()
+            st['pinned'] = torch.zeros(1, dtype=I32).pin_memory()
         st['pinned'].copy_(st['word'], non_blocking=True)
         st['event'] = torch.cuda.Event()
         st['event'].record()
@@ -2447,12 +2202,11 @@ def handoff_placement_ok(device):
             warnings.warn('graph-detr4d_amd: first use inside a graph capture - the XCD placement self-test cannot run, the step is '
                           'built without SIGNAL / WAIT hand-offs (run one eager forward before capturing to get them)')
             return False
-        lib = _lib.load()
         idx = torch.device(device).index
         with torch.cuda.device(idx if idx is not None else torch.cuda.current_device()):
             blocks = 2048
-            out = torch.full((blocks,), -1, device=st['dev'], dtype=torch.int32)
-            _lib.check(lib.gd4d_xcd_placement_probe(_dev(out, 'out', torch.int32), blocks, _stream()), 'gd4d_xcd_placement_probe')
+            out = torch.full((blocks,), -1, device=st['dev'], dtype=I32)
+            _call('gd4d_xcd_placement_probe', _dev(out, 'out', I32), blocks)
             ids = out.cpu()
         # (the probe's own shape: 2048 workgroups of one wave on the current stream; a time-out later on turns the hand-offs off
         #  for the device, check_handoff)
@@ -2476,8 +2230,8 @@ def chain_wait(flags, errors=None):
     """Two-program launches: hold this program until the other program's workgroup of the same 16 rows has signalled on
     `flags`; errors: int32 tensor (1 element) that counts waits that gave up (handoff_error_word()).  A WAIT that gives up
     poisons what the program LOADs afterwards (NaN)."""
-    return ChainOp(kind=CHAIN_WAIT, src=-1, dst=-1, res=-1, p0=_dev(flags, 'flags', torch.int32).value,
-                   gout=None if errors is None else _dev(errors, 'errors', torch.int32).value)
+    return ChainOp(kind=CHAIN_WAIT, src=-1, dst=-1, res=-1, p0=_dev(flags, 'flags', I32).value,
+                   gout=None if errors is None else _dev(errors, 'errors', I32).value)
 
 
 class ChainGuest(ctypes.Structure):
@@ -2493,17 +2247,15 @@ _VP_IMAGES = {}
 def value_proj_image(weight, bias=None):
     """gd4d_value_proj_image of a layer's value_proj (256, 256) weight and bias: the split-bf16 fragment image the guests of
     row_chain_fwd(..., guest=) stream through LDS, kept while neither changes (invalidate_chain_images)."""
-    if not weight.is_cuda or weight.dtype != torch.float32 or tuple(weight.shape) != (256, 256) or not weight.is_contiguous():
+    if not weight.is_cuda or weight.dtype != F32 or tuple(weight.shape) != (256, 256) or not weight.is_contiguous():
         raise ValueError('value_proj_image: a contiguous (256, 256) float32 GPU weight')
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != 256 or not bias.is_contiguous() or bias.device != weight.device):
+    if bias is not None and (bias.dtype != F32 or bias.numel() != 256 or not bias.is_contiguous() or bias.device != weight.device):
         raise ValueError('value_proj_image: bias (256) float32 on the weight\'s GPU')
 
     def build():
         lib = _lib.load()
-        img = torch.empty(int(lib.gd4d_value_proj_image_bytes()), device=weight.device, dtype=torch.uint8)
-        code = lib.gd4d_value_proj_image(_dev(weight, 'weight', torch.float32), None if bias is None else _dev(bias, 'bias', torch.float32),
-                                         _dev(img, 'image'), _stream())          # (_on_tensor_device: the weight's device is current)
-        _lib.check(code, 'gd4d_value_proj_image')
+        img = torch.empty(int(lib.gd4d_value_proj_image_bytes()), device=weight.device, dtype=U8)
+        _call('gd4d_value_proj_image', _dev(weight, 'weight', F32), _opt(bias, 'bias'), _dev(img, 'image'))          # (_on_tensor_device: the weight's device is current)
         return img
     return _kept(_VP_IMAGES, (weight.data_ptr(), None if bias is None else bias.data_ptr()), (weight, bias), build)
 
@@ -2514,11 +2266,11 @@ def chain_guest(levels, image, out, workgroups=0):
     chlast = [PyramidView.is_channels_last_level(t) and not t.is_contiguous() for t in levels]
     if any(chlast) != all(chlast) or (not any(chlast) and not all(t.is_contiguous() for t in levels)):
         raise ValueError('chain_guest: the levels must be all NCHW-contiguous or all channels-last')
-    if any(t.dtype != torch.float32 or not t.is_cuda or t.shape[-3] != 256 for t in levels) or len(levels) > 4:
+    if any(t.dtype != F32 or not t.is_cuda or t.shape[-3] != 256 for t in levels) or len(levels) > 4:
         raise ValueError('chain_guest: up to 4 float32 GPU levels of 256 channels')
     r = levels[0].numel() // (256 * levels[0].shape[-1] * levels[0].shape[-2])
     s = sum(t.shape[-1] * t.shape[-2] for t in levels)
-    if tuple(out.shape) != (r, s, 256) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != levels[0].device:
+    if tuple(out.shape) != (r, s, 256) or out.dtype != F32 or not out.is_contiguous() or out.device != levels[0].device:
         raise ValueError(f'chain_guest: out must be ({r}, {s}, 256) float32, contiguous')
     g = ChainGuest()
     for i, t in enumerate(levels):
@@ -2532,19 +2284,7 @@ def chain_guest(levels, image, out, workgroups=0):
 
 def value_proj_guest_fwd(guest, max_cus=0):
     """gd4d_value_proj_guest_fwd: a ChainGuest's job as a launch of its own."""
-    code = _lib.load().gd4d_value_proj_guest_fwd(ctypes.byref(guest), int(max_cus), _stream())
-    _lib.check(code, 'gd4d_value_proj_guest_fwd')
-
-
-def _chain_fills(lib, a, na, b, nb, m, fills):
-    """gd4d_row_chain_fill_fwd: the chain launch carries `fills` (PyramidGrad.take_fills) as guest workgroups."""
-    jobs, start, records, fb, fn, fhh = fills
-    arr = (FillJob * len(jobs))(*[FillJob(_dev(pl.buf, 'plan', torch.uint8).value, _dev(sl, 'slots').value,
-                                           None if pl.order is None else _order_ptr(pl.order, fb * pl.q).value, int(base), int(pl.q))
-                                   for pl, sl, base in jobs])
-    code = lib.gd4d_row_chain_fill_fwd(a, na, b, nb, int(m), arr, len(jobs), _dev(start, 'start', torch.int32), _dev(records, 'records'),
-                                       fb, fn, fhh, int(jobs[0][0].points), 0, _stream())
-    _lib.check(code, 'gd4d_row_chain_fill_fwd')
+    _call('gd4d_value_proj_guest_fwd', ctypes.byref(guest), int(max_cus))
 
 
 def row_chain_fwd(program, m, guest=None, fills=None):
@@ -2552,54 +2292,45 @@ def row_chain_fwd(program, m, guest=None, fills=None):
     stay alive until the stream has run it - the callers keep them in locals / return them).  guest (ChainGuest): the launch
     also carries that value_proj job on the compute units the chain leaves idle (gd4d_row_chain_guest_fwd).  fills (training;
     PyramidGrad.take_fills): it carries those record fills of the pyramid gradient (gd4d_row_chain_fill_fwd)."""
-    lib = _lib.load()
     arr = (ChainOp * len(program))(*program)
-    if fills is not None:
-        return _chain_fills(lib, arr, len(program), None, 0, m, fills)
-    if guest is not None:
-        code = lib.gd4d_row_chain_guest_fwd(arr, len(program), None, 0, int(m), ctypes.byref(guest), _stream())
-        _lib.check(code, 'gd4d_row_chain_guest_fwd')
-        return
-    code = lib.gd4d_row_chain_fwd(arr, len(program), int(m), _stream())
-    _lib.check(code, 'gd4d_row_chain_fwd')
+    if fills is not None:       # (as guest workgroups of the chain launch)
+        _call('gd4d_row_chain_fill_fwd', arr, len(program), None, 0, int(m), *_fill_args(fills), 0)
+    elif guest is not None:
+        _call('gd4d_row_chain_guest_fwd', arr, len(program), None, 0, int(m), ctypes.byref(guest))
+    else:
+        _call('gd4d_row_chain_fwd', arr, len(program), int(m))
 
 
 def row_chain2_fwd(program_a, program_b, m, guest=None, fills=None):
     """gd4d_row_chain2_fwd: two independent programs over the same `m` rows in one launch (each on its own workgroups);
     guest / fills as row_chain_fwd."""
-    lib = _lib.load()
     a = (ChainOp * len(program_a))(*program_a)
     b = (ChainOp * len(program_b))(*program_b)
     if fills is not None:
-        return _chain_fills(lib, a, len(program_a), b, len(program_b), m, fills)
-    if guest is not None:
-        code = lib.gd4d_row_chain_guest_fwd(a, len(program_a), b, len(program_b), int(m), ctypes.byref(guest), _stream())
-        _lib.check(code, 'gd4d_row_chain_guest_fwd')
-        return
-    code = lib.gd4d_row_chain2_fwd(a, len(program_a), b, len(program_b), int(m), _stream())
-    _lib.check(code, 'gd4d_row_chain2_fwd')
+        _call('gd4d_row_chain_fill_fwd', a, len(program_a), b, len(program_b), int(m), *_fill_args(fills), 0)
+    elif guest is not None:
+        _call('gd4d_row_chain_guest_fwd', a, len(program_a), b, len(program_b), int(m), ctypes.byref(guest))
+    else:
+        _call('gd4d_row_chain2_fwd', a, len(program_a), b, len(program_b), int(m))
 
 
 def mha_core_presplit_fwd(q, kv, num_heads, attn_mask=None, want_lse=False, dropout_p=0., seed=None):
     """gd4d_mha_core_presplit_fwd: the self-attention core (batch 1) on K / V planes a chain GEMM wrote (KVPlanes).
     q (M, 1, C); attn_mask, want_lse, dropout_p / seed as for mha_core_fwd.  Returns (M, 1, C) [, lse]; without dropout
     bit-identical to mha_core_fwd on the fp32 rows."""
-    lib = _lib.load()
     lq, b, c = q.shape
     _, _, _, _, _, _, kind, mptr, keep = _mha_args(q, q, q, num_heads, attn_mask)
     if b != 1 or lq != kv.m or c != kv.c or num_heads != kv.heads:
         raise ValueError('mha_core_presplit_fwd: batch 1, the planes of these rows')
-    if not q.is_cuda or q.dtype != torch.float32 or q.stride(2) != 1:
+    if not q.is_cuda or q.dtype != F32 or q.stride(2) != 1:
         raise _lib.Gd4dError('q must be a float32 GPU tensor with unit channel stride')
     d = c // num_heads
-    out = torch.empty(lq, 1, c, device=q.device, dtype=torch.float32)
-    lse = torch.empty(lq, 1, num_heads, device=q.device, dtype=torch.float32) if want_lse else None
+    out = torch.empty(lq, 1, c, device=q.device, dtype=F32)
+    lse = torch.empty(lq, 1, num_heads, device=q.device, dtype=F32) if want_lse else None
     sptr = _mha_seed(dropout_p, seed, q.device)
-    code = lib.gd4d_mha_core_presplit_fwd(ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(kv.k.data_ptr()),
-                                          ctypes.c_void_p(kv.v.data_ptr()), _dev(out, 'out'), lq, num_heads, d, q.stride(0), c,
-                                          kv.k[0].numel(), kv.v[0].numel(), mptr, kind, 1.0 / (d ** 0.5),
-                                          None if lse is None else _dev(lse, 'lse'), float(dropout_p), sptr, _stream())
-    _lib.check(code, 'gd4d_mha_core_presplit_fwd')
+    _call('gd4d_mha_core_presplit_fwd', ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(kv.k.data_ptr()), ctypes.c_void_p(kv.v.data_ptr()),
+          _dev(out, 'out'), lq, num_heads, d, q.stride(0), c, kv.k[0].numel(), kv.v[0].numel(), mptr, kind, 1.0 / (d ** 0.5),
+          _opt(lse, 'lse', None), float(dropout_p), sptr)
     return (out, lse) if want_lse else out
 
 
@@ -2872,9 +2603,8 @@ def _weight_image(entry, nbytes, unsupported, weight, *dims, name='weight'):
     raises `unsupported`) of device memory, filled by lib.<entry>(weight, *dims, image, stream)."""
     if nbytes == 0:
         raise _lib.Gd4dError(unsupported)
-    img = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
-    code = getattr(_lib.load(), entry)(_dev(weight.contiguous(), name, torch.float32), *dims, _dev(img, 'image', torch.uint8), _stream())
-    _lib.check(code, entry)
+    img = torch.empty(nbytes, device=weight.device, dtype=U8)
+    _call(entry, _dev(weight.contiguous(), name, F32), *dims, _dev(img, 'image', U8))
     return img
 
 
@@ -2892,22 +2622,15 @@ def cam_gate_fwd(intrinsics, ida00, fc1_w, fc1_b, fc2_w, fc2_b, se_reduce_w, se_
     """gd4d_cam_gate_fwd: intrinsics (N, 4, 4), ida00 (1 or N) = ida[..., 0, 0] -> the camera gate (N, 256) =
     sigmoid(se(mlp(pixel_size * scale_depth_factor / aug_scale))) of DepthNet.forward (detr3d_head_pe_camaware.py:86-100).
     The weights as the modules hold them (mlp.fc1 (256, 1), 1x1 convolutions (256, 256, 1, 1))."""
-    lib = _lib.load()
-    f32 = torch.float32
     n = intrinsics.shape[0]
     if tuple(intrinsics.shape) != (n, 4, 4) or ida00.dim() != 1:
         raise ValueError('cam_gate_fwd: intrinsics (N, 4, 4) and ida00 (1 or N) expected')
     c = fc2_w.shape[0]
-    if out is None:
-        out = torch.empty(n, c, device=intrinsics.device, dtype=f32)
-    elif tuple(out.shape) != (n, c):
-        raise ValueError(f'cam_gate_fwd: out must be ({n}, {c})')
+    out = _out(out, (n, c), intrinsics.device, 'cam_gate_fwd: out')
     w = [t.detach().contiguous() for t in (fc1_w, fc1_b, fc2_w, fc2_b, se_reduce_w, se_reduce_b, se_expand_w, se_expand_b)]
     names = ('fc1_w', 'fc1_b', 'fc2_w', 'fc2_b', 'se_reduce_w', 'se_reduce_b', 'se_expand_w', 'se_expand_b')
-    code = lib.gd4d_cam_gate_fwd(_dev(intrinsics, 'intrinsics', f32), _dev(ida00, 'ida00', f32), int(n), int(ida00.shape[0]),
-                                 float(scale_depth_factor), *[_dev(t, nm, f32) for t, nm in zip(w, names)], int(c),
-                                 _dev(out, 'out', f32), _stream())
-    _lib.check(code, 'gd4d_cam_gate_fwd')
+    _call('gd4d_cam_gate_fwd', _dev(intrinsics, 'intrinsics', F32), _dev(ida00, 'ida00', F32), int(n), int(ida00.shape[0]),
+          float(scale_depth_factor), *[_dev(t, nm, F32) for t, nm in zip(w, names)], int(c), _dev(out, 'out', F32))
     return out
 
 
@@ -2915,24 +2638,20 @@ def depth_conv_fwd(feats, image, bias, bn_mean, bn_var, bn_weight, bn_bias, eps,
     """gd4d_depth_conv_fwd: L <= 4 levels (N, 256, H_l, W_l) fp32 NCHW -> relu(BN(conv3x3(x) + bias)) * gate[:, :, None, None]
     per level, all levels in one launch.  image = depth_net_image(reduce_conv[0].weight); BN with its running statistics;
     gate (N, 256) (cam_gate_fwd).  outs: the L (N, 256, H_l, W_l) tensors to write."""
-    lib = _lib.load()
-    f32 = torch.float32
     nl = len(feats)
     n = feats[0].shape[0]
     if any(f.dim() != 4 or f.shape[0] != n or f.shape[1] != feats[0].shape[1] for f in feats):
         raise ValueError('depth_conv_fwd: levels (N, C, H, W) with the same N and C expected')
     if outs is None:
-        outs = [torch.empty(f.shape, device=f.device, dtype=f32) for f in feats]
+        outs = [torch.empty(f.shape, device=f.device, dtype=F32) for f in feats]
     elif len(outs) != nl or any(tuple(o.shape) != tuple(f.shape) for o, f in zip(outs, feats)):
         raise ValueError('depth_conv_fwd: outs must match the levels\' shapes')
-    fp = (ctypes.c_void_p * nl)(*[_dev(f, 'feats', f32).value for f in feats])
-    op = (ctypes.c_void_p * nl)(*[_dev(o, 'outs', f32).value for o in outs])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in feats for x in f.shape[2:]])
-    code = lib.gd4d_depth_conv_fwd(fp, op, lv, nl, int(n), int(feats[0].shape[1]), _dev(image, 'image', torch.uint8),
-                                   _dev(bias, 'bias', f32), _dev(bn_mean, 'bn_mean', f32), _dev(bn_var, 'bn_var', f32),
-                                   _dev(bn_weight, 'bn_weight', f32), _dev(bn_bias, 'bn_bias', f32), float(eps),
-                                   _dev(gate, 'gate', f32), _stream())
-    _lib.check(code, 'gd4d_depth_conv_fwd')
+    fp = _ptrs(feats, 'feats')
+    op = _ptrs(outs, 'outs')
+    lv = _levels(feats)
+    _call('gd4d_depth_conv_fwd', fp, op, lv, nl, int(n), int(feats[0].shape[1]), _dev(image, 'image', U8), _dev(bias, 'bias', F32),
+          _dev(bn_mean, 'bn_mean', F32), _dev(bn_var, 'bn_var', F32), _dev(bn_weight, 'bn_weight', F32), _dev(bn_bias, 'bn_bias', F32),
+          float(eps), _dev(gate, 'gate', F32))
     return outs
 
 
@@ -2945,12 +2664,7 @@ def _depth_levels(what, *lists):
     for other in lists[1:]:
         if len(other) != nl or any(tuple(o.shape) != tuple(f.shape) for o, f in zip(other, first)):
             raise ValueError(f'{what}: every list must match the levels\' shapes')
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(x) for f in first for x in f.shape[2:]])
-    return nl, int(n), int(c), lv
-
-
-def _depth_ptrs(tensors, name):
-    return (ctypes.c_void_p * len(tensors))(*[_dev(t, name, torch.float32).value for t in tensors])
+    return nl, int(n), int(c), _levels(first)
 
 
 def depth_net_image_t(conv_w):
@@ -2964,7 +2678,7 @@ def depth_net_image_t(conv_w):
 
 def depth_conv_tiles(level_hw, n):
     """gd4d_depth_conv_tiles: the number of 16 x 16 tiles of the levels [(H, W), ...] with N cameras (the conv's grid)."""
-    lv = (ctypes.c_int32 * (2 * len(level_hw)))(*[int(v) for hw in level_hw for v in hw])
+    lv = _levels(level_hw)
     return int(_lib.load().gd4d_depth_conv_tiles(lv, len(level_hw), int(n)))
 
 
@@ -2972,51 +2686,41 @@ def depth_conv_raw(feats, image, bias=None, want_partials=False, outs=None):
     """gd4d_depth_conv_raw: L <= 4 levels (N, 256, H_l, W_l) -> conv3x3 (+ bias) per level, one launch, no BatchNorm / ReLU / gate.
     want_partials: also returns the (tiles, 2, 256) per-tile mean / M2 partials depth_bn_stats merges."""
     lib = _lib.load()
-    f32 = torch.float32
     if outs is None:
-        outs = [torch.empty(f.shape, device=f.device, dtype=f32) for f in feats]
+        outs = [torch.empty(f.shape, device=f.device, dtype=F32) for f in feats]
     nl, n, c, lv = _depth_levels('depth_conv_raw', feats, outs)
     partials = None
     if want_partials:
         tiles = int(lib.gd4d_depth_conv_tiles(lv, nl, n))
-        partials = torch.empty(max(tiles, 1), 2, 256, device=feats[0].device, dtype=f32)
-    code = lib.gd4d_depth_conv_raw(_depth_ptrs(feats, 'feats'), _depth_ptrs(outs, 'outs'), lv, nl, n, c, _dev(image, 'image', torch.uint8),
-                                   None if bias is None else _dev(bias, 'bias', f32),
-                                   None if partials is None else _dev(partials, 'partials', f32), _stream())
-    _lib.check(code, 'gd4d_depth_conv_raw')
+        partials = torch.empty(max(tiles, 1), 2, 256, device=feats[0].device, dtype=F32)
+    _call('gd4d_depth_conv_raw', _ptrs(feats, 'feats'), _ptrs(outs, 'outs'), lv, nl, n, c, _dev(image, 'image', U8), _opt(bias, 'bias'),
+          _opt(partials, 'partials'))
     return (outs, partials) if want_partials else outs
 
 
 def depth_bn_stats(partials, level_hw, n, bn_weight, running_mean, running_var, momentum, eps, frozen=False):
     """gd4d_depth_bn_stats: stats (L, 3, 256) = mu, rstd, scale per level from depth_conv_raw's partials (frozen: from the running
     buffers, partials may be None); not frozen: running_mean / running_var are updated in place, level after level."""
-    lib = _lib.load()
-    f32 = torch.float32
     nl = len(level_hw)
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(v) for hw in level_hw for v in hw])
+    lv = _levels(level_hw)
     if not frozen and partials is None:
         raise ValueError('depth_bn_stats: partials are needed unless frozen')
-    stats = torch.empty(nl, 3, 256, device=bn_weight.device, dtype=f32)
-    code = lib.gd4d_depth_bn_stats(None if partials is None else _dev(partials, 'partials', f32), lv, nl, int(n), int(bn_weight.shape[0]),
-                                   _dev(bn_weight, 'bn_weight', f32), _dev(running_mean, 'running_mean', f32),
-                                   _dev(running_var, 'running_var', f32), float(momentum), float(eps), int(bool(frozen)),
-                                   _dev(stats, 'stats', f32), _stream())
-    _lib.check(code, 'gd4d_depth_bn_stats')
+    stats = torch.empty(nl, 3, 256, device=bn_weight.device, dtype=F32)
+    _call('gd4d_depth_bn_stats', _opt(partials, 'partials'), lv, nl, int(n), int(bn_weight.shape[0]), _dev(bn_weight, 'bn_weight', F32),
+          _dev(running_mean, 'running_mean', F32), _dev(running_var, 'running_var', F32), float(momentum), float(eps), int(bool(frozen)),
+          _dev(stats, 'stats', F32))
     return stats
 
 
 def depth_bn_act_fwd(ys, stats, bn_bias, gate, outs=None):
     """gd4d_depth_bn_act_fwd: out_l = relu((y_l - mu_l) scale_l + bn_bias) * gate[:, :, None, None] for L <= 4 levels."""
-    lib = _lib.load()
-    f32 = torch.float32
     if outs is None:
         outs = [torch.empty_like(y) for y in ys]
     nl, n, c, lv = _depth_levels('depth_bn_act_fwd', ys, outs)
     if tuple(stats.shape) != (nl, 3, c) or tuple(gate.shape) != (n, c):
         raise ValueError(f'depth_bn_act_fwd: stats ({nl}, 3, {c}) and gate ({n}, {c}) expected')
-    code = lib.gd4d_depth_bn_act_fwd(_depth_ptrs(ys, 'ys'), _depth_ptrs(outs, 'outs'), lv, nl, n, c, _dev(stats, 'stats', f32),
-                                     _dev(bn_bias, 'bn_bias', f32), _dev(gate, 'gate', f32), _stream())
-    _lib.check(code, 'gd4d_depth_bn_act_fwd')
+    _call('gd4d_depth_bn_act_fwd', _ptrs(ys, 'ys'), _ptrs(outs, 'outs'), lv, nl, n, c, _dev(stats, 'stats', F32),
+          _dev(bn_bias, 'bn_bias', F32), _dev(gate, 'gate', F32))
     return outs
 
 
@@ -3024,20 +2728,17 @@ def depth_bn_bwd(douts, ys, stats, bn_bias, gate, frozen=False):
     """gd4d_depth_bn_bwd: the BatchNorm / ReLU / gate backward of L <= 4 levels -> (dy list, dgamma, dbeta, dgate (N, 256), dbias),
     dgamma / dbeta / dgate / dbias summed over the levels of the call."""
     lib = _lib.load()
-    f32 = torch.float32
     dys = [torch.empty_like(y) for y in ys]
     nl, n, c, lv = _depth_levels('depth_bn_bwd', ys, douts, dys)
     if tuple(stats.shape) != (nl, 3, c) or tuple(gate.shape) != (n, c):
         raise ValueError(f'depth_bn_bwd: stats ({nl}, 3, {c}) and gate ({n}, {c}) expected')
     dev = ys[0].device
-    ws = torch.empty(max(int(lib.gd4d_depth_bn_bwd_workspace_bytes(nl, n)) // 4, 1), device=dev, dtype=f32)
-    small = torch.empty(3 + n, c, device=dev, dtype=f32)
+    ws = torch.empty(max(int(lib.gd4d_depth_bn_bwd_workspace_bytes(nl, n)) // 4, 1), device=dev, dtype=F32)
+    small = torch.empty(3 + n, c, device=dev, dtype=F32)
     dgamma, dbeta, dbias, dgate = small[0], small[1], small[2], small[3:]
-    code = lib.gd4d_depth_bn_bwd(_depth_ptrs(douts, 'douts'), _depth_ptrs(ys, 'ys'), _depth_ptrs(dys, 'dys'), lv, nl, n, c,
-                                 _dev(stats, 'stats', f32), _dev(bn_bias, 'bn_bias', f32), _dev(gate, 'gate', f32), int(bool(frozen)),
-                                 _dev(ws, 'workspace', f32), _dev(dgamma, 'dgamma', f32), _dev(dbeta, 'dbeta', f32),
-                                 _dev(dgate, 'dgate', f32), _dev(dbias, 'dbias', f32), _stream())
-    _lib.check(code, 'gd4d_depth_bn_bwd')
+    _call('gd4d_depth_bn_bwd', _ptrs(douts, 'douts'), _ptrs(ys, 'ys'), _ptrs(dys, 'dys'), lv, nl, n, c, _dev(stats, 'stats', F32),
+          _dev(bn_bias, 'bn_bias', F32), _dev(gate, 'gate', F32), int(bool(frozen)), _dev(ws, 'workspace', F32),
+          _dev(dgamma, 'dgamma', F32), _dev(dbeta, 'dbeta', F32), _dev(dgate, 'dgate', F32), _dev(dbias, 'dbias', F32))
     return dys, dgamma, dbeta, dgate, dbias
 
 
@@ -3045,7 +2746,6 @@ def depth_conv_wgrad(dys, feats, partitions=None):
     """gd4d_depth_conv_wgrad: dW (256, 256, 3, 3) = sum over L <= 4 levels, cameras and pixels of dy[oc, p] x[ic, p + tap], one launch
     plus the reduction over `partitions` partial sums (default: one workgroup per compute unit, at most one partition per tile)."""
     lib = _lib.load()
-    f32 = torch.float32
     nl, n, c, lv = _depth_levels('depth_conv_wgrad', feats, dys)
     dev = feats[0].device
     if partitions is None:
@@ -3055,15 +2755,14 @@ def depth_conv_wgrad(dys, feats, partitions=None):
     nbytes = int(lib.gd4d_depth_conv_wgrad_workspace_bytes(partitions))
     if nbytes == 0:
         raise ValueError(f'depth_conv_wgrad: partitions = {partitions}')
-    ws = torch.empty(nbytes // 4, device=dev, dtype=f32)
-    dw = torch.empty(256, 256, 3, 3, device=dev, dtype=f32)
-    code = lib.gd4d_depth_conv_wgrad(_depth_ptrs(dys, 'dys'), _depth_ptrs(feats, 'feats'), lv, nl, n, c, partitions,
-                                     _dev(ws, 'workspace', f32), _dev(dw, 'dw', f32), _stream())
-    _lib.check(code, 'gd4d_depth_conv_wgrad')
+    ws = torch.empty(nbytes // 4, device=dev, dtype=F32)
+    dw = torch.empty(256, 256, 3, 3, device=dev, dtype=F32)
+    _call('gd4d_depth_conv_wgrad', _ptrs(dys, 'dys'), _ptrs(feats, 'feats'), lv, nl, n, c, partitions, _dev(ws, 'workspace', F32),
+          _dev(dw, 'dw', F32))
     return dw
 
 
-_GRID_MASK_DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+_GRID_MASK_DTYPES = {F32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 GRID_MASK_BLOCK_WORDS, GRID_MASK_STATE_WORDS = 8, 4
 
 
@@ -3075,15 +2774,15 @@ def _is_cl(t):
 def fpn_empty(n, h, w, device, channels_last=False):
     """An (N, 256, H, W) fp32 map for the neck's kernels to write: contiguous NCHW, or the same logical shape stored (N, H, W, 256)."""
     if channels_last:
-        return torch.empty(n, h, w, 256, device=device, dtype=torch.float32).permute(0, 3, 1, 2)
-    return torch.empty(n, 256, h, w, device=device, dtype=torch.float32)
+        return torch.empty(n, h, w, 256, device=device, dtype=F32).permute(0, 3, 1, 2)
+    return torch.empty(n, 256, h, w, device=device, dtype=F32)
 
 
 def _fpn_map(t, name):
     """(device pointer, channels-last flag) of an (N, 256, H, W) fp32 map in either of the two layouts the neck's kernels take."""
     if not t.is_cuda:
         raise _lib.Gd4dError(f'{name} must live on the GPU (no CPU fallback in graph-detr4d_amd)')
-    if t.dtype != torch.float32 or t.dim() != 4:
+    if t.dtype != F32 or t.dim() != 4:
         raise TypeError(f'{name} must be a float32 (N, C, H, W) map, got {t.dtype} {tuple(t.shape)}')
     if t.is_contiguous():
         return ctypes.c_void_p(t.data_ptr()), 0
@@ -3112,8 +2811,6 @@ def fpn_lateral_fwd(x, image, bias, up=None, out=None, channels_last_out=False):
     """gd4d_fpn_lateral_fwd: x (N, Cin, H, W) fp32 NCHW -> (conv1x1(x) + bias) + nearest-upsampled `up` (the finished coarser lateral
     (N, 256, Hc, Wc), NCHW or channels-last; None: the coarsest level).  out: the (N, 256, H, W) map to write (either layout; default a
     new one, channels-last when channels_last_out)."""
-    lib = _lib.load()
-    f32 = torch.float32
     if x.dim() != 4:
         raise ValueError('fpn_lateral_fwd: x (N, Cin, H, W) expected')
     n, cin, h, w = (int(v) for v in x.shape)
@@ -3128,17 +2825,14 @@ def fpn_lateral_fwd(x, image, bias, up=None, out=None, channels_last_out=False):
             raise ValueError(f'fpn_lateral_fwd: up must be ({n}, 256, Hc, Wc)')
         up_ptr, up_cl = _fpn_map(up, 'up')
         uh, uw = int(up.shape[2]), int(up.shape[3])
-    code = lib.gd4d_fpn_lateral_fwd(_dev(x, 'x', f32), n, cin, h, w, _dev(image, 'image', torch.uint8), _dev(bias, 'bias', f32), up_ptr, uh,
-                                    uw, up_cl, op, 256, out_cl, _stream())
-    _lib.check(code, 'gd4d_fpn_lateral_fwd')
+    _call('gd4d_fpn_lateral_fwd', _dev(x, 'x', F32), n, cin, h, w, _dev(image, 'image', U8), _dev(bias, 'bias', F32), up_ptr, uh, uw, up_cl,
+          op, 256, out_cl)
     return out
 
 
 def fpn_conv_fwd(feats, images, biases, outs=None, channels_last_out=False):
     """gd4d_fpn_conv_fwd: L <= 4 NCHW levels (N, 256, H_l, W_l) -> conv3x3(x_l; images[l]) + biases[l] (pad 1, stride 1), one launch;
     images[l] = depth_net_image(weight_l), biases[l] (256) or None.  outs: the L maps to write, all NCHW or all channels-last."""
-    lib = _lib.load()
-    f32 = torch.float32
     nl = len(feats)
     if len(images) != nl or len(biases) != nl:
         raise ValueError('fpn_conv_fwd: one image and one bias (or None) per level')
@@ -3152,21 +2846,18 @@ def fpn_conv_fwd(feats, images, biases, outs=None, channels_last_out=False):
     maps = [_fpn_map(o, 'outs') for o in outs]
     if len({cl for _, cl in maps}) != 1:
         raise ValueError('fpn_conv_fwd: outs must be all NCHW or all channels-last')
-    fp = (ctypes.c_void_p * nl)(*[_dev(f, 'feats', f32).value for f in feats])
+    fp = _ptrs(feats, 'feats')
     op = (ctypes.c_void_p * nl)(*[m[0].value for m in maps])
-    ip = (ctypes.c_void_p * nl)(*[_dev(i, 'images', torch.uint8).value for i in images])
-    bp = (ctypes.c_void_p * nl)(*[None if b is None else _dev(b, 'biases', f32).value for b in biases])
-    lv = (ctypes.c_int32 * (2 * nl))(*[int(v) for f in feats for v in f.shape[2:]])
-    code = lib.gd4d_fpn_conv_fwd(fp, op, lv, nl, int(n), int(feats[0].shape[1]), ip, bp, maps[0][1], _stream())
-    _lib.check(code, 'gd4d_fpn_conv_fwd')
+    ip = _ptrs(images, 'images', U8)
+    bp = _ptrs(biases, 'biases', optional=True)
+    lv = _levels(feats)
+    _call('gd4d_fpn_conv_fwd', fp, op, lv, nl, int(n), int(feats[0].shape[1]), ip, bp, maps[0][1])
     return outs
 
 
 def fpn_extra_conv_fwd(x, image, bias=None, relu_in=False, out=None, channels_last_out=False):
     """gd4d_fpn_extra_conv_fwd: x (N, 256, H, W) fp32, NCHW or channels-last -> conv3x3 stride 2 pad 1 of x (relu_in: of relu(x)) + bias,
     (N, 256, (H + 1) // 2, (W + 1) // 2); image = depth_net_image(weight)."""
-    lib = _lib.load()
-    f32 = torch.float32
     xp, x_cl = _fpn_map(x, 'x')
     n, c, h, w = (int(v) for v in x.shape)
     ho, wo = (h + 1) // 2, (w + 1) // 2
@@ -3175,9 +2866,7 @@ def fpn_extra_conv_fwd(x, image, bias=None, relu_in=False, out=None, channels_la
     elif tuple(out.shape) != (n, 256, ho, wo):
         raise ValueError(f'fpn_extra_conv_fwd: out must be ({n}, 256, {ho}, {wo})')
     op, out_cl = _fpn_map(out, 'out')
-    code = lib.gd4d_fpn_extra_conv_fwd(xp, n, c, h, w, x_cl, _dev(image, 'image', torch.uint8),
-                                       None if bias is None else _dev(bias, 'bias', f32), int(bool(relu_in)), op, out_cl, _stream())
-    _lib.check(code, 'gd4d_fpn_extra_conv_fwd')
+    _call('gd4d_fpn_extra_conv_fwd', xp, n, c, h, w, x_cl, _dev(image, 'image', U8), _opt(bias, 'bias'), int(bool(relu_in)), op, out_cl)
     return out
 
 
@@ -3190,7 +2879,7 @@ def fpn_lateral_image_t(weight):
 def _fpn_grad_map(t, name, channels=256):
     if t.dim() != 4 or (channels is not None and t.shape[1] != channels):
         raise ValueError(f'{name} must be an (N, {channels if channels else "C"}, H, W) map, got {tuple(t.shape)}')
-    return _dev(t, name, torch.float32)
+    return _dev(t, name, F32)
 
 
 def fpn_lateral_dgrad(g, image_t, cin):
@@ -3202,9 +2891,8 @@ def fpn_lateral_dgrad(g, image_t, cin):
     cin = int(cin)
     if int(lib.gd4d_fpn_lateral_image_mode_bytes(cin, 1)) != image_t.numel():
         raise ValueError(f'fpn_lateral_dgrad: image_t of {image_t.numel()} bytes is not the transposed image of a lateral with Cin = {cin}')
-    dx = torch.empty(n, cin, h, w, device=g.device, dtype=torch.float32)
-    code = lib.gd4d_fpn_lateral_dgrad(gp, n, cin, h, w, _dev(image_t, 'image_t', torch.uint8), _dev(dx, 'dx', torch.float32), _stream())
-    _lib.check(code, 'gd4d_fpn_lateral_dgrad')
+    dx = torch.empty(n, cin, h, w, device=g.device, dtype=F32)
+    _call('gd4d_fpn_lateral_dgrad', gp, n, cin, h, w, _dev(image_t, 'image_t', U8), _dev(dx, 'dx', F32))
     return dx
 
 
@@ -3213,7 +2901,6 @@ def fpn_lateral_wgrad(g, x, partitions=None):
     pixels of g[oc, p] x[ic, p] and of g[oc, p], K split over `partitions` partial sums added in order (default: about two workgroups
     per compute unit, at most one partition per 64-pixel tile)."""
     lib = _lib.load()
-    f32 = torch.float32
     gp = _fpn_grad_map(g, 'g')
     xp = _fpn_grad_map(x, 'x', None)
     n, cin, h, w = (int(v) for v in x.shape)
@@ -3228,25 +2915,21 @@ def fpn_lateral_wgrad(g, x, partitions=None):
     nbytes = int(lib.gd4d_fpn_lateral_wgrad_workspace_bytes(cin, partitions))
     if nbytes == 0:
         raise _lib.Gd4dError(f'fpn_lateral_wgrad: Cin = {cin} (a multiple of 32 in [32, 2048]), partitions = {partitions} (1 .. 4096)')
-    ws = torch.empty(nbytes // 4, device=g.device, dtype=f32)
-    dw = torch.empty(256, cin, 1, 1, device=g.device, dtype=f32)
-    db = torch.empty(256, device=g.device, dtype=f32)
-    code = lib.gd4d_fpn_lateral_wgrad(gp, xp, n, cin, h, w, partitions, _dev(ws, 'workspace', f32), _dev(dw, 'dw', f32), _dev(db, 'db', f32),
-                                      _stream())
-    _lib.check(code, 'gd4d_fpn_lateral_wgrad')
+    ws = torch.empty(nbytes // 4, device=g.device, dtype=F32)
+    dw = torch.empty(256, cin, 1, 1, device=g.device, dtype=F32)
+    db = torch.empty(256, device=g.device, dtype=F32)
+    _call('gd4d_fpn_lateral_wgrad', gp, xp, n, cin, h, w, partitions, _dev(ws, 'workspace', F32), _dev(dw, 'dw', F32), _dev(db, 'db', F32))
     return dw, db
 
 
 def fpn_topdown_bwd(g_fine, g_coarse):
     """gd4d_fpn_topdown_bwd: g_coarse (N, 256, Hc, Wc) += U^T g_fine (N, 256, H, W), IN PLACE: the adjoint of the forward's nearest
     upsampling add; every coarse pixel adds its children in row-major order.  Returns g_coarse."""
-    lib = _lib.load()
     fp, cp = _fpn_grad_map(g_fine, 'g_fine'), _fpn_grad_map(g_coarse, 'g_coarse')
     n, _, h, w = (int(v) for v in g_fine.shape)
     if g_coarse.shape[0] != n:
         raise ValueError('fpn_topdown_bwd: the two maps must hold the same cameras')
-    code = lib.gd4d_fpn_topdown_bwd(fp, n, 256, h, w, cp, int(g_coarse.shape[2]), int(g_coarse.shape[3]), _stream())
-    _lib.check(code, 'gd4d_fpn_topdown_bwd')
+    _call('gd4d_fpn_topdown_bwd', fp, n, 256, h, w, cp, int(g_coarse.shape[2]), int(g_coarse.shape[3]))
     return g_coarse
 
 
@@ -3254,8 +2937,6 @@ def fpn_extra_conv_dgrad(dy, image_t, hw, mask=None, add=None):
     """gd4d_fpn_extra_conv_dgrad: dy (N, 256, (H + 1) // 2, (W + 1) // 2) -> the stride-2 level's input gradient (N, 256, H, W), hw = (H, W);
     image_t = depth_net_image_t(weight).  mask (N, 256, H, W): the result is kept where mask > 0 (the input the forward applied its
     ReLU to); add (N, 256, H, W): added after that (the level's own incoming gradient)."""
-    lib = _lib.load()
-    f32 = torch.float32
     dp = _fpn_grad_map(dy, 'dy')
     n, h, w = int(dy.shape[0]), int(hw[0]), int(hw[1])
     if tuple(dy.shape[2:]) != ((h + 1) // 2, (w + 1) // 2):
@@ -3263,40 +2944,32 @@ def fpn_extra_conv_dgrad(dy, image_t, hw, mask=None, add=None):
     for t, name in ((mask, 'mask'), (add, 'add')):
         if t is not None and tuple(t.shape) != (n, 256, h, w):
             raise ValueError(f'fpn_extra_conv_dgrad: {name} must be ({n}, 256, {h}, {w})')
-    dx = torch.empty(n, 256, h, w, device=dy.device, dtype=f32)
-    code = lib.gd4d_fpn_extra_conv_dgrad(dp, n, 256, h, w, _dev(image_t, 'image_t', torch.uint8),
-                                         None if mask is None else _dev(mask, 'mask', f32), None if add is None else _dev(add, 'add', f32),
-                                         _dev(dx, 'dx', f32), _stream())
-    _lib.check(code, 'gd4d_fpn_extra_conv_dgrad')
+    dx = torch.empty(n, 256, h, w, device=dy.device, dtype=F32)
+    _call('gd4d_fpn_extra_conv_dgrad', dp, n, 256, h, w, _dev(image_t, 'image_t', U8), _opt(mask, 'mask'), _opt(add, 'add'),
+          _dev(dx, 'dx', F32))
     return dx
 
 
 def fpn_extra_conv_wgrad(dy, x, relu_in=False):
     """gd4d_fpn_extra_conv_wgrad: dy (N, 256, (H + 1) // 2, (W + 1) // 2), x (N, 256, H, W) fp32 NCHW -> (dW (256, 256, 3, 3), db (256)) of
     the stride-2 convolution (relu_in: of relu(x))."""
-    lib = _lib.load()
-    f32 = torch.float32
     dp, xp = _fpn_grad_map(dy, 'dy'), _fpn_grad_map(x, 'x')
     n, _, h, w = (int(v) for v in x.shape)
     if tuple(dy.shape) != (n, 256, (h + 1) // 2, (w + 1) // 2):
         raise ValueError(f'fpn_extra_conv_wgrad: dy {tuple(dy.shape)} is not the stride-2 output of x {tuple(x.shape)}')
-    dw = torch.empty(256, 256, 3, 3, device=x.device, dtype=f32)
-    db = torch.empty(256, device=x.device, dtype=f32)
-    code = lib.gd4d_fpn_extra_conv_wgrad(dp, xp, n, 256, h, w, int(bool(relu_in)), _dev(dw, 'dw', f32), _dev(db, 'db', f32), _stream())
-    _lib.check(code, 'gd4d_fpn_extra_conv_wgrad')
+    dw = torch.empty(256, 256, 3, 3, device=x.device, dtype=F32)
+    db = torch.empty(256, device=x.device, dtype=F32)
+    _call('gd4d_fpn_extra_conv_wgrad', dp, xp, n, 256, h, w, int(bool(relu_in)), _dev(dw, 'dw', F32), _dev(db, 'db', F32))
     return dw, db
 
 
 def fpn_bias_grad(g):
     """gd4d_fpn_bias_grad: g (N, 256, H, W) fp32 NCHW -> db (256), its channel sums in a fixed order."""
-    lib = _lib.load()
-    f32 = torch.float32
     gp = _fpn_grad_map(g, 'g')
     n, _, h, w = (int(v) for v in g.shape)
-    ws = torch.empty(n * 256, device=g.device, dtype=f32)
-    db = torch.empty(256, device=g.device, dtype=f32)
-    code = lib.gd4d_fpn_bias_grad(gp, n, 256, h, w, _dev(ws, 'workspace', f32), _dev(db, 'db', f32), _stream())
-    _lib.check(code, 'gd4d_fpn_bias_grad')
+    ws = torch.empty(n * 256, device=g.device, dtype=F32)
+    db = torch.empty(256, device=g.device, dtype=F32)
+    _call('gd4d_fpn_bias_grad', gp, n, 256, h, w, _dev(ws, 'workspace', F32), _dev(db, 'db', F32))
     return db
 
 
@@ -3316,18 +2989,17 @@ def grid_mask_fwd(x, d=2, l=1, st_h=0, st_w=0, use_h=True, use_w=True, mode=0, o
     if out.shape != x.shape or out.dtype not in _GRID_MASK_DTYPES or (out_dtype is not None and out.dtype != out_dtype):
         raise ValueError(f'grid_mask_fwd: out must have x\'s shape and the dtype asked for, got {tuple(out.shape)} {out.dtype}')
     r, c, h, w = x.shape
-    optr = _dev(offset, 'offset', torch.float32) if offset is not None else None
+    optr = _opt(offset, 'offset')
     if offset is not None and tuple(offset.shape) != (h, w):
         raise ValueError(f'grid_mask_fwd: offset ({h}, {w}) expected, got {tuple(offset.shape)}')
     bptr = None
     if block is not None:
         if block.numel() != GRID_MASK_BLOCK_WORDS:
             raise ValueError('grid_mask_fwd: block is the (8,) int32 parameter block')
-        bptr = _dev(block, 'block', torch.int32)
-    code = _lib.load().gd4d_grid_mask_fwd(xp, _dev(out, 'out'), _GRID_MASK_DTYPES[x.dtype], _GRID_MASK_DTYPES[out.dtype], r, c, h, w,
-                                          int(bool(apply)), int(d), int(l), int(st_h), int(st_w), int(bool(use_h)), int(bool(use_w)),
-                                          int(mode), optr, bptr, int(bool(gen_offset)), _stream())
-    _lib.check(code, 'gd4d_grid_mask_fwd')
+        bptr = _dev(block, 'block', I32)
+    _call('gd4d_grid_mask_fwd', xp, _dev(out, 'out'), _GRID_MASK_DTYPES[x.dtype], _GRID_MASK_DTYPES[out.dtype], r, c, h, w,
+          int(bool(apply)), int(d), int(l), int(st_h), int(st_w), int(bool(use_h)), int(bool(use_w)), int(mode), optr, bptr,
+          int(bool(gen_offset)))
     return out
 
 
@@ -3336,9 +3008,7 @@ def grid_mask_draw(state, block, h, ratio):
     counter in `state` advances by one.  On the current stream, capturable."""
     if state.numel() != GRID_MASK_STATE_WORDS or block.numel() != GRID_MASK_BLOCK_WORDS:
         raise ValueError('grid_mask_draw: state (4,) and block (8,) int32 expected')
-    code = _lib.load().gd4d_grid_mask_draw(_dev(state, 'state', torch.int32), _dev(block, 'block', torch.int32), int(h), float(ratio),
-                                           _stream())
-    _lib.check(code, 'gd4d_grid_mask_draw')
+    _call('gd4d_grid_mask_draw', _dev(state, 'state', I32), _dev(block, 'block', I32), int(h), float(ratio))
     return block
 
 
@@ -3376,17 +3046,11 @@ def _dcn_x(x, name):
 def dcn_offset_conv_fwd(x, image, bias=None, stride=1, out=None):
     """gd4d_dcn_offset_conv_fwd: x (N, Cin, H, W) fp32 NCHW -> (N, 27, Ho, Wo): conv3x3(x; stride, pad 1) + bias with the sigmoid applied
     to channels 18..26 (18 offsets, 9 modulations); image = dcn_weight_image(conv_offset.weight)."""
-    lib = _lib.load()
-    f32 = torch.float32
     n, cin, h, w = _dcn_x(x, 'dcn_offset_conv_fwd')
     ho, wo = dcn_out_hw(h, w, stride)
-    if out is None:
-        out = torch.empty(n, DCN_OFFSET_CHANNELS, ho, wo, device=x.device, dtype=f32)
-    elif tuple(out.shape) != (n, DCN_OFFSET_CHANNELS, ho, wo):
-        raise ValueError(f'dcn_offset_conv_fwd: out must be ({n}, {DCN_OFFSET_CHANNELS}, {ho}, {wo})')
-    code = lib.gd4d_dcn_offset_conv_fwd(_dev(x, 'x', f32), n, cin, h, w, int(stride), _dev(image, 'image', torch.uint8),
-                                        None if bias is None else _dev(bias, 'bias', f32), _dev(out, 'out', f32), _stream())
-    _lib.check(code, 'gd4d_dcn_offset_conv_fwd')
+    out = _out(out, (n, DCN_OFFSET_CHANNELS, ho, wo), x.device, 'dcn_offset_conv_fwd: out')
+    _call('gd4d_dcn_offset_conv_fwd', _dev(x, 'x', F32), n, cin, h, w, int(stride), _dev(image, 'image', U8), _opt(bias, 'bias'),
+          _dev(out, 'out', F32))
     return out
 
 
@@ -3395,7 +3059,6 @@ def dcn_fwd(x, offmask, image, cout, stride=1, scale=None, shift=None, relu=Fals
     deformable 3x3 convolution (pad 1) with the weight of image = dcn_weight_image(weight), then * scale + shift per channel (each (cout)
     or None; shift alone is the bias) and ReLU when asked."""
     lib = _lib.load()
-    f32 = torch.float32
     n, cin, h, w = _dcn_x(x, 'dcn_fwd')
     ho, wo = dcn_out_hw(h, w, stride)
     if tuple(offmask.shape) != (n, DCN_OFFSET_CHANNELS, ho, wo):
@@ -3405,14 +3068,9 @@ def dcn_fwd(x, offmask, image, cout, stride=1, scale=None, shift=None, relu=Fals
             raise ValueError(f'dcn_fwd: {name} must be ({int(cout)},)')
     if int(lib.gd4d_dcn_weight_image_bytes(cin, int(cout))) != image.numel() or int(cout) == DCN_OFFSET_CHANNELS:
         raise _lib.Gd4dError(f'dcn_fwd: the image is not dcn_weight_image of a ({int(cout)}, {cin}, 3, 3) weight the kernel takes')
-    if out is None:
-        out = torch.empty(n, int(cout), ho, wo, device=x.device, dtype=f32)
-    elif tuple(out.shape) != (n, int(cout), ho, wo):
-        raise ValueError(f'dcn_fwd: out must be ({n}, {int(cout)}, {ho}, {wo})')
-    code = lib.gd4d_dcn_fwd(_dev(x, 'x', f32), _dev(offmask, 'offmask', f32), n, cin, int(cout), h, w, int(stride),
-                            _dev(image, 'image', torch.uint8), None if scale is None else _dev(scale, 'scale', f32),
-                            None if shift is None else _dev(shift, 'shift', f32), int(bool(relu)), _dev(out, 'out', f32), _stream())
-    _lib.check(code, 'gd4d_dcn_fwd')
+    out = _out(out, (n, int(cout), ho, wo), x.device, 'dcn_fwd: out')
+    _call('gd4d_dcn_fwd', _dev(x, 'x', F32), _dev(offmask, 'offmask', F32), n, cin, int(cout), h, w, int(stride), _dev(image, 'image', U8),
+          _opt(scale, 'scale'), _opt(shift, 'shift'), int(bool(relu)), _dev(out, 'out', F32))
     return out
 
 
@@ -3444,20 +3102,17 @@ def dcn_bwd_data(dout, x, offmask, image_t, cout, stride=1, y=None, scale=None, 
     with sigmoid_grad (the gradient of conv_offset's raw output).  dx is ADDED into with float atomics (the one output whose last bits
     depend on the run): a given dx must hold zeros (or what to add to); by default a zeroed one is made."""
     lib = _lib.load()
-    f32 = torch.float32
     n, cin, cout, h, w, ho, wo = _dcn_bwd_args('dcn_bwd_data', dout, y, scale, x, offmask, cout, stride)
     if int(lib.gd4d_dcn_weight_image_t_bytes(cin, cout)) != image_t.numel() or image_t.numel() == 0:
         raise _lib.Gd4dError(f'dcn_bwd_data: the image is not dcn_weight_image_t of a ({cout}, {cin}, 3, 3) weight the kernel takes')
     if dx is None and want_dx:
-        dx = torch.zeros(n, cin, h, w, device=x.device, dtype=f32)
+        dx = torch.zeros(n, cin, h, w, device=x.device, dtype=F32)
     elif dx is not None and tuple(dx.shape) != (n, cin, h, w):
         raise ValueError(f'dcn_bwd_data: dx must be ({n}, {cin}, {h}, {w})')
-    doff = torch.empty(n, DCN_OFFSET_CHANNELS, ho, wo, device=x.device, dtype=f32)
-    code = lib.gd4d_dcn_bwd_data(_dev(dout, 'dout', f32), None if y is None else _dev(y, 'y', f32),
-                                 None if scale is None else _dev(scale, 'scale', f32), _dev(x, 'x', f32), _dev(offmask, 'offmask', f32),
-                                 n, cin, cout, h, w, int(stride), _dev(image_t, 'image_t', torch.uint8), int(bool(sigmoid_grad)),
-                                 None if dx is None else _dev(dx, 'dx', f32), _dev(doff, 'doff', f32), _stream())
-    _lib.check(code, 'gd4d_dcn_bwd_data')
+    doff = torch.empty(n, DCN_OFFSET_CHANNELS, ho, wo, device=x.device, dtype=F32)
+    _call('gd4d_dcn_bwd_data', _dev(dout, 'dout', F32), _opt(y, 'y'), _opt(scale, 'scale'), _dev(x, 'x', F32),
+          _dev(offmask, 'offmask', F32), n, cin, cout, h, w, int(stride), _dev(image_t, 'image_t', U8), int(bool(sigmoid_grad)),
+          _opt(dx, 'dx'), _dev(doff, 'doff', F32))
     return dx, doff
 
 
@@ -3476,21 +3131,17 @@ def dcn_wgrad(dout, x, offmask, cout, stride=1, y=None, scale=None, partitions=N
     scale as dcn_bwd_data.  One launch plus the reduction over `partitions` partial sums (default: about two workgroups per compute
     unit, at most one partition per 64-pixel tile)."""
     lib = _lib.load()
-    f32 = torch.float32
     n, cin, cout, h, w, ho, wo = _dcn_bwd_args('dcn_wgrad', dout, y, scale, x, offmask, cout, stride)
     partitions = _dcn_partitions(lib, x.device, n, cin, h, w, stride, partitions, 4)
     nbytes = int(lib.gd4d_dcn_wgrad_workspace_bytes(cin, cout, partitions))
     if nbytes == 0:
         raise _lib.Gd4dError(f'dcn_wgrad: Cin = {cin}, Cout = {cout}, partitions = {partitions}: the kernel takes channels that are multiples '
                              'of 64 in [64, 512] and 1..4096 partitions')
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=f32)
-    dw = torch.empty(cout, cin, 3, 3, device=x.device, dtype=f32)
-    db = torch.empty(cout, device=x.device, dtype=f32)
-    code = lib.gd4d_dcn_wgrad(_dev(dout, 'dout', f32), None if y is None else _dev(y, 'y', f32),
-                              None if scale is None else _dev(scale, 'scale', f32), _dev(x, 'x', f32), _dev(offmask, 'offmask', f32),
-                              n, cin, cout, h, w, int(stride), partitions, _dev(ws, 'workspace', f32), _dev(dw, 'dw', f32),
-                              _dev(db, 'dbias', f32), _stream())
-    _lib.check(code, 'gd4d_dcn_wgrad')
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=F32)
+    dw = torch.empty(cout, cin, 3, 3, device=x.device, dtype=F32)
+    db = torch.empty(cout, device=x.device, dtype=F32)
+    _call('gd4d_dcn_wgrad', _dev(dout, 'dout', F32), _opt(y, 'y'), _opt(scale, 'scale'), _dev(x, 'x', F32), _dev(offmask, 'offmask', F32),
+          n, cin, cout, h, w, int(stride), partitions, _dev(ws, 'workspace', F32), _dev(dw, 'dw', F32), _dev(db, 'dbias', F32))
     return dw, db
 
 
@@ -3505,14 +3156,11 @@ def _dcn_doff(name, doff, x, stride):
 def dcn_offset_conv_dgrad(doff, weight, dx, stride=1):
     """gd4d_dcn_offset_conv_dgrad: dx (N, Cin, H, W) += conv_transpose3x3(doff (N, 27, Ho, Wo), weight (27, Cin, 3, 3); stride, pad 1), in
     place: a plain read-modify-write (run it after dcn_bwd_data on the same stream).  Returns dx."""
-    lib = _lib.load()
-    f32 = torch.float32
     n, cin, h, w = _dcn_doff('dcn_offset_conv_dgrad', doff, dx, stride)
     if tuple(weight.shape) != (DCN_OFFSET_CHANNELS, cin, 3, 3):
         raise ValueError(f'dcn_offset_conv_dgrad: weight must be ({DCN_OFFSET_CHANNELS}, {cin}, 3, 3)')
-    code = lib.gd4d_dcn_offset_conv_dgrad(_dev(doff, 'doff', f32), _dev(weight, 'weight', f32), n, cin, h, w, int(stride), _dev(dx, 'dx', f32),
-                                          _stream())
-    _lib.check(code, 'gd4d_dcn_offset_conv_dgrad')
+    _call('gd4d_dcn_offset_conv_dgrad', _dev(doff, 'doff', F32), _dev(weight, 'weight', F32), n, cin, h, w, int(stride),
+          _dev(dx, 'dx', F32))
     return dx
 
 
@@ -3520,19 +3168,17 @@ def dcn_offset_conv_wgrad(doff, x, stride=1, partitions=None):
     """gd4d_dcn_offset_conv_wgrad: (dW (27, Cin, 3, 3), db (27)) of conv_offset from doff (N, 27, Ho, Wo) and its input x; `partitions` as
     dcn_wgrad."""
     lib = _lib.load()
-    f32 = torch.float32
     n, cin, h, w = _dcn_doff('dcn_offset_conv_wgrad', doff, x, stride)
     partitions = _dcn_partitions(lib, x.device, n, cin, h, w, stride, partitions, 1)
     nbytes = int(lib.gd4d_dcn_offset_conv_wgrad_workspace_bytes(cin, partitions))
     if nbytes == 0:
         raise _lib.Gd4dError(f'dcn_offset_conv_wgrad: Cin = {cin}, partitions = {partitions}: the kernel takes Cin a multiple of 64 in '
                              '[64, 512] and 1..4096 partitions')
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=f32)
-    dw = torch.empty(DCN_OFFSET_CHANNELS, cin, 3, 3, device=x.device, dtype=f32)
-    db = torch.empty(DCN_OFFSET_CHANNELS, device=x.device, dtype=f32)
-    code = lib.gd4d_dcn_offset_conv_wgrad(_dev(doff, 'doff', f32), _dev(x, 'x', f32), n, cin, h, w, int(stride), partitions,
-                                          _dev(ws, 'workspace', f32), _dev(dw, 'dw', f32), _dev(db, 'db', f32), _stream())
-    _lib.check(code, 'gd4d_dcn_offset_conv_wgrad')
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=F32)
+    dw = torch.empty(DCN_OFFSET_CHANNELS, cin, 3, 3, device=x.device, dtype=F32)
+    db = torch.empty(DCN_OFFSET_CHANNELS, device=x.device, dtype=F32)
+    _call('gd4d_dcn_offset_conv_wgrad', _dev(doff, 'doff', F32), _dev(x, 'x', F32), n, cin, h, w, int(stride), partitions,
+          _dev(ws, 'workspace', F32), _dev(dw, 'dw', F32), _dev(db, 'db', F32))
     return dw, db
 
 
@@ -3552,7 +3198,6 @@ def conv3x3_bn_relu(x, image, cout, scale, shift, stride=1, out=None, m_blocks=0
     conv3x3_image(weight), scale / shift (cout) the folded frozen BatchNorm.  m_blocks: 0, or the M tiling to force (1, 2, 3, 4, 5 or 7
     row blocks of 32 channels per workgroup, dividing cout / 32; the same bits either way)."""
     lib = _lib.load()
-    f32 = torch.float32
     n, cin, h, w = _dcn_x(x, 'conv3x3_bn_relu')
     cout = int(cout)
     ho, wo = dcn_out_hw(h, w, stride)
@@ -3563,13 +3208,9 @@ def conv3x3_bn_relu(x, image, cout, scale, shift, stride=1, out=None, m_blocks=0
     if nbytes == 0 or nbytes != image.numel():
         raise _lib.Gd4dError(f'conv3x3_bn_relu: the image is not conv3x3_image of a ({cout}, {cin}, 3, 3) weight the kernel takes '
                              '(Cin a multiple of 32 in [32, 1024], Cout a multiple of 32 in [32, 256])')
-    if out is None:
-        out = torch.empty(n, cout, ho, wo, device=x.device, dtype=f32)
-    elif tuple(out.shape) != (n, cout, ho, wo):
-        raise ValueError(f'conv3x3_bn_relu: out must be ({n}, {cout}, {ho}, {wo})')
-    code = lib.gd4d_conv3x3_bn_relu_fwd(_dev(x, 'x', f32), n, cin, h, w, int(stride), _dev(image, 'image', torch.uint8), cout,
-                                        _dev(scale, 'scale', f32), _dev(shift, 'shift', f32), _dev(out, 'out', f32), int(m_blocks), _stream())
-    _lib.check(code, 'gd4d_conv3x3_bn_relu_fwd')
+    out = _out(out, (n, cout, ho, wo), x.device, 'conv3x3_bn_relu: out')
+    _call('gd4d_conv3x3_bn_relu_fwd', _dev(x, 'x', F32), n, cin, h, w, int(stride), _dev(image, 'image', U8), cout,
+          _dev(scale, 'scale', F32), _dev(shift, 'shift', F32), _dev(out, 'out', F32), int(m_blocks))
     return out
 
 
@@ -3591,7 +3232,6 @@ def osa_concat_conv(sources, image, cout, scale, shift, out=None, partials=None,
     with a multiple of 32 channels; the concatenation is never written.  Returns (out (N, cout, H, W), partials (N, tiles, cout)): each
     128-pixel tile's per-channel sum of the outputs, what ese_gate averages.  m_blocks: as conv3x3_bn_relu's."""
     lib = _lib.load()
-    f32 = torch.float32
     sources = list(sources)
     if not 1 <= len(sources) <= OSA_MAX_SOURCES:
         raise _lib.Gd4dError(f'osa_concat_conv: {len(sources)} sources; the kernel takes 1 to {OSA_MAX_SOURCES}')
@@ -3609,28 +3249,18 @@ def osa_concat_conv(sources, image, cout, scale, shift, out=None, partials=None,
         raise _lib.Gd4dError(f'osa_concat_conv: sources of {chans} channels -> {cout}: the kernel takes multiples of 32, K up to 2304 and '
                              'Cout up to 1024, with image = osa_concat_image of the (Cout, K) weight')
     tiles = int(lib.gd4d_osa_concat_tiles(h, w))
-    if out is None:
-        out = torch.empty(n, cout, h, w, device=sources[0].device, dtype=f32)
-    elif tuple(out.shape) != (n, cout, h, w):
-        raise ValueError(f'osa_concat_conv: out must be ({n}, {cout}, {h}, {w})')
-    if partials is None:
-        partials = torch.empty(n, tiles, cout, device=sources[0].device, dtype=f32)
-    elif tuple(partials.shape) != (n, tiles, cout):
-        raise ValueError(f'osa_concat_conv: partials must be ({n}, {tiles}, {cout})')
-    ptrs = (ctypes.c_void_p * len(sources))(*[_dev(s, 'sources', f32) for s in sources])
+    out = _out(out, (n, cout, h, w), sources[0].device, 'osa_concat_conv: out')
+    partials = _out(partials, (n, tiles, cout), sources[0].device, 'osa_concat_conv: partials')
+    ptrs = _ptrs(sources, 'sources')
     ch = (ctypes.c_int32 * len(sources))(*chans)
-    code = lib.gd4d_osa_concat_conv_fwd(ptrs, ch, len(sources), n, h, w, _dev(image, 'image', torch.uint8), cout,
-                                        _dev(scale, 'scale', f32), _dev(shift, 'shift', f32), _dev(out, 'out', f32),
-                                        _dev(partials, 'partials', f32), int(m_blocks), _stream())
-    _lib.check(code, 'gd4d_osa_concat_conv_fwd')
+    _call('gd4d_osa_concat_conv_fwd', ptrs, ch, len(sources), n, h, w, _dev(image, 'image', U8), cout, _dev(scale, 'scale', F32),
+          _dev(shift, 'shift', F32), _dev(out, 'out', F32), _dev(partials, 'partials', F32), int(m_blocks))
     return out, partials
 
 
 def ese_gate(partials, hw, fc_weight, fc_bias, out=None):
     """gd4d_ese_gate_fwd: partials (N, tiles, C) of osa_concat_conv, hw = H W -> gate (N, C) = relu6(fc_weight mean + fc_bias + 3) / 6;
     fc_weight (C, C) or (C, C, 1, 1), C a multiple of 32 up to 1024."""
-    lib = _lib.load()
-    f32 = torch.float32
     if partials.dim() != 3:
         raise ValueError('ese_gate: partials (N, tiles, C) expected')
     n, tiles, c = (int(v) for v in partials.shape)
@@ -3638,21 +3268,15 @@ def ese_gate(partials, hw, fc_weight, fc_bias, out=None):
         raise ValueError(f'ese_gate: fc_weight ({c}, {c}[, 1, 1]) and fc_bias ({c},) expected')
     if c % 32 or not 32 <= c <= 1024:
         raise _lib.Gd4dError(f'ese_gate: C = {c}; the kernel takes a multiple of 32 in [32, 1024]')
-    if out is None:
-        out = torch.empty(n, c, device=partials.device, dtype=f32)
-    elif tuple(out.shape) != (n, c):
-        raise ValueError(f'ese_gate: out must be ({n}, {c})')
-    code = lib.gd4d_ese_gate_fwd(_dev(partials, 'partials', f32), n, tiles, c, int(hw), _dev(fc_weight, 'fc_weight', f32),
-                                 _dev(fc_bias, 'fc_bias', f32), _dev(out, 'out', f32), _stream())
-    _lib.check(code, 'gd4d_ese_gate_fwd')
+    out = _out(out, (n, c), partials.device, 'ese_gate: out')
+    _call('gd4d_ese_gate_fwd', _dev(partials, 'partials', F32), n, tiles, c, int(hw), _dev(fc_weight, 'fc_weight', F32),
+          _dev(fc_bias, 'fc_bias', F32), _dev(out, 'out', F32))
     return out
 
 
 def ese_apply(xt, gate, identity=None, out=None):
     """gd4d_ese_apply_fwd: xt (N, C, H, W) * gate (N, C) (+ identity, xt's shape) -> out (a new tensor, or the one given: xt itself is
     allowed)."""
-    lib = _lib.load()
-    f32 = torch.float32
     n, c, h, w = _dcn_x(xt, 'ese_apply')
     if tuple(gate.shape) != (n, c):
         raise ValueError(f'ese_apply: gate must be ({n}, {c})')
@@ -3662,9 +3286,8 @@ def ese_apply(xt, gate, identity=None, out=None):
         out = torch.empty_like(xt)
     elif out.shape != xt.shape:
         raise ValueError(f'ese_apply: out must have xt\'s shape {tuple(xt.shape)}')
-    code = lib.gd4d_ese_apply_fwd(_dev(xt, 'xt', f32), _dev(gate, 'gate', f32), None if identity is None else _dev(identity, 'identity', f32),
-                                  n, c, h * w, _dev(out, 'out', f32), _stream())
-    _lib.check(code, 'gd4d_ese_apply_fwd')
+    _call('gd4d_ese_apply_fwd', _dev(xt, 'xt', F32), _dev(gate, 'gate', F32), _opt(identity, 'identity'), n, c, h * w,
+          _dev(out, 'out', F32))
     return out
 
 
