@@ -40,6 +40,9 @@ SIGNATURES = {
     'gd4d_value_proj_image': (_i, [_vp, _vp, _vp, _vp]),
     'gd4d_value_proj_guest_fwd': (_i, [_vp, _i, _vp]),
     'gd4d_row_chain_guest_fwd': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
+    'gd4d_row_chain_choice': (_i, [_vp, _i, _vp, _i, _i]),
+    'gd4d_row_chain_choice_name': (_c.c_char_p, [_i]),
+    'gd4d_row_chain_specialise': (_i, [_i]),
     'gd4d_row_chain_fill_fwd': (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'gd4d_cross_attn_agg_items_count_fwd': (_i, [_vp, _vp, _vp, _c.c_int64, _c.c_int64, _vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _vp, _vp, _c.c_size_t, _vp]),
     'gd4d_pyramid_slice_planar_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

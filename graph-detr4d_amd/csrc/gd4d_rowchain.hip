@@ -86,6 +86,9 @@ __device__ __forceinline__ float rc_act_in(float v, int flags) { return (flags &
 #ifndef RC_TRACE_OPS
 #define RC_TRACE_OPS 0   // dev: stamp every operation's end in the device timeline (tools/trace_step.py)
 #endif
+#ifndef RC_FORCE_TRAIN
+#define RC_FORCE_TRAIN 0   // dev A/B: every launch (guests' chains too) runs the TRAIN = true instantiation - the larger instruction stream, same results
+#endif
 #ifndef RC_DBG
 #define RC_DBG 0      // dev ablation (compile with -DRC_DBG=n): 1 = no MFMAs, 2 = no weight loads
 #endif
@@ -191,32 +194,93 @@ __global__ __launch_bounds__(256) void chain_weight_image_group_kernel(const gd4
   }
 }
 
+// WHAT A PROGRAM NEEDS, and what an instantiation of the chain kernel holds.  The body below is one interpreter; every operation kind
+// and every variant of an operation is a run-time test in it, and the tests of all of them sit in every epilogue: 40 KB of code for
+// the inference kernel, of which a given launch walks a part.  `SPEC` (an RcSpec) names at compile time the kinds and variants that
+// may occur: an absent kind leaves the switch (if constexpr), an absent variant's test becomes `false` and its code goes.  The
+// arithmetic of what remains is the same text - same MFMA order, same sums.  rc_needs() computes the same bits from a program on the
+// host, with the conditions the device code tests; rc_launch picks the first instantiation of RC_TABLE whose mask holds them all,
+// else the generic one (everything, TRAIN both ways).
+// Bits 1 .. 11: operation kind k occurs (1 << k).
+constexpr uint64_t rcn_kind(int k) { return 1ull << k; }
+enum : uint64_t {
+  RCN_G_PLAIN = 1ull << 16,      // GEMM on three products
+  RCN_G_EXACT = 1ull << 17,      // GEMM on six (GD4D_CHAIN_EXACT)
+  RCN_G_SRC2 = 1ull << 18, RCN_G_SPLIT_OUT = 1ull << 19, RCN_G_SPLIT_KV = 1ull << 20, RCN_G_KV_KEEP = 1ull << 21,
+  RCN_G_RELU = 1ull << 22, RCN_G_SIGMOID = 1ull << 23,
+  RCN_G_RES = 1ull << 24,        // residual buffer (res >= 0 without SRC2)
+  RCN_G_ADD = 1ull << 25,        // global addend p2 (or MASK_P2's operand)
+  RCN_G_ADD2 = 1ull << 26,       // second global addend p3
+  RCN_G_DST = 1ull << 27, RCN_G_GOUT = 1ull << 28,       // (gout of a GEMM that is not SPLIT_OUT)
+  RCN_G_TRAIN = 1ull << 29,      // MASK_P2, DROPOUT
+  RCN_L_SECOND = 1ull << 32, RCN_L_RELU = 1ull << 33, RCN_L_GOUT = 1ull << 34, RCN_L_DST = 1ull << 35,      // LAYERNORM
+  RCN_LD_INV = 1ull << 36, RCN_LD_NARROW = 1ull << 37, RCN_LD_WIDE = 1ull << 38, RCN_LD_P1 = 1ull << 39,    // LOAD
+  RCN_H_ADD = 1ull << 40, RCN_H_RES = 1ull << 41, RCN_H_GOUT = 1ull << 42, RCN_H_DST = 1ull << 43,          // HEADGEMM
+  RCN_T_GOUT = 1ull << 44,       // LOAD / ADD / SMALL_LINEAR store their rows (a training step)
+};
+// what only a training step uses: these live in the TRAIN instantiation alone (with them compiled in, the inference step's chains ran
+// 10 % slower - 221 against 163 registers, longer epilogues)
+constexpr uint64_t RCN_TRAIN = rcn_kind(GD4D_CHAIN_LN_BWD) | rcn_kind(GD4D_CHAIN_DROPMASK) | RCN_G_TRAIN | RCN_T_GOUT;
+template <uint64_t MASK>
+struct RcSpec {
+  static constexpr uint64_t mask = MASK;
+  static constexpr bool has(uint64_t bits) { return (MASK & bits) != 0; }
+  static constexpr bool kind(int k) { return (MASK & rcn_kind(k)) != 0; }
+};
+template <bool TRAIN>
+struct RcAll : RcSpec<TRAIN ? ~0ull : ~RCN_TRAIN> {};       // every program: the generic instantiations
+// The table: the launches of fused_decoder.run_single / initial_reference and of the head's box epilogue (functional.head_outputs),
+// each mask the union of what its one or two programs need.  First entry that covers a launch wins.
+constexpr uint64_t RCN_LG = rcn_kind(GD4D_CHAIN_LOAD) | rcn_kind(GD4D_CHAIN_GEMM) | RCN_LD_WIDE;
+// LOAD x + pos, LOAD x, the packed in-projection (q, k from x + pos, v from x; K / V as planes)
+struct RcInProj : RcSpec<RCN_LG | RCN_LD_P1 | RCN_G_PLAIN | RCN_G_SRC2 | RCN_G_SPLIT_KV | RCN_G_GOUT> {};
+// sigmoid(Linear(query_pos)) on six products
+struct RcInitRef : RcSpec<RCN_LG | RCN_G_EXACT | RCN_G_SIGMOID | RCN_G_GOUT> {};
+// [chain A: out_proj + x, LayerNorm with x1 + pos beside it, the three Linears of query + query_pos | reg branch, REFINE]
+struct RcChainA : RcSpec<RCN_LG | rcn_kind(GD4D_CHAIN_LAYERNORM) | rcn_kind(GD4D_CHAIN_REFINE) | RCN_G_PLAIN | RCN_G_EXACT | RCN_G_ADD | RCN_G_DST |
+                         RCN_G_SPLIT_OUT | RCN_G_RELU | RCN_L_DST | RCN_L_GOUT | RCN_L_SECOND> {};
+// [position_encoder, SIGNAL | chain B': HEADGEMM (+ pagg), WAIT, output_proj, FFN, the next in-projection] - the launch with guests
+constexpr uint64_t RCN_B = RCN_LG | rcn_kind(GD4D_CHAIN_SMALL_LINEAR) | rcn_kind(GD4D_CHAIN_LAYERNORM) | rcn_kind(GD4D_CHAIN_SIGNAL) |
+                           rcn_kind(GD4D_CHAIN_WAIT) | rcn_kind(GD4D_CHAIN_HEADGEMM) | RCN_LD_NARROW | RCN_LD_INV | RCN_LD_P1 | RCN_L_RELU |
+                           RCN_L_DST | RCN_L_GOUT | RCN_G_PLAIN | RCN_G_DST | RCN_G_RES | RCN_G_RELU | RCN_H_ADD | RCN_H_DST;
+struct RcChainB : RcSpec<RCN_B | RCN_L_SECOND | RCN_G_SRC2 | RCN_G_SPLIT_KV | RCN_G_GOUT> {};
+// the last layer's: no in-projection; the reg branch on six products and REFINE close it
+struct RcChainBLast : RcSpec<RCN_B | RCN_G_EXACT | rcn_kind(GD4D_CHAIN_REFINE)> {};
+// the head's [cls branch | reg branch]: Linear / LayerNorm / ReLU stacks, the reg branch on six products
+struct RcHead : RcSpec<RCN_LG | rcn_kind(GD4D_CHAIN_LAYERNORM) | RCN_G_PLAIN | RCN_G_EXACT | RCN_G_RELU | RCN_G_DST | RCN_G_GOUT | RCN_L_RELU | RCN_L_DST> {};
+
 // GEMM over the workgroup's 16 rows: out[:, n] = act(sum_k in[:, k] * W[n, k] + bias[n]) (+ residuals), n < N.
 // Wave w owns columns [256 pass + RC_COLS w, + RC_COLS) of every pass; A fragments are split from the LDS buffer, the W fragments
 // come pre-split from the image (global / L2) through a register ring RC_DEPTH k-steps deep.
 // EXACT (GD4D_CHAIN_EXACT): both operands cut into THREE bf16 pieces and the six products of combined order <= 2 summed
 // (x y ~= sum_{i + j <= 2} x_i y_j, ~2^-24 relative: fp32-class), for the GEMMs whose outputs become reference points -
 // a point's error is multiplied by the 102-m range and the focal length before it selects pixels.
-template <bool EXACT, bool TRAIN>
+template <bool EXACT, class SPEC>
 __device__ __forceinline__ void rc_gemm(const ChainOp& op, float (*bufs)[RC_M][RC_LD], int m0, int M, int lane, int wave) {
   constexpr int FRAG = EXACT ? 3072 : 2048;
+  constexpr bool TRAIN = SPEC::has(RCN_G_TRAIN);
   const int i16 = lane & 15, g = lane >> 4;
   const int K = op.K, N = op.N;
   const int steps = K / 32, tiles = (N + 15) / 16;
   const char* img = reinterpret_cast<const char*>(op.p0);
+  // (SPEC::has(...) below: a variant no program of this instantiation uses is `false` at compile time)
   // GD4D_CHAIN_SRC2: the passes from column ld0 on (a multiple of 256 = one pass of all waves) take their A operand from buffer
   // `res` instead of `src` - the packed in-projection (q, k from x + pos, v from x) as ONE operation.
   // GD4D_CHAIN_SPLIT_OUT: the N columns go to three global tensors (gout | p2 | p3, each as wide as its row stride) - the
   // three Linears of query + query_pos (camera logits, offsets, attention logits) as ONE operation over their stacked weights.
-  const bool src2 = (op.flags & GD4D_CHAIN_SRC2) != 0, split_out = (op.flags & GD4D_CHAIN_SPLIT_OUT) != 0;
+  const bool src2 = SPEC::has(RCN_G_SRC2) && (op.flags & GD4D_CHAIN_SRC2) != 0;
+  const bool split_out = SPEC::has(RCN_G_SPLIT_OUT) && (op.flags & GD4D_CHAIN_SPLIT_OUT) != 0;
   // GD4D_CHAIN_SPLIT_KV: pass 1 (K) and pass 2 (V) of the packed in-projection also leave as bf16 hi / lo planes (p2: K row-major,
   // p3: V^T) - the operands gd4d_mha_core_presplit_fwd feeds to its MFMAs without converting anything
-  const bool split_kv = (op.flags & GD4D_CHAIN_SPLIT_KV) != 0;
-  const bool kv_fp32_too = (op.flags & GD4D_CHAIN_SPLIT_KV_KEEP) != 0;    // (a training step: the attention BACKWARD reads fp32 rows)
+  const bool split_kv = SPEC::has(RCN_G_SPLIT_KV) && (op.flags & GD4D_CHAIN_SPLIT_KV) != 0;
+  const bool kv_fp32_too = SPEC::has(RCN_G_KV_KEEP) && (op.flags & GD4D_CHAIN_SPLIT_KV_KEEP) != 0;    // (a training step: the attention BACKWARD reads fp32 rows)
   // GD4D_CHAIN_MASK_P2: p2 is not an addend but the OUTPUT a ReLU produced in the forward pass - the result (the gradient at that
   // ReLU's output) passes where it was > 0, times `eps` when that is non-zero (the 1 / (1 - p) of a dropout that followed the ReLU
   // and left its zeros in p2 as well)
-  const bool mask_p2 = TRAIN && (op.flags & GD4D_CHAIN_MASK_P2) != 0;      // (TRAIN: the training operations live in their own instantiation of the kernel - the inference step's chains ran 10 % slower with them compiled in)
+  const bool mask_p2 = TRAIN && (op.flags & GD4D_CHAIN_MASK_P2) != 0;
+  const bool relu = SPEC::has(RCN_G_RELU) && (op.flags & GD4D_CHAIN_RELU) != 0, sigmoid = SPEC::has(RCN_G_SIGMOID) && (op.flags & GD4D_CHAIN_SIGMOID) != 0;
+  const bool add = SPEC::has(RCN_G_ADD) && op.p2 && !split_out && !split_kv;       // global addend(s) / MASK_P2's operand
+  const bool to_res = SPEC::has(RCN_G_RES) && op.res >= 0 && !src2, to_dst = SPEC::has(RCN_G_DST) && op.dst >= 0;
   const float mask_scale = op.eps != 0.f ? op.eps : 1.f;
   // GD4D_CHAIN_DROPOUT (a training step with the modules in train mode): the output - after bias / activation, before the
   // residuals - is dropped like nn.Dropout does: kept elements times eps = 1 / (1 - p).  Which elements: csrc/gd4d_mha_dropout.h's
@@ -244,7 +308,7 @@ __device__ __forceinline__ void rc_gemm(const ChainOp& op, float (*bufs)[RC_M][R
     // global addends p2 (+ p3) of the epilogue - the residual rows a LOAD operation would otherwise park in a buffer first:
     // requested here, consumed after the K loop (their fabric round trip hides under the weight stream)
     float e_add[RC_TILES][4];
-    if (op.p2 && !split_out && !split_kv) {
+    if (add) {
 #pragma unroll
       for (int c = 0; c < RC_TILES; ++c) {
         const int n = min(n_base + 16 * c + i16, N - 1);
@@ -252,7 +316,7 @@ __device__ __forceinline__ void rc_gemm(const ChainOp& op, float (*bufs)[RC_M][R
         for (int r = 0; r < 4; ++r) {
           const size_t m = (size_t)min(m0 + 4 * g + r, M - 1);
           const float a2 = op.p2[m * op.ld2 + n];
-          e_add[c][r] = (op.p3 && !drop) ? a2 + op.p3[m * op.ld1 + n] : a2;
+          e_add[c][r] = (SPEC::has(RCN_G_ADD2) && op.p3 && !drop) ? a2 + op.p3[m * op.ld1 + n] : a2;
         }
       }
     }
@@ -329,14 +393,14 @@ __device__ __forceinline__ void rc_gemm(const ChainOp& op, float (*bufs)[RC_M][R
       for (int r = 0; r < 4; ++r) {
         const int row = 4 * g + r, m = m0 + row;
         float v = acc[c][r] + e_bias[c];
-        if (op.flags & GD4D_CHAIN_RELU) v = fmaxf(v, 0.f);
-        if (op.flags & GD4D_CHAIN_SIGMOID) v = 1.0f / (1.0f + expf(-v));
+        if (relu) v = fmaxf(v, 0.f);
+        if (sigmoid) v = 1.0f / (1.0f + expf(-v));
         if (drop) v = mha_drop_keep(drop_lo, drop_hi, (uint32_t)m * (uint32_t)N + (uint32_t)n, (uint32_t)op.reserved) ? v * op.eps : 0.f;
         if (mask_p2) v = e_add[c][r] > 0.f ? v * mask_scale : 0.f;
-        if (op.res >= 0 && !src2) v += bufs[op.res][row][n];
-        if (op.p2 && !split_out && !mask_p2 && !split_kv) v += e_add[c][r];
+        if (to_res) v += bufs[op.res][row][n];
+        if (add && !mask_p2) v += e_add[c][r];
         if (split_kv) kv[r] = v;
-        if (op.dst >= 0) bufs[op.dst][row][op.dst_col + n] = v;
+        if (to_dst) bufs[op.dst][row][op.dst_col + n] = v;
         if (split_out) {
           if (m < M) {
             const int c1 = op.ldg, c2 = op.ldg + op.ld2;
@@ -345,7 +409,7 @@ __device__ __forceinline__ void rc_gemm(const ChainOp& op, float (*bufs)[RC_M][R
                               : const_cast<float*>(op.p3) + (size_t)m * op.ld1 + (n - c2);
             *o = v;
           }
-        } else if (op.gout && m < M && !(split_kv && !kv_fp32_too && n_base >= RC_COLS * RC_WAVES)) {   // (K and V leave as planes only)
+        } else if (SPEC::has(RCN_G_GOUT) && op.gout && m < M && !(split_kv && !kv_fp32_too && n_base >= RC_COLS * RC_WAVES)) {   // (K and V leave as planes only)
           op.gout[(size_t)m * op.ldg + n] = v;
         }
       }
@@ -391,6 +455,7 @@ __device__ __forceinline__ void rc_gemm(const ChainOp& op, float (*bufs)[RC_M][R
 // column ownership, weight image and arithmetic as rc_gemm; the A fragments of a k-step come from the rows of the two
 // heads a wave's 64 columns belong to (Dh = 32: tiles 0, 1 -> one head, tiles 2, 3 -> the next; Dh = 64: one head),
 // through a 2-deep register ring beside the weight fragments.  Requires Dh % 32 == 0, K % 64 == 0.
+template <class SPEC>
 __device__ __forceinline__ void rc_headgemm(const ChainOp& op, float (*bufs)[RC_M][RC_LD], int m0, int M, int lane, int wave) {
   constexpr int HD = 2;                                        // ring depth (k-steps)
   const int i16 = lane & 15, g = lane >> 4;
@@ -398,6 +463,7 @@ __device__ __forceinline__ void rc_headgemm(const ChainOp& op, float (*bufs)[RC_
   const int steps = K / 32, tiles = (N + 15) / 16;
   const char* img = reinterpret_cast<const char*>(op.p0);
   const int m_ld = min(m0 + i16, M - 1);                       // rows past M repeat the last row (never stored)
+  const bool add_gout = SPEC::has(RCN_H_ADD) && (op.flags & GD4D_CHAIN_ADD_GOUT) != 0;
   for (int n_base = RC_COLS * wave; n_base < N; n_base += RC_COLS * RC_WAVES) {
     const char* wf[RC_TILES];
 #pragma unroll
@@ -423,7 +489,7 @@ __device__ __forceinline__ void rc_headgemm(const ChainOp& op, float (*bufs)[RC_
     }
     // GD4D_CHAIN_ADD_GOUT: the (M, N) addend at gout, requested before the k loop (the lane's own output elements)
     float addend[RC_TILES][4];
-    if (op.flags & GD4D_CHAIN_ADD_GOUT) {
+    if (add_gout) {
 #pragma unroll
       for (int c = 0; c < RC_TILES; ++c)
 #pragma unroll
@@ -482,10 +548,10 @@ __device__ __forceinline__ void rc_headgemm(const ChainOp& op, float (*bufs)[RC_
       for (int r = 0; r < 4; ++r) {
         const int row = 4 * g + r, m = m0 + row;
         float v = fmaf(e_bias[c], op.p3[(size_t)min(m, M - 1) * heads + hc], acc[c][r]);
-        if (op.res >= 0) v += bufs[op.res][row][n];
-        if (op.flags & GD4D_CHAIN_ADD_GOUT) v += addend[c][r];
-        if (op.dst >= 0) bufs[op.dst][row][op.dst_col + n] = v;
-        if (op.gout && !(op.flags & GD4D_CHAIN_ADD_GOUT) && m < M) op.gout[(size_t)m * op.ldg + n] = v;
+        if (SPEC::has(RCN_H_RES) && op.res >= 0) v += bufs[op.res][row][n];
+        if (add_gout) v += addend[c][r];
+        if (SPEC::has(RCN_H_DST) && op.dst >= 0) bufs[op.dst][row][op.dst_col + n] = v;
+        if (SPEC::has(RCN_H_GOUT) && op.gout && !add_gout && m < M) op.gout[(size_t)m * op.ldg + n] = v;
       }
     }
   }
@@ -493,6 +559,7 @@ __device__ __forceinline__ void rc_headgemm(const ChainOp& op, float (*bufs)[RC_
 
 // LayerNorm over N columns (N % 64 == 0, N <= 512) of the 16 rows: wave w normalises rows 4 w .. 4 w + 3, 16 lanes per
 // row, a lane owns columns 64 ch + 4 l16 .. + 4 of every 64-column chunk.  gamma / beta are requested first.
+template <class SPEC>
 __device__ __forceinline__ void rc_layernorm(const ChainOp& op, float (*bufs)[RC_M][RC_LD], int m0, int M, int lane, int wave) {
   constexpr int MAXCH = RC_W / 64;
   if (wave >= RC_M / 4) return;                                // 4 rows per wave: with more than 4 waves the rest wait at the barrier
@@ -500,7 +567,7 @@ __device__ __forceinline__ void rc_layernorm(const ChainOp& op, float (*bufs)[RC
   float4 gm[MAXCH], bt[MAXCH], x[MAXCH], ad[MAXCH];
   // second output (res >= 0 with p2): buf[res] = result + p2[m, :] - the ADD operation that would follow (x + query_pos for
   // the next projection), its global rows requested here with gamma / beta
-  const bool second = op.res >= 0 && op.p2;
+  const bool second = SPEC::has(RCN_L_SECOND) && op.res >= 0 && op.p2;
   const size_t m_ld = (size_t)min(m0 + row, M - 1);
 #pragma unroll
   for (int ch = 0; ch < MAXCH; ++ch) {
@@ -528,7 +595,7 @@ __device__ __forceinline__ void rc_layernorm(const ChainOp& op, float (*bufs)[RC
   for (int o = 1; o < 16; o <<= 1) q += __shfl_xor(q, o);
   const float rstd = 1.0f / sqrtf(q / (float)N + op.eps);
   const int m = m0 + row;
-  const bool relu = op.flags & GD4D_CHAIN_RELU;
+  const bool relu = SPEC::has(RCN_L_RELU) && (op.flags & GD4D_CHAIN_RELU) != 0;
 #pragma unroll
   for (int ch = 0; ch < MAXCH; ++ch) {
     if (ch >= nch) break;
@@ -537,8 +604,8 @@ __device__ __forceinline__ void rc_layernorm(const ChainOp& op, float (*bufs)[RC
     v.x = (x[ch].x - mean) * rstd * gm[ch].x + bt[ch].x; v.y = (x[ch].y - mean) * rstd * gm[ch].y + bt[ch].y;
     v.z = (x[ch].z - mean) * rstd * gm[ch].z + bt[ch].z; v.w = (x[ch].w - mean) * rstd * gm[ch].w + bt[ch].w;
     if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-    if (op.dst >= 0) *reinterpret_cast<float4*>(&bufs[op.dst][row][n]) = v;
-    if (op.gout && m < M) *reinterpret_cast<float4*>(op.gout + (size_t)m * op.ldg + n) = v;
+    if (SPEC::has(RCN_L_DST) && op.dst >= 0) *reinterpret_cast<float4*>(&bufs[op.dst][row][n]) = v;
+    if (SPEC::has(RCN_L_GOUT) && op.gout && m < M) *reinterpret_cast<float4*>(op.gout + (size_t)m * op.ldg + n) = v;
     if (second)
       *reinterpret_cast<float4*>(&bufs[op.res][row][n]) = make_float4(ad[ch].x + v.x, ad[ch].y + v.y, ad[ch].z + v.z, ad[ch].w + v.w);
   }
@@ -645,11 +712,12 @@ __device__ __forceinline__ void rc_layernorm_bwd(const ChainOp& op, float (*bufs
 // Rows of global tensors into / onto an LDS buffer, float4 per lane, every load issued before the first use:
 //   LOAD: dst[:, dst_col + n] = f(p0[m, n]) (+ p1[m, n]);   ADD: dst[:, n] = src[:, n] (+ res[:, n]) (+ p2[m, n])
 // wave w handles RC_ROWS_PER_WAVE consecutive rows; N % 4 == 0, N <= 512 (two 256-column chunks per row).
-template <bool IS_ADD, bool TRAIN>
+template <bool IS_ADD, class SPEC>
 __device__ __forceinline__ void rc_rows(const ChainOp& op, float (*bufs)[RC_M][RC_LD], int m0, int M, int lane, int wave) {
   const int N = op.N;
   const float* ga = IS_ADD ? op.p2 : op.p0;                  // first global operand (may be null for ADD)
-  const float* gb = IS_ADD ? nullptr : op.p1;                 // second global operand (LOAD only)
+  constexpr bool TRAIN = SPEC::has(RCN_T_GOUT);
+  const float* gb = (IS_ADD || !SPEC::has(RCN_LD_P1)) ? nullptr : op.p1;   // second global operand (LOAD only)
   const int lda = IS_ADD ? op.ld2 : op.ld0, ldb = op.ld1;
   float4 va[RC_ROWS_PER_WAVE][2], vb[RC_ROWS_PER_WAVE][2];
 #pragma unroll
@@ -670,7 +738,7 @@ __device__ __forceinline__ void rc_rows(const ChainOp& op, float (*bufs)[RC_M][R
       const int n = 256 * cb + 4 * lane;
       if (n >= N) continue;
       float4 v = va[r][cb];
-      if (!IS_ADD && (op.flags & GD4D_CHAIN_INV_SIGMOID)) { v.x = inv_sigmoid(v.x); v.y = inv_sigmoid(v.y); v.z = inv_sigmoid(v.z); v.w = inv_sigmoid(v.w); }
+      if (!IS_ADD && SPEC::has(RCN_LD_INV) && (op.flags & GD4D_CHAIN_INV_SIGMOID)) { v.x = inv_sigmoid(v.x); v.y = inv_sigmoid(v.y); v.z = inv_sigmoid(v.z); v.w = inv_sigmoid(v.w); }
       v.x += vb[r][cb].x; v.y += vb[r][cb].y; v.z += vb[r][cb].z; v.w += vb[r][cb].w;
       if (IS_ADD) {
         const float4 s0 = *reinterpret_cast<const float4*>(&bufs[op.src][row][n]);
@@ -703,8 +771,9 @@ typedef const ChainProgram* rc_prog_ptr_t;
 #endif
 
 // bx: the workgroup's index in the launch (blockIdx.x).
-template <bool TRAIN>
+template <class SPEC>
 __device__ __forceinline__ void row_chain_body(const rc_prog_ptr_t pp, const int bx) {
+  constexpr bool TRAIN = SPEC::has(RCN_T_GOUT);             // (the stores of LOAD / SMALL_LINEAR; LN_BWD and DROPMASK by their kinds)
   const int M = pp->M, split = pp->split;
   const int blocks = (M + RC_M - 1) / RC_M;
   // Two programs: the second one's workgroups start at `split` = blocks rounded up to a multiple of 8, so that row block i of
@@ -781,7 +850,7 @@ __device__ __forceinline__ void row_chain_body(const rc_prog_ptr_t pp, const int
   // (bit 0) the weight images of the program's GEMMs, this workgroup's share of each
   auto touch_images = [&]() {
     for (int oi = op_base; oi < op_base + nops; ++oi) {
-      if (pp->ops[oi].kind == GD4D_CHAIN_HEADGEMM) {           // this workgroup's own aggregate rows (written by another XCD: cold)
+      if (SPEC::kind(GD4D_CHAIN_HEADGEMM) && pp->ops[oi].kind == GD4D_CHAIN_HEADGEMM) {           // this workgroup's own aggregate rows (written by another XCD: cold)
         const int rows = min(RC_M, M - m0);
         const char* a = reinterpret_cast<const char*>(pp->ops[oi].p2 + (size_t)m0 * pp->ops[oi].ld0 * pp->ops[oi].K);
         const unsigned pieces = (unsigned)rows * (unsigned)pp->ops[oi].ld0 * (unsigned)pp->ops[oi].K / 16u;
@@ -814,7 +883,8 @@ __device__ __forceinline__ void row_chain_body(const rc_prog_ptr_t pp, const int
     const ChainOp op = pp->ops[oi];                        // uniform: scalar loads
     switch (op.kind) {
       case GD4D_CHAIN_LOAD: {                              // dst[:, :N] = f(p0[m, :N]) (+ p1[m, :N])
-        if ((op.N & 3) == 0 && (op.dst_col & 3) == 0) { rc_rows<false, TRAIN>(op, bufs, m0, M, lane, wave); break; }
+        if (SPEC::has(RCN_LD_WIDE) && (op.N & 3) == 0 && (op.dst_col & 3) == 0) { rc_rows<false, SPEC>(op, bufs, m0, M, lane, wave); break; }
+        if constexpr (SPEC::has(RCN_LD_NARROW))
         for (int e = tid; e < RC_M * op.N; e += 64 * RC_WAVES) {      // a handful of columns (reference points)
           const int row = e / op.N, n = e - row * op.N;
           const int m = min(m0 + row, M - 1);
@@ -826,14 +896,25 @@ __device__ __forceinline__ void row_chain_body(const rc_prog_ptr_t pp, const int
         break;
       }
       case GD4D_CHAIN_GEMM:
-        if (op.flags & GD4D_CHAIN_EXACT) rc_gemm<true, TRAIN>(op, bufs, m0, M, lane, wave);
-        else rc_gemm<false, TRAIN>(op, bufs, m0, M, lane, wave);
+        if constexpr (SPEC::has(RCN_G_EXACT) && SPEC::has(RCN_G_PLAIN)) {
+          if (op.flags & GD4D_CHAIN_EXACT) rc_gemm<true, SPEC>(op, bufs, m0, M, lane, wave);
+          else rc_gemm<false, SPEC>(op, bufs, m0, M, lane, wave);
+        } else if constexpr (SPEC::has(RCN_G_EXACT)) {
+          rc_gemm<true, SPEC>(op, bufs, m0, M, lane, wave);
+        } else if constexpr (SPEC::has(RCN_G_PLAIN)) {
+          rc_gemm<false, SPEC>(op, bufs, m0, M, lane, wave);
+        }
         break;
-      case GD4D_CHAIN_HEADGEMM: rc_headgemm(op, bufs, m0, M, lane, wave); break;
-      case GD4D_CHAIN_LAYERNORM: rc_layernorm(op, bufs, m0, M, lane, wave); break;
-      case GD4D_CHAIN_ADD: rc_rows<true, TRAIN>(op, bufs, m0, M, lane, wave); break;   // dst = src + (res buffer) + (p2 global)
-      case GD4D_CHAIN_DROPMASK: {                         // buf[dst] = nn.Dropout's mask of a forward GEMM applied to buf[src]
-        if (!TRAIN) break;
+      case GD4D_CHAIN_HEADGEMM:
+        if constexpr (SPEC::kind(GD4D_CHAIN_HEADGEMM)) rc_headgemm<SPEC>(op, bufs, m0, M, lane, wave);
+        break;
+      case GD4D_CHAIN_LAYERNORM:
+        if constexpr (SPEC::kind(GD4D_CHAIN_LAYERNORM)) rc_layernorm<SPEC>(op, bufs, m0, M, lane, wave);
+        break;
+      case GD4D_CHAIN_ADD:                                 // dst = src + (res buffer) + (p2 global)
+        if constexpr (SPEC::kind(GD4D_CHAIN_ADD)) rc_rows<true, SPEC>(op, bufs, m0, M, lane, wave);
+        break;
+      case GD4D_CHAIN_DROPMASK: if constexpr (SPEC::kind(GD4D_CHAIN_DROPMASK)) {   // buf[dst] = nn.Dropout's mask of a forward GEMM applied to buf[src]
         const uint32_t lo = reinterpret_cast<const uint32_t*>(op.p0)[0], hi = reinterpret_cast<const uint32_t*>(op.p0)[1];
         const int nv = op.N / 4;
         for (int e = tid; e < RC_M * nv; e += 64 * RC_WAVES) {
@@ -848,12 +929,12 @@ __device__ __forceinline__ void row_chain_body(const rc_prog_ptr_t pp, const int
           if (op.gout && m0 + row < M) *reinterpret_cast<float4*>(op.gout + (size_t)(m0 + row) * op.ldg + n) = v;
         }
         break;
-      }
+      } else break;
       case GD4D_CHAIN_LN_BWD:
-        if (TRAIN)
+        if constexpr (SPEC::kind(GD4D_CHAIN_LN_BWD))
           rc_layernorm_bwd(op, bufs, reinterpret_cast<float*>(rc_smem + sizeof(float) * RC_BUFS * RC_M * RC_LD + 256 * RC_WAVES), m0, M, wg, tid);
         break;
-      case GD4D_CHAIN_SMALL_LINEAR: {                      // K <= 8 inputs (position_encoder's first Linear): plain FMAs
+      case GD4D_CHAIN_SMALL_LINEAR: if constexpr (SPEC::kind(GD4D_CHAIN_SMALL_LINEAR)) {   // K <= 8 inputs (position_encoder's first Linear): plain FMAs
         // The first version evaluated inverse_sigmoid (a division and a logarithm) for every (row, output, input) and
         // fetched the weights inside the loop: 5.1 us for 16 x 256 x 3 MACs, on the critical path of the dual launch.
         // Now: the K inputs of a row are transformed once (into columns 8 .. 8 + K of the source buffer, which nothing
@@ -893,8 +974,8 @@ __device__ __forceinline__ void row_chain_body(const rc_prog_ptr_t pp, const int
           }
         }
         break;
-      }
-      case GD4D_CHAIN_REFINE: {                            // detr3d_transformer.py:201-214 on src = reg-branch output
+      } else break;
+      case GD4D_CHAIN_REFINE: if constexpr (SPEC::kind(GD4D_CHAIN_REFINE)) {   // detr3d_transformer.py:201-214 on src = reg-branch output
         if (tid < RC_M && m0 + tid < M) {
           const int m = m0 + tid;
           const float* t = bufs[op.src][tid];
@@ -909,8 +990,8 @@ __device__ __forceinline__ void row_chain_body(const rc_prog_ptr_t pp, const int
           bufs[op.dst][tid][0] = bufs[op.dst][tid][1] = bufs[op.dst][tid][2] = 0.5f;
         }
         break;
-      }
-      case GD4D_CHAIN_SIGNAL: {
+      } else break;
+      case GD4D_CHAIN_SIGNAL: if constexpr (SPEC::kind(GD4D_CHAIN_SIGNAL)) {
         // This row block's global outputs so far (gout of the operations above) are handed to row block wg of the OTHER
         // program of the launch.  Both sit on one XCD (see `split`), so the L2 is their point of coherence: every thread
         // waits until its stores have been acknowledged by the L2 (the L1 is write-through), the workgroup meets, one
@@ -920,8 +1001,8 @@ __device__ __forceinline__ void row_chain_body(const rc_prog_ptr_t pp, const int
         __syncthreads();
         if (tid == 0) __hip_atomic_store(reinterpret_cast<unsigned*>(op.gout) + wg, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         break;
-      }
-      case GD4D_CHAIN_WAIT: {
+      } else break;
+      case GD4D_CHAIN_WAIT: if constexpr (SPEC::kind(GD4D_CHAIN_WAIT)) {
         // ... and the consumer: one thread polls the flag in the L2 (bounded: ~0.2 s - then the error word at gout is raised,
         // the rows this program LOADs from here on are replaced by NaN, and the program goes on: a loud wrong result instead of
         // a hung GPU; the host reads the error word, ops.check_handoff), the barrier below releases the others.  The rows the next LOAD reads were never in this CU's L1 (invalidated at the launch's
@@ -944,12 +1025,12 @@ __device__ __forceinline__ void row_chain_body(const rc_prog_ptr_t pp, const int
           if (!rc_poison) __hip_atomic_store(const_cast<unsigned*>(f), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         break;
-      }
+      } else break;
       default: break;
     }
     __syncthreads();
-    if (op.kind == GD4D_CHAIN_WAIT) poisoned = rc_poison != 0;             // (workgroup-uniform)
-    if (poisoned && op.kind == GD4D_CHAIN_LOAD && op.dst >= 0) {
+    if (SPEC::kind(GD4D_CHAIN_WAIT) && op.kind == GD4D_CHAIN_WAIT) poisoned = rc_poison != 0;             // (workgroup-uniform)
+    if (SPEC::kind(GD4D_CHAIN_WAIT) && poisoned && op.kind == GD4D_CHAIN_LOAD && op.dst >= 0) {
       for (int e = tid; e < RC_M * op.N; e += 64 * RC_WAVES) {
         const int row = e / op.N, n = e - row * op.N;
         bufs[op.dst][row][op.dst_col + n] = __builtin_nanf("");
@@ -964,7 +1045,7 @@ __device__ __forceinline__ void row_chain_body(const rc_prog_ptr_t pp, const int
   trace_mark_if(g_trace_rowchain, (second ? 0x87ull : 0x81ull) | ((unsigned long long)nops << 8), wg == 0);
 }
 
-template <bool TRAIN>
+template <class SPEC>
 __global__ __launch_bounds__(64 * RC_WAVES) void row_chain_kernel(const ChainProgram by_value) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const rc_prog_ptr_t pp = (rc_prog_ptr_t)__builtin_amdgcn_kernarg_segment_ptr();   // explicit arguments start at 0
@@ -972,7 +1053,7 @@ __global__ __launch_bounds__(64 * RC_WAVES) void row_chain_kernel(const ChainPro
   const ChainProgram* pp = &by_value;
 #endif
   (void)by_value;
-  row_chain_body<TRAIN>(pp, (int)blockIdx.x);
+  row_chain_body<SPEC>(pp, (int)blockIdx.x);
 }
 
 // gd4d_row_chain_guest_fwd: the row chain(s) of a launch plus GUEST workgroups that run one decoder layer's value_proj over a few
@@ -980,7 +1061,7 @@ __global__ __launch_bounds__(64 * RC_WAVES) void row_chain_kernel(const ChainPro
 // of the 256 compute units for 15-50 us and is bound by the latency of ONE unit; the others idle.  The guests are dispatched
 // after the chain's workgroups (higher indices), ask for the same LDS (one workgroup per compute unit) and share nothing with
 // the chain: no hand-off, no second stream, no cross-stream edge in a replayed graph - the launch ends when both have.
-template <bool IN_CHLAST>
+template <bool IN_CHLAST, class SPEC>
 __global__ __launch_bounds__(64 * RC_WAVES) void row_chain_guest_kernel(const ChainProgram by_value, const VpaParams guest, const int gbase,
                                                                          const int gcount) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -996,7 +1077,7 @@ __global__ __launch_bounds__(64 * RC_WAVES) void row_chain_guest_kernel(const Ch
     trace_mark_if(g_trace_rowchain, 0x89ull, (int)blockIdx.x == gbase);
     return;
   }
-  row_chain_body<false>(pp, (int)blockIdx.x);
+  row_chain_body<SPEC>(pp, (int)blockIdx.x);
 }
 
 // A TRAINING chain with the pyramid gradient's record fills as guests (gd4d_row_chain_fill_fwd): the fills of a step need the scan
@@ -1026,7 +1107,7 @@ __global__ __launch_bounds__(64 * RC_WAVES) void row_chain_fill_kernel(const Cha
     }
     return;
   }
-  row_chain_body<true>(pp, (int)blockIdx.x);
+  row_chain_body<RcAll<true>>(pp, (int)blockIdx.x);
 }
 
 // XCC id of every workgroup of a launch (gd4d_xcd_placement_probe): the hand-offs above rely on workgroups j and j + 8 k sharing
@@ -1178,6 +1259,91 @@ static int rc_validate(const gd4d_chain_op* program, int nops, int which) {
   return GD4D_OK;
 }
 
+// The bits a program needs: the conditions the device code tests (rc_gemm, rc_headgemm, rc_layernorm, rc_rows, row_chain_body).
+static uint64_t rc_needs(const gd4d_chain_op* program, int nops) {
+  using namespace gd4d;
+  uint64_t n = 0;
+  for (int i = 0; i < nops; ++i) {
+    const gd4d_chain_op& op = program[i];
+    if (op.kind >= 1 && op.kind <= 11) n |= rcn_kind(op.kind);
+    switch (op.kind) {
+      case GD4D_CHAIN_GEMM: {
+        const bool split_out = op.flags & GD4D_CHAIN_SPLIT_OUT, split_kv = op.flags & GD4D_CHAIN_SPLIT_KV, src2 = op.flags & GD4D_CHAIN_SRC2;
+        n |= (op.flags & GD4D_CHAIN_EXACT) ? RCN_G_EXACT : RCN_G_PLAIN;
+        if (src2) n |= RCN_G_SRC2;
+        if (split_out) n |= RCN_G_SPLIT_OUT;
+        if (split_kv) n |= RCN_G_SPLIT_KV;
+        if (op.flags & GD4D_CHAIN_SPLIT_KV_KEEP) n |= RCN_G_KV_KEEP;
+        if (op.flags & GD4D_CHAIN_RELU) n |= RCN_G_RELU;
+        if (op.flags & GD4D_CHAIN_SIGMOID) n |= RCN_G_SIGMOID;
+        if (op.flags & (GD4D_CHAIN_MASK_P2 | GD4D_CHAIN_DROPOUT)) n |= RCN_G_TRAIN;
+        if (op.res >= 0 && !src2) n |= RCN_G_RES;
+        if (op.p2 && !split_out && !split_kv) n |= RCN_G_ADD | (op.p3 ? RCN_G_ADD2 : 0);
+        if (op.dst >= 0) n |= RCN_G_DST;
+        if (op.gout && !split_out) n |= RCN_G_GOUT;
+        break;
+      }
+      case GD4D_CHAIN_HEADGEMM:
+        if (op.flags & GD4D_CHAIN_ADD_GOUT) n |= RCN_H_ADD;
+        else if (op.gout) n |= RCN_H_GOUT;
+        if (op.res >= 0) n |= RCN_H_RES;
+        if (op.dst >= 0) n |= RCN_H_DST;
+        break;
+      case GD4D_CHAIN_LAYERNORM:
+        if (op.res >= 0 && op.p2) n |= RCN_L_SECOND;
+        if (op.flags & GD4D_CHAIN_RELU) n |= RCN_L_RELU;
+        if (op.gout) n |= RCN_L_GOUT;
+        if (op.dst >= 0) n |= RCN_L_DST;
+        break;
+      case GD4D_CHAIN_LOAD:
+        n |= ((op.N & 3) == 0 && (op.dst_col & 3) == 0) ? RCN_LD_WIDE : RCN_LD_NARROW;
+        if (op.flags & GD4D_CHAIN_INV_SIGMOID) n |= RCN_LD_INV;
+        if (op.p1) n |= RCN_LD_P1;
+        if (op.gout) n |= RCN_T_GOUT;
+        break;
+      case GD4D_CHAIN_ADD:
+      case GD4D_CHAIN_SMALL_LINEAR:
+        if (op.gout) n |= RCN_T_GOUT;
+        break;
+      default: break;
+    }
+  }
+  return n;
+}
+
+// The instantiations by index: 0 = generic inference, 1 .. 6 = the table, 7 = generic training.  Only RcChainB (and the generic
+// inference body) exist with guests.
+enum { RC_GENERIC = 0, RC_TABLE_N = 6, RC_GENERIC_TRAIN = 7 };
+static const struct { const char* name; uint64_t mask; bool guests; } RC_TABLE[RC_TABLE_N] = {
+    {"in_proj", gd4d::RcInProj::mask, false},        {"initial_reference", gd4d::RcInitRef::mask, false},
+    {"chain_a", gd4d::RcChainA::mask, false},        {"chain_b", gd4d::RcChainB::mask, true},
+    {"chain_b_last", gd4d::RcChainBLast::mask, false}, {"head", gd4d::RcHead::mask, false}};
+static int g_rc_specialise = 1;        // process-wide (gd4d_row_chain_specialise)
+
+static int rc_choose(uint64_t needs, bool guests) {
+  if (RC_FORCE_TRAIN || (needs & gd4d::RCN_TRAIN)) return RC_GENERIC_TRAIN;
+  if (!g_rc_specialise) return RC_GENERIC;
+  for (int i = 0; i < RC_TABLE_N; ++i)
+    if ((needs & ~RC_TABLE[i].mask) == 0 && (!guests || RC_TABLE[i].guests)) return i + 1;
+  return RC_GENERIC;
+}
+
+// f(SPEC{}) for the instantiation `choice` names
+template <class F>
+static int rc_with_spec(int choice, F f) {
+  using namespace gd4d;
+  switch (choice) {
+    case 1: return f(RcInProj{});
+    case 2: return f(RcInitRef{});
+    case 3: return f(RcChainA{});
+    case 4: return f(RcChainB{});
+    case 5: return f(RcChainBLast{});
+    case 6: return f(RcHead{});
+    case RC_GENERIC_TRAIN: return f(RcAll<true>{});
+    default: return f(RcAll<false>{});
+  }
+}
+
 static int rc_launch(const gd4d_chain_op* a, int na, const gd4d_chain_op* b, int nb, int M, void* stream,
                      const gd4d_chain_guest* guest = nullptr, const gd4d::FillGuest* fills = nullptr, int fill_workgroups = 0) {
   using namespace gd4d;
@@ -1194,27 +1360,18 @@ static int rc_launch(const gd4d_chain_op* a, int na, const gd4d_chain_op* b, int
         if (op.ld2 < heads * blocks * 512 || op.ld1 < heads * ((blocks + 1) / 2) * 1024) return GD4D_EINVAL;
       }
     }
-  // the operations only a training step uses (and the stores of LOAD / ADD / SMALL_LINEAR) are compiled into a second
-  // instantiation: with them in, the inference step's chains ran 10 % slower (221 against 163 registers, longer epilogues)
-  bool train = false;
-  for (int w = 0; w < 2; ++w) {
-    const gd4d_chain_op* pr = w ? b : a;
-    for (int i = 0; i < (w ? nb : na); ++i) {
-      const gd4d_chain_op& op = pr[i];
-      train = train || op.kind == GD4D_CHAIN_LN_BWD || op.kind == GD4D_CHAIN_DROPMASK ||
-              (op.kind == GD4D_CHAIN_GEMM && (op.flags & (GD4D_CHAIN_MASK_P2 | GD4D_CHAIN_DROPOUT))) ||
-              ((op.kind == GD4D_CHAIN_LOAD || op.kind == GD4D_CHAIN_ADD || op.kind == GD4D_CHAIN_SMALL_LINEAR) && op.gout);
-    }
-  }
+  // which instantiation: what both programs need against the table (the operations only a training step uses, and the stores of
+  // LOAD / ADD / SMALL_LINEAR, live in the generic training instantiation alone)
+  const uint64_t needs = rc_needs(a, na) | (nb > 0 ? rc_needs(b, nb) : 0);
+  const int choice = rc_choose(needs, guest != nullptr);
+  const bool train = choice == RC_GENERIC_TRAIN;
   // the guests' job (gd4d_value_proj_fwd's geometry: one layer, pixel-major fp32 rows) - checked before anything touches the device
   VpaParams g{};
   if (guest) {
-    if (train) return GD4D_EUNSUPPORTED;
+    if (train && !RC_FORCE_TRAIN) return GD4D_EUNSUPPORTED;
     if (int rc = va_guest_params(guest, g)) return rc;
   }
   const size_t lds = sizeof(float) * RC_BUFS * RC_M * RC_LD + 256 * RC_WAVES + (train ? sizeof(float) * 8 * RC_W : 0);   // row buffers + the prefetch dump area (+ LN_BWD's partial sums)
-  const void* kern = train ? reinterpret_cast<const void*>(row_chain_kernel<true>) : reinterpret_cast<const void*>(row_chain_kernel<false>);
-  if (!allow_dynamic_lds(kern, (int)lds)) return GD4D_ELAUNCH;
   const int blocks = (M + RC_M - 1) / RC_M;
   ChainProgram prog{};
   const int split = nb > 0 ? (blocks + 7) & ~7 : 0;      // second program: same XCD per row block (see the kernel)
@@ -1240,7 +1397,12 @@ static int rc_launch(const gd4d_chain_op* a, int na, const gd4d_chain_op* b, int
       hipLaunchKernelGGL(kern, dim3(gbase + gcount), dim3(64 * RC_WAVES), lds, static_cast<hipStream_t>(stream), prog, g, gbase, gcount);
       return check_launch();
     };
-    return g.in_chlast ? go(row_chain_guest_kernel<true>) : go(row_chain_guest_kernel<false>);
+#if RC_FORCE_TRAIN
+    return g.in_chlast ? go(row_chain_guest_kernel<true, RcAll<true>>) : go(row_chain_guest_kernel<false, RcAll<true>>);
+#else
+    if (choice == 4) return g.in_chlast ? go(row_chain_guest_kernel<true, RcChainB>) : go(row_chain_guest_kernel<false, RcChainB>);
+    return g.in_chlast ? go(row_chain_guest_kernel<true, RcAll<false>>) : go(row_chain_guest_kernel<false, RcAll<false>>);
+#endif
   }
   if (fills) {                                             // (the training instantiation, whatever the program holds)
     if (guest) return GD4D_EINVAL;
@@ -1259,11 +1421,33 @@ static int rc_launch(const gd4d_chain_op* a, int na, const gd4d_chain_op* b, int
                        gbase, gcount);
     return check_launch();
   }
-  if (train)
-    hipLaunchKernelGGL(row_chain_kernel<true>, dim3(nb > 0 ? split + blocks : blocks), dim3(64 * RC_WAVES), lds, static_cast<hipStream_t>(stream), prog);
-  else
-    hipLaunchKernelGGL(row_chain_kernel<false>, dim3(nb > 0 ? split + blocks : blocks), dim3(64 * RC_WAVES), lds, static_cast<hipStream_t>(stream), prog);
-  return check_launch();
+  return rc_with_spec(choice, [&](auto spec) -> int {
+    auto kern = row_chain_kernel<decltype(spec)>;
+    if (!allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return GD4D_ELAUNCH;
+    hipLaunchKernelGGL(kern, dim3(nb > 0 ? split + blocks : blocks), dim3(64 * RC_WAVES), lds, static_cast<hipStream_t>(stream), prog);
+    return check_launch();
+  });
+}
+
+extern "C" int gd4d_row_chain_specialise(int on) {
+  const int was = g_rc_specialise;
+  if (on >= 0) g_rc_specialise = on != 0;
+  return was;
+}
+
+extern "C" int gd4d_row_chain_choice(const gd4d_chain_op* program_a, int nops_a, const gd4d_chain_op* program_b, int nops_b, int guests) {
+  if (!program_a || nops_a <= 0 || nops_b < 0 || (nops_b > 0 && !program_b)) return GD4D_EINVAL;
+  if (nops_a + nops_b > GD4D_CHAIN_MAX_OPS) return GD4D_EUNSUPPORTED;
+  if (int rc = rc_validate(program_a, nops_a, nops_b > 0 ? 1 : 0)) return rc;
+  if (nops_b > 0)
+    if (int rc = rc_validate(program_b, nops_b, 2)) return rc;
+  return rc_choose(rc_needs(program_a, nops_a) | (nops_b > 0 ? rc_needs(program_b, nops_b) : 0), guests != 0);
+}
+
+extern "C" const char* gd4d_row_chain_choice_name(int choice) {
+  if (choice == RC_GENERIC) return "generic";
+  if (choice == RC_GENERIC_TRAIN) return "generic_train";
+  return choice >= 1 && choice <= RC_TABLE_N ? RC_TABLE[choice - 1].name : "";
 }
 
 extern "C" int gd4d_xcd_placement_probe(int32_t* out, int blocks, void* stream) {

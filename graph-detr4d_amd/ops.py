@@ -2314,6 +2314,24 @@ def row_chain2_fwd(program_a, program_b, m, guest=None, fills=None):
         _call('gd4d_row_chain2_fwd', a, len(program_a), b, len(program_b), int(m))
 
 
+def row_chain_choice(program_a, program_b=None, guest=False):
+    """gd4d_row_chain_choice (no GPU): the name of the chain kernel's instantiation a launch of these program(s) runs - 'generic',
+    a table entry ('in_proj', 'initial_reference', 'chain_a', 'chain_b', 'chain_b_last', 'head') or 'generic_train'.  The programs are
+    validated as a launch validates them (Gd4dError)."""
+    lib = _lib.load()
+    a = (ChainOp * len(program_a))(*program_a)
+    b = (ChainOp * len(program_b))(*program_b) if program_b else None
+    code = lib.gd4d_row_chain_choice(a, len(program_a), b, len(program_b) if program_b else 0, int(bool(guest)))
+    _lib.check(code if code < 0 else 0, 'gd4d_row_chain_choice')
+    return lib.gd4d_row_chain_choice_name(code).decode()
+
+
+def row_chain_specialise(on=None):
+    """gd4d_row_chain_specialise: False sends every inference chain launch of the PROCESS to the generic kernel (an A/B: same bits),
+    True (the default) uses the table of specialised instantiations; None only asks.  Returns the setting before the call."""
+    return bool(_lib.load().gd4d_row_chain_specialise(-1 if on is None else int(bool(on))))
+
+
 def mha_core_presplit_fwd(q, kv, num_heads, attn_mask=None, want_lse=False, dropout_p=0., seed=None):
     """gd4d_mha_core_presplit_fwd: the self-attention core (batch 1) on K / V planes a chain GEMM wrote (KVPlanes).
     q (M, 1, C); attn_mask, want_lse, dropout_p / seed as for mha_core_fwd.  Returns (M, 1, C) [, lse]; without dropout

@@ -702,6 +702,22 @@ int gd4d_row_chain_guest_fwd(const gd4d_chain_op* program_a, int nops_a, const g
  * the side stream, beside the first layer's query side).  max_cus as gd4d_value_proj_fwd. */
 int gd4d_value_proj_guest_fwd(const gd4d_chain_guest* job, int max_cus, void* stream);
 
+/* Which instantiation of the chain kernel a launch runs.  The kernel is one interpreter; besides the two generic instantiations (every
+ * operation; with and without the training operations) the library holds a small table of instantiations that name, at compile time,
+ * the operation kinds and variants their programs may use - the launches of the inference decoder step and of the head's box epilogue -
+ * with the other kinds and variants' code left out.  A launch takes the first table entry that covers what its one or two programs
+ * need, else the generic kernel.  Same arithmetic, same bits.
+ *   gd4d_row_chain_choice (no GPU): the instantiation gd4d_row_chain_fwd / gd4d_row_chain2_fwd (nops_b > 0) /
+ *     gd4d_row_chain_guest_fwd (guests != 0) would run: 0 = generic, 1 .. 6 = a table entry, 7 = generic with the training operations;
+ *     a negative code = what the launch would return for these programs (GD4D_EINVAL, GD4D_EUNSUPPORTED, GD4D_EALIGN).
+ *   gd4d_row_chain_choice_name: "generic", "in_proj", "initial_reference", "chain_a", "chain_b", "chain_b_last", "head",
+ *     "generic_train"; "" for another number.
+ *   gd4d_row_chain_specialise(on): on = 0 sends every inference launch of the process to the generic kernel (an A/B), 1 (the default)
+ *     uses the table, a negative value changes nothing; returns the setting before the call. */
+int gd4d_row_chain_choice(const gd4d_chain_op* program_a, int nops_a, const gd4d_chain_op* program_b, int nops_b, int guests);
+const char* gd4d_row_chain_choice_name(int choice);
+int gd4d_row_chain_specialise(int on);
+
 /* gd4d_mha_core_presplit_fwd - gd4d_mha_core_fwd (batch 1, Lq = Lk = L; mask / mask_kind, lse, drop_p / seed as there) with K and V handed over as the
  * split-bf16 operands of its MFMAs instead of fp32 rows: the two plane pairs a GEMM operation with GD4D_CHAIN_SPLIT_KV writes
  * beside the fp32 in-projection (layouts there; k_plane_stride / v_plane_stride = elements from the hi to the lo plane).  The
