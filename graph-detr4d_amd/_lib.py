@@ -35,6 +35,9 @@ SIGNATURES = {
     'gd4d_cross_attn_agg_sliced_fwd': (_i, [_vp, _c.c_int64, _vp, _vp] + [_i] * 8 + [_vp, _i, _i, _vp]),
     'gd4d_cross_attn_agg_items_fwd': (_i, [_vp, _vp, _vp, _c.c_int64, _c.c_int64, _vp, _vp, _vp] + [_i] * 8 + [_vp, _i, _i, _vp]),
     'gd4d_cross_attn_agg_items_coarse_fwd': (_i, [_vp, _vp, _vp, _c.c_int64, _c.c_int64, _vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 8 + [_vp, _vp]),
+    'gd4d_gather_slice_group': (_i, [_i]),
+    'gd4d_gather_slice_group_get': (_i, []),
+    'gd4d_gather_walk': (_i, [_i, _i, _i, _i, _vp, _vp]),
     'gd4d_chain_guest_bytes': (_c.c_size_t, []),
     'gd4d_value_proj_image_bytes': (_c.c_size_t, []),
     'gd4d_value_proj_image': (_i, [_vp, _vp, _vp, _vp]),

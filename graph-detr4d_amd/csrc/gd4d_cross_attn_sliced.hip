@@ -262,8 +262,10 @@ struct SlicedParams {
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-// (the walk: which (position, slice) workgroup `block` is; false: none)
-__device__ __forceinline__ bool sliced_walk(const SlicedParams& p, int block, int& pos, int& sl) {
+// (the walk: which (position, phase) workgroup `block` is; false: none.  A phase is one of the launch's slice_n slices - in
+//  gd4d_cross_attn_agg_items_coarse_fwd one of its 8 / NS groups of NS consecutive slices, then the projected rows' phase.  Host
+//  and device: gd4d_gather_walk runs it without a GPU)
+__host__ __device__ __forceinline__ bool sliced_walk(const SlicedParams& p, int block, int& pos, int& sl) {
   const int xcd = block & 7, jb = block >> 3;
   const int per_blk = p.blk * p.slice_n;                   // workgroups of one block of queries
   const int kb = jb / per_blk, rb = jb - kb * per_blk;
@@ -385,14 +387,24 @@ struct ItemsParams {
 // covers 8 items x 2 levels), LV0 = the first level gathered (levels LV0 .. LV0 + LT - 1 of the records and the geometry).
 // COARSE (gd4d_cross_attn_agg_items_coarse_fwd): the workgroup is the query's ninth "slice": wave h gathers head h's 128 bytes of
 // the PROJECTED rows of levels LV0 .. (ip.gc / ip.proj_base) and writes pagg instead of agg.
-template <int HH, int LT, typename VT, bool WIDE, int LAP = 4, int LV0 = 0, bool COARSE = false>
+//
+// NS = consecutive slices [sl, sl + NS) of the query gathered by this workgroup (gd4d_gather_slice_group; the training gathers
+// and the projected rows: 1).  Records, pairs, the LDS patch and wsum do not depend on the slice: a step's pairs are worked out
+// and parked once, then every slice of the group runs the step's passes from the patch - its own acc0 / acc1, its own base, the
+// same loads and FMAs in the same order, so a (query, head, slice) sums what it sums at NS = 1, bit for bit.  Still one pass in
+// flight per wave.
+#ifndef GD4D_GATHER_NOLOAD
+#define GD4D_GATHER_NOLOAD 0     // 1 (dev builds, timing only - results are wrong): no feature load, a value made of its offset instead
+#endif
+template <int HH, int LT, typename VT, bool WIDE, int LAP = 4, int LV0 = 0, bool COARSE = false, int NS = 1>
 __device__ __forceinline__ void cross_attn_agg_items_body(const ItemsParams& ip, const int pos, const int sl, char* s_raw) {
   const SlicedParams& p = ip.s;
   const PyramidGeom& geo = COARSE ? ip.gc : ip.g;
   constexpr int ES = sizeof(VT);
   constexpr int LA = LT;                                  // a lane set = the LAP level slots of an item
   static_assert(LA <= LAP && LV0 + LAP <= 4 && (LAP == 2 || LAP == 4), "level slots");
-  static_assert(!COARSE || (std::is_same<VT, float>::value && !WIDE && HH * kSlice == kChannels), "projected rows: fp32, 32 channels per head");
+  static_assert(!COARSE || (std::is_same<VT, float>::value && !WIDE && HH * kSlice == kChannels && NS == 1), "projected rows: fp32, 32 channels per head");
+  static_assert(NS == 1 || NS == 2 || NS == 4 || NS == 8, "slices per workgroup");
   constexpr int IPP = 16 / LAP;                           // items per pass: 4 (LAP = 2: 8)
   constexpr int IPS = 64 / LAP;                           // items per step (four passes): 16 (32)
   constexpr int CH = 4;                                   // passes per step (20 KB of LDS per workgroup of 8 waves)
@@ -431,6 +443,11 @@ __device__ __forceinline__ void cross_attn_agg_items_body(const ItemsParams& ip,
   const int T = (M + IPP - 1) / IPP;
   const int m_even = (M + 1) & ~1;                                         // a load covers a PAIR of items: the odd one out is
   f2v acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};                                // written with weight 0 (its line is in flight already)
+  f2v accn0[NS], accn1[NS];                                                // (NS > 1: the sums of slice s + n)
+  if constexpr (NS > 1) {
+#pragma unroll
+    for (int n = 0; n < NS; ++n) { accn0[n] = f2v{0.f, 0.f}; accn1[n] = f2v{0.f, 0.f}; }
+  }
   float wsum_lane = 0.f;
   if (M < IPS && M > 0) {                                                   // wave-uniform: items past M repeat the last one
     const int src = min(i_of, M - 1) * LAP + l_of;
@@ -471,48 +488,106 @@ __device__ __forceinline__ void cross_attn_agg_items_body(const ItemsParams& ip,
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const int t0 = it0 / IPP;
     const int nt = min(CH, T - t0);
-    for (int k = 0; k < nt; ++k) {
-      const uint4* row = reinterpret_cast<const uint4*>(rd + k * PASS);
-      uint4 pr[4];
+    if constexpr (NS == 1) {                                               // (kept as written: every NS = 1 kernel, the training
+      for (int k = 0; k < nt; ++k) {                                       //  gathers among them, compiles to the code it had)
+        const uint4* row = reinterpret_cast<const uint4*>(rd + k * PASS);
+        uint4 pr[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) pr[i] = row[i];                          // pairs j = 2 i, 2 i + 1: {off, w, off, w}
-      const int left = M - (t0 + k) * IPP;                                 // wave-uniform: items of this pass; load j's pair exists
-      float4 val[8];                                                       // while 2 (j / LAP) < left
+        for (int i = 0; i < 4; ++i) pr[i] = row[i];                          // pairs j = 2 i, 2 i + 1: {off, w, off, w}
+        const int left = M - (t0 + k) * IPP;                                 // wave-uniform: items of this pass; load j's pair exists
+        float4 val[8];                                                       // while 2 (j / LAP) < left
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if ((j % LAP) >= LA) continue;
-        if (2 * (j / LAP) >= left) break;
-        const unsigned raw = (j & 1) ? pr[j >> 1].z : pr[j >> 1].x;
-        const unsigned o = raw + lane_off;
-        const VT* ap = WIDE ? reinterpret_cast<const VT*>(base[j % LAP] + (((size_t)raw << 4) + lane_off))
-                            : reinterpret_cast<const VT*>(base[j % LAP] + o);
-        val[j] = Quad<VT>::load(ap);
+        for (int j = 0; j < 8; ++j) {
+          if ((j % LAP) >= LA) continue;
+          if (2 * (j / LAP) >= left) break;
+          const unsigned raw = (j & 1) ? pr[j >> 1].z : pr[j >> 1].x;
+          const unsigned o = raw + lane_off;
+          const VT* ap = WIDE ? reinterpret_cast<const VT*>(base[j % LAP] + (((size_t)raw << 4) + lane_off))
+                              : reinterpret_cast<const VT*>(base[j % LAP] + o);
+#if GD4D_GATHER_NOLOAD
+          val[j] = make_float4(__uint_as_float(o), 1.f, 2.f, 3.f); (void)ap;
+#else
+          val[j] = Quad<VT>::load(ap);
+#endif
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if ((j % LAP) >= LA) continue;
+          if (2 * (j / LAP) >= left) break;
+          const float w = __uint_as_float((j & 1) ? pr[j >> 1].w : pr[j >> 1].y);
+          const f2v ww = {w, w};
+          acc0 = __builtin_elementwise_fma(ww, f2v{val[j].x, val[j].y}, acc0);
+          acc1 = __builtin_elementwise_fma(ww, f2v{val[j].z, val[j].w}, acc1);
+        }
       }
-      __builtin_amdgcn_sched_barrier(0);
+    } else {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if ((j % LAP) >= LA) continue;
-        if (2 * (j / LAP) >= left) break;
-        const float w = __uint_as_float((j & 1) ? pr[j >> 1].w : pr[j >> 1].y);
-        const f2v ww = {w, w};
-        acc0 = __builtin_elementwise_fma(ww, f2v{val[j].x, val[j].y}, acc0);
-        acc1 = __builtin_elementwise_fma(ww, f2v{val[j].z, val[j].w}, acc1);
+      for (int n = 0; n < NS; ++n) {                                         // (the next step's barrier follows the last slice's passes)
+        const char* bs[LA];
+#pragma unroll
+        for (int l = 0; l < LA; ++l) bs[l] = base[l] + (size_t)n * p.slice_stride;
+        for (int k = 0; k < nt; ++k) {
+          const uint4* row = reinterpret_cast<const uint4*>(rd + k * PASS);
+          uint4 pr[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) pr[i] = row[i];                        // pairs j = 2 i, 2 i + 1: {off, w, off, w}
+          const int left = M - (t0 + k) * IPP;                               // wave-uniform: items of this pass; load j's pair exists
+          float4 val[8];                                                     // while 2 (j / LAP) < left
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            if ((j % LAP) >= LA) continue;
+            if (2 * (j / LAP) >= left) break;
+            const unsigned raw = (j & 1) ? pr[j >> 1].z : pr[j >> 1].x;
+            const unsigned o = raw + lane_off;
+            const VT* ap = WIDE ? reinterpret_cast<const VT*>(bs[j % LAP] + (((size_t)raw << 4) + lane_off))
+                                : reinterpret_cast<const VT*>(bs[j % LAP] + o);
+#if GD4D_GATHER_NOLOAD
+            val[j] = make_float4(__uint_as_float(o), 1.f, 2.f, 3.f); (void)ap;
+#else
+            val[j] = Quad<VT>::load(ap);
+#endif
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            if ((j % LAP) >= LA) continue;
+            if (2 * (j / LAP) >= left) break;
+            const float w = __uint_as_float((j & 1) ? pr[j >> 1].w : pr[j >> 1].y);
+            const f2v ww = {w, w};
+            accn0[n] = __builtin_elementwise_fma(ww, f2v{val[j].x, val[j].y}, accn0[n]);
+            accn1[n] = __builtin_elementwise_fma(ww, f2v{val[j].z, val[j].w}, accn1[n]);
+          }
+        }
       }
     }
   }
-  float4 acc = make_float4(acc0.x, acc0.y, acc1.x, acc1.y);
-  // the 8 corner slots meet in a fixed order (deterministic)
+  if constexpr (NS == 1) {
+    float4 acc = make_float4(acc0.x, acc0.y, acc1.x, acc1.y);
+    // the 8 corner slots meet in a fixed order (deterministic)
 #pragma unroll
-  for (int o = 8; o < 64; o <<= 1) {
-    acc.x += __shfl_xor(acc.x, o); acc.y += __shfl_xor(acc.y, o);
-    acc.z += __shfl_xor(acc.z, o); acc.w += __shfl_xor(acc.w, o);
+    for (int o = 8; o < 64; o <<= 1) {
+      acc.x += __shfl_xor(acc.x, o); acc.y += __shfl_xor(acc.y, o);
+      acc.z += __shfl_xor(acc.z, o); acc.w += __shfl_xor(acc.w, o);
+    }
+    if (COARSE) {
+      if (g == 0) *reinterpret_cast<float4*>(ip.pagg + (size_t)bq * kChannels + h * kSlice + c * 4) = acc;
+      return;
+    }
+    if (g == 0) *reinterpret_cast<float4*>(p.agg + ((size_t)bq * HH + h) * kChannels + s * kSlice + c * 4) = acc;
+  } else {
+#pragma unroll
+    for (int n = 0; n < NS; ++n) {
+      float4 acc = make_float4(accn0[n].x, accn0[n].y, accn1[n].x, accn1[n].y);
+#pragma unroll
+      for (int o = 8; o < 64; o <<= 1) {
+        acc.x += __shfl_xor(acc.x, o); acc.y += __shfl_xor(acc.y, o);
+        acc.z += __shfl_xor(acc.z, o); acc.w += __shfl_xor(acc.w, o);
+      }
+      if (g == 0) *reinterpret_cast<float4*>(p.agg + ((size_t)bq * HH + h) * kChannels + (s + n) * kSlice + c * 4) = acc;
+    }
   }
-  if (COARSE) {
-    if (g == 0) *reinterpret_cast<float4*>(ip.pagg + (size_t)bq * kChannels + h * kSlice + c * 4) = acc;
-    return;
-  }
-  if (g == 0) *reinterpret_cast<float4*>(p.agg + ((size_t)bq * HH + h) * kChannels + s * kSlice + c * 4) = acc;
-  if (s == 0 && ip.wsum) {                                                 // wave-uniform
+  if (s == 0 && ip.wsum) {                                                 // wave-uniform: the group that holds slice 0
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) wsum_lane += __shfl_xor(wsum_lane, o);
     if (lane == 0) ip.wsum[(size_t)bq * HH + h] = wsum_lane;
@@ -537,14 +612,17 @@ __global__ __launch_bounds__(64 * HH, OCC) void cross_attn_agg_items_kernel(cons
 // phase of an XCD), wave = head as everywhere: the same number of loads as one raw slice of the two fine levels, so the
 // launch stays balanced; its sums go to pagg (BQ, 256), which HEADGEMM adds to W_h agg_h + b_h wsum_h (wsum then
 // holds the fine levels' weights only: the projected rows carry their bias).
-template <int HH, typename VT, int OCC, bool WIDE = false>
+//
+// NS (gd4d_gather_slice_group): a fine workgroup gathers NS consecutive slices of its query from one set of pairs; the walk's
+// phases are then the 8 / NS slice groups and, last, the projected rows (still one workgroup per query).
+template <int HH, typename VT, int OCC, bool WIDE = false, int NS = 1>
 __global__ __launch_bounds__(64 * HH, OCC) void cross_attn_agg_items_coarse_kernel(const ItemsParams ip) {
   extern __shared__ __attribute__((aligned(16))) char s_raw[];   // [HH][CH][8][GP]
   trace_mark(g_trace_sliced, 6ull);
   int pos, sl;
   if (!sliced_walk(ip.s, blockIdx.x, pos, sl)) return;
-  if (sl == kSlices) cross_attn_agg_items_body<HH, 2, float, false, 2, 2, true>(ip, pos, sl, s_raw);
-  else cross_attn_agg_items_body<HH, 2, VT, WIDE, 2, 0, false>(ip, pos, sl, s_raw);
+  if (sl == kSlices / NS) cross_attn_agg_items_body<HH, 2, float, false, 2, 2, true>(ip, pos, sl, s_raw);
+  else cross_attn_agg_items_body<HH, 2, VT, WIDE, 2, 0, false, NS>(ip, pos, sl * NS, s_raw);
   trace_mark(g_trace_sliced, 0x86ull);
 }
 
@@ -801,10 +879,25 @@ static int fill_plan_params(PlanParams& pp, const float* ref, const float* offse
 }  // namespace gd4d
 
 namespace gd4d {
+// workgroups of a walk: 8 XCDs x (the sector in whole blocks of blk queries) x phases
+static long long gather_grid(int per_xcd, int blk, int phases) { return 8ll * ((per_xcd + blk - 1) / blk) * blk * phases; }
+
+// Slices per fine workgroup of gd4d_cross_attn_agg_items_coarse_fwd, process-wide (gd4d_gather_slice_group).  The default is the
+// fastest measured (docs/measurements_r28.md); EXTRA=-DGD4D_GATHER_SLICE_GROUP=n builds another one in for an A/B.
+#ifndef GD4D_GATHER_SLICE_GROUP
+#define GD4D_GATHER_SLICE_GROUP 2
+#endif
+static_assert(GD4D_GATHER_SLICE_GROUP == 1 || GD4D_GATHER_SLICE_GROUP == 2 || GD4D_GATHER_SLICE_GROUP == 4 || GD4D_GATHER_SLICE_GROUP == 8,
+              "slices per workgroup");
+static int g_gather_ns = GD4D_GATHER_SLICE_GROUP;
+// waves per SIMD the NS instantiation is compiled for - what its 4 NS sums per lane leave room for without scratch (a workgroup is
+// 2 waves per SIMD: 6 = three workgroups per CU, 4 = two, 2 = one)
+constexpr int gather_occ(bool wide, int ns) { return wide ? (ns > 4 ? 2 : 4) : (ns > 2 ? 4 : 6); }
+
 template <int HH, typename VT>
 static int launch_sliced(const SlicedParams& p, int L, hipStream_t s) {
   const size_t lds = (size_t)HH * 6 * 8 * 80;                       // [HH][CH][8][GP]
-  const dim3 grid(8 * ((p.per_xcd + p.blk - 1) / p.blk) * p.blk * p.slice_n);
+  const dim3 grid(gather_grid(p.per_xcd, p.blk, p.slice_n));
   auto go = [&](auto kern) -> int {
     if (lds > 65536 && !allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return GD4D_ELAUNCH;
     hipLaunchKernelGGL(kern, grid, dim3(64 * HH), lds, s, p);
@@ -873,7 +966,7 @@ template <int HH, typename VT>
 static int launch_items(const ItemsParams& ip, int L, bool wide, hipStream_t s, CountArgs* ca = nullptr) {
   const SlicedParams& p = ip.s;
   const size_t lds = (size_t)HH * 4 * 8 * 80;                        // [HH][CH][8][GP]
-  const dim3 grid(8 * ((p.per_xcd + p.blk - 1) / p.blk) * p.blk * p.slice_n);
+  const dim3 grid(gather_grid(p.per_xcd, p.blk, p.slice_n));
   if (ca) {                                            // gather + record count in one launch (training forward)
     if (HH != 8 || L != 4 || sizeof(VT) != 4 || wide) return GD4D_EUNSUPPORTED;
     const int wgs = (ca->BQ * HH + HH - 1) / HH;       // a count workgroup = HH (position, head) waves
@@ -998,17 +1091,50 @@ extern "C" int gd4d_cross_attn_agg_items_coarse_fwd(const void* const* level_ptr
   ip.item = reinterpret_cast<const float4*>(ip.s.pair);
   ip.wsum = wsum; ip.pagg = pagg;
   ip.cap_i = plan_cap_items(N, P);
-  ip.s.slice_n = kSlices + 1;                                        // the walk's ninth phase: the projected rows
+  const int ns = g_gather_ns;                                        // read at launch: a captured graph keeps its kernel and grid
+  ip.s.slice_n = kSlices / ns + 1;                                   // the walk's phases: the slice groups, then the projected rows
   const SlicedParams& p = ip.s;
   const size_t lds = (size_t)8 * 4 * 8 * 80;                         // [HH][CH][8][GP]
-  const dim3 grid(8 * ((p.per_xcd + p.blk - 1) / p.blk) * p.blk * p.slice_n);
+  const dim3 grid(gather_grid(p.per_xcd, p.blk, p.slice_n));
   hipStream_t s = static_cast<hipStream_t>(stream);
   auto go = [&](auto kern) -> int {
     hipLaunchKernelGGL(kern, grid, dim3(64 * 8), lds, s, ip);
     return check_launch();
   };
-  if (feats_dtype == GD4D_BF16) return wide ? go(cross_attn_agg_items_coarse_kernel<8, uint16_t, 4, true>) : go(cross_attn_agg_items_coarse_kernel<8, uint16_t, 6>);
-  return wide ? go(cross_attn_agg_items_coarse_kernel<8, float, 4, true>) : go(cross_attn_agg_items_coarse_kernel<8, float, 6>);
+  auto with_ns = [&](auto vt, auto w) -> int {                       // (NS > 1 holds 4 NS sums per lane: GATHER_OCC)
+    using VT = decltype(vt);
+    constexpr bool W = decltype(w)::value;
+    switch (ns) {
+      case 2: return go(cross_attn_agg_items_coarse_kernel<8, VT, gather_occ(W, 2), W, 2>);
+      case 4: return go(cross_attn_agg_items_coarse_kernel<8, VT, gather_occ(W, 4), W, 4>);
+      case 8: return go(cross_attn_agg_items_coarse_kernel<8, VT, gather_occ(W, 8), W, 8>);
+      default: return go(cross_attn_agg_items_coarse_kernel<8, VT, gather_occ(W, 1), W, 1>);
+    }
+  };
+  if (feats_dtype == GD4D_BF16) return wide ? with_ns(uint16_t{}, std::true_type{}) : with_ns(uint16_t{}, std::false_type{});
+  return wide ? with_ns(float{}, std::true_type{}) : with_ns(float{}, std::false_type{});
+}
+
+extern "C" int gd4d_gather_slice_group(int ns) {
+  const int was = gd4d::g_gather_ns;
+  if (ns == 1 || ns == 2 || ns == 4 || ns == 8) gd4d::g_gather_ns = ns;
+  return was;
+}
+
+extern "C" int gd4d_gather_slice_group_get(void) { return gd4d::g_gather_ns; }
+
+extern "C" int gd4d_gather_walk(int BQ, int blk, int ns, int block, int* pos, int* group) {
+  using namespace gd4d;
+  if (BQ <= 0 || blk <= 0 || (ns != 1 && ns != 2 && ns != 4 && ns != 8)) return GD4D_EINVAL;
+  SlicedParams p{};
+  p.BQ = BQ; p.per_xcd = (BQ + 7) / 8; p.blk = blk; p.slice_n = kSlices / ns + 1;
+  const long long grid = gather_grid(p.per_xcd, p.blk, p.slice_n);
+  if (grid > 0x7fffffffll) return GD4D_EUNSUPPORTED;
+  int q = -1, g = -1;
+  if (block < 0 || block >= grid || !sliced_walk(p, block, q, g)) q = g = -1;
+  if (pos) *pos = q;
+  if (group) *group = g;
+  return (int)grid;
 }
 
 extern "C" int gd4d_cross_attn_agg_items_count_fwd(const void* const* level_ptrs, const int32_t* level_hw,

@@ -2332,6 +2332,29 @@ def row_chain_specialise(on=None):
     return bool(_lib.load().gd4d_row_chain_specialise(-1 if on is None else int(bool(on))))
 
 
+def gather_slice_group(ns=None):
+    """gd4d_gather_slice_group / gd4d_gather_slice_group_get: how many consecutive slices a fine workgroup of
+    cross_attn_agg_coarse_fwd gathers from one set of pairs - 1, 2, 4 or 8 (ValueError otherwise), for every later launch of the
+    PROCESS (same bits for every value; a captured graph keeps what it was captured with); None only asks.  Returns the value
+    before the call."""
+    lib = _lib.load()
+    if ns is None:
+        return int(lib.gd4d_gather_slice_group_get())
+    if ns not in (1, 2, 4, 8):
+        raise ValueError('gather_slice_group: 1, 2, 4 or 8 slices per workgroup')
+    return int(lib.gd4d_gather_slice_group(int(ns)))
+
+
+def gather_walk(bq, blk, ns, block=-1):
+    """gd4d_gather_walk (no GPU): (grid size, position, group) of workgroup `block` in the walk of cross_attn_agg_coarse_fwd over
+    `bq` queries in blocks of `blk` with `ns` slices per workgroup; group 8 // ns is the projected rows' phase, position and group
+    are -1 for a workgroup with nothing to do."""
+    pos, group = ctypes.c_int(-1), ctypes.c_int(-1)
+    grid = _lib.load().gd4d_gather_walk(int(bq), int(blk), int(ns), int(block), ctypes.byref(pos), ctypes.byref(group))
+    _lib.check(grid if grid < 0 else 0, 'gd4d_gather_walk')
+    return grid, pos.value, group.value
+
+
 def mha_core_presplit_fwd(q, kv, num_heads, attn_mask=None, want_lse=False, dropout_p=0., seed=None):
     """gd4d_mha_core_presplit_fwd: the self-attention core (batch 1) on K / V planes a chain GEMM wrote (KVPlanes).
     q (M, 1, C); attn_mask, want_lse, dropout_p / seed as for mha_core_fwd.  Returns (M, 1, C) [, lse]; without dropout

@@ -222,6 +222,23 @@ int gd4d_cross_attn_agg_items_coarse_fwd(const void* const* level_ptrs, const in
                                          float* pagg, int B, int N, int Q, int Hh, int C, int L, int P, int feats_dtype,
                                          const int32_t* query_order, void* stream);
 
+/* How many slices a fine workgroup of gd4d_cross_attn_agg_items_coarse_fwd gathers.  Records, {offset, weight} pairs and wsum of a
+ * (query, head) do not depend on the slice: with ns > 1 a workgroup is (query, group of ns consecutive slices), works the pairs of a
+ * step out once and runs every slice of its group from them - each slice its own sums, the same loads and FMAs in the same order, so
+ * agg, wsum and pagg are bit-identical for every ns.  The walk's phases are the 8 / ns slice groups, then the projected rows (one
+ * workgroup per query as before).
+ *   gd4d_gather_slice_group(ns): ns = 1, 2, 4 or 8 sets the value for every later launch of the process, anything else changes
+ *     nothing; returns the value before the call.  Read at launch: a captured graph keeps what it was captured with.
+ *   gd4d_gather_slice_group_get(): the current value (the default: the fastest measured, docs/measurements_r28.md).
+ *   gd4d_gather_walk (no GPU): the launch's walk on the host, for B*Q = BQ queries, blocks of blk queries (a launch uses
+ *     ceil(BQ / 8), an XCD's whole sector) and ns slices per workgroup.  Returns the grid size (GD4D_EINVAL: BQ <= 0, blk <= 0 or ns not
+ *     one of 1, 2, 4, 8) and writes which workgroup `block` is: *pos = position in the locality order, *group = slice group
+ *     (slices [ns group, ns group + ns)), 8 / ns = the projected rows' phase; both -1 for a block that has nothing to do or lies
+ *     outside the grid.  pos / group may be NULL. */
+int gd4d_gather_slice_group(int ns);
+int gd4d_gather_slice_group_get(void);
+int gd4d_gather_walk(int BQ, int blk, int ns, int block, int* pos, int* group);
+
 /* gd4d_cross_attn_agg_items_count_fwd - a TRAINING step's forward gather and the first step of the pyramid gradient's bookkeeping
  * in one launch: gd4d_cross_attn_agg_items_fwd (all slices, every level) on plan_items and gd4d_pyramid_grad_count on plan_pairs (the
  * two forms of one plan: GD4D_CA_PLAN_BOTH) - the same results as the two launches (the slots, as there, in an order the atomics

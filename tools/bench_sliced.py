@@ -26,6 +26,8 @@ def main():
     ap.add_argument('--dtype', default='fp32')
     ap.add_argument('--plan', default='items', help='items (the inference step) | pairs (what the training kernels read)')
     ap.add_argument('--coarse', action='store_true', help='also time gd4d_cross_attn_agg_items_coarse_fwd and the projection of levels 2-3')
+    ap.add_argument('--ns', default='', help='with --coarse: time the coarse-projected gather at these slices per workgroup too '
+                                             '(ops.gather_slice_group), e.g. 1,2,4,8')
     ap.add_argument('--footprint', action='store_true',
                     help='count the distinct pixels the visible samples touch per level: the bytes a gather has to bring in at least once')
     a = ap.parse_args()
@@ -100,6 +102,14 @@ def main():
         ops.cross_attn_agg_coarse_fwd(plan, coarse, agg=ca, pagg=cp)
         mixed = ops.value_proj_heads_fwd(ca, plan.wsum, wv, bv) + cp
         print(f'coarse-projected gather {tc:.1f} us per launch; max |difference| to the raw gather {float((mixed - full).abs().max()):.2e}')
+        was = ops.gather_slice_group()
+        for ns in [int(x) for x in a.ns.split(',') if x]:
+            ops.gather_slice_group(ns)
+            ca2, cp2 = ops.cross_attn_agg_coarse_fwd(plan, coarse)
+            tn = timed(lambda: [ops.cross_attn_agg_coarse_fwd(plan, coarse, agg=ca2, pagg=cp2) for _ in range(6)], a.iters, 6)
+            print(f'coarse-projected gather, {ns} slice(s) per workgroup: {tn:.1f} us per launch; equal to the default\'s result: '
+                  f'{bool(torch.equal(ca2, ca) and torch.equal(cp2, cp))}')
+        ops.gather_slice_group(was)
     print(f'plan {a.plan} layout {a.layout} alias {a.alias} {a.dtype}: plan {t_plan:.1f} us, '
           f'sliced gather {t:.1f} us per launch ({corner_bytes / t / 1e6:.2f} TB/s of corner bytes)')
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Device-side timeline of ONE replayed decoder step without a profiler (dev tool): block 0 of the row-chain, attention
-core, channels-last copy and aggregate kernels stamps s_memrealtime (100 MHz) into a buffer (gd4d_trace_enable)."""
+core, channels-last copy and aggregate kernels stamps s_memrealtime (100 MHz) into a buffer (gd4d_trace_enable).
+Arguments: nhwc (channels-last levels), ns=K (ops.gather_slice_group(K) before the step is captured)."""
 import ctypes
 import os
 import sys
@@ -20,6 +21,10 @@ NAMES = {1: 'row_chain', 2: 'mha_core', 3: 'aggregate', 4: 'channels_last_copy',
 def main():
     dev = torch.device('cuda', 0)
     n_cams, layers, queries = 24, 6, 900
+    for arg in sys.argv[1:]:
+        if arg.startswith('ns='):
+            from graph_detr4d_amd import ops
+            ops.gather_slice_group(int(arg[3:]))
     tr, regs = bench.build_decoder(G, n_cams, layers, 'fp32', 1002)
     feats = [f.to(dev) for f in synthetic.feature_pyramid(n_cams, synthetic.R50_LEVELS, seed=1002)]
     if 'nhwc' in sys.argv[1:]:                           # the levels stored channels-last: gathered in place, no per-sample copy
