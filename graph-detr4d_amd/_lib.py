@@ -206,6 +206,19 @@ SIGNATURES = {
     'gd4d_osa_concat_conv_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     'gd4d_ese_gate_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'gd4d_ese_apply_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'gd4d_conv3x3_image_t_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_conv3x3_image_t': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_osa_concat_image_t_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_osa_concat_image_t': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_conv3x3_dgrad': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    'gd4d_osa_concat_dgrad': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    'gd4d_conv3x3_wgrad_tiles': (_c.c_longlong, [_i, _i, _i]),
+    'gd4d_osa_concat_wgrad_tiles': (_c.c_longlong, [_i, _i, _i]),
+    'gd4d_conv_wgrad_workspace_bytes': (_c.c_size_t, [_i, _i, _i, _i]),
+    'gd4d_conv3x3_wgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd4d_osa_concat_wgrad': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd4d_ese_bwd_workspace_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_ese_bwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

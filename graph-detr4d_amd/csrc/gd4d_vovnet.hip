@@ -18,7 +18,8 @@
 // v_mfma_f32_32x32x16_bf16.  No atomics; every sum has a fixed order (K: chunk by chunk of 32 channels, tap by tap inside a chunk; pool:
 // 32 lanes by an xor butterfly, then the four waves, then the tiles in order): two runs give the same bits.
 //
-// One GEMM kernel, vv_gemm_kernel<MT, MODE>, in the style of depth_conv_kernel (gd4d_depth_net.hip): the weight image is the MFMA's A
+// One GEMM kernel, vv_gemm_kernel<MT, MODE, EPI> (gd4d_vovnet_gemm.h: gd4d_vovnet_train.hip instantiates it too, with the backward
+// epilogue), in the style of depth_conv_kernel (gd4d_depth_net.hip): the weight image is the MFMA's A
 // operand, the pixels its B operand, so an accumulator lane holds one pixel and 16 channels and the NCHW stores of a wave are 16-pixel
 // row segments.  A workgroup is 4 waves and owns 128 output pixels (8 rows x 16 columns; MODE OSA: 128 consecutive pixels of the
 // flattened image) x 32 MT output channels; wave w holds pixels 32 w .. 32 w + 31 and all MT row blocks (MT f32x16 accumulators).
@@ -51,251 +52,9 @@
 // pack_conv_image (gd4d_conv_common.h has the format).
 // Left off: a 2 x 2 register tile per wave (halves the A reads from LDS), a double-buffered stride-2 halo, fusing the gate's matvec
 // into the last aggregation tile, NHWC.
-#include "gd4d_common.h"
-#include "gd4d_bf16x3.h"
-#include "gd4d_conv_common.h"
+#include "gd4d_vovnet_gemm.h"
 
 namespace gd4d {
-
-constexpr int VV_THREADS = 256, VV_KC = 32, VV_TY = 8, VV_TX = 16, VV_PIX = VV_TY * VV_TX;
-constexpr int VV_MAX_SRC = 6;
-enum { VV_S1 = 0, VV_S2 = 1, VV_OSA = 2 };
-
-template <int MODE> struct VvGeom;
-template <> struct VvGeom<VV_S1> { static constexpr int TAPS = 9, STRIDE = 1, HE_H = VV_TY + 2, HE_W = VV_TX + 2, HBUF = 2; };
-template <> struct VvGeom<VV_S2> { static constexpr int TAPS = 9, STRIDE = 2, HE_H = 2 * VV_TY + 1, HE_W = 2 * VV_TX + 1, HBUF = 1; };
-template <> struct VvGeom<VV_OSA> { static constexpr int TAPS = 1, STRIDE = 1, HE_H = 1, HE_W = VV_PIX, HBUF = 2; };
-
-template <int MODE> constexpr int vv_halo() { return VvGeom<MODE>::HE_H * VvGeom<MODE>::HE_W; }
-template <int MODE> constexpr int vv_h_stage() { return 2 * 4 * vv_halo<MODE>() * 16; }               // hi + lo planes of one chunk
-constexpr int vv_w_stage(int mt) { return 2 * 4 * 32 * mt * 16; }                                   // hi + lo planes of one step
-template <int MT, int MODE> constexpr int vv_lds() { return 2 * vv_w_stage(MT) + VvGeom<MODE>::HBUF * vv_h_stage<MODE>(); }
-
-static_assert(vv_lds<7, VV_S2>() <= 160 * 1024 && vv_lds<7, VV_S1>() <= 160 * 1024, "LDS budget of a CU");
-
-// the M tiling: MT row blocks of 32 per workgroup, one of {7, 5, 4, 3, 2, 1} that divides Cout / 32.  A workgroup's time goes as
-// MT + 0.4 (its MFMAs, and per step the barrier and the B fragments every tiling pays; 0.4 fits the two pairs measured in
-// docs/measurements_r22.md), a launch's as that times the workgroups, of which fewer than one per CU cost as much as one per CU:
-// with pixels enough the largest count wins (the least B traffic), with few pixels (stage 5, six cameras) the launch is cut into
-// more workgroups.  Ties go to the larger count.  The 0.4 is a two-point fit taken on one part (an MI355X, V-99 at 320 x 800 and six
-// cameras): a tuning constant, not a model; the result's bits do not depend on the choice.  The CU count is the current device's.
-static long long vv_cus() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
-  return cus;
-}
-static inline int vv_mt(int cout, long long tiles) {
-  const long long VV_CUS = vv_cus();
-  const int nb = cout / 32;
-  const int pick[6] = {7, 5, 4, 3, 2, 1};
-  int best = 1;
-  long long best_cost = -1;
-  for (int i = 0; i < 6; ++i) {
-    if (nb % pick[i]) continue;
-    const long long groups = tiles * (nb / pick[i]);
-    const long long cost = (groups > VV_CUS ? groups : VV_CUS) * (10 * pick[i] + 4);
-    if (best_cost < 0 || cost < best_cost) {
-      best = pick[i];
-      best_cost = cost;
-    }
-  }
-  return best;
-}
-// m_blocks of the entry points: 0 = vv_mt's choice, or one of the six counts that divides Cout / 32 (the tests run every tiling)
-static inline bool vv_mt_ok(int cout, int m_blocks) {
-  return m_blocks == 0 || ((m_blocks == 7 || (m_blocks >= 1 && m_blocks <= 5)) && (cout / 32) % m_blocks == 0);
-}
-
-// ---- the GEMM ---------------------------------------------------------------------------------------------------------------
-struct VvParams {
-  const float* src[VV_MAX_SRC];   // NCHW maps of the same N, H, W; the convolutions have one
-  int src_ch[VV_MAX_SRC];         // channels of each map
-  int src_chunk0[VV_MAX_SRC];     // the first K chunk of each map
-  int n_src, chunks;
-  int h, w, ho, wo, tiles_x, tiles_img;
-  int cout;
-  const char* image;
-  const float *scale, *shift;
-  float* out;
-  float* partials;                // OSA: (N, tiles_img, cout)
-};
-
-template <int MT, int MODE>
-__global__ __launch_bounds__(VV_THREADS) void vv_gemm_kernel(const VvParams p) {
-  using G = VvGeom<MODE>;
-  constexpr int TAPS = G::TAPS, S = G::STRIDE, HE_W = G::HE_W, HALO = vv_halo<MODE>();
-  constexpr int ROWS = 32 * MT, W_BLK = 2 * 4 * 32 * 16, W_ARR = W_BLK / 2, W_STAGE = MT * W_BLK;   // a row block's step: hi + lo, 4 KB
-  constexpr int H_ITEMS = 4 * HALO, H_ARR = H_ITEMS * 16, H_STAGE = 2 * H_ARR;
-  constexpr int H_PASSES = (H_ITEMS + VV_THREADS - 1) / VV_THREADS;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* const wbuf = smem;                                   // [2][MT row blocks][hi, lo][4][32][16 B]
-  char* const hbuf = smem + 2 * W_STAGE;                     // [HBUF][hi, lo][4][HALO][16 B]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int l32 = lane & 31, kg = lane >> 5;
-
-  // work item: (image, pixel tile) x row tile
-  const int img = blockIdx.x / p.tiles_img, rt = blockIdx.x - img * p.tiles_img;
-  const int tile_m = blockIdx.y;
-  const int ty0 = MODE == VV_OSA ? 0 : (rt / p.tiles_x) * VV_TY;
-  const int tx0 = MODE == VV_OSA ? rt * VV_PIX : (rt % p.tiles_x) * VV_TX;     // OSA: the first pixel of the flattened image
-  const int H = p.h, W = p.w;
-  const size_t HW = (size_t)H * W;
-  const int steps = p.chunks * TAPS;
-  const char* const image = p.image + (size_t)tile_m * MT * steps * W_BLK + tid * 16;   // row block j: + j steps W_BLK
-
-  // halo staging role: item (k-group, halo pixel) = 8 channels of one input pixel, zero outside the image
-  int h_off[H_PASSES], h_ch[H_PASSES];
-  bool h_in[H_PASSES];
-#pragma unroll
-  for (int ps = 0; ps < H_PASSES; ++ps) {
-    const int it = tid + VV_THREADS * ps;
-    const int kgrp = it / HALO, hp = it % HALO;
-    h_ch[ps] = kgrp * 8;
-    if (MODE == VV_OSA) {
-      const size_t pix = (size_t)tx0 + hp;
-      h_in[ps] = it < H_ITEMS && pix < HW;
-      h_off[ps] = h_in[ps] ? (int)pix : 0;
-    } else {
-      const int y = ty0 * S - 1 + hp / HE_W, x = tx0 * S - 1 + hp % HE_W;
-      h_in[ps] = it < H_ITEMS && y >= 0 && y < H && x >= 0 && x < W;
-      h_off[ps] = h_in[ps] ? y * W + x : 0;
-    }
-  }
-  float hr[H_PASSES][8];
-  auto issue_halo = [&](int chunk) {
-    const float* base = p.src[0];
-    int c0 = 0, cs = p.src_ch[0];
-    if (MODE == VV_OSA) {
-#pragma unroll
-      for (int i = 1; i < VV_MAX_SRC; ++i)
-        if (i < p.n_src && chunk >= p.src_chunk0[i]) {
-          base = p.src[i];
-          c0 = p.src_chunk0[i];
-          cs = p.src_ch[i];
-        }
-    }
-    const float* const cb = base + ((size_t)img * cs + (size_t)(chunk - c0) * VV_KC) * HW;
-#pragma unroll
-    for (int ps = 0; ps < H_PASSES; ++ps)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) hr[ps][j] = h_in[ps] ? cb[(size_t)(h_ch[ps] + j) * HW + h_off[ps]] : 0.f;
-  };
-  auto park_halo = [&](int buf) {
-    char* const base = hbuf + buf * H_STAGE;
-#pragma unroll
-    for (int ps = 0; ps < H_PASSES; ++ps) {
-      const int it = tid + VV_THREADS * ps;
-      if (it < H_ITEMS) {
-        u32x4 hi, lo;
-        split8(hr[ps], hi, lo);
-        *reinterpret_cast<u32x4*>(base + it * 16) = hi;
-        *reinterpret_cast<u32x4*>(base + H_ARR + it * 16) = lo;
-      }
-    }
-  };
-  u32x4 wr[MT];
-  auto issue_w = [&](int s) {
-    const char* const src = image + (size_t)s * W_BLK;
-#pragma unroll
-    for (int j = 0; j < MT; ++j) wr[j] = *reinterpret_cast<const u32x4*>(src + (size_t)j * steps * W_BLK);
-  };
-  auto park_w = [&](int buf) {
-    char* const base = wbuf + buf * W_STAGE + tid * 16;
-#pragma unroll
-    for (int j = 0; j < MT; ++j) *reinterpret_cast<u32x4*>(base + j * W_BLK) = wr[j];
-  };
-
-  f32x16 acc[MT];
-#pragma unroll
-  for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;
-
-  // B fragments: pixel pp = 32 wave + l32 of the tile; its halo entry for tap (ky, kx) is (S py + ky) * HE_W + S px + kx
-  const int pp = 32 * wave + l32;
-  const int py = pp >> 4, px = pp & 15;
-  const int pix_hp = MODE == VV_OSA ? pp : (py * S) * HE_W + px * S;
-
-  issue_halo(0);
-  park_halo(0);
-  issue_w(0);
-  park_w(0);
-  if (steps > 1) issue_w(1);
-  __syncthreads();
-  for (int chunk = 0; chunk < p.chunks; ++chunk) {
-    const bool more = chunk + 1 < p.chunks;
-    if (more) issue_halo(chunk + 1);                         // in flight under the chunk's MFMAs, parked after its last tap
-    const char* const hb = hbuf + (G::HBUF == 2 ? (chunk & 1) : 0) * H_STAGE;
-#pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap) {
-      const int s = chunk * TAPS + tap;
-      const char* const wb = wbuf + (s & 1) * W_STAGE;
-      const int tap_off = (tap / 3) * HE_W + tap % 3;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int kgrp = 2 * ks + kg;
-        const int boff = (kgrp * HALO + pix_hp + tap_off) * 16;
-        const u32x4 bh = *reinterpret_cast<const u32x4*>(hb + boff);
-        const u32x4 bl = *reinterpret_cast<const u32x4*>(hb + H_ARR + boff);
-#pragma unroll
-        for (int mi = 0; mi < MT; ++mi) {
-          const int aoff = mi * W_BLK + (kgrp * 32 + l32) * 16;
-          const u32x4 ah = *reinterpret_cast<const u32x4*>(wb + aoff);
-          const u32x4 al = *reinterpret_cast<const u32x4*>(wb + W_ARR + aoff);
-          acc[mi] = mfma_32x32x16_x3(ah, al, bh, bl, acc[mi]);
-        }
-      }
-      if (s + 1 < steps) {
-        park_w((s + 1) & 1);                                 // its readers finished before the last barrier
-        if (s + 2 < steps) issue_w(s + 2);
-      }
-      if (tap == TAPS - 1 && more) {
-        if (G::HBUF == 1) __syncthreads();                   // one buffer: every wave is done with this chunk's patch
-        park_halo(G::HBUF == 2 ? (chunk + 1) & 1 : 0);       // two: the buffer was last read in chunk - 1
-      }
-      __syncthreads();
-    }
-  }
-
-  // C/D of 32x32x16: column (pixel) = l32, rows (channels) 4 kg + (r & 3) + 8 (r >> 2)
-  bool ok;
-  size_t off, plane;
-  if (MODE == VV_OSA) {
-    const size_t pix = (size_t)tx0 + pp;
-    ok = pix < HW;
-    off = ok ? pix : 0;
-    plane = HW;
-  } else {
-    const int y = ty0 + py, x = tx0 + px;
-    ok = y < p.ho && x < p.wo;
-    off = ok ? (size_t)y * p.wo + x : 0;
-    plane = (size_t)p.ho * p.wo;
-  }
-  const int crow0 = tile_m * ROWS;
-  float* const outp = p.out + ((size_t)img * p.cout + crow0) * plane + off;
-  float* const red = reinterpret_cast<float*>(smem);          // OSA: [4 waves][ROWS] (the main loop's last barrier is behind every wave)
-#pragma unroll
-  for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int cl = 32 * mi + 4 * kg + (r & 3) + 8 * (r >> 2);
-      const float v = fmaxf(acc[mi][r] * p.scale[crow0 + cl] + p.shift[crow0 + cl], 0.f);
-      if (ok) outp[(size_t)cl * plane] = v;
-      if (MODE == VV_OSA) {
-        const float s = half_wave_sum(ok ? v : 0.f);
-        if (l32 == 0) red[wave * ROWS + cl] = s;
-      }
-    }
-  if (MODE == VV_OSA) {
-    __syncthreads();
-    if (tid < ROWS)
-      p.partials[((size_t)img * p.tiles_img + rt) * p.cout + crow0 + tid] =
-          (red[tid] + red[ROWS + tid]) + (red[2 * ROWS + tid] + red[3 * ROWS + tid]);
-  }
-}
 
 // ---- eSE --------------------------------------------------------------------------------------------------------------------
 constexpr int VV_ESE_MAX_C = 1024;
@@ -361,42 +120,6 @@ __global__ __launch_bounds__(256) void vv_ese_apply_kernel(const float* xt, cons
   }
 }
 
-template <int MT, int MODE>
-static int vv_launch_mt(const VvParams& p, unsigned tiles, unsigned row_tiles, hipStream_t stream) {
-  constexpr int lds = vv_lds<MT, MODE>();
-  if (!allow_dynamic_lds(reinterpret_cast<const void*>(vv_gemm_kernel<MT, MODE>), lds)) return GD4D_ELAUNCH;
-  hipLaunchKernelGGL((vv_gemm_kernel<MT, MODE>), dim3(tiles, row_tiles), dim3(VV_THREADS), lds, stream, p);
-  return check_launch();
-}
-
-template <int MODE>
-static int vv_launch(const VvParams& p, long long tiles, int m_blocks, void* stream) {
-  const int mt = m_blocks ? m_blocks : vv_mt(p.cout, tiles);
-  const unsigned rows = (unsigned)(p.cout / (32 * mt)), t = (unsigned)tiles;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (mt) {
-    case 7: return vv_launch_mt<7, MODE>(p, t, rows, st);
-    case 5: return vv_launch_mt<5, MODE>(p, t, rows, st);
-    case 4: return vv_launch_mt<4, MODE>(p, t, rows, st);
-    case 3: return vv_launch_mt<3, MODE>(p, t, rows, st);
-    case 2: return vv_launch_mt<2, MODE>(p, t, rows, st);
-    default: return vv_launch_mt<1, MODE>(p, t, rows, st);
-  }
-}
-
-static bool vv_conv_channels(int cin, int cout) {
-  return cin % 32 == 0 && cin >= 32 && cin <= 1024 && cout % 32 == 0 && cout >= 32 && cout <= 256;
-}
-static bool vv_osa_channels(int k, int cout) {
-  return k % 32 == 0 && k >= 32 && k <= 2304 && cout % 32 == 0 && cout >= 32 && cout <= 1024;
-}
-
-// w (cout, cin, taps): a (row block of 32 output channels, step = chunk * taps + tap) is 4 KB; the image does not depend on the M tiling
-static int vv_image(const float* weight, int cin, int cout, int taps, void* image, void* stream) {
-  if (!aligned16(image)) return GD4D_EALIGN;
-  const ConvImage d{cin, cout, taps, 32, VV_KC, cout, 0, 0, 0};
-  return pack_conv_image(d, weight, image, static_cast<hipStream_t>(stream));
-}
 
 }  // namespace gd4d
 

@@ -40,8 +40,8 @@ def refuse_outside_limits(module, name, limits):
 
 class KernelRoute:
     """Mixin in front of nn.Module.  A module calls `_init_route` in its constructor and may override `_route_name`, `_limits`,
-    `_in_train_mode`, `_kernels` (the phrase of the two refusals) and `_kept_values`; a module with a training route has the
-    attribute `hip_train`."""
+    `_in_train_mode`, `_kernels` (the phrase of the two refusals), `_kept_values` and the two hooks of a training route; a module with a
+    training route has the attribute `hip_train`."""
     torch_ops = False
     _kernels = 'kernels have no backward'          # "graph-detr4d_amd's <_kernels>", in the train-mode and autograd refusals
 
@@ -65,6 +65,13 @@ class KernelRoute:
         """Fetches every kept value a captured forward reads (each through `_keep`)."""
         raise NotImplementedError
 
+    def _has_train_route(self):
+        """Whether the refusals may name `hip_train=True`: a module with a training route sets the attribute in __init__."""
+        return 'hip_train' in self.__dict__
+
+    def _refuse_train_route(self):
+        """Called where the rule is about to answer 'train': raises Gd4dError for what the module's training route does not take."""
+
     # ---- the rule ------------------------------------------------------------------------------------------------------------
     def _route(self, *inputs):
         """'torch', 'train' or 'infer' for a call on these tensor inputs, or Gd4dError: the module docstring's rule."""
@@ -73,10 +80,11 @@ class KernelRoute:
         limits = self._limits(*inputs)
         if limits:                                              # (the name is made only where something is refused)
             refuse_outside_limits(self, self._route_name(), limits)
-        switch = 'hip_train' in self.__dict__                   # (a module with a training route sets it in __init__)
+        switch = self._has_train_route()
         route = 'infer'
         if switch and self.hip_train:
             if self._in_train_mode() or Fn.wants_grad(self, *inputs):
+                self._refuse_train_route()
                 route = 'train'
         elif self._in_train_mode():
             raise _lib.Gd4dError(f'{self._route_name()} in train() mode: graph-detr4d_amd\'s {self._kernels}.  `torch_ops=True` (or '

@@ -3332,6 +3332,168 @@ def ese_apply(xt, gate, identity=None, out=None):
     return out
 
 
+# ---- VoVNet, training behind frozen BatchNorms (gd4d_vovnet_train.hip) ----------------------------------------------------------
+def conv3x3_image_t(weight, scale=None):
+    """gd4d_conv3x3_image_t: the image conv3x3_dgrad reads, of the (Cout, Cin, 3, 3) fp32 weight times scale[co] (the folded BatchNorm's;
+    None: the weight as it is) - transposed, taps flipped.  Limits as conv3x3_image.  Remake it when the weight or the scale changes."""
+    if scale is not None:
+        weight = weight * scale.view(-1, 1, 1, 1)
+    return _conv3x3_weight_image('conv3x3_image_t', 'gd4d_conv3x3_image_t', weight, 'the kernel takes',
+                                 'Cin a multiple of 32 in [32, 1024] and Cout a multiple of 32 in [32, 256]')
+
+
+def osa_concat_image_t(weight, scale=None):
+    """gd4d_osa_concat_image_t: the image osa_concat_dgrad reads, of the aggregation's (Cout, K[, 1, 1]) weight times scale[co],
+    transposed.  Limits as osa_concat_image."""
+    if weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1):
+        weight = weight.reshape(weight.shape[0], weight.shape[1])
+    if weight.dim() != 2:
+        raise _lib.Gd4dError(f'osa_concat_image_t: weight {tuple(weight.shape)}; the kernel takes (Cout, K) or (Cout, K, 1, 1)')
+    cout, k = int(weight.shape[0]), int(weight.shape[1])
+    if scale is not None:
+        weight = weight * scale.view(-1, 1)
+    return _weight_image('gd4d_osa_concat_image_t', int(_lib.load().gd4d_osa_concat_image_t_bytes(k, cout)),
+                         f'osa_concat_image_t: weight {tuple(weight.shape)}; the kernel takes K a multiple of 32 in [32, 2304] and Cout '
+                         'a multiple of 32 in [32, 1024]', weight, k, cout)
+
+
+def conv3x3_dgrad(dz, image_t, cin, add=None, mask=None, add2=None, out=None, m_blocks=0):
+    """gd4d_conv3x3_dgrad: dz (N, Cout, H, W) fp32 -> (conv3x3^T(dz) (+ add)) ([mask > 0]) (+ add2), (N, cin, H, W): the stride-1
+    convolution's input gradient with image_t = conv3x3_image_t(weight, scale); add / mask / add2 optional maps of the result's shape
+    (out may be add or add2).  m_blocks: as conv3x3_bn_relu's, dividing cin / 32; the same bits either way."""
+    lib = _lib.load()
+    n, cout, h, w = _dcn_x(dz, 'conv3x3_dgrad')
+    cin = int(cin)
+    nbytes = int(lib.gd4d_conv3x3_image_t_bytes(cin, cout))
+    if nbytes == 0 or nbytes != image_t.numel():
+        raise _lib.Gd4dError(f'conv3x3_dgrad: the image is not conv3x3_image_t of a ({cout}, {cin}, 3, 3) weight the kernel takes '
+                             '(Cin a multiple of 32 in [32, 1024], Cout a multiple of 32 in [32, 256])')
+    for t, name in ((add, 'add'), (mask, 'mask'), (add2, 'add2')):
+        if t is not None and tuple(t.shape) != (n, cin, h, w):
+            raise ValueError(f'conv3x3_dgrad: {name} must be ({n}, {cin}, {h}, {w})')
+    out = _out(out, (n, cin, h, w), dz.device, 'conv3x3_dgrad: out')
+    _call('gd4d_conv3x3_dgrad', _dev(dz, 'dz', F32), n, cin, cout, h, w, _dev(image_t, 'image_t', U8), _opt(add, 'add'), _opt(mask, 'mask'),
+          _opt(add2, 'add2'), _dev(out, 'out', F32), int(m_blocks))
+    return out
+
+
+def osa_concat_dgrad(dz, image_t, channels, mask_last=None, outs=None, m_blocks=0):
+    """gd4d_osa_concat_dgrad: dz (N, Cout, H, W) fp32 -> one map (N, channels[i], H, W) per source of the aggregation, the rows of source
+    i of W^T dz with image_t = osa_concat_image_t(weight, scale); the concatenation's gradient is never written.  mask_last: the last
+    map is zeroed where mask_last <= 0.  A forced m_blocks must divide every channels[i] / 32."""
+    lib = _lib.load()
+    n, cout, h, w = _dcn_x(dz, 'osa_concat_dgrad')
+    chans = [int(c) for c in channels]
+    if not 1 <= len(chans) <= OSA_MAX_SOURCES:
+        raise _lib.Gd4dError(f'osa_concat_dgrad: {len(chans)} destinations; the kernel takes 1 to {OSA_MAX_SOURCES}')
+    nbytes = int(lib.gd4d_osa_concat_image_t_bytes(sum(chans), cout))
+    if nbytes == 0 or nbytes != image_t.numel() or any(c % 32 or c <= 0 for c in chans):
+        raise _lib.Gd4dError(f'osa_concat_dgrad: {cout} -> maps of {chans} channels: the kernel takes multiples of 32, K up to 2304 and '
+                             'Cout up to 1024, with image_t = osa_concat_image_t of the (Cout, K) weight')
+    if mask_last is not None and tuple(mask_last.shape) != (n, chans[-1], h, w):
+        raise ValueError(f'osa_concat_dgrad: mask_last must be ({n}, {chans[-1]}, {h}, {w})')
+    if outs is None:
+        outs = [torch.empty(n, c, h, w, device=dz.device, dtype=F32) for c in chans]
+    elif [tuple(o.shape) for o in outs] != [(n, c, h, w) for c in chans]:
+        raise ValueError('osa_concat_dgrad: outs must be one (N, channels[i], H, W) map per destination')
+    _call('gd4d_osa_concat_dgrad', _dev(dz, 'dz', F32), n, cout, h, w, _dev(image_t, 'image_t', U8), _ptrs(outs, 'outs'),
+          (ctypes.c_int32 * len(chans))(*chans), len(chans), _opt(mask_last, 'mask_last'), int(m_blocks))
+    return list(outs)
+
+
+def _vv_partitions(dev, tiles, chunks, partitions):
+    """About two workgroups per compute unit, at most one partition per tile."""
+    if dev.type != 'cuda':
+        raise _lib.Gd4dError('the maps must live on the GPU (no CPU fallback in graph-detr4d_amd)')
+    if partitions is None:
+        partitions = max(1, min(tiles, 2 * torch.cuda.get_device_properties(dev).multi_processor_count // max(1, chunks), 4096))
+    return int(partitions)
+
+
+def _vv_wgrad_outputs(name, lib, weight, bn, cin, cout, taps, partitions, want):
+    if tuple(bn.shape) != (3, cout):
+        raise ValueError(f'{name}: bn must be (3, {cout}): scale, rstd, mean')
+    if weight.numel() != cout * cin * taps or int(weight.shape[0]) != cout:
+        raise ValueError(f'{name}: weight of {cout} x {cin} x {taps} values expected, got {tuple(weight.shape)}')
+    if not any(want):
+        raise ValueError(f'{name}: nothing asked for')
+    nbytes = int(lib.gd4d_conv_wgrad_workspace_bytes(cin, cout, taps, partitions))
+    if nbytes == 0:
+        raise _lib.Gd4dError(f'{name}: {cin} -> {cout} channels, partitions = {partitions}: the kernel takes multiples of 32 within the '
+                             'forward\'s limits and 1..4096 partitions')
+    dev = weight.device
+    ws = torch.empty(nbytes // 4, device=dev, dtype=F32)
+    dw = torch.empty(weight.shape, device=dev, dtype=F32) if want[0] else None
+    dgamma = torch.empty(cout, device=dev, dtype=F32) if want[1] else None
+    dbeta = torch.empty(cout, device=dev, dtype=F32) if want[2] else None
+    return ws, dw, dgamma, dbeta
+
+
+def conv3x3_wgrad(dz, x, weight, bn, want=(True, True, True), partitions=None):
+    """gd4d_conv3x3_wgrad: the parameter gradients of relu(BN(conv3x3(x))) behind a frozen BatchNorm from dz (N, Cout, H, W), the
+    gradient of the BatchNorm's output after the ReLU mask, and the convolution's input x (N, Cin, H, W): (dW (Cout, Cin, 3, 3), dgamma,
+    dbeta), None where `want` says so.  weight: the unscaled fp32 weight; bn (3, Cout): scale = gamma rstd, rstd, mean."""
+    lib = _lib.load()
+    n, cout, h, w = _dcn_x(dz, 'conv3x3_wgrad')
+    if x.dim() != 4 or (int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) != (n, h, w):
+        raise ValueError(f'conv3x3_wgrad: x {tuple(x.shape)} for dz {tuple(dz.shape)}')
+    cin = int(x.shape[1])
+    partitions = _vv_partitions(dz.device, int(lib.gd4d_conv3x3_wgrad_tiles(n, h, w)), cin // 32, partitions)
+    ws, dw, dgamma, dbeta = _vv_wgrad_outputs('conv3x3_wgrad', lib, weight, bn, cin, cout, 9, partitions, want)
+    _call('gd4d_conv3x3_wgrad', _dev(dz, 'dz', F32), _dev(x, 'x', F32), n, cin, cout, h, w, partitions, _dev(ws, 'workspace', F32),
+          _dev(weight, 'weight', F32), _dev(bn, 'bn', F32), _opt(dw, 'dw'), _opt(dgamma, 'dgamma'), _opt(dbeta, 'dbeta'))
+    return dw, dgamma, dbeta
+
+
+def osa_concat_wgrad(dz, dz_sums, sources, weight, bn, want=(True, True, True), partitions=None):
+    """gd4d_osa_concat_wgrad: conv3x3_wgrad's counterpart for the aggregation: sources are the L + 1 maps where they lie, dz_sums
+    (N, Cout) dz's plane sums (ese_bwd's second result), weight (Cout, K[, 1, 1]).  Returns (dW of weight's shape, dgamma, dbeta)."""
+    lib = _lib.load()
+    n, cout, h, w = _dcn_x(dz, 'osa_concat_wgrad')
+    sources = list(sources)
+    if not 1 <= len(sources) <= OSA_MAX_SOURCES:
+        raise _lib.Gd4dError(f'osa_concat_wgrad: {len(sources)} sources; the kernel takes 1 to {OSA_MAX_SOURCES}')
+    for s in sources:
+        if s.dim() != 4 or (int(s.shape[0]), int(s.shape[2]), int(s.shape[3])) != (n, h, w):
+            raise ValueError(f'osa_concat_wgrad: every source must be ({n}, C_i, {h}, {w}), got {tuple(s.shape)}')
+    if tuple(dz_sums.shape) != (n, cout):
+        raise ValueError(f'osa_concat_wgrad: dz_sums must be ({n}, {cout})')
+    chans = [int(s.shape[1]) for s in sources]
+    k = sum(chans)
+    if any(c % 32 for c in chans):
+        raise _lib.Gd4dError(f'osa_concat_wgrad: sources of {chans} channels; the kernel takes multiples of 32')
+    partitions = _vv_partitions(dz.device, int(lib.gd4d_osa_concat_wgrad_tiles(n, h, w)), ((k + 63) // 64) * ((cout + 255) // 256), partitions)
+    ws, dw, dgamma, dbeta = _vv_wgrad_outputs('osa_concat_wgrad', lib, weight, bn, k, cout, 1, partitions, want)
+    _call('gd4d_osa_concat_wgrad', _dev(dz, 'dz', F32), _dev(dz_sums, 'dz_sums', F32), _ptrs(sources, 'sources'),
+          (ctypes.c_int32 * len(chans))(*chans), len(chans), n, h, w, cout, partitions, _dev(ws, 'workspace', F32),
+          _dev(weight, 'weight', F32), _dev(bn, 'bn', F32), _opt(dw, 'dw'), _opt(dgamma, 'dgamma'), _opt(dbeta, 'dbeta'))
+    return dw, dgamma, dbeta
+
+
+def ese_bwd(dout, xt, partials, gate, fc_weight, want_fc=(True, True)):
+    """gd4d_ese_bwd: the backward of out = xt * gate (+ identity) with gate = ese_gate(partials, ...), up to the aggregation's BatchNorm
+    output: returns (dz (N, C, H, W) = (dout gate + fc_w^T dv / HW) [xt > 0], its plane sums (N, C), dfc_w, dfc_b), where dv =
+    (sum_hw dout xt) / 6 for 0 < gate < 1 and 0 at and beyond the clamp's corners; dfc_w / dfc_b are None where want_fc says so."""
+    lib = _lib.load()
+    n, c, h, w = _dcn_x(xt, 'ese_bwd')
+    if dout.shape != xt.shape or tuple(gate.shape) != (n, c) or partials.dim() != 3 or (int(partials.shape[0]), int(partials.shape[2])) != (n, c):
+        raise ValueError(f'ese_bwd: dout of xt\'s shape {tuple(xt.shape)}, gate ({n}, {c}) and partials ({n}, tiles, {c}) expected')
+    if fc_weight.numel() != c * c or tuple(fc_weight.shape[:2]) != (c, c):
+        raise ValueError(f'ese_bwd: fc_weight ({c}, {c}[, 1, 1]) expected')
+    nbytes = int(lib.gd4d_ese_bwd_workspace_bytes(n, c))
+    if nbytes == 0:
+        raise _lib.Gd4dError(f'ese_bwd: C = {c}; the kernel takes a multiple of 32 in [32, 1024]')
+    dev = xt.device
+    ws = torch.empty(nbytes // 4, device=dev, dtype=F32)
+    dz, sums = torch.empty_like(xt), torch.empty(n, c, device=dev, dtype=F32)
+    dfc_w = torch.empty(fc_weight.shape, device=dev, dtype=F32) if want_fc[0] else None
+    dfc_b = torch.empty(c, device=dev, dtype=F32) if want_fc[1] else None
+    _call('gd4d_ese_bwd', _dev(dout, 'dout', F32), _dev(xt, 'xt', F32), _dev(partials, 'partials', F32), int(partials.shape[1]),
+          _dev(gate, 'gate', F32), _dev(fc_weight, 'fc_weight', F32), n, c, h * w, _dev(ws, 'workspace', F32), _dev(dz, 'dz', F32),
+          _dev(sums, 'dz_sums', F32), _opt(dfc_w, 'dfc_w'), _opt(dfc_b, 'dfc_b'))
+    return dz, sums, dfc_w, dfc_b
+
+
 def _first_tensor(args):
     for a in args:
         if torch.is_tensor(a):

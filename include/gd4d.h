@@ -1627,6 +1627,49 @@ int gd4d_ese_gate_fwd(const float* partials, int n, int tiles, int channels, int
                       void* stream);
 int gd4d_ese_apply_fwd(const float* xt, const float* gate, const float* identity, int n, int channels, int hw, float* out, void* stream);
 
+/* VoVNet, training of one OSA module behind frozen BatchNorms (gd4d_vovnet_train.hip has the arithmetic; additive exports, the ABI version
+ * stays).  Maps contiguous NCHW fp32; split-bf16 x 3 products, fp32 sums in a fixed order, no atomics: two runs give the same bits.  dz is
+ * always the gradient of a BatchNorm's OUTPUT after the ReLU mask (unscaled); bn is (3, cout) fp32: scale = gamma rstd, rstd, mean.
+ * gd4d_conv3x3_image_t / gd4d_osa_concat_image_t - the image of the data gradient's GEMM: the weight read transposed (M = the forward's
+ *   input channels, K = its output channels), the 3x3 taps flipped.  Pass the weight ALREADY times scale[co]; sizes and limits as the
+ *   forward images'.
+ * gd4d_conv3x3_dgrad - dx (N, cin, h, w) = (conv3x3^T(dz (N, cout, h, w)) (+ add)) ([mask > 0]) (+ add2); add, mask, add2 optional maps of
+ *   dx's shape; add and add2 may be dx.  m_blocks as the forward's, dividing cin / 32.
+ * gd4d_osa_concat_dgrad - dst[i] (N, dst_channels[i], h, w) = the rows of source i of W^T dz (N, cout, h, w), 1 <= n_dst <= 6, one launch
+ *   per destination; mask_last (optional, the last destination's shape): the last destination is zeroed where mask_last <= 0.  A forced
+ *   m_blocks must divide every dst_channels[i] / 32.
+ * gd4d_conv3x3_wgrad - G[co, ci, tap] = sum over images and pixels of dz[co, p] x[ci, p + tap]; dw = scale (x) G, dbeta[co] = sum dz,
+ *   dgamma[co] = rstd[co] (<weight[co], G[co]> - mean[co] dbeta[co]); each of dw, dgamma, dbeta may be NULL, not all three.  weight is the
+ *   UNSCALED (cout, cin, 3, 3).  partitions (1 .. 4096) of the gd4d_conv3x3_wgrad_tiles(n, h, w) 16 x 16 tiles; workspace
+ *   gd4d_conv_wgrad_workspace_bytes(cin, cout, 9, partitions) bytes, 16-B aligned.
+ * gd4d_osa_concat_wgrad - the same for the aggregation's (cout, K) weight with x the n_src maps where they lie; dz_sums (N, cout): dz's
+ *   plane sums (gd4d_ese_bwd leaves them).  Tiles of 64 pixels (gd4d_osa_concat_wgrad_tiles); workspace
+ *   gd4d_conv_wgrad_workspace_bytes(K, cout, 1, partitions).
+ * gd4d_ese_bwd - from dout, xt (N, channels, hw), the forward's pool partials (N, tiles, channels) and gate (N, channels): dz = (dout gate +
+ *   dm / hw) [xt > 0] with dm = fc_w^T dv, dv = (sum_hw dout xt) / 6 where 0 < gate < 1, else 0; dz_sums (N, channels) its plane sums; dfc_w
+ *   (channels, channels) = sum_n dv (x) mean, dfc_b = sum_n dv (each may be NULL).  workspace gd4d_ese_bwd_workspace_bytes(n, channels).
+ * Errors as the forward's: NULL required pointer GD4D_EINVAL; sizes outside the limits, partitions outside 1 .. 4096 GD4D_EUNSUPPORTED
+ *   (0 bytes / 0 tiles from the size queries); a misaligned image or workspace GD4D_EALIGN. */
+size_t gd4d_conv3x3_image_t_bytes(int cin, int cout);
+int gd4d_conv3x3_image_t(const float* weight, int cin, int cout, void* image, void* stream);
+size_t gd4d_osa_concat_image_t_bytes(int k, int cout);
+int gd4d_osa_concat_image_t(const float* weight, int k, int cout, void* image, void* stream);
+int gd4d_conv3x3_dgrad(const float* dz, int n, int cin, int cout, int h, int w, const void* image_t, const float* add, const float* mask,
+                       const float* add2, float* dx, int m_blocks, void* stream);
+int gd4d_osa_concat_dgrad(const float* dz, int n, int cout, int h, int w, const void* image_t, float* const* dst,
+                          const int32_t* dst_channels, int n_dst, const float* mask_last, int m_blocks, void* stream);
+long long gd4d_conv3x3_wgrad_tiles(int n, int h, int w);
+long long gd4d_osa_concat_wgrad_tiles(int n, int h, int w);
+size_t gd4d_conv_wgrad_workspace_bytes(int cin, int cout, int taps, int partitions);
+int gd4d_conv3x3_wgrad(const float* dz, const float* x, int n, int cin, int cout, int h, int w, int partitions, float* workspace,
+                       const float* weight, const float* bn, float* dw, float* dgamma, float* dbeta, void* stream);
+int gd4d_osa_concat_wgrad(const float* dz, const float* dz_sums, const float* const* src, const int32_t* src_channels, int n_src, int n,
+                          int h, int w, int cout, int partitions, float* workspace, const float* weight, const float* bn, float* dw,
+                          float* dgamma, float* dbeta, void* stream);
+size_t gd4d_ese_bwd_workspace_bytes(int n, int channels);
+int gd4d_ese_bwd(const float* dout, const float* xt, const float* partials, int tiles, const float* gate, const float* fc_w, int n,
+                 int channels, int hw, float* workspace, float* dz, float* dz_sums, float* dfc_w, float* dfc_b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

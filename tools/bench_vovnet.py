@@ -4,6 +4,7 @@ torch-op route (the reference's op sequence on MIOpen's fp32 convolutions) on th
 2-5) and for the whole forward, at 6 and at 24 cameras of 3 x 320 x 800.  Prints ONE JSON line.
 
     python tools/bench_vovnet.py [--cams 6,24] [--hw 320 800] [--reps 7] [--window-ms 200] [--hip-only]
+    python tools/bench_vovnet.py --train [--cams 6] ...     one training step (forward + backward) instead, see bench_train
 
 Timing: each piece runs on the input the kernel route hands it (computed once).  After a warm-up of both routes on every shape, a WINDOW
 is k consecutive calls between two device events, k chosen from the warm-up so that a window lasts at least --window-ms; the two routes'
@@ -150,6 +151,52 @@ def bench(net, cams, hw, reps, window_ms, routes=('hip', 'torch'), dev='cuda', c
     return out
 
 
+def bench_train(net, cams, hw, reps, window_ms, dev='cuda'):
+    """Forward + backward of the backbone as every config trains it (train() mode, norm_eval=True, every parameter trained, the images
+    need no gradient) with a fixed cotangent per output: hip_train=True beside the torch-op route, each with with_cp on and off - four
+    cases whose windows alternate in one process.  Per case the median ms per step and the peak allocated memory of one step above what
+    is allocated between steps; `stem_*`: the stem's step alone (under hip_train it runs its own torch layers: what leaving it there
+    costs)."""
+    from graph_detr4d_amd import vovnet
+    net.train()
+    x = torch.randn(cams, 3, *hw, device=dev, generator=torch.Generator(dev).manual_seed(cams))
+    osa = [m for m in net.modules() if isinstance(m, vovnet._OSA_module)]
+    with torch.no_grad():
+        couts = [torch.randn(o.shape, device=dev, generator=torch.Generator(dev).manual_seed(i)) for i, o in enumerate(net(x))]
+
+    def step(route, with_cp, module=net, inp=x, cot=couts):
+        def f():
+            net.torch_ops, net.hip_train = route == 'torch', route == 'hip'
+            for m in osa:
+                m.with_cp = with_cp
+            module.zero_grad(set_to_none=True)
+            out = module(inp)
+            torch.autograd.backward(out, cot)
+        return f
+    cases = {f'{r}_cp{int(c)}': step(r, c) for r in ('hip', 'torch') for c in (True, False)}
+    out = {'cams': cams, 'hw': list(hw), 'mode': 'train'}
+    for k, (ms, calls, spread) in windows(cases, reps, window_ms).items():
+        out[f'{k}_ms'], out[f'{k}_calls_per_window'], out[f'{k}_spread'] = ms, calls, spread
+    for k, f in cases.items():
+        f()
+        net.zero_grad(set_to_none=True)
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        f()
+        torch.cuda.synchronize()
+        out[f'{k}_peak_mb'] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+    with torch.no_grad():
+        y = net.stem(x)
+    gy = torch.randn(y.shape, device=dev, generator=torch.Generator(dev).manual_seed(99))
+    stem = {f'stem_{r}': step(r, True, net.stem, x, [gy]) for r in ('hip', 'torch')}
+    for k, (ms, calls, spread) in windows(stem, reps, window_ms).items():
+        out[f'{k}_ms'], out[f'{k}_spread'] = ms, spread
+    out['stem_share_of_hip_cp1'] = out['stem_hip_ms'] / out['hip_cp1_ms']
+    out['hip_over_torch_cp1'], out['hip_over_torch_cp0'] = out['hip_cp1_ms'] / out['torch_cp1_ms'], out['hip_cp0_ms'] / out['torch_cp0_ms']
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--cams', default='6,24')
@@ -157,11 +204,16 @@ def main():
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--window-ms', type=float, default=200.0)
     ap.add_argument('--hip-only', action='store_true')
+    ap.add_argument('--train', action='store_true', help='time one training step: hip_train=True beside the torch-op route, with_cp on and off')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_vovnet.py needs a GPU: a CPU timing says nothing about the kernels')
     net = make_net(0, 'cuda')
     routes = ('hip',) if args.hip_only else ('hip', 'torch')
+    if args.train:
+        print(json.dumps({'device': torch.cuda.get_device_name(0), 'spec': 'V-99-eSE', 'reps': args.reps, 'window_ms': args.window_ms,
+                          'runs': [bench_train(net, int(c), tuple(args.hw), args.reps, args.window_ms) for c in args.cams.split(',')]}))
+        return
     res = {'device': torch.cuda.get_device_name(0), 'spec': 'V-99-eSE', 'reps': args.reps, 'window_ms': args.window_ms,
            'runs': [bench(net, int(c), tuple(args.hw), args.reps, args.window_ms, routes) for c in args.cams.split(',')]}
     print(json.dumps(res))
