@@ -62,6 +62,12 @@ __device__ __forceinline__ f32x16 mfma_32x32x16_x3(const u32x4& ah, const u32x4&
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(ah), frag(bh), acc, 0, 0, 0);
   return acc;
 }
+// C/D of 32x32x16: a lane holds column lane & 31 and, with kg = lane >> 5, accumulator register r (0 .. 15) is row
+// 4 kg + (r & 3) + 8 (r >> 2) of the tile.  row0 = the tile's first row: added first, so that the register's constant stays the last
+// term of the sum and folds into the store's address as when the sum is written out (added to a finished row it costs an
+// instruction per store, and registers in dcn_bwd_data_kernel).
+__host__ __device__ __forceinline__ constexpr int mfma32_row(int kg, int r, int row0 = 0) { return row0 + 4 * kg + (r & 3) + 8 * (r >> 2); }
+
 __device__ __forceinline__ f32x4 mfma_16x16x32_x3(const u32x4& ah, const u32x4& al, const u32x4& bh, const u32x4& bl,
                                                  f32x4 acc) {
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(al), frag(bh), acc, 0, 0, 0);

@@ -1,5 +1,8 @@
 // What the convolution families on the bf16 MFMA (gd4d_depth_net, gd4d_fpn, gd4d_vovnet, gd4d_dcn and their training halves) share
-// that is not kernel-specific: the weight image's format and its one packer, and the in-order sum of a weight gradient's partitions.
+// that is not kernel-specific: the weight image's format and its one packer, and what the partitioned weight gradients have in
+// common - the bound on the partition count (CONV_MAX_PARTITIONS, partitions_ok), a partition's share of the tile list
+// (partition_range), the in-order sum of the partitions (sum_partitions) - and the workgroup's fixed-order sum (block_sum_256).
+// gd4d_conv_wgrad.h holds the two weight-gradient GEMM bodies, gd4d_bf16x3.h the MFMA's C/D row (mfma32_row).
 //
 // The weight image.  Every one of these GEMMs reads its weight as the MFMA's A operand from a split-bf16 image made of 16-byte items:
 // 8 consecutive K values of one output row, in the hi plane or the lo plane (gd4d_bf16x3.h: hi = bf16(x), lo = bf16(x - hi)), ordered
@@ -46,5 +49,29 @@ int pack_conv_image(const ConvImage& d, const float* w, void* image, hipStream_t
 // dw[i] (i < total) = sum over q of ws[q * total + i] and db[i] (i < nb) = sum over q of ws_b[q * nb + i], q = 0 .. partitions - 1 in
 // order: the second launch of the partitioned weight gradients.  check_launch()'s code (of this launch and those before it).
 int sum_partitions(const float* ws, const float* ws_b, int partitions, int total, int nb, float* dw, float* db, hipStream_t stream);
+
+// The partition count every partitioned weight gradient accepts (its workspace has one slab per partition).
+constexpr int CONV_MAX_PARTITIONS = 4096;
+inline bool partitions_ok(int partitions) { return partitions >= 1 && partitions <= CONV_MAX_PARTITIONS; }
+
+// The tiles [t_begin, t_end) of partition `part` of a list of `tiles` cut into `partitions` (empty when there are fewer tiles).
+__device__ __forceinline__ void partition_range(int part, int tiles, int partitions, int& t_begin, int& t_end) {
+  t_begin = (int)((long long)part * tiles / partitions);
+  t_end = (int)((long long)(part + 1) * tiles / partitions);
+}
+
+// sum over the workgroup's 256 threads in a fixed order: a tree over LDS (red: 256 floats); the result in every thread
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  return red[0];
+}
 
 }  // namespace gd4d

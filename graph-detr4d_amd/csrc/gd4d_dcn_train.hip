@@ -51,7 +51,6 @@ namespace gd4d {
 
 constexpr int DT_THREADS = 512, DT_WAVES = 8, DT_ROWS = 32;      // data kernel: 8 waves, items of 32 (tap, ci) rows
 constexpr int DW_THREADS = 256, DW_PX = 64, DW_NC = 32;          // weight gradients: 64-pixel tiles, 32 input channels per item
-constexpr int DCN_MAX_PARTITIONS = 4096;
 
 // g of one element: dout, masked by the forward's ReLU (y > 0) and scaled by the folded BatchNorm
 __device__ __forceinline__ float dcn_g(const float* __restrict__ dout, const float* __restrict__ y, size_t i, float scale) {
@@ -160,7 +159,7 @@ __global__ __launch_bounds__(DT_THREADS) void dcn_bwd_data_kernel(const DcnBwdDa
       float s_mod = 0.f, s_dy = 0.f, s_dx = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ci = chunk * DT_ROWS + 4 * kg + (r & 3) + 8 * (r >> 2);
+        const int ci = mfma32_row(kg, r, chunk * DT_ROWS);
         const char* const xp = reinterpret_cast<const char*>(xin + (size_t)ci * HW);
         float v[4];
 #pragma unroll
@@ -221,7 +220,8 @@ __global__ __launch_bounds__(DW_THREADS) void dcn_wgrad_kernel(const DcnWgradPar
   const int item = blockIdx.x % items, part = blockIdx.x / items;
   const int tap = item / p.chunks, chunk = item - tap * p.chunks;
   const int ky = tap / 3, kx = tap - 3 * ky;
-  const int t_begin = (int)((long long)part * p.tiles / p.partitions), t_end = (int)((long long)(part + 1) * p.tiles / p.partitions);
+  int t_begin, t_end;
+  partition_range(part, p.tiles, p.partitions, t_begin, t_end);
   const int H = p.h, W = p.w;
   const size_t HW = (size_t)H * W;
   const int HWo = p.ho * p.wo;
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(DW_THREADS) void dcn_wgrad_kernel(const DcnWgradPar
     }
   }
 
-  // C/D of 32x32x16: column (input channel) = l32, rows (output channels) 4 kg + (r & 3) + 8 (r >> 2)
+  // column (input channel) = l32, rows (output channels) by mfma32_row
   float* const ws = p.ws + (size_t)part * p.cout * p.cin * DCN_TAPS;
   const int ci = chunk * DW_NC + l32;
 #pragma unroll
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(DW_THREADS) void dcn_wgrad_kernel(const DcnWgradPar
     if (32 * (wave + 4 * i) >= p.cout) continue;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = 32 * (wave + 4 * i) + 4 * kg + (r & 3) + 8 * (r >> 2);
+      const int co = mfma32_row(kg, r, 32 * (wave + 4 * i));
       ws[((size_t)co * p.cin + ci) * DCN_TAPS + tap] = acc[i][r];
     }
     if (item == 0) {
@@ -364,7 +364,8 @@ __global__ __launch_bounds__(64) void dcn_offset_wgrad_kernel(const DcnOffsetWgr
   const int item = blockIdx.x % items, part = blockIdx.x / items;
   const int tap = item / p.chunks, chunk = item - tap * p.chunks;
   const int ky = tap / 3, kx = tap - 3 * ky;
-  const int t_begin = (int)((long long)part * p.tiles / p.partitions), t_end = (int)((long long)(part + 1) * p.tiles / p.partitions);
+  int t_begin, t_end;
+  partition_range(part, p.tiles, p.partitions, t_begin, t_end);
   const size_t HW = (size_t)p.h * p.w;
   const int HWo = p.ho * p.wo;
   const int ci = chunk * DW_NC + l32;
@@ -402,7 +403,7 @@ __global__ __launch_bounds__(64) void dcn_offset_wgrad_kernel(const DcnOffsetWgr
   float* const ws = p.ws + (size_t)part * DCN_OFF_C * p.cin * DCN_TAPS;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int j = 4 * kg + (r & 3) + 8 * (r >> 2);
+    const int j = mfma32_row(kg, r);
     if (j < DCN_OFF_C) ws[((size_t)j * p.cin + ci) * DCN_TAPS + tap] = acc[r];
   }
   if (item == 0) {
@@ -410,8 +411,6 @@ __global__ __launch_bounds__(64) void dcn_offset_wgrad_kernel(const DcnOffsetWgr
     if (kg == 0 && l32 < DCN_OFF_C) p.ws_b[(size_t)part * DCN_OFF_C + l32] = bsum + other;
   }
 }
-
-static bool dcn_partitions_ok(int partitions) { return partitions >= 1 && partitions <= DCN_MAX_PARTITIONS; }
 
 template <int NI>
 static int dcn_bwd_data_launch(DcnBwdDataParams& p, int n, void* stream) {
@@ -466,7 +465,7 @@ extern "C" long long gd4d_dcn_wgrad_tiles(int n, int h, int w, int stride) {
 extern "C" size_t gd4d_dcn_wgrad_workspace_bytes(int cin, int cout, int partitions) {
   using namespace gd4d;
   int mpad, kc;
-  if (!dcn_cin_ok(cin) || cout == DCN_OFF_C || !dcn_geometry(cout, mpad, kc) || !dcn_partitions_ok(partitions)) return 0;
+  if (!dcn_cin_ok(cin) || cout == DCN_OFF_C || !dcn_geometry(cout, mpad, kc) || !partitions_ok(partitions)) return 0;
   return (size_t)partitions * cout * ((size_t)cin * DCN_TAPS + 1) * sizeof(float);
 }
 
@@ -476,7 +475,7 @@ extern "C" int gd4d_dcn_wgrad(const float* dout, const float* y, const float* sc
   if (!dout || !x || !offmask || !workspace || !dw || !dbias) return GD4D_EINVAL;
   int ho, wo, mpad, kc;
   if (!dcn_cin_ok(cin) || cout == DCN_OFF_C || !dcn_geometry(cout, mpad, kc) || !dcn_out_hw(n, cin, cout, h, w, stride, ho, wo) ||
-      !dcn_partitions_ok(partitions))
+      !partitions_ok(partitions))
     return GD4D_EUNSUPPORTED;
   if (!aligned16(workspace)) return GD4D_EALIGN;
   const long long tiles = gd4d_dcn_wgrad_tiles(n, h, w, stride);
@@ -504,7 +503,7 @@ extern "C" int gd4d_dcn_offset_conv_dgrad(const float* doff, const float* weight
 
 extern "C" size_t gd4d_dcn_offset_conv_wgrad_workspace_bytes(int cin, int partitions) {
   using namespace gd4d;
-  if (!dcn_cin_ok(cin) || !dcn_partitions_ok(partitions)) return 0;
+  if (!dcn_cin_ok(cin) || !partitions_ok(partitions)) return 0;
   return (size_t)partitions * DCN_OFF_C * ((size_t)cin * DCN_TAPS + 1) * sizeof(float);
 }
 
@@ -513,7 +512,7 @@ extern "C" int gd4d_dcn_offset_conv_wgrad(const float* doff, const float* x, int
   using namespace gd4d;
   if (!doff || !x || !workspace || !dw || !db) return GD4D_EINVAL;
   int ho, wo;
-  if (!dcn_cin_ok(cin) || !dcn_out_hw(n, cin, DCN_OFF_C, h, w, stride, ho, wo) || !dcn_partitions_ok(partitions)) return GD4D_EUNSUPPORTED;
+  if (!dcn_cin_ok(cin) || !dcn_out_hw(n, cin, DCN_OFF_C, h, w, stride, ho, wo) || !partitions_ok(partitions)) return GD4D_EUNSUPPORTED;
   if (!aligned16(workspace)) return GD4D_EALIGN;
   const long long tiles = gd4d_dcn_wgrad_tiles(n, h, w, stride);
   if (tiles > (1ll << 30)) return GD4D_EUNSUPPORTED;

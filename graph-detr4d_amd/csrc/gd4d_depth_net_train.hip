@@ -14,20 +14,14 @@
 //   gd4d_depth_conv_wgrad    dW[oc, ic, ky, kx] = sum over levels, cameras, pixels of dy[oc, p] x[ic, p + (ky - 1, kx - 1)]: a GEMM
 //                            256 x 2304 whose K runs over the pixels, on the split-bf16 x 3 MFMA (gd4d_bf16x3.h).
 //
-// The weight gradient.  Grid 8 (chunks of 32 input channels) x P (partitions of the (level, camera, 16 x 16 tile) list, the forward's
-// order).  A workgroup of 8 waves owns 256 output channels x 32 input channels x 9 taps: wave w the output channels 32 w .. 32 w + 31
-// and nine 32 x 32 accumulator tiles (144 registers).  The MFMA's k index is the pixel: one K-step of 16 is one row of the tile, and
-// both operands want 8 consecutive pixels of one channel per lane - NCHW as it lies.  dy is read by exactly one wave of the
-// workgroup, so it goes from global memory to registers (a row ahead), is split there and never touches LDS.  The chunk's 18 x 18
-// halo of x is shared by all waves and all taps: it is staged once per tile, split hi / lo, as THREE copies, one per kx, each
-// shifted by kx pixels ([kx][plane][32 channels][18 rows][16 pixels] bf16, rows of 32 B, channels 592 B apart): tap (ky, kx) of
-// tile row py is then the aligned 16-B read at (row py + ky, pixels 8 kg ..) of copy kx.  Zero fill outside the image makes the
-// padding and the ragged tiles exact; pixels of dy outside the image are zeros.  111 KB of LDS, one workgroup per CU.
-// Each workgroup stores its partial dW into a (P, 9, 256, 256) workspace (empty partitions: zeros); a second kernel adds the P
-// partials in order and writes the (256, 256, 3, 3) layout.  No atomics anywhere.
+// The weight gradient is conv3x3_wgrad_body (gd4d_conv_wgrad.h has the algorithm) with everything fixed at compile time: 256 / 256
+// channels, so a grid of 8 chunks x P and workgroups of 8 waves, over the (level, camera, 16 x 16 tile) list in the forward's order
+// (DepthWgradShape finds a tile's level in the table); no bias sum (gd4d_depth_bn_bwd has it).  The FPN's 3x3 convolutions train
+// through this entry point too.  depth_wgrad_sum_kernel adds the P partials of the (P, 9, 256, 256) workspace in order and writes the
+// (256, 256, 3, 3) layout.
 // Register / spill figures of the compiler's resource report: see docs/measurements_r16.md.
 #include "gd4d_common.h"
-#include "gd4d_bf16x3.h"
+#include "gd4d_conv_wgrad.h"
 
 namespace gd4d {
 
@@ -161,20 +155,6 @@ __device__ __forceinline__ T pick(T const (&v)[DT_MAX_LEVELS], int lv) {
   return r;
 }
 
-// sum over the workgroup's 256 threads in a fixed order: a tree over LDS; the result in every thread
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 __global__ __launch_bounds__(256) void depth_bn_act_kernel(const DepthPlaneParams p) {
   const PlaneAt a = plane_at(p);
   const float* st = p.stats + (size_t)a.lv * 3 * DT_C;
@@ -276,13 +256,8 @@ __global__ __launch_bounds__(DT_C) void depth_bn_bwd_bias_kernel(const float* __
 }
 
 // ---- weight gradient ------------------------------------------------------------------------------------------------------
-constexpr int WG_THREADS = 512, WG_KC = 32, WG_CHUNKS = DT_C / WG_KC, WG_HE = DT_T + 2;
-constexpr int WG_CH_STRIDE = WG_HE * 32 + 16;                 // 18 rows of 16 bf16 + 16 B: 16 lanes of a read on 16 distinct slots
-constexpr int WG_PLANE = WG_KC * WG_CH_STRIDE;                // 18 944 B
-constexpr int WG_LDS = 3 * 2 * WG_PLANE;                      // 113 664 B
-constexpr int WG_ITEMS = 3 * WG_KC * WG_HE * 2;               // (kx, channel, halo row, 8-pixel half): 3456
+constexpr int WG_THREADS = 512, WG_CHUNKS = DT_C / CW3_KC;
 constexpr int WG_DW = DT_C * DT_C * 9;
-static_assert(WG_LDS <= 160 * 1024, "LDS budget of a CU");
 
 struct DepthWgradParams {
   const float* dy[DT_MAX_LEVELS];
@@ -292,22 +267,14 @@ struct DepthWgradParams {
   float* ws;                       // (partitions, 9, 256, 256)
 };
 
-__global__ __launch_bounds__(WG_THREADS) void depth_wgrad_kernel(const DepthWgradParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int l32 = lane & 31, kg = lane >> 5;
-  const int chunk = blockIdx.x % WG_CHUNKS, part = blockIdx.x / WG_CHUNKS;
-  const int t_begin = (int)((long long)part * p.tiles / p.partitions), t_end = (int)((long long)(part + 1) * p.tiles / p.partitions);
-
-  f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-  const int oc_a = 32 * wave + l32;                          // the A operand's row of this lane
-  for (int t = t_begin; t < t_end; ++t) {
+// conv3x3_wgrad_body's policy: everything fixed at compile time, a tile looked up in the level table
+struct DepthWgradShape {
+  const DepthWgradParams& p;
+  static constexpr int cin() { return DT_C; }
+  static constexpr int cout() { return DT_C; }
+  static constexpr int chunks() { return WG_CHUNKS; }
+  static constexpr int threads() { return WG_THREADS; }
+  __device__ __forceinline__ Conv3x3Tile tile(int t, int chunk, int oc_a) const {
     int lv = 0;
 #pragma unroll
     for (int l = 1; l < DT_MAX_LEVELS; ++l)
@@ -317,71 +284,14 @@ __global__ __launch_bounds__(WG_THREADS) void depth_wgrad_kernel(const DepthWgra
     const int local = t - pick(p.start, lv);
     const int cam = local / tpc;
     const int rt = local - cam * tpc;
-    const int ty0 = (rt / tpx) * DT_T, tx0 = (rt % tpx) * DT_T;
-    const float* const xin = pick(p.x, lv) + ((size_t)cam * DT_C + chunk * WG_KC) * HW;
-    const float* const dyp = pick(p.dy, lv) + ((size_t)cam * DT_C + oc_a) * HW;
-
-    // one row of the dy tile: 8 pixels of this lane's output channel, zeros outside the image
-    auto load_dy = [&](int py, float* v) {
-      const int y = ty0 + py;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int x = tx0 + 8 * kg + j;
-        v[j] = (y < H && x < W) ? dyp[(size_t)y * W + x] : 0.f;
-      }
-    };
-    float a_next[8];
-    load_dy(0, a_next);
-
-    __syncthreads();                                         // the previous tile's readers are done
-    for (int it = tid; it < WG_ITEMS; it += WG_THREADS) {
-      const int half = it & 1, q = it >> 1;
-      const int hy = q % WG_HE, q2 = q / WG_HE;
-      const int ic = q2 % WG_KC, kx = q2 / WG_KC;
-      const int y = ty0 - 1 + hy, x0 = tx0 - 1 + kx + 8 * half;
-      const bool row_in = y >= 0 && y < H;
-      const float* src = xin + (size_t)ic * HW + (row_in ? (size_t)y * W : 0);
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int x = x0 + j;
-        v[j] = (row_in && x >= 0 && x < W) ? src[x] : 0.f;
-      }
-      u32x4 hi, lo;
-      split8(v, hi, lo);
-      char* dst = smem + (size_t)(kx * 2) * WG_PLANE + ic * WG_CH_STRIDE + hy * 32 + half * 16;
-      *reinterpret_cast<u32x4*>(dst) = hi;
-      *reinterpret_cast<u32x4*>(dst + WG_PLANE) = lo;
-    }
-    __syncthreads();
-
-    const char* const bbase = smem + l32 * WG_CH_STRIDE + kg * 16;
-#pragma unroll 1
-    for (int py = 0; py < DT_T; ++py) {
-      u32x4 ah, al;
-      split8(a_next, ah, al);
-      if (py + 1 < DT_T) load_dy(py + 1, a_next);
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          const char* b = bbase + (kx * 2) * WG_PLANE + (py + ky) * 32;
-          const u32x4 bh = *reinterpret_cast<const u32x4*>(b);
-          const u32x4 bl = *reinterpret_cast<const u32x4*>(b + WG_PLANE);
-          acc[3 * ky + kx] = mfma_32x32x16_x3(ah, al, bh, bl, acc[3 * ky + kx]);
-        }
-    }
+    return {H, W, (rt / tpx) * DT_T, (rt % tpx) * DT_T, pick(p.x, lv) + ((size_t)cam * DT_C + chunk * CW3_KC) * HW,
+            pick(p.dy, lv) + ((size_t)cam * DT_C + oc_a) * HW};
   }
+};
 
-  // C/D of 32x32x16: column (input channel) = l32, rows (output channels) 4 kg + (r & 3) + 8 (r >> 2)
-  float* const ws = p.ws + (size_t)part * WG_DW;
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int oc = 32 * wave + 4 * kg + (r & 3) + 8 * (r >> 2);
-      ws[((size_t)t * DT_C + oc) * DT_C + chunk * WG_KC + l32] = acc[t][r];
-    }
+__global__ __launch_bounds__(WG_THREADS) void depth_wgrad_kernel(const DepthWgradParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  conv3x3_wgrad_body<DepthWgradShape, false>(DepthWgradShape{p}, smem);
 }
 
 // dW (256, 256, 3, 3) = the partitions' partials added in order
@@ -500,7 +410,7 @@ extern "C" int gd4d_depth_conv_wgrad(const float* const* dy, const float* const*
                                      int partitions, float* workspace, float* dw, void* stream) {
   using namespace gd4d;
   if (!dy || !x || !level_hw || !workspace || !dw) return GD4D_EINVAL;
-  if (channels != DT_C || levels < 1 || levels > DT_MAX_LEVELS || n <= 0 || partitions < 1 || partitions > 4096) return GD4D_EUNSUPPORTED;
+  if (channels != DT_C || levels < 1 || levels > DT_MAX_LEVELS || n <= 0 || !partitions_ok(partitions)) return GD4D_EUNSUPPORTED;
   if (!aligned16(workspace)) return GD4D_EALIGN;
   DepthWgradParams p{};
   long long tiles = 0;
@@ -522,9 +432,9 @@ extern "C" int gd4d_depth_conv_wgrad(const float* const* dy, const float* const*
   p.tiles = (int)tiles;
   p.partitions = partitions;
   p.ws = workspace;
-  if (!allow_dynamic_lds(reinterpret_cast<const void*>(depth_wgrad_kernel), WG_LDS)) return GD4D_ELAUNCH;
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(depth_wgrad_kernel), CW3_LDS)) return GD4D_ELAUNCH;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(depth_wgrad_kernel, dim3((unsigned)(WG_CHUNKS * partitions)), dim3(WG_THREADS), WG_LDS, s, p);
+  hipLaunchKernelGGL(depth_wgrad_kernel, dim3((unsigned)(WG_CHUNKS * partitions)), dim3(WG_THREADS), CW3_LDS, s, p);
   hipLaunchKernelGGL(depth_wgrad_sum_kernel, dim3((WG_DW + 255) / 256), dim3(256), 0, s, workspace, partitions, dw);
   return check_launch();
 }

@@ -1,18 +1,10 @@
 // Training of the image neck (gd4d_fpn.hip holds the forward and the two input-gradient kinds of its GEMM; the 3x3 output
 // convolutions' gradients are gd4d_fpn_conv_fwd on transposed images and gd4d_depth_conv_wgrad).  With gl_i the gradient of lateral i:
 //
-//   gd4d_fpn_lateral_wgrad     dW (256, Cin) = sum over cameras and pixels of gl[oc, p] x[ic, p], db (256) = sum of gl[oc, p]: a GEMM
-//                              whose K runs over the pixels, on the split-bf16 x 3 MFMA (gd4d_bf16x3.h).  Both operands want 8
-//                              consecutive pixels of one channel per lane - NCHW as it lies.  Grid: (chunks of 64 input channels) x P
-//                              partitions of the (camera, 64-pixel tile) list.  A workgroup of 4 waves owns 256 output channels x 64
-//                              input channels (wave w: output channels 64 w .. 64 w + 63, four 32 x 32 accumulators).  gl is read by
-//                              exactly one wave of the workgroup: global memory to registers, split there.  The tile's 64 x 64 block
-//                              of x is shared by the waves: staged once, split hi / lo, in LDS ([plane][channel][8-pixel group],
-//                              channels 9 units apart); the next tile's loads are issued before the tile's MFMAs.  Pixels past the
-//                              level and channels past Cin are zeros.  Each workgroup stores its partial dW into a (P, 256, Cin)
-//                              workspace (empty partitions: zeros); the workgroups of chunk 0 also sum the gl values they read, per
-//                              output channel, into (P, 256).  A second kernel adds the P partials in order.  gl is read Cin / 64
-//                              times: at Cin = 512 that, not the MFMA, is what the kernel waits for (untuned).
+//   gd4d_fpn_lateral_wgrad     dW (256, Cin) = sum over cameras and pixels of gl[oc, p] x[ic, p], db (256) = sum of gl[oc, p]:
+//                              conv1x1_wgrad_body (gd4d_conv_wgrad.h has the algorithm) with all 256 output channels in one
+//                              workgroup (no guard), one input map, and the bias sum: a (P, 256, Cin) + (P, 256) workspace, then
+//                              sum_partitions.
 //   gd4d_fpn_topdown_bwd       the adjoint of the forward's fused nearest-upsampling add, in place on the coarser gradient: one
 //                              thread per coarse element adds its children of the finer gradient in row-major order.  The children
 //                              are found by testing candidates (an integer bracket, one pixel wider than the exact-ratio range on
@@ -26,7 +18,7 @@
 // No atomics: every sum runs in a fixed order, two runs give the same bits.
 #include "gd4d_bf16x3.h"
 #include "gd4d_common.h"
-#include "gd4d_conv_common.h"
+#include "gd4d_conv_wgrad.h"
 #include "gd4d_fpn_index.h"
 
 namespace gd4d {
@@ -35,10 +27,6 @@ constexpr int FT_C = 256;
 constexpr int FT_MAX_CIN = 2048;
 
 // ---- lateral weight / bias gradient -------------------------------------------------------------------------------------------
-constexpr int LW_THREADS = 256, LW_PX = 64, LW_IC = 64;
-constexpr int LW_PITCH = 9;                            // 16-byte units per channel of the staged block: 8 pixel groups + 1
-constexpr int LW_B_ARR = LW_IC * LW_PITCH;
-
 struct LateralWgradParams {
   const float* g;          // (N, 256, H, W)
   const float* x;          // (N, Cin, H, W)
@@ -47,96 +35,20 @@ struct LateralWgradParams {
   int cin, hw, tiles_cam, tiles, partitions, chunks;
 };
 
-__global__ __launch_bounds__(LW_THREADS) void fpn_lateral_wgrad_kernel(const LateralWgradParams p) {
-  __shared__ __attribute__((aligned(16))) u32x4 s_b[2][LW_B_ARR];          // [hi, lo][channel][pixel group (+ 1)]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, kg = lane >> 5;
-  const int chunk = blockIdx.x % p.chunks, part = blockIdx.x / p.chunks;
-  const int t_begin = (int)((long long)part * p.tiles / p.partitions), t_end = (int)((long long)(part + 1) * p.tiles / p.partitions);
-  const size_t HW = (size_t)p.hw;
+// conv1x1_wgrad_body's policy: all 256 output channels in one workgroup, K = the channels of the one input map
+struct LateralWgradShape {
+  const LateralWgradParams& p;
+  const Conv1x1Wgrad g;
+  static constexpr bool GUARD = false;
+  static constexpr int cout() { return FT_C; }
+  __device__ __forceinline__ int oc0(int wave) const { return 64 * wave; }
+  __device__ __forceinline__ Conv1x1Source source(int icg, bool ok) const { return {p.x, p.cin, ok ? icg : 0}; }
+};
 
-  // staging role: thread = (channel of the chunk, 16 consecutive pixels of the tile)
-  const int s_ic = tid >> 2, s_q = tid & 3;
-  const int s_icg = chunk * LW_IC + s_ic;
-  const bool s_ic_ok = s_icg < p.cin;
-  float hr[16];
-  auto issue = [&](int t) {
-    const int cam = t / p.tiles_cam, p0 = (t - cam * p.tiles_cam) * LW_PX + 16 * s_q;
-    const float* src = p.x + ((size_t)cam * p.cin + (s_ic_ok ? s_icg : 0)) * HW;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) hr[j] = (s_ic_ok && p0 + j < p.hw) ? src[p0 + j] : 0.f;
-  };
-  auto park = [&]() {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      u32x4 hi, lo;
-      split8(hr + 8 * h, hi, lo);
-      s_b[0][s_ic * LW_PITCH + 2 * s_q + h] = hi;
-      s_b[1][s_ic * LW_PITCH + 2 * s_q + h] = lo;
-    }
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-  float bsum[2] = {0.f, 0.f};
-
-  if (t_begin < t_end) issue(t_begin);
-  for (int t = t_begin; t < t_end; ++t) {
-    __syncthreads();                                   // the previous tile's readers are done
-    park();
-    __syncthreads();
-    if (t + 1 < t_end) issue(t + 1);
-    const int cam = t / p.tiles_cam, p0 = (t - cam * p.tiles_cam) * LW_PX;
-    const float* const gp = p.g + ((size_t)cam * FT_C + 64 * wave + l32) * HW;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int px = p0 + 16 * ks + 8 * kg;
-      u32x4 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        float a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = px + j < p.hw ? gp[(size_t)(32 * i) * HW + px + j] : 0.f;
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s += a[j];
-        bsum[i] += s;
-        split8(a, ah[i], al[i]);
-        bh[i] = s_b[0][(32 * i + l32) * LW_PITCH + 2 * ks + kg];
-        bl[i] = s_b[1][(32 * i + l32) * LW_PITCH + 2 * ks + kg];
-      }
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma_32x32x16_x3(ah[mi], al[mi], bh[ni], bl[ni], acc[mi][ni]);
-    }
-  }
-
-  // C/D of 32x32x16: column (input channel) = l32, rows (output channels) 4 kg + (r & 3) + 8 (r >> 2)
-  float* const ws = p.ws + (size_t)part * FT_C * p.cin;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int ic = chunk * LW_IC + 32 * ni + l32;
-    if (ic >= p.cin) continue;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int oc = 64 * wave + 32 * mi + 4 * kg + (r & 3) + 8 * (r >> 2);
-        ws[(size_t)oc * p.cin + ic] = acc[mi][ni][r];
-      }
-  }
-  if (chunk == 0) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float other = __shfl_xor(bsum[i], 32);
-      if (kg == 0) p.ws_b[(size_t)part * FT_C + 64 * wave + 32 * i + l32] = bsum[i] + other;   // pixels 0-7 of a step, then 8-15
-    }
-  }
+__global__ __launch_bounds__(CW1_THREADS) void fpn_lateral_wgrad_kernel(const LateralWgradParams p) {
+  __shared__ __attribute__((aligned(16))) u32x4 s_b[2][CW1_B_ARR];         // [hi, lo][channel][pixel group (+ 1)]
+  conv1x1_wgrad_body<LateralWgradShape, true>(
+      LateralWgradShape{p, {p.g, p.ws, p.ws_b, p.cin, p.hw, p.tiles_cam, p.tiles, p.partitions, p.chunks}}, s_b);
 }
 
 // ---- top-down adjoint ---------------------------------------------------------------------------------------------------------
@@ -215,12 +127,12 @@ __global__ __launch_bounds__(256) void fpn_extra_wgrad_kernel(const ExtraWgradPa
       acc[i] = mfma_32x32x16_x3(ah, al, bh, bl, acc[i]);
     }
   }
-  // C/D of 32x32x16: column (input channel) = l32, rows (output channels) 4 kg + (r & 3) + 8 (r >> 2)
+  // column (input channel) = l32, rows (output channels) by mfma32_row
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int oc = 64 * wave + 32 * i + 4 * kg + (r & 3) + 8 * (r >> 2);
+      const int oc = mfma32_row(kg, r, 64 * wave + 32 * i);
       p.dw[((size_t)oc * FT_C + ic) * EW_TAPS + tap] = acc[i][r];
     }
   if (blockIdx.x == 0 && p.db) {
@@ -239,14 +151,8 @@ __global__ __launch_bounds__(256) void fpn_plane_sum_kernel(const float* __restr
   const float* src = g + (size_t)blockIdx.x * hw;
   float s = 0.f;
   for (int i = tid; i < hw; i += 256) s += src[i];
-  red[tid] = s;
-  __syncthreads();
-#pragma unroll
-  for (int k = 128; k > 0; k >>= 1) {
-    if (tid < k) red[tid] += red[tid + k];
-    __syncthreads();
-  }
-  if (tid == 0) part[blockIdx.x] = red[0];
+  s = block_sum_256(s, red);
+  if (tid == 0) part[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(FT_C) void fpn_plane_sum_cams_kernel(const float* __restrict__ part, const int n, float* __restrict__ db) {
@@ -262,13 +168,13 @@ static bool ft_cin_ok(int cin) { return cin >= 32 && cin <= FT_MAX_CIN && cin % 
 
 extern "C" size_t gd4d_fpn_lateral_wgrad_workspace_bytes(int cin, int partitions) {
   using namespace gd4d;
-  if (!ft_cin_ok(cin) || partitions < 1 || partitions > 4096) return 0;
+  if (!ft_cin_ok(cin) || !partitions_ok(partitions)) return 0;
   return (size_t)partitions * FT_C * ((size_t)cin + 1) * sizeof(float);
 }
 
 extern "C" long long gd4d_fpn_lateral_wgrad_tiles(int n, int h, int w) {
   if (n <= 0 || h <= 0 || w <= 0) return 0;
-  return (long long)n * (((long long)h * w + gd4d::LW_PX - 1) / gd4d::LW_PX);
+  return (long long)n * (((long long)h * w + gd4d::CW1_PX - 1) / gd4d::CW1_PX);
 }
 
 extern "C" int gd4d_fpn_lateral_wgrad(const float* g, const float* x, int n, int cin, int h, int w, int partitions, float* workspace,
@@ -276,11 +182,11 @@ extern "C" int gd4d_fpn_lateral_wgrad(const float* g, const float* x, int n, int
   using namespace gd4d;
   if (!g || !x || !workspace || !dw || !db) return GD4D_EINVAL;
   if (h <= 0 || w <= 0) return GD4D_EINVAL;
-  if (n <= 0 || !ft_cin_ok(cin) || partitions < 1 || partitions > 4096) return GD4D_EUNSUPPORTED;
+  if (n <= 0 || !ft_cin_ok(cin) || !partitions_ok(partitions)) return GD4D_EUNSUPPORTED;
   const long long hw = (long long)h * w;
   if ((long long)n * FT_MAX_CIN * hw > (1ll << 40) || hw > (1ll << 30)) return GD4D_EUNSUPPORTED;
   if (!aligned16(workspace)) return GD4D_EALIGN;
-  const long long tiles_cam = (hw + LW_PX - 1) / LW_PX;
+  const long long tiles_cam = (hw + CW1_PX - 1) / CW1_PX;
   if (tiles_cam * n > (1ll << 30)) return GD4D_EUNSUPPORTED;
   LateralWgradParams p{};
   p.g = g;
@@ -292,9 +198,9 @@ extern "C" int gd4d_fpn_lateral_wgrad(const float* g, const float* x, int n, int
   p.tiles_cam = (int)tiles_cam;
   p.tiles = (int)(tiles_cam * n);
   p.partitions = partitions;
-  p.chunks = (cin + LW_IC - 1) / LW_IC;
+  p.chunks = (cin + CW1_IC - 1) / CW1_IC;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(fpn_lateral_wgrad_kernel, dim3((unsigned)(p.chunks * partitions)), dim3(LW_THREADS), 0, s, p);
+  hipLaunchKernelGGL(fpn_lateral_wgrad_kernel, dim3((unsigned)(p.chunks * partitions)), dim3(CW1_THREADS), 0, s, p);
   return sum_partitions(p.ws, p.ws_b, partitions, FT_C * cin, FT_C, dw, db, s);   // dW (256, Cin) and db (256)
 }
 

@@ -18,37 +18,21 @@
 //                              forward's Cin (<= 1024) and K = its Cout (<= 256).  One launch per chain step: add = g_{i-1} from the
 //                              aggregation, mask = x_{i-1} (the next step's ReLU), add2 = dout for the residual at the input.
 //   gd4d_conv3x3_wgrad         G[c, k, tap] = sum over images and pixels of dz[c, p] x_in[k, p + tap] for any Cout <= 256, Cin <= 1024
-//                              (multiples of 32), after depth_wgrad_kernel: grid (Cin / 32 chunks) x P partitions of the (image,
-//                              16 x 16 tile) list; a workgroup of Cout / 32 waves, wave w = output channels 32 w .. 32 w + 31 and nine
-//                              32 x 32 accumulators; K runs over the pixels, a K step is one tile row; dz goes from global memory to
-//                              registers (a row ahead) and is also summed there (dbeta); the chunk's 18 x 18 halo of x_in is staged
-//                              once per tile, split hi / lo, as three copies shifted by kx.  Partials per partition in a workspace.
-//   gd4d_osa_concat_wgrad      the same for the 1x1 aggregation, after fpn_lateral_wgrad_kernel: grid (chunks of 64 concatenated
-//                              channels x P partitions of the (image, 64-pixel tile) list) x (blocks of 256 output channels); the
-//                              chunk's channels are read from the L + 1 maps where they lie.
+//                              (multiples of 32): conv3x3_wgrad_body (gd4d_conv_wgrad.h has the algorithm) with Cin, Cout and the
+//                              workgroup's Cout / 32 waves at run time, over the (image, 16 x 16 tile) list of one map, and the sum
+//                              of dz (dbeta's partials).
+//   gd4d_osa_concat_wgrad      the same for the 1x1 aggregation: conv1x1_wgrad_body with blocks of 256 output channels along
+//                              blockIdx.y, guarded at Cout, and K = the concatenated channels, each read from the one of the L + 1
+//                              maps where it lies; no sum of dz (gd4d_ese_bwd left it in dz_sums).
 //   (both)                     the finishing kernel, a workgroup per output channel c: G = the partitions' partials added in order,
 //                              dW[c] = s[c] G[c], dbeta[c] = sum dz, dgamma[c] = rstd[c] (<W[c], G[c]> - mean[c] dbeta[c]).  The
 //                              identity holds because the pre-BatchNorm map is W * x_in: no such map is stored or recomputed, and
 //                              gamma = 0 is exact.  dz is the UNSCALED gradient (of the BatchNorm's output).
 // All GEMMs on the split-bf16 x 3 MFMA (gd4d_bf16x3.h).  No atomics; every sum has a fixed order: two runs give the same bits.
-// Untuned: the weight-gradient kernels read dz once per input-channel chunk.
+#include "gd4d_conv_wgrad.h"
 #include "gd4d_vovnet_gemm.h"
 
 namespace gd4d {
-
-// sum over the workgroup's 256 threads in a fixed order: a tree over LDS; the result in every thread
-__device__ __forceinline__ float vt_block_sum_256(float v, float* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // ---- eSE backward -------------------------------------------------------------------------------------------------------------
 constexpr int VT_ESE_MAX_C = 1024;
@@ -59,7 +43,7 @@ __global__ __launch_bounds__(256) void vt_ese_reduce_kernel(const float* __restr
   const size_t base = (size_t)blockIdx.x * hw;
   float s = 0.f;
   for (int i = threadIdx.x; i < hw; i += 256) s += dout[base + i] * xt[base + i];
-  s = vt_block_sum_256(s, red);
+  s = block_sum_256(s, red);
   if (threadIdx.x == 0) dgate[blockIdx.x] = s;
 }
 
@@ -118,17 +102,12 @@ __global__ __launch_bounds__(256) void vt_ese_apply_kernel(const float* __restri
     dz[base + i] = v;
     s += v;
   }
-  s = vt_block_sum_256(s, red);
+  s = block_sum_256(s, red);
   if (threadIdx.x == 0) dz_sums[blockIdx.x] = s;
 }
 
 // ---- 3x3 weight gradient ------------------------------------------------------------------------------------------------------
-constexpr int VW_T = 16, VW_KC = 32, VW_HE = VW_T + 2, VW_MAX_THREADS = 512;
-constexpr int VW_CH_STRIDE = VW_HE * 32 + 16;                 // 18 rows of 16 bf16 + 16 B: 16 lanes of a read on 16 distinct slots
-constexpr int VW_PLANE = VW_KC * VW_CH_STRIDE;                // 18 944 B
-constexpr int VW_LDS = 3 * 2 * VW_PLANE;                      // 113 664 B
-constexpr int VW_ITEMS = 3 * VW_KC * VW_HE * 2;               // (kx, channel, halo row, 8-pixel half): 3456
-static_assert(VW_LDS <= 160 * 1024, "LDS budget of a CU");
+constexpr int VW_MAX_THREADS = 512;
 
 struct VvWgradParams {
   const float* dz;                 // (N, cout, H, W)
@@ -138,106 +117,29 @@ struct VvWgradParams {
   float* ws_b;                     // (partitions, cout)
 };
 
+// conv3x3_wgrad_body's policy: channel counts and the workgroup's size at run time, the tiles of a single map
+struct VvWgradShape {
+  const VvWgradParams& p;
+  __device__ __forceinline__ int cin() const { return p.cin; }
+  __device__ __forceinline__ int cout() const { return p.cout; }
+  __device__ __forceinline__ int chunks() const { return p.chunks; }
+  __device__ __forceinline__ int threads() const { return blockDim.x; }
+  __device__ __forceinline__ Conv3x3Tile tile(int t, int chunk, int oc_a) const {
+    const size_t HW = (size_t)p.h * p.w;
+    const int cam = t / p.tiles_img;
+    const int rt = t - cam * p.tiles_img;
+    return {p.h, p.w, (rt / p.tiles_x) * CW3_T, (rt % p.tiles_x) * CW3_T, p.x + ((size_t)cam * p.cin + chunk * CW3_KC) * HW,
+            p.dz + ((size_t)cam * p.cout + oc_a) * HW};
+  }
+};
+
 // blockDim = 64 (cout / 32)
 __global__ __launch_bounds__(VW_MAX_THREADS) void vt_conv3x3_wgrad_kernel(const VvWgradParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, threads = blockDim.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int l32 = lane & 31, kg = lane >> 5;
-  const int chunk = blockIdx.x % p.chunks, part = blockIdx.x / p.chunks;
-  const int t_begin = (int)((long long)part * p.tiles / p.partitions), t_end = (int)((long long)(part + 1) * p.tiles / p.partitions);
-  const int H = p.h, W = p.w;
-  const size_t HW = (size_t)H * W;
-
-  f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  float bsum = 0.f;
-
-  const int oc_a = 32 * wave + l32;                          // the A operand's row of this lane
-  for (int t = t_begin; t < t_end; ++t) {
-    const int cam = t / p.tiles_img;
-    const int rt = t - cam * p.tiles_img;
-    const int ty0 = (rt / p.tiles_x) * VW_T, tx0 = (rt % p.tiles_x) * VW_T;
-    const float* const xin = p.x + ((size_t)cam * p.cin + chunk * VW_KC) * HW;
-    const float* const dzp = p.dz + ((size_t)cam * p.cout + oc_a) * HW;
-
-    // one row of the dz tile: 8 pixels of this lane's output channel, zeros outside the image
-    auto load_dz = [&](int py, float* v) {
-      const int y = ty0 + py;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int x = tx0 + 8 * kg + j;
-        v[j] = (y < H && x < W) ? dzp[(size_t)y * W + x] : 0.f;
-      }
-    };
-    float a_next[8];
-    load_dz(0, a_next);
-
-    __syncthreads();                                         // the previous tile's readers are done
-    for (int it = tid; it < VW_ITEMS; it += threads) {
-      const int half = it & 1, q = it >> 1;
-      const int hy = q % VW_HE, q2 = q / VW_HE;
-      const int ic = q2 % VW_KC, kx = q2 / VW_KC;
-      const int y = ty0 - 1 + hy, x0 = tx0 - 1 + kx + 8 * half;
-      const bool row_in = y >= 0 && y < H;
-      const float* src = xin + (size_t)ic * HW + (row_in ? (size_t)y * W : 0);
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int x = x0 + j;
-        v[j] = (row_in && x >= 0 && x < W) ? src[x] : 0.f;
-      }
-      u32x4 hi, lo;
-      split8(v, hi, lo);
-      char* dst = smem + (size_t)(kx * 2) * VW_PLANE + ic * VW_CH_STRIDE + hy * 32 + half * 16;
-      *reinterpret_cast<u32x4*>(dst) = hi;
-      *reinterpret_cast<u32x4*>(dst + VW_PLANE) = lo;
-    }
-    __syncthreads();
-
-    const char* const bbase = smem + l32 * VW_CH_STRIDE + kg * 16;
-#pragma unroll 1
-    for (int py = 0; py < VW_T; ++py) {
-      u32x4 ah, al;
-      split8(a_next, ah, al);
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += a_next[j];
-      bsum += s;
-      if (py + 1 < VW_T) load_dz(py + 1, a_next);
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          const char* b = bbase + (kx * 2) * VW_PLANE + (py + ky) * 32;
-          const u32x4 bh = *reinterpret_cast<const u32x4*>(b);
-          const u32x4 bl = *reinterpret_cast<const u32x4*>(b + VW_PLANE);
-          acc[3 * ky + kx] = mfma_32x32x16_x3(ah, al, bh, bl, acc[3 * ky + kx]);
-        }
-    }
-  }
-
-  // C/D of 32x32x16: column (input channel) = l32, rows (output channels) 4 kg + (r & 3) + 8 (r >> 2)
-  float* const ws = p.ws + (size_t)part * 9 * p.cout * p.cin;
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int oc = 32 * wave + 4 * kg + (r & 3) + 8 * (r >> 2);
-      ws[((size_t)t * p.cout + oc) * p.cin + chunk * VW_KC + l32] = acc[t][r];
-    }
-  const float other = __shfl_xor(bsum, 32);
-  if (chunk == 0 && kg == 0) p.ws_b[(size_t)part * p.cout + oc_a] = bsum + other;               // pixels 0-7 of a row, then 8-15
+  conv3x3_wgrad_body<VvWgradShape, true>(VvWgradShape{p}, smem);
 }
 
 // ---- aggregation (1x1) weight gradient ----------------------------------------------------------------------------------------
-constexpr int VA_THREADS = 256, VA_PX = 64, VA_IC = 64, VA_OC = 256;
-constexpr int VA_PITCH = 9;                            // 16-byte units per channel of the staged block: 8 pixel groups + 1
-constexpr int VA_B_ARR = VA_IC * VA_PITCH;
-
 struct VvAggWgradParams {
   const float* dz;                 // (N, cout, H, W)
   const float* src[VV_MAX_SRC];
@@ -246,98 +148,27 @@ struct VvAggWgradParams {
   float* ws;                       // (partitions, cout, k)
 };
 
-__global__ __launch_bounds__(VA_THREADS) void vt_osa_wgrad_kernel(const VvAggWgradParams p) {
-  __shared__ __attribute__((aligned(16))) u32x4 s_b[2][VA_B_ARR];          // [hi, lo][channel][pixel group (+ 1)]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, kg = lane >> 5;
-  const int chunk = blockIdx.x % p.chunks, part = blockIdx.x / p.chunks;
-  const int oc0 = blockIdx.y * VA_OC + 64 * wave;
-  const int t_begin = (int)((long long)part * p.tiles / p.partitions), t_end = (int)((long long)(part + 1) * p.tiles / p.partitions);
-  const size_t HW = (size_t)p.hw;
-
-  // staging role: thread = (channel of the chunk, 16 consecutive pixels of the tile); the channel lies in one of the source maps
-  const int s_ic = tid >> 2, s_q = tid & 3;
-  const int s_icg = chunk * VA_IC + s_ic;
-  const bool s_ic_ok = s_icg < p.k;
-  const float* s_base = p.src[0];
-  int s_cs = p.src_ch[0], s_cl = s_ic_ok ? s_icg : 0;
+// conv1x1_wgrad_body's policy: a block of 256 output channels per blockIdx.y, guarded at cout; K is the concatenation of the source
+// maps, a staged channel is read from the map it lies in
+struct OsaWgradShape {
+  const VvAggWgradParams& p;
+  const Conv1x1Wgrad g;
+  static constexpr bool GUARD = true;
+  __device__ __forceinline__ int cout() const { return p.cout; }
+  __device__ __forceinline__ int oc0(int wave) const { return blockIdx.y * CW1_OC + 64 * wave; }
+  __device__ __forceinline__ Conv1x1Source source(int icg, bool ok) const {
+    Conv1x1Source s{p.src[0], p.src_ch[0], ok ? icg : 0};
 #pragma unroll
-  for (int i = 1; i < VV_MAX_SRC; ++i)
-    if (i < p.n_src && s_ic_ok && s_icg >= p.src_c0[i]) {
-      s_base = p.src[i];
-      s_cs = p.src_ch[i];
-      s_cl = s_icg - p.src_c0[i];
-    }
-  float hr[16];
-  auto issue = [&](int t) {
-    const int cam = t / p.tiles_img, p0 = (t - cam * p.tiles_img) * VA_PX + 16 * s_q;
-    const float* src = s_base + ((size_t)cam * s_cs + s_cl) * HW;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) hr[j] = (s_ic_ok && p0 + j < p.hw) ? src[p0 + j] : 0.f;
-  };
-  auto park = [&]() {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      u32x4 hi, lo;
-      split8(hr + 8 * h, hi, lo);
-      s_b[0][s_ic * VA_PITCH + 2 * s_q + h] = hi;
-      s_b[1][s_ic * VA_PITCH + 2 * s_q + h] = lo;
-    }
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-
-  bool a_ok[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) a_ok[i] = oc0 + 32 * i + l32 < p.cout;
-
-  if (t_begin < t_end) issue(t_begin);
-  for (int t = t_begin; t < t_end; ++t) {
-    __syncthreads();                                   // the previous tile's readers are done
-    park();
-    __syncthreads();
-    if (t + 1 < t_end) issue(t + 1);
-    const int cam = t / p.tiles_img, p0 = (t - cam * p.tiles_img) * VA_PX;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int px = p0 + 16 * ks + 8 * kg;
-      u32x4 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const float* const gp = p.dz + ((size_t)cam * p.cout + (a_ok[i] ? oc0 + 32 * i + l32 : 0)) * HW;
-        float a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = (a_ok[i] && px + j < p.hw) ? gp[px + j] : 0.f;
-        split8(a, ah[i], al[i]);
-        bh[i] = s_b[0][(32 * i + l32) * VA_PITCH + 2 * ks + kg];
-        bl[i] = s_b[1][(32 * i + l32) * VA_PITCH + 2 * ks + kg];
-      }
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma_32x32x16_x3(ah[mi], al[mi], bh[ni], bl[ni], acc[mi][ni]);
-    }
+    for (int i = 1; i < VV_MAX_SRC; ++i)
+      if (i < p.n_src && ok && icg >= p.src_c0[i]) s = {p.src[i], p.src_ch[i], icg - p.src_c0[i]};
+    return s;
   }
+};
 
-  // C/D of 32x32x16: column (input channel) = l32, rows (output channels) 4 kg + (r & 3) + 8 (r >> 2)
-  float* const ws = p.ws + (size_t)part * p.cout * p.k;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int ic = chunk * VA_IC + 32 * ni + l32;
-    if (ic >= p.k) continue;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int oc = oc0 + 32 * mi + 4 * kg + (r & 3) + 8 * (r >> 2);
-        if (oc < p.cout) ws[(size_t)oc * p.k + ic] = acc[mi][ni][r];
-      }
-  }
+__global__ __launch_bounds__(CW1_THREADS) void vt_osa_wgrad_kernel(const VvAggWgradParams p) {
+  __shared__ __attribute__((aligned(16))) u32x4 s_b[2][CW1_B_ARR];         // [hi, lo][channel][pixel group (+ 1)]
+  conv1x1_wgrad_body<OsaWgradShape, false>(
+      OsaWgradShape{p, {p.dz, p.ws, nullptr, p.k, p.hw, p.tiles_img, p.tiles, p.partitions, p.chunks}}, s_b);
 }
 
 // ---- the finishing step of both weight gradients: a workgroup per output channel ---------------------------------------------
@@ -364,7 +195,7 @@ __global__ __launch_bounds__(256) void vt_wgrad_finish_kernel(const VvFinishPara
     if (p.dw) p.dw[(size_t)c * per + i] = scale * g;
     dot = fmaf(p.weight[(size_t)c * per + i], g, dot);
   }
-  dot = vt_block_sum_256(dot, red);
+  dot = block_sum_256(dot, red);
   if (threadIdx.x == 0) {
     float b = 0.f;
     for (int q = 0; q < p.parts_b; ++q) b += p.ws_b[(size_t)q * p.cout + c];
@@ -372,8 +203,6 @@ __global__ __launch_bounds__(256) void vt_wgrad_finish_kernel(const VvFinishPara
     if (p.dgamma) p.dgamma[c] = p.bn[p.cout + c] * (dot - p.bn[2 * p.cout + c] * b);
   }
 }
-
-static bool vt_parts_ok(int partitions) { return partitions >= 1 && partitions <= 4096; }
 
 static int vt_image_t(const float* weight, int cin, int cout, int taps, void* image, void* stream) {
   if (!aligned16(image)) return GD4D_EALIGN;
@@ -467,17 +296,17 @@ extern "C" int gd4d_osa_concat_dgrad(const float* dz, int n, int cout, int h, in
 
 extern "C" long long gd4d_conv3x3_wgrad_tiles(int n, int h, int w) {
   if (n <= 0 || h <= 0 || w <= 0) return 0;
-  return (long long)n * ((h + gd4d::VW_T - 1) / gd4d::VW_T) * ((w + gd4d::VW_T - 1) / gd4d::VW_T);
+  return (long long)n * ((h + gd4d::CW3_T - 1) / gd4d::CW3_T) * ((w + gd4d::CW3_T - 1) / gd4d::CW3_T);
 }
 
 extern "C" long long gd4d_osa_concat_wgrad_tiles(int n, int h, int w) {
   if (n <= 0 || h <= 0 || w <= 0) return 0;
-  return (long long)n * (((long long)h * w + gd4d::VA_PX - 1) / gd4d::VA_PX);
+  return (long long)n * (((long long)h * w + gd4d::CW1_PX - 1) / gd4d::CW1_PX);
 }
 
 extern "C" size_t gd4d_conv_wgrad_workspace_bytes(int cin, int cout, int taps, int partitions) {
   using namespace gd4d;
-  if (!vt_parts_ok(partitions)) return 0;
+  if (!partitions_ok(partitions)) return 0;
   if (!(taps == 9 ? vv_conv_channels(cin, cout) : taps == 1 ? vv_osa_channels(cin, cout) : false)) return 0;
   return (size_t)partitions * ((size_t)taps * cout * cin + cout) * sizeof(float);
 }
@@ -496,7 +325,7 @@ extern "C" int gd4d_conv3x3_wgrad(const float* dz, const float* x, int n, int ci
                                   void* stream) {
   using namespace gd4d;
   if (!dz || !x || !workspace || !weight || !bn || (!dw && !dgamma && !dbeta)) return GD4D_EINVAL;
-  if (!vv_conv_channels(cin, cout) || n <= 0 || h <= 0 || w <= 0 || !vt_parts_ok(partitions)) return GD4D_EUNSUPPORTED;
+  if (!vv_conv_channels(cin, cout) || n <= 0 || h <= 0 || w <= 0 || !partitions_ok(partitions)) return GD4D_EUNSUPPORTED;
   if ((long long)h * w > (1ll << 30) || (long long)n * 1024 * h * w > (1ll << 40)) return GD4D_EUNSUPPORTED;
   if (!aligned16(workspace)) return GD4D_EALIGN;
   const long long tiles = gd4d_conv3x3_wgrad_tiles(n, h, w);
@@ -508,16 +337,16 @@ extern "C" int gd4d_conv3x3_wgrad(const float* dz, const float* x, int n, int ci
   p.cout = cout;
   p.h = h;
   p.w = w;
-  p.tiles_x = (w + VW_T - 1) / VW_T;
-  p.tiles_img = p.tiles_x * ((h + VW_T - 1) / VW_T);
+  p.tiles_x = (w + CW3_T - 1) / CW3_T;
+  p.tiles_img = p.tiles_x * ((h + CW3_T - 1) / CW3_T);
   p.tiles = (int)tiles;
   p.partitions = partitions;
-  p.chunks = cin / VW_KC;
+  p.chunks = cin / CW3_KC;
   p.ws = workspace;
   p.ws_b = workspace + (size_t)partitions * 9 * cout * cin;
-  if (!allow_dynamic_lds(reinterpret_cast<const void*>(vt_conv3x3_wgrad_kernel), VW_LDS)) return GD4D_ELAUNCH;
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(vt_conv3x3_wgrad_kernel), CW3_LDS)) return GD4D_ELAUNCH;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(vt_conv3x3_wgrad_kernel, dim3((unsigned)(p.chunks * partitions)), dim3(64 * (cout / 32)), VW_LDS, s, p);
+  hipLaunchKernelGGL(vt_conv3x3_wgrad_kernel, dim3((unsigned)(p.chunks * partitions)), dim3(64 * (cout / 32)), CW3_LDS, s, p);
   return vt_finish(p.ws, p.ws_b, partitions, partitions, cin, cout, 9, weight, bn, dw, dgamma, dbeta, s);
 }
 
@@ -526,7 +355,7 @@ extern "C" int gd4d_osa_concat_wgrad(const float* dz, const float* dz_sums, cons
                                      float* dw, float* dgamma, float* dbeta, void* stream) {
   using namespace gd4d;
   if (!dz || !dz_sums || !src || !src_channels || !workspace || !weight || !bn || (!dw && !dgamma && !dbeta)) return GD4D_EINVAL;
-  if (n_src < 1 || n_src > VV_MAX_SRC || n <= 0 || h <= 0 || w <= 0 || !vt_parts_ok(partitions)) return GD4D_EUNSUPPORTED;
+  if (n_src < 1 || n_src > VV_MAX_SRC || n <= 0 || h <= 0 || w <= 0 || !partitions_ok(partitions)) return GD4D_EUNSUPPORTED;
   const long long hw = (long long)h * w;
   if (hw > (1ll << 30) || (long long)n * 2304 * hw > (1ll << 40)) return GD4D_EUNSUPPORTED;
   VvAggWgradParams p{};
@@ -552,10 +381,10 @@ extern "C" int gd4d_osa_concat_wgrad(const float* dz, const float* dz_sums, cons
   p.tiles_img = (int)(tiles / n);
   p.tiles = (int)tiles;
   p.partitions = partitions;
-  p.chunks = (k + VA_IC - 1) / VA_IC;
+  p.chunks = (k + CW1_IC - 1) / CW1_IC;
   p.ws = workspace;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(vt_osa_wgrad_kernel, dim3((unsigned)(p.chunks * partitions), (unsigned)((cout + VA_OC - 1) / VA_OC)), dim3(VA_THREADS), 0,
+  hipLaunchKernelGGL(vt_osa_wgrad_kernel, dim3((unsigned)(p.chunks * partitions), (unsigned)((cout + CW1_OC - 1) / CW1_OC)), dim3(CW1_THREADS), 0,
                      s, p);
   return vt_finish(p.ws, dz_sums, partitions, n, k, cout, 1, weight, bn, dw, dgamma, dbeta, s);
 }
