@@ -16,6 +16,7 @@ ABI_VERSION = 56
 PIXEL_MAJOR, HEAD_MAJOR = 0, 1
 
 F32, BF16, F16 = 0, 1, 2
+GATHER_REVERSED = 0x100           # GD4D_GATHER_REVERSED: OR-ed into feats_dtype of gd4d_cross_attn_agg_items_coarse_fwd
 
 _c = ctypes
 _vp, _i, _f = _c.c_void_p, _c.c_int, _c.c_float
@@ -38,6 +39,7 @@ SIGNATURES = {
     'gd4d_gather_slice_group': (_i, [_i]),
     'gd4d_gather_slice_group_get': (_i, []),
     'gd4d_gather_walk': (_i, [_i, _i, _i, _i, _vp, _vp]),
+    'gd4d_gather_walk_dir': (_i, [_i, _i, _i, _i, _i, _vp, _vp]),
     'gd4d_chain_guest_bytes': (_c.c_size_t, []),
     'gd4d_value_proj_image_bytes': (_c.c_size_t, []),
     'gd4d_value_proj_image': (_i, [_vp, _vp, _vp, _vp]),

@@ -275,6 +275,15 @@ __host__ __device__ __forceinline__ bool sliced_walk(const SlicedParams& p, int 
   return qi < p.per_xcd && pos < p.BQ;
 }
 
+// The walk with a direction (gd4d_cross_attn_agg_items_coarse_fwd with GD4D_GATHER_REVERSED).  Reversed, every phase but the last is walked from the back - the
+// slice groups from last to first, the projected rows' short phase still closing the tail - so that a launch starts on the planes the
+// launch before it, walking forward, read last.  Which workgroup sums which (position, phase) changes, what it sums does not.
+__host__ __device__ __forceinline__ bool sliced_walk_dir(const SlicedParams& p, int block, int& pos, int& sl, bool reversed) {
+  const bool work = sliced_walk(p, block, pos, sl);
+  if (reversed && sl < p.slice_n - 1) sl = p.slice_n - 2 - sl;
+  return work;
+}
+
 template <int HH, int LT, typename VT>
 __device__ __forceinline__ void cross_attn_agg_sliced_body(const SlicedParams& p, const int pos, const int sl, char* s_raw) {
   constexpr int ES = sizeof(VT);
@@ -616,11 +625,11 @@ __global__ __launch_bounds__(64 * HH, OCC) void cross_attn_agg_items_kernel(cons
 // NS (gd4d_gather_slice_group): a fine workgroup gathers NS consecutive slices of its query from one set of pairs; the walk's
 // phases are then the 8 / NS slice groups and, last, the projected rows (still one workgroup per query).
 template <int HH, typename VT, int OCC, bool WIDE = false, int NS = 1>
-__global__ __launch_bounds__(64 * HH, OCC) void cross_attn_agg_items_coarse_kernel(const ItemsParams ip) {
+__global__ __launch_bounds__(64 * HH, OCC) void cross_attn_agg_items_coarse_kernel(const ItemsParams ip, const int reversed) {
   extern __shared__ __attribute__((aligned(16))) char s_raw[];   // [HH][CH][8][GP]
   trace_mark(g_trace_sliced, 6ull);
   int pos, sl;
-  if (!sliced_walk(ip.s, blockIdx.x, pos, sl)) return;
+  if (!sliced_walk_dir(ip.s, blockIdx.x, pos, sl, reversed != 0)) return;
   if (sl == kSlices / NS) cross_attn_agg_items_body<HH, 2, float, false, 2, 2, true>(ip, pos, sl, s_raw);
   else cross_attn_agg_items_body<HH, 2, VT, WIDE, 2, 0, false, NS>(ip, pos, sl * NS, s_raw);
   trace_mark(g_trace_sliced, 0x86ull);
@@ -1068,6 +1077,8 @@ extern "C" int gd4d_cross_attn_agg_items_coarse_fwd(const void* const* level_ptr
                                                     float* pagg, int B, int N, int Q, int Hh, int C, int L, int P, int feats_dtype,
                                                     const int32_t* query_order, void* stream) {
   using namespace gd4d;
+  const bool reversed = (feats_dtype & GD4D_GATHER_REVERSED) != 0;   // the walk's direction rides on the value type: per launch
+  feats_dtype &= ~GD4D_GATHER_REVERSED;
   if (!proj_ptrs || !proj_cam_stride_bytes || !pagg || !wsum) return GD4D_EINVAL;
   if (L != 4 || Hh != 8) return GD4D_EUNSUPPORTED;                   // (two fine + two coarse levels; a head = one 32-channel slice)
   ItemsParams ip{};
@@ -1098,7 +1109,7 @@ extern "C" int gd4d_cross_attn_agg_items_coarse_fwd(const void* const* level_ptr
   const dim3 grid(gather_grid(p.per_xcd, p.blk, p.slice_n));
   hipStream_t s = static_cast<hipStream_t>(stream);
   auto go = [&](auto kern) -> int {
-    hipLaunchKernelGGL(kern, grid, dim3(64 * 8), lds, s, ip);
+    hipLaunchKernelGGL(kern, grid, dim3(64 * 8), lds, s, ip, reversed ? 1 : 0);
     return check_launch();
   };
   auto with_ns = [&](auto vt, auto w) -> int {                       // (NS > 1 holds 4 NS sums per lane: GATHER_OCC)
@@ -1123,7 +1134,7 @@ extern "C" int gd4d_gather_slice_group(int ns) {
 
 extern "C" int gd4d_gather_slice_group_get(void) { return gd4d::g_gather_ns; }
 
-extern "C" int gd4d_gather_walk(int BQ, int blk, int ns, int block, int* pos, int* group) {
+extern "C" int gd4d_gather_walk_dir(int BQ, int blk, int ns, int reversed, int block, int* pos, int* group) {
   using namespace gd4d;
   if (BQ <= 0 || blk <= 0 || (ns != 1 && ns != 2 && ns != 4 && ns != 8)) return GD4D_EINVAL;
   SlicedParams p{};
@@ -1131,10 +1142,14 @@ extern "C" int gd4d_gather_walk(int BQ, int blk, int ns, int block, int* pos, in
   const long long grid = gather_grid(p.per_xcd, p.blk, p.slice_n);
   if (grid > 0x7fffffffll) return GD4D_EUNSUPPORTED;
   int q = -1, g = -1;
-  if (block < 0 || block >= grid || !sliced_walk(p, block, q, g)) q = g = -1;
+  if (block < 0 || block >= grid || !sliced_walk_dir(p, block, q, g, reversed != 0)) q = g = -1;
   if (pos) *pos = q;
   if (group) *group = g;
   return (int)grid;
+}
+
+extern "C" int gd4d_gather_walk(int BQ, int blk, int ns, int block, int* pos, int* group) {
+  return gd4d_gather_walk_dir(BQ, blk, ns, 0, block, pos, group);
 }
 
 extern "C" int gd4d_cross_attn_agg_items_count_fwd(const void* const* level_ptrs, const int32_t* level_hw,

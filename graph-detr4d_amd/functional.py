@@ -836,12 +836,13 @@ class LateValues:
                     t.record_stream(cur)
 
     def aggregate(self, module, ref, offsets, attn_logits, cam_logits, lidar2img, img_h, img_w, order=None, vp_weight=None,
-                  vp_bias=None, raw_cam_weights=False, coarse=False):
+                  vp_bias=None, raw_cam_weights=False, coarse=False, reverse=False):
         """Per-head aggregates of the raw features: agg (B, Q, Hh, C), wsum (B, Q, Hh); rows mode with vp_weight:
         (out (B, Q, C),) - value_proj applied in the kernel's epilogue.  raw_cam_weights: the camera logits are used as they
         are, without the sigmoid (the neighbour pass of Deform3DCrossAttnMP).  coarse (after coarse_setup, the buffer holding THIS
         module's projection): (agg, wsum, pagg) - the fine levels' aggregates and weight sums and the coarse levels' already
-        projected part (B, Q, C); value_proj of (agg, wsum) plus pagg is the layer's sampled value."""
+        projected part (B, Q, C); value_proj of (agg, wsum) plus pagg is the layer's sampled value.  reverse (with coarse): the
+        gather walks its slice groups from last to first (ops.cross_attn_agg_coarse_fwd)."""
         # (kernels: 1 / 2 / 4 / 8 points per head with 8 heads on the sliced form, 4 otherwise; other counts - the reference's
         #  constructor default is 5 - are padded with points that are never visible and weigh nothing)
         offsets, attn_logits = pad_points(offsets, attn_logits, (1, 2, 4, 8) if self.mode == 'sliced' and module.num_heads == 8 else (4,),
@@ -860,7 +861,7 @@ class LateValues:
                 ops.value_proj_guest_fwd(self.coarse_guest(module))
             self._wait_copy()
             if coarse:
-                agg, pagg = ops.cross_attn_agg_coarse_fwd(plan, self.coarse)
+                agg, pagg = ops.cross_attn_agg_coarse_fwd(plan, self.coarse, reverse=reverse)
                 return agg, plan.wsum, pagg
             agg = ops.cross_attn_agg_sliced_fwd(plan)
             if vp_weight is not None:

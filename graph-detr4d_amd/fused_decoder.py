@@ -218,6 +218,9 @@ def run_single(decoder, query, query_pos, value, reference_points, reg_branches,
     # the guest job of a chain launch that runs before gather l on compute units the chain leaves idle - layer 0's rides here,
     # layer l + 1's in chain B' of layer l (one buffer: gather l has read it by then).
     coarse = late.mode == 'sliced' and late.coarse_setup([l.attentions[1] for l in layers])
+    # Consecutive gathers walk the slice planes in opposite directions: a launch starts on the planes the one before it read last - 466-476
+    # against 486-497 us for gathers 1-5 of a step (docs/measurements_r31.md).  ops.gather_walk_alternate(False): all forward.
+    alternate = bool(coarse) and ops.gather_walk_alternate()
     first_guest = None
     if coarse and not late.take_first(layers[0].attentions[1]):      # (not enqueued beside the copy when `late` was made: rides here)
         first_guest = late.coarse_guest(layers[0].attentions[1])
@@ -286,7 +289,7 @@ def run_single(decoder, query, query_pos, value, reference_points, reg_branches,
             agg_raw, wsum = agg, agg
         elif coarse:
             agg_raw, wsum, pagg = late.aggregate(ca, ref, off.view(1, q, hh, npt, 3), att.view(1, q, hh, nlv, npt), cam, lidar2img,
-                                                 img_h, img_w, order=order, coarse=True)
+                                                 img_h, img_w, order=order, coarse=True, reverse=alternate and lid % 2 == 1)
             first = ops.chain_headgemm(agg_raw, wsum, ca.value_proj.weight, ca.value_proj.bias, dst=0, addend=pagg.view(q, c))
             keep.append(pagg)
         else:

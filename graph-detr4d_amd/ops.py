@@ -383,10 +383,11 @@ def coarse_supported(plan):
     return plan.items and len(plan.pyramid.level_hw) == 4 and plan.num_heads == 8
 
 
-def cross_attn_agg_coarse_fwd(plan, coarse, agg=None, pagg=None):
+def cross_attn_agg_coarse_fwd(plan, coarse, agg=None, pagg=None, reverse=False):
     """gd4d_cross_attn_agg_items_coarse_fwd: levels 0, 1 gathered raw from the Plan's pyramid, levels 2, 3 from `coarse`
     (CoarseValues of THIS layer's value_proj).  Returns agg (B, Q, 8, 256), pagg (B, Q, 256); plan.wsum holds the fine levels'
-    weight sums: value_proj_heads_fwd(agg, plan.wsum, W, b) + pagg is the layer's sampled value."""
+    weight sums: value_proj_heads_fwd(agg, plan.wsum, W, b) + pagg is the layer's sampled value.  reverse: the launch walks its
+    slice groups from last to first (GD4D_GATHER_REVERSED; the same bits)."""
     pyramid = plan.pyramid
     dev = pyramid.device
     b, q, hh, query_order = plan.b, plan.q, plan.num_heads, plan.order
@@ -406,7 +407,8 @@ def cross_attn_agg_coarse_fwd(plan, coarse, agg=None, pagg=None):
     pcs = (ctypes.c_int64 * 2)(*coarse.cam_stride)
     _call('gd4d_cross_attn_agg_items_coarse_fwd', ptrs, lv, cs, pyramid.pix_stride, pyramid.slice_stride, pp, pcs,
           _dev(plan.buf, 'plan', U8), _dev(agg, 'agg', F32), _dev(plan.wsum, 'wsum', F32), _dev(pagg, 'pagg', F32), b, pyramid.rows // b, q,
-          hh, 256, 4, plan.points, _lib.F32 if pyramid.dtype == F32 else _lib.BF16, _order_ptr(query_order, b * q))
+          hh, 256, 4, plan.points, (_lib.F32 if pyramid.dtype == F32 else _lib.BF16) | (_lib.GATHER_REVERSED if reverse else 0),
+          _order_ptr(query_order, b * q))
     return agg, pagg
 
 
@@ -2345,14 +2347,31 @@ def gather_slice_group(ns=None):
     return int(lib.gd4d_gather_slice_group(int(ns)))
 
 
-def gather_walk(bq, blk, ns, block=-1):
-    """gd4d_gather_walk (no GPU): (grid size, position, group) of workgroup `block` in the walk of cross_attn_agg_coarse_fwd over
-    `bq` queries in blocks of `blk` with `ns` slices per workgroup; group 8 // ns is the projected rows' phase, position and group
-    are -1 for a workgroup with nothing to do."""
+def gather_walk(bq, blk, ns, block=-1, reverse=False):
+    """gd4d_gather_walk / gd4d_gather_walk_dir (no GPU): (grid size, position, group) of workgroup `block` in the walk of
+    cross_attn_agg_coarse_fwd over `bq` queries in blocks of `blk` with `ns` slices per workgroup; group 8 // ns is the projected
+    rows' phase, position and group are -1 for a workgroup with nothing to do.  reverse: the walk of a reversed launch."""
     pos, group = ctypes.c_int(-1), ctypes.c_int(-1)
-    grid = _lib.load().gd4d_gather_walk(int(bq), int(blk), int(ns), int(block), ctypes.byref(pos), ctypes.byref(group))
+    if reverse:
+        grid = _lib.load().gd4d_gather_walk_dir(int(bq), int(blk), int(ns), 1, int(block), ctypes.byref(pos), ctypes.byref(group))
+    else:
+        grid = _lib.load().gd4d_gather_walk(int(bq), int(blk), int(ns), int(block), ctypes.byref(pos), ctypes.byref(group))
     _lib.check(grid if grid < 0 else 0, 'gd4d_gather_walk')
     return grid, pos.value, group.value
+
+
+_WALK_ALTERNATE = [True]
+
+
+def gather_walk_alternate(on=None):
+    """Whether fused_decoder.run_single reverses the gather's walk in every other layer (layer 0 walks forward), for the PROCESS - a
+    dev switch for A/B runs from one build: the same bits either way; a captured graph and a recorded request program keep what they
+    were made with.  None only asks.  Returns the setting before the call.  (Kept on this side of the library: the decoder reads
+    it while it enqueues, where a call into the library is a launch.)"""
+    was = _WALK_ALTERNATE[0]
+    if on is not None:
+        _WALK_ALTERNATE[0] = bool(on)
+    return was
 
 
 def mha_core_presplit_fwd(q, kv, num_heads, attn_mask=None, want_lse=False, dropout_p=0., seed=None):

@@ -239,6 +239,18 @@ int gd4d_gather_slice_group(int ns);
 int gd4d_gather_slice_group_get(void);
 int gd4d_gather_walk(int BQ, int blk, int ns, int block, int* pos, int* group);
 
+/* The direction of the walk.  Every launch of gd4d_cross_attn_agg_items_coarse_fwd pulls more over the fabric than the memory-side cache
+ * holds, and a sweep repeated in one order finds nothing of the sweep before it; walked the other way, a launch starts on the planes the
+ * launch before it read last (docs/measurements_r31.md).  Reversed, an XCD walks its slice groups from last to first; the projected rows
+ * stay the last phase.  Every (query, head, slice) sums the same loads in the same order: agg, wsum and pagg are bit-identical in both
+ * directions.
+ *   GD4D_GATHER_REVERSED: OR it into the feats_dtype argument of gd4d_cross_attn_agg_items_coarse_fwd (GD4D_F32 | GD4D_GATHER_REVERSED,
+ *     GD4D_BF16 | GD4D_GATHER_REVERSED) and that launch walks reversed - the direction is per launch, and a recorded request step
+ *     (GD4D_REQ_AGG_COARSE) carries it with its feats_dtype.  No other entry point takes the bit.
+ *   gd4d_gather_walk_dir (no GPU): gd4d_gather_walk for a direction (reversed = 0 / 1). */
+#define GD4D_GATHER_REVERSED 0x100
+int gd4d_gather_walk_dir(int BQ, int blk, int ns, int reversed, int block, int* pos, int* group);
+
 /* gd4d_cross_attn_agg_items_count_fwd - a TRAINING step's forward gather and the first step of the pyramid gradient's bookkeeping
  * in one launch: gd4d_cross_attn_agg_items_fwd (all slices, every level) on plan_items and gd4d_pyramid_grad_count on plan_pairs (the
  * two forms of one plan: GD4D_CA_PLAN_BOTH) - the same results as the two launches (the slots, as there, in an order the atomics
