@@ -247,33 +247,7 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_plan_kernel(const PlanP
 // any feature load it ran 65 us of the 133 us the launch took - issue-bound on work that is the same for all 8 slices.
 // Now a pass is: 512 B of plan pairs (one coalesced 8-byte load per lane, staged in the wave's own LDS patch), four
 // 16-byte LDS reads per lane (the 8 lanes of a corner slot read one address: broadcast), then per load one add, the
-// load, two packed FMAs.
-struct SlicedParams {
-  const char* lvl_base[4];      // level l: address of (camera row 0, pixel 0, slice 0, channel 0)
-  long long slice_stride;       // bytes between slices
-  const int* hdr;
-  const uint2* pair;
-  const int32_t* order;
-  float* agg;                   // (BQ, HH, 256)
-  int BQ, per_xcd, cap_t;
-  int slice_lo, slice_n;        // slices [slice_lo, slice_lo + slice_n) in this launch
-  int blk;                      // queries per block of the walk: within an XCD, block-major, then slice, then query
-};
-
-typedef float f2v __attribute__((ext_vector_type(2)));
-
-// (the walk: which (position, phase) workgroup `block` is; false: none.  A phase is one of the launch's slice_n slices - in
-//  gd4d_cross_attn_agg_items_coarse_fwd one of its 8 / NS groups of NS consecutive slices, then the projected rows' phase.  Host
-//  and device: gd4d_gather_walk runs it without a GPU)
-__host__ __device__ __forceinline__ bool sliced_walk(const SlicedParams& p, int block, int& pos, int& sl) {
-  const int xcd = block & 7, jb = block >> 3;
-  const int per_blk = p.blk * p.slice_n;                   // workgroups of one block of queries
-  const int kb = jb / per_blk, rb = jb - kb * per_blk;
-  sl = rb / p.blk;
-  const int qi = kb * p.blk + (rb - sl * p.blk);
-  pos = xcd * p.per_xcd + qi;
-  return qi < p.per_xcd && pos < p.BQ;
-}
+// load, two packed FMAs.  (SlicedParams, the walk, the pass and the corner-slot sum: gd4d_cross_attn_sliced.h.)
 
 // The walk with a direction (gd4d_cross_attn_agg_items_coarse_fwd with GD4D_GATHER_REVERSED).  Reversed, every phase but the last is walked from the back - the
 // slice groups from last to first, the projected rows' short phase still closing the tail - so that a launch starts on the planes the
@@ -287,9 +261,7 @@ __host__ __device__ __forceinline__ bool sliced_walk_dir(const SlicedParams& p, 
 template <int HH, int LT, typename VT>
 __device__ __forceinline__ void cross_attn_agg_sliced_body(const SlicedParams& p, const int pos, const int sl, char* s_raw) {
   constexpr int ES = sizeof(VT);
-  constexpr int CH = 6;                                   // passes staged per round (30 KB per workgroup: 4 per CU)
-  constexpr int GP = 80;                                  // LDS bytes per corner slot: 64 B of pairs + 16 B pad (conflict-free b128)
-  constexpr int PASS = 8 * GP;
+  constexpr int CH = kPairsCH, GP = kPatchGP, PASS = kPatchPass;
   const int lane = threadIdx.x & 63;
   const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int s = p.slice_lo + sl;
@@ -320,40 +292,9 @@ __device__ __forceinline__ void cross_attn_agg_sliced_body(const SlicedParams& p
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                 // wave-private LDS patch: no workgroup barrier
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int k = 0; k < nt; ++k) {
-      const uint4* row = reinterpret_cast<const uint4*>(rd + k * PASS);
-      uint4 pr[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) pr[i] = row[i];                          // pairs j = 2 i, 2 i + 1: {off, w, off, w}
-      const bool second = (t0 + k) * 4 + 2 < M;                            // wave-uniform: items 2, 3 of the pass exist
-      float4 val[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if ((j & 3) >= LT) continue;
-        if (j >= 4 && !second) break;
-        const unsigned o = ((j & 1) ? pr[j >> 1].z : pr[j >> 1].x) + lane_off;
-        const VT* ap = reinterpret_cast<const VT*>(base[j & 3] + o);
-        val[j] = Quad<VT>::load(ap);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if ((j & 3) >= LT) continue;
-        if (j >= 4 && !second) break;
-        const float w = __uint_as_float((j & 1) ? pr[j >> 1].w : pr[j >> 1].y);
-        const f2v ww = {w, w};
-        acc0 = __builtin_elementwise_fma(ww, f2v{val[j].x, val[j].y}, acc0);
-        acc1 = __builtin_elementwise_fma(ww, f2v{val[j].z, val[j].w}, acc1);
-      }
-    }
+    for (int k = 0; k < nt; ++k) gather_pass<LT, 4, VT, false>(rd + k * PASS, base, lane_off, M - (t0 + k) * 4, acc0, acc1);
   }
-  float4 acc = make_float4(acc0.x, acc0.y, acc1.x, acc1.y);
-  // the 8 corner slots meet in a fixed order (deterministic)
-#pragma unroll
-  for (int o = 8; o < 64; o <<= 1) {
-    acc.x += __shfl_xor(acc.x, o); acc.y += __shfl_xor(acc.y, o);
-    acc.z += __shfl_xor(acc.z, o); acc.w += __shfl_xor(acc.w, o);
-  }
+  const float4 acc = sum_corner_slots(acc0, acc1);
   if (g == 0) *reinterpret_cast<float4*>(p.agg + ((size_t)bq * HH + h) * kChannels + s * kSlice + c * 4) = acc;
 }
 
@@ -402,9 +343,6 @@ struct ItemsParams {
 // and parked once, then every slice of the group runs the step's passes from the patch - its own acc0 / acc1, its own base, the
 // same loads and FMAs in the same order, so a (query, head, slice) sums what it sums at NS = 1, bit for bit.  Still one pass in
 // flight per wave.
-#ifndef GD4D_GATHER_NOLOAD
-#define GD4D_GATHER_NOLOAD 0     // 1 (dev builds, timing only - results are wrong): no feature load, a value made of its offset instead
-#endif
 template <int HH, int LT, typename VT, bool WIDE, int LAP = 4, int LV0 = 0, bool COARSE = false, int NS = 1>
 __device__ __forceinline__ void cross_attn_agg_items_body(const ItemsParams& ip, const int pos, const int sl, char* s_raw) {
   const SlicedParams& p = ip.s;
@@ -417,8 +355,7 @@ __device__ __forceinline__ void cross_attn_agg_items_body(const ItemsParams& ip,
   constexpr int IPP = 16 / LAP;                           // items per pass: 4 (LAP = 2: 8)
   constexpr int IPS = 64 / LAP;                           // items per step (four passes): 16 (32)
   constexpr int CH = 4;                                   // passes per step (20 KB of LDS per workgroup of 8 waves)
-  constexpr int GP = 80;                                  // LDS bytes per corner slot: 64 B of pairs + 16 B pad (conflict-free b128)
-  constexpr int PASS = 8 * GP;
+  constexpr int GP = kPatchGP, PASS = kPatchPass;
   const int lane = threadIdx.x & 63;
   const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int s = COARSE ? h : p.slice_lo + sl;
@@ -451,12 +388,9 @@ __device__ __forceinline__ void cross_attn_agg_items_body(const ItemsParams& ip,
   const int M = __builtin_amdgcn_readfirstlane(__float_as_int(a.w));       // every record carries its head's count
   const int T = (M + IPP - 1) / IPP;
   const int m_even = (M + 1) & ~1;                                         // a load covers a PAIR of items: the odd one out is
-  f2v acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};                                // written with weight 0 (its line is in flight already)
-  f2v accn0[NS], accn1[NS];                                                // (NS > 1: the sums of slice s + n)
-  if constexpr (NS > 1) {
+  f2v acc0[NS], acc1[NS];                                                  // written with weight 0 (its line is in flight already)
 #pragma unroll
-    for (int n = 0; n < NS; ++n) { accn0[n] = f2v{0.f, 0.f}; accn1[n] = f2v{0.f, 0.f}; }
-  }
+  for (int n = 0; n < NS; ++n) { acc0[n] = f2v{0.f, 0.f}; acc1[n] = f2v{0.f, 0.f}; }   // (the sums of slice s + n)
   float wsum_lane = 0.f;
   if (M < IPS && M > 0) {                                                   // wave-uniform: items past M repeat the last one
     const int src = min(i_of, M - 1) * LAP + l_of;
@@ -497,106 +431,22 @@ __device__ __forceinline__ void cross_attn_agg_items_body(const ItemsParams& ip,
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const int t0 = it0 / IPP;
     const int nt = min(CH, T - t0);
-    if constexpr (NS == 1) {                                               // (kept as written: every NS = 1 kernel, the training
-      for (int k = 0; k < nt; ++k) {                                       //  gathers among them, compiles to the code it had)
-        const uint4* row = reinterpret_cast<const uint4*>(rd + k * PASS);
-        uint4 pr[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) pr[i] = row[i];                          // pairs j = 2 i, 2 i + 1: {off, w, off, w}
-        const int left = M - (t0 + k) * IPP;                                 // wave-uniform: items of this pass; load j's pair exists
-        float4 val[8];                                                       // while 2 (j / LAP) < left
+    for (int n = 0; n < NS; ++n) {                                           // (the next step's barrier follows the last slice's passes)
+      const char* bs[LA];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if ((j % LAP) >= LA) continue;
-          if (2 * (j / LAP) >= left) break;
-          const unsigned raw = (j & 1) ? pr[j >> 1].z : pr[j >> 1].x;
-          const unsigned o = raw + lane_off;
-          const VT* ap = WIDE ? reinterpret_cast<const VT*>(base[j % LAP] + (((size_t)raw << 4) + lane_off))
-                              : reinterpret_cast<const VT*>(base[j % LAP] + o);
-#if GD4D_GATHER_NOLOAD
-          val[j] = make_float4(__uint_as_float(o), 1.f, 2.f, 3.f); (void)ap;
-#else
-          val[j] = Quad<VT>::load(ap);
-#endif
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if ((j % LAP) >= LA) continue;
-          if (2 * (j / LAP) >= left) break;
-          const float w = __uint_as_float((j & 1) ? pr[j >> 1].w : pr[j >> 1].y);
-          const f2v ww = {w, w};
-          acc0 = __builtin_elementwise_fma(ww, f2v{val[j].x, val[j].y}, acc0);
-          acc1 = __builtin_elementwise_fma(ww, f2v{val[j].z, val[j].w}, acc1);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int n = 0; n < NS; ++n) {                                         // (the next step's barrier follows the last slice's passes)
-        const char* bs[LA];
-#pragma unroll
-        for (int l = 0; l < LA; ++l) bs[l] = base[l] + (size_t)n * p.slice_stride;
-        for (int k = 0; k < nt; ++k) {
-          const uint4* row = reinterpret_cast<const uint4*>(rd + k * PASS);
-          uint4 pr[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) pr[i] = row[i];                        // pairs j = 2 i, 2 i + 1: {off, w, off, w}
-          const int left = M - (t0 + k) * IPP;                               // wave-uniform: items of this pass; load j's pair exists
-          float4 val[8];                                                     // while 2 (j / LAP) < left
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            if ((j % LAP) >= LA) continue;
-            if (2 * (j / LAP) >= left) break;
-            const unsigned raw = (j & 1) ? pr[j >> 1].z : pr[j >> 1].x;
-            const unsigned o = raw + lane_off;
-            const VT* ap = WIDE ? reinterpret_cast<const VT*>(bs[j % LAP] + (((size_t)raw << 4) + lane_off))
-                                : reinterpret_cast<const VT*>(bs[j % LAP] + o);
-#if GD4D_GATHER_NOLOAD
-            val[j] = make_float4(__uint_as_float(o), 1.f, 2.f, 3.f); (void)ap;
-#else
-            val[j] = Quad<VT>::load(ap);
-#endif
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            if ((j % LAP) >= LA) continue;
-            if (2 * (j / LAP) >= left) break;
-            const float w = __uint_as_float((j & 1) ? pr[j >> 1].w : pr[j >> 1].y);
-            const f2v ww = {w, w};
-            accn0[n] = __builtin_elementwise_fma(ww, f2v{val[j].x, val[j].y}, accn0[n]);
-            accn1[n] = __builtin_elementwise_fma(ww, f2v{val[j].z, val[j].w}, accn1[n]);
-          }
-        }
-      }
+      for (int l = 0; l < LA; ++l) bs[l] = base[l] + (size_t)n * p.slice_stride;
+      for (int k = 0; k < nt; ++k)
+        gather_pass<LA, LAP, VT, WIDE>(rd + k * PASS, bs, lane_off, M - (t0 + k) * IPP, acc0[n], acc1[n]);
     }
   }
-  if constexpr (NS == 1) {
-    float4 acc = make_float4(acc0.x, acc0.y, acc1.x, acc1.y);
-    // the 8 corner slots meet in a fixed order (deterministic)
 #pragma unroll
-    for (int o = 8; o < 64; o <<= 1) {
-      acc.x += __shfl_xor(acc.x, o); acc.y += __shfl_xor(acc.y, o);
-      acc.z += __shfl_xor(acc.z, o); acc.w += __shfl_xor(acc.w, o);
-    }
-    if (COARSE) {
-      if (g == 0) *reinterpret_cast<float4*>(ip.pagg + (size_t)bq * kChannels + h * kSlice + c * 4) = acc;
-      return;
-    }
-    if (g == 0) *reinterpret_cast<float4*>(p.agg + ((size_t)bq * HH + h) * kChannels + s * kSlice + c * 4) = acc;
-  } else {
-#pragma unroll
-    for (int n = 0; n < NS; ++n) {
-      float4 acc = make_float4(accn0[n].x, accn0[n].y, accn1[n].x, accn1[n].y);
-#pragma unroll
-      for (int o = 8; o < 64; o <<= 1) {
-        acc.x += __shfl_xor(acc.x, o); acc.y += __shfl_xor(acc.y, o);
-        acc.z += __shfl_xor(acc.z, o); acc.w += __shfl_xor(acc.w, o);
-      }
-      if (g == 0) *reinterpret_cast<float4*>(p.agg + ((size_t)bq * HH + h) * kChannels + (s + n) * kSlice + c * 4) = acc;
-    }
+  for (int n = 0; n < NS; ++n) {
+    const float4 acc = sum_corner_slots(acc0[n], acc1[n]);
+    float* out = COARSE ? ip.pagg + (size_t)bq * kChannels + h * kSlice : p.agg + ((size_t)bq * HH + h) * kChannels + (s + n) * kSlice;
+    if (g == 0) *reinterpret_cast<float4*>(out + c * 4) = acc;
   }
-  if (s == 0 && ip.wsum) {                                                 // wave-uniform: the group that holds slice 0
+  if (!COARSE && s == 0 && ip.wsum) {                                      // wave-uniform: the group that holds slice 0
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) wsum_lane += __shfl_xor(wsum_lane, o);
     if (lane == 0) ip.wsum[(size_t)bq * HH + h] = wsum_lane;
@@ -903,54 +753,7 @@ static int g_gather_ns = GD4D_GATHER_SLICE_GROUP;
 // 2 waves per SIMD: 6 = three workgroups per CU, 4 = two, 2 = one)
 constexpr int gather_occ(bool wide, int ns) { return wide ? (ns > 4 ? 2 : 4) : (ns > 2 ? 4 : 6); }
 
-template <int HH, typename VT>
-static int launch_sliced(const SlicedParams& p, int L, hipStream_t s) {
-  const size_t lds = (size_t)HH * 6 * 8 * 80;                       // [HH][CH][8][GP]
-  const dim3 grid(gather_grid(p.per_xcd, p.blk, p.slice_n));
-  auto go = [&](auto kern) -> int {
-    if (lds > 65536 && !allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return GD4D_ELAUNCH;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * HH), lds, s, p);
-    return check_launch();
-  };
-  constexpr int OCC = HH == 16 ? 4 : 6;                             // waves per SIMD
-  switch (L) {
-    case 1: return go(cross_attn_agg_sliced_kernel<HH, 1, VT, OCC>);
-    case 2: return go(cross_attn_agg_sliced_kernel<HH, 2, VT, OCC>);
-    case 3: return go(cross_attn_agg_sliced_kernel<HH, 3, VT, OCC>);
-    default: return go(cross_attn_agg_sliced_kernel<HH, 4, VT, OCC>);
-  }
-}
-}  // namespace gd4d
-
-namespace gd4d {
-static int fill_sliced_params(SlicedParams& p, const void* const* level_ptrs, int64_t slice_stride_bytes, const void* plan, float* agg,
-                              int B, int N, int Q, int Hh, int C, int L, int P, int feats_dtype, const int32_t* query_order,
-                              int slice_lo, int slice_n) {
-  if (!level_ptrs || !plan || !agg) return GD4D_EINVAL;
-  if (B <= 0 || N <= 0 || Q <= 0 || Hh <= 0 || L <= 0) return GD4D_EINVAL;
-  if (C != kChannels || (P != 1 && P != 2 && P != 4 && P != 8) || (P != kPoints && Hh != 8) || L > 4 || N > 64 || B > 16)
-    return GD4D_EUNSUPPORTED;
-  if (feats_dtype != GD4D_F32 && feats_dtype != GD4D_BF16) return GD4D_EUNSUPPORTED;
-  if (Hh != 4 && Hh != 8 && Hh != 16) return GD4D_EUNSUPPORTED;
-  if (slice_lo < 0 || slice_n <= 0 || slice_lo + slice_n > kSlices) return GD4D_EINVAL;
-  if (!aligned16(agg) || !aligned16(plan)) return GD4D_EALIGN;
-  const int es = feats_dtype == GD4D_BF16 ? 2 : 4;
-  if (slice_stride_bytes % (4 * es)) return GD4D_EALIGN;
-  for (int l = 0; l < L; ++l) {
-    if (!level_ptrs[l]) return GD4D_EINVAL;
-    if (reinterpret_cast<uintptr_t>(level_ptrs[l]) % (4 * es)) return GD4D_EALIGN;
-    p.lvl_base[l] = static_cast<const char*>(level_ptrs[l]);
-  }
-  for (int l = L; l < 4; ++l) p.lvl_base[l] = p.lvl_base[0];
-  p.slice_stride = slice_stride_bytes;
-  p.hdr = static_cast<const int*>(plan);
-  p.pair = reinterpret_cast<const uint2*>(static_cast<const char*>(plan) + plan_hdr_bytes(B, Q));
-  p.order = query_order; p.agg = agg;
-  p.BQ = B * Q; p.per_xcd = (B * Q + 7) / 8; p.cap_t = plan_cap_t(N, P);
-  p.slice_lo = slice_lo; p.slice_n = slice_n;
-  p.blk = p.per_xcd;                                // one block = the XCD's whole sector: plain slice-major
-  return GD4D_OK;
-}
+constexpr int sliced_occ(int hh) { return hh == 16 ? 4 : 6; }       // waves per SIMD of the single-slice kernels
 }  // namespace gd4d
 
 extern "C" int gd4d_cross_attn_agg_sliced_fwd(const void* const* level_ptrs, int64_t slice_stride_bytes, const void* plan,
@@ -962,50 +765,43 @@ extern "C" int gd4d_cross_attn_agg_sliced_fwd(const void* const* level_ptrs, int
                                   slice_n))
     return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool bf16 = feats_dtype == GD4D_BF16;
-  switch (Hh) {
-    case 4: return bf16 ? launch_sliced<4, uint16_t>(p, L, s) : launch_sliced<4, float>(p, L, s);
-    case 8: return bf16 ? launch_sliced<8, uint16_t>(p, L, s) : launch_sliced<8, float>(p, L, s);
-    default: return bf16 ? launch_sliced<16, uint16_t>(p, L, s) : launch_sliced<16, float>(p, L, s);
-  }
+  const dim3 grid(gather_grid(p.per_xcd, p.blk, p.slice_n));
+  return dispatch_sliced(Hh, feats_dtype == GD4D_BF16, L, [&](auto hh, auto vt, auto lt) -> int {
+    constexpr int HH = decltype(hh)::value, LT = decltype(lt)::value;
+    auto kern = cross_attn_agg_sliced_kernel<HH, LT, decltype(vt), sliced_occ(HH)>;
+    const size_t lds = (size_t)HH * 6 * 8 * 80;                     // [HH][CH][8][GP]
+    if (lds > 65536 && !allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return GD4D_ELAUNCH;
+    hipLaunchKernelGGL(kern, grid, dim3(64 * HH), lds, s, p);
+    return check_launch();
+  });
 }
 
 namespace gd4d {
-template <int HH, typename VT>
-static int launch_items(const ItemsParams& ip, int L, bool wide, hipStream_t s, CountArgs* ca = nullptr) {
+static int launch_items(const ItemsParams& ip, int Hh, bool bf16, int L, bool wide, hipStream_t s, CountArgs* ca = nullptr) {
   const SlicedParams& p = ip.s;
-  const size_t lds = (size_t)HH * 4 * 8 * 80;                        // [HH][CH][8][GP]
   const dim3 grid(gather_grid(p.per_xcd, p.blk, p.slice_n));
   if (ca) {                                            // gather + record count in one launch (training forward)
-    if (HH != 8 || L != 4 || sizeof(VT) != 4 || wide) return GD4D_EUNSUPPORTED;
-    const int wgs = (ca->BQ * HH + HH - 1) / HH;       // a count workgroup = HH (position, head) waves
-    ca->groups = (wgs + 7) / 8;
+    if (Hh != 8 || bf16 || L != 4 || wide) return GD4D_EUNSUPPORTED;
+    ca->groups = (ca->BQ + 7) / 8;                     // a count workgroup = the 8 (position, head) waves of a position
     const int ggroups = (int)(grid.x / 8);
     ca->every = ggroups / ca->groups;
     if (ca->every < 1) return GD4D_EUNSUPPORTED;
-    hipLaunchKernelGGL((cross_attn_agg_items_count_kernel<8, 4, float, 6>), dim3(grid.x + 8 * ca->groups), dim3(64 * 8), lds, s, ip, *ca);
+    hipLaunchKernelGGL((cross_attn_agg_items_count_kernel<8, 4, float, 6>), dim3(grid.x + 8 * ca->groups), dim3(64 * 8),
+                       (size_t)8 * 4 * 8 * 80, s, ip, *ca);
     return check_launch();
   }
-  auto go = [&](auto kern) -> int {
-    if (lds > 65536 && !allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return GD4D_ELAUNCH;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * HH), lds, s, ip);
-    return check_launch();
-  };
-  constexpr int OCC = HH == 16 ? 4 : 6;                             // waves per SIMD
-  if (wide) {                                                       // (a 64-bit address per load: 4 waves per SIMD, no spills)
-    switch (L) {
-      case 1: return go(cross_attn_agg_items_kernel<HH, 1, VT, 4, true>);
-      case 2: return go(cross_attn_agg_items_kernel<HH, 2, VT, 4, true>);
-      case 3: return go(cross_attn_agg_items_kernel<HH, 3, VT, 4, true>);
-      default: return go(cross_attn_agg_items_kernel<HH, 4, VT, 4, true>);
-    }
-  }
-  switch (L) {
-    case 1: return go(cross_attn_agg_items_kernel<HH, 1, VT, OCC>);
-    case 2: return go(cross_attn_agg_items_kernel<HH, 2, VT, OCC>);
-    case 3: return go(cross_attn_agg_items_kernel<HH, 3, VT, OCC>);
-    default: return go(cross_attn_agg_items_kernel<HH, 4, VT, OCC>);
-  }
+  return dispatch_sliced(Hh, bf16, L, [&](auto hh, auto vt, auto lt) -> int {
+    constexpr int HH = decltype(hh)::value, LT = decltype(lt)::value;
+    using VT = decltype(vt);
+    const size_t lds = (size_t)HH * 4 * 8 * 80;                      // [HH][CH][8][GP]
+    auto go = [&](auto kern) -> int {
+      if (lds > 65536 && !allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return GD4D_ELAUNCH;
+      hipLaunchKernelGGL(kern, grid, dim3(64 * HH), lds, s, ip);
+      return check_launch();
+    };
+    // (wide: a 64-bit address per load: 4 waves per SIMD, no spills)
+    return wide ? go(cross_attn_agg_items_kernel<HH, LT, VT, 4, true>) : go(cross_attn_agg_items_kernel<HH, LT, VT, sliced_occ(HH)>);
+  });
 }
 
 // geometry of an items-form gather: 32-bit offsets inside a level - bytes while every level spans < 4 GiB, units of 16 bytes
@@ -1053,14 +849,7 @@ static int items_fwd_impl(const void* const* level_ptrs, const int32_t* level_hw
   ip.item = reinterpret_cast<const float4*>(ip.s.pair);
   ip.wsum = wsum;
   ip.cap_i = plan_cap_items(N, P);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool bf16 = feats_dtype == GD4D_BF16;
-  if (ca) return (Hh == 8 && !bf16) ? launch_items<8, float>(ip, L, wide, s, ca) : GD4D_EUNSUPPORTED;
-  switch (Hh) {
-    case 4: return bf16 ? launch_items<4, uint16_t>(ip, L, wide, s) : launch_items<4, float>(ip, L, wide, s);
-    case 8: return bf16 ? launch_items<8, uint16_t>(ip, L, wide, s) : launch_items<8, float>(ip, L, wide, s);
-    default: return bf16 ? launch_items<16, uint16_t>(ip, L, wide, s) : launch_items<16, float>(ip, L, wide, s);
-  }
+  return launch_items(ip, Hh, feats_dtype == GD4D_BF16, L, wide, static_cast<hipStream_t>(stream), ca);
 }
 
 extern "C" int gd4d_cross_attn_agg_items_fwd(const void* const* level_ptrs, const int32_t* level_hw, const int64_t* cam_stride_bytes,

@@ -193,29 +193,22 @@ __device__ __forceinline__ void value_proj_heads_bwd_weight_sum_body(const float
 // (g, c) with 8 four-channel products (j = 0..7); a transposing butterfly over the 8 lanes of a corner slot (7 shuffles
 // instead of 24) leaves lane (g, c) the sum for j = c.  One coalesced 256-byte store per pass and slice.
 struct DotParams {
-  const char* lvl_base[4];
-  long long slice_stride;
-  const int* hdr;
-  const uint2* pair;
-  const int32_t* order;
-  const float* gagg;        // (BQ, HH, 256) dL/d agg
+  SlicedParams s;           // s.agg: (BQ, HH, 256) dL/d agg, read; all 8 slices, one block per XCD
   float* dpart;             // [kSlices][BQ * HH * cap_t * 64]
   long long dslice;         // floats per slice of dpart
-  int BQ, per_xcd, cap_t;
 };
 
 template <int HH, int LT, typename VT>
-__device__ __forceinline__ void cross_attn_dot_sliced_body(const DotParams& p, const int bid, char* s_raw) {   // s_raw: [HH][CH][8][GP]
-  constexpr int CH = 6, GP = 80, PASS = 8 * GP, ES = sizeof(VT);
+__device__ __forceinline__ void cross_attn_dot_sliced_body(const DotParams& dp_, const int bid, char* s_raw) {   // s_raw: [HH][CH][8][GP]
+  const SlicedParams& p = dp_.s;
+  constexpr int CH = kPairsCH, GP = kPatchGP, PASS = kPatchPass, ES = sizeof(VT);
   const int lane = threadIdx.x & 63;
   const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int xcd = bid & 7, jb = bid >> 3;
-  const int s = jb / p.per_xcd, qi = jb - s * p.per_xcd;
-  const int pos = xcd * p.per_xcd + qi;
-  if (pos >= p.BQ) return;
+  int pos, s;                                             // (slice_lo = 0: the walk's phase is the slice)
+  if (!sliced_walk(p, bid, pos, s)) return;
   const size_t prow = ((size_t)pos * HH + h) * p.cap_t * 64 + lane;
   const uint2* pp = p.pair + prow;
-  float* dp = p.dpart + (size_t)s * p.dslice + prow;
+  float* dp = dp_.dpart + (size_t)s * dp_.dslice + prow;
   const uint2 first = pp[0];
   const int M = __builtin_amdgcn_readfirstlane(p.hdr[pos * kPlanHdr + h]);
   const int bq = p.order ? p.order[pos] : pos;
@@ -228,7 +221,7 @@ __device__ __forceinline__ void cross_attn_dot_sliced_body(const DotParams& p, c
 #pragma unroll
   for (int l = 0; l < LT; ++l) base[l] = p.lvl_base[l] + (size_t)s * p.slice_stride;
   const unsigned lane_off = (unsigned)(c * 4 * ES);
-  const float4 ga = *reinterpret_cast<const float4*>(p.gagg + ((size_t)bq * HH + h) * kChannels + s * kSlice + c * 4);
+  const float4 ga = *reinterpret_cast<const float4*>(p.agg + ((size_t)bq * HH + h) * kChannels + s * kSlice + c * 4);
   const bool b4 = c & 4, b2 = c & 2, b1 = c & 1;
 
   for (int t0 = 0; t0 < T; t0 += CH) {
@@ -1024,59 +1017,34 @@ static int dot_sliced_impl(const void* const* level_ptrs, int64_t slice_stride_b
                           const float* grad_agg, void* dpart, size_t dpart_bytes, int B, int N, int Q, int Hh,
                           int C, int L, int P, int feats_dtype, const int32_t* query_order, void* stream, gd4d::WgradGuest* wg) {
   using namespace gd4d;
-  if (!level_ptrs || !plan || !grad_agg || !dpart) return GD4D_EINVAL;
-  if (B <= 0 || N <= 0 || Q <= 0 || Hh <= 0 || L <= 0) return GD4D_EINVAL;
-  if (C != kChannels || (P != kPoints && P != 8) || L > 4 || N > 64 || B > 16) return GD4D_EUNSUPPORTED;    // (P only sizes the plan)
-  if (feats_dtype != GD4D_F32 && feats_dtype != GD4D_BF16) return GD4D_EUNSUPPORTED;
-  if (Hh != 4 && Hh != 8 && Hh != 16) return GD4D_EUNSUPPORTED;
-  const int es = feats_dtype == GD4D_BF16 ? 2 : 4;
-  if (!aligned16(grad_agg) || !aligned16(plan) || slice_stride_bytes % (4 * es)) return GD4D_EALIGN;
-  if (dpart_bytes < gd4d_cross_attn_dot_bytes(B, N, Q, Hh, P)) return GD4D_EWORKSPACE;
-  DotParams p{};
-  for (int l = 0; l < L; ++l) {
-    if (!level_ptrs[l]) return GD4D_EINVAL;
-    if (reinterpret_cast<uintptr_t>(level_ptrs[l]) % (4 * es)) return GD4D_EALIGN;
-    p.lvl_base[l] = static_cast<const char*>(level_ptrs[l]);
-  }
-  for (int l = L; l < 4; ++l) p.lvl_base[l] = p.lvl_base[0];
-  p.slice_stride = slice_stride_bytes;
-  p.hdr = static_cast<const int*>(plan);
-  p.pair = reinterpret_cast<const uint2*>(static_cast<const char*>(plan) + plan_hdr_bytes(B, Q));
-  p.order = query_order; p.gagg = grad_agg;
-  p.dpart = static_cast<float*>(dpart);
-  p.BQ = B * Q; p.per_xcd = (B * Q + 7) / 8; p.cap_t = plan_cap_t(N, P);
-  p.dslice = (long long)B * Q * Hh * p.cap_t * 64;
+  if (!dpart) return GD4D_EINVAL;
+  DotParams dp{};
+  SlicedParams& p = dp.s;
+  // (P only sizes the plan here: 4 or 8)
+  if (int rc = fill_sliced_params(p, level_ptrs, slice_stride_bytes, plan, const_cast<float*>(grad_agg), B, N, Q, Hh, C, L, P, feats_dtype,
+                                  query_order, 0, kSlices, true, dpart_bytes >= gd4d_cross_attn_dot_bytes(B, N, Q, Hh, P)))
+    return rc;
+  dp.dpart = static_cast<float*>(dpart);
+  dp.dslice = (long long)B * Q * Hh * p.cap_t * 64;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(8 * p.per_xcd * kSlices);
   if (wg) {                                              // queued weight gradients ride along
     if (Hh != 8 || L != 4 || feats_dtype != GD4D_F32) return GD4D_EUNSUPPORTED;
     wg->guest_groups = (wg->tiles + 7) / 8;
     wg->total_groups = (int)(grid.x / 8) + wg->guest_groups;
-    wg->p = p;
+    wg->p = dp;
     hipLaunchKernelGGL((cross_attn_dot_sliced_wgrad_kernel<8, 4, float, 6>), dim3(8 * wg->total_groups), dim3(64 * 8),
                        (size_t)8 * 6 * 8 * 80, s, *wg);
     return check_launch();
   }
-  auto go = [&](auto kern, int hh) -> int {
-    const size_t lds = (size_t)hh * 6 * 8 * 80;
+  return dispatch_sliced(Hh, feats_dtype == GD4D_BF16, L, [&](auto hh, auto vt, auto lt) -> int {
+    constexpr int HH = decltype(hh)::value, LT = decltype(lt)::value;
+    auto kern = cross_attn_dot_sliced_kernel<HH, LT, decltype(vt), (HH == 16 ? 4 : 6)>;
+    const size_t lds = (size_t)HH * 6 * 8 * 80;
     if (lds > 65536 && !allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds)) return GD4D_ELAUNCH;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * hh), lds, s, p);
+    hipLaunchKernelGGL(kern, grid, dim3(64 * HH), lds, s, dp);
     return check_launch();
-  };
-#define GD4D_DOT_L(HH_, VT_, OCC_)                                                  \
-  switch (L) {                                                                      \
-    case 1: return go(cross_attn_dot_sliced_kernel<HH_, 1, VT_, OCC_>, HH_);        \
-    case 2: return go(cross_attn_dot_sliced_kernel<HH_, 2, VT_, OCC_>, HH_);        \
-    case 3: return go(cross_attn_dot_sliced_kernel<HH_, 3, VT_, OCC_>, HH_);        \
-    default: return go(cross_attn_dot_sliced_kernel<HH_, 4, VT_, OCC_>, HH_);       \
-  }
-  const bool bf16 = feats_dtype == GD4D_BF16;
-  switch (Hh) {
-    case 4: if (bf16) { GD4D_DOT_L(4, uint16_t, 6) } else { GD4D_DOT_L(4, float, 6) }
-    case 8: if (bf16) { GD4D_DOT_L(8, uint16_t, 6) } else { GD4D_DOT_L(8, float, 6) }
-    default: if (bf16) { GD4D_DOT_L(16, uint16_t, 4) } else { GD4D_DOT_L(16, float, 4) }
-  }
-#undef GD4D_DOT_L
+  });
 }
 
 extern "C" int gd4d_cross_attn_dot_sliced(const void* const* level_ptrs, int64_t slice_stride_bytes, const void* plan,
