@@ -62,6 +62,15 @@ __device__ __forceinline__ float half_wave_sum(float s) {
   return s;
 }
 
+// the sum over the WIDTH lanes of an aligned lane group, widest exchange first: every lane of the group gets the same bits
+template <int WIDTH>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int o = WIDTH / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) { return group_sum<GD4D_WAVE>(v); }
+
 // inverse_sigmoid of the reference (deform3d_cross_attn.py:16-31), eps = 1e-5
 __device__ __forceinline__ float inv_sigmoid(float x) {
   x = fminf(fmaxf(x, 0.f), 1.f);

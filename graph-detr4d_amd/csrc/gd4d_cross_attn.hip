@@ -63,17 +63,8 @@ void cross_attn_fwd_block(const CrossAttnParams p) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // Workgroup i runs on XCD i % 8 (round-robin dispatch), each XCD with a private L2.  With a locality order of the
-  // queries every XCD takes a contiguous range of it, so queries that look at the same camera region share an L2.
-  int bq = blockIdx.x;
-  if (p.order) {
-    const int per_xcd = (p.B * p.Q + 7) >> 3;
-    const int pos = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if ((int)(blockIdx.x >> 3) >= per_xcd || pos >= p.B * p.Q) return;
-    bq = p.order[pos];
-  } else if (bq >= p.B * p.Q) {
-    return;
-  }
+  int bq;
+  if (!query_of_block<false>(p.order, p.B * p.Q, bq)) return;
   const int b = bq / p.Q;
   const int q = bq - b * p.Q;
   const int L = LT > 0 ? LT : p.L;
@@ -84,52 +75,18 @@ void cross_attn_fwd_block(const CrossAttnParams p) {
   // a thread's 3-D point (its (head, point) never changes between its entries) is formed once, and the per-head softmax is
   // computed by HH x (L * PT) threads with cross-lane reductions instead of HH threads looping (11 us -> 4 us of 40).
   float* s_mat = s_aw + HH * (LMAX * PT);          // [N][12]: rows 0-2 of lidar2img
-  for (int i = tid; i < p.N * 12; i += THREADS) s_mat[i] = p.lidar2img[((size_t)b * p.N + i / 12) * 16 + i % 12];
-  if (!BMULTI) {                                   // softmax over L * PT logits per head, one thread per logit
+  stage_matrices<THREADS>(p, b, s_mat);
+  if (!BMULTI) {                                   // softmax over L * PT logits per head
     constexpr int LP = LMAX * PT;                  // <= 32 for the compiled shapes with LT > 0
     const int n_lp = L * PT;
-    if (LT > 0 && (LP & (LP - 1)) == 0 && LP <= 32) {
-      // LP is a power of two: head = tid / LP, groups of LP lanes reduce with xor shuffles
-      if (tid < HH * LP) {
-        const int hd = tid / LP, i = tid % LP;
-        const float x = p.attn_logits[((size_t)bq * HH + hd) * n_lp + i];
-        float mx = x;
-#pragma unroll
-        for (int o = 1; o < LP; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-        const float e = expf(x - mx);
-        float sum = e;
-#pragma unroll
-        for (int o = 1; o < LP; o <<= 1) sum += __shfl_xor(sum, o);
-        s_aw[hd * LP + i] = e * (1.0f / sum);
-      }
-    } else if (tid < HH) {                         // other shapes: one thread per head
-      float w[LP];
-      softmax_lp(p.attn_logits + ((size_t)bq * HH + tid) * n_lp, n_lp, w);
-      for (int i = 0; i < n_lp; ++i) s_aw[tid * LP + i] = w[i];
-    }
+    // LP a power of two: one thread per logit; other shapes: one thread per head
+    head_softmax_to_lds<HH, LP, (LT > 0 && softmax_can_shuffle(LP)), THREADS>(p.attn_logits + (size_t)bq * HH * n_lp, 0, 1, n_lp, s_aw);
   }
   __syncthreads();
   {
-    const int total = p.N * E;
-    static_assert(E <= GD4D_WAVE && GD4D_WAVE % E == 0 && THREADS % E == 0, "a thread keeps its (head, point)");
-    const int hp = tid % E;
-    const float* rp = p.ref + (size_t)bq * 3;
-    const float* offs = p.offsets + ((size_t)bq * E + hp) * 3;
-    const float X = (rp[0] * p.rng_scale[0] + p.rng_lo[0]) + offs[0];     // two roundings, then the offset (:222-229)
-    const float Y = (rp[1] * p.rng_scale[1] + p.rng_lo[1]) + offs[1];
-    const float Z = (rp[2] * p.rng_scale[2] + p.rng_lo[2]) + offs[2];
-    for (int e0 = wave * GD4D_WAVE; e0 < total; e0 += THREADS) {
-      const int e = e0 + lane;
-      bool vis = false;
-      if (e < total) {
-        const int n = e / E;
-        float u, v;
-        vis = project_entry(p, s_mat + n * 12, X, Y, Z, u, v);
-        s_uv[e] = vis ? make_float2(u, v) : make_float2(-1.f, -1.f);
-        const size_t o = (((size_t)b * p.N + n) * p.Q + q) * E + hp;
-        if (p.mask_out) p.mask_out[o] = vis ? 1 : 0;
-        if (p.uv_out) { p.uv_out[o * 2] = u; p.uv_out[o * 2 + 1] = v; }
-      }
+    float X, Y, Z;
+    query_point<E>(p, bq, tid % E, X, Y, Z);
+    project_query<E, THREADS>(p, b, q, s_mat, s_uv, X, Y, Z, [&](int e0, bool vis) {
       // per-camera "any point of any head visible": E consecutive entries belong to one camera
       const unsigned long long bal = __ballot(vis);
       constexpr int CPW = GD4D_WAVE / E;          // whole cameras covered by one wave iteration
@@ -138,7 +95,7 @@ void cross_attn_fwd_block(const CrossAttnParams p) {
         const unsigned long long ones = E == 64 ? ~0ull : ((1ull << (E & 63)) - 1ull);
         if (n < p.N) s_camvis[n] = (bal & (ones << (lane * (E & 63)))) ? 1 : 0;
       }
-    }
+    });
   }
   __syncthreads();
 
@@ -174,8 +131,7 @@ void cross_attn_fwd_block(const CrossAttnParams p) {
       const int bb = row % p.B;
       softmax_lp(p.attn_logits + (((size_t)bb * p.Q + q) * HH + h) * L * PT, L * PT, aw_reg);
     }
-    const float cl = p.cam_logits[(size_t)b * p.Q * p.N + (size_t)n * p.Q + q];
-    const float cw = p.raw_cam ? cl : 1.0f / (1.0f + expf(-cl));
+    const float cw = camera_weight(p, camera_logit(p, b, q, n));
     const VT* vrow = static_cast<const VT*>(p.value) + (size_t)row * p.S * kChannels;   // wave-uniform
     // pixel stride / lane offset of the two layouts (elements)
     const unsigned pix_stride = p.head_major ? (unsigned)DH : (unsigned)kChannels;
@@ -198,17 +154,14 @@ void cross_attn_fwd_block(const CrossAttnParams p) {
       for (int l = 0; l < LMAX; ++l) {
         if (LT == 0 && l >= L) break;
         const int W = p.lvl_w[l], H = p.lvl_h[l];
-        const float x = fmaf(u, (float)W, -0.5f);
-        const float y = fmaf(v, (float)H, -0.5f);
-        const float xf = floorf(x), yf = floorf(y);
-        fx[l] = x - xf; fy[l] = y - yf;
-        const int x0 = (int)xf, y0 = (int)yf;
-        const bool x0ok = x0 >= 0, x1ok = x0 + 1 < W;
-        const bool y0ok = y0 >= 0, y1ok = y0 + 1 < H;
-        okm |= ((x0ok ? 1u : 0u) | (x1ok ? 2u : 0u) | (y0ok ? 4u : 0u) | (y1ok ? 8u : 0u)) << (4 * l);
+        const BilinearCell cell(u, v, (float)W, (float)H);
+        fx[l] = cell.dx; fy[l] = cell.dy;
+        const int x0 = cell.x0, y0 = cell.y0;
+        const unsigned ok = cell.ok_bits(W, H);
+        okm |= ok << (4 * l);
         // corners outside the map contribute 0 (zero padding); their loads are clamped onto the map
-        const int xa = x0ok ? x0 : 0, xb = x1ok ? x0 + 1 : W - 1;
-        const int ya = y0ok ? y0 : 0, yb = y1ok ? y0 + 1 : H - 1;
+        const int xa = (ok & 1u) ? x0 : 0, xb = (ok & 2u) ? x0 + 1 : W - 1;
+        const int ya = (ok & 4u) ? y0 : 0, yb = (ok & 8u) ? y0 + 1 : H - 1;
         const unsigned r0 = (unsigned)(p.lvl_start[l] + ya * W), r1 = (unsigned)(p.lvl_start[l] + yb * W);
         off[l][0] = (r0 + xa) * pix_stride + lane_off;
         off[l][1] = (r0 + xb) * pix_stride + lane_off;
@@ -239,10 +192,10 @@ void cross_attn_fwd_block(const CrossAttnParams p) {
           const float wl = (BMULTI ? aw_reg[BMULTI ? l * PT + k : 0] : aw_lds[l * PT + k]) * cwk;
           const float dx = fx[l], dy = fy[l];
           const unsigned ok = okm >> (4 * l);
-          const float w00 = ((ok & 5u) == 5u) ? wl * (1.f - dx) * (1.f - dy) : 0.f;
-          const float w01 = ((ok & 6u) == 6u) ? wl * dx * (1.f - dy) : 0.f;
-          const float w10 = ((ok & 9u) == 9u) ? wl * (1.f - dx) * dy : 0.f;
-          const float w11 = ((ok & 10u) == 10u) ? wl * dx * dy : 0.f;
+          const float w00 = corner_ok(ok, 0) ? wl * (1.f - dx) * (1.f - dy) : 0.f;
+          const float w01 = corner_ok(ok, 1) ? wl * dx * (1.f - dy) : 0.f;
+          const float w10 = corner_ok(ok, 2) ? wl * (1.f - dx) * dy : 0.f;
+          const float w11 = corner_ok(ok, 3) ? wl * dx * dy : 0.f;
           const float wc[4] = {w00, w01, w10, w11};
 #pragma unroll
           for (int c = 0; c < 4; ++c) {

@@ -22,6 +22,7 @@
 // workspace; a second small kernel sums them over b in a fixed order and applies the softmax backward.  B == 1 keeps
 // everything in one kernel.  Supported: fp32 value, pixel-major layout.
 #include "gd4d_common.h"
+#include "gd4d_cross_attn_shared.h"
 
 namespace gd4d {
 
@@ -50,28 +51,17 @@ struct CrossAttnBwdParams {
   float img_h, img_w;
 };
 
-constexpr int kBP = 4;        // points per head
-constexpr int kBC = 256;      // channels
-
-// sum over the `width` lanes of an aligned lane group (width = lanes per head)
-template <int WIDTH>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = WIDTH / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 template <int HH, int LT, int WAVES, bool BMULTI>
 __global__ __launch_bounds__(GD4D_WAVE * WAVES) void cross_attn_bwd_block(const CrossAttnBwdParams p) {
-  constexpr int DH = kBC / HH;
+  constexpr int DH = kChannels / HH;
   constexpr int LPH = DH / 4;                     // lanes per head
-  constexpr int E = HH * kBP;
+  constexpr int E = HH * kPoints;
   constexpr int L = LT;
-  constexpr int LP = L * kBP;
+  constexpr int LP = L * kPoints;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   // [WAVES][HH][LP + 12] partial sums (attention-weight grads, point grads) | [N] camera visibility
   float* s_part = reinterpret_cast<float*>(smem_raw);
-  constexpr int PSTRIDE = LP + 3 * kBP;
+  constexpr int PSTRIDE = LP + 3 * kPoints;
   int* s_camvis = reinterpret_cast<int*>(s_part + WAVES * HH * PSTRIDE);
   float* s_pt = reinterpret_cast<float*>(s_camvis + 64);                   // [E][3] metre-space points
   float* s_gab = s_pt + E * 3;                                             // BMULTI: [WAVES][B][HH][LP] dL/d a per logit class
@@ -79,15 +69,8 @@ __global__ __launch_bounds__(GD4D_WAVE * WAVES) void cross_attn_bwd_block(const 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // with a locality order every XCD (workgroup i -> XCD i % 8) takes a contiguous range of it: the atomic adds into
-  // grad_value then meet in that XCD's L2 like the forward's reads do
-  int bq = blockIdx.x;
-  if (p.order) {
-    const int per_xcd = (p.B * p.Q + 7) >> 3;
-    const int pos = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if ((int)(blockIdx.x >> 3) >= per_xcd || pos >= p.B * p.Q) return;
-    bq = p.order[pos];
-  }
+  int bq;
+  if (!query_of_block<true>(p.order, p.B * p.Q, bq)) return;
   const int b = bq / p.Q;
   const int q = bq - b * p.Q;
   const int h = lane / LPH;
@@ -96,84 +79,58 @@ __global__ __launch_bounds__(GD4D_WAVE * WAVES) void cross_attn_bwd_block(const 
     for (int i = tid; i < WAVES * p.B * HH * LP; i += GD4D_WAVE * WAVES) s_gab[i] = 0.f;
 
   // metre-space sample points of this query (same arithmetic as the forward)
-  {
-    const float* rp = p.ref + (size_t)bq * 3;
-    const float* offs = p.offsets + (size_t)bq * E * 3;
-    for (int e = tid; e < E; e += GD4D_WAVE * WAVES) {
-      s_pt[3 * e + 0] = (rp[0] * p.rng_scale[0] + p.rng_lo[0]) + offs[3 * e + 0];
-      s_pt[3 * e + 1] = (rp[1] * p.rng_scale[1] + p.rng_lo[1]) + offs[3 * e + 1];
-      s_pt[3 * e + 2] = (rp[2] * p.rng_scale[2] + p.rng_lo[2]) + offs[3 * e + 2];
-    }
-  }
+  for (int e = tid; e < E; e += GD4D_WAVE * WAVES) query_point<E>(p, bq, e, s_pt[3 * e], s_pt[3 * e + 1], s_pt[3 * e + 2]);
   __syncthreads();
 
   // softmax weights of this lane's head (B > 1: of the logit class of each camera, recomputed per camera)
   float aw[LP];
-  auto softmax_of = [&](int bb) {
-    const float* lg = p.attn_logits + (((size_t)bb * p.Q + q) * HH + h) * LP;
-    float mx = lg[0];
-#pragma unroll
-    for (int i = 1; i < LP; ++i) mx = fmaxf(mx, lg[i]);
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < LP; ++i) { aw[i] = expf(lg[i] - mx); sum += aw[i]; }
-    const float inv = 1.0f / sum;
-#pragma unroll
-    for (int i = 0; i < LP; ++i) aw[i] *= inv;
-  };
+  auto softmax_of = [&](int bb) { softmax_lp(p.attn_logits + (((size_t)bb * p.Q + q) * HH + h) * LP, LP, aw); };
   if (!BMULTI) softmax_of(b);
-  const float4 g = *reinterpret_cast<const float4*>(p.grad_out + (size_t)bq * kBC + lane * 4);
+  const float4 g = *reinterpret_cast<const float4*>(p.grad_out + (size_t)bq * kChannels + lane * 4);
   // the same row again, lane-contiguous: channel 64 i + lane.  The atomic adds into grad_value use THIS mapping, so one
   // wave instruction covers whole 128-byte lines (64 consecutive channels of a pixel row) instead of 8 dwords in each
   // of 8 lines: a quarter of the L2 atomic requests.
   float gl4[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) gl4[i] = p.grad_out[(size_t)bq * kBC + 64 * i + lane];
+  for (int i = 0; i < 4; ++i) gl4[i] = p.grad_out[(size_t)bq * kChannels + 64 * i + lane];
 
   float ga[LP];                                    // dL/d a (before the softmax backward), this head
-  float gpt[kBP][3];                               // dL/d (metre point) of this head's points
+  float gpt[kPoints][3];                           // dL/d (metre point) of this head's points
 #pragma unroll
   for (int i = 0; i < LP; ++i) ga[i] = 0.f;
 #pragma unroll
-  for (int k = 0; k < kBP; ++k) { gpt[k][0] = gpt[k][1] = gpt[k][2] = 0.f; }
+  for (int k = 0; k < kPoints; ++k) { gpt[k][0] = gpt[k][1] = gpt[k][2] = 0.f; }
 
   for (int n = wave; n < p.N; n += WAVES) {        // cameras dealt to waves (all cameras: cheap skip below)
     const int row = b * p.N + n;
     const float* m = p.lidar2img + (size_t)row * 16;
-    float u[kBP], v[kBP], cxv[kBP], cyv[kBP], czv[kBP];
-    bool vis[kBP];
+    float u[kPoints], v[kPoints], cxv[kPoints], cyv[kPoints], czv[kPoints];
+    bool vis[kPoints];
     bool any = false;
 #pragma unroll
-    for (int k = 0; k < kBP; ++k) {
-      const float X = s_pt[3 * (h * kBP + k) + 0], Y = s_pt[3 * (h * kBP + k) + 1], Z = s_pt[3 * (h * kBP + k) + 2];
-      const float eps = 1e-5f;
-      cxv[k] = ((m[0] * X + m[1] * Y) + m[2] * Z) + m[3];
-      cyv[k] = ((m[4] * X + m[5] * Y) + m[6] * Z) + m[7];
-      czv[k] = ((m[8] * X + m[9] * Y) + m[10] * Z) + m[11];
-      const float zc = fmaxf(czv[k], eps);
-      u[k] = (cxv[k] / zc) / p.img_w;
-      v[k] = (cyv[k] / zc) / p.img_h;
-      vis[k] = czv[k] > eps && u[k] > 0.f && u[k] < 1.f && v[k] > 0.f && v[k] < 1.f;
+    for (int k = 0; k < kPoints; ++k) {
+      const float X = s_pt[3 * (h * kPoints + k) + 0], Y = s_pt[3 * (h * kPoints + k) + 1], Z = s_pt[3 * (h * kPoints + k) + 2];
+      project_camera(m, X, Y, Z, p.img_w, p.img_h, cxv[k], cyv[k], czv[k], u[k], v[k]);
+      vis[k] = in_image(czv[k], u[k], v[k]);
       any |= vis[k];
     }
     if (!__any(any)) {                              // nobody in this wave sees camera n
       if (lane == 0) p.grad_cam_logits[(size_t)b * p.Q * p.N + (size_t)n * p.Q + q] = 0.f;
       continue;
     }
-    const float cl = p.cam_logits[(size_t)b * p.Q * p.N + (size_t)n * p.Q + q];
-    const float cw = p.raw_cam ? cl : 1.0f / (1.0f + expf(-cl));
+    const float cw = camera_weight(p, camera_logit(p, b, q, n));
     const int bb = BMULTI ? row % p.B : 0;           // logit class of this value row (:277)
     if (BMULTI) {
       softmax_of(bb);
 #pragma unroll
       for (int i = 0; i < LP; ++i) ga[i] = 0.f;      // per camera; parked per class below
     }
-    const float* vrow = p.value + (size_t)row * p.S * kBC;
-    float* gvrow = p.grad_value + (size_t)row * p.S * kBC;
+    const float* vrow = p.value + (size_t)row * p.S * kChannels;
+    float* gvrow = p.grad_value + (size_t)row * p.S * kChannels;
     float cam_acc = 0.f;                             // sum_{l,p} a * T of this head (group-uniform)
 
 #pragma unroll
-    for (int k = 0; k < kBP; ++k) {
+    for (int k = 0; k < kPoints; ++k) {
       if (!__any(vis[k])) continue;                  // wave-uniform; heads that do not see the point run with ok = false
       const bool vk = vis[k];
       const float uk = vk ? u[k] : 0.5f, vvk = vk ? v[k] : 0.5f;
@@ -181,17 +138,15 @@ __global__ __launch_bounds__(GD4D_WAVE * WAVES) void cross_attn_bwd_block(const 
 #pragma unroll
       for (int l = 0; l < L; ++l) {
         const int W = p.lvl_w[l], H = p.lvl_h[l];
-        const float x = fmaf(uk, (float)W, -0.5f);
-        const float y = fmaf(vvk, (float)H, -0.5f);
-        const float xf = floorf(x), yf = floorf(y);
-        const float dx = x - xf, dy = y - yf;
-        const int x0 = (int)xf, y0 = (int)yf;
-        const bool x0ok = x0 >= 0, x1ok = x0 + 1 < W, y0ok = y0 >= 0, y1ok = y0 + 1 < H;
-        const float a = aw[l * kBP + k];
+        const BilinearCell cell(uk, vvk, (float)W, (float)H);
+        const int x0 = cell.x0, y0 = cell.y0;
+        const unsigned okb = cell.ok_bits(W, H);
+        const float a = aw[l * kPoints + k];
         const float wq = cw * a;                     // weight of this (camera, level, point) on out
         float d[4] = {0.f, 0.f, 0.f, 0.f};            // <g_h, v_corner>
-        const bool ok[4] = {vk && x0ok && y0ok, vk && x1ok && y0ok, vk && x0ok && y1ok, vk && x1ok && y1ok};
-        const float bw[4] = {(1.f - dx) * (1.f - dy), dx * (1.f - dy), (1.f - dx) * dy, dx * dy};
+        const bool ok[4] = {vk && corner_ok(okb, 0), vk && corner_ok(okb, 1), vk && corner_ok(okb, 2), vk && corner_ok(okb, 3)};
+        float bw[4];
+        cell.weights(bw);
         // the four corners' value rows requested together (a load under `if (ok[c])`, each followed by the corner's atomics,
         // was one round trip per corner); corners outside the map read the level's first pixel and are dropped by the select
         int pixc[4];
@@ -199,7 +154,7 @@ __global__ __launch_bounds__(GD4D_WAVE * WAVES) void cross_attn_bwd_block(const 
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           pixc[c] = ok[c] ? p.lvl_start[l] + (y0 + (c >> 1)) * W + (x0 + (c & 1)) : -1;   // head-group uniform
-          valc[c] = *reinterpret_cast<const float4*>(vrow + (size_t)max(pixc[c], p.lvl_start[l]) * kBC + lane * 4);
+          valc[c] = *reinterpret_cast<const float4*>(vrow + (size_t)max(pixc[c], p.lvl_start[l]) * kChannels + lane * 4);
         }
         asm volatile("" : "+v"(valc[0].x), "+v"(valc[0].y), "+v"(valc[0].z), "+v"(valc[0].w), "+v"(valc[1].x), "+v"(valc[1].y),
                           "+v"(valc[1].z), "+v"(valc[1].w), "+v"(valc[2].x), "+v"(valc[2].y), "+v"(valc[2].z), "+v"(valc[2].w),
@@ -217,29 +172,23 @@ __global__ __launch_bounds__(GD4D_WAVE * WAVES) void cross_attn_bwd_block(const 
             const int src = ((64 * i + lane) / DH) * LPH;
             const int hp = __shfl(pix, src);
             const float hs = __shfl(s, src);
-            if (hp >= 0) atomicAdd(gvrow + (size_t)hp * kBC + 64 * i + lane, hs * gl4[i]);
+            if (hp >= 0) atomicAdd(gvrow + (size_t)hp * kChannels + 64 * i + lane, hs * gl4[i]);
           }
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) d[c] = group_sum<LPH>(d[c]);
-        const float T = (bw[0] * d[0] + bw[1] * d[1]) + (bw[2] * d[2] + bw[3] * d[3]);
-        ga[l * kBP + k] += cw * T;
+        float T, dTdx, dTdy;                         // d/dx, d/dy of the bilinear weights (zero-padded corners have d = 0)
+        bilinear_adjoint(cell, d, T, dTdx, dTdy);
+        ga[l * kPoints + k] += cw * T;
         cam_acc += a * T;
-        // d/dx, d/dy of the bilinear weights (zero-padded corners have d = 0)
-        const float dTdx = (1.f - dy) * (d[1] - d[0]) + dy * (d[3] - d[2]);
-        const float dTdy = (1.f - dx) * (d[2] - d[0]) + dx * (d[3] - d[1]);
         gu += a * dTdx * (float)W;
         gv += a * dTdy * (float)H;
       }
       gu *= cw; gv *= cw;
       // u = cx / (cz * Wimg), v = cy / (cz * Himg)   (cz > eps for visible points; gu = gv = 0 for the others)
-      const float iz = vk ? 1.0f / czv[k] : 0.f;
-      const float gcx = gu * iz / p.img_w;
-      const float gcy = gv * iz / p.img_h;
-      const float gcz = -(gu * cxv[k] * iz * iz / p.img_w + gv * cyv[k] * iz * iz / p.img_h);
-      gpt[k][0] += gcx * m[0] + gcy * m[4] + gcz * m[8];
-      gpt[k][1] += gcx * m[1] + gcy * m[5] + gcz * m[9];
-      gpt[k][2] += gcx * m[2] + gcy * m[6] + gcz * m[10];
+      float gp[3];
+      project_adjoint(m, cxv[k], cyv[k], vk ? 1.0f / czv[k] : 0.f, gu, gv, p.img_w, p.img_h, gp);
+      gpt[k][0] += gp[0]; gpt[k][1] += gp[1]; gpt[k][2] += gp[2];
     }
     if (BMULTI && sub == 0) {                        // one lane per (wave, head): no race
       float* dst = s_gab + (((size_t)wave * p.B + bb) * HH + h) * LP;
@@ -247,9 +196,7 @@ __global__ __launch_bounds__(GD4D_WAVE * WAVES) void cross_attn_bwd_block(const 
       for (int i = 0; i < LP; ++i) dst[i] += ga[i];
     }
     // camera-logit gradient: sum over heads of (a * T), one lane per head then across the groups
-    float cs = (sub == 0) ? cam_acc : 0.f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o);
+    const float cs = wave_sum((sub == 0) ? cam_acc : 0.f);
     if (lane == 0) p.grad_cam_logits[(size_t)b * p.Q * p.N + (size_t)n * p.Q + q] = (p.raw_cam ? 1.f : cw * (1.f - cw)) * cs;
   }
 
@@ -259,7 +206,7 @@ __global__ __launch_bounds__(GD4D_WAVE * WAVES) void cross_attn_bwd_block(const 
 #pragma unroll
     for (int i = 0; i < LP; ++i) dst[i] = ga[i];
 #pragma unroll
-    for (int k = 0; k < kBP; ++k) { dst[LP + 3 * k] = gpt[k][0]; dst[LP + 3 * k + 1] = gpt[k][1]; dst[LP + 3 * k + 2] = gpt[k][2]; }
+    for (int k = 0; k < kPoints; ++k) { dst[LP + 3 * k] = gpt[k][0]; dst[LP + 3 * k + 1] = gpt[k][1]; dst[LP + 3 * k + 2] = gpt[k][2]; }
   }
   __syncthreads();
   if (tid < HH) {
@@ -301,15 +248,15 @@ __global__ __launch_bounds__(GD4D_WAVE * WAVES) void cross_attn_bwd_block(const 
 #pragma unroll
       for (int i = 0; i < LP; ++i) gl[i] = a2[i] * (tot[i] - dot);
     }
-    float* go = p.grad_offsets + ((size_t)bq * HH + hh) * kBP * 3;
+    float* go = p.grad_offsets + ((size_t)bq * HH + hh) * kPoints * 3;
 #pragma unroll
-    for (int i = 0; i < kBP * 3; ++i) go[i] = tot[LP + i];
+    for (int i = 0; i < kPoints * 3; ++i) go[i] = tot[LP + i];
     // re-park the per-head point gradient sums for the reference-point reduction
 #pragma unroll
     for (int d3 = 0; d3 < 3; ++d3) {
       float t = 0.f;
 #pragma unroll
-      for (int k = 0; k < kBP; ++k) t += tot[LP + 3 * k + d3];
+      for (int k = 0; k < kPoints; ++k) t += tot[LP + 3 * k + d3];
       s_pt[3 * hh + d3] = t;
     }
   }
@@ -358,14 +305,14 @@ static int launch_bwd(const CrossAttnBwdParams& p, hipStream_t s) {
   const dim3 grid(p.order ? ((p.B * p.Q + 7) / 8) * 8 : p.B * p.Q);
   const bool multi = p.B > 1;
   auto lds_for = [&](int L) {
-    return (size_t)WAVES * HH * (L * kBP + 3 * kBP) * sizeof(float) + 64 * sizeof(int) + (size_t)HH * kBP * 3 * sizeof(float) +
-           (multi ? (size_t)WAVES * p.B * HH * L * kBP * sizeof(float) : 0);
+    return (size_t)WAVES * HH * (L * kPoints + 3 * kPoints) * sizeof(float) + 64 * sizeof(int) + (size_t)HH * kPoints * 3 * sizeof(float) +
+           (multi ? (size_t)WAVES * p.B * HH * L * kPoints * sizeof(float) : 0);
   };
 #define GD4D_BWD_GO(L_)                                                                                                       \
   if (multi) {                                                                                                                \
     hipLaunchKernelGGL((cross_attn_bwd_block<HH, L_, WAVES, true>), grid, dim3(GD4D_WAVE * WAVES), lds_for(L_), s, p);        \
     if (int rc = check_launch()) return rc;                                                                                   \
-    hipLaunchKernelGGL((cross_attn_bwd_logits_kernel<L_ * kBP>), dim3(p.B * p.Q), dim3(64), 0, s, p, HH);                     \
+    hipLaunchKernelGGL((cross_attn_bwd_logits_kernel<L_ * kPoints>), dim3(p.B * p.Q), dim3(64), 0, s, p, HH);                     \
   } else {                                                                                                                    \
     hipLaunchKernelGGL((cross_attn_bwd_block<HH, L_, WAVES, false>), grid, dim3(GD4D_WAVE * WAVES), lds_for(L_), s, p);       \
   }
@@ -400,7 +347,7 @@ extern "C" int gd4d_cross_attn_bwd(const void* value, const int32_t* level_hw, c
       !grad_out || !grad_value || !grad_ref || !grad_offsets || !grad_attn_logits || !grad_cam_logits)
     return GD4D_EINVAL;
   if (B <= 0 || N <= 0 || Q <= 0 || Hh <= 0 || Dh <= 0 || L <= 0 || !(img_h > 0.f) || !(img_w > 0.f)) return GD4D_EINVAL;
-  if (B > 8 || Hh * Dh != kBC || P != kBP || L > 4 || N > 64 || value_dtype != GD4D_F32 ||
+  if (B > 8 || Hh * Dh != kChannels || P != kPoints || L > 4 || N > 64 || value_dtype != GD4D_F32 ||
       value_layout != GD4D_LAYOUT_PIXEL_MAJOR)
     return GD4D_EUNSUPPORTED;
   if (B > 1 && (!workspace || workspace_bytes < gd4d_cross_attn_bwd_workspace_bytes(B, Q, Hh, L, P))) return GD4D_EWORKSPACE;

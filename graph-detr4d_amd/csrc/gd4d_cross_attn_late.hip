@@ -179,64 +179,19 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_agg_kernel(const CrossA
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   trace_mark(g_trace_late, 3ull);
-  int bq = blockIdx.x;
-  if (p.order) {                                   // XCD-contiguous ranges of the locality order (see gd4d_cross_attn_fwd)
-    const int per_xcd = (p.B * p.Q + 7) >> 3;
-    const int pos = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if ((int)(blockIdx.x >> 3) >= per_xcd || pos >= p.B * p.Q) return;
-    bq = p.order[pos];
-  } else if (bq >= p.B * p.Q) {
-    return;
-  }
+  int bq;
+  if (!query_of_block<false>(p.order, p.B * p.Q, bq)) return;
   const int b = bq / p.Q;
   const int q = bq - b * p.Q;
 
   // ---------------- phase A ----------------
-  for (int i = tid; i < p.N * 12; i += THREADS) s_mat[i] = p.lidar2img[((size_t)b * p.N + i / 12) * 16 + i % 12];
-  if (tid < p.N) {
-    const float cl = p.cam_logits[(size_t)b * p.Q * p.N + (size_t)tid * p.Q + q];   // raw-view scramble (:211-212)
-    s_cw[tid] = p.raw_cam ? cl : 1.0f / (1.0f + expf(-cl));
-  }
-  if ((LP & (LP - 1)) == 0 && LP <= 32) {          // softmax over L * P logits per head, one thread per logit
-    if (tid < HH * LP) {
-      const int hd = tid / LP, i = tid % LP;
-      const float x = p.attn_logits[((size_t)bq * HH + hd) * LP + i];
-      float mx = x;
-#pragma unroll
-      for (int o = 1; o < LP; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-      const float e = expf(x - mx);
-      float sum = e;
-#pragma unroll
-      for (int o = 1; o < LP; o <<= 1) sum += __shfl_xor(sum, o);
-      s_aw[hd * LP + i] = e * (1.0f / sum);
-    }
-  } else if (tid < HH) {
-    float w[LP];
-    softmax_lp(p.attn_logits + ((size_t)bq * HH + tid) * LP, LP, w);
-    for (int i = 0; i < LP; ++i) s_aw[tid * LP + i] = w[i];
-  }
+  stage_cameras<THREADS>(p, b, q, s_mat, s_cw);
+  head_softmax_to_lds<HH, LP, softmax_can_shuffle(LP), THREADS>(p.attn_logits + (size_t)bq * HH * LP, 0, 1, LP, s_aw);
   __syncthreads();
   {
-    const int total = p.N * E;
-    static_assert(E <= GD4D_WAVE && GD4D_WAVE % E == 0 && THREADS % E == 0, "a thread keeps its (head, point)");
-    const int hp = tid % E;
-    const float* rp = p.ref + (size_t)bq * 3;
-    const float* offs = p.offsets + ((size_t)bq * E + hp) * 3;
-    const float X = (rp[0] * p.rng_scale[0] + p.rng_lo[0]) + offs[0];     // two roundings, then the offset (:222-229)
-    const float Y = (rp[1] * p.rng_scale[1] + p.rng_lo[1]) + offs[1];
-    const float Z = (rp[2] * p.rng_scale[2] + p.rng_lo[2]) + offs[2];
-    for (int e0 = wave * GD4D_WAVE; e0 < total; e0 += THREADS) {
-      const int e = e0 + lane;
-      if (e < total) {
-        const int n = e / E;
-        float u, v;
-        const bool vis = project_entry(p, s_mat + n * 12, X, Y, Z, u, v);
-        s_uv[e] = vis ? make_float2(u, v) : make_float2(-1.f, -1.f);
-        const size_t o = (((size_t)b * p.N + n) * p.Q + q) * E + hp;
-        if (p.mask_out) p.mask_out[o] = vis ? 1 : 0;
-        if (p.uv_out) { p.uv_out[o * 2] = u; p.uv_out[o * 2 + 1] = v; }
-      }
-    }
+    float X, Y, Z;
+    query_point<E>(p, bq, tid % E, X, Y, Z);
+    project_query<E, THREADS>(p, b, q, s_mat, s_uv, X, Y, Z);
   }
   __syncthreads();
 
@@ -285,17 +240,10 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_agg_kernel(const CrossA
           const int cand = s_items[h * ncand + min(item, M - 1)];
           const int n = cand / PT, k = cand % PT;
           const float2 uv = s_uv[n * E + h * PT + k];
-          const float x = fmaf(uv.x, (float)lw, -0.5f);
-          const float y = fmaf(uv.y, (float)lh, -0.5f);
-          const float xf = floorf(x), yf = floorf(y);
-          const float dx = x - xf, dy = y - yf;
-          const int xi = (int)xf + (c_of & 1), yi = (int)yf + (c_of >> 1);
-          const bool ok = valid && xi >= 0 && xi < lw && yi >= 0 && yi < lh;
+          const BilinearCell::Corner cn = BilinearCell(uv.x, uv.y, (float)lw, (float)lh).corner(c_of, lw, lh);
           const float wl = s_aw[h * LP + l * PT + k] * s_cw[n];
-          const float wx = (c_of & 1) ? dx : 1.f - dx, wy = (c_of >> 1) ? dy : 1.f - dy;
-          const float w = ok ? wl * wx * wy : 0.f;
-          const int xc = min(max(xi, 0), lw - 1), yc = min(max(yi, 0), lh - 1);
-          const unsigned pixel = valid ? (unsigned)((b * p.N + n) * p.S + ls + yc * lw + xc) : 0u;
+          const float w = (valid && cn.in) ? wl * cn.wx * cn.wy : 0.f;
+          const unsigned pixel = valid ? (unsigned)((b * p.N + n) * p.S + ls + cn.yc * lw + cn.xc) : 0u;
           wsum_lane[hi] += w;
 #pragma unroll
           for (int s = 0; s < 4; ++s) {
@@ -322,9 +270,7 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_agg_kernel(const CrossA
       const int h = wave + hi * WAVES;
       if (h >= HH) break;
       if (p.agg) *reinterpret_cast<float4*>(p.agg + ((size_t)bq * HH + h) * kChannels + lane * 4) = acc[hi];
-      float t = wsum_lane[hi];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+      const float t = wave_sum(wsum_lane[hi]);
       if (lane == 0 && p.wsum) p.wsum[(size_t)bq * HH + h] = t;
     }
     return;
@@ -350,18 +296,10 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_agg_kernel(const CrossA
       const int cand = s_items[h * ncand + min(item, M - 1)];
       const int n = cand / PT, k = cand % PT;
       const float2 uv = s_uv[n * E + h * PT + k];
-      const float x = fmaf(uv.x, (float)lw, -0.5f);
-      const float y = fmaf(uv.y, (float)lh, -0.5f);
-      const float xf = floorf(x), yf = floorf(y);
-      const float dx = x - xf, dy = y - yf;
-      const int xi = (int)xf + (c_of & 1), yi = (int)yf + (c_of >> 1);
-      const bool ok = valid && xi >= 0 && xi < lw && yi >= 0 && yi < lh;
+      const BilinearCell::Corner cn = BilinearCell(uv.x, uv.y, (float)lw, (float)lh).corner(c_of, lw, lh);
       const float wl = s_aw[h * LP + min(l_of, LT - 1) * PT + k] * s_cw[n];
-      const float wx = (c_of & 1) ? dx : 1.f - dx, wy = (c_of >> 1) ? dy : 1.f - dy;
-      const float w = ok ? wl * wx * wy : 0.f;
-      // corners outside the map contribute 0 (zero padding); their loads are clamped onto the map
-      const int xc = min(max(xi, 0), lw - 1), yc = min(max(yi, 0), lh - 1);
-      const unsigned pixel = valid ? (unsigned)((b * p.N + n) * p.S + ls + yc * lw + xc) : 0u;
+      const float w = (valid && cn.in) ? wl * cn.wx * cn.wy : 0.f;
+      const unsigned pixel = valid ? (unsigned)((b * p.N + n) * p.S + ls + cn.yc * lw + cn.xc) : 0u;
       wsum_lane += w;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
@@ -382,8 +320,7 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_agg_kernel(const CrossA
       }
     }
     if (p.agg) *reinterpret_cast<float4*>(p.agg + ((size_t)bq * HH + h) * kChannels + lane * 4) = acc;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) wsum_lane += __shfl_xor(wsum_lane, o);
+    wsum_lane = wave_sum(wsum_lane);
     if (lane == 0 && p.wsum) p.wsum[(size_t)bq * HH + h] = wsum_lane;
     if (p.vp_w) {
       // value_proj of this head's aggregate in the epilogue (exact fp32): out[h*Dh + d] = <W[h*Dh + d, :], agg> + b wsum.

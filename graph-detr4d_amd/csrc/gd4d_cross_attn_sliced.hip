@@ -75,57 +75,14 @@ __device__ __forceinline__ void cross_attn_plan_body(const PlanParams& pp, const
   const int bq = p.order ? p.order[pos] : pos;
   const int b = bq / p.Q, q = bq - b * p.Q;
 
-  for (int i = tid; i < p.N * 12; i += THREADS) s_mat[i] = p.lidar2img[((size_t)b * p.N + i / 12) * 16 + i % 12];
-  if (tid < p.N) {
-    const float cl = p.cam_logits[(size_t)b * p.Q * p.N + (size_t)tid * p.Q + q];   // raw-view scramble (:211-212)
-    s_cw[tid] = p.raw_cam ? cl : 1.0f / (1.0f + expf(-cl));
-  }
+  stage_cameras<THREADS>(p, b, q, s_mat, s_cw);
   // softmax over L * P logits per head; value row i = b*N + n is paired with the logits of batch (i % B) (:277)
-  if ((LP & (LP - 1)) == 0 && LP <= 32 && (HH * LP) % GD4D_WAVE == 0) {      // one thread per logit, xor-shuffle reductions
-    for (int t = tid; t < p.B * HH * LP; t += THREADS) {
-      const int bh = t / LP, i = t % LP;
-      const int bb = bh / HH, hd = bh - bb * HH;
-      const float x = p.attn_logits[(((size_t)bb * p.Q + q) * HH + hd) * LP + i];
-      float mx = x;
-#pragma unroll
-      for (int o = 1; o < LP; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-      const float e = expf(x - mx);
-      float sum = e;
-#pragma unroll
-      for (int o = 1; o < LP; o <<= 1) sum += __shfl_xor(sum, o);
-      s_aw[t] = e * (1.0f / sum);
-    }
-  } else {
-    for (int t = tid; t < p.B * HH; t += THREADS) {
-      const int bb = t / HH, hd = t - bb * HH;
-      float w[LP];
-      softmax_lp(p.attn_logits + (((size_t)bb * p.Q + q) * HH + hd) * LP, LP, w);
-#pragma unroll
-      for (int i = 0; i < LP; ++i) s_aw[t * LP + i] = w[i];
-    }
-  }
+  head_softmax_to_lds<HH, LP, kPlanSoftmaxShuffles<HH, LP>, THREADS>(p.attn_logits + (size_t)q * HH * LP, (size_t)p.Q * HH * LP, p.B, LP, s_aw);
   {
-    const int total = p.N * E;
-    static_assert(E <= GD4D_WAVE && GD4D_WAVE % E == 0 && THREADS % E == 0, "a thread keeps its (head, point)");
-    const int hp = tid % E;
-    const float* rp = p.ref + (size_t)bq * 3;
-    const float* offs = p.offsets + ((size_t)bq * E + hp) * 3;
-    const float X = (rp[0] * p.rng_scale[0] + p.rng_lo[0]) + offs[0];     // two roundings, then the offset (:222-229)
-    const float Y = (rp[1] * p.rng_scale[1] + p.rng_lo[1]) + offs[1];
-    const float Z = (rp[2] * p.rng_scale[2] + p.rng_lo[2]) + offs[2];
+    float X, Y, Z;
+    query_point<E>(p, bq, tid % E, X, Y, Z);
     __syncthreads();
-    for (int e0 = wave * GD4D_WAVE; e0 < total; e0 += THREADS) {
-      const int e = e0 + lane;
-      if (e < total) {
-        const int n = e / E;
-        float u, v;
-        const bool vis = project_entry(p, s_mat + n * 12, X, Y, Z, u, v);
-        s_uv[e] = vis ? make_float2(u, v) : make_float2(-1.f, -1.f);
-        const size_t o = (((size_t)b * p.N + n) * p.Q + q) * E + hp;
-        if (p.mask_out) p.mask_out[o] = vis ? 1 : 0;
-        if (p.uv_out) { p.uv_out[o * 2] = u; p.uv_out[o * 2 + 1] = v; }
-      }
-    }
+    project_query<E, THREADS>(p, b, q, s_mat, s_uv, X, Y, Z);
   }
   __syncthreads();
   // wave w: heads w, w + WAVES, ...: compact the visible (camera, point) pairs, then the corners: lane = (item % 16, level)
@@ -145,19 +102,7 @@ __device__ __forceinline__ void cross_attn_plan_body(const PlanParams& pp, const
   // where the four pairs of this lane go inside their pass: [g][j], g = (item & 1, corner), j = (item >> 1 & 1, level)
   const int slot0 = (((i_of & 1) << 2) << 3) | (((i_of >> 1) & 1) << 2) | l_of;
   for (int h = wave; h < HH; h += WAVES) {
-    int M = 0;
-    for (int c0 = 0; c0 < ncand; c0 += GD4D_WAVE) {
-      const int cand = c0 + lane;
-      const int n = min(cand, ncand - 1) / PT, k = cand % PT;
-      const float2 uvc = s_uv[n * E + h * PT + k];
-      const bool vis = cand < ncand && uvc.x >= 0.f;
-      const unsigned long long bal = __ballot(vis);
-      if (vis) items[M + __popcll(bal & ((1ull << lane) - 1ull))] = make_float4(uvc.x, uvc.y, __int_as_float((b * p.N + n) * PT + k), s_cw[n]);
-      M += __popcll(bal);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                 // wave-private list: no workgroup barrier
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int M = compact_head_items<PT>(s_uv, s_cw, E, p.N, b, h, items);
     if (pp.item) {
       // ITEMS form (the inference step): 32 bytes per visible (camera, point) item - {u, v, camera row, M} {weight of
       // level 0..3} - instead of 4 levels x 4 corners x {offset, weight} = 128: the eight slices of a query re-read their
@@ -198,29 +143,12 @@ __device__ __forceinline__ void cross_attn_plan_body(const PlanParams& pp, const
       const int row = rk / PT, k = rk % PT;
       const int lb = p.B == 1 ? 0 : row % p.B;                              // logits of batch (row % B) (:277)
       const float wl = aw_h[lb * HH * LP + k] * rec.w;
-      const float x = fmaf(rec.x, flw, -0.5f);
-      const float y = fmaf(rec.y, flh, -0.5f);
-      const float xf = floorf(x), yf = floorf(y);
-      const float dx = x - xf, dy = y - yf;
-      const int x0 = (int)xf, y0 = (int)yf;
+      const BilinearCell cell(rec.x, rec.y, flw, flh);
       const float live = item < M ? lvl_on : 0.f;
-      const unsigned rbase = (unsigned)row * cstr;
-      uint2* dst = out + (size_t)(item >> 2) * 64 + slot0;
-#pragma unroll
-      for (int c_of = 0; c_of < 4; ++c_of) {
-        const int xi = x0 + (c_of & 1), yi = y0 + (c_of >> 1);
-        // corners outside the map contribute 0 (zero padding); their loads are clamped onto the map
-        const int xc = min(max(xi, 0), lw - 1), yc = min(max(yi, 0), lh - 1);
-        const float in = (xc == xi && yc == yi) ? live : 0.f;
-        const float wx = (c_of & 1) ? dx : 1.f - dx, wy = (c_of >> 1) ? dy : 1.f - dy;
-        const float w = (wl * wx * wy) * in;
-        const unsigned off = rbase + (unsigned)(yc * lw + xc) * pp.g.pix_stride;
-        wsum_lane += w;
-        if (item < m_pad) dst[c_of << 3] = make_uint2(off, __float_as_uint(w));
-      }
+      corner_pairs(cell, lw, lh, wl, live, (unsigned)row * cstr, pp.g.pix_stride, item < m_pad,
+                   out + (size_t)(item >> 2) * 64 + slot0, 8, wsum_lane);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) wsum_lane += __shfl_xor(wsum_lane, o);
+    wsum_lane = wave_sum(wsum_lane);
     if (lane == 0) {
       pp.hdr[pos * kPlanHdr + h] = M;
       if (p.wsum) p.wsum[(size_t)bq * HH + h] = wsum_lane;
@@ -289,9 +217,7 @@ __device__ __forceinline__ void cross_attn_agg_sliced_body(const SlicedParams& p
       const uint2 v = (k == 0 && t0 == 0) ? first : pp[(size_t)(t0 + k) * 64];
       *reinterpret_cast<uint2*>(wr + k * PASS) = v;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                 // wave-private LDS patch: no workgroup barrier
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();                                                      // wave-private LDS patch: no workgroup barrier
     for (int k = 0; k < nt; ++k) gather_pass<LT, 4, VT, false>(rd + k * PASS, base, lane_off, M - (t0 + k) * 4, acc0, acc1);
   }
   const float4 acc = sum_corner_slots(acc0, acc1);
@@ -400,35 +326,20 @@ __device__ __forceinline__ void cross_attn_agg_items_body(const ItemsParams& ip,
     const int item = it0 + i_of;
     {
       const int row = __float_as_int(a.z);
-      const float x = fmaf(a.x, flw, -0.5f);
-      const float y = fmaf(a.y, flh, -0.5f);
-      const float xf = floorf(x), yf = floorf(y);
-      const float dx = x - xf, dy = y - yf;
-      const int x0 = (int)xf, y0 = (int)yf;
+      const BilinearCell cell(a.x, a.y, flw, flh);
       const float live = item < M ? lvl_on : 0.f;
       const unsigned rbase = (unsigned)row * cstr;
       if (it0 > 0) __builtin_amdgcn_wave_barrier();                         // the previous step's passes have read the patch
-#pragma unroll
-      for (int c_of = 0; c_of < 4; ++c_of) {
-        const int xi = x0 + (c_of & 1), yi = y0 + (c_of >> 1);
-        // corners outside the map contribute 0 (zero padding); their loads are clamped onto the map
-        const int xc = min(max(xi, 0), lw - 1), yc = min(max(yi, 0), lh - 1);
-        const float in = (xc == xi && yc == yi) ? live : 0.f;
-        const float wx = (c_of & 1) ? dx : 1.f - dx, wy = (c_of >> 1) ? dy : 1.f - dy;
-        const float w = (wl * wx * wy) * in;
-        const unsigned off = rbase + (unsigned)(yc * lw + xc) * geo.pix_stride;
-        wsum_lane += w;
-        if (item < m_even && l_of < LA) *reinterpret_cast<uint2*>(wr + c_of * GP) = make_uint2(off, __float_as_uint(w));
-      }
+      static_assert(GP % sizeof(uint2) == 0, "corner slots are whole pairs apart");
+      corner_pairs(cell, lw, lh, wl, live, rbase, geo.pix_stride, item < m_even && l_of < LA, reinterpret_cast<uint2*>(wr),
+                   GP / (int)sizeof(uint2), wsum_lane);
     }
     if (it0 + IPS < M) {                                                    // the next step's records fly under this step's passes
       const int nx = min(item + IPS, M - 1);
       a = rec[nx * 2];
       wl = reinterpret_cast<const float*>(rec + nx * 2 + 1)[LV0 + l_of];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                 // wave-private LDS patch: no workgroup barrier
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();                                                      // wave-private LDS patch: no workgroup barrier
     const int t0 = it0 / IPP;
     const int nt = min(CH, T - t0);
 #pragma unroll
@@ -448,7 +359,7 @@ __device__ __forceinline__ void cross_attn_agg_items_body(const ItemsParams& ip,
   }
   if (!COARSE && s == 0 && ip.wsum) {                                      // wave-uniform: the group that holds slice 0
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) wsum_lane += __shfl_xor(wsum_lane, o);
+    for (int o = 32; o > 0; o >>= 1) wsum_lane += __shfl_xor(wsum_lane, o);   // (written out: wave_sum() here costs the gathers a register)
     if (lane == 0) ip.wsum[(size_t)bq * HH + h] = wsum_lane;
   }
 }

@@ -233,9 +233,7 @@ __device__ __forceinline__ void cross_attn_dot_sliced_body(const DotParams& dp_,
       const uint2 v = (k == 0 && t0 == 0) ? first : pp[(size_t)(t0 + k) * 64];
       *reinterpret_cast<uint2*>(wr + k * PASS) = v;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
     for (int k = 0; k < nt; ++k) {
       const uint4* row = reinterpret_cast<const uint4*>(rd + k * PASS);
       uint4 pr[4];
@@ -368,54 +366,16 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_plan_bwd_kernel(const P
   const int bq = p.order ? p.order[pos] : pos;
   const int b = bq / p.Q, q = bq - b * p.Q;
 
-  for (int i = tid; i < p.N * 12; i += THREADS) s_mat[i] = p.lidar2img[((size_t)b * p.N + i / 12) * 16 + i % 12];
-  if (tid < p.N) {
-    const float cl = p.cam_logits[(size_t)b * p.Q * p.N + (size_t)tid * p.Q + q];
-    s_cw[tid] = p.raw_cam ? cl : 1.0f / (1.0f + expf(-cl));
-  }
+  stage_cameras<THREADS>(p, b, q, s_mat, s_cw);
   for (int i = tid; i < HH * ncand; i += THREADS) s_camT[i] = 0.f;
-  if ((LP & (LP - 1)) == 0 && LP <= 32 && (HH * LP) % GD4D_WAVE == 0) {      // as the plan kernel (same weights bit for bit)
-    for (int t = tid; t < p.B * HH * LP; t += THREADS) {
-      const int bh = t / LP, i = t % LP;
-      const int bb = bh / HH, hd = bh - bb * HH;
-      const float x = p.attn_logits[(((size_t)bb * p.Q + q) * HH + hd) * LP + i];
-      float mx = x;
-#pragma unroll
-      for (int o = 1; o < LP; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-      const float e = expf(x - mx);
-      float sum = e;
-#pragma unroll
-      for (int o = 1; o < LP; o <<= 1) sum += __shfl_xor(sum, o);
-      s_aw[t] = e * (1.0f / sum);
-    }
-  } else {
-    for (int t = tid; t < p.B * HH; t += THREADS) {
-      const int bb = t / HH, hd = t - bb * HH;
-      float w[LP];
-      softmax_lp(p.attn_logits + (((size_t)bb * p.Q + q) * HH + hd) * LP, LP, w);
-#pragma unroll
-      for (int i = 0; i < LP; ++i) s_aw[t * LP + i] = w[i];
-    }
-  }
+  head_softmax_to_lds<HH, LP, kPlanSoftmaxShuffles<HH, LP>, THREADS>(p.attn_logits + (size_t)q * HH * LP, (size_t)p.Q * HH * LP, p.B, LP, s_aw);
   {
-    const int total = p.N * E;
-    static_assert(E <= GD4D_WAVE && GD4D_WAVE % E == 0 && THREADS % E == 0, "a thread keeps its (head, point)");
     const int hp = tid % E;
-    const float* rp = p.ref + (size_t)bq * 3;
-    const float* offs = p.offsets + ((size_t)bq * E + hp) * 3;
-    const float X = (rp[0] * p.rng_scale[0] + p.rng_lo[0]) + offs[0];
-    const float Y = (rp[1] * p.rng_scale[1] + p.rng_lo[1]) + offs[1];
-    const float Z = (rp[2] * p.rng_scale[2] + p.rng_lo[2]) + offs[2];
+    float X, Y, Z;
+    query_point<E>(p, bq, hp, X, Y, Z);
     if (tid < E) { s_pt[hp * 4] = X; s_pt[hp * 4 + 1] = Y; s_pt[hp * 4 + 2] = Z; }
     __syncthreads();
-    for (int e0 = wave * GD4D_WAVE; e0 < total; e0 += THREADS) {
-      const int e = e0 + lane;
-      if (e < total) {
-        float u, v;
-        const bool vis = project_entry(p, s_mat + (e / E) * 12, X, Y, Z, u, v);
-        s_uv[e] = vis ? make_float2(u, v) : make_float2(-1.f, -1.f);
-      }
-    }
+    project_query<E, THREADS, false>(p, b, q, s_mat, s_uv, X, Y, Z);
   }
   __syncthreads();
 
@@ -431,20 +391,8 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_plan_bwd_kernel(const P
   const int slot0 = (((i_of & 1) << 2) << 3) | (((i_of >> 1) & 1) << 2) | l_of;
   for (int h = wave; h < HH; h += WAVES) {
     for (int i = lane; i < ncand * 4; i += GD4D_WAVE) { ga_w[i] = 0.f; gpt_w[i] = 0.f; }
-    int M = 0;
-    for (int c0 = 0; c0 < ncand; c0 += GD4D_WAVE) {
-      const int cand = c0 + lane;
-      const int n = min(cand, ncand - 1) / PT, k = cand % PT;
-      const float2 uvc = s_uv[n * E + h * PT + k];
-      const bool vis = cand < ncand && uvc.x >= 0.f;
-      const unsigned long long bal = __ballot(vis);
-      if (vis) items[M + __popcll(bal & ((1ull << lane) - 1ull))] = make_float4(uvc.x, uvc.y, __int_as_float((b * p.N + n) * PT + k), s_cw[n]);
-      M += __popcll(bal);
-    }
+    const int M = compact_head_items<PT>(s_uv, s_cw, E, p.N, b, h, items);
     if (pp.status && lane == 0 && M != pp.hdr[pos * kPlanHdr + h]) *pp.status = 1;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const size_t prow = ((size_t)pos * HH + h) * pp.cap_t * 64;
     const float* aw_h = s_aw + h * LP + min(l_of, LT - 1) * PT;
     const float beta = pp.beta ? pp.beta[(size_t)bq * HH + h] : 0.f;
@@ -459,11 +407,7 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_plan_bwd_kernel(const P
       const int lb = p.B == 1 ? 0 : row % p.B;
       const float a = aw_h[lb * HH * LP + k];
       const float cw = rec.w;
-      const float x = fmaf(rec.x, flw, -0.5f);
-      const float y = fmaf(rec.y, flh, -0.5f);
-      const float xf = floorf(x), yf = floorf(y);
-      const float dx = x - xf, dy = y - yf;
-      const int x0 = (int)xf, y0 = (int)yf;
+      const BilinearCell cell(rec.x, rec.y, flw, flh);
       // the 4 x 8 slice partials of this lane's corners, all requested before the first is used (a pass of the gather-dot
       // writes all 64 of its entries, so every address below holds a finite or at least harmless value: lanes past the list's
       // end read their slot of its last pass; what a dead lane or a corner outside the map reads is dropped by the select).
@@ -477,18 +421,15 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_plan_bwd_kernel(const P
       float d[4];
 #pragma unroll
       for (int c_of = 0; c_of < 4; ++c_of) {
-        const int xi = x0 + (c_of & 1), yi = y0 + (c_of >> 1);
-        const bool in = live && xi >= 0 && xi < lw && yi >= 0 && yi < lh;
+        const bool in = live && cell.corner(c_of, lw, lh).in;
         float t = 0.f;
 #pragma unroll
         for (int s = 0; s < kSlices; ++s) t += part[c_of][s];
         t += beta;
         d[c_of] = in ? t : 0.f;                       // corners outside the map (zero padding) and dead lanes: 0
       }
-      const float bw0 = (1.f - dx) * (1.f - dy), bw1 = dx * (1.f - dy), bw2 = (1.f - dx) * dy, bw3 = dx * dy;
-      const float T = (bw0 * d[0] + bw1 * d[1]) + (bw2 * d[2] + bw3 * d[3]);
-      const float dTdx = (1.f - dy) * (d[1] - d[0]) + dy * (d[3] - d[2]);
-      const float dTdy = (1.f - dx) * (d[2] - d[0]) + dx * (d[3] - d[1]);
+      float T, dTdx, dTdy;
+      bilinear_adjoint(cell, d, T, dTdx, dTdy);
       if (live) ga_w[cand * 4 + l_of] = cw * T;
       float camv = a * T, gu = a * dTdx * flw, gv = a * dTdy * flh;       // dead lanes: T = 0
       camv += __shfl_xor(camv, 1); gu += __shfl_xor(gu, 1); gv += __shfl_xor(gv, 1);
@@ -498,21 +439,12 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_plan_bwd_kernel(const P
         gu *= cw; gv *= cw;
         const float* m = s_mat + n * 12;
         const float X = s_pt[(h * PT + k) * 4], Y = s_pt[(h * PT + k) * 4 + 1], Z = s_pt[(h * PT + k) * 4 + 2];
-        const float cx = ((m[0] * X + m[1] * Y) + m[2] * Z) + m[3];
-        const float cy = ((m[4] * X + m[5] * Y) + m[6] * Z) + m[7];
-        const float cz = ((m[8] * X + m[9] * Y) + m[10] * Z) + m[11];
-        const float iz = 1.0f / cz;                    // visible: cz > eps
-        const float gcx = gu * iz / p.img_w;
-        const float gcy = gv * iz / p.img_h;
-        const float gcz = -(gu * cx * iz * iz / p.img_w + gv * cy * iz * iz / p.img_h);
-        gpt_w[cand * 4 + 0] = gcx * m[0] + gcy * m[4] + gcz * m[8];
-        gpt_w[cand * 4 + 1] = gcx * m[1] + gcy * m[5] + gcz * m[9];
-        gpt_w[cand * 4 + 2] = gcx * m[2] + gcy * m[6] + gcz * m[10];
+        float cx, cy, cz, u, v;
+        project_camera(m, X, Y, Z, p.img_w, p.img_h, cx, cy, cz, u, v);
+        project_adjoint(m, cx, cy, 1.0f / cz, gu, gv, p.img_w, p.img_h, gpt_w + cand * 4);   // visible: cz > eps
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
     // fixed-order sums over the cameras
     {
       const int i = lane;                                // logit (level, point) = (i / PT, i % PT)
@@ -522,9 +454,7 @@ __global__ __launch_bounds__(64 * WAVES) void cross_attn_plan_bwd_kernel(const P
         if (i < LP)
           for (int n = 0; n < p.N; ++n) tot += ga_w[(n * PT + k) * 4 + l];
         const float ai = i < LP ? s_aw[h * LP + i] : 0.f;
-        float dot = ai * tot;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+        const float dot = wave_sum(ai * tot);
         if (i < LP) pp.grad_attn_logits[((size_t)bq * HH + h) * LP + i] = ai * (tot - dot);
       } else if (i < LP) {
         for (int cls = 0; cls < p.B; ++cls) {

@@ -9,6 +9,7 @@
 // far less traffic than re-laying-out the whole pyramid first.  The projection is spread over the
 // first N threads (bit-exact arithmetic, translation unit built with -ffp-contract=off).
 #include "gd4d_common.h"
+#include "gd4d_cross_attn_shared.h"
 
 namespace gd4d {
 
@@ -34,6 +35,16 @@ __device__ __forceinline__ float unnormalize(float g, int size) {
   return ((g + 1.f) * (float)size - 1.f) / 2.f;
 }
 
+// project_camera, then DETR3D's own rule (detr3d_transformer.py:421, :676): u, v mapped to grid coordinates in [-1, 1]; visible =
+// in front of the camera and strictly inside
+__device__ __forceinline__ bool project_grid(const float* __restrict__ m, float X, float Y, float Z, float img_w, float img_h,
+                                             float& cx, float& cy, float& cz, float& u, float& v) {
+  project_camera(m, X, Y, Z, img_w, img_h, cx, cy, cz, u, v);
+  u = (u - 0.5f) * 2.f;
+  v = (v - 0.5f) * 2.f;
+  return cz > kDepthEps && (u > -1.f) && (u < 1.f) && (v > -1.f) && (v < 1.f);
+}
+
 __global__ __launch_bounds__(256) void detr3d_fwd_kernel(const Detr3dParams p) {
   extern __shared__ float s_mem[];
   float2* s_uv = reinterpret_cast<float2*>(s_mem);            // [N] grid coords in [-1,1]
@@ -51,17 +62,8 @@ __global__ __launch_bounds__(256) void detr3d_fwd_kernel(const Detr3dParams p) {
     const float Y = rp[1] * p.rng_scale[1] + p.rng_lo[1];
     const float Z = rp[2] * p.rng_scale[2] + p.rng_lo[2];
     const float* m = p.lidar2img + ((size_t)b * p.N + n) * 16;
-    const float eps = 1e-5f;
-    const float cx = ((m[0] * X + m[1] * Y) + m[2] * Z) + m[3];
-    const float cy = ((m[4] * X + m[5] * Y) + m[6] * Z) + m[7];
-    const float cz = ((m[8] * X + m[9] * Y) + m[10] * Z) + m[11];
-    bool vis = cz > eps;
-    const float zc = fmaxf(cz, eps);
-    float u = (cx / zc) / p.img_w;
-    float v = (cy / zc) / p.img_h;
-    u = (u - 0.5f) * 2.f;                                     // detr3d_transformer.py:421
-    v = (v - 0.5f) * 2.f;
-    vis = vis && (u > -1.f) && (u < 1.f) && (v > -1.f) && (v < 1.f);
+    float cx, cy, cz, u, v;
+    const bool vis = project_grid(m, X, Y, Z, p.img_w, p.img_h, cx, cy, cz, u, v);
     s_uv[n] = make_float2(u, v);
     s_vis[n] = vis ? 1 : 0;
     if (p.mask_out) p.mask_out[((size_t)b * p.N + n) * p.Q + q] = vis ? 1 : 0;
@@ -146,17 +148,8 @@ __global__ __launch_bounds__(256) void detr3d_v2_fwd_kernel(const Detr3dV2Params
     const float Y = rp[1] * p.rng_scale[1] + p.rng_lo[1];
     const float Z = rp[2] * p.rng_scale[2] + p.rng_lo[2];
     const float* m = p.lidar2img + ((size_t)b * p.N + n) * 16;
-    const float eps = 1e-5f;
-    const float cx = ((m[0] * X + m[1] * Y) + m[2] * Z) + m[3];
-    const float cy = ((m[4] * X + m[5] * Y) + m[6] * Z) + m[7];
-    const float cz = ((m[8] * X + m[9] * Y) + m[10] * Z) + m[11];
-    bool vis = cz > eps;
-    const float zc = fmaxf(cz, eps);
-    float u = (cx / zc) / p.img_w;
-    float v = (cy / zc) / p.img_h;
-    u = (u - 0.5f) * 2.f;                                     // :676
-    v = (v - 0.5f) * 2.f;
-    vis = vis && (u > -1.f) && (u < 1.f) && (v > -1.f) && (v < 1.f);
+    float cx, cy, cz, u, v;
+    const bool vis = project_grid(m, X, Y, Z, p.img_w, p.img_h, cx, cy, cz, u, v);
     s_uv[n] = make_float2(u, v);
     s_vis[n] = vis ? 1 : 0;
     if (p.mask_out) p.mask_out[((size_t)b * p.N + n) * p.Q + q] = vis ? 1 : 0;
@@ -257,17 +250,8 @@ __global__ __launch_bounds__(256) void detr3d_bwd_kernel(const Detr3dBwdParams p
   const float Z = rp[2] * p.rng_scale[2] + p.rng_lo[2];
   if (t < p.N) {
     const float* m = p.lidar2img + ((size_t)b * p.N + t) * 16;
-    const float eps = 1e-5f;
-    const float cx = ((m[0] * X + m[1] * Y) + m[2] * Z) + m[3];
-    const float cy = ((m[4] * X + m[5] * Y) + m[6] * Z) + m[7];
-    const float cz = ((m[8] * X + m[9] * Y) + m[10] * Z) + m[11];
-    bool vis = cz > eps;
-    const float zc = fmaxf(cz, eps);
-    float u = (cx / zc) / p.img_w;
-    float v = (cy / zc) / p.img_h;
-    u = (u - 0.5f) * 2.f;
-    v = (v - 0.5f) * 2.f;
-    vis = vis && (u > -1.f) && (u < 1.f) && (v > -1.f) && (v < 1.f);
+    float cx, cy, cz, u, v;
+    const bool vis = project_grid(m, X, Y, Z, p.img_w, p.img_h, cx, cy, cz, u, v);
     s_uv[t] = make_float2(u, v);
     s_cam[4 * t] = cx; s_cam[4 * t + 1] = cy; s_cam[4 * t + 2] = cz; s_cam[4 * t + 3] = vis ? 1.f : 0.f;
   }
@@ -317,10 +301,7 @@ __global__ __launch_bounds__(256) void detr3d_bwd_kernel(const Detr3dBwdParams p
         }
       }
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) part[k] += __shfl_xor(part[k], o);
-      }
+      for (int k = 0; k < 3; ++k) part[k] = wave_sum(part[k]);
       __syncthreads();                                        // (s_red of the previous level has been read)
       if (lane == 0) { s_red[wave * 3] = part[0]; s_red[wave * 3 + 1] = part[1]; s_red[wave * 3 + 2] = part[2]; }
       __syncthreads();
@@ -337,13 +318,9 @@ __global__ __launch_bounds__(256) void detr3d_bwd_kernel(const Detr3dBwdParams p
     if (t == 0) {
       const float* m = p.lidar2img + ((size_t)b * p.N + n) * 16;
       const float cx = s_cam[4 * n], cy = s_cam[4 * n + 1], cz = s_cam[4 * n + 2];
-      const float iz = 1.0f / cz;                             // visible: cz > eps
-      const float gcx = gu * iz / p.img_w;
-      const float gcy = gv * iz / p.img_h;
-      const float gcz = -(gu * cx * iz * iz / p.img_w + gv * cy * iz * iz / p.img_h);
-      s_pt[0] += gcx * m[0] + gcy * m[4] + gcz * m[8];
-      s_pt[1] += gcx * m[1] + gcy * m[5] + gcz * m[9];
-      s_pt[2] += gcx * m[2] + gcy * m[6] + gcz * m[10];
+      float gp[3];
+      project_adjoint(m, cx, cy, 1.0f / cz, gu, gv, p.img_w, p.img_h, gp);   // visible: cz > eps
+      s_pt[0] += gp[0]; s_pt[1] += gp[1]; s_pt[2] += gp[2];
     }
   }
   __syncthreads();
@@ -491,17 +468,8 @@ __global__ __launch_bounds__(256) void detr3d_v2_bwd_kernel(const Detr3dV2BwdPar
   const float Z = rp[2] * p.rng_scale[2] + p.rng_lo[2];
   if (t < p.N) {
     const float* m = p.lidar2img + ((size_t)b * p.N + t) * 16;
-    const float eps = 1e-5f;
-    const float cx = ((m[0] * X + m[1] * Y) + m[2] * Z) + m[3];
-    const float cy = ((m[4] * X + m[5] * Y) + m[6] * Z) + m[7];
-    const float cz = ((m[8] * X + m[9] * Y) + m[10] * Z) + m[11];
-    bool vis = cz > eps;
-    const float zc = fmaxf(cz, eps);
-    float u = (cx / zc) / p.img_w;
-    float v = (cy / zc) / p.img_h;
-    u = (u - 0.5f) * 2.f;
-    v = (v - 0.5f) * 2.f;
-    vis = vis && (u > -1.f) && (u < 1.f) && (v > -1.f) && (v < 1.f);
+    float cx, cy, cz, u, v;
+    const bool vis = project_grid(m, X, Y, Z, p.img_w, p.img_h, cx, cy, cz, u, v);
     s_uv[t] = make_float2(u, v);
     s_cam[4 * t] = cx; s_cam[4 * t + 1] = cy; s_cam[4 * t + 2] = cz; s_cam[4 * t + 3] = vis ? 1.f : 0.f;
   }
@@ -599,13 +567,9 @@ __global__ __launch_bounds__(256) void detr3d_v2_bwd_kernel(const Detr3dV2BwdPar
       const float gu = 2.f * ggx, gv = 2.f * ggy;             // g = (u - 0.5) 2
       const float* m = p.lidar2img + ((size_t)b * p.N + n) * 16;
       const float cx = s_cam[4 * n], cy = s_cam[4 * n + 1], cz = s_cam[4 * n + 2];
-      const float iz = 1.0f / cz;                             // visible: cz > eps
-      const float gcx = gu * iz / p.img_w;
-      const float gcy = gv * iz / p.img_h;
-      const float gcz = -(gu * cx * iz * iz / p.img_w + gv * cy * iz * iz / p.img_h);
-      s_pt[0] += gcx * m[0] + gcy * m[4] + gcz * m[8];
-      s_pt[1] += gcx * m[1] + gcy * m[5] + gcz * m[9];
-      s_pt[2] += gcx * m[2] + gcy * m[6] + gcz * m[10];
+      float gp[3];
+      project_adjoint(m, cx, cy, 1.0f / cz, gu, gv, p.img_w, p.img_h, gp);   // visible: cz > eps
+      s_pt[0] += gp[0]; s_pt[1] += gp[1]; s_pt[2] += gp[2];
     }
     __syncthreads();
   }
