@@ -208,6 +208,12 @@ SIGNATURES = {
     'gd4d_osa_concat_conv_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     'gd4d_ese_gate_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'gd4d_ese_apply_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'gd4d_conv1x1_image_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_conv1x1_image': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_conv1x1_bn_act_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    'gd4d_conv3x3_act_image_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_conv3x3_act_image': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_conv3x3_bn_act_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     'gd4d_conv3x3_image_t_bytes': (_c.c_size_t, [_i, _i]),
     'gd4d_conv3x3_image_t': (_i, [_vp, _i, _i, _vp, _vp]),
     'gd4d_osa_concat_image_t_bytes': (_c.c_size_t, [_i, _i]),

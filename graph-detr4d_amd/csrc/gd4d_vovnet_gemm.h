@@ -6,6 +6,10 @@
 //            tap-flipped) weight image, with the gradient that is already there added, the next layer's ReLU mask applied and the
 //            residual's gradient added after the mask.  add, mask, add2 are optional maps of the output's shape; add and add2 may be
 //            the output itself (an element is read before it is written, by the same thread).
+//   VV_RES   the ResNet blocks' (gd4d_resnet.hip): v = acc * scale[c] + shift[c]; v += identity[e] where there is one; max(v, 0) where
+//            relu is set; no pool sums.  BatchNorm, then the residual, then the ReLU: the block's own order.
+// MODE VV_P2 is the pointwise convolution with stride 2 (a stage's downsample): an 8 x 16 tile of OUTPUT pixels whose B operand is the
+// 128 input pixels (2 y, 2 x), staged as VV_OSA stages its 128 consecutive ones; gd4d_resnet.hip alone instantiates it.
 #pragma once
 #include "gd4d_common.h"
 #include "gd4d_bf16x3.h"
@@ -15,13 +19,14 @@ namespace gd4d {
 
 constexpr int VV_THREADS = 256, VV_KC = 32, VV_TY = 8, VV_TX = 16, VV_PIX = VV_TY * VV_TX;
 constexpr int VV_MAX_SRC = 6;
-enum { VV_S1 = 0, VV_S2 = 1, VV_OSA = 2 };
-enum { VV_FWD = 0, VV_BWD = 1 };
+enum { VV_S1 = 0, VV_S2 = 1, VV_OSA = 2, VV_P2 = 3 };
+enum { VV_FWD = 0, VV_BWD = 1, VV_RES = 2 };
 
 template <int MODE> struct VvGeom;
 template <> struct VvGeom<VV_S1> { static constexpr int TAPS = 9, STRIDE = 1, HE_H = VV_TY + 2, HE_W = VV_TX + 2, HBUF = 2; };
 template <> struct VvGeom<VV_S2> { static constexpr int TAPS = 9, STRIDE = 2, HE_H = 2 * VV_TY + 1, HE_W = 2 * VV_TX + 1, HBUF = 1; };
 template <> struct VvGeom<VV_OSA> { static constexpr int TAPS = 1, STRIDE = 1, HE_H = 1, HE_W = VV_PIX, HBUF = 2; };
+template <> struct VvGeom<VV_P2> { static constexpr int TAPS = 1, STRIDE = 2, HE_H = 1, HE_W = VV_PIX, HBUF = 2; };
 
 template <int MODE> constexpr int vv_halo() { return VvGeom<MODE>::HE_H * VvGeom<MODE>::HE_W; }
 template <int MODE> constexpr int vv_h_stage() { return 2 * 4 * vv_halo<MODE>() * 16; }               // hi + lo planes of one chunk
@@ -77,6 +82,8 @@ struct VvParams {
   float* out;
   float* partials;                // OSA: (N, tiles_img, cout)
   const float *add, *mask, *add2;  // VV_BWD: optional maps of the output's shape (appended: the forward's fields keep their offsets)
+  const float* identity;          // VV_RES: an optional map of the output's shape, added before the ReLU
+  int relu;                       // VV_RES: whether the ReLU runs
 };
 
 template <int MT, int MODE, int EPI = VV_FWD>
@@ -116,6 +123,10 @@ __global__ __launch_bounds__(VV_THREADS) void vv_gemm_kernel(const VvParams p) {
       const size_t pix = (size_t)tx0 + hp;
       h_in[ps] = it < H_ITEMS && pix < HW;
       h_off[ps] = h_in[ps] ? (int)pix : 0;
+    } else if (MODE == VV_P2) {                               // the input pixel under output pixel hp of the tile: no halo, no padding
+      const int y = 2 * (ty0 + hp / VV_TX), x = 2 * (tx0 + hp % VV_TX);
+      h_in[ps] = it < H_ITEMS && y < H && x < W;
+      h_off[ps] = h_in[ps] ? y * W + x : 0;
     } else {
       const int y = ty0 * S - 1 + hp / HE_W, x = tx0 * S - 1 + hp % HE_W;
       h_in[ps] = it < H_ITEMS && y >= 0 && y < H && x >= 0 && x < W;
@@ -175,7 +186,7 @@ __global__ __launch_bounds__(VV_THREADS) void vv_gemm_kernel(const VvParams p) {
   // B fragments: pixel pp = 32 wave + l32 of the tile; its halo entry for tap (ky, kx) is (S py + ky) * HE_W + S px + kx
   const int pp = 32 * wave + l32;
   const int py = pp >> 4, px = pp & 15;
-  const int pix_hp = MODE == VV_OSA ? pp : (py * S) * HE_W + px * S;
+  const int pix_hp = MODE == VV_OSA || MODE == VV_P2 ? pp : (py * S) * HE_W + px * S;
 
   issue_halo(0);
   park_halo(0);
@@ -245,6 +256,22 @@ __global__ __launch_bounds__(VV_THREADS) void vv_gemm_kernel(const VvParams p) {
         if (p.add) v = v + p.add[e];
         if (p.mask && !(p.mask[e] > 0.f)) v = 0.f;           // strict, as torch's ReLU
         if (p.add2) v = v + p.add2[e];
+        p.out[e] = v;
+      }
+    return;
+  }
+  if constexpr (EPI == VV_RES) {
+    if (!ok) return;
+    const size_t o = ((size_t)img * p.cout + crow0) * plane + off;
+#pragma unroll
+    for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int cl = 32 * mi + 4 * kg + (r & 3) + 8 * (r >> 2);
+        const size_t e = o + (size_t)cl * plane;
+        float v = acc[mi][r] * p.scale[crow0 + cl] + p.shift[crow0 + cl];
+        if (p.identity) v = v + p.identity[e];
+        if (p.relu) v = fmaxf(v, 0.f);
         p.out[e] = v;
       }
     return;

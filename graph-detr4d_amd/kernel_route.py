@@ -1,6 +1,6 @@
 """The host-side skeleton of the modules that run on the bf16-MFMA convolution kernels: DepthNet, FPN / CPFPN, the two DCNv2 classes,
-VoVNet's stem and OSA module.  Each mixes in `KernelRoute` and supplies its name for messages, its limits and what train mode means
-for it; the route rule, the refusals, the values kept from parameters, `refresh_images()` and the input cast are stated here, once.
+VoVNet's stem and OSA module, ResNet's blocks with `plain_kernels=True`.  Each mixes in `KernelRoute` and supplies its name for
+messages, its limits and what train mode means for it; the route rule, the refusals, the values kept from parameters, `refresh_images()` and the input cast are stated here, once.
 
 THE ROUTE RULE.  `_route(*inputs)` answers, per call, in this order:
     1. chosen     `module.torch_ops` (the constructor keyword `torch_ops=True`, `with Fn.torch_ops_for(module):`) or GD4D_TORCH_OPS=1

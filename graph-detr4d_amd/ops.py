@@ -3351,6 +3351,63 @@ def ese_apply(xt, gate, identity=None, out=None):
     return out
 
 
+# ---- ResNet: the blocks' plain convolutions + frozen BN (+ identity) (+ ReLU) (gd4d_resnet.hip) ---------------------------------
+_CONV1X1_LIMITS = 'K a multiple of 32 in [32, 2304] and Cout a multiple of 32 in [32, 2048]'
+_CONV3X3_ACT_LIMITS = 'Cin a multiple of 32 in [32, 1024] and Cout a multiple of 32 in [32, 512]'
+
+
+def conv1x1_image(weight):
+    """gd4d_conv1x1_image: a 1x1 convolution's weight (Cout, K) or (Cout, K, 1, 1) fp32 -> its bf16 hi / lo fragment image.  K a multiple
+    of 32 in [32, 2304], Cout a multiple of 32 in [32, 2048].  Remake it when the weight changes."""
+    if weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1):
+        weight = weight.reshape(weight.shape[0], weight.shape[1])
+    if weight.dim() != 2:
+        raise _lib.Gd4dError(f'conv1x1_image: weight {tuple(weight.shape)}; the kernel takes (Cout, K) or (Cout, K, 1, 1)')
+    cout, k = int(weight.shape[0]), int(weight.shape[1])
+    return _weight_image('gd4d_conv1x1_image', int(_lib.load().gd4d_conv1x1_image_bytes(k, cout)),
+                         f'conv1x1_image: weight {tuple(weight.shape)}; the kernel takes {_CONV1X1_LIMITS}', weight, k, cout)
+
+
+def conv3x3_act_image(weight):
+    """gd4d_conv3x3_act_image: conv3x3_image for conv3x3_bn_act, whose Cout reaches 512: Cin a multiple of 32 in [32, 1024], Cout a
+    multiple of 32 in [32, 512]; the same bytes as conv3x3_image where both take the weight."""
+    return _conv3x3_weight_image('conv3x3_act_image', 'gd4d_conv3x3_act_image', weight, 'the kernel takes', _CONV3X3_ACT_LIMITS)
+
+
+def _conv_bn_act(name, taps, x, image, cout, scale, shift, stride, identity, relu, out, m_blocks):
+    lib = _lib.load()
+    n, cin, h, w = _dcn_x(x, name)
+    cout = int(cout)
+    ho, wo = dcn_out_hw(h, w, stride)
+    for t, what in ((scale, 'scale'), (shift, 'shift')):
+        if tuple(t.shape) != (cout,):
+            raise ValueError(f'{name}: {what} must be ({cout},)')
+    if identity is not None and tuple(identity.shape) != (n, cout, ho, wo):
+        raise ValueError(f'{name}: identity must be ({n}, {cout}, {ho}, {wo}), got {tuple(identity.shape)}')
+    nbytes = int((lib.gd4d_conv3x3_act_image_bytes if taps == 9 else lib.gd4d_conv1x1_image_bytes)(cin, cout))
+    if nbytes == 0 or nbytes != image.numel():
+        made, shape, limits = ('conv3x3_act_image', f'({cout}, {cin}, 3, 3)', _CONV3X3_ACT_LIMITS) if taps == 9 else \
+            ('conv1x1_image', f'({cout}, {cin})', _CONV1X1_LIMITS)
+        raise _lib.Gd4dError(f'{name}: the image is not {made} of a {shape} weight the kernel takes ({limits})')
+    out = _out(out, (n, cout, ho, wo), x.device, f'{name}: out')
+    _call(f'gd4d_{name}_fwd', _dev(x, 'x', F32), n, cin, h, w, int(stride), _dev(image, 'image', U8), cout, _dev(scale, 'scale', F32),
+          _dev(shift, 'shift', F32), _opt(identity, 'identity'), int(bool(relu)), _dev(out, 'out', F32), int(m_blocks))
+    return out
+
+
+def conv1x1_bn_act(x, image, cout, scale, shift, stride=1, identity=None, relu=True, out=None, m_blocks=0):
+    """gd4d_conv1x1_bn_act_fwd: x (N, Cin, H, W) fp32 NCHW -> act(conv1x1(x; stride 1 or 2) * scale + shift (+ identity)), (N, cout, Ho,
+    Wo); image = conv1x1_image(weight), scale / shift (cout) the folded frozen BatchNorm, identity an optional map of the result's shape
+    (added before the ReLU), act the ReLU unless relu=False (a downsample branch).  m_blocks: as conv3x3_bn_relu's."""
+    return _conv_bn_act('conv1x1_bn_act', 1, x, image, cout, scale, shift, stride, identity, relu, out, m_blocks)
+
+
+def conv3x3_bn_act(x, image, cout, scale, shift, stride=1, identity=None, relu=True, out=None, m_blocks=0):
+    """gd4d_conv3x3_bn_act_fwd: conv1x1_bn_act's counterpart for the 3x3 (pad 1); image = conv3x3_act_image(weight) (or conv3x3_image's:
+    the same bytes).  With identity=None and relu=True it gives conv3x3_bn_relu's bits."""
+    return _conv_bn_act('conv3x3_bn_act', 9, x, image, cout, scale, shift, stride, identity, relu, out, m_blocks)
+
+
 # ---- VoVNet, training behind frozen BatchNorms (gd4d_vovnet_train.hip) ----------------------------------------------------------
 def conv3x3_image_t(weight, scale=None):
     """gd4d_conv3x3_image_t: the image conv3x3_dgrad reads, of the (Cout, Cin, 3, 3) fp32 weight times scale[co] (the folded BatchNorm's;

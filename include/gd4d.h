@@ -1639,6 +1639,26 @@ int gd4d_ese_gate_fwd(const float* partials, int n, int tiles, int channels, int
                       void* stream);
 int gd4d_ese_apply_fwd(const float* xt, const float* gate, const float* identity, int n, int channels, int hw, float* out, void* stream);
 
+/* ResNet (mmdet's Bottleneck and BasicBlock), the plain convolutions with frozen BatchNorm, inference (gd4d_resnet.hip; additive exports,
+ * the ABI version stays).  Maps contiguous NCHW fp32; the VoVNet GEMM and its arithmetic: two runs and every M tiling give the same bits.
+ * gd4d_conv1x1_image - a (cout, k) fp32 weight of a 1x1 convolution as gd4d_osa_concat_image packs it; k a multiple of 32 in [32, 2304],
+ *   cout a multiple of 32 in [32, 2048]; gd4d_conv1x1_image_bytes(k, cout) bytes (0: outside the limits), 16-B aligned.
+ * gd4d_conv3x3_act_image - a (cout, cin, 3, 3) fp32 weight in gd4d_conv3x3_image's format; cin a multiple of 32 in [32, 1024], cout a
+ *   multiple of 32 in [32, 512]; gd4d_conv3x3_act_image_bytes(cin, cout) bytes.
+ * gd4d_conv1x1_bn_act_fwd / gd4d_conv3x3_bn_act_fwd - out (N, cout, Ho, Wo) = act(conv(x; stride 1 or 2, 3x3: pad 1, no bias) * scale[co] +
+ *   shift[co] (+ identity)), Ho = (H - 1) / stride + 1, Wo likewise; identity: NULL or a map of out's shape, added after the folded
+ *   BatchNorm and before the ReLU; act: ReLU where relu != 0, else nothing (a downsample branch).  m_blocks as the VoVNet GEMMs'.
+ * A NULL required pointer: GD4D_EINVAL; channels, stride or m_blocks outside the limits, N / h / w <= 0, more than 2^30 pixels in one
+ *   plane: GD4D_EUNSUPPORTED; a misaligned image: GD4D_EALIGN. */
+size_t gd4d_conv1x1_image_bytes(int k, int cout);
+int gd4d_conv1x1_image(const float* weight, int k, int cout, void* image, void* stream);
+int gd4d_conv1x1_bn_act_fwd(const float* x, int n, int cin, int h, int w, int stride, const void* image, int cout, const float* scale,
+                            const float* shift, const float* identity, int relu, float* out, int m_blocks, void* stream);
+size_t gd4d_conv3x3_act_image_bytes(int cin, int cout);
+int gd4d_conv3x3_act_image(const float* weight, int cin, int cout, void* image, void* stream);
+int gd4d_conv3x3_bn_act_fwd(const float* x, int n, int cin, int h, int w, int stride, const void* image, int cout, const float* scale,
+                            const float* shift, const float* identity, int relu, float* out, int m_blocks, void* stream);
+
 /* VoVNet, training of one OSA module behind frozen BatchNorms (gd4d_vovnet_train.hip has the arithmetic; additive exports, the ABI version
  * stays).  Maps contiguous NCHW fp32; split-bf16 x 3 products, fp32 sums in a fixed order, no atomics: two runs give the same bits.  dz is
  * always the gradient of a BatchNorm's OUTPUT after the ReLU mask (unscaled); bn is (3, cout) fp32: scale = gamma rstd, rstd, mean.
