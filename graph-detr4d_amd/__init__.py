@@ -27,9 +27,12 @@ from .backbones import BasicBlock, Bottleneck, ResNet, VoVNet, VoVNetCP  # noqa:
 from . import functional, plumbing  # noqa: F401
 from .detr3d_transformer import (Detr3DCrossAtten, Detr3DCrossAttenV2, Detr3DTransformer, Detr3DTransformerDecoder,  # noqa: F401
                                  HDetr3DTransformer, feature_sampling, inverse_sigmoid)
+from .petr_transformer import (PETRMultiheadAttention, PETRTransformer, PETRTransformerDecoder,  # noqa: F401
+                               PETRTransformerDecoderLayer, PETRTransformerEncoder)
 
 __all__ = ['Deform3DCrossAttn', 'Deform3DCrossAttnMP', 'DGCNNAttn', 'Detr3DCrossAtten', 'Detr3DCrossAttenV2', 'feature_sampling', 'Detr3DTransformer',
            'Detr3DTransformerDecoder', 'HDetr3DTransformer', 'MultiheadAttention', 'FFN', 'BaseTransformerLayer',
            'DetrTransformerDecoderLayer', 'TransformerLayerSequence', 'inverse_sigmoid',
            'NMSFreeCoder', 'HungarianAssigner3D', 'Detr3DCriterion', 'HDetr3DCriterion', 'DistillHungarianAssigner3D', 'get_instance_distill_loss', 'FeatureDistillLoss', 'get_feat_distill_loss', 'FeaturePositionEmbedding', 'DepthNet', 'TrainRecipe', 'GridMask', 'FPN', 'CPFPN', 'NECKS', 'build_neck', 'ModulatedDeformConv2d', 'ModulatedDeformConv2dPack', 'CONV_LAYERS', 'build_conv_layer',
-           'BasicBlock', 'Bottleneck', 'ResNet', 'VoVNet', 'VoVNetCP', 'BACKBONES', 'build_backbone', 'BBOX_CODERS', 'BBOX_ASSIGNERS', 'ATTENTION', 'TRANSFORMER', 'TRANSFORMER_LAYER', 'TRANSFORMER_LAYER_SEQUENCE']
+           'BasicBlock', 'Bottleneck', 'ResNet', 'VoVNet', 'VoVNetCP', 'BACKBONES', 'build_backbone', 'BBOX_CODERS', 'BBOX_ASSIGNERS', 'ATTENTION', 'TRANSFORMER', 'TRANSFORMER_LAYER', 'TRANSFORMER_LAYER_SEQUENCE',
+           'PETRMultiheadAttention', 'PETRTransformer', 'PETRTransformerDecoder', 'PETRTransformerDecoderLayer', 'PETRTransformerEncoder']

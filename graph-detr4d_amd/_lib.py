@@ -114,6 +114,11 @@ SIGNATURES = {
     'gd4d_row_chain_fwd': (_i, [_vp, _i, _i, _vp]),
     'gd4d_row_chain2_fwd': (_i, [_vp, _i, _vp, _i, _i, _vp]),
     'gd4d_mha_core_presplit_fwd': (_i, [_vp] * 4 + [_i] * 5 + [_c.c_longlong, _c.c_longlong, _vp, _i, _f, _vp, _f, _vp, _vp]),
+    'gd4d_cross_mha_plan': (_i, [_i] * 6 + [_vp]),
+    'gd4d_cross_mha_plane_elems': (_c.c_size_t, [_i] * 3),
+    'gd4d_cross_mha_workspace_bytes': (_c.c_size_t, [_i] * 6),
+    'gd4d_cross_mha_pack_kv': (_i, [_vp, _vp, _i, _i, _vp, _vp, _c.c_longlong] + [_i] * 4 + [_vp]),
+    'gd4d_cross_mha_fwd': (_i, [_vp, _vp, _vp, _c.c_longlong, _vp, _vp, _vp, _vp, _c.c_size_t] + [_i] * 7 + [_f, _i, _i, _vp]),
     'gd4d_xcd_placement_probe': (_i, [_vp, _i, _vp]),
     'gd4d_mlp2_image_bytes': (_c.c_size_t, [_i] * 3),
     'gd4d_mlp2_image': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),

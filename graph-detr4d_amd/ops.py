@@ -2394,6 +2394,112 @@ def mha_core_presplit_fwd(q, kv, num_heads, attn_mask=None, want_lse=False, drop
     return (out, lse) if want_lse else out
 
 
+CROSS_MHA_MAX_SPLITS = 64
+
+
+class CrossKV:
+    """The keys and values of one cross-attention layer as split-bf16 planes in the MFMA fragment layout of gd4d_cross_mha_fwd
+    (include/gd4d.h has the layouts): k (3 = hi | mid | lo, B, H, steps of 32 keys, 2, 64, 8) and v (2 = hi | lo, ...) bf16 - the
+    scores are taken on six products, the second product on three.  cross_mha_pack_kv fills them."""
+
+    def __init__(self, lk, b, device, heads=8):
+        self.lk, self.b, self.heads, self.c = int(lk), int(b), int(heads), 32 * int(heads)
+        self.steps = (self.lk + 31) // 32
+        if torch.device(device).type != 'cuda':
+            raise _lib.Gd4dError('CrossKV must live on the GPU (no CPU fallback in graph-detr4d_amd)')
+        self.k = torch.empty(3, self.b, heads, self.steps, 2, 64, 8, device=device, dtype=torch.bfloat16)
+        self.v = torch.empty(2, self.b, heads, self.steps, 2, 64, 8, device=device, dtype=torch.bfloat16)
+
+    @property
+    def plane(self):
+        return self.k[0].numel()
+
+    def k_rows(self):
+        """(3, steps * 32, B, C): the planes as plain rows (tests)."""
+        b, h, s = self.b, self.heads, self.steps
+        # [plane][b][h][s][t][g][key % 16][c % 8]  ->  key = 32 s + 16 t + key % 16, channel = 32 h + 8 g + c % 8
+        return self.k.view(3, b, h, s, 2, 4, 16, 8).permute(0, 3, 4, 6, 1, 2, 5, 7).reshape(3, s * 32, b, h * 32)
+
+    def v_rows(self):
+        """(2, steps * 32, B, C): the planes as plain rows (tests)."""
+        b, h, s = self.b, self.heads, self.steps
+        # [plane][b][h][s][half][g][d % 16][t][r]  ->  key = 32 s + 16 t + 4 g + r, channel = 32 h + 16 half + d % 16
+        return self.v.view(2, b, h, s, 2, 4, 16, 2, 4).permute(0, 3, 7, 5, 8, 1, 2, 4, 6).reshape(2, s * 32, b, h * 32)
+
+
+def _rows_lbc(t, name):
+    """The row stride of a float32 GPU tensor (L, B, C') addressed as rows l B + b: contiguous, or a last-dim slice of a wider one."""
+    if not t.is_cuda or t.dtype != F32:
+        raise _lib.Gd4dError(f'{name} must be a float32 GPU tensor')
+    if t.dim() != 3 or t.stride(2) != 1 or t.stride(0) != t.stride(1) * t.shape[1]:
+        raise ValueError(f'{name} must be row-strided (L, B, C)')
+    return t.stride(1)
+
+
+def cross_mha_pack_kv(k, v, kv=None, num_heads=8):
+    """gd4d_cross_mha_pack_kv: k, v (Lk, B, C) float32 - contiguous, or the two halves of one (Lk, B, 2C) projection - split to bf16
+    pieces once (k: hi / mid / lo, v: hi / lo), into the planes gd4d_cross_mha_fwd reads (pad keys of the last step written as zeros).  Returns the CrossKV."""
+    ldk, ldv = _rows_lbc(k, 'k'), _rows_lbc(v, 'v')
+    lk, b, c = k.shape
+    if tuple(v.shape) != (lk, b, c) or c != 32 * num_heads:
+        raise ValueError('cross_mha_pack_kv: k and v (Lk, B, 32 heads)')
+    if kv is None:
+        kv = CrossKV(lk, b, k.device, num_heads)
+    elif (kv.lk, kv.b, kv.heads) != (lk, b, num_heads):
+        raise ValueError('cross_mha_pack_kv: the planes were made for another shape')
+    _call('gd4d_cross_mha_pack_kv', ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(v.data_ptr()), ldk, ldv, _dev(kv.k, 'kv.k'),
+          _dev(kv.v, 'kv.v'), kv.plane, lk, b, num_heads, 32)
+    return kv
+
+
+class CrossMhaPlan:
+    """cross_mha_plan's answer: q_tile queries per workgroup, `splits` key ranges of whole 32-key steps - ranges[i] = [first, last)
+    keys of split i - and the launch's grid (query blocks, heads x splits, batch)."""
+
+    def __init__(self, raw, lk):
+        self.q_tile, self.splits, self.steps = raw[0], raw[1], raw[2]
+        self.grid = (raw[3], raw[4], raw[5])
+        self.ranges = [(32 * raw[6 + i], min(int(lk), 32 * raw[7 + i])) for i in range(self.splits)]
+
+    @property
+    def workgroups(self):
+        return self.grid[0] * self.grid[1] * self.grid[2]
+
+
+def cross_mha_plan(lq, lk, b, heads=8, q_tile=0, splits=0):
+    """gd4d_cross_mha_plan (no GPU): how cross_mha_fwd divides (lq, lk, b, heads) among workgroups.  q_tile / splits: 0 = the
+    library's choice (what a cross_mha_fwd call without them uses)."""
+    raw = (ctypes.c_int32 * (7 + CROSS_MHA_MAX_SPLITS))()
+    _lib.check(_lib.load().gd4d_cross_mha_plan(int(lq), int(lk), int(b), int(heads), int(q_tile), int(splits), raw), 'gd4d_cross_mha_plan')
+    return CrossMhaPlan(list(raw), lk)
+
+
+def cross_mha_fwd(q, kv, num_heads, key_padding_mask=None, want_lse=False, q_tile=0, splits=0):
+    """gd4d_cross_mha_fwd: softmax(q k^T / sqrt(32) + key-padding mask) v on the planes of `kv` (CrossKV).  q (Lq, B, C) float32,
+    contiguous or a last-dim slice; key_padding_mask (B, Lk) bool / uint8, nonzero = ignore the key.  Returns (Lq, B, C) [, lse
+    (Lq, B, heads)].  q_tile / splits: cross_mha_plan's (0 = the library's choice)."""
+    ldq = _rows_lbc(q, 'q')
+    lq, b, c = q.shape
+    if not isinstance(kv, CrossKV):
+        raise TypeError('cross_mha_fwd: kv must be a CrossKV (cross_mha_pack_kv)')
+    if b != kv.b or c != kv.c or num_heads != kv.heads:
+        raise ValueError('cross_mha_fwd: the planes were made for another batch, width or head count')
+    mptr = None
+    if key_padding_mask is not None:
+        if key_padding_mask.dtype not in (torch.bool, U8) or tuple(key_padding_mask.shape) != (b, kv.lk):
+            raise ValueError(f'key_padding_mask must be bool / uint8 ({b}, {kv.lk})')
+        key_padding_mask = key_padding_mask.contiguous().view(U8)
+        mptr = _dev(key_padding_mask, 'key_padding_mask', U8)
+    lib = _lib.load()
+    ws_bytes = int(lib.gd4d_cross_mha_workspace_bytes(lq, kv.lk, b, num_heads, int(q_tile), int(splits)))
+    ws = torch.empty(ws_bytes // 4, device=q.device, dtype=F32) if ws_bytes else None
+    out = torch.empty(lq, b, c, device=q.device, dtype=F32)
+    lse = torch.empty(lq, b, num_heads, device=q.device, dtype=F32) if want_lse else None
+    _call('gd4d_cross_mha_fwd', ctypes.c_void_p(q.data_ptr()), _dev(kv.k, 'kv.k'), _dev(kv.v, 'kv.v'), kv.plane, mptr, _dev(out, 'out'),
+          _opt(lse, 'lse'), _opt(ws, 'workspace'), ws_bytes, lq, kv.lk, b, num_heads, 32, ldq, c, 1.0 / (32 ** 0.5), int(q_tile), int(splits))
+    return (out, lse) if want_lse else out
+
+
 class RequestRef(ctypes.Structure):
     """gd4d_request_ref (include/gd4d.h)."""
     _fields_ = [('binding', ctypes.c_int32), ('reserved', ctypes.c_int32), ('value', ctypes.c_int64)]
@@ -3594,7 +3700,7 @@ def _on_tensor_device(fn):
 
 
 _HOST_ONLY = {'linear_sum_assignment_batch', 'cross_attn_plan_bytes', 'invalidate_chain_images', 'kept_in_place', 'chain_load', 'chain_gemm', 'chain_small_linear', 'chain_layernorm',
-              'chain_add', 'chain_refine', 'row_chain_fwd', 'chain_weight_image', 'chain_layernorm_bwd'}
+              'chain_add', 'chain_refine', 'row_chain_fwd', 'chain_weight_image', 'chain_layernorm_bwd', 'cross_mha_plan'}
 for _name, _fn in list(globals().items()):
     if inspect.isfunction(_fn) and _fn.__module__ == __name__ and not _name.startswith('_') and _name not in _HOST_ONLY:
         globals()[_name] = _on_tensor_device(_fn)

@@ -758,6 +758,44 @@ int gd4d_mha_core_presplit_fwd(const float* q, const void* k_planes, const void*
                                int ldq, int ldo, long long k_plane_stride, long long v_plane_stride, const void* mask,
                                int mask_kind, float scale, float* lse, float drop_p, const void* seed, void* stream);
 
+/* gd4d_cross_mha_fwd - dense cross-attention over a long key axis with a key-padding mask (gd4d_cross_mha.hip): PETR's global
+ * cross-attention, 900 queries x every pixel of every camera (projects/mmdet3d_plugin/models/utils/petr_transformer.py,
+ * PETRMultiheadAttention -> nn.MultiheadAttention with key_padding_mask).  Inference only: no dropout, no (Lq, Lk) mask.
+ *   out = softmax(q k^T scale + mask) v per (batch, head) in split-bf16 arithmetic with fp32 accumulation and a base-2 online
+ *   softmax, as gd4d_mha_core_fwd - except that the scores take SIX bf16 MFMAs (q and k as hi + mid + lo, ~2^-24: a row that one key
+ *   dominates has that key's score as its lse, and three products leave 1.6e-4 on a score of 57); P V takes three.
+ *   q (Lq, B, H D) fp32, row (l B + b) at stride ldq; out the same at stride ldo; lse (Lq, B, H) or NULL: the natural-log sum of
+ *   exp(scaled, masked scores).  D = 32 and H = 8 (GD4D_EUNSUPPORTED otherwise).
+ *   key_padding_mask: (B, Lk) bytes, nonzero = ignore the key, or NULL.  A (query, batch) row whose keys are all masked is NaN in
+ *   every channel (as ATen), its lse -inf; other rows are unaffected.
+ *   k_planes / v_planes: the keys split to bf16 hi / mid / lo and the values to hi / lo ONCE (gd4d_cross_mha_pack_kv), in the MFMA
+ *   fragment layout, each plane plane_stride elements after the one before - k_planes holds three, v_planes two (plane_stride >=
+ *   gd4d_cross_mha_plane_elems(Lk, B, H), a multiple of 8):
+ *     K [plane][b][h][step of 32 keys][t][lane = 16 (c / 8) + key % 16][8 channels 8 (c / 8) ..], key = 32 step + 16 t + key % 16
+ *     V [plane][b][h][step][half = d / 16][lane = 16 g + d % 16][j], key = 32 step + 16 (j >> 2) + 4 g + (j & 3)
+ *   The pack writes the pad keys of the last step as zeros; the core gives them probability 0.
+ *   A workgroup owns q_tile queries (64, or 32; 0 = 64) of one (batch, head) and one of `splits` key ranges (0 = chosen by
+ *   gd4d_cross_mha_plan, at most GD4D_CROSS_MHA_MAX_SPLITS); with splits > 1 the ranges' partials go through `workspace`
+ *   (gd4d_cross_mha_workspace_bytes; GD4D_EWORKSPACE if NULL or smaller) and a second small kernel merges them.
+ * gd4d_cross_mha_plan (no GPU): plan[0..5] = q_tile, splits, key steps, grid x (query blocks), grid y (H splits), grid z (B);
+ *   plan[6 .. 6 + splits] = the first key step of each split and, last, the number of steps: split i owns keys
+ *   [32 plan[6 + i], min(Lk, 32 plan[7 + i])).  Splits are whole steps, every step is in exactly one, none is empty unless splits >
+ *   steps was asked for.  plan holds 7 + GD4D_CROSS_MHA_MAX_SPLITS entries.
+ * gd4d_cross_mha_pack_kv: k / v fp32 rows (l B + b) at strides ldk / ldv (the two halves of one (Lk, B, 512) projection, or two
+ *   tensors) -> the planes.  Every element of every fragment of ceil(Lk / 32) steps is written.
+ * GD4D_EINVAL: a NULL q / planes / out (k / v), sizes <= 0, strides below H D, a short plane_stride; GD4D_EALIGN: q, k or the planes
+ * not 16-byte aligned, ldq / ldk not a multiple of 4; all before any GPU work. */
+#define GD4D_CROSS_MHA_MAX_SPLITS 64
+int gd4d_cross_mha_plan(int Lq, int Lk, int B, int H, int q_tile, int splits, int32_t* plan);
+size_t gd4d_cross_mha_plane_elems(int Lk, int B, int H);
+size_t gd4d_cross_mha_workspace_bytes(int Lq, int Lk, int B, int H, int q_tile, int splits);
+int gd4d_cross_mha_pack_kv(const float* k, const float* v, int ldk, int ldv, void* k_planes, void* v_planes,
+                           long long plane_stride, int Lk, int B, int H, int D, void* stream);
+int gd4d_cross_mha_fwd(const float* q, const void* k_planes, const void* v_planes, long long plane_stride,
+                       const void* key_padding_mask, float* out, float* lse, void* workspace, size_t workspace_bytes,
+                       int Lq, int Lk, int B, int H, int D, int ldq, int ldo, float scale, int q_tile, int splits,
+                       void* stream);
+
 /* gd4d_mlp2_bf16x3_fwd - out = relu(x W1^T + b1) W2^T + b2 in ONE kernel (gd4d_mlp2.hip): the head's position-embedding MLPs -
  * Conv1x1, ReLU, Conv1x1 over every pixel of every camera (dense_heads/detr3d_head_pe.py:380-390 `position_encoder`, applied at
  * :543-553: 192 -> 1024 -> 256 over 739 800 pixels at 24 cameras).  The hidden activation (3 GB as a tensor) stays in registers:

@@ -338,6 +338,14 @@ class TransformerLayerSequence(BaseModule):
         self.embed_dims = self.layers[0].embed_dims
         self.pre_norm = self.layers[0].pre_norm
 
+    def forward(self, query, key, value, query_pos=None, key_pos=None, attn_masks=None,
+                query_key_padding_mask=None, key_padding_mask=None, **kwargs):
+        # mmcv 1.x: every layer gets the same keys, values and masks (the PETR sequences call this through super())
+        for layer in self.layers:
+            query = layer(query, key, value, query_pos=query_pos, key_pos=key_pos, attn_masks=attn_masks,
+                          query_key_padding_mask=query_key_padding_mask, key_padding_mask=key_padding_mask, **kwargs)
+        return query
+
 
 def build_transformer_layer_sequence(cfg, default_args=None):
     return TRANSFORMER_LAYER_SEQUENCE.build(cfg, **(default_args or {}))
@@ -759,3 +767,48 @@ def load_vovnet():
                 spec.loader.exec_module(mod)
         mods.append(sys.modules[full])
     return tuple(mods)
+
+
+# --------------------------------------------------------------------------------------
+# PETR's transformer (global cross-attention over every pixel of every camera)
+# --------------------------------------------------------------------------------------
+def _build_dropout(cfg, default_args=None):
+    cfg = dict(cfg)
+    typ = cfg.pop('type')
+    if typ != 'Dropout':
+        raise KeyError(f'dropout layer {typ}: only mmcv\'s Dropout (= nn.Dropout with drop_prob) is stubbed')
+    return nn.Dropout(cfg.get('drop_prob', 0.5), cfg.get('inplace', False))
+
+
+def _build_norm_layer(cfg, num_features, postfix=''):
+    if cfg.get('type') != 'LN':
+        raise KeyError(f'norm layer {cfg.get("type")}: only LN is stubbed')
+    return 'ln' + str(postfix), nn.LayerNorm(num_features, eps=cfg.get('eps', 1e-5))
+
+
+def _deprecated_api_warning(name_dict, cls_name=None):
+    """mmcv.utils.deprecated_api_warning: renames deprecated keyword arguments (here: residual -> identity)."""
+    def wrap(fn):
+        def inner(*args, **kwargs):
+            for old, new in name_dict.items():
+                if old in kwargs:
+                    kwargs[new] = kwargs.pop(old)
+            return fn(*args, **kwargs)
+        inner.__wrapped__ = fn
+        return inner
+    return wrap
+
+
+def load_petr_transformer():
+    """Import the reference's models/utils/petr_transformer.py unmodified and return the module.  Stand-ins: build_dropout,
+    build_norm_layer (LN), the mmcv.utils names it imports, and TransformerLayerSequence.forward above; its
+    PETRMultiheadAttention wraps torch's own nn.MultiheadAttention, so what it computes is the reference's arithmetic."""
+    install_stubs()
+    _mod('mmcv.cnn.bricks.drop', build_dropout=_build_dropout)
+    cnn = sys.modules['mmcv.cnn']
+    cnn.build_activation_layer = lambda cfg: nn.ReLU(inplace=cfg.get('inplace', False))
+    cnn.build_conv_layer = None                                  # imported, never called
+    cnn.build_norm_layer = _build_norm_layer
+    _mod('mmcv.utils', ConfigDict=dict, build_from_cfg=lambda cfg, registry, default_args=None: registry.build(cfg, **(default_args or {})),
+         deprecated_api_warning=_deprecated_api_warning, to_2tuple=lambda x: (x, x))
+    return load_reference(('petr_transformer',))['petr_transformer']
