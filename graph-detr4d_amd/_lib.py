@@ -119,6 +119,11 @@ SIGNATURES = {
     'gd4d_cross_mha_workspace_bytes': (_c.c_size_t, [_i] * 6),
     'gd4d_cross_mha_pack_kv': (_i, [_vp, _vp, _i, _i, _vp, _vp, _c.c_longlong] + [_i] * 4 + [_vp]),
     'gd4d_cross_mha_fwd': (_i, [_vp, _vp, _vp, _c.c_longlong, _vp, _vp, _vp, _vp, _c.c_size_t] + [_i] * 7 + [_f, _i, _i, _vp]),
+    'gd4d_cross_mha_train_fwd': (_i, [_vp, _vp, _vp, _c.c_longlong, _vp, _vp, _vp, _vp, _c.c_size_t] + [_i] * 7 + [_f, _i, _i, _f, _vp, _vp]),
+    'gd4d_cross_mha_pack_kv_train': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _c.c_longlong] + [_i] * 4 + [_vp]),
+    'gd4d_cross_mha_bwd_plan': (_i, [_i] * 6 + [_vp]),
+    'gd4d_cross_mha_bwd_workspace_bytes': (_c.c_size_t, [_i] * 6),
+    'gd4d_cross_mha_bwd': (_i, [_vp] * 7 + [_c.c_longlong] + [_vp] * 5 + [_c.c_size_t] + [_i] * 11 + [_f, _f, _vp, _i, _i, _vp]),
     'gd4d_xcd_placement_probe': (_i, [_vp, _i, _vp]),
     'gd4d_mlp2_image_bytes': (_c.c_size_t, [_i] * 3),
     'gd4d_mlp2_image': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -9,7 +9,9 @@ Inference takes the fully fused HIP path (functional.py); with autograd enabled 
   * LinearFunction     - gd4d_linear_fwd forward, gd4d_linear_fwd with the transposed-weight flag for the input
                          gradient, gd4d_linear_bwd_weight for the weight / bias gradient;
   * LayerNormFunction  - gd4d_layernorm_fwd / gd4d_layernorm_bwd (optionally with the ReLU that follows);
-  * MhaCoreFunction    - gd4d_mha_core_fwd (saving the log-sum-exp) / gd4d_mha_core_bwd.
+  * MhaCoreFunction    - gd4d_mha_core_fwd (saving the log-sum-exp) / gd4d_mha_core_bwd;
+  * CrossMhaFunction   - gd4d_cross_mha_train_fwd / gd4d_cross_mha_bwd: PETR's cross-attention over a long key axis with a
+                         (batch, keys) padding mask.
 What is left to ATen in a training step: residual adds, ReLU between two Linears, dropout, autograd's own accumulations.
 """
 import os
@@ -626,6 +628,44 @@ class MhaCorePackedFunction(torch.autograd.Function):
         dqk, dv = ops.mha_core_bwd(qk[..., :c], qk[..., c:], v, out, grad_out.contiguous(), lse, ctx.heads, ctx.mask,
                                    packed_qk=True, dropout_p=ctx.drop[0], seed=ctx.drop[1])
         return dqk, dv, None, None, None
+
+
+class CrossMhaFunction(torch.autograd.Function):
+    """softmax(q k^T / sqrt(32) + key-padding mask) v over a long key axis (the middle of PETRMultiheadAttention):
+    gd4d_cross_mha_train_fwd on the training planes (always: a 32-query tile and P V on six products, with dropout_p = 0 as well),
+    which saves the row log-sum-exp, and gd4d_cross_mha_bwd - dq, dk and dv are all computed whichever inputs want a gradient (one
+    export runs both backward kernels).  apply(q, kv, v, key_padding_mask,
+    num_heads, dropout_p): q (Lq, B, C); kv the (Lk, B, 2C) K|V projection with v = None - its gradient is then ONE tensor, dk | dv
+    written as its halves - or k with v, (Lk, B, C) each.  dropout_p: dropout of the probabilities from a seed drawn here
+    (ops.mha_dropout_seed), as MhaCoreFunction.
+
+    Saved: q, the fp32 projection(s), out, lse, the mask and the seed - nothing of size Lq x Lk, and not the split-bf16 planes: the
+    backward packs what it reads again from the projection (25 MB kept per layer and sample at 12 000 keys instead of 74 MB for twelve
+    planes)."""
+
+    @staticmethod
+    def forward(ctx, q, kv, v, key_padding_mask, num_heads, dropout_p=0.):
+        c = q.shape[-1]
+        k, vv = (kv[..., :c], kv[..., c:]) if v is None else (kv, v)
+        seed = ops.mha_dropout_seed(q.device) if dropout_p > 0. else None
+        planes = ops.cross_mha_pack_kv(k, vv, num_heads=num_heads, train='forward')
+        out, lse = ops.cross_mha_fwd(q, planes, num_heads, key_padding_mask=key_padding_mask, want_lse=True, dropout_p=dropout_p,
+                                     seed=seed)
+        ctx.save_for_backward(q, kv, v, out, lse, key_padding_mask, seed)
+        ctx.heads, ctx.drop = num_heads, dropout_p
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, kv, v, out, lse, mask, seed = ctx.saved_tensors
+        c = q.shape[-1]
+        k, vv = (kv[..., :c], kv[..., c:]) if v is None else (kv, v)
+        planes = ops.cross_mha_pack_kv(k, vv, num_heads=ctx.heads, train='backward')
+        res = ops.cross_mha_bwd(grad_out.contiguous(), q, out, lse, planes, ctx.heads, key_padding_mask=mask, dropout_p=ctx.drop,
+                                seed=seed, packed_kv=v is None)
+        if v is None:
+            return res[0], res[1], None, None, None, None
+        return res[0], res[1], res[2], None, None, None
 
 
 class Detr3DSampleFunction(torch.autograd.Function):

@@ -13,26 +13,29 @@
 //     (m, l, O) partials and a small merge kernel combines them.  gd4d_cross_mha_plan is the split on the host.
 //   - the mask is (B, Lk) bytes: 32 lanes read one byte each per key step, a ballot turns them into the step's 32 mask bits (keys past
 //     Lk are folded in as masked), a step whose bits are all set is skipped.
-#include "gd4d_common.h"
-#include "gd4d_bf16x3.h"
+//   - training (gd4d_cross_mha_train_fwd): the TRAIN instantiations take P V on six products as well (P and V as hi + mid + lo; the
+//     training pack writes a third V plane) - `out` feeds the out-projection's weight gradient and Dq of the backward, and on three
+//     products those were 5 - 7 times as far from the reference as the fp32 torch-op route's - and drop probabilities as
+//     gd4d_mha_core_fwd does (gd4d_mha_dropout.h: a function of the seed and the element's index); l and the lse stay those of the
+//     full softmax.
+#include "gd4d_cross_mha.h"
+#include "gd4d_mha_dropout.h"
 
 namespace gd4d {
-
-constexpr int XM_D = 32;          // head dimension (MHA_D)
-constexpr int XM_WAVES = 4;
 
 struct CrossMhaParams {
   const float* q;
   const unsigned short* kp;       // [plane hi, mid, lo][b][h][step][tile t][lane = 16 (c / 8) + key % 16][8 channels], key = 32 step + 16 t + key % 16
-  const unsigned short* vp;       // [plane hi, lo][b][h][step][half = d / 16][lane = 16 g + d % 16][j] <-> key 32 step + 16 (j >> 2) + 4 g + (j & 3)
+  const unsigned short* vp;       // [plane hi, lo (TRAIN: hi, mid, lo)][b][h][step][half = d / 16][lane = 16 g + d % 16][j] <-> key 32 step + 16 (j >> 2) + 4 g + (j & 3)
   long long plane;                // elements from one plane to the next
   const uint8_t* mask;            // (B, Lk), nonzero = ignore the key; or null
   float* out; float* lse; float* ws;
   int Lq, Lk, B, H, ldq, ldo, steps, splits;
   float qscale;                   // scale * log2(e): base-2 softmax
+  const uint32_t* seed;           // TRAIN: two words in device memory, the threshold round(p 2^32) and 1 / (1 - p)
+  uint32_t drop_thresh;
+  float inv_keep;
 };
-
-__host__ __device__ inline int xm_split_first(int steps, int splits, int s) { return (int)((long long)steps * s / splits); }
 
 // partials of the key splits: O (splits, B, H, Lq, 32), then m and l (splits, B, H, Lq) each
 __host__ __device__ inline size_t xm_ws_o(const int B, const int H, const int Lq, int s, int b, int h) {
@@ -47,7 +50,7 @@ struct XmShared {
 };
 
 // grid (query blocks of 16 NQ, H * splits, B), 4 waves
-template <int NQ>
+template <int NQ, bool TRAIN>
 __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_mha_kernel(const CrossMhaParams p) {
   __shared__ XmShared<NQ> sh;
   const int tid = threadIdx.x;
@@ -71,6 +74,13 @@ __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_mha_kernel(const Cross
                          c.x * p.qscale, c.y * p.qscale, c.z * p.qscale, c.w * p.qscale};
     split8x3(qf, qh[t], qm[t], ql[t]);
   }
+  uint32_t seed_lo = 0, seed_hi = 0, drow[NQ];
+  const bool drop = TRAIN && p.drop_thresh != 0u;
+  if constexpr (TRAIN) {
+    if (drop) { seed_lo = p.seed[0]; seed_hi = p.seed[1]; }
+#pragma unroll
+    for (int t = 0; t < NQ; ++t) drow[t] = mha_drop_row(b, h, q0 + 16 * t + qi, p.H, p.Lq, p.Lk);
+  }
   f32x4 o0[NQ], o1[NQ];                // O^T rows d = 4 g + r, and 16 + 4 g + r
   float m[NQ], l[NQ];
 #pragma unroll
@@ -83,7 +93,7 @@ __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_mha_kernel(const Cross
 
   const int s_first = xm_split_first(p.steps, p.splits, split), s_last = xm_split_first(p.steps, p.splits, split + 1);
   const size_t frag0 = ((size_t)b * p.H + h) * p.steps * 2;          // in fragments of 64 lanes x 8 bf16
-  struct StepData { u32x4 kh[2], km[2], kl[2], vh[2], vl[2]; unsigned mk; };
+  struct StepData { u32x4 kh[2], km[2], kl[2], vh[2], vm[2], vl[2]; unsigned mk; int step; };
   auto fetch = [&](const int step, StepData& d) {                   // step in [s_first, s_last): every fragment of it was written
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -92,10 +102,16 @@ __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_mha_kernel(const Cross
       d.km[t] = *reinterpret_cast<const u32x4*>(p.kp + p.plane + e);
       d.kl[t] = *reinterpret_cast<const u32x4*>(p.kp + 2 * p.plane + e);
       d.vh[t] = *reinterpret_cast<const u32x4*>(p.vp + e);
-      d.vl[t] = *reinterpret_cast<const u32x4*>(p.vp + p.plane + e);
+      if constexpr (TRAIN) {
+        d.vm[t] = *reinterpret_cast<const u32x4*>(p.vp + p.plane + e);
+        d.vl[t] = *reinterpret_cast<const u32x4*>(p.vp + 2 * p.plane + e);
+      } else {
+        d.vl[t] = *reinterpret_cast<const u32x4*>(p.vp + p.plane + e);
+      }
     }
     const int key = step * 32 + (lane & 31);                          // one mask byte per key; a key past Lk counts as masked
     d.mk = key >= p.Lk ? 1u : (p.mask ? (unsigned)p.mask[(size_t)b * p.Lk + key] : 0u);
+    d.step = step;
   };
   auto compute = [&](const StepData& d) {
     const unsigned bits = (unsigned)__ballot(d.mk != 0);              // wave-uniform: bit i <-> key 32 step + i
@@ -134,13 +150,27 @@ __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_mha_kernel(const Cross
       for (int j = 0; j < 8; ++j) pr[j] = __builtin_amdgcn_exp2f(sc[j] - m_new);
       l[t] = l[t] * corr + (((pr[0] + pr[1]) + (pr[2] + pr[3])) + ((pr[4] + pr[5]) + (pr[6] + pr[7])));
       m[t] = m_new;
+      if (drop) {                                                      // (after l: the lse is the full softmax's)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const uint32_t key = (uint32_t)(32 * d.step + 16 * (j >> 2) + 4 * g + (j & 3));
+          pr[j] = mha_drop_keep(seed_lo, seed_hi, drow[t] + key, p.drop_thresh) ? pr[j] * p.inv_keep : 0.f;
+        }
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) { o0[t][r] *= corr; o1[t][r] *= corr; }
       // ---- O^T += V^T P^T: A = V^T[d = lane & 15 (+ 16)][k = 8 g + j], B = P^T = this lane's own eight probabilities ----
-      u32x4 ph, pl;
-      split8(pr, ph, pl);
-      o0[t] = mfma_16x16x32_x3(d.vh[0], d.vl[0], ph, pl, o0[t]);
-      o1[t] = mfma_16x16x32_x3(d.vh[1], d.vl[1], ph, pl, o1[t]);
+      if constexpr (TRAIN) {
+        u32x4 ph, pm, pl;
+        split8x3(pr, ph, pm, pl);
+        o0[t] = xm_x6(d.vh[0], d.vm[0], d.vl[0], ph, pm, pl, o0[t]);
+        o1[t] = xm_x6(d.vh[1], d.vm[1], d.vl[1], ph, pm, pl, o1[t]);
+      } else {
+        u32x4 ph, pl;
+        split8(pr, ph, pl);
+        o0[t] = mfma_16x16x32_x3(d.vh[0], d.vl[0], ph, pl, o0[t]);
+        o1[t] = mfma_16x16x32_x3(d.vh[1], d.vl[1], ph, pl, o1[t]);
+      }
     }
   };
   {
@@ -273,31 +303,6 @@ __global__ __launch_bounds__(64 * XM_WAVES) void cross_mha_pack_kernel(const Cro
   }
 }
 
-static int xm_plan(int Lq, int Lk, int B, int H, int q_tile, int splits, int* qt_out, int* splits_out) {
-  if (Lq <= 0 || Lk <= 0 || B <= 0 || H <= 0 || q_tile < 0 || splits < 0) return GD4D_EINVAL;
-  if ((q_tile != 0 && q_tile != 32 && q_tile != 64) || splits > GD4D_CROSS_MHA_MAX_SPLITS || B > 65535 ||
-      (long long)H * GD4D_CROSS_MHA_MAX_SPLITS > 65535)
-    return GD4D_EUNSUPPORTED;
-  const int steps = (Lk + 31) / 32;
-  const int qt = q_tile ? q_tile : 64;
-  int s = splits;
-  if (s == 0) {
-    // At two waves per SIMD (226 registers) two workgroups share a compute unit: as many splits as keep the grid within the 512
-    // places of 256 compute units (one residency: 900 queries -> 4 splits, 480 workgroups; 6 splits need a second round and measure
-    // slower), and at least one workgroup per compute unit.  A split is worth a workgroup from four steps per wave (below that the
-    // merge's traffic is most of what it does).
-    const long long groups = (long long)((Lq + qt - 1) / qt) * H * B;
-    s = (int)((256 + groups - 1) / groups);
-    if (512 / groups > s) s = (int)(512 / groups);
-    const int most = steps / (4 * XM_WAVES) > 1 ? steps / (4 * XM_WAVES) : 1;
-    if (s > most) s = most;
-    if (s > GD4D_CROSS_MHA_MAX_SPLITS) s = GD4D_CROSS_MHA_MAX_SPLITS;
-  }
-  *qt_out = qt;
-  *splits_out = s;
-  return GD4D_OK;
-}
-
 }  // namespace gd4d
 
 extern "C" int gd4d_cross_mha_plan(int Lq, int Lk, int B, int H, int q_tile, int splits, int32_t* plan) {
@@ -337,13 +342,20 @@ extern "C" int gd4d_cross_mha_pack_kv(const float* k, const float* v, int ldk, i
   return check_launch();
 }
 
-extern "C" int gd4d_cross_mha_fwd(const float* q, const void* k_planes, const void* v_planes, long long plane_stride,
-                                  const void* key_padding_mask, float* out, float* lse, void* workspace, size_t workspace_bytes,
-                                  int Lq, int Lk, int B, int H, int D, int ldq, int ldo, float scale, int q_tile, int splits,
-                                  void* stream) {
-  using namespace gd4d;
+namespace gd4d {
+
+static int cross_mha_launch(const float* q, const void* k_planes, const void* v_planes, long long plane_stride,
+                            const void* key_padding_mask, float* out, float* lse, void* workspace, size_t workspace_bytes,
+                            int Lq, int Lk, int B, int H, int D, int ldq, int ldo, float scale, int q_tile, int splits,
+                            bool train, float drop_p, const void* seed, void* stream) {
   if (!q || !k_planes || !v_planes || !out || Lq <= 0 || Lk <= 0 || B <= 0 || H <= 0) return GD4D_EINVAL;
+  if (train && (!(drop_p >= 0.f && drop_p < 1.f) || (drop_p > 0.f && !seed))) return GD4D_EINVAL;
   if (D != XM_D || H != 8) return GD4D_EUNSUPPORTED;
+  if (drop_p > 0.f && (double)B * H * Lq * Lk >= 4294967296.0) return GD4D_EUNSUPPORTED;   // element ids are 32 bits
+  if (train) {                                        // six products for P V and a third V plane: the 64-query tile would spill
+    if (q_tile == 64) return GD4D_EUNSUPPORTED;
+    if (q_tile == 0) q_tile = 32;
+  }
   int qt, s;
   const int rc = xm_plan(Lq, Lk, B, H, q_tile, splits, &qt, &s);
   if (rc != GD4D_OK) return rc;
@@ -353,14 +365,37 @@ extern "C" int gd4d_cross_mha_fwd(const float* q, const void* k_planes, const vo
   if (need && (!workspace || workspace_bytes < need)) return GD4D_EWORKSPACE;
   CrossMhaParams p{q, static_cast<const unsigned short*>(k_planes), static_cast<const unsigned short*>(v_planes), plane_stride,
                    static_cast<const uint8_t*>(key_padding_mask), out, lse, static_cast<float*>(workspace),
-                   Lq, Lk, B, H, ldq, ldo, (Lk + 31) / 32, s, scale * 1.4426950408889634f};
+                   Lq, Lk, B, H, ldq, ldo, (Lk + 31) / 32, s, scale * 1.4426950408889634f,
+                   static_cast<const uint32_t*>(seed), mha_drop_thresh(drop_p), 1.f / (1.f - drop_p)};
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid((Lq + qt - 1) / qt, H * s, B), block(64 * XM_WAVES);
-  if (qt == 64) hipLaunchKernelGGL((cross_mha_kernel<4>), grid, block, 0, st, p);
-  else hipLaunchKernelGGL((cross_mha_kernel<2>), grid, block, 0, st, p);
+  if (train) {
+    hipLaunchKernelGGL((cross_mha_kernel<2, true>), grid, block, 0, st, p);
+  } else {
+    if (qt == 64) hipLaunchKernelGGL((cross_mha_kernel<4, false>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((cross_mha_kernel<2, false>), grid, block, 0, st, p);
+  }
   if (s > 1) {
     const size_t n = (size_t)Lq * B * H * XM_D;
     hipLaunchKernelGGL(cross_mha_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
   }
   return check_launch();
+}
+
+}  // namespace gd4d
+
+extern "C" int gd4d_cross_mha_fwd(const float* q, const void* k_planes, const void* v_planes, long long plane_stride,
+                                  const void* key_padding_mask, float* out, float* lse, void* workspace, size_t workspace_bytes,
+                                  int Lq, int Lk, int B, int H, int D, int ldq, int ldo, float scale, int q_tile, int splits,
+                                  void* stream) {
+  return gd4d::cross_mha_launch(q, k_planes, v_planes, plane_stride, key_padding_mask, out, lse, workspace, workspace_bytes, Lq, Lk, B,
+                                H, D, ldq, ldo, scale, q_tile, splits, false, 0.f, nullptr, stream);
+}
+
+extern "C" int gd4d_cross_mha_train_fwd(const float* q, const void* k_planes, const void* v_planes, long long plane_stride,
+                                        const void* key_padding_mask, float* out, float* lse, void* workspace,
+                                        size_t workspace_bytes, int Lq, int Lk, int B, int H, int D, int ldq, int ldo, float scale,
+                                        int q_tile, int splits, float drop_p, const void* seed, void* stream) {
+  return gd4d::cross_mha_launch(q, k_planes, v_planes, plane_stride, key_padding_mask, out, lse, workspace, workspace_bytes, Lq, Lk, B,
+                                H, D, ldq, ldo, scale, q_tile, splits, true, drop_p, seed, stream);
 }

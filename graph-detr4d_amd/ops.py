@@ -2400,15 +2400,23 @@ CROSS_MHA_MAX_SPLITS = 64
 class CrossKV:
     """The keys and values of one cross-attention layer as split-bf16 planes in the MFMA fragment layout of gd4d_cross_mha_fwd
     (include/gd4d.h has the layouts): k (3 = hi | mid | lo, B, H, steps of 32 keys, 2, 64, 8) and v (2 = hi | lo, ...) bf16 - the
-    scores are taken on six products, the second product on three.  cross_mha_pack_kv fills them."""
+    scores are taken on six products, the second product on three.  cross_mha_pack_kv fills them.  train: the training form - v
+    holds three planes too (gd4d_cross_mha_train_fwd takes P V on six products), vk (V as row fragments) and kv (K as column
+    fragments), 3 planes each, are what gd4d_cross_mha_bwd reads beside k.  train='forward' / 'backward': only what that pass reads."""
 
-    def __init__(self, lk, b, device, heads=8):
+    def __init__(self, lk, b, device, heads=8, train=False):
         self.lk, self.b, self.heads, self.c = int(lk), int(b), int(heads), 32 * int(heads)
         self.steps = (self.lk + 31) // 32
         if torch.device(device).type != 'cuda':
             raise _lib.Gd4dError('CrossKV must live on the GPU (no CPU fallback in graph-detr4d_amd)')
         self.k = torch.empty(3, self.b, heads, self.steps, 2, 64, 8, device=device, dtype=torch.bfloat16)
-        self.v = torch.empty(2, self.b, heads, self.steps, 2, 64, 8, device=device, dtype=torch.bfloat16)
+        if train not in (False, True, 'forward', 'backward'):
+            raise ValueError("CrossKV: train is False, True, 'forward' or 'backward'")
+        self.train = train
+        self.v = None if train == 'backward' else torch.empty(3 if train else 2, self.b, heads, self.steps, 2, 64, 8, device=device,
+                                                              dtype=torch.bfloat16)
+        self.vk = torch.empty_like(self.k) if train in (True, 'backward') else None
+        self.kv = torch.empty_like(self.k) if train in (True, 'backward') else None
 
     @property
     def plane(self):
@@ -2424,7 +2432,8 @@ class CrossKV:
         """(2, steps * 32, B, C): the planes as plain rows (tests)."""
         b, h, s = self.b, self.heads, self.steps
         # [plane][b][h][s][half][g][d % 16][t][r]  ->  key = 32 s + 16 t + 4 g + r, channel = 32 h + 16 half + d % 16
-        return self.v.view(2, b, h, s, 2, 4, 16, 2, 4).permute(0, 3, 7, 5, 8, 1, 2, 4, 6).reshape(2, s * 32, b, h * 32)
+        n = self.v.shape[0]
+        return self.v.view(n, b, h, s, 2, 4, 16, 2, 4).permute(0, 3, 7, 5, 8, 1, 2, 4, 6).reshape(n, s * 32, b, h * 32)
 
 
 def _rows_lbc(t, name):
@@ -2436,17 +2445,22 @@ def _rows_lbc(t, name):
     return t.stride(1)
 
 
-def cross_mha_pack_kv(k, v, kv=None, num_heads=8):
+def cross_mha_pack_kv(k, v, kv=None, num_heads=8, train=False):
     """gd4d_cross_mha_pack_kv: k, v (Lk, B, C) float32 - contiguous, or the two halves of one (Lk, B, 2C) projection - split to bf16
-    pieces once (k: hi / mid / lo, v: hi / lo), into the planes gd4d_cross_mha_fwd reads (pad keys of the last step written as zeros).  Returns the CrossKV."""
+    pieces once (k: hi / mid / lo, v: hi / lo), into the planes gd4d_cross_mha_fwd reads (pad keys of the last step written as zeros).  Returns the CrossKV.
+    train (True, 'forward', 'backward'): gd4d_cross_mha_pack_kv_train - the training form, see CrossKV."""
     ldk, ldv = _rows_lbc(k, 'k'), _rows_lbc(v, 'v')
     lk, b, c = k.shape
     if tuple(v.shape) != (lk, b, c) or c != 32 * num_heads:
         raise ValueError('cross_mha_pack_kv: k and v (Lk, B, 32 heads)')
     if kv is None:
-        kv = CrossKV(lk, b, k.device, num_heads)
-    elif (kv.lk, kv.b, kv.heads) != (lk, b, num_heads):
-        raise ValueError('cross_mha_pack_kv: the planes were made for another shape')
+        kv = CrossKV(lk, b, k.device, num_heads, train=train)
+    elif (kv.lk, kv.b, kv.heads) != (lk, b, num_heads) or getattr(kv, 'train', False) != train:
+        raise ValueError('cross_mha_pack_kv: the planes were made for another shape or form')
+    if train:
+        _call('gd4d_cross_mha_pack_kv_train', ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(v.data_ptr()), ldk, ldv, _dev(kv.k, 'kv.k'),
+              _opt(kv.v, 'kv.v', None), _opt(kv.vk, 'kv.vk', None), _opt(kv.kv, 'kv.kv', None), kv.plane, lk, b, num_heads, 32)
+        return kv
     _call('gd4d_cross_mha_pack_kv', ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(v.data_ptr()), ldk, ldv, _dev(kv.k, 'kv.k'),
           _dev(kv.v, 'kv.v'), kv.plane, lk, b, num_heads, 32)
     return kv
@@ -2474,30 +2488,110 @@ def cross_mha_plan(lq, lk, b, heads=8, q_tile=0, splits=0):
     return CrossMhaPlan(list(raw), lk)
 
 
-def cross_mha_fwd(q, kv, num_heads, key_padding_mask=None, want_lse=False, q_tile=0, splits=0):
+def _cross_mha_mask(key_padding_mask, b, lk):
+    if key_padding_mask is None:
+        return None, None
+    if key_padding_mask.dtype not in (torch.bool, U8) or tuple(key_padding_mask.shape) != (b, lk):
+        raise ValueError(f'key_padding_mask must be bool / uint8 ({b}, {lk})')
+    key_padding_mask = key_padding_mask.contiguous().view(U8)
+    return key_padding_mask, _dev(key_padding_mask, 'key_padding_mask', U8)
+
+
+def cross_mha_fwd(q, kv, num_heads, key_padding_mask=None, want_lse=False, q_tile=0, splits=0, dropout_p=0., seed=None):
     """gd4d_cross_mha_fwd: softmax(q k^T / sqrt(32) + key-padding mask) v on the planes of `kv` (CrossKV).  q (Lq, B, C) float32,
     contiguous or a last-dim slice; key_padding_mask (B, Lk) bool / uint8, nonzero = ignore the key.  Returns (Lq, B, C) [, lse
-    (Lq, B, heads)].  q_tile / splits: cross_mha_plan's (0 = the library's choice)."""
+    (Lq, B, heads)].  q_tile / splits: cross_mha_plan's (0 = the library's choice).  On training planes (cross_mha_pack_kv(train=True
+    or 'forward')) it is gd4d_cross_mha_train_fwd: P V on six products, a 32-query tile, and with dropout_p and seed (mha_dropout_seed)
+    dropout of the probabilities as mha_core_fwd draws it (mha_dropout_keep_mask rebuilds the mask)."""
     ldq = _rows_lbc(q, 'q')
     lq, b, c = q.shape
-    if not isinstance(kv, CrossKV):
-        raise TypeError('cross_mha_fwd: kv must be a CrossKV (cross_mha_pack_kv)')
+    if not isinstance(kv, CrossKV) or kv.v is None:
+        raise TypeError('cross_mha_fwd: kv must be a CrossKV with the planes of the forward (cross_mha_pack_kv)')
     if b != kv.b or c != kv.c or num_heads != kv.heads:
         raise ValueError('cross_mha_fwd: the planes were made for another batch, width or head count')
-    mptr = None
-    if key_padding_mask is not None:
-        if key_padding_mask.dtype not in (torch.bool, U8) or tuple(key_padding_mask.shape) != (b, kv.lk):
-            raise ValueError(f'key_padding_mask must be bool / uint8 ({b}, {kv.lk})')
-        key_padding_mask = key_padding_mask.contiguous().view(U8)
-        mptr = _dev(key_padding_mask, 'key_padding_mask', U8)
+    train = bool(getattr(kv, 'train', False))
+    if dropout_p and not train:
+        raise ValueError("cross_mha_fwd: dropout needs the training planes (cross_mha_pack_kv(train=True or 'forward'))")
+    if train and not q_tile:
+        q_tile = 32
+    key_padding_mask, mptr = _cross_mha_mask(key_padding_mask, b, kv.lk)
+    sptr = _mha_seed(dropout_p, seed, q.device)
     lib = _lib.load()
     ws_bytes = int(lib.gd4d_cross_mha_workspace_bytes(lq, kv.lk, b, num_heads, int(q_tile), int(splits)))
     ws = torch.empty(ws_bytes // 4, device=q.device, dtype=F32) if ws_bytes else None
     out = torch.empty(lq, b, c, device=q.device, dtype=F32)
     lse = torch.empty(lq, b, num_heads, device=q.device, dtype=F32) if want_lse else None
-    _call('gd4d_cross_mha_fwd', ctypes.c_void_p(q.data_ptr()), _dev(kv.k, 'kv.k'), _dev(kv.v, 'kv.v'), kv.plane, mptr, _dev(out, 'out'),
-          _opt(lse, 'lse'), _opt(ws, 'workspace'), ws_bytes, lq, kv.lk, b, num_heads, 32, ldq, c, 1.0 / (32 ** 0.5), int(q_tile), int(splits))
+    args = (ctypes.c_void_p(q.data_ptr()), _dev(kv.k, 'kv.k'), _dev(kv.v, 'kv.v'), kv.plane, mptr, _dev(out, 'out'),
+            _opt(lse, 'lse'), _opt(ws, 'workspace'), ws_bytes, lq, kv.lk, b, num_heads, 32, ldq, c, 1.0 / (32 ** 0.5), int(q_tile), int(splits))
+    if train:
+        _call('gd4d_cross_mha_train_fwd', *args, float(dropout_p), sptr)
+    else:
+        _call('gd4d_cross_mha_fwd', *args)
     return (out, lse) if want_lse else out
+
+
+class CrossMhaBwdPlan:
+    """cross_mha_bwd_plan's answer.  Query-side kernel: q_tile queries per workgroup, `splits` key ranges (ranges[i] = [first, last)
+    keys), query_grid, query_block; key-side kernel: key_block keys per workgroup, key_grid, key_block_threads; workspace bytes of
+    the query-side pack (pack_bytes, read by both kernels), of the split partials (partial_bytes) and their sum (workspace_bytes)."""
+
+    def __init__(self, raw, lk):
+        self.q_tile, self.splits, self.steps, self.query_steps = raw[0], raw[1], raw[2], raw[3]
+        self.query_grid, self.query_block = (raw[4], raw[5], raw[6]), raw[7]
+        self.key_block, self.key_grid, self.key_block_threads = raw[8], (raw[9], raw[10], raw[11]), raw[12]
+        self.pack_bytes, self.partial_bytes, self.workspace_bytes = raw[13], raw[14], raw[15]
+        self.ranges = [(32 * raw[16 + i], min(int(lk), 32 * raw[17 + i])) for i in range(self.splits)]
+
+    def __repr__(self):
+        return (f'CrossMhaBwdPlan(query side: grid {self.query_grid} x {self.query_block} threads, {self.q_tile} queries, {self.splits} splits; '
+                f'key side: grid {self.key_grid} x {self.key_block_threads} threads, {self.key_block} keys; workspace {self.pack_bytes} + '
+                f'{self.partial_bytes} bytes)')
+
+
+def cross_mha_bwd_plan(lq, lk, b, heads=8, q_tile=0, splits=0):
+    """gd4d_cross_mha_bwd_plan (no GPU): grids, blocks and workspace of cross_mha_bwd's two compute kernels."""
+    raw = (ctypes.c_int64 * (17 + CROSS_MHA_MAX_SPLITS))()
+    _lib.check(_lib.load().gd4d_cross_mha_bwd_plan(int(lq), int(lk), int(b), int(heads), int(q_tile), int(splits), raw),
+               'gd4d_cross_mha_bwd_plan')
+    return CrossMhaBwdPlan(list(raw), lk)
+
+
+def cross_mha_bwd(grad_out, q, out, lse, kv, num_heads, key_padding_mask=None, dropout_p=0., seed=None, q_tile=0, splits=0,
+                  packed_kv=False, workspace=None):
+    """gd4d_cross_mha_bwd: the gradients of cross_mha_fwd's q, k and v from grad_out, q, out, lse (want_lse) and the training planes
+    of k and v (cross_mha_pack_kv(train=True)); key_padding_mask, dropout_p and seed as in the forward.  Returns (dq (Lq, B, C), dk,
+    dv (Lk, B, C)); packed_kv: (dq, dkv (Lk, B, 2C)) - dk | dv written as the two halves of one buffer, what the backward of a K|V
+    projection takes.  Rows of masked keys are exact zeros.  A row whose keys are all masked has unspecified gradients.
+    workspace: a float32 tensor of at least cross_mha_bwd_plan(...).workspace_bytes to use instead of a new one (its content does
+    not matter: every element that is read is written first)."""
+    ldq, ldo, ldg = _rows_lbc(q, 'q'), _rows_lbc(out, 'out'), _rows_lbc(grad_out, 'grad_out')
+    lq, b, c = q.shape
+    if not isinstance(kv, CrossKV) or kv.vk is None:
+        raise TypeError('cross_mha_bwd: kv must be a CrossKV with the training planes (cross_mha_pack_kv(train=True))')
+    if b != kv.b or c != kv.c or num_heads != kv.heads:
+        raise ValueError('cross_mha_bwd: the planes were made for another batch, width or head count')
+    if tuple(out.shape) != (lq, b, c) or tuple(grad_out.shape) != (lq, b, c) or tuple(lse.shape) != (lq, b, num_heads):
+        raise ValueError('cross_mha_bwd: out, grad_out (Lq, B, C) and lse (Lq, B, heads) of the forward call')
+    key_padding_mask, mptr = _cross_mha_mask(key_padding_mask, b, kv.lk)
+    sptr = _mha_seed(dropout_p, seed, q.device)
+    lib = _lib.load()
+    ws_bytes = int(lib.gd4d_cross_mha_bwd_workspace_bytes(lq, kv.lk, b, num_heads, int(q_tile), int(splits)))
+    ws = torch.empty(max(ws_bytes, 16) // 4, device=q.device, dtype=F32) if workspace is None else workspace
+    if ws.dtype != F32 or ws.numel() * 4 < ws_bytes:
+        raise ValueError(f'cross_mha_bwd: workspace must be float32 of at least {ws_bytes} bytes')
+    dq = torch.empty(lq, b, c, device=q.device, dtype=F32)
+    if packed_kv:
+        dkv = torch.empty(kv.lk, b, 2 * c, device=q.device, dtype=F32)
+        dk, dv, ldd = dkv[..., :c], dkv[..., c:], 2 * c
+    else:
+        dk = torch.empty(kv.lk, b, c, device=q.device, dtype=F32)
+        dv = torch.empty(kv.lk, b, c, device=q.device, dtype=F32)
+        ldd = c
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())    # noqa: E731
+    _call('gd4d_cross_mha_bwd', vp(grad_out), vp(q), vp(out), _dev(lse, 'lse', F32), _dev(kv.k, 'kv.k'), _dev(kv.vk, 'kv.vk'),
+          _dev(kv.kv, 'kv.kv'), kv.plane, mptr, _dev(dq, 'dq'), vp(dk), vp(dv), _dev(ws, 'workspace'), ws_bytes, lq, kv.lk, b, num_heads,
+          32, ldg, ldq, ldo, c, ldd, ldd, 1.0 / (32 ** 0.5), float(dropout_p), sptr, int(q_tile), int(splits))
+    return (dq, dkv) if packed_kv else (dq, dk, dv)
 
 
 class RequestRef(ctypes.Structure):
@@ -3700,7 +3794,7 @@ def _on_tensor_device(fn):
 
 
 _HOST_ONLY = {'linear_sum_assignment_batch', 'cross_attn_plan_bytes', 'invalidate_chain_images', 'kept_in_place', 'chain_load', 'chain_gemm', 'chain_small_linear', 'chain_layernorm',
-              'chain_add', 'chain_refine', 'row_chain_fwd', 'chain_weight_image', 'chain_layernorm_bwd', 'cross_mha_plan'}
+              'chain_add', 'chain_refine', 'row_chain_fwd', 'chain_weight_image', 'chain_layernorm_bwd', 'cross_mha_plan', 'cross_mha_bwd_plan'}
 for _name, _fn in list(globals().items()):
     if inspect.isfunction(_fn) and _fn.__module__ == __name__ and not _name.startswith('_') and _name not in _HOST_ONLY:
         globals()[_name] = _on_tensor_device(_fn)

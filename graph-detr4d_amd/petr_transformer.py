@@ -7,8 +7,10 @@ projects/configs/petr/* and petrv2/* configs.  Type names, constructor keywords 
 
 Inference runs on the library's kernels: the query and K|V projections on gd4d_linear_fwd (positional encodings added inside the
 GEMM), gd4d_cross_mha_pack_kv + gd4d_cross_mha_fwd for the attention over 6 000 - 48 000 keys with the (bs, keys) padding mask, and
-the out-projection with the residual (and the LayerNorm that follows) in its epilogue.  Training and anything the kernels do not
-cover is the reference's op sequence on torch - chosen with torch_ops=True, never silently (Fn.torch_ops_route).
+the out-projection with the residual (and the LayerNorm that follows) in its epilogue.  Training runs on the kernels with
+hip_train=True (autograd.CrossMhaFunction: gd4d_cross_mha_train_fwd / gd4d_cross_mha_bwd, the projections on the library's GEMMs);
+without it, and for anything the kernels do not cover, it is the reference's op sequence on torch - chosen with torch_ops=True,
+never silently (Fn.torch_ops_route).
 """
 import torch
 import torch.nn as nn
@@ -25,10 +27,17 @@ from .transformer_layers import BaseTransformerLayer, TransformerLayerSequence, 
 @ATTENTION.register_module()
 class PETRMultiheadAttention(nn.Module):
     """Reference :227-367: nn.MultiheadAttention with the positional encodings added to query and key (not to value), a key-padding
-    mask, and the identity connection.  torch_ops=True: F.multi_head_attention_forward on this module's parameters (differentiable)."""
+    mask, and the identity connection.  torch_ops=True: F.multi_head_attention_forward on this module's parameters (differentiable).
+
+    hip_train=True (opt-in): a call in train mode or under autograd runs on the kernels too - the q, K|V and out projections through
+    Fn.linear_autograd (weight gradients on gd4d_linear_bwd_weight, main_grad accumulation as everywhere), the core through
+    autograd.CrossMhaFunction with attn_drop applied inside the kernel in train mode (0 in eval mode); proj_drop and dropout_layer
+    stay nn.Dropout, the residual and an offered LayerNorm go through Fn.residual_norm_autograd.  Nothing of size queries x keys is
+    stored.  An attn_mask, another width or head dim, a dtype other than float32, or B heads Lq Lk >= 2^32 with dropout are refused,
+    naming torch_ops=True.  A row whose keys are all masked is NaN forward, as ATen makes it; its gradients are unspecified."""
 
     def __init__(self, embed_dims, num_heads, attn_drop=0., proj_drop=0., dropout_layer=dict(type='Dropout', drop_prob=0.),
-                 init_cfg=None, batch_first=False, torch_ops=False, **kwargs):
+                 init_cfg=None, batch_first=False, torch_ops=False, hip_train=False, **kwargs):
         super().__init__()
         dropout_layer = dict(dropout_layer) if dropout_layer else None
         if 'dropout' in kwargs:                      # deprecated alias used by the reference configs (:258-265)
@@ -44,6 +53,7 @@ class PETRMultiheadAttention(nn.Module):
         self.batch_first = batch_first
         self.attn_drop = float(attn_drop)
         self.torch_ops = bool(torch_ops)
+        self.hip_train = bool(hip_train)
         self.attn = _PackedAttnParams(embed_dims)
         self.proj_drop = nn.Dropout(proj_drop)
         self.dropout_layer = nn.Dropout(dropout_layer.get('drop_prob', 0.)) if dropout_layer else nn.Identity()
@@ -66,10 +76,25 @@ class PETRMultiheadAttention(nn.Module):
         what = (f'PETRMultiheadAttention with embed_dims {self.embed_dims}, head dim {d}, '
                 f'{"an attn_mask" if attn_mask is not None else "no attn_mask"}, '
                 f'{"train" if self.training else "eval"} mode, {"autograd" if grad else "no autograd"}, dtype {query.dtype}')
-        supported = (self.embed_dims == 256 and d == 32 and attn_mask is None and not self.training and not grad
-                     and query.dtype == torch.float32 and key.dtype == torch.float32 and value.dtype == torch.float32)
+        covered = (self.embed_dims == 256 and d == 32 and attn_mask is None
+                   and query.dtype == torch.float32 and key.dtype == torch.float32 and value.dtype == torch.float32)
+        train = self.hip_train and (self.training or grad)
+        if train:
+            drop = self.attn_drop if self.training else 0.
+            axis = 1 if self.batch_first else 0
+            elements = query.shape[1 - axis] * self.num_heads * query.shape[axis] * key.shape[axis]
+            what += f', hip_train, attn_drop {drop}, B heads Lq Lk = {elements}'
+            supported = covered and (drop == 0. or elements < 2 ** 32)
+        else:
+            supported = covered and not self.training and not grad
         if Fn.torch_ops_route(what, supported, module=self):
             return self._forward_torch(query, key, value, identity, query_pos, key_pos, attn_mask, key_padding_mask)
+        if train:
+            tr = (lambda t: None if t is None else t.transpose(0, 1)) if self.batch_first else (lambda t: t)      # noqa: E731
+            out = self._attention_train(tr(query), tr(key), tr(value), tr(query_pos), tr(key_pos), key_padding_mask, drop,
+                                        value_is_key=value is key)
+            out = self.dropout_layer(self.proj_drop(tr(out)))
+            return Fn.residual_norm_autograd(kwargs, identity, out)
         if self.batch_first:
             tr = lambda t: None if t is None else t.transpose(0, 1)      # noqa: E731
             out = self._forward_kernels(tr(query), tr(key), tr(value), tr(identity), tr(query_pos), tr(key_pos), key_padding_mask,
@@ -100,6 +125,27 @@ class PETRMultiheadAttention(nn.Module):
             fused['done'] = True
             return Fn.linear_norm(o, wo, bo, fused['norm'], r1=identity)
         return Fn.linear(o, wo, bo, r1=identity.expand_as(o))
+
+    def _attention_train(self, query, key, value, query_pos, key_pos, key_padding_mask, drop, value_is_key):
+        """(L, B, C) tensors -> the out-projection's output, every step an autograd node on the library's kernels.  Without a key
+        encoding K|V is one GEMM and its gradient one tensor; with one (PETR's case) K and V read different rows: two GEMMs."""
+        from .autograd import CrossMhaFunction
+        c = self.embed_dims
+        w, bias = self.attn.in_proj_weight, self.attn.in_proj_bias
+        rows = lambda lo, hi: (Fn.main_grad(w, (lo, hi)), Fn.main_grad(bias, (lo, hi)))      # noqa: E731
+        q_in = query if query_pos is None else query + query_pos
+        q = Fn.linear_autograd(q_in.contiguous(), w[:c], bias[:c], main=rows(0, c))
+        if key_padding_mask is not None and key_padding_mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError('key_padding_mask must be bool or uint8')
+        if value_is_key and key_pos is None:
+            kvp = Fn.linear_autograd(key.contiguous(), w[c:], bias[c:], main=rows(c, 3 * c))
+            o = CrossMhaFunction.apply(q, kvp, None, key_padding_mask, self.num_heads, drop)
+        else:
+            k_in = key if key_pos is None else key + key_pos
+            k = Fn.linear_autograd(k_in.contiguous(), w[c:2 * c], bias[c:2 * c], main=rows(c, 2 * c))
+            v = Fn.linear_autograd(value.contiguous(), w[2 * c:], bias[2 * c:], main=rows(2 * c, 3 * c))
+            o = CrossMhaFunction.apply(q, k, v, key_padding_mask, self.num_heads, drop)
+        return Fn.linear_autograd(o, self.attn.out_proj.weight, self.attn.out_proj.bias)
 
     def _forward_torch(self, query, key, value, identity, query_pos, key_pos, attn_mask, key_padding_mask):
         """The reference's op sequence (:341-367) with nn.MultiheadAttention.forward spelled as the functional it calls."""

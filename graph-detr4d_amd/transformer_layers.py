@@ -79,12 +79,15 @@ class MultiheadAttention(nn.Module):
         k_in = q_in if (key is query and key_pos is query_pos) else (key if key_pos is None else key + key_pos)
         if self.batch_first:
             q_in, k_in, value = (t.transpose(0, 1) for t in (q_in, k_in, value))
-        out = self._attention_autograd(q_in, k_in, value, attn_mask) if grad else \
+        # train mode without autograd is the first pass of a checkpointed layer (PETRTransformerDecoderLayer(with_cp=True)): it must
+        # draw the seeds and take the kernels of the pass that is recomputed under autograd, or the two disagree
+        train = grad or self.training
+        out = self._attention_autograd(q_in, k_in, value, attn_mask) if train else \
             self._attention(q_in, k_in, value, attn_mask)
         if self.batch_first:
             out = out.transpose(0, 1)
         out = self.dropout_layer(self.proj_drop(out))
-        return Fn.residual_norm_autograd(kwargs, identity, out) if grad else identity + out
+        return Fn.residual_norm_autograd(kwargs, identity, out) if train else identity + out
 
     def _packed_self_attention(self, query, query_pos, attn_mask, identity, fused=None):
         """The decoder's case (q = k = query + query_pos, v = query): one in-projection GEMM with the

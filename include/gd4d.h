@@ -796,6 +796,62 @@ int gd4d_cross_mha_fwd(const float* q, const void* k_planes, const void* v_plane
                        int Lq, int Lk, int B, int H, int D, int ldq, int ldo, float scale, int q_tile, int splits,
                        void* stream);
 
+/* Training of the same attention (gd4d_cross_mha.hip, gd4d_cross_mha_train.hip): nothing of size Lq x Lk is stored.
+ * gd4d_cross_mha_train_fwd - gd4d_cross_mha_fwd on the planes of gd4d_cross_mha_pack_kv_train (v_planes holds THREE planes, hi / mid
+ *   / lo, and P V takes six products as the scores do: out feeds the out-projection's weight gradient and the backward's Dq) for a
+ *   workgroup of q_tile = 32 queries (0 = 32; 64 is GD4D_EUNSUPPORTED here; the workspace is
+ *   gd4d_cross_mha_workspace_bytes(.., 32, splits)), plus dropout of the probabilities, with gd4d_mha_core_fwd's contract: element
+ *   (b, h, q, key) is kept iff mha_drop_keep(seed, mha_drop_row(b, h, q, H, Lq, Lk) + key, round(drop_p 2^32)) (gd4d_mha_dropout.h;
+ *   seed = two uint32 words in DEVICE memory), a kept probability is scaled by 1 / (1 - drop_p) before it multiplies v; l, and so
+ *   lse, stay those of the full softmax.  GD4D_EINVAL for drop_p outside [0, 1) or
+ *   drop_p > 0 without seed; GD4D_EUNSUPPORTED for drop_p > 0 with B H Lq Lk >= 2^32 (element ids are 32 bits).
+ * gd4d_cross_mha_pack_kv_train - the training form of the pack: every group holds three planes, hi / mid / lo.  k_planes (K as row
+ *   fragments, the bits gd4d_cross_mha_pack_kv writes) and v_planes (V as column fragments; the first two planes are that pack's
+ *   hi / lo) are what the training forward reads; the backward reads k_planes and
+ *   vk_planes (V as ROW fragments: dP^T = V dout^T reduces over channels) and kv_planes (K as COLUMN fragments, hi / mid /
+ *   lo: dq^T += K^T dS^T reduces over keys).  v_planes, vk_planes and kv_planes may each be NULL (not written); the layouts are those of
+ *   gd4d_cross_mha_fwd's K (rows) and V (columns), plane_stride elements from one plane of a group to the next.  With vk_planes, v
+ *   must be 16-byte aligned and ldv a multiple of 4 (GD4D_EALIGN).
+ * gd4d_cross_mha_bwd - with M = keep / (1 - drop_p), P = exp(scale q k^T + mask - lse), Dq = sum_d dout o out and
+ *   dS = P o (M o (dout v^T) - Dq):   dq = scale dS k,   dk = scale dS^T q,   dv = (P o M)^T dout.
+ *   dout, q, out (Lq, B, H D) fp32 rows (l B + b) at strides ld_dout / ldq / ldo; lse (Lq, B, H) as the forward wrote it; the planes
+ *   of gd4d_cross_mha_pack_kv_train (k_planes, vk_planes, kv_planes); key_padding_mask, drop_p and seed as in the forward.
+ *   dq (Lq, B, H D) at stride ld_dq, dk and dv (Lk, B, H D) at strides ld_dk / ld_dv (the two halves of one (Lk, B, 2 H D) buffer:
+ *   ld_dk = ld_dv = 2 H D): every row is written, a masked key's dk and dv rows as exact zeros, nothing past Lk.
+ *   Arithmetic: the score recompute takes the forward's six bf16 products of the same hi / mid / lo pieces of q scale log2(e) and k,
+ *   so P agrees with the saved lse; dout v^T, dS k, dS^T q and (P o M)^T dout take six as well (both operands as hi + mid + lo:
+ *   dS = P (dout v^T - Dq) cancels in a row that one key dominates, and three products missed the tests' bounds there); all with
+ *   fp32 accumulation.
+ *   No atomics: every sum has one owner and a fixed order - results are bit-identical from run to run.
+ *   Four launches: a query-side pack (q, dout -> split-bf16 fragments in both layouts, Dq and lse log2(e), once), the query-side
+ *   kernel (a workgroup owns q_tile = 32 queries (0 = 32; 64 is GD4D_EUNSUPPORTED here) of one (batch, head) and one of `splits` key
+ *   ranges, splits as in gd4d_cross_mha_plan for that tile) with its merge over the splits in split order, and the key-side kernel
+ *   (a workgroup owns 64 keys of one (batch, head) and walks all queries).  A (query, batch) row whose keys are all masked is NaN
+ *   forward; its gradients are unspecified.
+ *   workspace: gd4d_cross_mha_bwd_workspace_bytes (16-byte aligned; GD4D_EWORKSPACE if NULL or smaller).
+ * gd4d_cross_mha_bwd_plan (no GPU): plan[0..3] = q_tile, splits, key steps, query steps; plan[4..7] = the query-side kernel's grid
+ *   x (query steps), y (H splits), z (B) and its block size; plan[8] = keys per workgroup of the key-side kernel, plan[9..12] = its
+ *   grid x (key blocks), y (H), z (B) and block size; plan[13] = workspace bytes of the query-side pack (read by both kernels),
+ *   plan[14] = those of the query-side kernel's split partials, plan[15] = their sum = gd4d_cross_mha_bwd_workspace_bytes;
+ *   plan[16 .. 16 + splits] = the first key step of each split and the number of steps, as in gd4d_cross_mha_plan.  plan holds
+ *   17 + GD4D_CROSS_MHA_MAX_SPLITS entries.
+ * GD4D_EINVAL: a NULL tensor / plane / output, sizes <= 0, strides below H D, a short plane_stride, a bad drop_p; GD4D_EUNSUPPORTED:
+ *   D != 32, H != 8, a q_tile or splits outside the plan's range; GD4D_EALIGN: dout, q, out, k (v) or the planes or the workspace not
+ *   16-byte aligned, their strides not a multiple of 4; all before any GPU work. */
+int gd4d_cross_mha_train_fwd(const float* q, const void* k_planes, const void* v_planes, long long plane_stride,
+                             const void* key_padding_mask, float* out, float* lse, void* workspace, size_t workspace_bytes,
+                             int Lq, int Lk, int B, int H, int D, int ldq, int ldo, float scale, int q_tile, int splits,
+                             float drop_p, const void* seed, void* stream);
+int gd4d_cross_mha_pack_kv_train(const float* k, const float* v, int ldk, int ldv, void* k_planes, void* v_planes, void* vk_planes,
+                                 void* kv_planes, long long plane_stride, int Lk, int B, int H, int D, void* stream);
+int gd4d_cross_mha_bwd_plan(int Lq, int Lk, int B, int H, int q_tile, int splits, int64_t* plan);
+size_t gd4d_cross_mha_bwd_workspace_bytes(int Lq, int Lk, int B, int H, int q_tile, int splits);
+int gd4d_cross_mha_bwd(const float* dout, const float* q, const float* out, const float* lse, const void* k_planes,
+                       const void* vk_planes, const void* kv_planes, long long plane_stride, const void* key_padding_mask,
+                       float* dq, float* dk, float* dv, void* workspace, size_t workspace_bytes, int Lq, int Lk, int B, int H,
+                       int D, int ld_dout, int ldq, int ldo, int ld_dq, int ld_dk, int ld_dv, float scale, float drop_p,
+                       const void* seed, int q_tile, int splits, void* stream);
+
 /* gd4d_mlp2_bf16x3_fwd - out = relu(x W1^T + b1) W2^T + b2 in ONE kernel (gd4d_mlp2.hip): the head's position-embedding MLPs -
  * Conv1x1, ReLU, Conv1x1 over every pixel of every camera (dense_heads/detr3d_head_pe.py:380-390 `position_encoder`, applied at
  * :543-553: 192 -> 1024 -> 256 over 739 800 pixels at 24 cameras).  The hidden activation (3 GB as a tensor) stays in registers:
