@@ -132,6 +132,8 @@ SIGNATURES = {
     'gd4d_mlp2_frustum_fwd': (_i, [_vp, _vp, _i, _i, _c.c_float, _c.c_float, _i, _c.c_float, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     'gd4d_mlp2_pe_se_fwd': (_i, [_vp, _vp, _vp, _i, _i, _c.c_float, _c.c_float, _i, _c.c_float, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp,
                                   _vp, _vp]),
+    'gd4d_petr_keys_plan': (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
+    'gd4d_petr_keys_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'gd4d_adamw_flat_workspace_bytes': (_c.c_size_t, []),
     'gd4d_adamw_flat': (_i, [_vp] * 6 + [_c.c_size_t, _c.c_int64] + [_f] * 6 + [_vp]),
     'gd4d_adamw_recipe_flat_workspace_bytes': (_c.c_size_t, []),

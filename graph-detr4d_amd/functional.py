@@ -433,7 +433,8 @@ def head_outputs(hs, init_reference, inter_references, cls_branches, reg_branche
             # both branches of a layer as the two programs of ONE row-chain launch (the reg branch on six products, as the decoder
             # computes it for the refinement): 6 launches instead of 6 x (6 Linear + 2 LayerNorm)
             rows = x.view(-1, x.shape[-1])
-            last_c, last_r = cls_branches[lvl][-1], reg_branches[lvl][-1]
+            seq = isinstance(cls_branches[lvl], torch.nn.Sequential) and isinstance(reg_branches[lvl], torch.nn.Sequential)
+            last_c, last_r = (cls_branches[lvl][-1], reg_branches[lvl][-1]) if seq else (None, None)     # (PETRv2's RegLayer: run_branch)
             if isinstance(last_c, torch.nn.Linear) and isinstance(last_r, torch.nn.Linear):
                 cls = torch.empty(*x.shape[:-1], last_c.out_features, device=x.device, dtype=torch.float32)
                 tmp = torch.empty(*x.shape[:-1], last_r.out_features, device=x.device, dtype=torch.float32)

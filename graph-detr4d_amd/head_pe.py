@@ -147,6 +147,17 @@ class FeaturePositionEmbedding(nn.Module):
         but their MEMORY is (B, N, H, W, C) - the decoder's gathers read such levels in place, so its per-sample slice-planar
         copy (0.27 ms of a 1.6-ms sample at 24 cameras) does not run.  Leave it off when other code takes `.view()`s of the maps."""
         super().__init__()
+        self._configure(embed_dims, depth_num, depth_start, pc_range, num_feats, temperature, normalize, scale, eps, offset, with_detach,
+                        cams_per_frame, channels_last_out)
+        self.position_encoder = nn.Sequential(nn.Conv2d(self.position_dim, embed_dims * 4, 1), nn.ReLU(),
+                                              nn.Conv2d(embed_dims * 4, embed_dims, 1))
+        self.adapt_pos3d = nn.Sequential(nn.Conv2d(embed_dims * 3 // 2, embed_dims * 4, 1), nn.ReLU(),
+                                         nn.Conv2d(embed_dims * 4, embed_dims, 1))
+        self.fpe = SELayer(embed_dims)
+
+    def _configure(self, embed_dims, depth_num, depth_start, pc_range, num_feats, temperature, normalize, scale, eps, offset,
+                   with_detach=True, cams_per_frame=6, channels_last_out=False):
+        """Everything of the constructor but the three parameter-holding submodules: the settings and the empty caches."""
         if pc_range is None:
             raise ValueError('pc_range is required (the head takes it from its bbox coder)')
         self.with_detach, self.cams_per_frame = bool(with_detach), int(cams_per_frame)
@@ -155,11 +166,6 @@ class FeaturePositionEmbedding(nn.Module):
         self.embed_dims, self.depth_num, self.depth_start = embed_dims, depth_num, depth_start
         self.pc_range = list(pc_range)
         self.position_dim = 3 * depth_num
-        self.position_encoder = nn.Sequential(nn.Conv2d(self.position_dim, embed_dims * 4, 1), nn.ReLU(),
-                                              nn.Conv2d(embed_dims * 4, embed_dims, 1))
-        self.adapt_pos3d = nn.Sequential(nn.Conv2d(embed_dims * 3 // 2, embed_dims * 4, 1), nn.ReLU(),
-                                         nn.Conv2d(embed_dims * 4, embed_dims, 1))
-        self.fpe = SELayer(embed_dims)
         # SinePositionalEncoding3D(num_feats, temperature, normalize, scale, eps, offset) has no parameters
         self.num_feats, self.temperature, self.normalize = num_feats, temperature, normalize
         self.scale, self.eps, self.offset = scale, eps, offset
@@ -172,6 +178,19 @@ class FeaturePositionEmbedding(nn.Module):
         self._pe_read = {}          # stream -> event: the last read of the kept embedding on that stream
         self._pe_written = None     # event: the last (re)computation / in-place update of the kept embedding
         self._i2l = {}              # (device, request slot, R) -> [host matrices, (R, 4, 4) device tensor]: _matrices_device
+
+    @classmethod
+    def sine_only(cls, adapt_pos3d, *, embed_dims, depth_num, depth_start, pc_range, num_feats, temperature=10000, normalize=True,
+                  scale=2 * math.pi, eps=1e-6, offset=0.):
+        """For a head that owns its MLPs under its own state-dict keys (PETRHead / PETRv2Head): an instance over the caller's
+        `adapt_pos3d` - held as a plain attribute, so its parameters are registered once, in the caller - that serves padding_masks,
+        the kept sine branch (_sine_branch) and the persistent img2lidar buffer (_img2lidar, _matrices_device).  It has no
+        position_encoder and no fpe: forward and the other routes of this class are not for it."""
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self._configure(embed_dims, depth_num, depth_start, pc_range, num_feats, temperature, normalize, scale, eps, offset)
+        self.__dict__['adapt_pos3d'] = adapt_pos3d
+        return self
 
     # ---- pieces -------------------------------------------------------------------------------------------------
     def padding_masks(self, img_metas, feats):

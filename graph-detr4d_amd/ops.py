@@ -1389,6 +1389,49 @@ def mlp2_frustum_fwd(img2lidar, level_hw, pad_hw, depth_num, depth_start, pc_ran
     return out.view(r, s_tot, n2)
 
 
+def petr_keys_plan(bs, n, h, w, want_rows=True):
+    """gd4d_petr_keys_plan (host only, no GPU): (workgroups, rows per workgroup, key_rows) of petr_keys_fwd's launch - key_rows[m], a
+    list, is the key row that input row m = (b n + cam) h w + pix is written to (None with want_rows=False)."""
+    lib = _lib.load()
+    grid, per = ctypes.c_int32(0), ctypes.c_int32(0)
+    rows = (ctypes.c_int64 * (bs * n * h * w))() if want_rows else None
+    _lib.check(lib.gd4d_petr_keys_plan(int(bs), int(n), int(h), int(w), ctypes.addressof(grid), ctypes.addressof(per),
+                                       None if rows is None else ctypes.addressof(rows)), 'gd4d_petr_keys_plan')
+    return grid.value, per.value, None if rows is None else list(rows)
+
+
+def petr_keys_fwd(x, img2lidar, pad_hw, depth_num, depth_start, position_range, pe_image, pe_b2, sine, se_image=None, se_b2=None,
+                  memory=None, key_pos=None):
+    """gd4d_petr_keys_fwd: x (bs, n, 256, H, W) = input_proj's output, img2lidar (bs n, 4, 4), pe_image = mlp2_frustum_image of
+    position_encoder, sine (bs n, H W, 256) = the adapt_pos3d branch in channels-last rows, se_image = mlp2_image of fpe.conv_reduce /
+    conv_expand or None (no gate) -> (memory, key_pos), both (n H W, bs, 256): PETRTransformer.forward_keys' keys and key_pos."""
+    if x.dim() != 5 or x.shape[2] != 256:
+        raise ValueError(f'petr_keys_fwd: x must be (bs, n, 256, H, W), got {tuple(x.shape)}')
+    bs, n, c, h, w = x.shape
+    k1, pe_h, n2 = pe_image.shape_khn
+    if k1 != 3 * depth_num or n2 != 256:
+        raise ValueError(f'petr_keys_fwd: the position image is {k1} -> {pe_h} -> {n2}, the frustum has {3 * depth_num} channels')
+    se_h = 0
+    if se_image is not None:
+        sk, se_h, sn = se_image.shape_khn
+        if sk != 256 or sn != 256:
+            raise ValueError('petr_keys_fwd: the gate image must be 256 -> H -> 256')
+    if img2lidar.numel() != bs * n * 16 or sine.numel() != bs * n * h * w * 256:
+        raise ValueError(f'petr_keys_fwd: img2lidar must hold ({bs * n}, 4, 4) and sine ({bs * n}, {h * w}, 256)')
+    if se_b2 is not None and se_image is None:
+        raise ValueError('petr_keys_fwd: se_b2 is the gate\'s second bias: it comes with se_image')
+    for bias, what in ((pe_b2, 'pe_b2'), (se_b2, 'se_b2')):               # (the kernel reads 256 floats of each)
+        if bias is not None and bias.numel() != 256:
+            raise ValueError(f'petr_keys_fwd: {what} must hold 256 values, got {tuple(bias.shape)}')
+    memory = _out(memory, (n * h * w, bs, 256), x.device, 'memory')
+    key_pos = _out(key_pos, (n * h * w, bs, 256), x.device, 'key_pos')
+    _call('gd4d_petr_keys_fwd', _dev(x, 'x', F32), _dev(img2lidar, 'img2lidar', F32), bs, n, c, h, w, float(pad_hw[0]), float(pad_hw[1]),
+          int(depth_num), float(depth_start), _range6(position_range), _dev(pe_image, 'pe_image', U8), _opt(pe_b2, 'pe_b2'), pe_h,
+          _opt(se_image, 'se_image', U8), _opt(se_b2, 'se_b2'), se_h, _dev(sine, 'sine', F32), _dev(memory, 'memory', F32),
+          _dev(key_pos, 'key_pos', F32))
+    return memory, key_pos
+
+
 def gemm_tn_bf16x3(a, b, relu_b=False, want_colsum=True):
     """gd4d_gemm_tn_bf16x3: a (R, M), b (R, N) fp32 row-major -> (a^T b (M, N), column sums of a (M) or None): the weight /
     bias gradients of a Linear over R rows (a = output gradient, b = input; relu_b: ReLU on b as it is read)."""
@@ -3794,7 +3837,7 @@ def _on_tensor_device(fn):
 
 
 _HOST_ONLY = {'linear_sum_assignment_batch', 'cross_attn_plan_bytes', 'invalidate_chain_images', 'kept_in_place', 'chain_load', 'chain_gemm', 'chain_small_linear', 'chain_layernorm',
-              'chain_add', 'chain_refine', 'row_chain_fwd', 'chain_weight_image', 'chain_layernorm_bwd', 'cross_mha_plan', 'cross_mha_bwd_plan'}
+              'chain_add', 'chain_refine', 'row_chain_fwd', 'chain_weight_image', 'chain_layernorm_bwd', 'cross_mha_plan', 'cross_mha_bwd_plan', 'petr_keys_plan'}
 for _name, _fn in list(globals().items()):
     if inspect.isfunction(_fn) and _fn.__module__ == __name__ and not _name.startswith('_') and _name not in _HOST_ONLY:
         globals()[_name] = _on_tensor_device(_fn)

@@ -274,13 +274,21 @@ class PETRTransformer(nn.Module):
         bs, n, c, h, w = t.shape
         return t.permute(1, 3, 4, 0, 2).reshape(n * h * w, bs, c)
 
+    def forward_keys(self, keys, key_pos, key_padding_mask, query_embed, reg_branch=None):
+        """The decoder on key-major rows: keys, key_pos (n h w, bs, c) - what forward makes of its (bs, n, c, h, w) arguments with two
+        copies, and what ops.petr_keys_fwd writes directly -, key_padding_mask (bs, n h w), nonzero = padded pixel; query_embed
+        (num_query, c).  Returns out_dec (num_layers or 1, bs, num_query, c)."""
+        bs = keys.shape[1]
+        query_pos = query_embed[:, None, :].expand(-1, bs, -1).contiguous()        # the same embedding for every sample
+        states = self.decoder(query=torch.zeros_like(query_pos), key=keys, value=keys, key_pos=key_pos, query_pos=query_pos,
+                              key_padding_mask=key_padding_mask, reg_branch=reg_branch)
+        return states.transpose(1, 2)
+
     def forward(self, x, mask, query_embed, pos_embed, reg_branch=None):
         """x, pos_embed (bs, n, c, h, w); mask (bs, n, h, w), nonzero = padded pixel; query_embed (num_query, c).  Returns out_dec
         (num_layers or 1, bs, num_query, c) and memory (bs, n, c, h, w) - the keys laid out as x again."""
         bs, n, c, h, w = x.shape
         keys = self._camera_pixels_first(x)
         key_pos = self._camera_pixels_first(pos_embed)
-        query_pos = query_embed[:, None, :].expand(-1, bs, -1).contiguous()        # the same embedding for every sample
-        states = self.decoder(query=torch.zeros_like(query_pos), key=keys, value=keys, key_pos=key_pos, query_pos=query_pos,
-                              key_padding_mask=mask.reshape(bs, n * h * w), reg_branch=reg_branch)
-        return states.transpose(1, 2), keys.reshape(n, h, w, bs, c).permute(3, 0, 4, 1, 2)
+        out_dec = self.forward_keys(keys, key_pos, mask.reshape(bs, n * h * w), query_embed, reg_branch)
+        return out_dec, keys.reshape(n, h, w, bs, c).permute(3, 0, 4, 1, 2)

@@ -72,6 +72,7 @@ NECKS = Registry('neck', _mmcv('mmdet.models.builder.NECKS'))
 # (not mirrored into a real mmcv / mmdet: 'DCNv2' and 'ResNet' there are mmcv's and mmdet's own classes, which stay theirs)
 CONV_LAYERS = Registry('conv layer')
 BACKBONES = Registry('backbone')
+HEADS = Registry('head', _mmcv('mmdet.models.builder.HEADS'))
 
 
 def build_attention(cfg, default_args=None):
@@ -119,3 +120,7 @@ def build_conv_layer(cfg, *args, **kwargs):
 
 def build_backbone(cfg, default_args=None):
     return build_from_cfg(cfg, BACKBONES, default_args)
+
+
+def build_head(cfg, default_args=None):
+    return build_from_cfg(cfg, HEADS, default_args)

@@ -895,6 +895,24 @@ int gd4d_mlp2_pe_se_fwd(const float* img2lidar, const void* const* feats, const 
                         float pad_w, int D, float depth_start, const double* pc_range, const void* pe_image, const float* pe_b2,
                         int pe_H, const void* se_image, const float* se_b2, int se_H, const float* sine, void* const* outs,
                         float* pe_out, void* stream);
+/* gd4d_petr_keys_fwd - the key side of PETRHead / PETRv2Head in one launch (reference: dense_heads/petr_head.py:383-403,
+ * petrv2_head.py:444-469): for the R = bs n cameras of a request, x (R, C = 256, H, W) fp32 NCHW = input_proj's output and img2lidar
+ * (R, 16),
+ *     memory [(cam H W + p) bs + b, :] = x[b, cam, :, p]
+ *     key_pos[(cam H W + p) bs + b, :] = position_encoder(frustum)[b, cam, p, :] * sigmoid(conv_expand(relu(conv_reduce(x)))) + sine
+ * both (n H W, bs, 256): the key-major rows PETRTransformer's decoder takes, without the two permute copies, the (R, S, 192) frustum
+ * tensor, the (R, S, 1024) hidden activation or the (R, S, 256) embedding.  pe_image / pe_b2 / pe_H: as gd4d_mlp2_pe_se_fwd (the
+ * permuted image; pe_H = 1024 only); se_image / se_b2 / se_H (256 only): gd4d_mlp2_image of fpe.conv_reduce / conv_expand, or NULL -
+ * PETRHead, with_fpe=False - for key_pos = position_encoder(frustum) + sine; sine (R, H W, 256): the adapt_pos3d branch, channels-last
+ * rows; pad_h / pad_w, D (64 only), depth_start, position_range[6]: as gd4d_frustum_pe_input_fwd.  Every row of both outputs is
+ * written.  Other shapes: GD4D_EUNSUPPORTED.
+ * gd4d_petr_keys_plan (host only): the launch's grid, its rows per workgroup and - key_rows not NULL, bs n H W entries - the key row
+ * each input row m = (b n + cam) H W + p is written to. */
+int gd4d_petr_keys_plan(int bs, int n, int H, int W, int32_t* grid, int32_t* rows_per_block, int64_t* key_rows);
+int gd4d_petr_keys_fwd(const float* x, const float* img2lidar, int bs, int n, int C, int H, int W, float pad_h, float pad_w, int D,
+                       float depth_start, const double* position_range, const void* pe_image, const float* pe_b2, int pe_H,
+                       const void* se_image, const float* se_b2, int se_H, const float* sine, float* memory, float* key_pos,
+                       void* stream);
 
 /* gd4d_adamw_flat - the optimizer step of the reference's training recipe over ONE flat fp32 parameter / gradient buffer: clipping
  * of the gradient's L2 norm (torch.nn.utils.clip_grad_norm_: g *= min(1, max_norm / (norm + 1e-6)); max_norm <= 0: none) followed by

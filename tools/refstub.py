@@ -812,3 +812,61 @@ def load_petr_transformer():
     _mod('mmcv.utils', ConfigDict=dict, build_from_cfg=lambda cfg, registry, default_args=None: registry.build(cfg, **(default_args or {})),
          deprecated_api_warning=_deprecated_api_warning, to_2tuple=lambda x: (x, x))
     return load_reference(('petr_transformer',))['petr_transformer']
+
+
+# --------------------------------------------------------------------------------------
+# PETRHead / PETRv2Head: the stage between the neck and the boxes of the petr / petrv2 configs
+# --------------------------------------------------------------------------------------
+class AnchorFreeHead(nn.Module):
+    """mmdet's AnchorFreeHead as far as the PETR heads use it: the base constructor (they build their own layers) and the place in
+    the MRO that `super(AnchorFreeHead, self)._load_from_state_dict` skips."""
+
+    def __init__(self, num_classes, in_channels, init_cfg=None, **kwargs):
+        super().__init__()
+
+
+def load_petr_head():
+    """Import the reference's dense_heads/petr_head.py and petrv2_head.py unmodified and return the two modules.  Their transformer is
+    the reference's own (load_petr_transformer), their positional encoding its own SinePositionalEncoding3D, their coder its own
+    NMSFreeCoder.  Stand-ins: AnchorFreeHead (above), build_loss (an object with the loss's `use_sigmoid`: the forward pass reads
+    nothing else), the registries' build_* functions, mmcv's Conv2d / Linear (= torch's); `inverse_sigmoid` is the reference's own copy
+    (utils/detr3d_transformer.py:28-43).  Build the heads with train_cfg=None: assigner and sampler are not stubbed."""
+    load_petr_transformer()
+    coder = load_coder()
+    BBOX_CODERS.register_module(module=coder.NMSFreeCoder)
+    ref = load_reference(('detr3d_transformer',))['detr3d_transformer']
+    cnn = sys.modules['mmcv.cnn']
+    cnn.Conv2d, cnn.Linear = nn.Conv2d, nn.Linear
+    cnn.bias_init_with_prob = lambda p: float(-math.log((1 - p) / p))
+    cnn.kaiming_init = None                                       # imported, never called
+    bricks = sys.modules['mmcv.cnn.bricks.transformer']
+    bricks.POSITIONAL_ENCODING = POSITIONAL_ENCODING
+    bricks.build_positional_encoding = lambda cfg: POSITIONAL_ENCODING.build(cfg)
+    run = sys.modules['mmcv.runner']
+    run.force_fp32 = run.auto_fp16 = lambda *a, **k: (lambda f: f)
+    run.BaseModule = BaseModule
+    core = sys.modules['mmdet.core']
+    for name in ('bbox_cxcywh_to_xyxy', 'bbox_xyxy_to_cxcywh', 'build_assigner', 'build_sampler', 'reduce_mean'):
+        setattr(core, name, None)
+    core.multi_apply = multi_apply
+    utils = sys.modules['mmdet.models.utils']
+    utils.build_transformer = lambda cfg: TRANSFORMER.build(cfg)
+    utils.NormedLinear = None                                     # normedlinear=False in every shipped config
+    models = sys.modules['mmdet.models']
+    models.HEADS = Registry('head')
+    models.build_loss = lambda cfg: types.SimpleNamespace(use_sigmoid=cfg.get('use_sigmoid', False))
+    _mod('mmdet.models.dense_heads')
+    _mod('mmdet.models.dense_heads.anchor_free_head', AnchorFreeHead=AnchorFreeHead)
+    _mod('mmdet.models.utils.transformer', inverse_sigmoid=ref.inverse_sigmoid, DetrTransformerDecoderLayer=DetrTransformerDecoderLayer)
+    _mod('mmdet3d.core.bbox.coders', build_bbox_coder=lambda cfg: BBOX_CODERS.build(cfg))
+    for full in ('projects.mmdet3d_plugin.models', 'projects.mmdet3d_plugin.models.dense_heads', 'projects.mmdet3d_plugin.models.utils'):
+        if full not in sys.modules:
+            m = types.ModuleType(full)
+            m.__path__ = [os.path.join(REFERENCE_ROOT, *full.split('.'))]
+            sys.modules[full] = m
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        importlib.import_module('projects.mmdet3d_plugin.models.utils.positional_encoding')     # registers SinePositionalEncoding3D
+        v1 = importlib.import_module('projects.mmdet3d_plugin.models.dense_heads.petr_head')
+        v2 = importlib.import_module('projects.mmdet3d_plugin.models.dense_heads.petrv2_head')
+    return v1, v2
