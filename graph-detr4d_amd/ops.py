@@ -993,10 +993,10 @@ def linear_group_fwd(x, weights, biases, x2=None, want_xsum=False):
     return (outs, xsum) if want_xsum else outs
 
 
-def layernorm_fwd(x, gamma, beta, eps=1e-5, res=None, relu=False):
-    """gd4d_layernorm_fwd over the last dimension of a contiguous tensor."""
+def layernorm_fwd(x, gamma, beta, eps=1e-5, res=None, relu=False, out=None):
+    """gd4d_layernorm_fwd over the last dimension of a contiguous tensor.  out: the tensor of x's shape to write (default a new one)."""
     c = x.shape[-1]
-    out = torch.empty_like(x)
+    out = _out(out, x.shape, x.device, 'layernorm_fwd: out')
     _call('gd4d_layernorm_fwd', _dev(x, 'x', F32), _opt(res, 'res'), _dev(gamma, 'gamma', F32), _dev(beta, 'beta', F32), _dev(out, 'out'),
           x.numel() // c, c, float(eps), int(bool(relu)))
     return out
@@ -1142,15 +1142,24 @@ def mha_core_bwd(q, k, v, out, grad_out, lse, num_heads, attn_mask=None, packed_
     return (dqk, dv) if packed_qk else (dq, dk, dv)
 
 
-def layernorm_bwd(x, gamma, beta, grad_y, eps=1e-5, res=None, relu=False, into=None, defer=False):
+def layernorm_bwd(x, gamma, beta, grad_y, eps=1e-5, res=None, relu=False, into=None, defer=False, outs=None):
     """gd4d_layernorm_bwd.  Returns (dx like x, dgamma, dbeta); into=(g_buf, b_buf): dgamma / dbeta are ADDED to these.
     defer=True: only dx and the partial column sums are computed - returns (dx, workspace, (M, C)) for
-    layernorm_bwd_reduce_group."""
+    layernorm_bwd_reduce_group.  outs=(dx, dgamma, dbeta): the tensors to write (not with into / defer; default new ones)."""
     lib = _lib.load()
     c = x.shape[-1]
     m = x.numel() // c
-    dx = torch.empty_like(x)
-    dg, db = (None, None) if defer else ((torch.empty_like(gamma), torch.empty_like(gamma)) if into is None else into)
+    if outs is not None and (into is not None or defer):
+        raise ValueError('layernorm_bwd: outs goes with neither into nor defer')
+    o_dx, o_dg, o_db = outs if outs is not None else (None, None, None)
+    dx = _out(o_dx, x.shape, x.device, 'layernorm_bwd: dx')
+    if defer:
+        dg, db = None, None
+    elif into is None:
+        dg = _out(o_dg, gamma.shape, gamma.device, 'layernorm_bwd: dgamma')
+        db = _out(o_db, gamma.shape, gamma.device, 'layernorm_bwd: dbeta')
+    else:
+        dg, db = into
     nbytes = lib.gd4d_layernorm_bwd_workspace_bytes(m, c)
     ws = torch.empty(nbytes, device=x.device, dtype=U8)
     _call('gd4d_layernorm_bwd', _dev(x, 'x', F32), _opt(res, 'res'), _dev(gamma, 'gamma', F32), _opt(beta, 'beta'),
@@ -2985,17 +2994,19 @@ def depth_conv_tiles(level_hw, n):
     return int(_lib.load().gd4d_depth_conv_tiles(lv, len(level_hw), int(n)))
 
 
-def depth_conv_raw(feats, image, bias=None, want_partials=False, outs=None):
+def depth_conv_raw(feats, image, bias=None, want_partials=False, outs=None, partials=None):
     """gd4d_depth_conv_raw: L <= 4 levels (N, 256, H_l, W_l) -> conv3x3 (+ bias) per level, one launch, no BatchNorm / ReLU / gate.
-    want_partials: also returns the (tiles, 2, 256) per-tile mean / M2 partials depth_bn_stats merges."""
+    want_partials: also returns the (tiles, 2, 256) per-tile mean / M2 partials depth_bn_stats merges (written into `partials` when
+    given)."""
     lib = _lib.load()
     if outs is None:
         outs = [torch.empty(f.shape, device=f.device, dtype=F32) for f in feats]
     nl, n, c, lv = _depth_levels('depth_conv_raw', feats, outs)
-    partials = None
     if want_partials:
         tiles = int(lib.gd4d_depth_conv_tiles(lv, nl, n))
-        partials = torch.empty(max(tiles, 1), 2, 256, device=feats[0].device, dtype=F32)
+        partials = _out(partials, (max(tiles, 1), 2, 256), feats[0].device, 'depth_conv_raw: partials')
+    elif partials is not None:
+        raise ValueError('depth_conv_raw: partials given without want_partials')
     _call('gd4d_depth_conv_raw', _ptrs(feats, 'feats'), _ptrs(outs, 'outs'), lv, nl, n, c, _dev(image, 'image', U8), _opt(bias, 'bias'),
           _opt(partials, 'partials'))
     return (outs, partials) if want_partials else outs
@@ -3027,17 +3038,18 @@ def depth_bn_act_fwd(ys, stats, bn_bias, gate, outs=None):
     return outs
 
 
-def depth_bn_bwd(douts, ys, stats, bn_bias, gate, frozen=False):
+def depth_bn_bwd(douts, ys, stats, bn_bias, gate, frozen=False, outs=None, small=None, workspace=None):
     """gd4d_depth_bn_bwd: the BatchNorm / ReLU / gate backward of L <= 4 levels -> (dy list, dgamma, dbeta, dgate (N, 256), dbias),
-    dgamma / dbeta / dgate / dbias summed over the levels of the call."""
+    dgamma / dbeta / dgate / dbias summed over the levels of the call.  outs: the L dy maps to write; small: the (3 + N, 256) tensor
+    whose rows become dgamma, dbeta, dbias and dgate; workspace: the kernel's scratch floats (defaults: new ones)."""
     lib = _lib.load()
-    dys = [torch.empty_like(y) for y in ys]
+    dys = [torch.empty_like(y) for y in ys] if outs is None else list(outs)
     nl, n, c, lv = _depth_levels('depth_bn_bwd', ys, douts, dys)
     if tuple(stats.shape) != (nl, 3, c) or tuple(gate.shape) != (n, c):
         raise ValueError(f'depth_bn_bwd: stats ({nl}, 3, {c}) and gate ({n}, {c}) expected')
     dev = ys[0].device
-    ws = torch.empty(max(int(lib.gd4d_depth_bn_bwd_workspace_bytes(nl, n)) // 4, 1), device=dev, dtype=F32)
-    small = torch.empty(3 + n, c, device=dev, dtype=F32)
+    ws = _out(workspace, (max(int(lib.gd4d_depth_bn_bwd_workspace_bytes(nl, n)) // 4, 1),), dev, 'depth_bn_bwd: workspace')
+    small = _out(small, (3 + n, c), dev, 'depth_bn_bwd: small')
     dgamma, dbeta, dbias, dgate = small[0], small[1], small[2], small[3:]
     _call('gd4d_depth_bn_bwd', _ptrs(douts, 'douts'), _ptrs(ys, 'ys'), _ptrs(dys, 'dys'), lv, nl, n, c, _dev(stats, 'stats', F32),
           _dev(bn_bias, 'bn_bias', F32), _dev(gate, 'gate', F32), int(bool(frozen)), _dev(ws, 'workspace', F32),
@@ -3045,9 +3057,10 @@ def depth_bn_bwd(douts, ys, stats, bn_bias, gate, frozen=False):
     return dys, dgamma, dbeta, dgate, dbias
 
 
-def depth_conv_wgrad(dys, feats, partitions=None):
+def depth_conv_wgrad(dys, feats, partitions=None, out=None, workspace=None):
     """gd4d_depth_conv_wgrad: dW (256, 256, 3, 3) = sum over L <= 4 levels, cameras and pixels of dy[oc, p] x[ic, p + tap], one launch
-    plus the reduction over `partitions` partial sums (default: one workgroup per compute unit, at most one partition per tile)."""
+    plus the reduction over `partitions` partial sums (default: one workgroup per compute unit, at most one partition per tile).
+    out / workspace: the dW tensor and the partial sums' scratch floats to use (defaults: new ones)."""
     lib = _lib.load()
     nl, n, c, lv = _depth_levels('depth_conv_wgrad', feats, dys)
     dev = feats[0].device
@@ -3058,8 +3071,8 @@ def depth_conv_wgrad(dys, feats, partitions=None):
     nbytes = int(lib.gd4d_depth_conv_wgrad_workspace_bytes(partitions))
     if nbytes == 0:
         raise ValueError(f'depth_conv_wgrad: partitions = {partitions}')
-    ws = torch.empty(nbytes // 4, device=dev, dtype=F32)
-    dw = torch.empty(256, 256, 3, 3, device=dev, dtype=F32)
+    ws = _out(workspace, (nbytes // 4,), dev, 'depth_conv_wgrad: workspace')
+    dw = _out(out, (256, 256, 3, 3), dev, 'depth_conv_wgrad: out')
     _call('gd4d_depth_conv_wgrad', _ptrs(dys, 'dys'), _ptrs(feats, 'feats'), lv, nl, n, c, partitions, _dev(ws, 'workspace', F32),
           _dev(dw, 'dw', F32))
     return dw
@@ -3147,14 +3160,17 @@ def fpn_conv_fwd(feats, images, biases, outs=None, channels_last_out=False):
     elif len(outs) != nl or any(tuple(o.shape) != tuple(f.shape) for o, f in zip(outs, feats)):
         raise ValueError('fpn_conv_fwd: outs must match the levels\' shapes')
     maps = [_fpn_map(o, 'outs') for o in outs]
-    if len({cl for _, cl in maps}) != 1:
+    # a one-pixel level is stored the same way in both layouts: it goes with whatever the other levels are
+    layouts = {cl for o, (_, cl) in zip(outs, maps) if not (o.is_contiguous() and _is_cl(o))}
+    if len(layouts) > 1:
         raise ValueError('fpn_conv_fwd: outs must be all NCHW or all channels-last')
+    out_cl = layouts.pop() if layouts else 0
     fp = _ptrs(feats, 'feats')
     op = (ctypes.c_void_p * nl)(*[m[0].value for m in maps])
     ip = _ptrs(images, 'images', U8)
     bp = _ptrs(biases, 'biases', optional=True)
     lv = _levels(feats)
-    _call('gd4d_fpn_conv_fwd', fp, op, lv, nl, int(n), int(feats[0].shape[1]), ip, bp, maps[0][1])
+    _call('gd4d_fpn_conv_fwd', fp, op, lv, nl, int(n), int(feats[0].shape[1]), ip, bp, out_cl)
     return outs
 
 
@@ -3185,24 +3201,25 @@ def _fpn_grad_map(t, name, channels=256):
     return _dev(t, name, F32)
 
 
-def fpn_lateral_dgrad(g, image_t, cin):
+def fpn_lateral_dgrad(g, image_t, cin, out=None):
     """gd4d_fpn_lateral_dgrad: g (N, 256, H, W) fp32 NCHW, the lateral's gradient -> dx (N, Cin, H, W) = W^T g;
-    image_t = fpn_lateral_image_t(weight)."""
+    image_t = fpn_lateral_image_t(weight).  out: the dx tensor to write (default a new one)."""
     lib = _lib.load()
     gp = _fpn_grad_map(g, 'g')
     n, _, h, w = (int(v) for v in g.shape)
     cin = int(cin)
     if int(lib.gd4d_fpn_lateral_image_mode_bytes(cin, 1)) != image_t.numel():
         raise ValueError(f'fpn_lateral_dgrad: image_t of {image_t.numel()} bytes is not the transposed image of a lateral with Cin = {cin}')
-    dx = torch.empty(n, cin, h, w, device=g.device, dtype=F32)
+    dx = _out(out, (n, cin, h, w), g.device, 'fpn_lateral_dgrad: out')
     _call('gd4d_fpn_lateral_dgrad', gp, n, cin, h, w, _dev(image_t, 'image_t', U8), _dev(dx, 'dx', F32))
     return dx
 
 
-def fpn_lateral_wgrad(g, x, partitions=None):
+def fpn_lateral_wgrad(g, x, partitions=None, outs=None, workspace=None):
     """gd4d_fpn_lateral_wgrad: g (N, 256, H, W), x (N, Cin, H, W) fp32 NCHW -> (dW (256, Cin, 1, 1), db (256)): the sums over cameras and
     pixels of g[oc, p] x[ic, p] and of g[oc, p], K split over `partitions` partial sums added in order (default: about two workgroups
-    per compute unit, at most one partition per 64-pixel tile)."""
+    per compute unit, at most one partition per 64-pixel tile).  outs=(dW, db) / workspace: the tensors to write and the partial
+    sums' scratch floats (defaults: new ones)."""
     lib = _lib.load()
     gp = _fpn_grad_map(g, 'g')
     xp = _fpn_grad_map(x, 'x', None)
@@ -3218,9 +3235,10 @@ def fpn_lateral_wgrad(g, x, partitions=None):
     nbytes = int(lib.gd4d_fpn_lateral_wgrad_workspace_bytes(cin, partitions))
     if nbytes == 0:
         raise _lib.Gd4dError(f'fpn_lateral_wgrad: Cin = {cin} (a multiple of 32 in [32, 2048]), partitions = {partitions} (1 .. 4096)')
-    ws = torch.empty(nbytes // 4, device=g.device, dtype=F32)
-    dw = torch.empty(256, cin, 1, 1, device=g.device, dtype=F32)
-    db = torch.empty(256, device=g.device, dtype=F32)
+    o_dw, o_db = outs if outs is not None else (None, None)
+    ws = _out(workspace, (nbytes // 4,), g.device, 'fpn_lateral_wgrad: workspace')
+    dw = _out(o_dw, (256, cin, 1, 1), g.device, 'fpn_lateral_wgrad: dW')
+    db = _out(o_db, (256,), g.device, 'fpn_lateral_wgrad: db')
     _call('gd4d_fpn_lateral_wgrad', gp, xp, n, cin, h, w, partitions, _dev(ws, 'workspace', F32), _dev(dw, 'dw', F32), _dev(db, 'db', F32))
     return dw, db
 
@@ -3236,10 +3254,11 @@ def fpn_topdown_bwd(g_fine, g_coarse):
     return g_coarse
 
 
-def fpn_extra_conv_dgrad(dy, image_t, hw, mask=None, add=None):
+def fpn_extra_conv_dgrad(dy, image_t, hw, mask=None, add=None, out=None):
     """gd4d_fpn_extra_conv_dgrad: dy (N, 256, (H + 1) // 2, (W + 1) // 2) -> the stride-2 level's input gradient (N, 256, H, W), hw = (H, W);
     image_t = depth_net_image_t(weight).  mask (N, 256, H, W): the result is kept where mask > 0 (the input the forward applied its
-    ReLU to); add (N, 256, H, W): added after that (the level's own incoming gradient)."""
+    ReLU to); add (N, 256, H, W): added after that (the level's own incoming gradient).  out: the dx tensor to write (default a new
+    one)."""
     dp = _fpn_grad_map(dy, 'dy')
     n, h, w = int(dy.shape[0]), int(hw[0]), int(hw[1])
     if tuple(dy.shape[2:]) != ((h + 1) // 2, (w + 1) // 2):
@@ -3247,31 +3266,33 @@ def fpn_extra_conv_dgrad(dy, image_t, hw, mask=None, add=None):
     for t, name in ((mask, 'mask'), (add, 'add')):
         if t is not None and tuple(t.shape) != (n, 256, h, w):
             raise ValueError(f'fpn_extra_conv_dgrad: {name} must be ({n}, 256, {h}, {w})')
-    dx = torch.empty(n, 256, h, w, device=dy.device, dtype=F32)
+    dx = _out(out, (n, 256, h, w), dy.device, 'fpn_extra_conv_dgrad: out')
     _call('gd4d_fpn_extra_conv_dgrad', dp, n, 256, h, w, _dev(image_t, 'image_t', U8), _opt(mask, 'mask'), _opt(add, 'add'),
           _dev(dx, 'dx', F32))
     return dx
 
 
-def fpn_extra_conv_wgrad(dy, x, relu_in=False):
+def fpn_extra_conv_wgrad(dy, x, relu_in=False, outs=None):
     """gd4d_fpn_extra_conv_wgrad: dy (N, 256, (H + 1) // 2, (W + 1) // 2), x (N, 256, H, W) fp32 NCHW -> (dW (256, 256, 3, 3), db (256)) of
-    the stride-2 convolution (relu_in: of relu(x))."""
+    the stride-2 convolution (relu_in: of relu(x)).  outs=(dW, db): the tensors to write (default new ones)."""
     dp, xp = _fpn_grad_map(dy, 'dy'), _fpn_grad_map(x, 'x')
     n, _, h, w = (int(v) for v in x.shape)
     if tuple(dy.shape) != (n, 256, (h + 1) // 2, (w + 1) // 2):
         raise ValueError(f'fpn_extra_conv_wgrad: dy {tuple(dy.shape)} is not the stride-2 output of x {tuple(x.shape)}')
-    dw = torch.empty(256, 256, 3, 3, device=x.device, dtype=F32)
-    db = torch.empty(256, device=x.device, dtype=F32)
+    o_dw, o_db = outs if outs is not None else (None, None)
+    dw = _out(o_dw, (256, 256, 3, 3), x.device, 'fpn_extra_conv_wgrad: dW')
+    db = _out(o_db, (256,), x.device, 'fpn_extra_conv_wgrad: db')
     _call('gd4d_fpn_extra_conv_wgrad', dp, xp, n, 256, h, w, int(bool(relu_in)), _dev(dw, 'dw', F32), _dev(db, 'db', F32))
     return dw, db
 
 
-def fpn_bias_grad(g):
-    """gd4d_fpn_bias_grad: g (N, 256, H, W) fp32 NCHW -> db (256), its channel sums in a fixed order."""
+def fpn_bias_grad(g, out=None, workspace=None):
+    """gd4d_fpn_bias_grad: g (N, 256, H, W) fp32 NCHW -> db (256), its channel sums in a fixed order.  out / workspace: the db tensor
+    and the (N 256) scratch floats to use (defaults: new ones)."""
     gp = _fpn_grad_map(g, 'g')
     n, _, h, w = (int(v) for v in g.shape)
-    ws = torch.empty(n * 256, device=g.device, dtype=F32)
-    db = torch.empty(256, device=g.device, dtype=F32)
+    ws = _out(workspace, (n * 256,), g.device, 'fpn_bias_grad: workspace')
+    db = _out(out, (256,), g.device, 'fpn_bias_grad: out')
     _call('gd4d_fpn_bias_grad', gp, n, 256, h, w, _dev(ws, 'workspace', F32), _dev(db, 'db', F32))
     return db
 
@@ -3398,12 +3419,13 @@ def _dcn_bwd_args(name, dout, y, scale, x, offmask, cout, stride):
     return n, cin, cout, h, w, ho, wo
 
 
-def dcn_bwd_data(dout, x, offmask, image_t, cout, stride=1, y=None, scale=None, sigmoid_grad=False, dx=None, want_dx=True):
+def dcn_bwd_data(dout, x, offmask, image_t, cout, stride=1, y=None, scale=None, sigmoid_grad=False, dx=None, want_dx=True, doff=None):
     """gd4d_dcn_bwd_data: the input and offset / modulation gradients of dcn_fwd in one pass.  dout (N, cout, Ho, Wo); y: the forward's
     output when it applied its ReLU (the mask y > 0), scale: the folded BatchNorm's, both optional; image_t = dcn_weight_image_t(weight).
     Returns (dx (N, Cin, H, W) or None, doff (N, 27, Ho, Wo)): doff[:18] the offset gradient, doff[18:] the modulation's - times m (1 - m)
     with sigmoid_grad (the gradient of conv_offset's raw output).  dx is ADDED into with float atomics (the one output whose last bits
-    depend on the run): a given dx must hold zeros (or what to add to); by default a zeroed one is made."""
+    depend on the run): a given dx must hold zeros (or what to add to); by default a zeroed one is made.  doff: the tensor to write
+    (default a new one)."""
     lib = _lib.load()
     n, cin, cout, h, w, ho, wo = _dcn_bwd_args('dcn_bwd_data', dout, y, scale, x, offmask, cout, stride)
     if int(lib.gd4d_dcn_weight_image_t_bytes(cin, cout)) != image_t.numel() or image_t.numel() == 0:
@@ -3412,7 +3434,7 @@ def dcn_bwd_data(dout, x, offmask, image_t, cout, stride=1, y=None, scale=None, 
         dx = torch.zeros(n, cin, h, w, device=x.device, dtype=F32)
     elif dx is not None and tuple(dx.shape) != (n, cin, h, w):
         raise ValueError(f'dcn_bwd_data: dx must be ({n}, {cin}, {h}, {w})')
-    doff = torch.empty(n, DCN_OFFSET_CHANNELS, ho, wo, device=x.device, dtype=F32)
+    doff = _out(doff, (n, DCN_OFFSET_CHANNELS, ho, wo), x.device, 'dcn_bwd_data: doff')
     _call('gd4d_dcn_bwd_data', _dev(dout, 'dout', F32), _opt(y, 'y'), _opt(scale, 'scale'), _dev(x, 'x', F32),
           _dev(offmask, 'offmask', F32), n, cin, cout, h, w, int(stride), _dev(image_t, 'image_t', U8), int(bool(sigmoid_grad)),
           _opt(dx, 'dx'), _dev(doff, 'doff', F32))
@@ -3429,10 +3451,11 @@ def _dcn_partitions(lib, dev, n, cin, h, w, stride, partitions, waves_per_block)
     return int(partitions)
 
 
-def dcn_wgrad(dout, x, offmask, cout, stride=1, y=None, scale=None, partitions=None):
+def dcn_wgrad(dout, x, offmask, cout, stride=1, y=None, scale=None, partitions=None, outs=None, workspace=None):
     """gd4d_dcn_wgrad: (dW (cout, Cin, 3, 3), dbias (cout)) of dcn_fwd, the modulated samples recomputed as the forward forms them; y /
     scale as dcn_bwd_data.  One launch plus the reduction over `partitions` partial sums (default: about two workgroups per compute
-    unit, at most one partition per 64-pixel tile)."""
+    unit, at most one partition per 64-pixel tile).  outs=(dW, dbias) / workspace: the tensors to write and the partial sums' scratch
+    floats (defaults: new ones)."""
     lib = _lib.load()
     n, cin, cout, h, w, ho, wo = _dcn_bwd_args('dcn_wgrad', dout, y, scale, x, offmask, cout, stride)
     partitions = _dcn_partitions(lib, x.device, n, cin, h, w, stride, partitions, 4)
@@ -3440,9 +3463,10 @@ def dcn_wgrad(dout, x, offmask, cout, stride=1, y=None, scale=None, partitions=N
     if nbytes == 0:
         raise _lib.Gd4dError(f'dcn_wgrad: Cin = {cin}, Cout = {cout}, partitions = {partitions}: the kernel takes channels that are multiples '
                              'of 64 in [64, 512] and 1..4096 partitions')
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=F32)
-    dw = torch.empty(cout, cin, 3, 3, device=x.device, dtype=F32)
-    db = torch.empty(cout, device=x.device, dtype=F32)
+    o_dw, o_db = outs if outs is not None else (None, None)
+    ws = _out(workspace, (nbytes // 4,), x.device, 'dcn_wgrad: workspace')
+    dw = _out(o_dw, (cout, cin, 3, 3), x.device, 'dcn_wgrad: dW')
+    db = _out(o_db, (cout,), x.device, 'dcn_wgrad: dbias')
     _call('gd4d_dcn_wgrad', _dev(dout, 'dout', F32), _opt(y, 'y'), _opt(scale, 'scale'), _dev(x, 'x', F32), _dev(offmask, 'offmask', F32),
           n, cin, cout, h, w, int(stride), partitions, _dev(ws, 'workspace', F32), _dev(dw, 'dw', F32), _dev(db, 'dbias', F32))
     return dw, db
@@ -3467,9 +3491,9 @@ def dcn_offset_conv_dgrad(doff, weight, dx, stride=1):
     return dx
 
 
-def dcn_offset_conv_wgrad(doff, x, stride=1, partitions=None):
+def dcn_offset_conv_wgrad(doff, x, stride=1, partitions=None, outs=None, workspace=None):
     """gd4d_dcn_offset_conv_wgrad: (dW (27, Cin, 3, 3), db (27)) of conv_offset from doff (N, 27, Ho, Wo) and its input x; `partitions` as
-    dcn_wgrad."""
+    dcn_wgrad, and so are outs=(dW, db) / workspace."""
     lib = _lib.load()
     n, cin, h, w = _dcn_doff('dcn_offset_conv_wgrad', doff, x, stride)
     partitions = _dcn_partitions(lib, x.device, n, cin, h, w, stride, partitions, 1)
@@ -3477,9 +3501,10 @@ def dcn_offset_conv_wgrad(doff, x, stride=1, partitions=None):
     if nbytes == 0:
         raise _lib.Gd4dError(f'dcn_offset_conv_wgrad: Cin = {cin}, partitions = {partitions}: the kernel takes Cin a multiple of 64 in '
                              '[64, 512] and 1..4096 partitions')
-    ws = torch.empty(nbytes // 4, device=x.device, dtype=F32)
-    dw = torch.empty(DCN_OFFSET_CHANNELS, cin, 3, 3, device=x.device, dtype=F32)
-    db = torch.empty(DCN_OFFSET_CHANNELS, device=x.device, dtype=F32)
+    o_dw, o_db = outs if outs is not None else (None, None)
+    ws = _out(workspace, (nbytes // 4,), x.device, 'dcn_offset_conv_wgrad: workspace')
+    dw = _out(o_dw, (DCN_OFFSET_CHANNELS, cin, 3, 3), x.device, 'dcn_offset_conv_wgrad: dW')
+    db = _out(o_db, (DCN_OFFSET_CHANNELS,), x.device, 'dcn_offset_conv_wgrad: db')
     _call('gd4d_dcn_offset_conv_wgrad', _dev(doff, 'doff', F32), _dev(x, 'x', F32), n, cin, h, w, int(stride), partitions,
           _dev(ws, 'workspace', F32), _dev(dw, 'dw', F32), _dev(db, 'db', F32))
     return dw, db
@@ -3729,7 +3754,7 @@ def _vv_partitions(dev, tiles, chunks, partitions):
     return int(partitions)
 
 
-def _vv_wgrad_outputs(name, lib, weight, bn, cin, cout, taps, partitions, want):
+def _vv_wgrad_outputs(name, lib, weight, bn, cin, cout, taps, partitions, want, outs=None, workspace=None):
     if tuple(bn.shape) != (3, cout):
         raise ValueError(f'{name}: bn must be (3, {cout}): scale, rstd, mean')
     if weight.numel() != cout * cin * taps or int(weight.shape[0]) != cout:
@@ -3741,32 +3766,35 @@ def _vv_wgrad_outputs(name, lib, weight, bn, cin, cout, taps, partitions, want):
         raise _lib.Gd4dError(f'{name}: {cin} -> {cout} channels, partitions = {partitions}: the kernel takes multiples of 32 within the '
                              'forward\'s limits and 1..4096 partitions')
     dev = weight.device
-    ws = torch.empty(nbytes // 4, device=dev, dtype=F32)
-    dw = torch.empty(weight.shape, device=dev, dtype=F32) if want[0] else None
-    dgamma = torch.empty(cout, device=dev, dtype=F32) if want[1] else None
-    dbeta = torch.empty(cout, device=dev, dtype=F32) if want[2] else None
+    o_dw, o_dgamma, o_dbeta = outs if outs is not None else (None, None, None)
+    ws = _out(workspace, (nbytes // 4,), dev, f'{name}: workspace')
+    dw = _out(o_dw, weight.shape, dev, f'{name}: dW') if want[0] else None
+    dgamma = _out(o_dgamma, (cout,), dev, f'{name}: dgamma') if want[1] else None
+    dbeta = _out(o_dbeta, (cout,), dev, f'{name}: dbeta') if want[2] else None
     return ws, dw, dgamma, dbeta
 
 
-def conv3x3_wgrad(dz, x, weight, bn, want=(True, True, True), partitions=None):
+def conv3x3_wgrad(dz, x, weight, bn, want=(True, True, True), partitions=None, outs=None, workspace=None):
     """gd4d_conv3x3_wgrad: the parameter gradients of relu(BN(conv3x3(x))) behind a frozen BatchNorm from dz (N, Cout, H, W), the
     gradient of the BatchNorm's output after the ReLU mask, and the convolution's input x (N, Cin, H, W): (dW (Cout, Cin, 3, 3), dgamma,
-    dbeta), None where `want` says so.  weight: the unscaled fp32 weight; bn (3, Cout): scale = gamma rstd, rstd, mean."""
+    dbeta), None where `want` says so.  weight: the unscaled fp32 weight; bn (3, Cout): scale = gamma rstd, rstd, mean.
+    outs=(dW, dgamma, dbeta) / workspace: the tensors to write and the partial sums' scratch floats (defaults: new ones)."""
     lib = _lib.load()
     n, cout, h, w = _dcn_x(dz, 'conv3x3_wgrad')
     if x.dim() != 4 or (int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) != (n, h, w):
         raise ValueError(f'conv3x3_wgrad: x {tuple(x.shape)} for dz {tuple(dz.shape)}')
     cin = int(x.shape[1])
     partitions = _vv_partitions(dz.device, int(lib.gd4d_conv3x3_wgrad_tiles(n, h, w)), cin // 32, partitions)
-    ws, dw, dgamma, dbeta = _vv_wgrad_outputs('conv3x3_wgrad', lib, weight, bn, cin, cout, 9, partitions, want)
+    ws, dw, dgamma, dbeta = _vv_wgrad_outputs('conv3x3_wgrad', lib, weight, bn, cin, cout, 9, partitions, want, outs, workspace)
     _call('gd4d_conv3x3_wgrad', _dev(dz, 'dz', F32), _dev(x, 'x', F32), n, cin, cout, h, w, partitions, _dev(ws, 'workspace', F32),
           _dev(weight, 'weight', F32), _dev(bn, 'bn', F32), _opt(dw, 'dw'), _opt(dgamma, 'dgamma'), _opt(dbeta, 'dbeta'))
     return dw, dgamma, dbeta
 
 
-def osa_concat_wgrad(dz, dz_sums, sources, weight, bn, want=(True, True, True), partitions=None):
+def osa_concat_wgrad(dz, dz_sums, sources, weight, bn, want=(True, True, True), partitions=None, outs=None, workspace=None):
     """gd4d_osa_concat_wgrad: conv3x3_wgrad's counterpart for the aggregation: sources are the L + 1 maps where they lie, dz_sums
-    (N, Cout) dz's plane sums (ese_bwd's second result), weight (Cout, K[, 1, 1]).  Returns (dW of weight's shape, dgamma, dbeta)."""
+    (N, Cout) dz's plane sums (ese_bwd's second result), weight (Cout, K[, 1, 1]).  Returns (dW of weight's shape, dgamma, dbeta);
+    outs / workspace as conv3x3_wgrad's."""
     lib = _lib.load()
     n, cout, h, w = _dcn_x(dz, 'osa_concat_wgrad')
     sources = list(sources)
@@ -3782,17 +3810,18 @@ def osa_concat_wgrad(dz, dz_sums, sources, weight, bn, want=(True, True, True), 
     if any(c % 32 for c in chans):
         raise _lib.Gd4dError(f'osa_concat_wgrad: sources of {chans} channels; the kernel takes multiples of 32')
     partitions = _vv_partitions(dz.device, int(lib.gd4d_osa_concat_wgrad_tiles(n, h, w)), ((k + 63) // 64) * ((cout + 255) // 256), partitions)
-    ws, dw, dgamma, dbeta = _vv_wgrad_outputs('osa_concat_wgrad', lib, weight, bn, k, cout, 1, partitions, want)
+    ws, dw, dgamma, dbeta = _vv_wgrad_outputs('osa_concat_wgrad', lib, weight, bn, k, cout, 1, partitions, want, outs, workspace)
     _call('gd4d_osa_concat_wgrad', _dev(dz, 'dz', F32), _dev(dz_sums, 'dz_sums', F32), _ptrs(sources, 'sources'),
           (ctypes.c_int32 * len(chans))(*chans), len(chans), n, h, w, cout, partitions, _dev(ws, 'workspace', F32),
           _dev(weight, 'weight', F32), _dev(bn, 'bn', F32), _opt(dw, 'dw'), _opt(dgamma, 'dgamma'), _opt(dbeta, 'dbeta'))
     return dw, dgamma, dbeta
 
 
-def ese_bwd(dout, xt, partials, gate, fc_weight, want_fc=(True, True)):
+def ese_bwd(dout, xt, partials, gate, fc_weight, want_fc=(True, True), outs=None, workspace=None):
     """gd4d_ese_bwd: the backward of out = xt * gate (+ identity) with gate = ese_gate(partials, ...), up to the aggregation's BatchNorm
     output: returns (dz (N, C, H, W) = (dout gate + fc_w^T dv / HW) [xt > 0], its plane sums (N, C), dfc_w, dfc_b), where dv =
-    (sum_hw dout xt) / 6 for 0 < gate < 1 and 0 at and beyond the clamp's corners; dfc_w / dfc_b are None where want_fc says so."""
+    (sum_hw dout xt) / 6 for 0 < gate < 1 and 0 at and beyond the clamp's corners; dfc_w / dfc_b are None where want_fc says so.
+    outs=(dz, sums, dfc_w, dfc_b) / workspace: the tensors to write and the scratch floats (defaults: new ones)."""
     lib = _lib.load()
     n, c, h, w = _dcn_x(xt, 'ese_bwd')
     if dout.shape != xt.shape or tuple(gate.shape) != (n, c) or partials.dim() != 3 or (int(partials.shape[0]), int(partials.shape[2])) != (n, c):
@@ -3803,10 +3832,11 @@ def ese_bwd(dout, xt, partials, gate, fc_weight, want_fc=(True, True)):
     if nbytes == 0:
         raise _lib.Gd4dError(f'ese_bwd: C = {c}; the kernel takes a multiple of 32 in [32, 1024]')
     dev = xt.device
-    ws = torch.empty(nbytes // 4, device=dev, dtype=F32)
-    dz, sums = torch.empty_like(xt), torch.empty(n, c, device=dev, dtype=F32)
-    dfc_w = torch.empty(fc_weight.shape, device=dev, dtype=F32) if want_fc[0] else None
-    dfc_b = torch.empty(c, device=dev, dtype=F32) if want_fc[1] else None
+    o_dz, o_sums, o_w, o_b = outs if outs is not None else (None, None, None, None)
+    ws = _out(workspace, (nbytes // 4,), dev, 'ese_bwd: workspace')
+    dz, sums = _out(o_dz, xt.shape, dev, 'ese_bwd: dz'), _out(o_sums, (n, c), dev, 'ese_bwd: sums')
+    dfc_w = _out(o_w, fc_weight.shape, dev, 'ese_bwd: dfc_w') if want_fc[0] else None
+    dfc_b = _out(o_b, (c,), dev, 'ese_bwd: dfc_b') if want_fc[1] else None
     _call('gd4d_ese_bwd', _dev(dout, 'dout', F32), _dev(xt, 'xt', F32), _dev(partials, 'partials', F32), int(partials.shape[1]),
           _dev(gate, 'gate', F32), _dev(fc_weight, 'fc_weight', F32), n, c, h * w, _dev(ws, 'workspace', F32), _dev(dz, 'dz', F32),
           _dev(sums, 'dz_sums', F32), _opt(dfc_w, 'dfc_w'), _opt(dfc_b, 'dfc_b'))
