@@ -41,6 +41,19 @@ inline bool allow_dynamic_lds(const void* kern, int bytes) {
   return true;
 }
 
+// The metre range of the reference points, as every kernel that de-normalises one reads it: rng_scale =
+// float(double(hi) - double(lo)), rng_lo = float(lo), for as many axes as the struct keeps (pc_range = lo xyz, hi xyz).
+// Written once: the kernels that project a query must agree on these two roundings bit for bit.
+template <class P>
+inline void fill_metre_range(P& p, const double* pc_range) {
+  constexpr int axes = sizeof(p.rng_scale) / sizeof(p.rng_scale[0]);
+  static_assert(axes <= 3 && sizeof(p.rng_lo) == sizeof(p.rng_scale), "rng_scale / rng_lo: one float per axis");
+  for (int k = 0; k < axes; ++k) {
+    p.rng_scale[k] = static_cast<float>(pc_range[k + 3] - pc_range[k]);
+    p.rng_lo[k] = static_cast<float>(pc_range[k]);
+  }
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t v) {

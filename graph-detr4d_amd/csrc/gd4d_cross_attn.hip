@@ -301,10 +301,7 @@ extern "C" int gd4d_cross_attn_fwd(const void* value, const int32_t* level_hw, c
     start += h * w;
   }
   p.S = start;
-  for (int k = 0; k < 3; ++k) {
-    p.rng_scale[k] = static_cast<float>(pc_range[k + 3] - pc_range[k]);
-    p.rng_lo[k] = static_cast<float>(pc_range[k]);
-  }
+  fill_metre_range(p, pc_range);
   p.img_h = img_h; p.img_w = img_w;
   hipStream_t s = static_cast<hipStream_t>(stream);
   return value_dtype == GD4D_F32 ? launch_heads<float>(p, Hh, s) : launch_heads<uint16_t>(p, Hh, s);

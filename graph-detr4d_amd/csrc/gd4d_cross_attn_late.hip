@@ -527,10 +527,7 @@ extern "C" int gd4d_cross_attn_agg_fwd(const void* feats_cl, const int32_t* leve
   }
   p.S = start;
   if ((unsigned long long)B * N * start >= (1ull << 31)) return GD4D_EUNSUPPORTED;   // pixel indices are 32-bit
-  for (int k = 0; k < 3; ++k) {
-    p.rng_scale[k] = static_cast<float>(pc_range[k + 3] - pc_range[k]);
-    p.rng_lo[k] = static_cast<float>(pc_range[k]);
-  }
+  fill_metre_range(p, pc_range);
   p.img_h = img_h; p.img_w = img_w;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool bf16 = feats_dtype == GD4D_BF16;

@@ -4,7 +4,7 @@
 // them (plus gd4d_detr3d.hip) run its adjoint:
 //   gd4d_cross_attn.hip             gather from projected values          gd4d_cross_attn_bwd.hip          its backward
 //   gd4d_cross_attn_late.hip        aggregate raw features per head       gd4d_cross_attn_sliced_bwd.hip   the plan's backward
-//   gd4d_cross_attn_sliced.hip      plan + channel-sliced gathers         gd4d_detr3d.hip                  projection + adjoint only
+//   gd4d_cross_attn_sliced.hip      plan + channel-sliced gathers         gd4d_detr3d.hip                  projection, softmax_lp, both adjoints
 // INVARIANT: every kernel that names a (camera, head, point) entry's visibility, image coordinates, softmax weight or corner
 // weights takes them from the helpers below, so the bits agree between kernels by construction: item m of head h in the
 // plan's backward IS item m of the plan, and the mask of every forward form is the same bytes.  All units are built with
@@ -318,8 +318,9 @@ __device__ __forceinline__ void corner_pairs(const BilinearCell& cell, int lw, i
 }
 
 // Backward of the cell: d[c] = dL/d(corner c's weight) (0 for a corner outside the map) -> T = sum_c bw_c d_c and its
-// derivatives by x and y (pixel units)
-__device__ __forceinline__ void bilinear_adjoint(const BilinearCell& cell, const float d[4], float& T, float& dTdx, float& dTdy) {
+// derivatives by x and y (pixel units).  Cell: BilinearCell, or gd4d_detr3d.hip's GridCell - anything with dx, dy and weights().
+template <class Cell>
+__device__ __forceinline__ void bilinear_adjoint(const Cell& cell, const float d[4], float& T, float& dTdx, float& dTdy) {
   const float dx = cell.dx, dy = cell.dy;
   float bw[4];
   cell.weights(bw);

@@ -600,10 +600,7 @@ static int gd4d_fill_plan_params_impl(gd4d::PlanParams& pp, const float* ref, co
   p.mask_out = mask_out; p.uv_out = uv_out; p.order = query_order; p.wsum = wsum;
   p.B = B; p.N = N; p.Q = Q; p.L = L; p.P = P;
   p.raw_cam = (flags & GD4D_CA_RAW_CAM_WEIGHTS) ? 1 : 0;
-  for (int k = 0; k < 3; ++k) {
-    p.rng_scale[k] = static_cast<float>(pc_range[k + 3] - pc_range[k]);
-    p.rng_lo[k] = static_cast<float>(pc_range[k]);
-  }
+  fill_metre_range(p, pc_range);
   p.img_h = img_h; p.img_w = img_w;
   for (int l = 0; l < 4; ++l) { pp.g.lvl_w[l] = 1; pp.g.lvl_h[l] = 1; pp.g.cam_stride[l] = 0; }
   for (int l = 0; l < L; ++l) {

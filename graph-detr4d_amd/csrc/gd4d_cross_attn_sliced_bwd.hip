@@ -1017,10 +1017,7 @@ extern "C" int gd4d_cross_attn_plan_bwd(const float* ref, const float* offsets, 
   p.order = query_order;
   p.B = B; p.N = N; p.Q = Q; p.L = L; p.P = P;
   p.raw_cam = (flags & GD4D_CA_RAW_CAM_WEIGHTS) ? 1 : 0;
-  for (int k = 0; k < 3; ++k) {
-    p.rng_scale[k] = static_cast<float>(pc_range[k + 3] - pc_range[k]);
-    p.rng_lo[k] = static_cast<float>(pc_range[k]);
-  }
+  fill_metre_range(p, pc_range);
   p.img_h = img_h; p.img_w = img_w;
   for (int l = 0; l < 4; ++l) { pp.lvl_w[l] = 1; pp.lvl_h[l] = 1; }
   for (int l = 0; l < L; ++l) {

@@ -92,10 +92,7 @@ static int fill(OrderParams& p, const double* pc_range, int B, int Q) {
   if (B <= 0 || Q <= 0) return GD4D_EINVAL;
   if (B > ORD_MAX_BINS / 8 || (long long)B * Q > 4LL * ORD_THREADS) return GD4D_EUNSUPPORTED;
   p.B = B; p.Q = Q; p.abins = ORD_MAX_BINS / B;
-  for (int k = 0; k < 2; ++k) {
-    p.rng_scale[k] = static_cast<float>(pc_range[k + 3] - pc_range[k]);
-    p.rng_lo[k] = static_cast<float>(pc_range[k]);
-  }
+  fill_metre_range(p, pc_range);
   return GD4D_OK;
 }
 

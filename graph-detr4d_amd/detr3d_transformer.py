@@ -37,6 +37,26 @@ def feature_sampling(mlvl_feats, reference_points, pc_range, img_metas):
     return reference_points.clone(), r['sampled'], mask
 
 
+def _project_to_grid(reference_points, lidar2img, pc_range, img_h, img_w):
+    """The torch-ops projection of both modules' GD4D_TORCH_OPS=1 routes (reference :402-427, :671-680), differentiable:
+    reference points (B, Q, 3) in [0, 1] -> metres -> camera -> grid coordinates in [-1, 1] (B, N, Q, 2) and the boolean
+    visibility (B, N, Q): in front of the camera and strictly inside the image."""
+    b, q = reference_points.shape[:2]
+    n = lidar2img.shape[1]
+    lo = reference_points.new_tensor(pc_range[:3])
+    scale = reference_points.new_tensor([pc_range[3] - pc_range[0], pc_range[4] - pc_range[1], pc_range[5] - pc_range[2]])
+    pts = reference_points * scale + lo                                   # metres (:402-405)
+    pts = torch.cat([pts, torch.ones_like(pts[..., :1])], dim=-1)         # (B, Q, 4)
+    cam = torch.matmul(lidar2img.view(b, n, 1, 4, 4), pts.view(b, 1, q, 4, 1)).squeeze(-1)   # (B, N, Q, 4)
+    eps = 1e-5
+    mask = cam[..., 2:3] > eps
+    xy = cam[..., 0:2] / torch.maximum(cam[..., 2:3], torch.full_like(cam[..., 2:3], eps))
+    xy = torch.stack([xy[..., 0] / img_w, xy[..., 1] / img_h], dim=-1)
+    xy = (xy - 0.5) * 2
+    mask = mask & (xy[..., 0:1] > -1.0) & (xy[..., 0:1] < 1.0) & (xy[..., 1:2] > -1.0) & (xy[..., 1:2] < 1.0)
+    return xy, mask.squeeze(-1)
+
+
 @ATTENTION.register_module()
 class Detr3DCrossAtten(nn.Module):
     """DETR3D baseline cross-attention (reference :229-390): one sampling point per query, no
@@ -130,18 +150,7 @@ class Detr3DCrossAtten(nn.Module):
             out = Fn.sequential_autograd(self.output_proj, agg).permute(1, 0, 2)
             pos_feat = Fn.sequential_autograd(self.position_encoder, Fn.inverse_sigmoid(reference_points)).permute(1, 0, 2)
             return self.dropout(out) + inp_residual + pos_feat
-        rng = self.pc_range
-        lo = reference_points.new_tensor(rng[:3])
-        scale = reference_points.new_tensor([rng[3] - rng[0], rng[4] - rng[1], rng[5] - rng[2]])
-        pts = reference_points * scale + lo                                   # metres (:402-405)
-        pts = torch.cat([pts, torch.ones_like(pts[..., :1])], dim=-1)         # (B, Q, 4)
-        cam = torch.matmul(lidar2img.view(b, n, 1, 4, 4), pts.view(b, 1, q, 4, 1)).squeeze(-1)   # (B, N, Q, 4)
-        eps = 1e-5
-        mask = cam[..., 2:3] > eps
-        xy = cam[..., 0:2] / torch.maximum(cam[..., 2:3], torch.full_like(cam[..., 2:3], eps))
-        xy = torch.stack([xy[..., 0] / img_w, xy[..., 1] / img_h], dim=-1)
-        xy = (xy - 0.5) * 2
-        mask = mask & (xy[..., 0:1] > -1.0) & (xy[..., 0:1] < 1.0) & (xy[..., 1:2] > -1.0) & (xy[..., 1:2] < 1.0)
+        xy, mask = _project_to_grid(reference_points, lidar2img, self.pc_range, img_h, img_w)
         mask = mask.view(b, n, 1, q, 1, 1).permute(0, 2, 3, 1, 4, 5)          # (B, 1, Q, N, 1, 1)
         sampled = []
         for feat in value:
@@ -262,17 +271,8 @@ class Detr3DCrossAttenV2(nn.Module):
         off = Fn.sequential_autograd(self.sampling_offsets, x).view(b, q, n, hh, nl, npt, 2)
         lidar2img = Fn.lidar2img_device(img_metas, query)
         img_h, img_w = Fn.img_hw(img_metas)
-        rng = self.pc_range
-        lo = reference_points.new_tensor(rng[:3])
-        scale = reference_points.new_tensor([rng[3] - rng[0], rng[4] - rng[1], rng[5] - rng[2]])
-        pts = reference_points * scale + lo
-        pts = torch.cat([pts, torch.ones_like(pts[..., :1])], dim=-1)
-        cam = torch.matmul(lidar2img.view(b, n, 1, 4, 4), pts.view(b, 1, q, 4, 1)).squeeze(-1)   # (1, N, Q, 4)
-        eps = 1e-5
-        z_ok = cam[..., 2] > eps
-        xy = cam[..., 0:2] / torch.maximum(cam[..., 2:3], torch.full_like(cam[..., 2:3], eps))
-        g = (torch.stack([xy[..., 0] / img_w, xy[..., 1] / img_h], dim=-1) - 0.5) * 2
-        mask = (z_ok & (g[..., 0] > -1.0) & (g[..., 0] < 1.0) & (g[..., 1] > -1.0) & (g[..., 1] < 1.0)).to(x.dtype)
+        g, mask = _project_to_grid(reference_points, lidar2img, self.pc_range, img_h, img_w)   # (1, N, Q, 2), (1, N, Q)
+        mask = mask.to(x.dtype)
         out = x.new_zeros(q, hh, d)
         for lvl, feat in enumerate(value):
             h_l, w_l = feat.shape[-2:]
