@@ -1,5 +1,5 @@
-// What gd4d_cross_mha.hip (forward, inference pack) and gd4d_cross_mha_train.hip (training pack, backward) share: the sizes, the
-// key-split plan and the two fragment layouts of the split-bf16 planes.
+// What gd4d_cross_mha.hip (forward) and gd4d_cross_mha_train.hip (both packs, backward) share beyond the device pieces of
+// gd4d_attn_pieces.h: the sizes, the key-split plan, the layout checks and the two fragment layouts of the split-bf16 planes.
 //
 // A plane holds rows (keys, or queries) x 32 channels of one (batch, head) in steps of 32 rows, two fragments of 64 lanes x 8 bf16
 // per step, in one of two layouts - named after the planes the forward reads:
@@ -18,12 +18,11 @@
 //   q scale log2(e) and dout, each as rows and as columns: both backward kernels, packed per gd4d_cross_mha_bwd call into its workspace
 //   (the rows are the queries; pad queries are zeros there too, with Dq = 0 and lse = +inf beside them).
 #pragma once
-#include "gd4d_common.h"
-#include "gd4d_bf16x3.h"
+#include "gd4d_attn_pieces.h"
 
 namespace gd4d {
 
-constexpr int XM_D = 32;          // head dimension (MHA_D)
+constexpr int XM_D = ATTN_D;      // head dimension
 constexpr int XM_WAVES = 4;
 
 __host__ __device__ inline int xm_split_first(int steps, int splits, int s) { return (int)((long long)steps * s / splits); }
@@ -33,17 +32,11 @@ __host__ __device__ inline size_t xm_frag(int H, int steps, int b, int h, int st
   return ((((((size_t)b * H + h) * steps + step) * 2 + t) * 64) + lane) * 8;
 }
 
-// acc + a b with both operands as hi + mid + lo: six products (lo x lo, lo x mid, mid x lo dropped), smallest terms first, summed
-// on their own before they meet the accumulator
-__device__ __forceinline__ f32x4 xm_x6(const u32x4& ah, const u32x4& am, const u32x4& al, const u32x4& bh, const u32x4& bm,
-                                      const u32x4& bl, const f32x4 acc) {
-  f32x4 t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(am), frag(bm), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-  t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(al), frag(bh), t, 0, 0, 0);
-  t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bl), t, 0, 0, 0);
-  t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(am), frag(bh), t, 0, 0, 0);
-  t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bm), t, 0, 0, 0);
-  t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bh), t, 0, 0, 0);
-  return acc + t;
+// What the four entry points that take planes check after their own arguments and their plan, in this order: the
+// smallest row stride of their fp32 operands and the plane stride (EINVAL), then `aligned` (EALIGN)
+inline int xm_check_layout(int min_ld, long long plane_stride, int Lk, int B, int H, bool aligned) {
+  if (min_ld < H * XM_D || plane_stride < (long long)gd4d_cross_mha_plane_elems(Lk, B, H) || (plane_stride & 7)) return GD4D_EINVAL;
+  return aligned ? GD4D_OK : GD4D_EALIGN;
 }
 
 inline int xm_plan(int Lq, int Lk, int B, int H, int q_tile, int splits, int* qt_out, int* splits_out) {

@@ -1,4 +1,5 @@
-// Backward of gd4d_cross_mha_fwd / gd4d_cross_mha_train_fwd: PETR's global cross-attention trained on a long key axis.
+// The packs (fp32 rows -> split-bf16 planes) of gd4d_cross_mha_fwd / gd4d_cross_mha_train_fwd, inference and training, and the
+// backward: PETR's global cross-attention trained on a long key axis.
 // Reference: projects/mmdet3d_plugin/models/utils/petr_transformer.py (PETRMultiheadAttention.forward -> nn.MultiheadAttention with
 // key_padding_mask and attn_drop, under autograd).
 //
@@ -14,10 +15,11 @@
 // All accumulate in fp32.
 // No atomics: every sum has one owner and a fixed order.
 //
-//   cross_bwd_pack_kernel     fp32 rows -> split-bf16 planes in both fragment layouts (gd4d_cross_mha.h).  One body, two uses: the
-//                             training form of the K|V pack (K rows x3 and V columns x3 as the training forward reads them, V rows x3 and K
-//                             columns x3 for the backward), and the query-side pack of a backward call (q scaled by scale log2(e): rows x3, columns x3;
-//                             dout: rows x3, columns x3) which also leaves Dq and lse log2(e) per (batch, head, query).
+//   cross_pack_kernel         fp32 rows -> split-bf16 planes in both fragment layouts (gd4d_cross_mha.h).  One body, three uses: the
+//                             inference K|V pack (K rows x3, V columns x2: gd4d_cross_mha_pack_kv), its training form (K rows x3 and V
+//                             columns x3 as the training forward reads them, V rows x3 and K columns x3 for the backward), and the
+//                             query-side pack of a backward call (q scaled by scale log2(e): rows x3, columns x3; dout: rows x3,
+//                             columns x3) which also leaves Dq and lse log2(e) per (batch, head, query).
 //   cross_bwd_query_kernel    a workgroup owns 32 queries of one (batch, head) and one key split, as the forward: its waves take the
 //                             split's 32-key steps round-robin, S^T = K Q^T and dP^T = V dout^T come out in one register layout,
 //                             dS^T in that layout is the B operand of dq^T += K^T dS^T.  Waves merge in LDS in wave order, splits
@@ -34,18 +36,17 @@ namespace gd4d {
 
 constexpr int XB_KEYS = 64;       // keys per workgroup of the key-side kernel
 constexpr int XB_QPLANES = 12;    // planes of the query-side pack
-constexpr float XB_LN2 = 0.6931471805599453f;
-constexpr float XB_LOG2E = 1.4426950408889634f;
 
 // ---------------------------------------------------------------- pack ----------------------------------------------------------------
 struct CrossPackGroup {
   const float* src;               // rows (l B + b) at stride ld
-  unsigned short* dst;            // three planes (hi, mid, lo), `plane` elements apart
+  unsigned short* dst;            // `planes` planes, `plane` elements apart
   int ld, columns;                // columns: 0 = row fragments, 1 = column fragments
   float scale;
+  int planes;                     // 3: hi, mid, lo (split8x3); 2: hi, lo (split8: what the inference forward's P V reads of V)
 };
 
-struct CrossTrainPackParams {
+struct CrossPackParams {
   CrossPackGroup g[4];
   long long plane;
   int groups, L, B, H, steps;
@@ -56,7 +57,7 @@ struct CrossTrainPackParams {
 };
 
 // grid (steps, groups [+ 1 with dsum], B), 4 waves; a wave writes whole fragments (1 KB contiguous per plane)
-__global__ __launch_bounds__(64 * XM_WAVES) void cross_bwd_pack_kernel(const CrossTrainPackParams p) {
+__global__ __launch_bounds__(64 * XM_WAVES) void cross_pack_kernel(const CrossPackParams p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int step = blockIdx.x, b = blockIdx.z;
   const int lo = lane & 15, g = lane >> 4;
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(64 * XM_WAVES) void cross_bwd_pack_kernel(const Cro
         const float4 x = *reinterpret_cast<const float4*>(a + d), y = *reinterpret_cast<const float4*>(o + d);
         s += x.x * y.x; s += x.y * y.y; s += x.z * y.z; s += x.w * y.w;
       }
-      l2 = p.lse[((size_t)row * p.B + b) * p.H + h] * XB_LOG2E;
+      l2 = p.lse[((size_t)row * p.B + b) * p.H + h] * ATTN_LOG2E;
     }
     const size_t e = (((size_t)b * p.H + h) * p.steps + step) * 32 + r;
     p.dsum[e] = s;
@@ -106,10 +107,14 @@ __global__ __launch_bounds__(64 * XM_WAVES) void cross_bwd_pack_kernel(const Cro
     }
     const size_t e = xm_frag(p.H, p.steps, b, h, step, t, lane);
     u32x4 hi, md, lw;
-    split8x3(x, hi, md, lw);
+    if (G.planes == 3) {
+      split8x3(x, hi, md, lw);
+      *reinterpret_cast<u32x4*>(G.dst + p.plane + e) = md;
+    } else {
+      split8(x, hi, lw);
+    }
     *reinterpret_cast<u32x4*>(G.dst + e) = hi;
-    *reinterpret_cast<u32x4*>(G.dst + p.plane + e) = md;
-    *reinterpret_cast<u32x4*>(G.dst + 2 * p.plane + e) = lw;
+    *reinterpret_cast<u32x4*>(G.dst + (G.planes - 1) * p.plane + e) = lw;
   }
 }
 
@@ -132,24 +137,9 @@ struct CrossBwdParams {
   float scale;
 };
 
-// The six-product score tile of the forward: a = the K pieces as A, b = the Q pieces as B there; the key-side kernel hands the
-// pieces over the other way round (A = Q, B = K) and gets the transposed tile of the same products in the same order.
-__device__ __forceinline__ f32x4 xb_scores(const u32x4& ah, const u32x4& am, const u32x4& al, const u32x4& bh, const u32x4& bm,
-                                          const u32x4& bl, bool a_is_k) {
-  f32x4 st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(am), frag(bm), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-  if (a_is_k) {
-    st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(al), frag(bh), st, 0, 0, 0);      // k_lo q_hi
-    st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bl), st, 0, 0, 0);      // k_hi q_lo
-    st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(am), frag(bh), st, 0, 0, 0);      // k_mid q_hi
-    st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bm), st, 0, 0, 0);      // k_hi q_mid
-  } else {
-    st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bl), st, 0, 0, 0);      // q_hi k_lo
-    st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(al), frag(bh), st, 0, 0, 0);      // q_lo k_hi
-    st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bm), st, 0, 0, 0);      // q_hi k_mid
-    st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(am), frag(bh), st, 0, 0, 0);      // q_mid k_hi
-  }
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag(ah), frag(bh), st, 0, 0, 0);
-}
+// (The score tiles are products6 of gd4d_attn_pieces.h: the query-side kernel hands it the K pieces as A and the Q pieces as B, as
+// the forward; the key-side kernel the other way round, products6<false>, and gets the transposed tile of the same products in the
+// same order.)
 
 struct XbQueryShared { float o[XM_WAVES][32][XM_D + 1]; };
 
@@ -166,18 +156,14 @@ __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_bwd_query_kernel(const
   const int b = blockIdx.z;
   const bool drop = p.drop_thresh != 0u;
 
-  u32x4 qh[2], qm[2], ql[2], gh[2], gm[2], gl[2];      // Q^T and dout^T as B operands: lane (query qi, g), channels 8 g .. 8 g + 7
+  Planes3 qp[2], gp[2];                // Q^T and dout^T as B operands: lane (query qi, g), channels 8 g .. 8 g + 7
   float lse2[2], dsum[2];
   uint32_t drow[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const size_t e = xm_frag(p.H, p.qsteps, b, h, qstep, t, lane);
-    qh[t] = *reinterpret_cast<const u32x4*>(p.qk + e);
-    qm[t] = *reinterpret_cast<const u32x4*>(p.qk + p.qplane + e);
-    ql[t] = *reinterpret_cast<const u32x4*>(p.qk + 2 * p.qplane + e);
-    gh[t] = *reinterpret_cast<const u32x4*>(p.dok + e);
-    gm[t] = *reinterpret_cast<const u32x4*>(p.dok + p.qplane + e);
-    gl[t] = *reinterpret_cast<const u32x4*>(p.dok + 2 * p.qplane + e);
+    qp[t] = load_planes(p.qk, p.qplane, e);
+    gp[t] = load_planes(p.dok, p.qplane, e);
     const size_t r = (((size_t)b * p.H + h) * p.qsteps + qstep) * 32 + 16 * t + qi;
     lse2[t] = p.lse2[r];                       // +inf past Lq: probability 0
     dsum[t] = p.dsum[r];
@@ -193,69 +179,49 @@ __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_bwd_query_kernel(const
   }
 
   const int s_first = xm_split_first(p.ksteps, p.splits, split), s_last = xm_split_first(p.ksteps, p.splits, split + 1);
-  struct StepData { u32x4 kh[2], km[2], kl[2], vh[2], vm[2], vl[2]; unsigned mk; int step; };      // (K columns: fetched where they are used)
+  struct StepData { Planes3 k[2], v[2]; KeyStepMask mask; };        // K rows, V rows (K columns: fetched where they are used)
   auto fetch = [&](const int step, StepData& d) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const size_t e = xm_frag(p.H, p.ksteps, b, h, step, t, lane);
-      d.kh[t] = *reinterpret_cast<const u32x4*>(p.kk + e);
-      d.km[t] = *reinterpret_cast<const u32x4*>(p.kk + p.kplane + e);
-      d.kl[t] = *reinterpret_cast<const u32x4*>(p.kk + 2 * p.kplane + e);
-      d.vh[t] = *reinterpret_cast<const u32x4*>(p.vk + e);
-      d.vm[t] = *reinterpret_cast<const u32x4*>(p.vk + p.kplane + e);
-      d.vl[t] = *reinterpret_cast<const u32x4*>(p.vk + 2 * p.kplane + e);
+      d.k[t] = load_planes(p.kk, p.kplane, e);
+      d.v[t] = load_planes(p.vk, p.kplane, e);
     }
-    const int key = step * 32 + (lane & 31);
-    d.mk = key >= p.Lk ? 1u : (p.mask ? (unsigned)p.mask[(size_t)b * p.Lk + key] : 0u);
-    d.step = step;
+    d.mask.fetch(p.mask, b, p.Lk, step, lane);
   };
-  auto compute = [&](const StepData& d) {
-    const unsigned bits = (unsigned)__ballot(d.mk != 0);              // wave-uniform: bit i <-> key 32 step + i
+  auto compute = [&](const int step, const StepData& d) {
+    const unsigned bits = d.mask.bits();
     if (bits == 0xffffffffu) return;                                  // every probability of the step is 0
-    const unsigned mb = bits >> (4 * g);                              // bit 16 kt + r <-> this lane's register r of key tile kt
-    u32x4 ch[2], cm[2], cl[2];
+    const unsigned mb = KeyStepMask::of_lane(bits, g);
+    Planes3 c[2];
 #pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      const size_t e = xm_frag(p.H, p.ksteps, b, h, d.step, half, lane);
-      ch[half] = *reinterpret_cast<const u32x4*>(p.kv + e);
-      cm[half] = *reinterpret_cast<const u32x4*>(p.kv + p.kplane + e);
-      cl[half] = *reinterpret_cast<const u32x4*>(p.kv + 2 * p.kplane + e);
-    }
+    for (int half = 0; half < 2; ++half) c[half] = load_planes(p.kv, p.kplane, xm_frag(p.H, p.ksteps, b, h, step, half, lane));
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       float ds[8];
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         // S^T and dP^T, lane (qi, g) register r <-> key 16 kt + 4 g + r of the step
-        const f32x4 st = xb_scores(d.kh[kt], d.km[kt], d.kl[kt], qh[t], qm[t], ql[t], true);
-        const f32x4 dp = xm_x6(d.vh[kt], d.vm[kt], d.vl[kt], gh[t], gm[t], gl[t], f32x4{0.f, 0.f, 0.f, 0.f});
+        const f32x4 st = products6(d.k[kt], qp[t]);
+        const f32x4 dp = xm_x6(d.v[kt], gp[t], f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float pr = ((mb >> (16 * kt + r)) & 1u) ? 0.f : __builtin_amdgcn_exp2f(st[r] - lse2[t]);
           float x = dp[r];
           if (drop) {
-            const uint32_t key = (uint32_t)(32 * d.step + 16 * kt + 4 * g + r);
+            const uint32_t key = (uint32_t)(32 * step + 16 * kt + 4 * g + r);
             x = mha_drop_keep(seed_lo, seed_hi, drow[t] + key, p.drop_thresh) ? x * p.inv_keep : 0.f;
           }
           ds[4 * kt + r] = pr * (x - dsum[t]);
         }
       }
       // dq^T += K^T dS^T: A = K^T[d = lane & 15 (+ 16)][k = 8 g + j], B = this lane's own eight dS
-      u32x4 dh, dm, dl;
-      split8x3(ds, dh, dm, dl);
-      a0[t] = xm_x6(ch[0], cm[0], cl[0], dh, dm, dl, a0[t]);
-      a1[t] = xm_x6(ch[1], cm[1], cl[1], dh, dm, dl, a1[t]);
+      const Planes3 dsp = split_planes3(ds);
+      a0[t] = xm_x6(c[0], dsp, a0[t]);
+      a1[t] = xm_x6(c[1], dsp, a1[t]);
     }
   };
-  {
-    StepData cur, nxt;                                                // one step of look-ahead, as the forward
-    if (s_first + wave < s_last) fetch(s_first + wave, cur);
-    for (int step = s_first + wave; step < s_last; step += XM_WAVES) {
-      if (step + XM_WAVES < s_last) fetch(step + XM_WAVES, nxt);
-      compute(cur);
-      cur = nxt;
-    }
-  }
+  walk_steps<XM_WAVES, StepData>(s_first, s_last, wave, fetch, compute);
 
   // ---- the waves' key slices, summed in wave order ----
 #pragma unroll
@@ -306,22 +272,17 @@ __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_bwd_key_kernel(const C
   const bool have = kstep < p.ksteps;                                  // (an odd number of key steps: the last block's second half)
   const bool drop = p.drop_thresh != 0u;
 
-  u32x4 kh[2], km[2], kl[2], vh[2], vm[2], vl[2];      // K^T and V^T as B operands: lane (key ki, g), channels 8 g .. 8 g + 7
+  Planes3 kp[2], vp[2];                // K^T and V^T as B operands: lane (key ki, g), channels 8 g .. 8 g + 7
   bool masked[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    const u32x4 zero{0u, 0u, 0u, 0u};
-    kh[t] = km[t] = kl[t] = vh[t] = vm[t] = vl[t] = zero;
+    kp[t] = vp[t] = Planes3{};
     const int key = 32 * kstep + 16 * t + ki;
     masked[t] = key >= p.Lk || (p.mask && p.mask[(size_t)b * p.Lk + key]);
     if (have) {
       const size_t e = xm_frag(p.H, p.ksteps, b, h, kstep, t, lane);
-      kh[t] = *reinterpret_cast<const u32x4*>(p.kk + e);
-      km[t] = *reinterpret_cast<const u32x4*>(p.kk + p.kplane + e);
-      kl[t] = *reinterpret_cast<const u32x4*>(p.kk + 2 * p.kplane + e);
-      vh[t] = *reinterpret_cast<const u32x4*>(p.vk + e);
-      vm[t] = *reinterpret_cast<const u32x4*>(p.vk + p.kplane + e);
-      vl[t] = *reinterpret_cast<const u32x4*>(p.vk + 2 * p.kplane + e);
+      kp[t] = load_planes(p.kk, p.kplane, e);
+      vp[t] = load_planes(p.vk, p.kplane, e);
     }
   }
   uint32_t seed_lo = 0, seed_hi = 0;
@@ -340,10 +301,7 @@ __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_bwd_key_kernel(const C
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {          // one query tile's row fragments at a time
         const size_t e = xm_frag(p.H, p.qsteps, b, h, qstep, qt, lane);
-        const u32x4 qh = *reinterpret_cast<const u32x4*>(p.qk + e), qm = *reinterpret_cast<const u32x4*>(p.qk + p.qplane + e),
-                    ql = *reinterpret_cast<const u32x4*>(p.qk + 2 * p.qplane + e);
-        const u32x4 gh = *reinterpret_cast<const u32x4*>(p.dok + e), gm = *reinterpret_cast<const u32x4*>(p.dok + p.qplane + e),
-                    gl = *reinterpret_cast<const u32x4*>(p.dok + 2 * p.qplane + e);
+        const Planes3 qp = load_planes(p.qk, p.qplane, e), gp = load_planes(p.dok, p.qplane, e);
         const size_t r0 = (((size_t)b * p.H + h) * p.qsteps + qstep) * 32 + 16 * qt + 4 * g;
         const float4 l4 = *reinterpret_cast<const float4*>(p.lse2 + r0), s4 = *reinterpret_cast<const float4*>(p.dsum + r0);
         const float lse2[4] = {l4.x, l4.y, l4.z, l4.w}, dsum[4] = {s4.x, s4.y, s4.z, s4.w};      // lse2 = +inf past Lq
@@ -355,8 +313,8 @@ __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_bwd_key_kernel(const C
 #pragma unroll
         for (int t = 0; t < 2; ++t) {           // this wave's two key tiles
           // S and dP, lane (ki, g) register r <-> query 16 qt + 4 g + r of the step
-          const f32x4 st = xb_scores(qh, qm, ql, kh[t], km[t], kl[t], false);
-          const f32x4 dp = xm_x6(gh, gm, gl, vh[t], vm[t], vl[t], f32x4{0.f, 0.f, 0.f, 0.f});
+          const f32x4 st = products6<false>(qp, kp[t]);
+          const f32x4 dp = xm_x6(gp, vp[t], f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float pr = masked[t] ? 0.f : __builtin_amdgcn_exp2f(st[r] - lse2[r]);
@@ -376,19 +334,13 @@ __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_bwd_key_kernel(const C
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         const size_t e = xm_frag(p.H, p.qsteps, b, h, qstep, half, lane);
-        const u32x4 gch = *reinterpret_cast<const u32x4*>(p.dov + e), gcm = *reinterpret_cast<const u32x4*>(p.dov + p.qplane + e),
-                    gcl = *reinterpret_cast<const u32x4*>(p.dov + 2 * p.qplane + e);
-        const u32x4 qch = *reinterpret_cast<const u32x4*>(p.qv + e), qcm = *reinterpret_cast<const u32x4*>(p.qv + p.qplane + e),
-                    qcl = *reinterpret_cast<const u32x4*>(p.qv + 2 * p.qplane + e);
+        const Planes3 gc = load_planes(p.dov, p.qplane, e), qc = load_planes(p.qv, p.qplane, e);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          u32x4 bh, bm, bl;
-          split8x3(pm[t], bh, bm, bl);
           f32x4& dv = half ? dv1[t] : dv0[t];
-          dv = xm_x6(gch, gcm, gcl, bh, bm, bl, dv);
-          split8x3(ds[t], bh, bm, bl);
+          dv = xm_x6(gc, split_planes3(pm[t]), dv);
           f32x4& dk = half ? dk1[t] : dk0[t];
-          dk = xm_x6(qch, qcm, qcl, bh, bm, bl, dk);
+          dk = xm_x6(qc, split_planes3(ds[t]), dk);
         }
       }
     }
@@ -413,7 +365,7 @@ __global__ __launch_bounds__(64 * XM_WAVES, 2) void cross_bwd_key_kernel(const C
     if (key >= p.Lk) continue;
     const int half = i >> 5, kk = i & 31;
     const float s = sh.o[half][kk][which][d] + sh.o[half + 2][kk][which][d];
-    if (which == 0) p.dk[((size_t)key * p.B + b) * p.ld_dk + h * XM_D + d] = s * XB_LN2;
+    if (which == 0) p.dk[((size_t)key * p.B + b) * p.ld_dk + h * XM_D + d] = s * ATTN_LN2;
     else p.dv[((size_t)key * p.B + b) * p.ld_dv + h * XM_D + d] = s;
   }
 }
@@ -461,27 +413,43 @@ extern "C" size_t gd4d_cross_mha_bwd_workspace_bytes(int Lq, int Lk, int B, int 
   return x.pack_bytes + x.dq_bytes;
 }
 
+namespace gd4d {
+
+// Both K | V packs, one launch of up to four groups: K rows always; V columns in `v_pieces` pieces (2: inference, 3: training), V
+// rows and K columns (the backward's) where their planes are given.  grid (steps, groups, B).
+static int cross_pack_kv(const float* k, const float* v, int ldk, int ldv, void* k_planes, void* v_planes, int v_pieces, void* vk_planes,
+                         void* kv_planes, long long plane_stride, int Lk, int B, int H, int D, void* stream) {
+  if (!k || !v || !k_planes || Lk <= 0 || B <= 0 || H <= 0) return GD4D_EINVAL;
+  if (D != XM_D || H != 8 || B > 65535) return GD4D_EUNSUPPORTED;
+  const int rc = xm_check_layout(ldk < ldv ? ldk : ldv, plane_stride, Lk, B, H,
+                                 aligned16(k) && !(ldk % 4) && aligned16(k_planes) && aligned16(v_planes) && aligned16(vk_planes) &&
+                                     aligned16(kv_planes) && (!vk_planes || (aligned16(v) && !(ldv % 4))));
+  if (rc != GD4D_OK) return rc;
+  const int steps = (Lk + 31) / 32;
+  CrossPackParams p{};
+  int n = 0;
+  p.g[n++] = CrossPackGroup{k, static_cast<unsigned short*>(k_planes), ldk, 0, 1.f, 3};
+  if (v_planes) p.g[n++] = CrossPackGroup{v, static_cast<unsigned short*>(v_planes), ldv, 1, 1.f, v_pieces};
+  if (vk_planes) p.g[n++] = CrossPackGroup{v, static_cast<unsigned short*>(vk_planes), ldv, 0, 1.f, 3};
+  if (kv_planes) p.g[n++] = CrossPackGroup{k, static_cast<unsigned short*>(kv_planes), ldk, 1, 1.f, 3};
+  p.plane = plane_stride;
+  p.groups = n; p.L = Lk; p.B = B; p.H = H; p.steps = steps;
+  hipLaunchKernelGGL(cross_pack_kernel, dim3(steps, n, B), dim3(64 * XM_WAVES), 0, static_cast<hipStream_t>(stream), p);
+  return check_launch();
+}
+
+}  // namespace gd4d
+
+extern "C" int gd4d_cross_mha_pack_kv(const float* k, const float* v, int ldk, int ldv, void* k_planes, void* v_planes,
+                                      long long plane_stride, int Lk, int B, int H, int D, void* stream) {
+  if (!v_planes) return GD4D_EINVAL;
+  return gd4d::cross_pack_kv(k, v, ldk, ldv, k_planes, v_planes, 2, nullptr, nullptr, plane_stride, Lk, B, H, D, stream);
+}
+
 extern "C" int gd4d_cross_mha_pack_kv_train(const float* k, const float* v, int ldk, int ldv, void* k_planes, void* v_planes,
                                             void* vk_planes, void* kv_planes, long long plane_stride, int Lk, int B, int H, int D,
                                             void* stream) {
-  using namespace gd4d;
-  if (!k || !v || !k_planes || Lk <= 0 || B <= 0 || H <= 0) return GD4D_EINVAL;
-  if (D != XM_D || H != 8 || B > 65535) return GD4D_EUNSUPPORTED;
-  if (ldk < H * D || ldv < H * D || plane_stride < (long long)gd4d_cross_mha_plane_elems(Lk, B, H) || (plane_stride & 7)) return GD4D_EINVAL;
-  if (!aligned16(k) || (ldk % 4) || !aligned16(k_planes) || !aligned16(v_planes) || !aligned16(vk_planes) || !aligned16(kv_planes) ||
-      (vk_planes && (!aligned16(v) || (ldv % 4))))
-    return GD4D_EALIGN;
-  const int steps = (Lk + 31) / 32;
-  CrossTrainPackParams p{};
-  int n = 0;
-  p.g[n++] = CrossPackGroup{k, static_cast<unsigned short*>(k_planes), ldk, 0, 1.f};
-  if (v_planes) p.g[n++] = CrossPackGroup{v, static_cast<unsigned short*>(v_planes), ldv, 1, 1.f};
-  if (vk_planes) p.g[n++] = CrossPackGroup{v, static_cast<unsigned short*>(vk_planes), ldv, 0, 1.f};
-  if (kv_planes) p.g[n++] = CrossPackGroup{k, static_cast<unsigned short*>(kv_planes), ldk, 1, 1.f};
-  p.plane = plane_stride;
-  p.groups = n; p.L = Lk; p.B = B; p.H = H; p.steps = steps;
-  hipLaunchKernelGGL(cross_bwd_pack_kernel, dim3(steps, n, B), dim3(64 * XM_WAVES), 0, static_cast<hipStream_t>(stream), p);
-  return check_launch();
+  return gd4d::cross_pack_kv(k, v, ldk, ldv, k_planes, v_planes, 3, vk_planes, kv_planes, plane_stride, Lk, B, H, D, stream);
 }
 
 extern "C" int gd4d_cross_mha_bwd(const float* dout, const float* q, const float* out, const float* lse, const void* k_planes,
@@ -493,19 +461,18 @@ extern "C" int gd4d_cross_mha_bwd(const float* dout, const float* q, const float
   using namespace gd4d;
   if (!dout || !q || !out || !lse || !k_planes || !vk_planes || !kv_planes || !dq || !dk || !dv || Lq <= 0 || Lk <= 0 || B <= 0 || H <= 0)
     return GD4D_EINVAL;
-  if (!(drop_p >= 0.f && drop_p < 1.f) || (drop_p > 0.f && !seed)) return GD4D_EINVAL;
-  if (D != XM_D || H != 8) return GD4D_EUNSUPPORTED;
-  if (drop_p > 0.f && (double)B * H * Lq * Lk >= 4294967296.0) return GD4D_EUNSUPPORTED;   // element ids are 32 bits
-  XbPlan x;
-  const int rc = xb_plan(Lq, Lk, B, H, q_tile, splits, &x);
+  int rc = attn_check_drop(drop_p, seed, (double)B * H * Lq * Lk);
   if (rc != GD4D_OK) return rc;
-  const int C = H * D;
-  if (ld_dout < C || ldq < C || ldo < C || ld_dq < C || ld_dk < C || ld_dv < C ||
-      plane_stride < (long long)gd4d_cross_mha_plane_elems(Lk, B, H) || (plane_stride & 7))
-    return GD4D_EINVAL;
-  if (!aligned16(dout) || !aligned16(q) || !aligned16(out) || (ld_dout % 4) || (ldq % 4) || (ldo % 4) || !aligned16(k_planes) ||
-      !aligned16(vk_planes) || !aligned16(kv_planes) || !aligned16(workspace))
-    return GD4D_EALIGN;
+  if (D != XM_D || H != 8) return GD4D_EUNSUPPORTED;
+  XbPlan x;
+  rc = xb_plan(Lq, Lk, B, H, q_tile, splits, &x);
+  if (rc != GD4D_OK) return rc;
+  int min_ld = ld_dout;
+  for (const int ld : {ldq, ldo, ld_dq, ld_dk, ld_dv}) min_ld = ld < min_ld ? ld : min_ld;
+  rc = xm_check_layout(min_ld, plane_stride, Lk, B, H,
+                       aligned16(dout) && aligned16(q) && aligned16(out) && !(ld_dout % 4) && !(ldq % 4) && !(ldo % 4) && aligned16(k_planes) &&
+                           aligned16(vk_planes) && aligned16(kv_planes) && aligned16(workspace));
+  if (rc != GD4D_OK) return rc;
   if (!workspace || workspace_bytes < x.pack_bytes + x.dq_bytes) return GD4D_EWORKSPACE;
 
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -513,17 +480,17 @@ extern "C" int gd4d_cross_mha_bwd(const float* dout, const float* q, const float
   unsigned short* planes = static_cast<unsigned short*>(workspace);
   float* rows = reinterpret_cast<float*>(planes + XB_QPLANES * qplane);
   const size_t nrows = (size_t)B * H * x.qsteps * 32;
-  const float qscale = scale * XB_LOG2E;
+  const float qscale = scale * ATTN_LOG2E;
 
-  CrossTrainPackParams pk{};
-  pk.g[0] = CrossPackGroup{q, planes, ldq, 0, qscale};
-  pk.g[1] = CrossPackGroup{dout, planes + 3 * qplane, ld_dout, 0, 1.f};
-  pk.g[2] = CrossPackGroup{q, planes + 6 * qplane, ldq, 1, qscale};
-  pk.g[3] = CrossPackGroup{dout, planes + 9 * qplane, ld_dout, 1, 1.f};
+  CrossPackParams pk{};
+  pk.g[0] = CrossPackGroup{q, planes, ldq, 0, qscale, 3};
+  pk.g[1] = CrossPackGroup{dout, planes + 3 * qplane, ld_dout, 0, 1.f, 3};
+  pk.g[2] = CrossPackGroup{q, planes + 6 * qplane, ldq, 1, qscale, 3};
+  pk.g[3] = CrossPackGroup{dout, planes + 9 * qplane, ld_dout, 1, 1.f, 3};
   pk.plane = (long long)qplane;
   pk.groups = 4; pk.L = Lq; pk.B = B; pk.H = H; pk.steps = x.qsteps;
   pk.dout = dout; pk.out = out; pk.lse = lse; pk.dsum = rows; pk.lse2 = rows + nrows; pk.ld_dout = ld_dout; pk.ld_out = ldo;
-  hipLaunchKernelGGL(cross_bwd_pack_kernel, dim3(x.qsteps, 5, B), dim3(64 * XM_WAVES), 0, st, pk);
+  hipLaunchKernelGGL(cross_pack_kernel, dim3(x.qsteps, 5, B), dim3(64 * XM_WAVES), 0, st, pk);
 
   CrossBwdParams p{static_cast<const unsigned short*>(k_planes), static_cast<const unsigned short*>(vk_planes),
                    static_cast<const unsigned short*>(kv_planes), plane_stride,

@@ -1,9 +1,8 @@
-// The split-bf16 self-attention core as a device function: gd4d_self_attn.hip launches it as a kernel of its own,
-// gd4d_rowchain.hip as the attention workgroups of a fused [attention | chain A] launch (gd4d_row_chain_mha_fwd).
+// The split-bf16 self-attention core as a device function: gd4d_self_attn.hip launches it as two kernels, on fp32 K / V rows
+// (mha_core_bf16x3_kernel) and on planes the in-projection wrote (mha_core_presplit_kernel).
 // Reference: see gd4d_self_attn.hip.
 #pragma once
-#include "gd4d_common.h"
-#include "gd4d_bf16x3.h"
+#include "gd4d_attn_pieces.h"
 #include "gd4d_mha_dropout.h"
 
 namespace gd4d {
@@ -24,52 +23,74 @@ struct MhaParams {
   long long ks_plane, vs_plane;   // elements per plane
 };
 
-constexpr int MHA_D = 32;
-#ifndef MHA_WAVES_N
-#define MHA_WAVES_N 8
-#endif
-constexpr int MHA_WAVES = MHA_WAVES_N;
-#ifndef MHA_PF_N
-#define MHA_PF_N 1
-#endif
-constexpr int MHA_PF = MHA_PF_N;       // tiles of keys a wave requests ahead (one chunk)
+constexpr int MHA_D = ATTN_D;
+constexpr int MHA_WAVES = 8;
 
-// ---------------------------------------------------------------------------------------------------------------
-// Inference form (no dropout, no saved log-sum-exp): both products on v_mfma_f32_16x16x32_bf16 with split operands
-// (x = hi + lo, a b ~= a_hi b_hi + a_lo b_hi + a_hi b_lo, fp32 accumulation: ~2^-16 relative per product - the arithmetic of
-// the row chains' GEMMs that feed and drain this kernel).  After the base-2 softmax the fp32 kernel above was bound by its
-// matrix pipe: 416 k v_mfma_f32_16x16x4_f32 of 32 cycles = 5.4 us of the 11.7; the same contractions are 12 bf16 MFMAs of
-// 16 cycles per 32 keys here (1.0 us).  Training keeps the fp32 kernel (its backward recomputes the probabilities in fp32).
-//
-// A wave takes 32 keys per step: two score tiles S^T = K Q^T (MFMA rows = keys kbase + 16 t + rho, columns = queries).  The
-// C/D layout leaves lane (query qi, g) the scores of keys kbase + 16 t + 4 g + r; numbering the k index of the second product
-// O^T = V^T P^T as 8 g + j <-> (t = j >> 2, r = j & 3) makes those eight probabilities exactly the lane's B operand: they
-// never move between lanes (the trick of the fp32 kernel, for the 32-deep instruction).
-
-// LDS of one workgroup (the kernel's own static arrays, or a piece of the fused launch's dynamic allocation)
+// The end of both self-attention kernels: the waves split the keys eight ways (flash-decoding style) and merge through LDS,
+// o as [wave][d][17].  The formula is combine_key_slices' without its guard - a row whose every key is masked comes out NaN in
+// `out` and `lse`, as ATen (tests/test_dense_gpu.py pins it) - but written out here, as is the softmax update in the body below:
+// on publish_key_slice / merge_key_slices and softmax_step the pre-split kernel, the one on the decoder's timed path, was 0.06 us
+// per call (0.7 %) slower than before, 0.02 us with the merge alone handed back, none with both (docs/measurements_r41.md,
+// section 3).  The cross-attention core and the fp32 kernel's softmax use the shared pieces.
 struct MhaShared {
   float m[MHA_WAVES][16];
   float l[MHA_WAVES][16];
   float o[MHA_WAVES][MHA_D][17];
 };
+__device__ __forceinline__ void mha_merge_and_store(const MhaParams& p, MhaShared& sh, const int q0, const int h, const int b,
+                                                    const float m, float l, const f32x4& o0, const f32x4& o1) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, qi = lane & 15, g = lane >> 4;
+  l += __shfl_xor(l, 16);
+  l += __shfl_xor(l, 32);
+  if (g == 0) { sh.m[wave][qi] = m; sh.l[wave][qi] = l; }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    sh.o[wave][4 * g + r][qi] = o0[r];
+    sh.o[wave][16 + 4 * g + r][qi] = o1[r];
+  }
+  __syncthreads();
+  for (int e = tid; e < 16 * MHA_D; e += 64 * MHA_WAVES) {
+    const int i = e / MHA_D, d = e % MHA_D;
+    if (q0 + i >= p.Lq) continue;
+    float mm = sh.m[0][i];
+#pragma unroll
+    for (int w = 1; w < MHA_WAVES; ++w) mm = fmaxf(mm, sh.m[w][i]);
+    float num = 0.f, den = 0.f;
+#pragma unroll
+    for (int w = 0; w < MHA_WAVES; ++w) {
+      const float f = __builtin_amdgcn_exp2f(sh.m[w][i] - mm);
+      num += sh.o[w][d][i] * f;
+      den += sh.l[w][i] * f;
+    }
+    p.out[((size_t)(q0 + i) * p.B + b) * p.ldo + h * MHA_D + d] = num / den;
+    if (p.lse && d == 0) p.lse[((size_t)(q0 + i) * p.B + b) * p.H + h] = mm * ATTN_LN2 + logf(den);
+  }
+}
 
+// ---------------------------------------------------------------------------------------------------------------
+// Both products on v_mfma_f32_16x16x32_bf16 with split operands (x = hi + lo, a b ~= a_hi b_hi + a_lo b_hi + a_hi b_lo, fp32
+// accumulation: ~2^-16 relative per product - the arithmetic of the row chains' GEMMs that feed and drain this kernel).  After
+// the base-2 softmax the fp32 kernel of gd4d_self_attn.hip was bound by its matrix pipe: 416 k v_mfma_f32_16x16x4_f32 of 32
+// cycles = 5.4 us of the 11.7; the same contractions are 12 bf16 MFMAs of 16 cycles per 32 keys here (1.0 us).  Inference and
+// training without dropout run this form (it writes the log-sum-exp when asked); with PRE it carries DROP as well.
+//
+// A wave takes 32 keys per step: two score tiles S^T = K Q^T (MFMA rows = keys kbase + 16 t + rho, columns = queries).  The
+// C/D layout leaves lane (query qi, g) the scores of keys kbase + 16 t + 4 g + r; numbering the k index of the second product
+// O^T = V^T P^T as 8 g + j <-> (t = j >> 2, r = j & 3) makes those eight probabilities exactly the lane's B operand: they
+// never move between lanes (the trick of the fp32 kernel, for the 32-deep instruction).
+//
 // One workgroup (8 waves) = one (16-query tile qblock, head h, batch b); the stores of `out` are the last thing it issues.
 // DROP (training, modules in train mode): the probabilities are dropped as in the fp32 kernel of gd4d_self_attn.hip - same element
 // ids, same hash, the normaliser and the saved log-sum-exp those of the full softmax.
-template <int MASK, int AHEAD = 1, bool PRE = false, bool DROP = false>
+template <int MASK, bool PRE = false, bool DROP = false>
 __device__ __forceinline__ void mha_core_bf16x3_body(const MhaParams& p, const int qblock, const int h, const int b, MhaShared& sh) {
-  float (&s_m)[MHA_WAVES][16] = sh.m;
-  float (&s_l)[MHA_WAVES][16] = sh.l;
-  float (&s_o)[MHA_WAVES][MHA_D][17] = sh.o;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
   const int qi = lane & 15;            // query column of this lane (score / output tiles); key row rho of a K tile; channel of a V^T tile
   const int g = lane >> 4;             // lane group
   const int q0 = qblock * 16;
   const float NEG_INF = -__builtin_inff();
-  constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-  const float qscale = p.scale * LOG2E;                       // base-2 softmax, as above
+  const float qscale = p.scale * ATTN_LOG2E;                  // base-2 softmax (softmax_step)
 
   u32x4 qh, ql;                                              // Q^T as B operand: lane (query qi, g) holds q[qi][8 g .. 8 g + 7]
   {
@@ -89,14 +110,11 @@ __device__ __forceinline__ void mha_core_bf16x3_body(const MhaParams& p, const i
   const int nsteps = (p.Lk + 31) / 32;
   const size_t hoff = (size_t)h * MHA_D;
   const size_t mask_row = (size_t)min(q0 + qi, p.Lq - 1) * p.Lk;
-  // One step of look-ahead (MHA_LOOKAHEAD, default on): q / k / v arrive cold from other XCDs (~2 us per round trip) and a wave
-  // has only ~4 steps, so "request, wait, compute" per step was a chain of four exposed round trips; the next step's rows are
-  // requested before this step's are consumed.
   // PRE: K and V arrive as the MFMA operands themselves (bf16 hi / lo planes): 8 loads of 16 / 8 bytes per step instead of 4
   // float4 + 16 dwords, and none of the 112 conversion instructions per step (two thirds of the kernel's splits)
   struct StepData { float4 ka[2], kc[2]; float v0[8], v1[8], mk[8]; u32x4 pkh[2], pkl[2], pvh[2], pvl[2]; };
-  auto fetch = [&](int kt, StepData& d) {
-    const int kbase = min(kt, nsteps - 1) * 32;
+  auto fetch = [&](const int kt, StepData& d) {
+    const int kbase = min(kt, nsteps - 1) * 32;              // (kt < nsteps here; the clamp is part of the measured form)
     if (PRE) {
       const int tiles = (p.Lk + 15) / 16;
 #pragma unroll
@@ -142,21 +160,13 @@ __device__ __forceinline__ void mha_core_bf16x3_body(const MhaParams& p, const i
       }
     }
   };
-#ifndef MHA_LOOKAHEAD
-#define MHA_LOOKAHEAD 1
-#endif
   auto step = [&](const int kt, const StepData& d) {
     const int kbase = kt * 32;
-    const float4 (&ka)[2] = d.ka;
-    const float4 (&kc)[2] = d.kc;
-    const float (&v0)[8] = d.v0;
-    const float (&v1)[8] = d.v1;
-    const float (&mk)[8] = d.mk;
     // ---- S^T = K Q^T, two tiles of 16 keys ----
-    float sc[8];
+    float pr[8];                                               // the scores, then their probabilities
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      const float kf[8] = {ka[t].x, ka[t].y, ka[t].z, ka[t].w, kc[t].x, kc[t].y, kc[t].z, kc[t].w};
+      const float kf[8] = {d.ka[t].x, d.ka[t].y, d.ka[t].z, d.ka[t].w, d.kc[t].x, d.kc[t].y, d.kc[t].z, d.kc[t].w};
       u32x4 kh, kl;
       if (PRE) { kh = d.pkh[t]; kl = d.pkl[t]; }
       else split8(kf, kh, kl);
@@ -168,22 +178,22 @@ __device__ __forceinline__ void mha_core_bf16x3_body(const MhaParams& p, const i
         if (key >= p.Lk) {
           val = NEG_INF;
         } else if (MASK == 1) {
-          if (mk[4 * t + r] != 0.f) val = NEG_INF;
+          if (d.mk[4 * t + r] != 0.f) val = NEG_INF;
         } else if (MASK == 2) {
-          val += mk[4 * t + r] * LOG2E;
+          val += d.mk[4 * t + r] * ATTN_LOG2E;
         }
-        sc[4 * t + r] = val;
+        pr[4 * t + r] = val;
       }
     }
-    float tmax = fmaxf(fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3])), fmaxf(fmaxf(sc[4], sc[5]), fmaxf(sc[6], sc[7])));
+    // softmax_step<8> written out (see mha_merge_and_store): the same operations in the same order
+    float tmax = fmaxf(fmaxf(fmaxf(pr[0], pr[1]), fmaxf(pr[2], pr[3])), fmaxf(fmaxf(pr[4], pr[5]), fmaxf(pr[6], pr[7])));
     tmax = fmaxf(tmax, __shfl_xor(tmax, 16));
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
     const float m_new = fmaxf(m, tmax);
-    const float m_use = (m_new == NEG_INF) ? 0.f : m_new;      // all keys so far masked: zero weights, no NaN here
-    const float corr = __builtin_amdgcn_exp2f(m - m_use);      // m = -inf -> 0
-    float pr[8];
+    const float m_use = (m_new == NEG_INF) ? 0.f : m_new;
+    const float corr = __builtin_amdgcn_exp2f(m - m_use);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) pr[j] = __builtin_amdgcn_exp2f(sc[j] - m_use);
+    for (int j = 0; j < 8; ++j) pr[j] = __builtin_amdgcn_exp2f(pr[j] - m_use);
     l = l * corr + (((pr[0] + pr[1]) + (pr[2] + pr[3])) + ((pr[4] + pr[5]) + (pr[6] + pr[7])));
     m = m_new;
     if (DROP) {
@@ -198,63 +208,14 @@ __device__ __forceinline__ void mha_core_bf16x3_body(const MhaParams& p, const i
     u32x4 ph, pl, vh, vl;
     split8(pr, ph, pl);
     if (PRE) { vh = d.pvh[0]; vl = d.pvl[0]; }
-    else split8(v0, vh, vl);
+    else split8(d.v0, vh, vl);
     o0 = mfma_16x16x32_x3(vh, vl, ph, pl, o0);
     if (PRE) { vh = d.pvh[1]; vl = d.pvl[1]; }
-    else split8(v1, vh, vl);
+    else split8(d.v1, vh, vl);
     o1 = mfma_16x16x32_x3(vh, vl, ph, pl, o1);
   };
-  if (AHEAD > 1) {
-    // the fused launch's form (gd4d_row_chain_mha_fwd): ONE workgroup per compute unit there, nobody else's work hides a round
-    // trip - with one step of look-ahead a wave waited ~1.5 us per step for rows (9.1 us per workgroup for 4.5 us of issue).
-    // All rows of AHEAD steps are requested before the first is consumed.
-    StepData d[AHEAD];
-    for (int base = wave; base < nsteps; base += MHA_WAVES * AHEAD) {
-#pragma unroll
-      for (int i = 0; i < AHEAD; ++i) fetch(base + MHA_WAVES * i, d[i]);        // (clamped: past the end = the last step again)
-#pragma unroll
-      for (int i = 0; i < AHEAD; ++i)
-        if (base + MHA_WAVES * i < nsteps) step(base + MHA_WAVES * i, d[i]);
-    }
-  } else {
-    StepData cur, nxt;
-    if (wave < nsteps) fetch(wave, cur);
-    for (int kt = wave; kt < nsteps; kt += MHA_WAVES) {
-      if (MHA_LOOKAHEAD) {
-        if (kt + MHA_WAVES < nsteps) fetch(kt + MHA_WAVES, nxt);
-      } else if (kt != wave) {
-        fetch(kt, cur);
-      }
-      step(kt, cur);
-      if (MHA_LOOKAHEAD) cur = nxt;
-    }
-  }
-  // ---- merge the key-slices (as the fp32 kernel) ----
-  l += __shfl_xor(l, 16);
-  l += __shfl_xor(l, 32);
-  if (g == 0) { s_m[wave][qi] = m; s_l[wave][qi] = l; }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    s_o[wave][4 * g + r][qi] = o0[r];
-    s_o[wave][16 + 4 * g + r][qi] = o1[r];
-  }
-  __syncthreads();
-  for (int e = tid; e < 16 * MHA_D; e += 64 * MHA_WAVES) {
-    const int i = e / MHA_D, d = e % MHA_D;
-    if (q0 + i >= p.Lq) continue;
-    float mm = s_m[0][i];
-#pragma unroll
-    for (int w = 1; w < MHA_WAVES; ++w) mm = fmaxf(mm, s_m[w][i]);
-    float num = 0.f, den = 0.f;
-#pragma unroll
-    for (int w = 0; w < MHA_WAVES; ++w) {
-      const float f = __builtin_amdgcn_exp2f(s_m[w][i] - mm);  // fully masked row: -inf - -inf = NaN, as ATen
-      num += s_o[w][d][i] * f;
-      den += s_l[w][i] * f;
-    }
-    p.out[((size_t)(q0 + i) * p.B + b) * p.ldo + h * MHA_D + d] = num / den;
-    if (p.lse && d == 0) p.lse[((size_t)(q0 + i) * p.B + b) * p.H + h] = mm * LN2 + logf(den);   // a training step's forward: for gd4d_mha_core_bwd
-  }
+  walk_steps<MHA_WAVES, StepData>(0, nsteps, wave, fetch, step);      // (a wave has only ~4 steps at 900 keys)
+  mha_merge_and_store(p, sh, q0, h, b, m, l, o0, o1);
 }
 
 }  // namespace gd4d

@@ -108,6 +108,34 @@ def test_mha_core_matches_fp64(l, b, mask):
     assert (lse.cpu().double() - sc.logsumexp(-1).view(b, h, l).permute(2, 0, 1)).abs().max().item() < 1e-4
 
 
+def test_mha_core_fully_masked_row_is_nan_and_leaves_the_others_alone():
+    """A query row whose every key is masked: the merge of the waves' key slices forms exp2(-inf - -inf), so the row's `out` and
+    its lse are NaN (as ATen's softmax of a row of -inf) in both kernels - the split-bf16 one (drop_p = 0) and the fp32 one
+    (drop_p > 0) - and no other row is touched by it."""
+    from graph_detr4d_amd import ops
+    torch.manual_seed(48)
+    l, b, h, d, dead = 48, 1, 8, 32, 17
+    qkv = torch.randn(l, b, 3 * h * d)
+    am = torch.rand(l, l) < 0.3
+    am[dead] = True
+    assert not am[torch.arange(l) != dead].all(dim=1).any()            # the only fully masked row
+    qv, kv, vv = qkv.cuda().split(h * d, dim=-1)
+    q, k, v = (t.reshape(l, b * h, d).transpose(0, 1).double() for t in qkv.split(h * d, dim=-1))
+    sc = torch.bmm(q / math.sqrt(d), k.transpose(1, 2)).masked_fill(am, float('-inf'))
+    ref = torch.bmm(sc.softmax(-1), v).transpose(0, 1).reshape(l, b, h * d)
+    ref_lse = sc.logsumexp(-1).view(b, h, l).permute(2, 0, 1)
+    live = torch.arange(l) != dead
+    for p in (0., 0.1):
+        seed = ops.mha_dropout_seed('cuda') if p else None
+        out, lse = ops.mha_core_fwd(qv, kv, vv, h, am.cuda(), want_lse=True, dropout_p=p, seed=seed)
+        out, lse = out.cpu(), lse.cpu()
+        assert out[dead].isnan().all() and lse[dead].isnan().all(), p
+        assert out[live].isfinite().all() and lse[live].isfinite().all(), p
+        if p == 0.:                                                    # the bounds of test_mha_core_matches_fp64 with the lse asked for
+            assert (out[live].double() - ref[live]).abs().max().item() < 2e-5
+            assert (lse[live].double() - ref_lse[live]).abs().max().item() < 1e-4
+
+
 def test_linear_inverse_sigmoid_input():
     """position_encoder input transform: Linear(inverse_sigmoid(ref)), K = 3 and 4."""
     from graph_detr4d_amd import ops
