@@ -85,6 +85,13 @@ def _asked(res, *optional, bare=True):
     return res[0] if bare and len(res) == 1 else res
 
 
+def _mask_uv(want_mask, want_uv, mask_out, uv_out, shape, device):
+    """The optional mask (shape, uint8) and uv (shape + (2,)) of the cross-attention front ends: new, the caller's, or None."""
+    mask = _out(mask_out, shape, device, 'mask_out', U8) if want_mask or mask_out is not None else None
+    uv = _out(uv_out, tuple(shape) + (2,), device, 'uv_out') if want_uv or uv_out is not None else None
+    return mask, uv
+
+
 def _value_dtype(t):
     if t.dtype == F32:
         return _lib.F32
@@ -95,11 +102,12 @@ def _value_dtype(t):
 
 def cross_attn_fwd(value, level_hw, ref, offsets, attn_logits, cam_logits, lidar2img, pc_range,
                    img_h, img_w, want_mask=False, want_uv=False, out=None, head_major=False, query_order=None,
-                   raw_cam_weights=False):
+                   raw_cam_weights=False, mask_out=None, uv_out=None):
     """gd4d_cross_attn_fwd.  value (B*N, S, Hh, Dh), or (B*N, Hh, S, Dh) with head_major=True;
     ref (B,Q,3); offsets (B,Q,Hh,P,3);
     attn_logits (B,Q,Hh,L,P) (or (B,Q,Hh,L*P)); cam_logits (B,Q,N); lidar2img (B,N,4,4).
     query_order: optional int32 permutation of [0, B*Q) from query_order_fwd (scheduling only, same result).
+    out / mask_out / uv_out: the tensors to write (mask_out / uv_out: asked for by being given).
     Returns out (B,Q,Hh*Dh) [, mask (B,N,Q,Hh,P) uint8] [, uv (B,N,Q,Hh,P,2)]."""
     b, q = ref.shape[0], ref.shape[1]
     n = lidar2img.shape[1]
@@ -111,10 +119,8 @@ def cross_attn_fwd(value, level_hw, ref, offsets, attn_logits, cam_logits, lidar
                          f'levels {level_hw}')
     if attn_logits.numel() != b * q * hh * nl * p or cam_logits.numel() != b * q * n:
         raise ValueError('attn_logits / cam_logits have the wrong number of elements')
-    if out is None:
-        out = torch.empty(b, q, hh * dh, device=ref.device, dtype=F32)
-    mask = torch.empty(b, n, q, hh, p, device=ref.device, dtype=U8) if want_mask else None
-    uv = torch.empty(b, n, q, hh, p, 2, device=ref.device, dtype=F32) if want_uv else None
+    out = _out(out, (b, q, hh * dh), ref.device, 'out')
+    mask, uv = _mask_uv(want_mask, want_uv, mask_out, uv_out, (b, n, q, hh, p), ref.device)
     _call('gd4d_cross_attn_fwd', _dev(value, 'value'), _levels(level_hw),
           *_camera_args(ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w), _dev(out, 'out', F32),
           _opt(mask, 'mask', None), _opt(uv, 'uv', None), b, n, q, hh, dh, nl, p, _value_dtype(value),
@@ -143,10 +149,11 @@ def pyramid_channels_last_fwd(feats, out=None, max_cus=0, out_dtype=torch.float3
 
 def cross_attn_agg_fwd(feats_cl, level_hw, ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w,
                        num_heads, want_mask=False, want_uv=False, query_order=None, raw_cam_weights=False,
-                       vp_weight=None, vp_bias=None):
+                       vp_weight=None, vp_bias=None, outs=None, mask_out=None, uv_out=None):
     """gd4d_cross_attn_agg_fwd.  feats_cl (B*N, S, 256) fp32 channels-last pyramid; the other arguments as cross_attn_fwd.
     Returns agg (B, Q, Hh, 256), wsum (B, Q, Hh) [, mask] [, uv]; with vp_weight (256, 256) [, vp_bias]: value_proj of the
-    aggregates applied in the kernel's epilogue - returns out (B, Q, 256) [, mask] [, uv] instead."""
+    aggregates applied in the kernel's epilogue - returns out (B, Q, 256) [, mask] [, uv] instead.
+    outs: the tensors to write, (agg, wsum) - or (out,) with vp_weight; mask_out / uv_out as cross_attn_fwd."""
     b, q = ref.shape[0], ref.shape[1]
     n = lidar2img.shape[1]
     hh, p = num_heads, offsets.shape[3]
@@ -157,11 +164,13 @@ def cross_attn_agg_fwd(feats_cl, level_hw, ref, offsets, attn_logits, cam_logits
     if offsets.numel() != b * q * hh * p * 3 or attn_logits.numel() != b * q * hh * nl * p or cam_logits.numel() != b * q * n:
         raise ValueError('offsets / attn_logits / cam_logits have the wrong number of elements')
     fused = vp_weight is not None
-    agg = None if fused else torch.empty(b, q, hh, c, device=ref.device, dtype=F32)
-    wsum = None if fused else torch.empty(b, q, hh, device=ref.device, dtype=F32)
-    out = torch.empty(b, q, c, device=ref.device, dtype=F32) if fused else None
-    mask = torch.empty(b, n, q, hh, p, device=ref.device, dtype=U8) if want_mask else None
-    uv = torch.empty(b, n, q, hh, p, 2, device=ref.device, dtype=F32) if want_uv else None
+    if outs is not None and len(outs) != (1 if fused else 2):
+        raise ValueError('outs must be (agg, wsum), or (out,) with vp_weight')
+    given = (None, None) if outs is None else tuple(outs)
+    agg = None if fused else _out(given[0], (b, q, hh, c), ref.device, 'outs[0]')
+    wsum = None if fused else _out(given[1], (b, q, hh), ref.device, 'outs[1]')
+    out = _out(given[0], (b, q, c), ref.device, 'outs[0]') if fused else None
+    mask, uv = _mask_uv(want_mask, want_uv, mask_out, uv_out, (b, n, q, hh, p), ref.device)
     _call('gd4d_cross_attn_agg_fwd', _dev(feats_cl, 'feats_cl'), _levels(level_hw),
           *_camera_args(ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w), _opt(agg, 'agg', None),
           _opt(wsum, 'wsum', None), _opt(mask, 'mask', None), _opt(uv, 'uv', None), b, n, q, hh, c, nl, p, _value_dtype(feats_cl),
@@ -287,12 +296,12 @@ CA_RAW_CAM_WEIGHTS, CA_PLAN_ITEMS, CA_PLAN_BOTH = 1, 2, 16
 
 def cross_attn_plan_fwd(pyramid, ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w, num_heads,
                         want_mask=False, want_uv=False, raw_cam_weights=False, plan=None, query_order=None, items=False,
-                        both=False):
+                        both=False, mask_out=None, uv_out=None):
     """gd4d_cross_attn_plan_fwd: projection + mask + softmax + camera weights + bilinear corners of one decoder layer's
     cross-attention -> what gd4d_cross_attn_agg_sliced_fwd walks on `pyramid` (a PyramidView).  The other arguments as
     cross_attn_fwd; plan: a Plan to overwrite; items: the 32-bytes-per-item form (the corners are worked out by the gather,
     which then also fills wsum).  both: pairs AND items in one launch (a training step: the forward gather reads the items, the
-    backward kernels the pairs).
+    backward kernels the pairs).  mask_out / uv_out as cross_attn_fwd.
     Returns Plan [, mask (B, N, Q, Hh, P) uint8] [, uv (B, N, Q, Hh, P, 2)]."""
     b, q = ref.shape[0], ref.shape[1]
     n = lidar2img.shape[1]
@@ -307,8 +316,7 @@ def cross_attn_plan_fwd(pyramid, ref, offsets, attn_logits, cam_logits, lidar2im
     buf = torch.empty(2 * nbytes if both else nbytes, device=ref.device, dtype=U8) if plan is None else plan.buf
     wsum = torch.empty(b, q, hh, device=ref.device, dtype=F32) if plan is None else plan.wsum
     plan = Plan(buf, query_order, pyramid, b, q, hh, wsum, items=items, points=p, items_buf=buf[nbytes:] if both else None)
-    mask = torch.empty(b, n, q, hh, p, device=ref.device, dtype=U8) if want_mask else None
-    uv = torch.empty(b, n, q, hh, p, 2, device=ref.device, dtype=F32) if want_uv else None
+    mask, uv = _mask_uv(want_mask, want_uv, mask_out, uv_out, (b, n, q, hh, p), ref.device)
     cs = (ctypes.c_int64 * nl)(*pyramid.cam_stride)
     _call('gd4d_cross_attn_plan_fwd', *_camera_args(ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w),
           _levels(pyramid.level_hw), cs, pyramid.pix_stride, _dev(buf, 'plan', U8), buf.numel(), _dev(wsum, 'wsum', F32),
@@ -526,8 +534,9 @@ def wgrads_ride_with(plan):
 
 
 def cross_attn_plan_bwd(plan, dpart, beta, ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w,
-                        raw_cam_weights=False, status=None):
+                        raw_cam_weights=False, status=None, outs=None, workspace=None):
     """gd4d_cross_attn_plan_bwd: the query-side gradients of the sliced path from D (cross_attn_dot_sliced) and beta.
+    outs: the four tensors to write; workspace: a uint8 buffer of gd4d_cross_attn_bwd_workspace_bytes (0 bytes with B = 1: none).
     Returns (grad_ref, grad_offsets, grad_attn_logits, grad_cam_logits) - what cross_attn_bwd returns after grad_value."""
     lib = _lib.load()
     plan.need_pairs('gd4d_cross_attn_plan_bwd')
@@ -537,18 +546,23 @@ def cross_attn_plan_bwd(plan, dpart, beta, ref, offsets, attn_logits, cam_logits
     level_hw = plan.pyramid.level_hw
     nl = len(level_hw)
     dev = ref.device
-    gr = torch.empty(b, q, 3, device=dev, dtype=F32)
-    go = torch.empty(b, q, hh, p, 3, device=dev, dtype=F32)
-    ga = torch.empty(b, q, hh, nl, p, device=dev, dtype=F32)
-    gc = torch.empty(b, q, n, device=dev, dtype=F32)
+    gr, go, ga, gc = _query_grads(outs, 0, (b, q, 3), (b, q, hh, p, 3), (b, q, hh, nl, p), (b, q, n), dev)
     nbytes = lib.gd4d_cross_attn_bwd_workspace_bytes(b, q, hh, nl, p)
-    ws = torch.empty(nbytes, device=dev, dtype=U8) if nbytes else None
+    ws = _out(workspace, (nbytes,), dev, 'workspace', U8) if nbytes else None
     _call('gd4d_cross_attn_plan_bwd', *_camera_args(ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w),
           _levels(level_hw), _dev(plan.buf, 'plan', U8), _dev(dpart, 'dpart', U8), _opt(beta, 'beta'), _dev(gr, 'grad_ref'),
           _dev(go, 'grad_offsets'), _dev(ga, 'grad_attn_logits'), _dev(gc, 'grad_cam_logits'), _opt(ws, 'workspace', None),
           ctypes.c_size_t(nbytes), _opt(status, 'status', I32), b, n, q, hh, nl, p, 1 if raw_cam_weights else 0,
           _order_ptr(plan.order, b * q))
     return gr, go, ga, gc
+
+
+def _query_grads(outs, first, *shapes_dev):
+    """grad_ref, grad_offsets, grad_attn_logits, grad_cam_logits of the two cross-attention backwards: new, or outs[first:]."""
+    *shapes, dev = shapes_dev
+    if outs is not None and len(outs) != first + 4:
+        raise ValueError(f'outs must hold {first + 4} tensors')
+    return tuple(_out(None if outs is None else outs[first + i], s, dev, f'outs[{first + i}]') for i, s in enumerate(shapes))
 
 
 _CHUNK_WALKS = {}
@@ -593,10 +607,17 @@ class PyramidGrad:
     _reduce): add_layer() per layer (in any order, each with its plan and its grad_agg rows), finish() once.
 
     Buffers are sized for `layers` layers of B*Q*Hh rows (alloc_table with a list: per-layer Q); the slot / record buffers by
-    the plans' capacity (8 bytes per pair a plan can hold - only what the counts say is touched)."""
+    the plans' capacity (8 bytes per pair a plan can hold - only what the counts say is touched).
+    alloc(what, shape, dtype, zero): every buffer this object owns comes from it (what: 'count', 'table', 'slots', 'start',
+    'scan_workspace', 'records', 'sorted', 'pxoff'; zero: the buffer must hold zeros); default: torch.zeros / torch.empty on the
+    pyramid's device."""
 
-    def __init__(self, pyramid, layers, b, q, num_heads, chunk_walk=True, points=4):
+    def _alloc(self, what, shape, dtype, zero):
+        return (torch.zeros if zero else torch.empty)(shape, device=self.pyramid.device, dtype=dtype)
+
+    def __init__(self, pyramid, layers, b, q, num_heads, chunk_walk=True, points=4, alloc=None):
         self.pyramid, self.layers, self.b, self.q, self.hh = pyramid, int(layers), int(b), int(q), int(num_heads)
+        self.alloc = self._alloc if alloc is None else alloc
         self.points = int(points)                 # points per head of the plans this sink takes (4, or 8 with 8 heads)
         dev = pyramid.device
         lib = _lib.load()
@@ -607,7 +628,7 @@ class PyramidGrad:
         self.chunks = int(lib.gd4d_pyramid_grad_chunks(self._lv, pyramid.rows, nl))
         if self.chunks <= 0:
             raise _lib.Gd4dError('gd4d_pyramid_grad_chunks: unsupported pyramid')
-        self.count = torch.zeros(self.chunks, device=dev, dtype=I32)
+        self.count = self.alloc('count', (self.chunks,), I32, True)
         self._scanned, self._riding = None, []
         self.table, self.layer_q = None, {}
         if self.layers > 0:
@@ -631,7 +652,7 @@ class PyramidGrad:
             self.row_base.append(self.row_base[-1] + self.b * q * self.hh)
         if self.row_base[-1] >= 1 << 26:
             raise _lib.Gd4dError('PyramidGrad: more than 2^26 table rows (a record keeps its row in 26 bits)')
-        self.table = torch.zeros(max(self.row_base[-1], 1), 256, device=self.pyramid.device, dtype=F32)
+        self.table = self.alloc('table', (max(self.row_base[-1], 1), 256), F32, True)
 
     def grad_agg_rows(self, layer):
         """(B, Q_layer, Hh, 256) view of the table: where layer `layer`'s gd4d_value_proj_heads_bwd writes."""
@@ -664,7 +685,7 @@ class PyramidGrad:
         if plan.points != self.points:
             raise _lib.Gd4dError(f'PyramidGrad: a plan with {plan.points} points per head handed to a sink made for {self.points}')
         slot_bytes = int(lib.gd4d_pyramid_grad_slots_bytes(self.b, self.n, plan.q, self.hh, plan.points))
-        slots = torch.empty(slot_bytes, device=self.pyramid.device, dtype=U8)
+        slots = self.alloc('slots', (slot_bytes,), U8, False)
         return slots, slot_bytes
 
     def prepare(self):
@@ -679,15 +700,15 @@ class PyramidGrad:
         mha_core_bwd(fills=...)); finish_prepare() launches whatever is left of them, and the sort."""
         lib = _lib.load()
         dev = self.pyramid.device
-        start = torch.empty(self.chunks, device=dev, dtype=I32)
+        start = self.alloc('start', (self.chunks,), I32, False)
         wsb = int(lib.gd4d_pyramid_grad_scan_workspace_bytes(self.chunks))
-        ws = torch.empty(wsb, device=dev, dtype=U8)
+        ws = self.alloc('scan_workspace', (wsb,), U8, False)
         _call('gd4d_pyramid_grad_scan', _dev(self.count, 'count', I32), _dev(start, 'start', I32), _dev(ws, 'workspace'),
               ctypes.c_size_t(wsb), self.chunks)
         if self.table is None:
             raise _lib.Gd4dError('PyramidGrad.prepare: alloc_table() first (the records carry table rows)')
         nbytes = max(sum(slots.numel() for _, _, slots in self.plans), self.slot_bytes)
-        self._scanned = (start, torch.empty(nbytes, device=dev, dtype=U8), nbytes)
+        self._scanned = (start, self.alloc('records', (nbytes,), U8, False), nbytes)
         for layer, plan, slots in self.plans:
             if layer >= self.layers or self.table_q[layer] != plan.q:
                 raise _lib.Gd4dError(f'PyramidGrad: layer {layer} ({plan.q} queries) does not match the table')
@@ -711,8 +732,8 @@ class PyramidGrad:
             _call('gd4d_pyramid_grad_fill', _dev(plan.buf, 'plan', U8), _dev(slots, 'slots'), _dev(start, 'start', I32),
                   _dev(records, 'records'), self.row_base[layer], _order_ptr(plan.order, self.b * plan.q), self.b, self.n, plan.q, self.hh,
                   plan.points)
-        sorted_ = torch.empty(nbytes, device=dev, dtype=U8)
-        pxoff = torch.empty(self.chunks, 65, device=dev, dtype=I32)
+        sorted_ = self.alloc('sorted', (nbytes,), U8, False)
+        pxoff = self.alloc('pxoff', (self.chunks, 65), I32, False)
         _call('gd4d_pyramid_grad_sort', _dev(self.count, 'count', I32), _dev(start, 'start', I32), _dev(records, 'records'),
               _dev(sorted_, 'sorted'), _dev(pxoff, 'pxoff', I32), self.chunks)
         self.prepared = (start, pxoff, sorted_)
@@ -1519,21 +1540,20 @@ def refine_reference_order_fwd(tmp, ref, pc_range):
 
 
 def cross_attn_bwd(value, level_hw, ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w,
-                   grad_out, query_order=None, raw_cam_weights=False):
-    """gd4d_cross_attn_bwd.  Returns (grad_value, grad_ref, grad_offsets, grad_attn_logits, grad_cam_logits)."""
+                   grad_out, query_order=None, raw_cam_weights=False, outs=None, workspace=None):
+    """gd4d_cross_attn_bwd.  Returns (grad_value, grad_ref, grad_offsets, grad_attn_logits, grad_cam_logits).
+    outs: the five tensors to write - grad_value is ADDED into and must hold zeros; workspace: a uint8 buffer of
+    gd4d_cross_attn_bwd_workspace_bytes (0 bytes with B = 1: none)."""
     lib = _lib.load()
     b, q = ref.shape[0], ref.shape[1]
     n = lidar2img.shape[1]
     hh, dh = value.shape[2], value.shape[3]
     p = offsets.shape[3]
     nl = len(level_hw)
-    gv = torch.zeros_like(value, dtype=F32)
-    gr = torch.empty_like(ref)
-    go = torch.empty(b, q, hh, p, 3, device=ref.device, dtype=F32)
-    ga = torch.empty(b, q, hh, nl, p, device=ref.device, dtype=F32)
-    gc = torch.empty(b, q, n, device=ref.device, dtype=F32)
+    gv = torch.zeros_like(value, dtype=F32) if outs is None else _out(outs[0], value.shape, ref.device, 'outs[0]')
+    gr, go, ga, gc = _query_grads(outs, 1, (b, q, 3), (b, q, hh, p, 3), (b, q, hh, nl, p), (b, q, n), ref.device)
     nbytes = lib.gd4d_cross_attn_bwd_workspace_bytes(b, q, hh, nl, p)          # B > 1: partial logit gradients per sample
-    ws = torch.empty(nbytes, device=ref.device, dtype=U8) if nbytes else None
+    ws = _out(workspace, (nbytes,), ref.device, 'workspace', U8) if nbytes else None
     _call('gd4d_cross_attn_bwd', _dev(value, 'value', F32), _levels(level_hw),
           *_camera_args(ref, offsets, attn_logits, cam_logits, lidar2img, pc_range, img_h, img_w), _dev(grad_out, 'grad_out', F32),
           _dev(gv, 'grad_value'), _dev(gr, 'grad_ref'), _dev(go, 'grad_offsets'), _dev(ga, 'grad_attn_logits'), _dev(gc, 'grad_cam_logits'),
