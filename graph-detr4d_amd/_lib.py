@@ -134,6 +134,13 @@ SIGNATURES = {
                                   _vp, _vp]),
     'gd4d_petr_keys_plan': (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     'gd4d_petr_keys_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    'gd4d_petr_keys_train_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _f, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                      _vp]),
+    'gd4d_petr_keys_bwd_rows': (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 5),
+    'gd4d_mlp2_wgrad_workspace_bytes': (_c.c_size_t, [_i] * 4),
+    'gd4d_mlp2_wgrad_plan': (_i, [_c.c_longlong, _i, _i, _vp, _vp]),
+    'gd4d_mlp2_wgrad': (_i, [_vp, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _c.c_longlong, _i, _i, _i, _vp, _c.c_size_t,
+                             _vp, _vp, _vp, _vp, _vp]),
     'gd4d_adamw_flat_workspace_bytes': (_c.c_size_t, []),
     'gd4d_adamw_flat': (_i, [_vp] * 6 + [_c.c_size_t, _c.c_int64] + [_f] * 6 + [_vp]),
     'gd4d_adamw_recipe_flat_workspace_bytes': (_c.c_size_t, []),

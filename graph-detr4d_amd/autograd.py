@@ -11,7 +11,9 @@ Inference takes the fully fused HIP path (functional.py); with autograd enabled 
   * LayerNormFunction  - gd4d_layernorm_fwd / gd4d_layernorm_bwd (optionally with the ReLU that follows);
   * MhaCoreFunction    - gd4d_mha_core_fwd (saving the log-sum-exp) / gd4d_mha_core_bwd;
   * CrossMhaFunction   - gd4d_cross_mha_train_fwd / gd4d_cross_mha_bwd: PETR's cross-attention over a long key axis with a
-                         (batch, keys) padding mask.
+                         (batch, keys) padding mask;
+  * PetrKeysFunction   - the key side of PETRHead / PETRv2Head as one node: gd4d_petr_keys_train_fwd forward,
+                         gd4d_petr_keys_bwd_rows + gd4d_mlp2_wgrad (+ the gate's and input_proj's existing kernels) backward.
 What is left to ATen in a training step: residual adds, ReLU between two Linears, dropout, autograd's own accumulations.
 """
 import os
@@ -710,3 +712,90 @@ class Detr3DV2SampleFunction(torch.autograd.Function):
         gf, gl, go, gr = ops.detr3d_v2_bwd(feats, ref, logits, offsets, lidar2img, pc_range, img_h, img_w, hh, grad_out.contiguous(),
                                            want_feats=any(ctx.needs_input_grad[8:]), want_ref=ctx.needs_input_grad[0])
         return (gr, gl.view_as(logits), go.view_as(offsets), None, None, None, None, None, *(gf if gf is not None else [None] * len(feats)))
+
+
+class PetrKeysFunction(torch.autograd.Function):
+    """The key side of PETRHead / PETRv2Head (petr_head.py:383-403, petrv2_head.py:444-469 of the reference) as ONE autograd node:
+    feat (bs, n, Cin, H, W) and the parameters of input_proj, position_encoder, adapt_pos3d and - PETRv2Head with_fpe, else four
+    Nones - fpe.conv_reduce / conv_expand -> (memory, key_pos), both (n H W, bs, 256): what PETRTransformer.forward_keys takes.
+
+    forward:  x = input_proj(feat) (gd4d_conv1x1_bn_act_fwd); the sine branch over the kept (R S, 384) expansion (gd4d_gemm_bf16x3_fwd
+              twice, as FeaturePositionEmbedding._sine_branch(chlast=True)); gd4d_petr_keys_train_fwd.  Kept for the backward: x,
+              and with a gate the embedding and the gate's logits - (rows, 256) each.  Nothing of rows x 1024 or rows x 192.
+    backward: gd4d_petr_keys_bwd_rows; gd4d_mlp2_wgrad for position_encoder (the frustum generated again) and adapt_pos3d; the gate's
+              two layers as head_pe._HeadPEFunction.backward does them (g1 = conv_reduce(x) recomputed); input_proj's gradients from
+              dx on gd4d_fpn_lateral_wgrad / _dgrad.  No atomics, every sum in a fixed order.
+    `geom` (not a tensor): dict(i2l (R, 4, 4): the backward reads it again - a tensor of the caller's that nothing writes in between,
+    not the head's persistent buffer), pad_hw, depth_num, depth_start, position_range, xs (R, S, 384), ip_image, ip_scale, ip_image_t
+    (a callable: the transposed image, made when feat needs a gradient), pe_image, se_image).  The buffers are consumed by the first
+    backward, and the versions of feat and the parameters are compared with the forward's, as in _HeadPEFunction."""
+
+    @staticmethod
+    def forward(ctx, feat, geom, *params):
+        ip_w, ip_b, w0, b0, w2, b2, a0, ab0, a2, ab2, wr, br, we, be = params
+        bs, n, cin, h, w = feat.shape
+        r, s = bs * n, h * w
+        flat = lambda t: t.detach().reshape(t.shape[0], -1).contiguous()      # noqa: E731
+        feat4 = feat.detach().flatten(0, 1).contiguous()
+        x = ops.conv1x1_bn_act(feat4, geom['ip_image'], 256, geom['ip_scale'], ip_b.detach().contiguous(), relu=False)
+        xs = geom['xs'].view(r * s, -1)
+        hs = ops.gemm_bf16x3_fwd(xs, *ops.split_bf16_fwd(flat(a0)), ab0.detach(), relu=True)
+        sine = ops.gemm_bf16x3_fwd(hs, *ops.split_bf16_fwd(flat(a2)), ab2.detach())
+        del hs
+        memory, key_pos, pe, logits = ops.petr_keys_train_fwd(
+            x.view(bs, n, 256, h, w), geom['i2l'], geom['pad_hw'], geom['depth_num'], geom['depth_start'], geom['position_range'],
+            geom['pe_image'], b2.detach(), sine.view(r, s, 256), geom['se_image'], None if be is None else be.detach())
+        ctx.bufs = dict(feat4=feat4, x=x, pe=pe, logits=logits, xs=xs)
+        ctx.geom, ctx.shape = geom, (bs, n, h, w)
+        ctx.weights = tuple(None if t is None else flat(t) for t in (w0, w2, a0, a2, wr, we))
+        ctx.biases = (b0.detach(), ab0.detach(), None if br is None else br.detach())
+        ctx.param_shapes = [None if t is None else tuple(t.shape) for t in params]
+        ctx.watched = [t for t in (feat,) + params if t is not None]
+        ctx.versions = [t._version for t in ctx.watched]
+        return memory, key_pos
+
+    @staticmethod
+    def backward(ctx, dmemory, dkey_pos):
+        if ctx.bufs is None:
+            raise RuntimeError('PETRHead key side: the saved activations were consumed by the first backward (retain_graph / double '
+                               'backward are not supported on the HIP path; torch_ops=True runs the torch-op route)')
+        if [t._version for t in ctx.watched] != ctx.versions:
+            raise RuntimeError('PETRHead key side: a feature map or a parameter of input_proj / position_encoder / adapt_pos3d / fpe was '
+                               'modified in place between the forward and the backward pass (the backward reads them) - as autograd '
+                               'itself refuses a saved tensor that was modified in place')
+        b, ctx.bufs = ctx.bufs, None
+        ctx.watched = None
+        geom = ctx.geom
+        bs, n, h, w = ctx.shape
+        w0, w2, a0, a2, wr, we = ctx.weights
+        b0, ab0, br = ctx.biases
+        need_feat, need = ctx.needs_input_grad[0], ctx.needs_input_grad[2:]
+        gate = b['logits'] is not None
+        x, feat4 = b['x'], b['feat4']
+        if dkey_pos is None:
+            dkey_pos = torch.zeros(n * h * w, bs, 256, device=x.device)
+        dpe, dlogit, dsine, dx = ops.petr_keys_bwd_rows(dkey_pos.contiguous(), None if dmemory is None else dmemory.contiguous(),
+                                                        ctx.shape, b['pe'], b['logits'])
+        out = [None] * 14
+        if any(need[2:6]):                                                        # position_encoder: the frustum generated again
+            frustum = (geom['i2l'], (h, w), geom['pad_hw'], geom['depth_num'], geom['depth_start'], geom['position_range'])
+            out[4], out[5], out[2], out[3] = ops.mlp2_wgrad(dpe, w0, b0, w2, frustum=frustum)
+        if any(need[6:10]):                                                       # adapt_pos3d over the kept sine expansion
+            out[8], out[9], out[6], out[7] = ops.mlp2_wgrad(dsine, a0, ab0, a2, x=b['xs'])
+        need_dx = need_feat or need[0] or need[1]
+        if gate and (need_dx or any(need[10:14])):
+            g1 = ops.value_proj_fwd([x], wr, br)                                  # conv_reduce(x), (R, S, 256): recomputed, the size of x
+            g1r = g1.view(-1, 256)
+            out[12], out[13] = ops.gemm_tn_bf16x3(dlogit, g1r, relu_b=True)
+            if need_dx or need[10] or need[11]:
+                ops.gemm_bf16x3_fwd(dlogit, *ops.split_bf16_fwd(we.t().contiguous()), out=g1r, mask_out=True)
+                out[10], out[11] = ops.value_proj_bwd_weight(g1, [x])
+                if need_dx:
+                    ops.value_proj_bwd_input(g1, wr, [(h, w)], grads=[dx], accumulate=True)
+        if need[0] or need[1]:
+            out[0], out[1] = ops.fpn_lateral_wgrad(dx, feat4)
+        dfeat = None
+        if need_feat:
+            dfeat = ops.fpn_lateral_dgrad(dx, geom['ip_image_t'](), feat4.shape[1]).view(bs, n, -1, h, w)
+        shaped = [o.view(sh) if o is not None and nd else None for o, sh, nd in zip(out, ctx.param_shapes, need)]
+        return (dfeat, None, *shaped)

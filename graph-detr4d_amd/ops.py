@@ -1462,6 +1462,128 @@ def petr_keys_fwd(x, img2lidar, pad_hw, depth_num, depth_start, position_range, 
     return memory, key_pos
 
 
+def petr_keys_train_fwd(x, img2lidar, pad_hw, depth_num, depth_start, position_range, pe_image, pe_b2, sine, se_image=None, se_b2=None,
+                        memory=None, key_pos=None, pe=None, logits=None):
+    """gd4d_petr_keys_train_fwd: petr_keys_fwd (the same arguments, memory / key_pos bit for bit) that also stores what the backward
+    reads.  Returns (memory, key_pos, pe, logits): with a gate pe (bs n H W, 256) = position_encoder(frustum) before the gate and logits
+    (bs n H W, 256) = the gate's logits, camera-major rows; without a gate both are None (dpe = dkey_pos)."""
+    if x.dim() != 5 or x.shape[2] != 256:
+        raise ValueError(f'petr_keys_train_fwd: x must be (bs, n, 256, H, W), got {tuple(x.shape)}')
+    bs, n, c, h, w = x.shape
+    k1, pe_h, n2 = pe_image.shape_khn
+    if k1 != 3 * depth_num or n2 != 256:
+        raise ValueError(f'petr_keys_train_fwd: the position image is {k1} -> {pe_h} -> {n2}, the frustum has {3 * depth_num} channels')
+    se_h = 0
+    if se_image is not None:
+        sk, se_h, sn = se_image.shape_khn
+        if sk != 256 or sn != 256:
+            raise ValueError('petr_keys_train_fwd: the gate image must be 256 -> H -> 256')
+    if img2lidar.numel() != bs * n * 16 or sine.numel() != bs * n * h * w * 256:
+        raise ValueError(f'petr_keys_train_fwd: img2lidar must hold ({bs * n}, 4, 4) and sine ({bs * n}, {h * w}, 256)')
+    if se_b2 is not None and se_image is None:
+        raise ValueError('petr_keys_train_fwd: se_b2 is the gate\'s second bias: it comes with se_image')
+    for bias, what in ((pe_b2, 'pe_b2'), (se_b2, 'se_b2')):
+        if bias is not None and bias.numel() != 256:
+            raise ValueError(f'petr_keys_train_fwd: {what} must hold 256 values, got {tuple(bias.shape)}')
+    m = bs * n * h * w
+    memory = _out(memory, (n * h * w, bs, 256), x.device, 'memory')
+    key_pos = _out(key_pos, (n * h * w, bs, 256), x.device, 'key_pos')
+    if se_image is not None:
+        pe = _out(pe, (m, 256), x.device, 'pe')
+        logits = _out(logits, (m, 256), x.device, 'logits')
+    elif pe is not None or logits is not None:
+        raise ValueError('petr_keys_train_fwd: pe / logits are stored with a gate only')
+    _call('gd4d_petr_keys_train_fwd', _dev(x, 'x', F32), _dev(img2lidar, 'img2lidar', F32), bs, n, c, h, w, float(pad_hw[0]),
+          float(pad_hw[1]), int(depth_num), float(depth_start), _range6(position_range), _dev(pe_image, 'pe_image', U8),
+          _opt(pe_b2, 'pe_b2'), pe_h, _opt(se_image, 'se_image', U8), _opt(se_b2, 'se_b2'), se_h, _dev(sine, 'sine', F32),
+          _dev(memory, 'memory', F32), _dev(key_pos, 'key_pos', F32), _opt(pe, 'pe'), _opt(logits, 'logits'))
+    return memory, key_pos, pe, logits
+
+
+def petr_keys_bwd_rows(dkey_pos, dmemory, shape, pe=None, logits=None, outs=None):
+    """gd4d_petr_keys_bwd_rows: dkey_pos, dmemory (n H W, bs, 256; dmemory None: zeros), shape = (bs, n, H, W), pe / logits = what
+    petr_keys_train_fwd stored (a gate) or None -> (dpe, dlogit, dsine (bs n H W, 256) camera-major rows, dx0 (bs n, 256, H, W) =
+    dmemory transposed).  Without a gate dlogit is None and dpe IS dsine; with bs = 1 key rows are camera-major rows and dsine IS
+    dkey_pos (no copy).  outs = (dpe, dlogit, dsine, dx0): the tensors to write (None entries: new ones)."""
+    bs, n, h, w = (int(v) for v in shape)
+    m = bs * n * h * w
+    if tuple(dkey_pos.shape) != (n * h * w, bs, 256) or (dmemory is not None and tuple(dmemory.shape) != (n * h * w, bs, 256)):
+        raise ValueError(f'petr_keys_bwd_rows: dkey_pos / dmemory must be ({n * h * w}, {bs}, 256)')
+    gate = logits is not None
+    if gate != (pe is not None) or (gate and (tuple(pe.shape) != (m, 256) or tuple(logits.shape) != (m, 256))):
+        raise ValueError(f'petr_keys_bwd_rows: pe and logits come together, ({m}, 256) each')
+    o_dpe, o_dlogit, o_dsine, o_dx0 = outs if outs is not None else (None,) * 4
+    dev = dkey_pos.device
+    dsine = None if bs == 1 else _out(o_dsine, (m, 256), dev, 'petr_keys_bwd_rows: dsine')
+    dpe = _out(o_dpe, (m, 256), dev, 'petr_keys_bwd_rows: dpe') if gate else None
+    dlogit = _out(o_dlogit, (m, 256), dev, 'petr_keys_bwd_rows: dlogit') if gate else None
+    dx0 = _out(o_dx0, (bs * n, 256, h, w), dev, 'petr_keys_bwd_rows: dx0')
+    _call('gd4d_petr_keys_bwd_rows', _dev(dkey_pos, 'dkey_pos', F32), _opt(dmemory, 'dmemory'), _opt(pe, 'pe'), _opt(logits, 'logits'),
+          bs, n, h, w, _opt(dpe, 'dpe'), _opt(dlogit, 'dlogit'), _opt(dsine, 'dsine'), _dev(dx0, 'dx0', F32))
+    if dsine is None:
+        dsine = dkey_pos.view(m, 256)
+    return (dpe if gate else dsine), dlogit, dsine, dx0
+
+
+def mlp2_wgrad_plan(m, partitions, h=1024):
+    """gd4d_mlp2_wgrad_plan (host only, no GPU): ((hidden chunks, partitions) = the grid, [(first tile, one past the last)] per
+    partition) of mlp2_wgrad over m rows: contiguous ranges of the 128-row tiles that cover every tile once; a range may be empty."""
+    lib = _lib.load()
+    grid = (ctypes.c_int32 * 2)()
+    ranges = (ctypes.c_int32 * (2 * max(int(partitions), 1)))()
+    _lib.check(lib.gd4d_mlp2_wgrad_plan(int(m), int(h), int(partitions), ctypes.addressof(grid), ctypes.addressof(ranges)),
+               'gd4d_mlp2_wgrad_plan')
+    return (grid[0], grid[1]), [(ranges[2 * q], ranges[2 * q + 1]) for q in range(int(partitions))]
+
+
+def mlp2_wgrad(dy, w1, b1, w2, x=None, frustum=None, partitions=None, outs=None, workspace=None, want_db2=True):
+    """gd4d_mlp2_wgrad: for y = relu(X W1^T + b1) W2^T + b2 and dy (M, 256) -> (dW2 (256, H), db2 (256) or None, dW1 (H, K1), db1 (H)),
+    no rows x H and no rows x K1 tensor written.  X: `x` (M, 384) fp32 rows, or `frustum` = (img2lidar (R, 4, 4), (H, W), pad_hw,
+    depth_num, depth_start, position_range): the 192 frustum inputs of R cameras generated in registers (M = R H W).  The rows are
+    split over `partitions` partial sums added in order (default: about two workgroups per compute unit over the H / 32 hidden
+    chunks, at most one partition per 128-row tile).  outs = (dW2, db2, dW1, db1) / workspace: the tensors to write and the partial
+    sums' scratch floats (defaults: new ones)."""
+    lib = _lib.load()
+    if (x is None) == (frustum is None):
+        raise ValueError('mlp2_wgrad: X is either `x` (rows in memory) or `frustum` (generated)')
+    m = int(dy.shape[0])
+    hid, k1 = (int(v) for v in w1.shape)
+    n2 = int(w2.shape[0])
+    if dy.dim() != 2 or dy.shape[1] != n2 or tuple(w2.shape) != (n2, hid) or b1.numel() != hid:
+        raise ValueError(f'mlp2_wgrad: dy {tuple(dy.shape)}, W1 {tuple(w1.shape)}, b1 {tuple(b1.shape)}, W2 {tuple(w2.shape)} do not form an MLP')
+    if x is not None and tuple(x.shape) != (m, k1):
+        raise ValueError(f'mlp2_wgrad: x must be ({m}, {k1}), got {tuple(x.shape)}')
+    i2l, r, fh, fw, pad_h, pad_w, depth_num, depth_start, rng = None, 0, 0, 0, 0.0, 0.0, 0, 0.0, None
+    if frustum is not None:
+        i2l, (fh, fw), (pad_h, pad_w), depth_num, depth_start, prange = frustum
+        r = i2l.numel() // 16
+        if r * fh * fw != m or k1 != 3 * depth_num:
+            raise ValueError(f'mlp2_wgrad: {r} cameras of {fh} x {fw} pixels and {3 * depth_num} inputs for dy of {m} rows, W1 of {k1} columns')
+        rng = _range6(prange)
+    if partitions is None:
+        tiles = (m + 127) // 128
+        chunks = max(hid // 32, 1)
+        cus = torch.cuda.get_device_properties(dy.device).multi_processor_count
+        partitions = max(1, min(tiles, (2 * cus + chunks - 1) // chunks))
+    partitions = int(partitions)
+    nbytes = int(lib.gd4d_mlp2_wgrad_workspace_bytes(k1, hid, n2, partitions))
+    if nbytes == 0:
+        raise _lib.Gd4dError(f'mlp2_wgrad: K1 = {k1} (192 generated, 384 read), H = {hid} (a multiple of 32 up to 4096), N2 = {n2} (256), '
+                             f'partitions = {partitions} (1 .. 4096) are the kernel\'s limits')
+    o_dw2, o_db2, o_dw1, o_db1 = outs if outs is not None else (None,) * 4
+    dev = dy.device
+    ws = _out(workspace, (nbytes // 4,), dev, 'mlp2_wgrad: workspace')
+    dw2 = _out(o_dw2, (n2, hid), dev, 'mlp2_wgrad: dW2')
+    db2 = _out(o_db2, (n2,), dev, 'mlp2_wgrad: db2') if want_db2 else None
+    dw1 = _out(o_dw1, (hid, k1), dev, 'mlp2_wgrad: dW1')
+    db1 = _out(o_db1, (hid,), dev, 'mlp2_wgrad: db1')
+    _call('gd4d_mlp2_wgrad', _opt(x, 'x'), k1, _opt(i2l, 'img2lidar'), r, int(fh), int(fw), float(pad_h), float(pad_w), int(depth_num),
+          float(depth_start), rng, _dev(w1, 'w1', F32), _dev(b1, 'b1', F32), _dev(w2, 'w2', F32), _dev(dy, 'dy', F32), m, hid, n2,
+          partitions, _dev(ws, 'workspace', F32), nbytes, _dev(dw2, 'dw2', F32), _opt(db2, 'db2'), _dev(dw1, 'dw1', F32),
+          _dev(db1, 'db1', F32))
+    return dw2, db2, dw1, db1
+
+
 def gemm_tn_bf16x3(a, b, relu_b=False, want_colsum=True):
     """gd4d_gemm_tn_bf16x3: a (R, M), b (R, N) fp32 row-major -> (a^T b (M, N), column sums of a (M) or None): the weight /
     bias gradients of a Linear over R rows (a = output gradient, b = input; relu_b: ReLU on b as it is read)."""

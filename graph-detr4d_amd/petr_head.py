@@ -12,8 +12,15 @@ copies of PETRTransformer.forward are never made -, and the branches + box epilo
 branch and query_embedding(pos2posemb3d(reference_points)) depend on parameters (and the padding masks) only: they are kept under
 ops._Stamp, the one validity rule.
 
-torch_ops=True: the reference's op sequence on torch, differentiable - what training takes.  What the kernels do not cover is
-refused in the name of that switch, at construction where the cause is known there; never a silent fallback.
+hip_train=True (opt-in): a call in train mode or under autograd runs on the kernels too.  The key side is ONE autograd node
+(autograd.PetrKeysFunction: gd4d_petr_keys_train_fwd forward; gd4d_petr_keys_bwd_rows, gd4d_mlp2_wgrad and the gate's / input_proj's
+existing kernels backward - no (rows, 1024) hidden activation and no (rows, 192) frustum tensor in either direction), the query
+embedding, the branches and the RegLayers go through Fn.linear_autograd, the box epilogue through autograd.BoxHeadFunction, and every
+PETRMultiheadAttention below the head gets hip_train = True.  Eval mode without autograd takes the inference route unchanged.
+
+torch_ops=True: the reference's op sequence on torch, differentiable - what training takes without hip_train; it wins over
+hip_train.  What the kernels do not cover is refused in the name of that switch, at construction where the cause is known there;
+never a silent fallback.
 """
 import copy
 import math
@@ -70,7 +77,8 @@ class RegLayer(nn.Module):
     without autograd the five heads run as ONE stacked (5 C, C) Linear + ReLU and ONE block-diagonal (sum of reg dims, 5 C) Linear on
     gd4d_linear_fwd; the stacked fp32 weights - what that kernel reads; it has no packed image form - are kept while the twenty
     parameters they are made of hold (ops._Stamp).  Train mode, autograd and other activations raise and name `torch_ops = True`,
-    which is the reference's op sequence on torch; PETRv2Head's torch-op route sets it."""
+    which is the reference's op sequence on torch; PETRv2Head's torch-op route sets it.  hip_train (set by a head built with
+    hip_train=True, not a keyword of its own): train mode / autograd run the trunk and the five heads through Fn.sequential_autograd."""
 
     def __init__(self, embed_dims=256, shared_reg_fcs=2, group_reg_dims=(2, 1, 3, 2, 2), act_layer=nn.ReLU, drop=0.0):
         super().__init__()
@@ -82,6 +90,7 @@ class RegLayer(nn.Module):
                                         for d in group_reg_dims)
         self._stacked = None
         self.torch_ops = False
+        self.hip_train = False
 
     def _stacked_heads(self):
         src = [p for h in self.task_heads for p in (h[0].weight, h[0].bias, h[2].weight, h[2].bias)]
@@ -100,11 +109,15 @@ class RegLayer(nn.Module):
             all(isinstance(m, (nn.Linear, nn.ReLU, nn.Dropout)) for m in self.reg_branch)
         what = (f'RegLayer in {"train" if self.training else "eval"} mode, {"autograd" if grad else "no autograd"}, dtype {x.dtype}, '
                 f'{"ReLU" if plain else "another activation"}')
-        covered = plain and x.dtype == torch.float32 and not self.training and not grad
+        train = self.hip_train and (self.training or grad)
+        covered = plain and x.dtype == torch.float32 and (train or (not self.training and not grad))
         if Fn.torch_ops_route(what, covered, module=self):               # (the head's torch-op route sets torch_ops on its RegLayers)
             reg_feat = self.reg_branch(x)                                # petrv2_head.py:82-89
             return torch.cat([head(reg_feat.clone()) for head in self.task_heads], -1)
         Fn.require_gpu(x, 'x')
+        if train:                                            # (the stacked form is for inference only)
+            reg_feat = Fn.sequential_autograd(self.reg_branch, x)
+            return torch.cat([Fn.sequential_autograd(head, reg_feat) for head in self.task_heads], -1)
         for m in self.reg_branch:                            # (eval mode: the Dropouts are the identity)
             if isinstance(m, nn.Linear):
                 x = Fn.linear(x, m.weight, m.bias, relu=True)
@@ -128,9 +141,11 @@ class _PETRHeadBase(nn.Module):
                                               iou_cost=dict(type='IoUCost', iou_mode='giou', weight=2.0))),
                  test_cfg=dict(max_per_img=100), with_position=True, with_multiview=False, depth_step=0.8, depth_num=64, LID=False,
                  depth_start=1, position_level=0, position_range=[-65, -65, -8.0, 65, 65, 8.0], group_reg_dims=(2, 1, 3, 2, 2),
-                 init_cfg=None, normedlinear=False, with_fpe=False, with_time=False, with_multi=False, torch_ops=False, **kwargs):
+                 init_cfg=None, normedlinear=False, with_fpe=False, with_time=False, with_multi=False, torch_ops=False, hip_train=False,
+                 **kwargs):
         super().__init__()
         self.torch_ops = bool(torch_ops)
+        self.hip_train = bool(hip_train)
         self.code_size = kwargs.get('code_size', 10)
         cw = code_weights if code_weights is not None else [1.0] * 8 + [0.2, 0.2]
         self.num_query, self.num_classes, self.in_channels, self.num_reg_fcs = num_query, num_classes, in_channels, num_reg_fcs
@@ -214,6 +229,12 @@ class _PETRHeadBase(nn.Module):
             self.fpe = SELayer(c)
         self._kept = {}                                       # name -> (stamp, value): images, input_proj's, the query embedding
         self.__dict__['_pe'] = None                           # FeaturePositionEmbedding's masks / sine pieces over THIS head's modules
+        self.__dict__['_xs'] = None                           # (masks, the (R, S, 384) sine expansion): a function of the masks alone
+        if self.hip_train:                                    # one keyword trains the stage, as ResNet(hip_train=True) tells its blocks
+            from .petr_transformer import PETRMultiheadAttention
+            for m in self.modules():
+                if isinstance(m, (PETRMultiheadAttention, RegLayer)):
+                    m.hip_train = True
 
     def init_weights(self):
         self.transformer.init_weights()
@@ -243,7 +264,7 @@ class _PETRHeadBase(nn.Module):
     def train(self, mode=True):
         if mode != self.training:
             self._kept.clear()
-            self.__dict__['_pe'] = None
+            self.__dict__['_pe'] = self.__dict__['_xs'] = None
         return super().train(mode)
 
     # ---- kept values ---------------------------------------------------------------------------------------------------
@@ -271,11 +292,15 @@ class _PETRHeadBase(nn.Module):
             self.__dict__['_pe'] = pe
         return pe
 
+    def _input_proj_image(self):
+        conv = self.input_proj
+        return self._keep('input_proj', [conv.weight], lambda: (ops.conv1x1_image(conv.weight.detach()),
+                                                                torch.ones(conv.out_channels, device=conv.weight.device)))
+
     def _input_proj(self, feat):
         """input_proj on gd4d_conv1x1_bn_act_fwd (scale 1, shift = the bias, no activation): (bs, n, cin, h, w) -> (bs, n, 256, h, w)."""
         conv = self.input_proj
-        image, scale = self._keep('input_proj', [conv.weight], lambda: (ops.conv1x1_image(conv.weight.detach()),
-                                                                        torch.ones(conv.out_channels, device=conv.weight.device)))
+        image, scale = self._input_proj_image()
         bs, n = feat.shape[:2]
         x = ops.conv1x1_bn_act(feat.flatten(0, 1).contiguous(), image, conv.out_channels, scale, conv.bias.detach().contiguous(), relu=False)
         return x.unflatten(0, (bs, n))
@@ -317,10 +342,13 @@ class _PETRHeadBase(nn.Module):
         what = (f'{type(self).__name__} in {"train" if self.training else "eval"} mode, {"autograd" if grad else "no autograd"}, '
                 f'in_channels {self.in_channels} (a multiple of 32 up to 2048), dtype {feat.dtype}'
                 + ''.join(f', {w}' for w, _ in no))
-        covered = not no and not self.training and not grad and feat.dtype == torch.float32 and \
+        train = self.hip_train and (self.training or grad)
+        covered = not no and (train or (not self.training and not grad)) and feat.dtype == torch.float32 and \
             self.in_channels % 32 == 0 and 32 <= self.in_channels <= 2048
-        if Fn.torch_ops_route(what, covered, module=self):
+        if Fn.torch_ops_route(what + (', hip_train' if train else ''), covered, module=self):
             return self._forward_torch(mlvl_feats, img_metas)
+        if train:
+            return self._forward_train(feat, img_metas)
         with torch.no_grad():
             return self._forward_kernels(feat, img_metas)
 
@@ -346,6 +374,56 @@ class _PETRHeadBase(nn.Module):
             # (after the pc_range scaling, which touches columns 0, 1 and 4 only; the reference's broadcast, petrv2_head.py:510)
             boxes = outs['all_bbox_preds']
             boxes[..., 8:] = boxes[..., 8:] / self._mean_time_stamp(img_metas, boxes, bs)
+        return outs
+
+    def _sine_expansion(self, masks):
+        """SinePositionalEncoding3D of the padding masks in channels-last rows, (R, S, 384): a function of the masks alone, kept while
+        padding_masks hands out the same mask objects - the one rows x K tensor that lives across training steps."""
+        hit = self.__dict__['_xs']
+        if hit is not None and hit[0] is masks[0]:
+            return hit[1]
+        pe, m = self._helper(), masks[0]
+        xs = torch.empty(m.shape[0] * m.shape[1], m.shape[2] * m.shape[3], 3 * pe.num_feats, device=m.device, dtype=torch.float32)
+        embeds, dim_t = pe._sine_embeds(m)
+        ops.sine_pe3d_fwd(*embeds, dim_t, out=xs, row_start=0)
+        self.__dict__['_xs'] = (m, xs)
+        return xs
+
+    def _forward_train(self, feat, img_metas):
+        """hip_train: the kernel route with autograd - the key side as one node, everything behind it on the library's autograd
+        Functions."""
+        from .autograd import PetrKeysFunction
+        bs, n, _, h, w = feat.shape
+        pe = self._helper()
+        masks, pad_hw = pe.padding_masks(img_metas, [feat])
+        ip_image, ip_scale = self._input_proj_image()
+        img = self._images()
+        conv = self.input_proj
+        # The node reads the matrices again in its backward (the frustum is generated again there), and _matrices_device hands out ONE
+        # persistent buffer that the next call with other img_metas refreshes in place: a second forward before the first backward
+        # (losses summed over samples) would give the first one the second one's cameras.  A private copy, as
+        # Fn.lidar2img_device makes under autograd (R x 64 bytes, device to device).
+        i2l = pe._matrices_device(pe._img2lidar(img_metas), feat.device).clone()
+        geom = dict(i2l=i2l, pad_hw=pad_hw, depth_num=self.depth_num,
+                    depth_start=self.depth_start, position_range=self.position_range, xs=self._sine_expansion(masks), ip_image=ip_image,
+                    ip_scale=ip_scale, pe_image=img['pe'], se_image=img['se'],
+                    ip_image_t=lambda: self._keep('input_proj_t', [conv.weight], lambda: ops.fpn_lateral_image_t(conv.weight.detach())))
+        seqs = [self.position_encoder, self.adapt_pos3d] + ([(self.fpe.conv_reduce, None, self.fpe.conv_expand)] if self.with_fpe else [])
+        params = [conv.weight, conv.bias] + [p for q in seqs for c in (q[0], q[2]) for p in (c.weight, c.bias)]
+        params += [None] * (14 - len(params))
+        memory, key_pos = PetrKeysFunction.apply(feat, geom, *params)
+        q0, q2 = self.query_embedding[0], self.query_embedding[2]
+        query_embeds = Fn.linear_autograd(Fn.linear_autograd(pos2posemb3d(self.reference_points.weight), q0.weight, q0.bias, relu=True),
+                                          q2.weight, q2.bias)                     # (not kept while parameters require grad)
+        out_dec = self.transformer.forward_keys(memory, key_pos, masks[0].reshape(bs, n * h * w), query_embeds, self.reg_branches)
+        out_dec = torch.nan_to_num(out_dec)
+        # (not detached: the reference adds inverse_sigmoid(reference_points) at every level, and BoxHeadFunction hands its gradient back)
+        ref = self.reference_points.weight.unsqueeze(0).expand(bs, -1, -1)
+        outs = Fn.head_outputs(out_dec.transpose(1, 2), ref, ref.unsqueeze(0).expand(out_dec.shape[0], -1, -1, -1), self.cls_branches,
+                               self.reg_branches, self.pc_range)
+        if self.with_time:                                   # (not in place: the boxes are an autograd node's output)
+            boxes = outs['all_bbox_preds']
+            outs['all_bbox_preds'] = torch.cat((boxes[..., :8], boxes[..., 8:] / self._mean_time_stamp(img_metas, boxes, bs)), -1)
         return outs
 
     def position_embeding(self, img_feats, img_metas, masks=None):

@@ -913,6 +913,36 @@ int gd4d_petr_keys_fwd(const float* x, const float* img2lidar, int bs, int n, in
                        float depth_start, const double* position_range, const void* pe_image, const float* pe_b2, int pe_H,
                        const void* se_image, const float* se_b2, int se_H, const float* sine, float* memory, float* key_pos,
                        void* stream);
+/* Training the key side (autograd.PetrKeysFunction; csrc/gd4d_petr_head_train.hip).
+ * gd4d_petr_keys_train_fwd - gd4d_petr_keys_fwd's kernel in its training instantiation: memory / key_pos bit for bit what
+ * gd4d_petr_keys_fwd writes, and - with a gate (se_image not NULL) - pe_out (R H W, 256) = position_encoder(frustum) after its bias and
+ * before the gate, logit_out (R H W, 256) = the gate's logits after se_b2, both in the camera-major rows m = (b n + cam) H W + p.
+ * Without a gate nothing more is stored (pe_out / logit_out are not read: dpe = dkey_pos) and the call IS gd4d_petr_keys_fwd.
+ * gd4d_petr_keys_bwd_rows - one pass over the rows, from dkey_pos / dmemory (n H W, bs, 256; dmemory NULL: zeros) read at the key row
+ * of m (gd4d_petr_keys_plan's map): dsine[m] = g, dpe[m] = g sigmoid(logit), dlogit[m] = g pe sigmoid' (logit not NULL: the gate; pe,
+ * dpe, dlogit come with it), all (R H W, 256), and dx0 (R, 256, H, W) = dmemory transposed into input_proj's NCHW map.  dsine NULL:
+ * not written (bs = 1: dkey_pos is it); dpe NULL without a gate: not written (it equals dsine).  Pointers 16-byte aligned.
+ * gd4d_mlp2_wgrad - for y = relu(X W1^T + b1) W2^T + b2 over M rows and dy (M, 256): dw2 (256, H), db2 (256; NULL: skipped), dw1
+ * (H, K1), db1 (H), without writing a rows x H or rows x K1 tensor.  x (M, K1 = 384) fp32 rows, or x NULL: the K1 = 192 frustum inputs
+ * of R cameras of fH x fW pixels generated in registers (img2lidar (R, 16), pad_h / pad_w, D = 64, depth_start, position_range as
+ * gd4d_frustum_pe_input_fwd; M = R fH fW; dw1's columns in the module's order 3 d + axis).  The grid is (H / 32 hidden chunks) x
+ * partitions; a partition walks a contiguous range of the 128-row tiles (gd4d_mlp2_wgrad_plan: grid[2] = {chunks, partitions},
+ * tile_ranges[2 q], [2 q + 1] = partition q's first tile and one past its last; a partition may be empty) and leaves one partial sum
+ * in the workspace (gd4d_mlp2_wgrad_workspace_bytes: independent of M; 0 = unsupported shape), added in partition order by a second
+ * launch: no atomics, run-to-run identical.  N2 = 256, H a multiple of 32 up to 4096, 1 .. 4096 partitions; x, w1, dy and the
+ * workspace 16-byte aligned. */
+int gd4d_petr_keys_train_fwd(const float* x, const float* img2lidar, int bs, int n, int C, int H, int W, float pad_h, float pad_w,
+                             int D, float depth_start, const double* position_range, const void* pe_image, const float* pe_b2,
+                             int pe_H, const void* se_image, const float* se_b2, int se_H, const float* sine, float* memory,
+                             float* key_pos, float* pe_out, float* logit_out, void* stream);
+int gd4d_petr_keys_bwd_rows(const float* dkey_pos, const float* dmemory, const float* pe, const float* logit, int bs, int n, int H,
+                            int W, float* dpe, float* dlogit, float* dsine, float* dx0, void* stream);
+size_t gd4d_mlp2_wgrad_workspace_bytes(int K1, int H, int N2, int partitions);
+int gd4d_mlp2_wgrad_plan(long long M, int H, int partitions, int32_t* grid, int32_t* tile_ranges);
+int gd4d_mlp2_wgrad(const float* x, int K1, const float* img2lidar, int R, int fH, int fW, float pad_h, float pad_w, int D,
+                    float depth_start, const double* position_range, const float* w1, const float* b1, const float* w2,
+                    const float* dy, long long M, int H, int N2, int partitions, float* workspace, size_t workspace_bytes, float* dw2,
+                    float* db2, float* dw1, float* db1, void* stream);
 
 /* gd4d_adamw_flat - the optimizer step of the reference's training recipe over ONE flat fp32 parameter / gradient buffer: clipping
  * of the gradient's L2 norm (torch.nn.utils.clip_grad_norm_: g *= min(1, max_norm / (norm + 1e-6)); max_norm <= 0: none) followed by
