@@ -246,6 +246,18 @@ SIGNATURES = {
     'gd4d_osa_concat_wgrad': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gd4d_ese_bwd_workspace_bytes': (_c.c_size_t, [_i, _i]),
     'gd4d_ese_bwd': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd4d_conv1x1_image_t_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_conv1x1_image_t': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_conv3x3_act_image_t_bytes': (_c.c_size_t, [_i, _i]),
+    'gd4d_conv3x3_act_image_t': (_i, [_vp, _i, _i, _vp, _vp]),
+    'gd4d_relu_mask_bwd': (_i, [_vp, _vp, _c.c_longlong, _vp, _vp]),
+    'gd4d_even_pixels_scatter': (_i, [_vp, _c.c_longlong, _i, _i, _vp, _vp]),
+    'gd4d_conv1x1_dgrad': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    'gd4d_conv3x3_act_dgrad': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    'gd4d_resnet_wgrad_tiles': (_c.c_longlong, [_i, _i, _i, _i, _i]),
+    'gd4d_resnet_wgrad_workspace_bytes': (_c.c_size_t, [_i] * 8),
+    'gd4d_conv1x1_wgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd4d_conv3x3_act_wgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

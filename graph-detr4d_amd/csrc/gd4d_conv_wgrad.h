@@ -12,6 +12,8 @@
 //   vt_conv3x3_wgrad_kernel    3x3       VvWgradShape        yes    run-time Cin / Cout / blockDim, tiles of one map
 //   fpn_lateral_wgrad_kernel   1x1       LateralWgradShape   yes    256 output channels (no guard), one source map
 //   vt_osa_wgrad_kernel        1x1       OsaWgradShape       no     blocks of 256 output channels (guarded), up to VV_MAX_SRC source maps
+//   rt_conv3x3_wgrad_kernel    3x3       RtWgradShape        yes    as VvWgradShape, Cout in blocks of up to 256 along blockIdx.y (ResNet)
+//   rt_conv1x1_wgrad_kernel    1x1       RtPwWgradShape      yes    blocks of 256 output channels (guarded), x read at stride 1 or 2 (ResNet)
 //
 // conv3x3_wgrad_body: dW[oc, ic, ky, kx] = sum over tiles and pixels of dy[oc, p] x[ic, p + (ky - 1, kx - 1)].
 //   Grid (Cin / 32 chunks of input channels) x P, a tile is 16 x 16 pixels.  A workgroup of Cout / 32 waves owns Cout output
@@ -168,7 +170,9 @@ struct Conv1x1Source {             // where a staged channel lies
 };
 
 // Shape: g (a Conv1x1Wgrad), cout(), GUARD (output channels past cout() exist in the block and are skipped), oc0(wave) (the wave's
-// first output channel) and source(channel of K, whether it is < k) -> Conv1x1Source.  s_b: [hi, lo][channel][pixel group (+ 1)].
+// first output channel), source(channel of K, whether it is < k) -> Conv1x1Source, and where pixel p of dy's map lies in x's:
+// x_plane() (the pixels of one channel of x) and x_pixel(p) (p itself, or the input pixel (2 yo, 2 xo) under output pixel p of a
+// stride-2 convolution).  s_b: [hi, lo][channel][pixel group (+ 1)].
 template <typename Shape, bool BSUM>
 __device__ __forceinline__ void conv1x1_wgrad_body(const Shape& s, u32x4 (&s_b)[2][CW1_B_ARR]) {
   const Conv1x1Wgrad& g = s.g;
@@ -187,9 +191,9 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const Shape& s, u32x4 (&s_b)[
   float hr[16];
   auto issue = [&](int t) {
     const int cam = t / g.tiles_img, p0 = (t - cam * g.tiles_img) * CW1_PX + 16 * s_q;
-    const float* src = from.base + ((size_t)cam * from.channels + from.local) * HW;
+    const float* src = from.base + ((size_t)cam * from.channels + from.local) * s.x_plane();
 #pragma unroll
-    for (int j = 0; j < 16; ++j) hr[j] = (s_ic_ok && p0 + j < g.hw) ? src[p0 + j] : 0.f;
+    for (int j = 0; j < 16; ++j) hr[j] = (s_ic_ok && p0 + j < g.hw) ? src[s.x_pixel(p0 + j)] : 0.f;
   };
   auto park = [&]() {
 #pragma unroll
@@ -272,5 +276,11 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const Shape& s, u32x4 (&s_b)[
     }
   }
 }
+
+// The finishing launch VoVNet's and ResNet's weight gradients share (gd4d_vovnet_train.hip: vt_wgrad_finish_kernel, a workgroup per
+// output channel): G = the partitions' slabs of ws (partitions, taps, cout, cin) added in order, dw[c] = scale[c] G[c], dbeta[c] = the
+// parts_b rows of ws_b added in order, dgamma[c] = rstd[c] (<weight[c], G[c]> - mean[c] dbeta[c]); bn = (3, cout): scale, rstd, mean.
+int vt_finish(const float* ws, const float* ws_b, int partitions, int parts_b, int cin, int cout, int taps, const float* weight,
+              const float* bn, float* dw, float* dgamma, float* dbeta, hipStream_t s);
 
 }  // namespace gd4d

@@ -43,6 +43,8 @@ struct LateralWgradShape {
   static constexpr int cout() { return FT_C; }
   __device__ __forceinline__ int oc0(int wave) const { return 64 * wave; }
   __device__ __forceinline__ Conv1x1Source source(int icg, bool ok) const { return {p.x, p.cin, ok ? icg : 0}; }
+  __device__ __forceinline__ size_t x_plane() const { return (size_t)g.hw; }
+  __device__ __forceinline__ int x_pixel(int px) const { return px; }
 };
 
 __global__ __launch_bounds__(CW1_THREADS) void fpn_lateral_wgrad_kernel(const LateralWgradParams p) {

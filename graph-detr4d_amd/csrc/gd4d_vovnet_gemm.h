@@ -8,8 +8,14 @@
 //            the output itself (an element is read before it is written, by the same thread).
 //   VV_RES   the ResNet blocks' (gd4d_resnet.hip): v = acc * scale[c] + shift[c]; v += identity[e] where there is one; max(v, 0) where
 //            relu is set; no pool sums.  BatchNorm, then the residual, then the ReLU: the block's own order.
+//            The ResNet blocks' adjoints (gd4d_resnet_train.hip) pass a fourth optional map, add_even, of HALF the output's
+//            resolution ((ho - 1) / 2 + 1 rows, (wo - 1) / 2 + 1 columns): add_even[y / 2, x / 2] is added where y and x are both even,
+//            after the mask - the gradient of a stride-2 downsample branch, which touches the even pixels only.
 // MODE VV_P2 is the pointwise convolution with stride 2 (a stage's downsample): an 8 x 16 tile of OUTPUT pixels whose B operand is the
 // 128 input pixels (2 y, 2 x), staged as VV_OSA stages its 128 consecutive ones; gd4d_resnet.hip alone instantiates it.
+// MODE VV_T2 is the adjoint of the 3x3 convolution with stride 2 (gd4d_resnet_train.hip alone instantiates it, with VV_BWD): VV_S1's
+// tile, halo and tap walk over the OUTPUT's (dx's) pixels, whose staged patch is the half-resolution source dz zero-interleaved -
+// halo pixel (y, x) is dz[y / 2, x / 2] where y and x are both even, else 0.  The full-resolution interleaved map exists in LDS only.
 #pragma once
 #include "gd4d_common.h"
 #include "gd4d_bf16x3.h"
@@ -19,7 +25,7 @@ namespace gd4d {
 
 constexpr int VV_THREADS = 256, VV_KC = 32, VV_TY = 8, VV_TX = 16, VV_PIX = VV_TY * VV_TX;
 constexpr int VV_MAX_SRC = 6;
-enum { VV_S1 = 0, VV_S2 = 1, VV_OSA = 2, VV_P2 = 3 };
+enum { VV_S1 = 0, VV_S2 = 1, VV_OSA = 2, VV_P2 = 3, VV_T2 = 4 };
 enum { VV_FWD = 0, VV_BWD = 1, VV_RES = 2 };
 
 template <int MODE> struct VvGeom;
@@ -27,6 +33,7 @@ template <> struct VvGeom<VV_S1> { static constexpr int TAPS = 9, STRIDE = 1, HE
 template <> struct VvGeom<VV_S2> { static constexpr int TAPS = 9, STRIDE = 2, HE_H = 2 * VV_TY + 1, HE_W = 2 * VV_TX + 1, HBUF = 1; };
 template <> struct VvGeom<VV_OSA> { static constexpr int TAPS = 1, STRIDE = 1, HE_H = 1, HE_W = VV_PIX, HBUF = 2; };
 template <> struct VvGeom<VV_P2> { static constexpr int TAPS = 1, STRIDE = 2, HE_H = 1, HE_W = VV_PIX, HBUF = 2; };
+template <> struct VvGeom<VV_T2> { static constexpr int TAPS = 9, STRIDE = 1, HE_H = VV_TY + 2, HE_W = VV_TX + 2, HBUF = 2; };
 
 template <int MODE> constexpr int vv_halo() { return VvGeom<MODE>::HE_H * VvGeom<MODE>::HE_W; }
 template <int MODE> constexpr int vv_h_stage() { return 2 * 4 * vv_halo<MODE>() * 16; }               // hi + lo planes of one chunk
@@ -84,6 +91,7 @@ struct VvParams {
   const float *add, *mask, *add2;  // VV_BWD: optional maps of the output's shape (appended: the forward's fields keep their offsets)
   const float* identity;          // VV_RES: an optional map of the output's shape, added before the ReLU
   int relu;                       // VV_RES: whether the ReLU runs
+  const float* add_even;          // VV_BWD: an optional map of half the output's resolution, added at the even pixels (appended)
 };
 
 template <int MT, int MODE, int EPI = VV_FWD>
@@ -107,7 +115,8 @@ __global__ __launch_bounds__(VV_THREADS) void vv_gemm_kernel(const VvParams p) {
   const int ty0 = MODE == VV_OSA ? 0 : (rt / p.tiles_x) * VV_TY;
   const int tx0 = MODE == VV_OSA ? rt * VV_PIX : (rt % p.tiles_x) * VV_TX;     // OSA: the first pixel of the flattened image
   const int H = p.h, W = p.w;
-  const size_t HW = (size_t)H * W;
+  const int HS = (H - 1) / 2 + 1, WS = (W - 1) / 2 + 1;      // VV_T2: the half-resolution source under an H x W output
+  const size_t HW = (size_t)H * W, SHW = MODE == VV_T2 ? (size_t)HS * WS : HW;   // the pixels of one source channel
   const int steps = p.chunks * TAPS;
   const char* const image = p.image + (size_t)tile_m * MT * steps * W_BLK + tid * 16;   // row block j: + j steps W_BLK
 
@@ -127,6 +136,10 @@ __global__ __launch_bounds__(VV_THREADS) void vv_gemm_kernel(const VvParams p) {
       const int y = 2 * (ty0 + hp / VV_TX), x = 2 * (tx0 + hp % VV_TX);
       h_in[ps] = it < H_ITEMS && y < H && x < W;
       h_off[ps] = h_in[ps] ? y * W + x : 0;
+    } else if (MODE == VV_T2) {                               // the zero-interleaved source: dz[y / 2, x / 2] at even (y, x), else 0
+      const int y = ty0 - 1 + hp / HE_W, x = tx0 - 1 + hp % HE_W;
+      h_in[ps] = it < H_ITEMS && y >= 0 && y < H && x >= 0 && x < W && !((y | x) & 1);
+      h_off[ps] = h_in[ps] ? (y >> 1) * WS + (x >> 1) : 0;
     } else {
       const int y = ty0 * S - 1 + hp / HE_W, x = tx0 * S - 1 + hp % HE_W;
       h_in[ps] = it < H_ITEMS && y >= 0 && y < H && x >= 0 && x < W;
@@ -146,11 +159,11 @@ __global__ __launch_bounds__(VV_THREADS) void vv_gemm_kernel(const VvParams p) {
           cs = p.src_ch[i];
         }
     }
-    const float* const cb = base + ((size_t)img * cs + (size_t)(chunk - c0) * VV_KC) * HW;
+    const float* const cb = base + ((size_t)img * cs + (size_t)(chunk - c0) * VV_KC) * SHW;
 #pragma unroll
     for (int ps = 0; ps < H_PASSES; ++ps)
 #pragma unroll
-      for (int j = 0; j < 8; ++j) hr[ps][j] = h_in[ps] ? cb[(size_t)(h_ch[ps] + j) * HW + h_off[ps]] : 0.f;
+      for (int j = 0; j < 8; ++j) hr[ps][j] = h_in[ps] ? cb[(size_t)(h_ch[ps] + j) * SHW + h_off[ps]] : 0.f;
   };
   auto park_halo = [&](int buf) {
     char* const base = hbuf + buf * H_STAGE;
@@ -232,30 +245,42 @@ __global__ __launch_bounds__(VV_THREADS) void vv_gemm_kernel(const VvParams p) {
   // C/D of 32x32x16: column (pixel) = l32, rows (channels) 4 kg + (r & 3) + 8 (r >> 2)
   bool ok;
   size_t off, plane;
+  [[maybe_unused]] int oy, ox;                               // the output pixel (VV_BWD's add_even asks for its parity)
   if (MODE == VV_OSA) {
     const size_t pix = (size_t)tx0 + pp;
     ok = pix < HW;
     off = ok ? pix : 0;
     plane = HW;
+    oy = (int)(off / (size_t)W);
+    ox = (int)(off - (size_t)oy * W);
   } else {
     const int y = ty0 + py, x = tx0 + px;
     ok = y < p.ho && x < p.wo;
     off = ok ? (size_t)y * p.wo + x : 0;
     plane = (size_t)p.ho * p.wo;
+    oy = y;
+    ox = x;
   }
   const int crow0 = tile_m * ROWS;
   if constexpr (EPI == VV_BWD) {
     if (!ok) return;
     const size_t o = ((size_t)img * p.cout + crow0) * plane + off;
+    // add_even: (N, cout, he, we) with he = (rows - 1) / 2 + 1; this lane's pixel takes part where both its coordinates are even
+    const int we = ((MODE == VV_OSA ? W : p.wo) - 1) / 2 + 1, he = ((MODE == VV_OSA ? H : p.ho) - 1) / 2 + 1;
+    const size_t plane_e = (size_t)he * we;
+    const bool even = p.add_even && !((oy | ox) & 1);
+    const size_t oe = ((size_t)img * p.cout + crow0) * plane_e + (size_t)(oy >> 1) * we + (ox >> 1);
 #pragma unroll
     for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const size_t e = o + (size_t)(32 * mi + 4 * kg + (r & 3) + 8 * (r >> 2)) * plane;
+        const int cl = 32 * mi + 4 * kg + (r & 3) + 8 * (r >> 2);
+        const size_t e = o + (size_t)cl * plane;
         float v = acc[mi][r];
         if (p.add) v = v + p.add[e];
         if (p.mask && !(p.mask[e] > 0.f)) v = 0.f;           // strict, as torch's ReLU
         if (p.add2) v = v + p.add2[e];
+        if (even) v = v + p.add_even[oe + (size_t)cl * plane_e];
         p.out[e] = v;
       }
     return;

@@ -163,6 +163,8 @@ struct OsaWgradShape {
       if (i < p.n_src && ok && icg >= p.src_c0[i]) s = {p.src[i], p.src_ch[i], icg - p.src_c0[i]};
     return s;
   }
+  __device__ __forceinline__ size_t x_plane() const { return (size_t)g.hw; }
+  __device__ __forceinline__ int x_pixel(int px) const { return px; }
 };
 
 __global__ __launch_bounds__(CW1_THREADS) void vt_osa_wgrad_kernel(const VvAggWgradParams p) {
@@ -312,7 +314,8 @@ extern "C" size_t gd4d_conv_wgrad_workspace_bytes(int cin, int cout, int taps, i
 }
 
 namespace gd4d {
-static int vt_finish(const float* ws, const float* ws_b, int partitions, int parts_b, int cin, int cout, int taps, const float* weight,
+// (not static: gd4d_resnet_train.hip finishes its weight gradients with it too; declared in gd4d_conv_wgrad.h)
+int vt_finish(const float* ws, const float* ws_b, int partitions, int parts_b, int cin, int cout, int taps, const float* weight,
                      const float* bn, float* dw, float* dgamma, float* dbeta, hipStream_t s) {
   VvFinishParams f{ws, ws_b, weight, bn, partitions, parts_b, cin, cout, taps, dw, dgamma, dbeta};
   hipLaunchKernelGGL(vt_wgrad_finish_kernel, dim3((unsigned)cout), dim3(256), 0, s, f);

@@ -3985,6 +3985,137 @@ def ese_bwd(dout, xt, partials, gate, fc_weight, want_fc=(True, True), outs=None
     return dz, sums, dfc_w, dfc_b
 
 
+# ---- ResNet, training behind frozen BatchNorms (gd4d_resnet_train.hip) ----------------------------------------------------------
+_CONV1X1_T_LIMITS = 'Cin and Cout multiples of 32 in [32, 2048]'
+
+
+def conv1x1_image_t(weight, scale=None):
+    """gd4d_conv1x1_image_t: the image conv1x1_dgrad reads, of the (Cout, Cin[, 1, 1]) fp32 weight times scale[co] (the folded
+    BatchNorm's; None: the weight as it is), transposed.  Cin and Cout multiples of 32 in [32, 2048]."""
+    if weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1):
+        weight = weight.reshape(weight.shape[0], weight.shape[1])
+    if weight.dim() != 2:
+        raise _lib.Gd4dError(f'conv1x1_image_t: weight {tuple(weight.shape)}; the kernel takes (Cout, Cin) or (Cout, Cin, 1, 1)')
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    if scale is not None:
+        weight = weight * scale.view(-1, 1)
+    return _weight_image('gd4d_conv1x1_image_t', int(_lib.load().gd4d_conv1x1_image_t_bytes(cin, cout)),
+                         f'conv1x1_image_t: weight {tuple(weight.shape)}; the kernel takes {_CONV1X1_T_LIMITS}', weight, cin, cout)
+
+
+def conv3x3_act_image_t(weight, scale=None):
+    """gd4d_conv3x3_act_image_t: conv3x3_image_t for conv3x3_act_dgrad, whose Cout reaches 512 (limits as conv3x3_act_image)."""
+    if scale is not None:
+        weight = weight * scale.view(-1, 1, 1, 1)
+    return _conv3x3_weight_image('conv3x3_act_image_t', 'gd4d_conv3x3_act_image_t', weight, 'the kernel takes', _CONV3X3_ACT_LIMITS)
+
+
+def relu_mask_bwd(dout, out_map, out=None):
+    """gd4d_relu_mask_bwd: dout where out_map > 0, else 0 (a ReLU's backward on its stored output); `out` may be dout."""
+    if dout.shape != out_map.shape:
+        raise ValueError(f'relu_mask_bwd: dout {tuple(dout.shape)} and the map {tuple(out_map.shape)} must have one shape')
+    g = _out(out, dout.shape, dout.device, 'relu_mask_bwd: out')
+    _call('gd4d_relu_mask_bwd', _dev(dout, 'dout', F32), _dev(out_map, 'out_map', F32), dout.numel(), _dev(g, 'out', F32))
+    return g
+
+
+def even_pixels_scatter(src, hw, out=None):
+    """gd4d_even_pixels_scatter: src (N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1) -> (N, C, H, W) with src[y / 2, x / 2] at the even
+    (y, x) and zeros elsewhere: the adjoint of x[:, :, ::2, ::2]."""
+    n, c, hs, ws = _dcn_x(src, 'even_pixels_scatter')
+    h, w = int(hw[0]), int(hw[1])
+    if dcn_out_hw(h, w, 2) != (hs, ws):
+        raise ValueError(f'even_pixels_scatter: src {tuple(src.shape)} is not half of ({h}, {w})')
+    out = _out(out, (n, c, h, w), src.device, 'even_pixels_scatter: out')
+    _call('gd4d_even_pixels_scatter', _dev(src, 'src', F32), n * c, h, w, _dev(out, 'out', F32))
+    return out
+
+
+def _rt_dgrad(name, taps, dz, image_t, cin, hw, stride, add, mask, add2, add_even, out, m_blocks):
+    lib = _lib.load()
+    n, cout, hz, wz = _dcn_x(dz, name)
+    cin, stride = int(cin), int(stride)
+    h, w = (hz, wz) if hw is None else (int(hw[0]), int(hw[1]))
+    if dcn_out_hw(h, w, stride) != (hz, wz):
+        raise ValueError(f'{name}: dz {tuple(dz.shape)} is not the stride-{stride} output of an ({h}, {w}) map (hw= says which)')
+    nbytes = int((lib.gd4d_conv3x3_act_image_t_bytes if taps == 9 else lib.gd4d_conv1x1_image_t_bytes)(cin, cout))
+    if nbytes == 0 or nbytes != image_t.numel():
+        made, limits = ('conv3x3_act_image_t', _CONV3X3_ACT_LIMITS) if taps == 9 else ('conv1x1_image_t', _CONV1X1_T_LIMITS)
+        raise _lib.Gd4dError(f'{name}: the image is not {made} of a ({cout}, {cin}) weight the kernel takes ({limits})')
+    for t, what in ((add, 'add'), (mask, 'mask'), (add2, 'add2')):
+        if t is not None and tuple(t.shape) != (n, cin, h, w):
+            raise ValueError(f'{name}: {what} must be ({n}, {cin}, {h}, {w}), got {tuple(t.shape)}')
+    if add_even is not None and tuple(add_even.shape) != (n, cin) + dcn_out_hw(h, w, 2):
+        raise ValueError(f'{name}: add_even must be {(n, cin) + dcn_out_hw(h, w, 2)}, got {tuple(add_even.shape)}')
+    out = _out(out, (n, cin, h, w), dz.device, f'{name}: out')
+    args = (_dev(image_t, 'image_t', U8), _opt(add, 'add'), _opt(mask, 'mask'), _opt(add2, 'add2'), _opt(add_even, 'add_even'),
+            _dev(out, 'out', F32), int(m_blocks))
+    if taps == 9:
+        _call('gd4d_conv3x3_act_dgrad', _dev(dz, 'dz', F32), n, cin, cout, h, w, stride, *args)
+    else:
+        _call('gd4d_conv1x1_dgrad', _dev(dz, 'dz', F32), n, cin, cout, h, w, *args)
+    return out
+
+
+def conv1x1_dgrad(dz, image_t, cin, add=None, mask=None, add2=None, add_even=None, out=None, m_blocks=0):
+    """gd4d_conv1x1_dgrad: dz (N, Cout, H, W) fp32 -> ((s W)^T dz (+ add)) ([mask > 0]) (+ add2) (+ add_even), (N, cin, H, W): a 1x1
+    convolution's input gradient with image_t = conv1x1_image_t(weight, scale).  add / mask / add2: optional maps of the result's shape
+    (out may be add or add2); add_even: an optional map of half its resolution, added at the pixels whose row and column are both
+    even (a stride-2 downsample's gradient: that branch's own adjoint is this call on its half-resolution dz).  m_blocks: as
+    conv3x3_bn_relu's, dividing cin / 32; the same bits either way."""
+    return _rt_dgrad('conv1x1_dgrad', 1, dz, image_t, cin, None, 1, add, mask, add2, add_even, out, m_blocks)
+
+
+def conv3x3_act_dgrad(dz, image_t, cin, hw=None, stride=1, add=None, mask=None, add2=None, add_even=None, out=None, m_blocks=0):
+    """gd4d_conv3x3_act_dgrad: conv1x1_dgrad's counterpart for the 3x3 (pad 1) of stride 1 or 2 with image_t =
+    conv3x3_act_image_t(weight, scale); hw = the result's (H, W), needed at stride 2 (dz is its stride-2 output's size)."""
+    return _rt_dgrad('conv3x3_act_dgrad', 9, dz, image_t, cin, hw, stride, add, mask, add2, add_even, out, m_blocks)
+
+
+def _rt_wgrad(name, taps, dz, x, weight, bn, stride, want, partitions, outs, workspace):
+    lib = _lib.load()
+    n, cout, hz, wz = _dcn_x(dz, name)
+    stride = int(stride)
+    if x.dim() != 4 or int(x.shape[0]) != n or dcn_out_hw(x.shape[2], x.shape[3], stride) != (hz, wz):
+        raise ValueError(f'{name}: x {tuple(x.shape)} for dz {tuple(dz.shape)} at stride {stride}')
+    cin, h, w = int(x.shape[1]), int(x.shape[2]), int(x.shape[3])
+    if tuple(bn.shape) != (3, cout):
+        raise ValueError(f'{name}: bn must be (3, {cout}): scale, rstd, mean')
+    if weight.numel() != cout * cin * taps or int(weight.shape[0]) != cout:
+        raise ValueError(f'{name}: weight of {cout} x {cin} x {taps} values expected, got {tuple(weight.shape)}')
+    if not any(want):
+        raise ValueError(f'{name}: nothing asked for')
+    work = cin // 32 * -(-cout // 256) if taps == 9 else -(-cin // 64) * -(-cout // 256)
+    partitions = _vv_partitions(dz.device, int(lib.gd4d_resnet_wgrad_tiles(taps, n, h, w, stride)), work, partitions)
+    nbytes = int(lib.gd4d_resnet_wgrad_workspace_bytes(taps, cin, cout, n, h, w, stride, partitions))
+    if nbytes == 0:
+        raise _lib.Gd4dError(f'{name}: {cin} -> {cout} channels, stride {stride}, partitions = {partitions}: the kernel takes '
+                             f'{_CONV3X3_ACT_LIMITS if taps == 9 else _CONV1X1_T_LIMITS}, stride 1 or 2 and 1..4096 partitions')
+    dev = dz.device
+    o_dw, o_dgamma, o_dbeta = outs if outs is not None else (None, None, None)
+    ws = _out(workspace, (nbytes // 4,), dev, f'{name}: workspace')
+    dw = _out(o_dw, weight.shape, dev, f'{name}: dW') if want[0] else None
+    dgamma = _out(o_dgamma, (cout,), dev, f'{name}: dgamma') if want[1] else None
+    dbeta = _out(o_dbeta, (cout,), dev, f'{name}: dbeta') if want[2] else None
+    _call('gd4d_conv3x3_act_wgrad' if taps == 9 else 'gd4d_conv1x1_wgrad', _dev(dz, 'dz', F32), _dev(x, 'x', F32), n, cin, cout, h, w,
+          stride, partitions, _dev(ws, 'workspace', F32), _dev(weight, 'weight', F32), _dev(bn, 'bn', F32), _opt(dw, 'dw'),
+          _opt(dgamma, 'dgamma'), _opt(dbeta, 'dbeta'))
+    return dw, dgamma, dbeta
+
+
+def conv1x1_wgrad(dz, x, weight, bn, stride=1, want=(True, True, True), partitions=None, outs=None, workspace=None):
+    """gd4d_conv1x1_wgrad: conv3x3_wgrad's counterpart for a ResNet block's 1x1 convolution of stride 1 or 2: dz (N, Cout, Ho, Wo), x
+    (N, Cin, H, W) read in place at the pixels (stride yo, stride xo), weight (Cout, Cin[, 1, 1]) unscaled, bn (3, Cout).  Returns
+    (dW of weight's shape, dgamma, dbeta), None where `want` says so; outs / workspace as conv3x3_wgrad's."""
+    return _rt_wgrad('conv1x1_wgrad', 1, dz, x, weight, bn, stride, want, partitions, outs, workspace)
+
+
+def conv3x3_act_wgrad(dz, x, weight, bn, stride=1, want=(True, True, True), partitions=None, outs=None, workspace=None):
+    """gd4d_conv3x3_act_wgrad: conv3x3_wgrad at ResNet's widths (Cout up to 512) and strides (1 or 2: dz is the stride's output size;
+    at stride 2 the workspace also holds dz zero-interleaved to x's resolution)."""
+    return _rt_wgrad('conv3x3_act_wgrad', 9, dz, x, weight, bn, stride, want, partitions, outs, workspace)
+
+
 def _first_tensor(args):
     for a in args:
         if torch.is_tensor(a):

@@ -1844,6 +1844,44 @@ size_t gd4d_ese_bwd_workspace_bytes(int n, int channels);
 int gd4d_ese_bwd(const float* dout, const float* xt, const float* partials, int tiles, const float* gate, const float* fc_w, int n,
                  int channels, int hw, float* workspace, float* dz, float* dz_sums, float* dfc_w, float* dfc_b, void* stream);
 
+/* ResNet, training of the blocks' plain convolutions behind frozen BatchNorms (gd4d_resnet_train.hip has the arithmetic; additive exports,
+ * the ABI version stays).  Conventions as the VoVNet training entry points': maps contiguous NCHW fp32, dz the gradient of a BatchNorm's
+ * OUTPUT after the ReLU mask (unscaled), bn (3, cout) = scale, rstd, mean; fixed summation order, no atomics: two runs give the same bits.
+ * gd4d_conv1x1_image_t / gd4d_conv3x3_act_image_t - the data gradients' images: the weight ALREADY times scale[co], read transposed, the
+ *   3x3's taps flipped.  1x1: cin and cout multiples of 32 in [32, 2048]; 3x3: cin in [32, 1024], cout in [32, 512].  *_bytes: the image's
+ *   size, 0 outside the limits; 16-B aligned.
+ * gd4d_relu_mask_bwd - g[i] = out[i] > 0 ? dout[i] : 0 for count elements.
+ * gd4d_even_pixels_scatter - dst (planes, h, w) = src (planes, (h - 1) / 2 + 1, (w - 1) / 2 + 1) at [y / 2, x / 2] where y and x are both
+ *   even, else 0.
+ * gd4d_conv1x1_dgrad - dx (N, cin, h, w) = ((s W)^T dz (N, cout, h, w) (+ add)) ([mask > 0]) (+ add2) (+ add_even); add, mask, add2 optional
+ *   maps of dx's shape (add and add2 may be dx); add_even an optional map (N, cin, (h - 1) / 2 + 1, (w - 1) / 2 + 1), added to dx[y, x] as
+ *   add_even[y / 2, x / 2] where y and x are both even (a stride-2 downsample's gradient).  m_blocks as the forward's, dividing cin / 32.
+ * gd4d_conv3x3_act_dgrad - the same for the 3x3 (pad 1) of stride 1 or 2; h, w are dx's, dz is (N, cout, (h - 1) / stride + 1, (w - 1) /
+ *   stride + 1).
+ * gd4d_conv1x1_wgrad / gd4d_conv3x3_act_wgrad - dw = scale (x) G, dbeta, dgamma as gd4d_conv3x3_wgrad's, G over the convolution of stride 1
+ *   or 2 from x (N, cin, h, w) to dz's resolution; each of dw, dgamma, dbeta may be NULL, not all three; weight UNSCALED.  partitions
+ *   (1 .. 4096) of the gd4d_resnet_wgrad_tiles(taps, n, h, w, stride) tiles (3x3: 16 x 16 input pixels, 1x1: 64 output pixels); workspace
+ *   gd4d_resnet_wgrad_workspace_bytes(taps, cin, cout, n, h, w, stride, partitions) bytes, 16-B aligned (the 3x3 of stride 2 keeps dz
+ *   zero-interleaved to the input's resolution there).
+ * Errors: NULL required pointer GD4D_EINVAL; sizes, stride, m_blocks or partitions outside the limits GD4D_EUNSUPPORTED (0 bytes / 0 tiles
+ *   from the size queries); a misaligned image or workspace GD4D_EALIGN. */
+size_t gd4d_conv1x1_image_t_bytes(int cin, int cout);
+int gd4d_conv1x1_image_t(const float* weight, int cin, int cout, void* image, void* stream);
+size_t gd4d_conv3x3_act_image_t_bytes(int cin, int cout);
+int gd4d_conv3x3_act_image_t(const float* weight, int cin, int cout, void* image, void* stream);
+int gd4d_relu_mask_bwd(const float* dout, const float* out, long long count, float* g, void* stream);
+int gd4d_even_pixels_scatter(const float* src, long long planes, int h, int w, float* dst, void* stream);
+int gd4d_conv1x1_dgrad(const float* dz, int n, int cin, int cout, int h, int w, const void* image_t, const float* add, const float* mask,
+                       const float* add2, const float* add_even, float* dx, int m_blocks, void* stream);
+int gd4d_conv3x3_act_dgrad(const float* dz, int n, int cin, int cout, int h, int w, int stride, const void* image_t, const float* add,
+                           const float* mask, const float* add2, const float* add_even, float* dx, int m_blocks, void* stream);
+long long gd4d_resnet_wgrad_tiles(int taps, int n, int h, int w, int stride);
+size_t gd4d_resnet_wgrad_workspace_bytes(int taps, int cin, int cout, int n, int h, int w, int stride, int partitions);
+int gd4d_conv1x1_wgrad(const float* dz, const float* x, int n, int cin, int cout, int h, int w, int stride, int partitions,
+                       float* workspace, const float* weight, const float* bn, float* dw, float* dgamma, float* dbeta, void* stream);
+int gd4d_conv3x3_act_wgrad(const float* dz, const float* x, int n, int cin, int cout, int h, int w, int stride, int partitions,
+                           float* workspace, const float* weight, const float* bn, float* dw, float* dgamma, float* dbeta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@ least --window-ms; the two routes' windows alternate, and the figure is the medi
 `graph_*`: the whole forward captured once per route and replayed in the same windows.  `tflop` counts 2 K Cout per output pixel over
 the piece's convolutions (a DCN conv2 as its plain 3x3 plus conv_offset).  `rel_err` is the largest difference of the two routes'
 outputs over the largest entry, at the timed size.
+
+    python tools/bench_resnet.py --train [--nets ...] [--cams 6,24] ...     one training step (forward + backward) instead: bench_train
 """
 import argparse
 import json
@@ -138,6 +140,79 @@ def bench(name, nets, cams, hw, reps, window_ms, dev='cuda'):
     return out
 
 
+def make_train_nets(name, seed, dev):
+    """make_nets' two networks as the configs train them: frozen_stages=1, norm_eval=True, frozen BatchNorm parameters, train() mode;
+    'kernels' with plain_train=True.  hip_train=True on the DCN layers of BOTH (the default route's stock layers around the DCN's own
+    training kernels is what the same commit offers without the switch)."""
+    kw = dict(NETS[name], norm_cfg=dict(type='BN', requires_grad=False), norm_eval=True, frozen_stages=1)
+    hip = 'dcn' in kw
+    eval_nets = make_nets(name, seed, 'cpu')
+    nets = {'kernels': G.ResNet(plain_kernels=True, plain_train=True, hip_train=hip, **kw), 'stock': G.ResNet(hip_train=hip, **kw)}
+    for r, net in nets.items():
+        net.load_state_dict(eval_nets['kernels'].state_dict(), strict=True)
+        nets[r] = net.to(dev).train()
+    return nets
+
+
+def kernel_times(fn):
+    """{kernel name: (calls, total ms)} of one call of fn, the library's GEMM, weight-gradient and elementwise kernels only, by
+    torch.profiler; {} with the reason under 'error' where the profiler is not available."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        rows = {}
+        for e in prof.key_averages():
+            total = getattr(e, 'device_time_total', None)
+            total = getattr(e, 'cuda_time_total', 0.0) if total is None else total
+            if any(t in e.key for t in ('gd4d', 'vv_gemm', 'rt_', 'vt_', 'dcn_')) and total > 0:
+                rows[e.key[:160]] = [int(e.count), total / 1e3]
+        return rows
+    except Exception as exc:                                                    # noqa: BLE001  (a tool: report, do not die)
+        return {'error': repr(exc)}
+
+
+def bench_train(name, nets, cams, hw, reps, window_ms, dev='cuda'):
+    """Forward + backward of the backbone (the images need no gradient, layer1 and the stem are frozen) with a fixed cotangent on the
+    outputs of layer2 .. layer4: plain_train=True beside the default route's stock torch layers, alternating windows.  Per route the
+    median ms per step, the peak allocated memory of one step above what is allocated between steps, and the HIP route's kernels."""
+    x = torch.randn(cams, 3, *hw, device=dev, generator=torch.Generator(dev).manual_seed(cams))
+    with torch.no_grad():
+        couts = [torch.randn(o.shape, device=dev, generator=torch.Generator(dev).manual_seed(i)) for i, o in enumerate(nets['stock'](x))]
+
+    def step(net):
+        def f():
+            net.zero_grad(set_to_none=True)
+            outs = net(x)
+            torch.autograd.backward(outs[1:], couts[1:])
+        return f
+    fns = {r: step(nets[r]) for r in ROUTES}
+    out = {'net': name, 'cams': cams, 'hw': list(hw), 'mode': 'train'}
+    for r, (ms, calls, spread) in windows(fns, reps, window_ms).items():
+        out[f'{r}_ms'], out[f'{r}_calls_per_window'], out[f'{r}_spread'] = ms, calls, spread
+    out['kernels_over_stock'] = out['kernels_ms'] / out['stock_ms']
+    grads = {}
+    for r, f in fns.items():
+        f()
+        grads[r] = {k: p.grad.clone() for k, p in nets[r].named_parameters() if p.grad is not None}
+        nets[r].zero_grad(set_to_none=True)
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        f()
+        torch.cuda.synchronize()
+        out[f'{r}_peak_mb'] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+    assert set(grads['kernels']) == set(grads['stock'])
+    out['grad_rel_err_max'] = max(float((grads['kernels'][k] - v).abs().max() / v.abs().max().clamp(min=1e-30)) for k, v in grads['stock'].items())
+    out['kernels_host_enqueue_ms'] = host_enqueue_ms(fns['kernels'], reps)
+    out['stock_host_enqueue_ms'] = host_enqueue_ms(fns['stock'], reps)
+    out['kernel_times_ms'] = kernel_times(fns['kernels'])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--nets', default='r50_dcn,r50,r18')
@@ -145,13 +220,19 @@ def main():
     ap.add_argument('--hw', type=int, nargs=2, default=(320, 800))
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--window-ms', type=float, default=200.0)
+    ap.add_argument('--train', action='store_true', help='time one training step: plain_train=True beside the default route')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_resnet.py needs a GPU: a CPU timing says nothing about the kernels')
     runs = []
     for name in args.nets.split(','):
-        nets = make_nets(name, 0, 'cuda')
+        nets = make_train_nets(name, 0, 'cuda') if args.train else make_nets(name, 0, 'cuda')
         for c in args.cams.split(','):
+            if args.train:
+                runs.append(bench_train(name, nets, int(c), tuple(args.hw), args.reps, args.window_ms))
+                print(f'{name} at {c} cameras, one training step: kernels {runs[-1]["kernels_ms"]:.2f} ms, stock {runs[-1]["stock_ms"]:.2f} ms',
+                      file=sys.stderr)
+                continue
             runs.append(bench(name, nets, int(c), tuple(args.hw), args.reps, args.window_ms))
             print(f'{name} at {c} cameras: kernels {runs[-1]["total_kernels_ms"]:.2f} ms, stock {runs[-1]["total_stock_ms"]:.2f} ms', file=sys.stderr)
         del nets
