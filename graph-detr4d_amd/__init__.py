@@ -6,8 +6,8 @@ when mmcv/mmdet are importable, in their real registries.
 """
 __version__ = '0.1.0'
 
-from .registry import (ATTENTION, BACKBONES, BBOX_ASSIGNERS, BBOX_CODERS, CONV_LAYERS, HEADS, NECKS, TRANSFORMER, TRANSFORMER_LAYER, TRANSFORMER_LAYER_SEQUENCE,  # noqa: F401
-                       build_assigner, build_attention, build_backbone, build_bbox_coder, build_conv_layer, build_head, build_neck, build_transformer, build_transformer_layer,
+from .registry import (ATTENTION, BACKBONES, BBOX_ASSIGNERS, BBOX_CODERS, CONV_LAYERS, HEADS, LOSSES, NECKS, TRANSFORMER, TRANSFORMER_LAYER, TRANSFORMER_LAYER_SEQUENCE,  # noqa: F401
+                       build_assigner, build_attention, build_backbone, build_bbox_coder, build_conv_layer, build_head, build_loss, build_neck, build_transformer, build_transformer_layer,
                        build_transformer_layer_sequence)
 from .transformer_layers import (FFN, BaseTransformerLayer, DetrTransformerDecoderLayer,  # noqa: F401
                                  MultiheadAttention, TransformerLayerSequence)
@@ -29,7 +29,7 @@ from .detr3d_transformer import (Detr3DCrossAtten, Detr3DCrossAttenV2, Detr3DTra
                                  HDetr3DTransformer, feature_sampling, inverse_sigmoid)
 from .petr_transformer import (PETRMultiheadAttention, PETRTransformer, PETRTransformerDecoder,  # noqa: F401
                                PETRTransformerDecoderLayer, PETRTransformerEncoder)
-from .petr_head import PETRHead, PETRv2Head  # noqa: F401
+from .petr_head import PETRHead, PETRHeadseg, PETRv2Head, Sigmoid_ce_loss  # noqa: F401
 
 __all__ = ['Deform3DCrossAttn', 'Deform3DCrossAttnMP', 'DGCNNAttn', 'Detr3DCrossAtten', 'Detr3DCrossAttenV2', 'feature_sampling', 'Detr3DTransformer',
            'Detr3DTransformerDecoder', 'HDetr3DTransformer', 'MultiheadAttention', 'FFN', 'BaseTransformerLayer',
@@ -37,4 +37,4 @@ __all__ = ['Deform3DCrossAttn', 'Deform3DCrossAttnMP', 'DGCNNAttn', 'Detr3DCross
            'NMSFreeCoder', 'HungarianAssigner3D', 'Detr3DCriterion', 'HDetr3DCriterion', 'DistillHungarianAssigner3D', 'get_instance_distill_loss', 'FeatureDistillLoss', 'get_feat_distill_loss', 'FeaturePositionEmbedding', 'DepthNet', 'TrainRecipe', 'GridMask', 'FPN', 'CPFPN', 'NECKS', 'build_neck', 'ModulatedDeformConv2d', 'ModulatedDeformConv2dPack', 'CONV_LAYERS', 'build_conv_layer',
            'BasicBlock', 'Bottleneck', 'ResNet', 'VoVNet', 'VoVNetCP', 'BACKBONES', 'build_backbone', 'BBOX_CODERS', 'BBOX_ASSIGNERS', 'ATTENTION', 'TRANSFORMER', 'TRANSFORMER_LAYER', 'TRANSFORMER_LAYER_SEQUENCE',
            'PETRMultiheadAttention', 'PETRTransformer', 'PETRTransformerDecoder', 'PETRTransformerDecoderLayer', 'PETRTransformerEncoder',
-           'PETRHead', 'PETRv2Head', 'HEADS', 'build_head']
+           'PETRHead', 'PETRv2Head', 'HEADS', 'build_head', 'PETRHeadseg', 'Sigmoid_ce_loss', 'LOSSES', 'build_loss']

@@ -258,6 +258,9 @@ SIGNATURES = {
     'gd4d_resnet_wgrad_workspace_bytes': (_c.c_size_t, [_i] * 8),
     'gd4d_conv1x1_wgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gd4d_conv3x3_act_wgrad': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd4d_lane_mask_loss_workspace_bytes': (_c.c_size_t, [_i, _i, _i]),
+    'gd4d_lane_mask_loss': (_i, [_vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp, _c.c_size_t, _vp]),
+    'gd4d_lane_map_fwd': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -799,3 +799,27 @@ class PetrKeysFunction(torch.autograd.Function):
             dfeat = ops.fpn_lateral_dgrad(dx, geom['ip_image_t'](), feat4.shape[1]).view(bs, n, -1, h, w)
         shaped = [o.view(sh) if o is not None and nd else None for o, sh, nd in zip(out, ctx.param_shapes, need)]
         return (dfeat, None, *shaped)
+
+
+class LaneMaskLossFunction(torch.autograd.Function):
+    """Sigmoid_ce_loss (losses/Sigmoid_ce_loss.py:39-43) of every decoder layer as ONE autograd node: logits (L, R, C), targets (R, C)
+    shared by the layers -> loss (L,), each through the nan_to_num of petr_head_seg.py:785.  gd4d_lane_mask_loss writes the loss and
+    d loss[l] / d logits[l] together; the backward scales that buffer IN PLACE by the incoming gradient of loss[l] - so it is consumed
+    by the first backward - and the targets get no gradient.  A layer whose loss was not finite has an all-zero gradient
+    (ops.lane_mask_loss states this deviation from torch)."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, loss_weight):
+        loss, dlogits = ops.lane_mask_loss(logits.detach().contiguous(), targets.detach().contiguous(), loss_weight)
+        ctx.dlogits = dlogits
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        if ctx.dlogits is None:
+            raise RuntimeError('Sigmoid_ce_loss: the gradient buffer was consumed by the first backward (retain_graph / double backward '
+                               'are not supported on the HIP path; torch_ops=True runs the torch-op route)')
+        d, ctx.dlogits = ctx.dlogits, None
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return d.mul_(grad_loss.view(-1, 1, 1)), None, None

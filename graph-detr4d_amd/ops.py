@@ -1814,6 +1814,57 @@ def distill_loss_fwd_bwd(s_cls, s_box, t_cls, t_box, assigned, code_weights, avg
     return loss, gcls, gbox
 
 
+def lane_mask_loss(logits, targets, loss_weight, outs=None, workspace=None):
+    """gd4d_lane_mask_loss: Sigmoid_ce_loss (losses/Sigmoid_ce_loss.py:39-43) of every decoder layer at once, forward and gradient.
+    logits (L, R, C), targets (R, C) shared by the layers -> (loss (L,), dlogits (L, R, C)) with dlogits[l] = d loss[l] / d logits[l];
+    loss[l] is already through the nan_to_num of petr_head_seg.py:785.
+
+    Deviation from torch: a layer whose loss is not finite before the nan_to_num (a NaN or infinite logit) gets the nan_to_num value and
+    an ALL-ZERO gradient; torch's backward leaves a NaN at the offending logit.  The other layers are unaffected bit for bit.
+    outs = (loss, dlogits) and workspace (uint8, at least gd4d_lane_mask_loss_workspace_bytes) may be the caller's."""
+    if logits.dim() != 3 or tuple(targets.shape) != tuple(logits.shape[1:]) or logits.numel() == 0:
+        raise ValueError(f'lane_mask_loss: logits (L, R, C) and targets (R, C) expected, got {tuple(logits.shape)} and {tuple(targets.shape)}')
+    nl, r, c = (int(s) for s in logits.shape)
+    lp, tp = _dev(logits, 'logits', F32), _dev(targets, 'targets', F32)
+    need = int(_lib.load().gd4d_lane_mask_loss_workspace_bytes(nl, r, c))
+    if need == 0:
+        raise _lib.Gd4dError(f'lane_mask_loss: {nl} layers of {r} x {c} are outside the kernel\'s limits (65535 layers, 2^40 elements)')
+    loss, dlogits = outs if outs is not None else (None, None)
+    loss = _out(loss, (nl,), logits.device, 'outs[0]')
+    dlogits = _out(dlogits, (nl, r, c), logits.device, 'outs[1]')
+    if workspace is None:
+        workspace = torch.empty(need, device=logits.device, dtype=U8)
+    elif workspace.numel() < need:
+        raise ValueError(f'lane_mask_loss: workspace of at least {need} bytes expected, got {workspace.numel()}')
+    _call('gd4d_lane_mask_loss', lp, tp, float(loss_weight), nl, r, c, _dev(loss, 'outs[0]', F32), _dev(dlogits, 'outs[1]', F32),
+          _dev(workspace, 'workspace', U8), workspace.numel())
+    return loss, dlogits
+
+
+def lane_map_fwd(logits, gt_map=None, outs=None):
+    """gd4d_lane_map_fwd: the map decode of Petr3D_seg.simple_test_pts (detectors/petr3d_seg.py:228-246) in one launch.  logits
+    (B, g g, 768) -> prob (B, 3, 16 g, 16 g) = fp32 1 / (1 + exp(-x)) at '(h w) c h1 w2 -> c (h h1) (w w2)' and binary = prob >= 0.5 as
+    fp32 0 / 1; with gt_map (B, 3, 16 g, 16 g) also sums (B, 3, 3) = sum(binary gt), sum(binary), sum(gt) per class and iou (B, 3) =
+    (2 inter + 0.01) / (sum(binary) + sum(gt) + 0.01).  Returns (prob, binary) or (prob, binary, sums, iou); outs may hold the
+    caller's tensors in that order."""
+    g = int(round(logits.shape[1] ** 0.5)) if logits.dim() == 3 else 0
+    if logits.dim() != 3 or logits.shape[0] < 1 or g < 1 or g * g != logits.shape[1] or logits.shape[2] != 768:
+        raise ValueError(f'lane_map_fwd: logits (B, g g, 768) expected, got {tuple(logits.shape)}')
+    b, shape = int(logits.shape[0]), (int(logits.shape[0]), 3, 16 * g, 16 * g)
+    if gt_map is not None and tuple(gt_map.shape) != shape:
+        raise ValueError(f'lane_map_fwd: gt_map must be {shape}, got {tuple(gt_map.shape)}')
+    lp, gp = _dev(logits, 'logits', F32), _opt(gt_map, 'gt_map')
+    outs = tuple(outs) if outs is not None else ()
+    outs += (None,) * (4 - len(outs))
+    prob, binary = _out(outs[0], shape, logits.device, 'outs[0]'), _out(outs[1], shape, logits.device, 'outs[1]')
+    sums = iou = None
+    if gt_map is not None:
+        sums, iou = _out(outs[2], (b, 3, 3), logits.device, 'outs[2]'), _out(outs[3], (b, 3), logits.device, 'outs[3]')
+    _call('gd4d_lane_map_fwd', lp, gp, b, g, _dev(prob, 'outs[0]', F32), _dev(binary, 'outs[1]', F32), _opt(sums, 'outs[2]'),
+          _opt(iou, 'outs[3]'))
+    return (prob, binary) if gt_map is None else (prob, binary, sums, iou)
+
+
 def _feat_distill_levels(levels, name, like=None):
     """The per-level arguments of the feature-distillation entry points: fp32 (R, 256, H_l, W_l) maps with one R -> (pointer array,
     level_hw array, R)."""

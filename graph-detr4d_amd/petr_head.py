@@ -21,6 +21,10 @@ PETRMultiheadAttention below the head gets hip_train = True.  Eval mode without 
 torch_ops=True: the reference's op sequence on torch, differentiable - what training takes without hip_train; it wins over
 hip_train.  What the kernels do not cover is refused in the name of that switch, at construction where the cause is known there;
 never a silent fallback.
+
+PETRHeadseg (dense_heads/petr_head_seg.py, the head of petrv2_BEVseg.py) is the same base class plus a lane half: a second
+PETRTransformer over the SAME key rows, one shared lane_branches MLP, Sigmoid_ce_loss on gd4d_lane_mask_loss and the map decode on
+gd4d_lane_map_fwd (csrc/gd4d_lane_head.hip).  The base class's routes are split into "keys" and "the rest" for it.
 """
 import copy
 import math
@@ -34,7 +38,7 @@ from . import functional as Fn
 from . import ops
 from ._lib import Gd4dError
 from .head_pe import FeaturePositionEmbedding, SELayer
-from .registry import HEADS, build_bbox_coder, build_transformer
+from .registry import HEADS, LOSSES, build_bbox_coder, build_loss, build_transformer
 
 
 def pos2posemb3d(pos, num_pos_feats=128, temperature=10000):
@@ -130,6 +134,7 @@ class _PETRHeadBase(nn.Module):
     RegLayer and whether the six levels share one branch object."""
     _version = 2
     _share_branches = True
+    _gate_name = 'fpe'                                        # the attribute (and state-dict prefix) of the with_fpe SE gate
 
     def __init__(self, num_classes, in_channels, num_query=100, num_reg_fcs=2, transformer=None, sync_cls_avg_factor=False,
                  positional_encoding=dict(type='SinePositionalEncoding', num_feats=128, normalize=True), code_weights=None,
@@ -226,7 +231,7 @@ class _PETRHeadBase(nn.Module):
         self.reference_points = nn.Embedding(self.num_query, 3)
         self.query_embedding = nn.Sequential(nn.Linear(c * 3 // 2, c), nn.ReLU(), nn.Linear(c, c))
         if self.with_fpe:
-            self.fpe = SELayer(c)
+            setattr(self, self._gate_name, SELayer(c))
         self._kept = {}                                       # name -> (stamp, value): images, input_proj's, the query embedding
         self.__dict__['_pe'] = None                           # FeaturePositionEmbedding's masks / sine pieces over THIS head's modules
         self.__dict__['_xs'] = None                           # (masks, the (R, S, 384) sine expansion): a function of the masks alone
@@ -292,6 +297,9 @@ class _PETRHeadBase(nn.Module):
             self.__dict__['_pe'] = pe
         return pe
 
+    def _gate(self):
+        return getattr(self, self._gate_name)
+
     def _input_proj_image(self):
         conv = self.input_proj
         return self._keep('input_proj', [conv.weight], lambda: (ops.conv1x1_image(conv.weight.detach()),
@@ -311,7 +319,7 @@ class _PETRHeadBase(nn.Module):
         img = {'pe': self._keep('pe_image', [pe0.weight, pe0.bias, pe2.weight],
                                 lambda: ops.mlp2_frustum_image(flat(pe0), pe0.bias.detach(), flat(pe2))), 'se': None}
         if self.with_fpe:
-            cr, ce = self.fpe.conv_reduce, self.fpe.conv_expand
+            cr, ce = self._gate().conv_reduce, self._gate().conv_expand
             img['se'] = self._keep('se_image', [cr.weight, cr.bias, ce.weight], lambda: ops.mlp2_image(flat(cr), cr.bias.detach(), flat(ce)))
         return img
 
@@ -348,11 +356,19 @@ class _PETRHeadBase(nn.Module):
         if Fn.torch_ops_route(what + (', hip_train' if train else ''), covered, module=self):
             return self._forward_torch(mlvl_feats, img_metas)
         if train:
-            return self._forward_train(feat, img_metas)
+            return self._forward_train(self._past_frames_detached(feat), img_metas)
         with torch.no_grad():
             return self._forward_kernels(feat, img_metas)
 
+    def _past_frames_detached(self, feat):
+        """PETRHeadseg's with_detach; the identity here."""
+        return feat
+
     def _forward_kernels(self, feat, img_metas):
+        return self._decode_kernels(*self._keys_kernels(feat, img_metas), img_metas)
+
+    def _keys_kernels(self, feat, img_metas):
+        """The key side in ONE launch -> memory, key_pos (n h w, bs, 256) and the key padding mask (bs, n h w)."""
         bs, n, _, h, w = feat.shape
         dev = feat.device
         pe = self._helper()
@@ -361,11 +377,15 @@ class _PETRHeadBase(nn.Module):
         sine = pe._sine_branch(masks, chlast=True)                                # (bs n, h w, 256), kept
         img = self._images()
         i2l = pe._matrices_device(pe._img2lidar(img_metas), dev)
-        se_b2 = self.fpe.conv_expand.bias if self.with_fpe else None
+        se_b2 = self._gate().conv_expand.bias if self.with_fpe else None
         memory, key_pos = ops.petr_keys_fwd(x, i2l, pad_hw, self.depth_num, self.depth_start, self.position_range, img['pe'],
                                             self.position_encoder[2].bias, sine, img['se'], se_b2)
-        out_dec = self.transformer.forward_keys(memory, key_pos, masks[0].reshape(bs, n * h * w), self._query_embeds(),
-                                                self.reg_branches)
+        return memory, key_pos, masks[0].reshape(bs, n * h * w)
+
+    def _decode_kernels(self, memory, key_pos, mask, img_metas):
+        """The decoder on the key rows, the branches and the box epilogue."""
+        bs = memory.shape[1]
+        out_dec = self.transformer.forward_keys(memory, key_pos, mask, self._query_embeds(), self.reg_branches)
         out_dec = torch.nan_to_num(out_dec)
         ref = self.reference_points.weight.detach().unsqueeze(0).expand(bs, -1, -1).contiguous()
         # init_reference = every inter_reference = reference_points: the reference adds inverse_sigmoid(reference_points) at every level
@@ -392,6 +412,9 @@ class _PETRHeadBase(nn.Module):
     def _forward_train(self, feat, img_metas):
         """hip_train: the kernel route with autograd - the key side as one node, everything behind it on the library's autograd
         Functions."""
+        return self._decode_train(*self._keys_train(feat, img_metas), img_metas)
+
+    def _keys_train(self, feat, img_metas):
         from .autograd import PetrKeysFunction
         bs, n, _, h, w = feat.shape
         pe = self._helper()
@@ -408,14 +431,19 @@ class _PETRHeadBase(nn.Module):
                     depth_start=self.depth_start, position_range=self.position_range, xs=self._sine_expansion(masks), ip_image=ip_image,
                     ip_scale=ip_scale, pe_image=img['pe'], se_image=img['se'],
                     ip_image_t=lambda: self._keep('input_proj_t', [conv.weight], lambda: ops.fpn_lateral_image_t(conv.weight.detach())))
-        seqs = [self.position_encoder, self.adapt_pos3d] + ([(self.fpe.conv_reduce, None, self.fpe.conv_expand)] if self.with_fpe else [])
+        seqs = [self.position_encoder, self.adapt_pos3d] + \
+            ([(self._gate().conv_reduce, None, self._gate().conv_expand)] if self.with_fpe else [])
         params = [conv.weight, conv.bias] + [p for q in seqs for c in (q[0], q[2]) for p in (c.weight, c.bias)]
         params += [None] * (14 - len(params))
         memory, key_pos = PetrKeysFunction.apply(feat, geom, *params)
+        return memory, key_pos, masks[0].reshape(bs, n * h * w)
+
+    def _decode_train(self, memory, key_pos, mask, img_metas):
+        bs = memory.shape[1]
         q0, q2 = self.query_embedding[0], self.query_embedding[2]
         query_embeds = Fn.linear_autograd(Fn.linear_autograd(pos2posemb3d(self.reference_points.weight), q0.weight, q0.bias, relu=True),
                                           q2.weight, q2.bias)                     # (not kept while parameters require grad)
-        out_dec = self.transformer.forward_keys(memory, key_pos, masks[0].reshape(bs, n * h * w), query_embeds, self.reg_branches)
+        out_dec = self.transformer.forward_keys(memory, key_pos, mask, query_embeds, self.reg_branches)
         out_dec = torch.nan_to_num(out_dec)
         # (not detached: the reference adds inverse_sigmoid(reference_points) at every level, and BoxHeadFunction hands its gradient back)
         ref = self.reference_points.weight.unsqueeze(0).expand(bs, -1, -1)
@@ -463,7 +491,7 @@ class _PETRHeadBase(nn.Module):
 
     def _forward_torch(self, mlvl_feats, img_metas):
         """The reference's forward (petr_head.py:359-451, petrv2_head.py:418-529), op for op, on torch."""
-        x = mlvl_feats[self.position_level]
+        x = self._past_frames_detached(mlvl_feats[self.position_level])
         batch_size, num_cams = x.size(0), x.size(1)
         input_img_h, input_img_w, _ = img_metas[0]['pad_shape'][0]
         masks = x.new_ones((batch_size, num_cams, input_img_h, input_img_w))
@@ -481,7 +509,7 @@ class _PETRHeadBase(nn.Module):
         if self.with_position:
             pos_embed, _ = self.position_embeding(mlvl_feats, img_metas, masks)
             if self.with_fpe:
-                gate = self.fpe.gate_logits(x.flatten(0, 1))
+                gate = self._gate().gate_logits(x.flatten(0, 1))
                 pos_embed = (pos_embed.flatten(0, 1) * gate.sigmoid()).view(x.size())
             pos_embed = pos_embed + self.adapt_pos3d(sin_embed.flatten(0, 1)).view(x.size())
         elif self.with_multiview:
@@ -584,3 +612,202 @@ class PETRv2Head(_PETRHeadBase):
     """petrv2_head.py:91-...: position_level, with_fpe (SELayer gate on input_proj's output), with_time (velocity over the mean
     timestamp difference), with_multi (RegLayer); the six levels hold deep copies of the branches."""
     _share_branches = False
+
+
+def pos2posemb2d(pos, num_pos_feats=128, temperature=10000):
+    """petr_head_seg.py:43-55."""
+    pos = pos * (2 * math.pi)
+    dim_t = torch.arange(num_pos_feats, dtype=torch.float32, device=pos.device)
+    dim_t = temperature ** (2 * (dim_t // 2) / num_pos_feats)
+    parts = []
+    for axis in (1, 0):                                      # (pos_y, pos_x)
+        p = pos[..., axis, None] / dim_t
+        parts.append(torch.stack((p[..., 0::2].sin(), p[..., 1::2].cos()), dim=-1).flatten(-2))
+    return torch.cat(parts, dim=-1)
+
+
+@LOSSES.register_module()
+class Sigmoid_ce_loss(nn.Module):
+    """losses/Sigmoid_ce_loss.py:19-43: binary cross entropy with logits, mean over all elements, each row's positives weighted by
+    #(t == 0) / max(#(t == 1), 1).  forward(inputs (R, C), targets (R, C)) -> a scalar, as the reference's.  fp32 tensors on the GPU go
+    through gd4d_lane_mask_loss (autograd.LaneMaskLossFunction with one layer); anything else (CPU, other dtypes, torch_ops = True)
+    through the reference's four lines.
+
+    layers(logits (L, R, C), targets (R, C)) -> (L,): every decoder layer in ONE call, each value through the nan_to_num of
+    petr_head_seg.py:785 - what PETRHeadseg.loss uses.  On the kernel a layer whose loss is not finite gets an all-zero gradient
+    (torch leaves a NaN at the offending logit).  The kernel applies the nan_to_num in forward() too - the head applies it to the module's
+    result next, and a finite loss is unchanged by it -, the torch lines of forward() are the reference's and do not."""
+
+    def __init__(self, loss_weight=1.0, torch_ops=False):
+        super().__init__()
+        self.loss_weight = loss_weight
+        self.torch_ops = bool(torch_ops)
+
+    def _on_kernel(self, inputs, targets):
+        return inputs.is_cuda and inputs.dtype == torch.float32 and targets.dtype == torch.float32 and \
+            not Fn.torch_ops_route('Sigmoid_ce_loss', True, module=self)
+
+    def _reference(self, inputs, targets):
+        pos_weight = (targets == 0).float().sum(dim=1) / (targets == 1).float().sum(dim=1).clamp(min=1.0)
+        weight_loss = targets * pos_weight.unsqueeze(1) + (1 - targets)
+        loss = F.binary_cross_entropy_with_logits(inputs, targets, reduction='mean', weight=weight_loss)
+        return self.loss_weight * loss
+
+    def layers(self, logits, targets):
+        if logits.dim() != 3 or tuple(targets.shape) != tuple(logits.shape[1:]):
+            raise ValueError(f'Sigmoid_ce_loss.layers: logits (L, R, C) and targets (R, C) expected, got {tuple(logits.shape)} and '
+                             f'{tuple(targets.shape)}')
+        if self._on_kernel(logits, targets):
+            from .autograd import LaneMaskLossFunction
+            return LaneMaskLossFunction.apply(logits, targets, float(self.loss_weight))
+        return torch.stack([torch.nan_to_num(self._reference(x, targets)) for x in logits])
+
+    def forward(self, inputs, targets):
+        if inputs.dim() == 2 and inputs.shape == targets.shape and inputs.numel() and self._on_kernel(inputs, targets):
+            from .autograd import LaneMaskLossFunction
+            return LaneMaskLossFunction.apply(inputs.unsqueeze(0), targets, float(self.loss_weight))[0]
+        return self._reference(inputs, targets)
+
+
+@HEADS.register_module()
+class PETRHeadseg(_PETRHeadBase):
+    """petr_head_seg.py:107-905: PETRv2's detection head plus a BEV map branch.  A second PETRTransformer (`transformer_lane`) runs
+    num_lane grid queries - query_embedding_lane(pos2posemb2d(reference_points_lane)) - over the SAME keys as the detection decoder, and
+    ONE lane_branches MLP under six names maps every lane query to 768 logits, a 3-class 16 x 16 patch of the map.  The SE gate lives
+    under `se.*` (keyword with_se); cls / reg / lane branches are shared by the six levels; reference_points_lane is a plain tensor,
+    neither a parameter nor a buffer, and follows the module's moves.
+
+    Kernel route: ONE ops.petr_keys_fwd launch feeds both decoders' forward_keys; the lane query embedding is a kept value; the lane
+    branch runs over all layers x bs x num_lane rows at once, three Linear launches.  hip_train: one PetrKeysFunction node feeds both
+    decoders (autograd sums their gradients into memory / key_pos), the lane embedding and lane_branches go through Fn.linear_autograd.
+    torch_ops=True: the reference's op sequence (:466-602).  with_detach: cameras 6: of the feature map are detached under autograd.
+
+    loss(): the detection terms from criterion(), the lane terms of all layers from ONE gd4d_lane_mask_loss call; the reference reads
+    gt_lanes[0] and lane_preds.squeeze(0), so it is meaningful at batch 1 only - a larger batch raises.  get_lane_map(): the decode of
+    Petr3D_seg.simple_test_pts (petr3d_seg.py:228-246) on gd4d_lane_map_fwd.
+
+    Limits beyond the base class's: num_lane must be a perfect square (the reference's round(sqrt(num_lane)) silently builds another
+    number of queries otherwise).  Left off: the two decoders on two streams."""
+    _share_branches = True
+    _gate_name = 'se'
+
+    def __init__(self, num_classes, in_channels, num_lane=100, transformer_lane=None, loss_lane_mask=None, with_se=False,
+                 with_detach=False, **kwargs):
+        if 'with_fpe' in kwargs:
+            raise TypeError('PETRHeadseg has no keyword \'with_fpe\' (its gate is with_se, under se.*)')
+        grid = round(math.sqrt(num_lane)) if num_lane >= 1 else 0
+        if grid < 1 or grid * grid != num_lane:
+            raise Gd4dError(f'PETRHeadseg: num_lane = {num_lane} is not a positive perfect square; the reference lays its lane queries out on a '
+                            f'round(sqrt(num_lane)) = {grid} x {grid} grid and would silently build {grid * grid} of them - refused on '
+                            'every route, torch_ops=True included')
+        self.num_lane, self.lane_grid, self.with_se, self.with_detach = num_lane, grid, bool(with_se), bool(with_detach)
+        self._lane_cfg = (copy.deepcopy(transformer_lane), copy.deepcopy(loss_lane_mask))
+        super().__init__(num_classes, in_channels, with_fpe=with_se, **kwargs)
+
+    def _init_layers(self):
+        self.transformer_lane = build_transformer(self._lane_cfg[0])
+        self.loss_lane_mask = build_loss(self._lane_cfg[1]) if self._lane_cfg[1] is not None else None
+        super()._init_layers()
+        c = self.embed_dims
+        lane_branch = []
+        for _ in range(self.num_reg_fcs):
+            lane_branch += [nn.Linear(c, c), nn.ReLU()]
+        lane_branch.append(nn.Linear(c, 768))
+        lane_branch = nn.Sequential(*lane_branch)
+        self.lane_branches = nn.ModuleList([lane_branch for _ in range(self.num_pred)])
+        x = (torch.arange(self.lane_grid) + 0.5) / self.lane_grid                      # :365-369, without the .cuda()
+        xy = torch.meshgrid(x, x, indexing='ij')
+        self.reference_points_lane = torch.cat([xy[0].reshape(-1)[..., None], xy[1].reshape(-1)[..., None]], -1)
+        self.query_embedding_lane = nn.Sequential(nn.Linear(c, c), nn.ReLU(), nn.Linear(c, c))
+
+    def init_weights(self):
+        super().init_weights()
+        self.transformer_lane.init_weights()
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self.reference_points_lane = fn(self.reference_points_lane)            # a plain tensor: moved with the parameters
+        return out
+
+    def _past_frames_detached(self, feat):
+        if not self.with_detach or not torch.is_grad_enabled():
+            return feat
+        return torch.cat([feat[:, :6], feat[:, 6:].detach()], 1)                # :484-487
+
+    # ---- the lane half of the three routes ------------------------------------------------------------------------------
+    def _lane_points(self):
+        return self.reference_points_lane.to(self.query_embedding_lane[0].weight.device)
+
+    def _lane_query_embeds(self):
+        """query_embedding_lane(pos2posemb2d(reference_points_lane)): parameters only - kept under the one validity rule."""
+        q0, q2 = self.query_embedding_lane[0], self.query_embedding_lane[2]
+        return self._keep('query_embeds_lane', [q0.weight, q0.bias, q2.weight, q2.bias],
+                          lambda: Fn.linear(Fn.linear(pos2posemb2d(self._lane_points()), q0.weight, q0.bias, relu=True), q2.weight, q2.bias))
+
+    @staticmethod
+    def _with_lanes(outs, lanes):
+        return {'all_cls_scores': outs['all_cls_scores'], 'all_bbox_preds': outs['all_bbox_preds'], 'all_lane_preds': lanes,
+                'enc_cls_scores': None, 'enc_bbox_preds': None}
+
+    def _decode_kernels(self, memory, key_pos, mask, img_metas):
+        outs = super()._decode_kernels(memory, key_pos, mask, img_metas)
+        lane = torch.nan_to_num(self.transformer_lane.forward_keys(memory, key_pos, mask, self._lane_query_embeds(), self.reg_branches))
+        branch = self.lane_branches[0]                       # ONE object under six names: all layers x bs x num_lane rows at once
+        x = lane.contiguous().view(-1, lane.shape[-1])
+        for m in branch:
+            if isinstance(m, nn.Linear):
+                x = Fn.linear(x, m.weight, m.bias, relu=m is not branch[-1])
+        return self._with_lanes(outs, x.view(*lane.shape[:-1], -1))
+
+    def _decode_train(self, memory, key_pos, mask, img_metas):
+        outs = super()._decode_train(memory, key_pos, mask, img_metas)
+        q0, q2 = self.query_embedding_lane[0], self.query_embedding_lane[2]
+        query_lane = Fn.linear_autograd(Fn.linear_autograd(pos2posemb2d(self._lane_points()), q0.weight, q0.bias, relu=True),
+                                        q2.weight, q2.bias)
+        lane = torch.nan_to_num(self.transformer_lane.forward_keys(memory, key_pos, mask, query_lane, self.reg_branches))
+        x = Fn.sequential_autograd(self.lane_branches[0], lane.contiguous().view(-1, lane.shape[-1]))
+        return self._with_lanes(outs, x.view(*lane.shape[:-1], -1))
+
+    def _forward_torch_ops(self, x, masks, query_embeds, pos_embed, reference_points, img_metas, batch_size):
+        outs = super()._forward_torch_ops(x, masks, query_embeds, pos_embed, reference_points, img_metas, batch_size)
+        query_lane = self.query_embedding_lane(pos2posemb2d(self._lane_points()))
+        lane, _ = self.transformer_lane(x, masks, query_lane, pos_embed, self.reg_branches)
+        lane = torch.nan_to_num(lane)
+        return self._with_lanes(outs, torch.stack([self.lane_branches[lvl](lane[lvl]) for lvl in range(lane.shape[0])]))
+
+    # ---- loss / map --------------------------------------------------------------------------------------------------------
+    def loss(self, gt_bboxes_list, gt_labels_list, preds_dicts, gt_lanes, gt_bboxes_ignore=None):
+        """petr_head_seg.py:790-881: the reference's keys - loss_cls, loss_bbox, loss_mask and d{i}.* of the earlier layers.  gt_lanes[0]
+        is the (num_lane, 768) target every layer is compared with."""
+        lanes = preds_dicts['all_lane_preds']
+        if lanes.shape[1] != 1:
+            raise Gd4dError(f'PETRHeadseg.loss: batch size {lanes.shape[1]}; the reference compares lane_preds.squeeze(0) with gt_lanes[0] '
+                            '(petr_head_seg.py:782-784), which is meaningful at batch size 1 only - on every route, torch_ops=True included')
+        if self.loss_lane_mask is None:
+            raise Gd4dError('PETRHeadseg.loss: the head was built without loss_lane_mask (dict(type=\'Sigmoid_ce_loss\', ...))')
+        det = self.criterion().loss(gt_bboxes_list, gt_labels_list, preds_dicts, gt_bboxes_ignore)
+        with Fn.torch_ops_for(*([self.loss_lane_mask] if self.torch_ops else [])):
+            masks = self.loss_lane_mask.layers(lanes.squeeze(1), gt_lanes[0])             # (layers,): ONE call
+        out = {'loss_cls': det['loss_cls'], 'loss_bbox': det['loss_bbox'], 'loss_mask': masks[-1]}
+        for i in range(lanes.shape[0] - 1):
+            out[f'd{i}.loss_cls'], out[f'd{i}.loss_bbox'], out[f'd{i}.loss_mask'] = det[f'd{i}.loss_cls'], det[f'd{i}.loss_bbox'], masks[i]
+        return out
+
+    def get_lane_map(self, preds_dicts, gt_map=None):
+        """The LAST layer's logits (B, g g, 768) -> (binary map (B, 3, 16 g, 16 g) of 0 / 1, iou (B, 3) against gt_map or None)."""
+        logits = preds_dicts['all_lane_preds'][-1]
+        covered = logits.is_cuda and logits.dtype == torch.float32 and (gt_map is None or (gt_map.is_cuda and gt_map.dtype == torch.float32))
+        if not Fn.torch_ops_route(f'PETRHeadseg.get_lane_map on {logits.device}, dtype {logits.dtype}', covered, module=self):
+            with torch.no_grad():
+                res = ops.lane_map_fwd(logits.detach().contiguous(), None if gt_map is None else gt_map.contiguous())
+            return res[1], (res[3] if gt_map is not None else None)
+        with torch.no_grad():                                # petr3d_seg.py:228-246, for any batch and grid
+            b, g = logits.shape[0], self.lane_grid
+            f_lane = logits.view(b, g, g, 3, 16, 16).permute(0, 3, 1, 4, 2, 5).reshape(b, 3, 16 * g, 16 * g).sigmoid()
+            f_lane[f_lane >= 0.5] = 1
+            f_lane[f_lane < 0.5] = 0
+            iou = None
+            if gt_map is not None:
+                p, t = f_lane.flatten(2), gt_map.flatten(2)
+                iou = (2 * (p * t).sum(dim=2) + 0.01) / (p.sum(dim=2) + t.sum(dim=2) + 0.01)
+        return f_lane, iou

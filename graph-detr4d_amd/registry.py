@@ -73,6 +73,7 @@ NECKS = Registry('neck', _mmcv('mmdet.models.builder.NECKS'))
 CONV_LAYERS = Registry('conv layer')
 BACKBONES = Registry('backbone')
 HEADS = Registry('head', _mmcv('mmdet.models.builder.HEADS'))
+LOSSES = Registry('loss', _mmcv('mmdet.models.builder.LOSSES'))
 
 
 def build_attention(cfg, default_args=None):
@@ -124,3 +125,7 @@ def build_backbone(cfg, default_args=None):
 
 def build_head(cfg, default_args=None):
     return build_from_cfg(cfg, HEADS, default_args)
+
+
+def build_loss(cfg, default_args=None):
+    return build_from_cfg(cfg, LOSSES, default_args)

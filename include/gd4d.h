@@ -1882,6 +1882,30 @@ int gd4d_conv1x1_wgrad(const float* dz, const float* x, int n, int cin, int cout
 int gd4d_conv3x3_act_wgrad(const float* dz, const float* x, int n, int cin, int cout, int h, int w, int stride, int partitions,
                            float* workspace, const float* weight, const float* bn, float* dw, float* dgamma, float* dbeta, void* stream);
 
+/* PETRHeadseg's lane stages (gd4d_lane_head.hip; additive exports, the ABI version stays).  All tensors contiguous fp32.
+ * gd4d_lane_mask_loss - Sigmoid_ce_loss (losses/Sigmoid_ce_loss.py:39-43) of L decoder layers against one target map, forward and
+ *   gradient together.  logits (L, R, C), targets (R, C) shared by the layers.  Per row pw = #(t == 0) / max(#(t == 1), 1) and
+ *   w = t pw + (1 - t); per layer loss[l] = nan_to_num(loss_weight * mean over R C of w (max(x, 0) - x t + log1p(exp(-|x|)))) and
+ *   dlogits[l] = loss_weight w (sigmoid(x) - t) / (R C), the gradient of loss[l] alone.  A layer whose loss is not finite before the
+ *   nan_to_num (a NaN or infinite logit) gets the nan_to_num value (0 for NaN, +-FLT_MAX for +-inf) and an ALL-ZERO gradient - torch
+ *   leaves a NaN at the offending logit; the other layers are unaffected bit for bit.  The row counts are taken once per row; the sums
+ *   are fp64 in a fixed order without atomics: two runs give the same bits.  16-byte accesses when C % 4 == 0 and logits, targets and
+ *   dlogits are 16-byte aligned, 4-byte ones otherwise.  workspace: gd4d_lane_mask_loss_workspace_bytes(L, R, C) bytes, 16-byte aligned
+ *   (0 = sizes outside the limits: L in 1 .. 65535, R C <= 2^40).  Three launches.
+ * gd4d_lane_map_fwd - the map decode of Petr3D_seg.simple_test_pts (detectors/petr3d_seg.py:228-246) in one launch.  logits
+ *   (B, g g, 768): query h g + w holds a 3 x 16 x 16 patch.  prob (B, 3, 16 g, 16 g) = fp32 1 / (1 + exp(-x)) at
+ *   [c, 16 h + h1, 16 w + w2]; binary = (prob >= 0.5) as 0 / 1 on that same fp32 value (a NaN logit gives 0, where the reference keeps
+ *   NaN).  gt_map (B, 3, 16 g, 16 g) or NULL; with it sums (B, 3, 3) = sum(binary gt), sum(binary), sum(gt) and iou (B, 3) =
+ *   (2 inter + 0.01) / (sum(binary) + sum(gt) + 0.01) (petr3d_seg.py:25-29), reduced in a fixed order (sum(binary) as an integer).
+ *   g in 1 .. 2048; every tensor 16-byte aligned.
+ * Errors: NULL required pointer or non-positive size GD4D_EINVAL (sums / iou are required with gt_map); sizes outside the limits
+ *   GD4D_EUNSUPPORTED; a missing or short workspace GD4D_EWORKSPACE; misalignment GD4D_EALIGN - all before any GPU work. */
+size_t gd4d_lane_mask_loss_workspace_bytes(int L, int R, int C);
+int gd4d_lane_mask_loss(const float* logits, const float* targets, float loss_weight, int L, int R, int C, float* loss, float* dlogits,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int gd4d_lane_map_fwd(const float* logits, const float* gt_map, int B, int g, float* prob, float* binary, float* sums, float* iou,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -870,3 +870,35 @@ def load_petr_head():
         v1 = importlib.import_module('projects.mmdet3d_plugin.models.dense_heads.petr_head')
         v2 = importlib.import_module('projects.mmdet3d_plugin.models.dense_heads.petrv2_head')
     return v1, v2
+
+
+# --------------------------------------------------------------------------------------
+# PETRHeadseg: PETRv2's head plus the BEV map branch of petrv2_BEVseg.py
+# --------------------------------------------------------------------------------------
+def load_petr_head_seg():
+    """Import the reference's dense_heads/petr_head_seg.py and losses/Sigmoid_ce_loss.py unmodified and return the two modules.  On
+    top of load_petr_head's stand-ins: a LOSSES registry the loss registers itself in, the two names Sigmoid_ce_loss.py imports and
+    never calls (bbox_overlaps, weighted_loss), and a build_loss that builds what that registry holds - the reference's own
+    Sigmoid_ce_loss - and keeps the `use_sigmoid` stand-in for the detection losses, of which the forward pass reads nothing else."""
+    load_petr_head()
+    losses = Registry('loss')
+    sys.modules['mmdet.core'].bbox_overlaps = None                # imported, never called
+    if 'mmdet.models.builder' not in sys.modules:
+        _mod('mmdet.models.builder')
+    sys.modules['mmdet.models.builder'].LOSSES = losses
+    if 'mmdet.models.losses' not in sys.modules:
+        _mod('mmdet.models.losses')
+    _mod('mmdet.models.losses.utils', weighted_loss=None)         # imported, never called
+    models = sys.modules['mmdet.models']
+    models.build_loss = lambda cfg: (losses.build(cfg) if cfg is not None and cfg.get('type') in losses.module_dict
+                                     else types.SimpleNamespace(use_sigmoid=(cfg or {}).get('use_sigmoid', False)))
+    full = 'projects.mmdet3d_plugin.models.losses'
+    if full not in sys.modules:
+        m = types.ModuleType(full)
+        m.__path__ = [os.path.join(REFERENCE_ROOT, *full.split('.'))]
+        sys.modules[full] = m
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        loss = importlib.import_module('projects.mmdet3d_plugin.models.losses.Sigmoid_ce_loss')
+        seg = importlib.import_module('projects.mmdet3d_plugin.models.dense_heads.petr_head_seg')
+    return seg, loss
