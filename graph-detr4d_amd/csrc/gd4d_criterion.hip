@@ -34,6 +34,9 @@ struct MatchCostParams {
 };
 
 // mmdet FocalLossCost (alpha, gamma = 2, eps = 1e-12) + BBox3DL1Cost over the first 8 code entries, then nan_to_num
+// The focal term is the reference's own fp32 formula, -log(1 - p + 1e-12) with p = 1 / (1 + expf(-x)): ill-conditioned by construction
+// once 1 - p loses its bits (x above ~6) and a constant once p rounds to 1 (x >= 24 ln 2); the cost then follows the rounding of p, not
+// the real-number formula.  The blocks of the non-empty samples tile the buffer: every element is written.
 __global__ __launch_bounds__(256) void match_cost_kernel(const MatchCostParams p) {
   __shared__ float s_gt[MC_MAX_GT * 8];
   __shared__ int s_lab[MC_MAX_GT];
@@ -93,6 +96,11 @@ struct HeadLossParams {
 // One workgroup per decoder layer, one thread per (sample, query) row: sigmoid focal loss (gamma = 2) over the classes
 // with label `num_classes` = background, L1 on the positives against the normalised ground truth (rows whose target is
 // not finite are dropped, :837-842), both already divided by their normalisers; gradients written in the same pass.
+// A matched row whose stored label is C is background for the focal term and KEEPS its box term (the reference's one_hot does the
+// same); labels outside [0, C] and assigned outside [0, sumG) make the reference raise and are background here.  The compared columns
+// are the first nk = min(gt_dim > 7 ? 10 : 8, code) of both sides (the reference only runs for (gt_dim, code) = (7, 8), (9, >= 10),
+// where this is its rule; an 8-entry box has vy = 0); gradient columns >= nk are +0.  The gradients are those of the two terms BEFORE
+// nan_to_num: a layer whose term was replaced keeps finite gradients wherever its own inputs are finite (torch zeroes the layer).
 __global__ __launch_bounds__(1024) void head_loss_kernel(const HeadLossParams p) {
   __shared__ float s_red[2][16];
   const int l = blockIdx.x;

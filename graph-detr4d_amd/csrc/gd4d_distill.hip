@@ -352,6 +352,11 @@ __device__ __forceinline__ float nan_to_num_f(float s) {
 //                divisor = max(num_total_pos, 1), or with reweight_score the local sum of max_c labels over rows with labels[:, 0] != 10
 //                (:908-911, not clamped);
 //   both terms through nan_to_num (:923-924).
+// Reference quirks kept on purpose (tests/test_loss_kernels_gpu.py pins each): the soft labels come from batch 0 for every sample; the
+// divisor rule compares with the literal 10, so with C != 10 every unmatched row (labels = C) adds C to it; the divisor is not clamped.
+// The gradients are those of the two terms BEFORE nan_to_num; when a layer's divisor is 0 (reweight, C == 10, nothing matched) or not
+// finite the second pass makes grad_box[:, :10] NaN in EVERY row of that layer (0 * inf), where torch leaves 0 in the rows its
+// isfinite filter drops.  assigned outside [b Qt, (b + 1) Qt) counts as unmatched.  Gradient columns >= 10 are +0.
 __global__ __launch_bounds__(1024) void distill_loss_kernel(const DistillLossParams p) {
   __shared__ float s_red[3][16];
   __shared__ float s_div;

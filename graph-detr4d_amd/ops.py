@@ -1684,29 +1684,39 @@ def cross_attn_bwd(value, level_hw, ref, offsets, attn_logits, cam_logits, lidar
     return gv, gr, go, ga, gc
 
 
-def match_cost_fwd(cls, box, gt_boxes, gt_labels, gt_start, max_gt, cls_weight=2.0, reg_weight=0.25, alpha=0.25):
+def match_cost_fwd(cls, box, gt_boxes, gt_labels, gt_start, max_gt, cls_weight=2.0, reg_weight=0.25, alpha=0.25, outs=None):
     """gd4d_match_cost_fwd.  cls (NL, B, Q, C), box (NL, B, Q, code) fp32; gt_boxes (sumG, 7..9) fp32, gt_labels (sumG)
     int32, gt_start (B + 1) int32 - all on the GPU; max_gt = largest per-sample count.  Returns the flat cost buffer
-    (NL * Q * sumG): block (l, b) at Q * (l * sumG + gt_start[b]), shape (Q, G_b)."""
+    (NL * Q * sumG): block (l, b) at Q * (l * sumG + gt_start[b]), shape (Q, G_b); every element is written (the blocks tile it).
+    The focal term is the reference's fp32 formula -log(1 - p + 1e-12) with p = 1 / (1 + expf(-x)), ill-conditioned by construction
+    once 1 - p loses its bits (x above ~6) and constant once p rounds to 1 (x above 24 ln 2).  outs = (cost,) may be the caller's."""
     nl, b, q, c = cls.shape
     sum_gt = gt_boxes.shape[0]
-    cost = torch.empty(nl * q * sum_gt, device=cls.device, dtype=F32)
+    cost = _out(outs[0] if outs is not None else None, (nl * q * sum_gt,), cls.device, 'outs[0]')
     _call('gd4d_match_cost_fwd', _dev(cls, 'cls', F32), _dev(box, 'box', F32), _dev(gt_boxes, 'gt_boxes', F32),
-          _dev(gt_labels, 'gt_labels', I32), _dev(gt_start, 'gt_start', I32), _dev(cost, 'cost'), nl, b, q, c, box.shape[-1],
+          _dev(gt_labels, 'gt_labels', I32), _dev(gt_start, 'gt_start', I32), _dev(cost, 'outs[0]', F32), nl, b, q, c, box.shape[-1],
           gt_boxes.shape[-1], sum_gt, int(max_gt), float(cls_weight), float(reg_weight), float(alpha))
     return cost
 
 
 def head_loss_fwd_bwd(cls, box, assigned, gt_boxes, gt_labels, code_weights, avg_factors, alpha=0.25,
-                      loss_cls_weight=2.0, loss_bbox_weight=0.25):
-    """gd4d_head_loss_fwd_bwd.  Returns (loss (NL, 2), grad_cls like cls, grad_box like box)."""
+                      loss_cls_weight=2.0, loss_bbox_weight=0.25, outs=None):
+    """gd4d_head_loss_fwd_bwd.  Returns (loss (NL, 2), grad_cls like cls, grad_box like box); outs may hold the caller's tensors in
+    that order.  A matched row whose stored label is C (or outside [0, C]) is background for the focal term and keeps its box term;
+    assigned outside [0, sumG) is background for both.  Box columns >= nk = min(gt_dim > 7 ? 10 : 8, code) get a zero gradient.
+
+    Deviation from torch: the gradients are those of the two terms BEFORE their nan_to_num.  Where a layer's term is not finite (a NaN
+    or infinite logit or box entry of that layer) torch's backward through nan_to_num zeroes that term's gradient in the whole layer
+    (times the local derivative: NaN at the offending entry); here every other entry keeps its usual finite value, a NaN logit's own
+    entry is NaN, a NaN box entry's 0 and a +/-inf box entry's its sign's.  Layers whose terms are finite equal torch's."""
     nl, b, q, c = cls.shape
-    loss = torch.empty(nl, 2, device=cls.device, dtype=F32)
-    gcls, gbox = torch.empty_like(cls), torch.empty_like(box)
+    outs = tuple(outs) if outs is not None else (None, None, None)
+    loss = _out(outs[0], (nl, 2), cls.device, 'outs[0]')
+    gcls, gbox = _out(outs[1], cls.shape, cls.device, 'outs[1]'), _out(outs[2], box.shape, cls.device, 'outs[2]')
     _call('gd4d_head_loss_fwd_bwd', _dev(cls, 'cls', F32), _dev(box, 'box', F32), _dev(assigned, 'assigned', I32),
           _dev(gt_boxes, 'gt_boxes', F32), _dev(gt_labels, 'gt_labels', I32), _dev(code_weights, 'code_weights', F32),
-          _dev(avg_factors, 'avg_factors', F32), _dev(loss, 'loss'), _dev(gcls, 'grad_cls'), _dev(gbox, 'grad_box'), nl, b, q, c,
-          box.shape[-1], gt_boxes.shape[-1], gt_boxes.shape[0], float(alpha), float(loss_cls_weight), float(loss_bbox_weight))
+          _dev(avg_factors, 'avg_factors', F32), _dev(loss, 'outs[0]', F32), _dev(gcls, 'outs[1]', F32), _dev(gbox, 'outs[2]', F32),
+          nl, b, q, c, box.shape[-1], gt_boxes.shape[-1], gt_boxes.shape[0], float(alpha), float(loss_cls_weight), float(loss_bbox_weight))
     return loss, gcls, gbox
 
 
@@ -1777,17 +1787,19 @@ def hungarian_assign_branches_fwd(costs, gt_start, nl, b, qs, ks, sum_gt, max_gt
     return assigned, copies, status
 
 
-def distill_match_cost_fwd(s_cls, s_box, t_cls, t_box, cls_weight=1.0, reg_weight=0.25, pseudo_gt=False):
+def distill_match_cost_fwd(s_cls, s_box, t_cls, t_box, cls_weight=1.0, reg_weight=0.25, pseudo_gt=False, outs=None):
     """gd4d_distill_match_cost_fwd.  s_cls (NL, B, Qs, C), s_box (NL, B, Qs, code), t_cls (NL, B, Qt, C), t_box (NL, B, Qt, 10) fp32 on
     the GPU: the teacher head's logits and box codes.  pseudo_gt=True: t_cls the soft labels per sample, t_box (NL, B, Qt, 9) the
-    denormalised boxes.  Returns the flat cost buffer (NL * B * Qs * Qt): block (l, b) at Qs * (l * B * Qt + b * Qt), shape (Qs, Qt)."""
+    denormalised boxes.  Returns the flat cost buffer (NL * B * Qs * Qt): block (l, b) at Qs * (l * B * Qt + b * Qt), shape (Qs, Qt).
+    Without pseudo_gt the soft labels of EVERY sample are sigmoid(t_cls[l, 0]) (the reference's batch-0 indexing); the boxes are each
+    sample's own.  outs = (cost,) may be the caller's."""
     nl, b, qs, c = s_cls.shape
     qt = t_cls.shape[2]
     if tuple(s_box.shape[:3]) != (nl, b, qs) or tuple(t_cls.shape) != (nl, b, qt, c) or tuple(t_box.shape) != (nl, b, qt, 9 if pseudo_gt else 10):
         raise ValueError('distill_match_cost_fwd: s_cls / s_box / t_cls / t_box shapes disagree')
-    cost = torch.empty(nl * b * qs * qt, device=s_cls.device, dtype=F32)
+    cost = _out(outs[0] if outs is not None else None, (nl * b * qs * qt,), s_cls.device, 'outs[0]')
     _call('gd4d_distill_match_cost_fwd', _dev(s_cls, 's_cls', F32), _dev(s_box, 's_box', F32), _dev(t_cls, 't_cls', F32),
-          _dev(t_box, 't_box', F32), _dev(cost, 'cost'), nl, b, qs, qt, c, s_box.shape[-1], 1 if pseudo_gt else 0, float(cls_weight),
+          _dev(t_box, 't_box', F32), _dev(cost, 'outs[0]', F32), nl, b, qs, qt, c, s_box.shape[-1], 1 if pseudo_gt else 0, float(cls_weight),
           float(reg_weight))
     return cost
 
@@ -1799,18 +1811,27 @@ def lsa_dense_fwd(cost, gt_start, nl, b, q, sum_gt, max_gt, assigned=None, statu
 
 
 def distill_loss_fwd_bwd(s_cls, s_box, t_cls, t_box, assigned, code_weights, avg_factors, reweight_score=False,
-                         loss_cls_weight=1.0, loss_reg_weight=1.0):
-    """gd4d_distill_loss_fwd_bwd.  Returns (loss (NL, 2), grad_s_cls like s_cls, grad_s_box like s_box)."""
+                         loss_cls_weight=1.0, loss_reg_weight=1.0, outs=None):
+    """gd4d_distill_loss_fwd_bwd.  Returns (loss (NL, 2), grad_s_cls like s_cls, grad_s_box like s_box); outs may hold the caller's
+    tensors in that order.  Reference quirks kept: a matched row's soft labels are sigmoid(t_cls[l, 0, t]) - batch 0 for every sample;
+    an unmatched row (assigned -1 or outside its sample's [b Qt, (b + 1) Qt)) has the label C in every class; with reweight_score the
+    divisor sums max_c labels over rows with labels[:, 0] != 10 - the literal 10, so with C != 10 every unmatched row adds C - and is
+    not clamped.  Box columns >= 10 get a zero gradient.
+
+    Deviation from torch: the gradients are those of the two terms BEFORE their nan_to_num (see head_loss_fwd_bwd), and when a
+    layer's reg divisor is 0 (reweight_score, C == 10, nothing matched) or not finite, grad_s_box[l, :, :, :10] is NaN in EVERY row
+    (0 * inf), where torch leaves 0 in the rows the isfinite filter drops.  The loss values and every other layer equal torch's."""
     nl, b, qs, c = s_cls.shape
     qt = t_cls.shape[2]
     if tuple(assigned.shape) != (nl, b, qs) or tuple(t_box.shape) != (nl, b, qt, 10) or tuple(t_cls.shape) != (nl, b, qt, c):
         raise ValueError('distill_loss_fwd_bwd: shapes disagree')
-    loss = torch.empty(nl, 2, device=s_cls.device, dtype=F32)
-    gcls, gbox = torch.empty_like(s_cls), torch.empty_like(s_box)
+    outs = tuple(outs) if outs is not None else (None, None, None)
+    loss = _out(outs[0], (nl, 2), s_cls.device, 'outs[0]')
+    gcls, gbox = _out(outs[1], s_cls.shape, s_cls.device, 'outs[1]'), _out(outs[2], s_box.shape, s_cls.device, 'outs[2]')
     _call('gd4d_distill_loss_fwd_bwd', _dev(s_cls, 's_cls', F32), _dev(s_box, 's_box', F32), _dev(t_cls, 't_cls', F32),
           _dev(t_box, 't_box', F32), _dev(assigned, 'assigned', I32), _dev(code_weights, 'code_weights', F32),
-          _dev(avg_factors, 'avg_factors', F32), _dev(loss, 'loss'), _dev(gcls, 'grad_cls'), _dev(gbox, 'grad_box'), nl, b, qs, qt, c,
-          s_box.shape[-1], 1 if reweight_score else 0, float(loss_cls_weight), float(loss_reg_weight))
+          _dev(avg_factors, 'avg_factors', F32), _dev(loss, 'outs[0]', F32), _dev(gcls, 'outs[1]', F32), _dev(gbox, 'outs[2]', F32),
+          nl, b, qs, qt, c, s_box.shape[-1], 1 if reweight_score else 0, float(loss_cls_weight), float(loss_reg_weight))
     return loss, gcls, gbox
 
 

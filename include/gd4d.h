@@ -1311,7 +1311,16 @@ size_t gd4d_cross_attn_bwd_workspace_bytes(int B, int Q, int Hh, int L, int P);
  *   Labels: a gt_labels entry outside [0, C) makes gd4d_match_cost_fwd write NaN into that column's costs (valid costs
  *   are never NaN: nan_to_num has been applied) - the host raises, as the reference's indexing does; the loss kernel
  *   treats assigned >= sum_gt or such a label as background (memory safety only).  The loss terms pass through
- *   torch.nan_to_num semantics (nan -> 0, +/-inf -> +/-FLT_MAX). */
+ *   torch.nan_to_num semantics (nan -> 0, +/-inf -> +/-FLT_MAX).
+ *   Reference behaviour kept: a stored label == C is background for the focal term while the row keeps its box term; the
+ *   focal COST is the fp32 formula -log(1 - p + 1e-12), p = 1 / (1 + expf(-x)) - it follows the rounding of p for x above
+ *   ~6 and is constant for x >= 24 ln 2.  Columns: the first nk = min(gt_dim > 7 ? 10 : 8, code) of prediction and target are
+ *   compared (an 8-entry box has vy = 0); grad_box columns >= nk are +0.  Every element of cost, loss and both gradients is
+ *   written.
+ *   Deviation from torch: grad_cls / grad_box are the gradients of the terms BEFORE nan_to_num.  In a layer whose term is
+ *   not finite (a NaN / inf logit or box entry) torch's backward through nan_to_num zeroes that term's gradient for the whole
+ *   layer (NaN at the offending entry); here the other entries keep their usual values, a NaN logit's entry is NaN, a NaN box
+ *   entry's is 0 and an infinite box entry's is its sign's.  Layers whose terms are finite are unaffected bit for bit. */
 int gd4d_match_cost_fwd(const float* cls, const float* box, const float* gt_boxes, const int32_t* gt_labels,
                         const int32_t* gt_start, float* cost, int NL, int B, int Q, int C, int code, int gt_dim,
                         int sum_gt, int max_gt, float cls_weight, float reg_weight, float alpha, void* stream);
@@ -1449,7 +1458,14 @@ int gd4d_depth_conv_wgrad(const float* const* dy, const float* const* x, const i
  *   and the target normalize_bbox(denormalize_bbox(t_box[l, b, t])); the others label num_classes (= C) and a zero target, which the
  *   isfinite filter drops.  code_weights (10); avg_factors DEVICE 2 floats (cls_avg_factor, num_total_pos, reduce_mean-ed, clamped to >= 1
  *   here); reweight != 0: the reg weights are multiplied by max_c labels and divided by the local sum of that maximum over rows with
- *   labels[:, 0] != 10 (:908-911) instead of num_total_pos.  Both terms through nan_to_num.  code in 10..16. */
+ *   labels[:, 0] != 10 (:908-911) instead of num_total_pos.  Both terms through nan_to_num.  code in 10..16.
+ *   Reference quirks kept: the soft labels are batch 0's for every sample (both entry points); "!= 10" is the literal 10, so with
+ *   C != 10 every unmatched row adds C to the reweight divisor; that divisor is not clamped.  assigned outside its sample's
+ *   [b Qt, (b + 1) Qt) counts as unmatched (memory safety; the solvers never write it).  grad_box columns >= 10 are +0; every element
+ *   of cost, loss and both gradients is written.
+ *   Deviation from torch: the gradients are those of the terms BEFORE nan_to_num (as gd4d_head_loss_fwd_bwd), and a layer whose
+ *   reweight divisor is 0 (C == 10 and nothing matched) or not finite gets NaN in grad_box[:, :10] of EVERY row (0 * inf), where
+ *   torch leaves 0 in the rows its isfinite filter drops; its loss_reg is nan_to_num's value.  Other layers are unaffected bit for bit. */
 int gd4d_distill_match_cost_fwd(const float* s_cls, const float* s_box, const float* t_cls, const float* t_box, float* cost, int NL,
                                 int B, int Qs, int Qt, int C, int code, int pseudo_gt, float cls_weight, float reg_weight, void* stream);
 size_t gd4d_lsa_dense_workspace_bytes(int NL, int B, int Q, int max_gt);
