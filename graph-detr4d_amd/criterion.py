@@ -169,21 +169,48 @@ class HungarianAssigner3D:
         return AssignResult(num_gts, gt_inds, None, labels=lab)
 
 
-class _HeadLossFunction(torch.autograd.Function):
-    """loss (NL, 2) from gd4d_head_loss_fwd_bwd; the gradients come out of the same launch."""
+def build_assigner(assigner, kind):
+    """An assigner given as a config dict (`type` dropped, the rest are `kind`'s keywords) or as an object."""
+    if isinstance(assigner, dict):
+        assigner = dict(assigner)
+        assigner.pop('type', None)
+        assigner = kind(**assigner)
+    return assigner
+
+
+def reduce_mean_normalisers(avg, sync_cls_avg_factor):
+    """`reduce_mean` (:825-826 and :835) of (cls_avg_factor, num_total_pos) pairs, a flat device tensor, in place: ONE all-reduce of
+    all of it.  num_total_pos is always averaged over the ranks, cls_avg_factor (the even entries) only with sync_cls_avg_factor
+    (:824) - else it keeps the local value."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        local_cls = avg[0::2].clone()
+        dist.all_reduce(avg)
+        avg /= dist.get_world_size()
+        if not sync_cls_avg_factor:
+            avg[0::2] = local_cls
+    return avg
+
+
+def scale_layer_grads(gcls, gbox, grad_loss):
+    """The gradients one loss launch wrote, (NL, B, Q, .) each, times their layer's two upstream scalars: grad_loss (NL, 2)."""
+    gl = grad_loss.view(-1, 2)
+    return gcls * gl[:, 0].view(-1, 1, 1, 1), gbox * gl[:, 1].view(-1, 1, 1, 1)
+
+
+class _LayerLossFunction(torch.autograd.Function):
+    """loss (NL, 2) = op(cls, box, *rest)[0] for an `ops` call that returns (loss, grad_cls, grad_box) from one launch
+    (ops.head_loss_fwd_bwd, ops.distill_loss_fwd_bwd); backward only scales.  cls and box, contiguous, get gradients; nothing else."""
 
     @staticmethod
-    def forward(ctx, cls, box, assigned, boxes, labels, code_weights, avg, alpha, wc, wb):
-        loss, gcls, gbox = ops.head_loss_fwd_bwd(cls.contiguous(), box.contiguous(), assigned, boxes, labels,
-                                                 code_weights, avg, alpha, wc, wb)
+    def forward(ctx, op, cls, box, *rest):
+        loss, gcls, gbox = op(cls, box, *rest)
         ctx.save_for_backward(gcls, gbox)
+        ctx.rest = len(rest)
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
-        gcls, gbox = ctx.saved_tensors
-        gl = grad_loss.view(-1, 2)
-        return (gcls * gl[:, 0].view(-1, 1, 1, 1), gbox * gl[:, 1].view(-1, 1, 1, 1)) + (None,) * 8
+        return (None,) + scale_layer_grads(*ctx.saved_tensors, grad_loss) + (None,) * ctx.rest
 
 
 class Detr3DCriterion(nn.Module):
@@ -208,11 +235,7 @@ class Detr3DCriterion(nn.Module):
             assigner = dict(type='HungarianAssigner3D', cls_cost=dict(type='FocalLossCost', weight=2.0),
                             reg_cost=dict(type='BBox3DL1Cost', weight=0.25), iou_cost=dict(type='IoUCost', weight=0.0),
                             pc_range=pc_range)
-        if isinstance(assigner, dict):
-            assigner = dict(assigner)
-            assigner.pop('type', None)
-            assigner = HungarianAssigner3D(**assigner)
-        self.assigner = assigner
+        self.assigner = build_assigner(assigner, HungarianAssigner3D)
 
     def normalisers(self, counts, num_query, device):
         """(cls_avg_factor, num_total_pos) as a 2-element device tensor, averaged over the ranks (`reduce_mean`,
@@ -220,13 +243,7 @@ class Detr3DCriterion(nn.Module):
         num_pos = float(sum(min(c, num_query) for c in counts))
         num_neg = float(len(counts) * num_query) - num_pos
         avg = torch.tensor([num_pos + num_neg * self.bg_cls_weight, num_pos], dtype=torch.float32, device=device)
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            local_cls = avg[0].clone()
-            dist.all_reduce(avg)
-            avg /= dist.get_world_size()
-            if not self.sync_cls_avg_factor:                 # :824: only num_total_pos is always synchronised
-                avg[0] = local_cls
-        return avg
+        return reduce_mean_normalisers(avg, self.sync_cls_avg_factor)
 
     def prepare_ground_truth(self, gt_bboxes_list, gt_labels_list, num_query, device):
         """What `loss` derives from the ground truth alone - the packed boxes / labels / offsets on the device and the two
@@ -258,8 +275,8 @@ class Detr3DCriterion(nn.Module):
         else:
             boxes, labels = packed[0], packed[1]
             assigned = self.assigner.assign_layers(cls, box, gts, gt_labels_list, packed)
-        loss = _HeadLossFunction.apply(cls.float(), box.float(), assigned, boxes, labels, self.code_weights, avg,
-                                       self.alpha, self.loss_cls_weight, self.loss_bbox_weight)
+        loss = _LayerLossFunction.apply(ops.head_loss_fwd_bwd, cls.float().contiguous(), box.float().contiguous(), assigned, boxes,
+                                        labels, self.code_weights, avg, self.alpha, self.loss_cls_weight, self.loss_bbox_weight)
         out = {'loss_cls': loss[-1, 0], 'loss_bbox': loss[-1, 1]}
         for i in range(nl - 1):
             out[f'd{i}.loss_cls'], out[f'd{i}.loss_bbox'] = loss[i, 0], loss[i, 1]
@@ -317,10 +334,7 @@ class _HybridLossFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss):
         gcls, gbox, gcls_m, gbox_m = ctx.saved_tensors
-        gl = grad_loss.view(-1, 2)
-        gm = gl * ctx.lam
-        return (gcls * gl[:, 0].view(-1, 1, 1, 1), gbox * gl[:, 1].view(-1, 1, 1, 1),
-                gcls_m * gm[:, 0].view(-1, 1, 1, 1), gbox_m * gm[:, 1].view(-1, 1, 1, 1)) + (None,) * 10
+        return scale_layer_grads(gcls, gbox, grad_loss) + scale_layer_grads(gcls_m, gbox_m, grad_loss * ctx.lam) + (None,) * 10
 
 
 class HDetr3DCriterion(Detr3DCriterion):
@@ -372,13 +386,7 @@ class HDetr3DCriterion(Detr3DCriterion):
         neg1, neg2 = float(len(counts) * q1) - pos1, float(len(counts) * q2) - pos2
         avg = torch.tensor([pos1 + neg1 * self.bg_cls_weight, pos1, pos2 + neg2 * self.bg_cls_weight, pos2],
                            dtype=torch.float32, device=device)
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            local_cls = avg[0::2].clone()
-            dist.all_reduce(avg)
-            avg /= dist.get_world_size()
-            if not self.sync_cls_avg_factor:
-                avg[0::2] = local_cls
-        return avg
+        return reduce_mean_normalisers(avg, self.sync_cls_avg_factor)
 
     def prepare_ground_truth(self, gt_bboxes_list, gt_labels_list, num_query=None, device=None):
         """Detr3DCriterion.prepare_ground_truth for both branches: the packed unrepeated ground truth (what both assignments and both

@@ -76,13 +76,49 @@ __device__ __forceinline__ float half_wave_sum(float s) {
 }
 
 // the sum over the WIDTH lanes of an aligned lane group, widest exchange first: every lane of the group gets the same bits
-template <int WIDTH>
-__device__ __forceinline__ float group_sum(float v) {
+// (T: float, double or int)
+template <int WIDTH, class T>
+__device__ __forceinline__ T group_sum(T v) {
 #pragma unroll
   for (int o = WIDTH / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
-__device__ __forceinline__ float wave_sum(float v) { return group_sum<GD4D_WAVE>(v); }
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) { return group_sum<GD4D_WAVE>(v); }
+
+// ---- the fixed-order workgroup sum --------------------------------------------------------------------------------------------
+// THE order of every sum over a workgroup (one value per thread) that promises equal bits from run to run: wave_sum in each wave,
+// lane 0 of wave w stores to s_red[w], a barrier, then ((s_red[0] + s_red[1]) + s_red[2]) + ... in wave order.  The first wave's
+// value starts the sum, no 0 is added: a site whose waves may all hold -0 and that wants +0 writes `0.f +` at its call.
+//   block_sum_put  the part before the barrier.  s_red: LDS, blockDim.x / 64 elements (blockDim.x a multiple of 64).
+//   block_sum_get  the part after it, for any thread that wants the sum: each gets the same bits.  WAVES: the wave count where it
+//                  is a constant of the kernel (the loop unrolls), 0 = blockDim.x / 64.
+//   block_sum      put, __syncthreads(), get: EVERY thread holds the sum.
+// The barrier between put and get is the caller's when it has several values (put them all, ONE barrier, get them) or a
+// __syncthreads_or to share.  Nothing here ENDS with a barrier: s_red is free for its next writer only after a barrier that
+// follows the last get - the caller's, where it reuses the array.
+template <class T>
+__device__ __forceinline__ void block_sum_put(T v, T* s_red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & (GD4D_WAVE - 1)) == 0) s_red[threadIdx.x / GD4D_WAVE] = v;
+}
+template <int WAVES = 0, class T>
+__device__ __forceinline__ T block_sum_get(const T* s_red) {
+  T s = s_red[0];
+  if constexpr (WAVES > 0) {
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) s += s_red[w];
+  } else {
+    for (int w = 1; w < (int)(blockDim.x / GD4D_WAVE); ++w) s += s_red[w];
+  }
+  return s;
+}
+template <int WAVES = 0, class T>
+__device__ __forceinline__ T block_sum(T v, T* s_red) {
+  block_sum_put(v, s_red);
+  __syncthreads();
+  return block_sum_get<WAVES>(s_red);
+}
 
 // inverse_sigmoid of the reference (deform3d_cross_attn.py:16-31), eps = 1e-5
 __device__ __forceinline__ float inv_sigmoid(float x) {

@@ -7,20 +7,12 @@
 // (hungarian_assigner_3d.py:117-144, detr3d_head_pe.py:782-845).  With these two kernels a step has ONE device -> host
 // copy (all layers' cost matrices), the assignment on the host, ONE host -> device copy, one loss launch that also
 // produces the gradients, and no .item(): the normalisers are read from device memory.
-#include "gd4d_common.h"
+#include "gd4d_loss_pieces.h"
 
 namespace gd4d {
 
 constexpr int MC_MAX_GT = 1024;      // ground-truth boxes per sample held in LDS
 constexpr int MC_QB = 64;            // queries per workgroup
-
-// core/bbox/util.py:38-58: (cx, cy, cz, w, l, h, rot[, vx, vy]) -> (cx, cy, log w, log l, cz, log h, sin, cos[, vx, vy])
-__device__ __forceinline__ void normalize_box(const float* b, int gt_dim, float* o) {
-  o[0] = b[0]; o[1] = b[1]; o[2] = logf(b[3]); o[3] = logf(b[4]); o[4] = b[2]; o[5] = logf(b[5]);
-  o[6] = sinf(b[6]); o[7] = cosf(b[6]);
-  o[8] = gt_dim > 7 ? b[7] : 0.f;
-  o[9] = gt_dim > 8 ? b[8] : 0.f;
-}
 
 struct MatchCostParams {
   const float* cls;          // (NL, B, Q, C) logits
@@ -64,17 +56,15 @@ __global__ __launch_bounds__(256) void match_cost_kernel(const MatchCostParams p
       continue;
     }
     const float x = p.cls[(row0 + q) * p.C + lab];
-    const float pr = 1.0f / (1.0f + expf(-x));
+    const float pr = sigmoid_f(x);
     const float neg = -logf(1.0f - pr + 1e-12f) * (1.0f - p.alpha) * (pr * pr);
     const float pos = -logf(pr + 1e-12f) * p.alpha * ((1.0f - pr) * (1.0f - pr));
     const float* bx = p.box + (row0 + q) * p.code;
     float l1 = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) l1 += fabsf(bx[k] - s_gt[8 * g + k]);
-    float c = (pos - neg) * p.cls_weight + l1 * p.reg_weight;
-    if (c != c || c == INFINITY) c = 100.0f;              // torch.nan_to_num(nan=100, posinf=100, neginf=-100)
-    else if (c == -INFINITY) c = -100.0f;
-    out[(size_t)q * G + g] = c;
+    const float c = (pos - neg) * p.cls_weight + l1 * p.reg_weight;
+    out[(size_t)q * G + g] = nan_to_num_f(c, 100.0f, 100.0f, -100.0f);     // hungarian_assigner_3d.py:139
   }
 }
 
@@ -101,8 +91,8 @@ struct HeadLossParams {
 // are the first nk = min(gt_dim > 7 ? 10 : 8, code) of both sides (the reference only runs for (gt_dim, code) = (7, 8), (9, >= 10),
 // where this is its rule; an 8-entry box has vy = 0); gradient columns >= nk are +0.  The gradients are those of the two terms BEFORE
 // nan_to_num: a layer whose term was replaced keeps finite gradients wherever its own inputs are finite (torch zeroes the layer).
-__global__ __launch_bounds__(1024) void head_loss_kernel(const HeadLossParams p) {
-  __shared__ float s_red[2][16];
+__global__ __launch_bounds__(LOSS_ROW_THREADS) void head_loss_kernel(const HeadLossParams p) {
+  __shared__ float s_red[2][LOSS_ROW_WAVES];
   const int l = blockIdx.x;
   const float cls_avg = fmaxf(p.avg_factors[0], 1.0f), pos_avg = fmaxf(p.avg_factors[1], 1.0f);
   const float kc = p.cls_weight / cls_avg, kb = p.box_weight / pos_avg;
@@ -118,12 +108,13 @@ __global__ __launch_bounds__(1024) void head_loss_kernel(const HeadLossParams p)
     for (int c = 0; c < p.C; ++c) {
       const float v = x[c];
       const bool t = c == label;
-      const float pr = 1.0f / (1.0f + expf(-v));
+      const float pr = sigmoid_f(v);
       const float pt = t ? 1.0f - pr : pr;
       const float aw = t ? p.alpha : 1.0f - p.alpha;
       const float fw = aw * (pt * pt);
-      // binary_cross_entropy_with_logits: max(v, 0) - v t + log(1 + exp(-|v|))
-      const float bce = fmaxf(v, 0.f) - (t ? v : 0.f) + log1pf(expf(-fabsf(v)));
+      // binary_cross_entropy_with_logits: max(v, 0) - v t + log(1 + exp(-|v|)).  Its own spelling: v t as a select (t is 0 or 1),
+      // which is 0 where the product v * 0 of distill_loss_kernel's soft-label form is NaN (v = +-inf)
+      const float bce = fmaxf(v, 0.f) - (t ? v : 0.f) + softplus_neg_abs(v);
       sum_cls += bce * fw;
       const float dpt = (t ? -1.0f : 1.0f) * pr * (1.0f - pr);
       gx[c] = kc * (fw * (pr - (t ? 1.0f : 0.f)) + bce * aw * 2.0f * pt * dpt);
@@ -134,32 +125,24 @@ __global__ __launch_bounds__(1024) void head_loss_kernel(const HeadLossParams p)
       float tgt[10];
       normalize_box(p.gt_boxes + (size_t)a * p.gt_dim, p.gt_dim, tgt);
       const int nk = min(p.gt_dim > 7 ? 10 : 8, p.code);
-      bool ok = true;
-      for (int k = 0; k < nk; ++k) ok = ok && (fabsf(tgt[k]) <= 3.402823466e38f);     // finite (NaN compares false)
-      if (ok) {
+      if (finite_f(tgt, nk)) {
         const float* bx = p.box + row * p.code;
         for (int k = 0; k < nk; ++k) {
           const float d = bx[k] - tgt[k], w = p.code_weights[k];
           sum_box += fabsf(d) * w;
-          gb[k] = kb * w * (d > 0.f ? 1.0f : (d < 0.f ? -1.0f : 0.f));
+          gb[k] = kb * w * l1_sign(d);
         }
       }
     }
   }
-  // fixed-order reduction: lanes, then the 16 waves
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { sum_cls += __shfl_xor(sum_cls, o); sum_box += __shfl_xor(sum_box, o); }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { s_red[0][wave] = sum_cls; s_red[1][wave] = sum_box; }
+  // the fixed-order workgroup sum of gd4d_common.h, both values behind one barrier; thread k finishes term k
+  block_sum_put(sum_cls, s_red[0]);
+  block_sum_put(sum_box, s_red[1]);
   __syncthreads();
   if (threadIdx.x < 2) {
-    float s = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += s_red[threadIdx.x][w];
-    s *= threadIdx.x == 0 ? kc : kb;
-    if (s != s) s = 0.f;                                   // torch.nan_to_num on the two loss terms (:844-845):
-    else if (s == INFINITY) s = 3.402823466e38f;           // nan -> 0, +/-inf -> +/-FLT_MAX
-    else if (s == -INFINITY) s = -3.402823466e38f;
-    p.loss[2 * l + threadIdx.x] = s;
+    // `0.f +`: this site's sum always started from +0, and a term can be -0 (a negative code weight times fabsf(0)): kept, not argued away
+    const float s = (0.f + block_sum_get<LOSS_ROW_WAVES>(s_red[threadIdx.x])) * (threadIdx.x == 0 ? kc : kb);
+    p.loss[2 * l + threadIdx.x] = nan_to_num_f(s);         // torch.nan_to_num on the two loss terms (:844-845)
   }
 }
 
@@ -193,6 +176,6 @@ extern "C" int gd4d_head_loss_fwd_bwd(const float* cls, const float* box, const 
   if (code < 8 || code > 16 || gt_dim < 7 || gt_dim > 9) return GD4D_EUNSUPPORTED;
   HeadLossParams p{cls, box, assigned, gt_boxes, gt_labels, code_weights, avg_factors, loss, grad_cls, grad_box,
                    NL, B, Q, C, code, gt_dim, sum_gt, alpha, loss_cls_weight, loss_bbox_weight};
-  hipLaunchKernelGGL(head_loss_kernel, dim3(NL), dim3(1024), 0, static_cast<hipStream_t>(stream), p);
+  hipLaunchKernelGGL(head_loss_kernel, dim3(NL), dim3(LOSS_ROW_THREADS), 0, static_cast<hipStream_t>(stream), p);
   return check_launch();
 }

@@ -10,23 +10,15 @@
 // The reference copies each of the 6 x B cost matrices to the host and solves it with scipy, then calls .item() once per layer.
 #include <limits.h>
 
-#include "gd4d_common.h"
+#include "gd4d_loss_pieces.h"
 
 namespace gd4d {
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// teacher pseudo ground truth: normalize_bbox(denormalize_bbox(t)) (core/bbox/util.py:38-87) for a 10-entry box code.  The round
-// trip is not the identity: sin / cos come back divided by hypot(sin, cos), w / l / h go through log(exp(.)) (exp may overflow to
-// inf, or underflow to 0 and give -inf).
-__device__ __forceinline__ void distill_teacher_box(const float* t, float* o) {
-  const float rot = atan2f(t[6], t[7]);
-  o[0] = t[0]; o[1] = t[1]; o[2] = logf(expf(t[2])); o[3] = logf(expf(t[3])); o[4] = t[4]; o[5] = logf(expf(t[5]));
-  o[6] = sinf(rot); o[7] = cosf(rot); o[8] = t[8]; o[9] = t[9];
-}
-
-// BCE-with-logits against 1 and against 0 (match_cost.py:52-75): max(x, 0) - x + log1p(exp(-|x|)) and max(x, 0) + log1p(exp(-|x|))
+// BCE-with-logits against 1 and against 0 (match_cost.py:52-75): max(x, 0) - x + log1p(exp(-|x|)) and max(x, 0) + log1p(exp(-|x|)).
+// Its own association: pos = (max + softplus) - x, where distill_loss_kernel's term is (max - v y) + softplus.
 __device__ __forceinline__ void bce_pos_neg(float x, float& pos, float& neg) {
-  const float sp = log1pf(expf(-fabsf(x)));
+  const float sp = softplus_neg_abs(x);
   neg = fmaxf(x, 0.f) + sp;
   pos = neg - x;
 }
@@ -58,19 +50,15 @@ __global__ __launch_bounds__(256) void distill_match_cost_kernel(const DistillCo
   for (int e = threadIdx.x; e < DC_TILE * C; e += blockDim.x) {
     const int r = e / C, c = e - r * C;
     if (q0 + r < p.Qs) bce_pos_neg(p.s_cls[(srow + q0 + r) * C + c], s_pos[r][c], s_neg[r][c]);
-    if (t0 + r < p.Qt) s_p[r][c] = p.pseudo_gt ? p.t_cls[(trow + t0 + r) * C + c] : 1.0f / (1.0f + expf(-p.t_cls[(t0row + t0 + r) * C + c]));
+    if (t0 + r < p.Qt) s_p[r][c] = p.pseudo_gt ? p.t_cls[(trow + t0 + r) * C + c] : sigmoid_f(p.t_cls[(t0row + t0 + r) * C + c]);
   }
   for (int r = threadIdx.x; r < DC_TILE; r += blockDim.x) {
     if (q0 + r < p.Qs)
       for (int k = 0; k < 8; ++k) s_sb[r][k] = p.s_box[(srow + q0 + r) * p.code + k];
     if (t0 + r < p.Qt) {
       float o[10];
-      if (p.pseudo_gt) {
-        const float* g = p.t_box + (trow + t0 + r) * 9;
-        o[0] = g[0]; o[1] = g[1]; o[2] = logf(g[3]); o[3] = logf(g[4]); o[4] = g[2]; o[5] = logf(g[5]); o[6] = sinf(g[6]); o[7] = cosf(g[6]);
-      } else {
-        distill_teacher_box(p.t_box + (trow + t0 + r) * 10, o);
-      }
+      if (p.pseudo_gt) normalize_box(p.t_box + (trow + t0 + r) * 9, 7, o);       // (gt_dim 7: the velocity columns are not read)
+      else distill_teacher_box(p.t_box + (trow + t0 + r) * 10, o);
       for (int k = 0; k < 8; ++k) s_tb[r][k] = o[k];
     }
   }
@@ -336,13 +324,6 @@ struct DistillLossParams {
   float cls_weight, reg_weight;
 };
 
-__device__ __forceinline__ float nan_to_num_f(float s) {
-  if (s != s) return 0.f;
-  if (s == INFINITY) return 3.402823466e38f;
-  if (s == -INFINITY) return -3.402823466e38f;
-  return s;
-}
-
 // One workgroup per decoder layer, one thread per (sample, query) row, fixed-order reductions (a replay equals an eager run bit for bit).
 //   labels[q]  = sigmoid(t_cls[l, 0, t]) for a matched row (teacher t; batch 0 for every sample, the reference's quirk), else num_classes
 //   loss_cls   = w_cls * sum BCE-with-logits(s_cls, labels) / max(cls_avg_factor, 1)               (distill_cross_entropy_loss.py:139-147)
@@ -357,8 +338,8 @@ __device__ __forceinline__ float nan_to_num_f(float s) {
 // The gradients are those of the two terms BEFORE nan_to_num; when a layer's divisor is 0 (reweight, C == 10, nothing matched) or not
 // finite the second pass makes grad_box[:, :10] NaN in EVERY row of that layer (0 * inf), where torch leaves 0 in the rows its
 // isfinite filter drops.  assigned outside [b Qt, (b + 1) Qt) counts as unmatched.  Gradient columns >= 10 are +0.
-__global__ __launch_bounds__(1024) void distill_loss_kernel(const DistillLossParams p) {
-  __shared__ float s_red[3][16];
+__global__ __launch_bounds__(LOSS_ROW_THREADS) void distill_loss_kernel(const DistillLossParams p) {
+  __shared__ float s_red[3][LOSS_ROW_WAVES];
   __shared__ float s_div;
   const int l = blockIdx.x, C = p.C;
   const float kc = p.cls_weight / fmaxf(p.avg_factors[0], 1.0f);
@@ -375,12 +356,12 @@ __global__ __launch_bounds__(1024) void distill_loss_kernel(const DistillLossPar
     const float* tl = p.t_cls + ((size_t)l * p.B * p.Qt + (t < 0 ? 0 : t)) * C;     // batch 0 of layer l
     float lmax = -INFINITY, l0 = (float)C;
     for (int c = 0; c < C; ++c) {
-      const float y = t >= 0 ? 1.0f / (1.0f + expf(-tl[c])) : (float)C;
+      const float y = t >= 0 ? sigmoid_f(tl[c]) : (float)C;
       if (c == 0) l0 = y;
       lmax = fmaxf(lmax, y);
       const float v = x[c];
-      sum_cls += fmaxf(v, 0.f) - v * y + log1pf(expf(-fabsf(v)));
-      gx[c] = kc * (1.0f / (1.0f + expf(-v)) - y);
+      sum_cls += fmaxf(v, 0.f) - v * y + softplus_neg_abs(v);
+      gx[c] = kc * (sigmoid_f(v) - y);
     }
     if (p.reweight && l0 != 10.0f) den += lmax;
     float* gb = p.grad_box + r * p.code;
@@ -388,29 +369,27 @@ __global__ __launch_bounds__(1024) void distill_loss_kernel(const DistillLossPar
     if (t >= 0) {
       float tn[10];
       distill_teacher_box(p.t_box + ((size_t)(l * p.B + b) * p.Qt + t) * 10, tn);
-      bool ok = true;
-      for (int k = 0; k < 10; ++k) ok = ok && (fabsf(tn[k]) <= 3.402823466e38f);
-      if (ok) {
+      if (finite_f(tn, 10)) {
         const float* bx = p.s_box + r * p.code;
         const float rw = p.reweight ? lmax : 1.0f;
         for (int k = 0; k < 10; ++k) {
           const float d = bx[k] - tn[k], w = 1.0f * p.code_weights[k] * rw;
           sum_reg += fabsf(d) * w;
-          gb[k] = w * (d > 0.f ? 1.0f : (d < 0.f ? -1.0f : 0.f));             // scaled by reg_weight / divisor below
+          gb[k] = w * l1_sign(d);                                             // scaled by reg_weight / divisor below
         }
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum_cls += __shfl_xor(sum_cls, o); sum_reg += __shfl_xor(sum_reg, o); den += __shfl_xor(den, o);
-  }
-  const int wave = threadIdx.x >> 6, nw = (int)(blockDim.x >> 6);
-  if ((threadIdx.x & 63) == 0) { s_red[0][wave] = sum_cls; s_red[1][wave] = sum_reg; s_red[2][wave] = den; }
+  // the fixed-order workgroup sum of gd4d_common.h, the three values behind one barrier
+  block_sum_put(sum_cls, s_red[0]);
+  block_sum_put(sum_reg, s_red[1]);
+  block_sum_put(den, s_red[2]);
   __syncthreads();
   if (threadIdx.x == 0) {
-    float sc_ = 0.f, sr_ = 0.f, d_ = 0.f;
-    for (int w = 0; w < nw; ++w) { sc_ += s_red[0][w]; sr_ += s_red[1][w]; d_ += s_red[2][w]; }
+    // `0.f +`: these sums always started from +0, and a term of sum_reg can be -0 (a negative code weight times fabsf(0)): kept
+    // (the constant wave count unrolls the three chains of LDS reads, so they overlap as they did in one loop: docs/measurements_r47.md)
+    constexpr int W = LOSS_ROW_WAVES;
+    const float sc_ = 0.f + block_sum_get<W>(s_red[0]), sr_ = 0.f + block_sum_get<W>(s_red[1]), d_ = 0.f + block_sum_get<W>(s_red[2]);
     const float div = p.reweight ? d_ : fmaxf(p.avg_factors[1], 1.0f);
     s_div = div;
     p.loss[2 * l] = nan_to_num_f(sc_ * kc);
@@ -469,6 +448,6 @@ extern "C" int gd4d_distill_loss_fwd_bwd(const float* s_cls, const float* s_box,
   if (code < 10 || code > 16) return GD4D_EUNSUPPORTED;
   DistillLossParams p{s_cls, s_box, t_cls, t_box, assigned, code_weights, avg_factors, loss, grad_cls, grad_box,
                       NL, B, Qs, Qt, C, code, reweight ? 1 : 0, loss_cls_weight, loss_reg_weight};
-  hipLaunchKernelGGL(distill_loss_kernel, dim3(NL), dim3(1024), 0, static_cast<hipStream_t>(stream), p);
+  hipLaunchKernelGGL(distill_loss_kernel, dim3(NL), dim3(LOSS_ROW_THREADS), 0, static_cast<hipStream_t>(stream), p);
   return check_launch();
 }

@@ -42,11 +42,6 @@ constexpr int FD_MAX_LEVELS = 8;
 // row of a 32x32 accumulator tile held in register i of lane half h
 __device__ __forceinline__ int fd_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
-__device__ __forceinline__ float fd_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 __device__ __forceinline__ float fd_wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
@@ -182,10 +177,10 @@ __global__ __launch_bounds__(256) void fd_fused_kernel(const FdFusedParams p) {
         acc[mi][ni][i] = g;
       }
     }
-  lsum = fd_wave_sum(lsum);
+  lsum = wave_sum(lsum);                              // block_sum_put, with the lane / wave indices this kernel already holds
   if (lane == 0) s_red[wave] = lsum;
   __syncthreads();                                    // (also: every wave is done reading the X fragments)
-  if (tid == 0) p.partial[blockIdx.x] = (((s_red[0] + s_red[1]) + s_red[2]) + s_red[3]) * p.lcoef;
+  if (tid == 0) p.partial[blockIdx.x] = block_sum_get<4>(s_red) * p.lcoef;
   // G -> the B fragments of the second product: registers 8s .. 8s+7 of channel block b are k-step 2b + s
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
@@ -319,14 +314,10 @@ __global__ __launch_bounds__(1024) void fd_loss_reduce_kernel(const float* __res
   __shared__ float s_red[16];
   float s = 0.f;
   for (long long i = threadIdx.x; i < count; i += 1024) s += partial[i];
-  s = fd_wave_sum(s);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
+  // (a thread's s starts from +0, and x + y is -0 only for two -0: no wave holds -0, the sum needs no 0 in front)
+  block_sum_put(s, s_red);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int w = 0; w < 16; ++w) t += s_red[w];
-    *loss = t;
-  }
+  if (threadIdx.x == 0) *loss = block_sum_get<16>(s_red);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -348,7 +339,7 @@ __global__ __launch_bounds__(256) void fd_stats_sums_kernel(const float* __restr
       col[q] += v;
       rs += v;
     }
-    rs = fd_wave_sum(rs);
+    rs = wave_sum(rs);
     if (lane == 0) rowpart[(size_t)blockIdx.x * FD_C + c] = rs;
   }
 #pragma unroll
@@ -358,12 +349,14 @@ __global__ __launch_bounds__(256) void fd_stats_sums_kernel(const float* __restr
   if (px < HW) colsum[(size_t)r * HW + px] = ((s_col[0][tid] + s_col[1][tid]) + s_col[2][tid]) + s_col[3][tid];
 }
 
+// the maximum or the sum (block_sum, gd4d_common.h) over the workgroup's 256 threads, in every thread
 __device__ __forceinline__ float fd_block_reduce(float v, bool is_max, float* s_tmp) {
-  v = is_max ? fd_wave_max(v) : fd_wave_sum(v);
-  __syncthreads();                                    // s_tmp's previous readers
+  __syncthreads();                                    // s_tmp's previous readers (block_sum does not end with a barrier)
+  if (!is_max) return block_sum<4>(v, s_tmp);
+  v = fd_wave_max(v);
   if ((threadIdx.x & 63) == 0) s_tmp[threadIdx.x >> 6] = v;
   __syncthreads();
-  return is_max ? fmaxf(fmaxf(s_tmp[0], s_tmp[1]), fmaxf(s_tmp[2], s_tmp[3])) : ((s_tmp[0] + s_tmp[1]) + s_tmp[2]) + s_tmp[3];
+  return fmaxf(fmaxf(s_tmp[0], s_tmp[1]), fmaxf(s_tmp[2], s_tmp[3]));
 }
 
 // One workgroup per camera: a_s = HW softmax_c(mean_p |t| / T) from the channel partials, a_c = 256 softmax_p(mean_c |t| / T) in place

@@ -110,8 +110,7 @@ __global__ __launch_bounds__(256) void frustum_pe_chlast_kernel(const FrustumPar
       if (lane < 48) *reinterpret_cast<float4*>(o + 4 * lane) = *reinterpret_cast<const float4*>(&s_row[wave][4 * lane]);
     }
     if (p.outside) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) n_out += __shfl_xor(n_out, off);
+      n_out = wave_sum(n_out);
       if (lane == 0) p.outside[idx] = (float)n_out > (float)p.D * 0.5f ? 1 : 0;
     }
   }

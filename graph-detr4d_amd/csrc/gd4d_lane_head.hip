@@ -7,8 +7,8 @@
 //                              to the workspace - once per row, shared by the layers;
 //     lane_loss_kernel         grid (chunks of LANE_CHUNK elements, layers): term = w (max(x, 0) - x t + log1p(exp(-|x|))) with
 //                              w = t pw + (1 - t), and dlogits = coef w (sigmoid(x) - t), coef = loss_weight / (R C).  The terms are
-//                              added in fp64: per thread in element order, the wave by an xor butterfly, the four waves in index
-//                              order; one fp64 partial per workgroup;
+//                              added in fp64: per thread in element order, the workgroup by block_sum (gd4d_common.h); one fp64
+//                              partial per workgroup;
 //     lane_loss_finish_kernel  one workgroup per layer adds the layer's partials in a fixed order, writes nan_to_num(loss) and - where
 //                              the loss was not finite - zeroes the layer's gradient (see include/gd4d.h for this deviation).
 //                           No floating-point atomics: two runs give the same bits.  16-byte accesses where C % 4 == 0 and the
@@ -21,9 +21,7 @@
 //                           With a ground-truth map one workgroup owns a whole (sample, class) plane and reduces inter = sum(binary gt),
 //                           sum(binary) (an integer count) and sum(gt) in a fixed order, then writes the IoU of petr3d_seg.py:25-29;
 //                           without one the plane's g patch rows are spread over g workgroups.
-#include <float.h>
-
-#include "gd4d_common.h"
+#include "gd4d_loss_pieces.h"
 
 namespace gd4d {
 
@@ -31,29 +29,6 @@ constexpr int LANE_THREADS = 256;
 constexpr int LANE_CHUNK = 4096;                     // elements of one layer per workgroup of lane_loss_kernel: 4 x float4 per thread
 constexpr int LANE_PATCH = 768;                      // 3 classes x 16 x 16: what lane_branches' last Linear writes per query
 constexpr int LANE_MAP_THREADS = 1024;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = GD4D_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int o = GD4D_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// the sum of one fp64 value per thread of a 256-thread workgroup, in a fixed order; valid in thread 0 (every thread of wave 0)
-__device__ __forceinline__ double block_sum_f64(double v, double* s_red) {
-  v = wave_sum_f64(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_red[wave] = v;
-  __syncthreads();
-  double s = s_red[0];
-  for (int i = 1; i < (int)(blockDim.x >> 6); ++i) s += s_red[i];
-  __syncthreads();
-  return s;
-}
 
 // ---- Sigmoid_ce_loss ------------------------------------------------------------------------------------------------------------
 template <bool VEC>
@@ -76,12 +51,13 @@ __global__ __launch_bounds__(LANE_THREADS) void lane_row_weight_kernel(const flo
       n0 += v == 0.f;
     }
   }
-  n1 = wave_sum_i32(n1);
-  n0 = wave_sum_i32(n0);
+  n1 = wave_sum(n1);
+  n0 = wave_sum(n0);
   if (lane == 0) pw[r] = (float)n0 / fmaxf((float)n1, 1.f);
 }
 
-// one element: its term of the mean and its gradient
+// one element: its term of the mean and its gradient.  Not sigmoid_f / softplus_neg_abs: one e = exp(-|x|) serves both, and the sigmoid
+// is the overflow-free e / (1 + e) for x < 0.
 __device__ __forceinline__ float lane_term(float x, float t, float pw, float coef, float& grad) {
   const float w = t * pw + (1.f - t);
   const float e = expf(-fabsf(x));                                    // in (0, 1]: never overflows
@@ -127,7 +103,7 @@ __global__ __launch_bounds__(LANE_THREADS) void lane_loss_kernel(const float* __
       }
     }
   }
-  const double s = block_sum_f64(acc, s_red);
+  const double s = block_sum(acc, s_red);
   if (threadIdx.x == 0) partial[(size_t)l * gridDim.x + blockIdx.x] = s;
 }
 
@@ -139,12 +115,11 @@ __global__ __launch_bounds__(LANE_THREADS) void lane_loss_finish_kernel(const do
   const double* p = partial + (size_t)l * chunks;
   double acc = 0.0;
   for (int i = threadIdx.x; i < chunks; i += LANE_THREADS) acc += p[i];
-  const double s = block_sum_f64(acc, s_red);
+  const double s = block_sum(acc, s_red);
   if (threadIdx.x == 0) {
     const float v = (float)(scale * s);                                 // loss_weight * mean
-    const bool bad = !(fabsf(v) <= FLT_MAX);                            // NaN or +-inf
-    loss[l] = bad ? (v != v ? 0.f : (v > 0.f ? FLT_MAX : -FLT_MAX)) : v;      // torch.nan_to_num
-    s_bad = bad;
+    loss[l] = nan_to_num_f(v);                                          // petr_head_seg.py:785
+    s_bad = !finite_f(&v, 1);
   }
   __syncthreads();
   if (s_bad) {
@@ -173,10 +148,10 @@ __global__ __launch_bounds__(LANE_MAP_THREADS) void lane_map_kernel(const float*
       const size_t dst = plane + (size_t)(16 * h + h1) * side + 16 * w + w2;
       const float4 x = *reinterpret_cast<const float4*>(logits + src);
       float4 p, q;
-      p.x = 1.f / (1.f + expf(-x.x));
-      p.y = 1.f / (1.f + expf(-x.y));
-      p.z = 1.f / (1.f + expf(-x.z));
-      p.w = 1.f / (1.f + expf(-x.w));
+      p.x = sigmoid_f(x.x);
+      p.y = sigmoid_f(x.y);
+      p.z = sigmoid_f(x.z);
+      p.w = sigmoid_f(x.w);
       q.x = p.x >= 0.5f ? 1.f : 0.f;
       q.y = p.y >= 0.5f ? 1.f : 0.f;
       q.z = p.z >= 0.5f ? 1.f : 0.f;
@@ -192,25 +167,14 @@ __global__ __launch_bounds__(LANE_MAP_THREADS) void lane_map_kernel(const float*
     }
   }
   if (GT) {                                                             // (gridDim.y == 1: this workgroup saw the whole plane)
-    inter = wave_sum(inter);
-    sum_gt = wave_sum(sum_gt);
-    sum_bin = wave_sum_i32(sum_bin);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-      s_inter[wave] = inter;
-      s_gt[wave] = sum_gt;
-      s_bin[wave] = sum_bin;
-    }
+    block_sum_put(inter, s_inter);                                      // the fixed-order workgroup sum of gd4d_common.h, the
+    block_sum_put(sum_gt, s_gt);                                        // three values behind one barrier
+    block_sum_put(sum_bin, s_bin);
     __syncthreads();
     if (threadIdx.x == 0) {
-      float a = s_inter[0], t = s_gt[0];
-      int n = s_bin[0];
-      for (int i = 1; i < LANE_MAP_THREADS / GD4D_WAVE; ++i) {
-        a += s_inter[i];
-        t += s_gt[i];
-        n += s_bin[i];
-      }
-      const float nb = (float)n;
+      constexpr int WAVES = LANE_MAP_THREADS / GD4D_WAVE;
+      const float a = block_sum_get<WAVES>(s_inter), t = block_sum_get<WAVES>(s_gt);
+      const float nb = (float)block_sum_get<WAVES>(s_bin);
       sums[3 * bc + 0] = a;
       sums[3 * bc + 1] = nb;
       sums[3 * bc + 2] = t;

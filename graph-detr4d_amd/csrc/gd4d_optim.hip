@@ -42,14 +42,10 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_sumsq_kernel(const float* _
       for (long long j = i; j < hi; ++j) s += g[j] * g[j];
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  block_sum_put(s, red);                                                      // (a sum of squares: no wave holds -0)
   __syncthreads();
   if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int w = 0; w < OPT_THREADS / 64; ++w) t += red[w];
-    partial[blockIdx.x] = t;
+    partial[blockIdx.x] = block_sum_get<OPT_THREADS / 64>(red);
     if (blockIdx.x == 0) state[0] += 1.0f;                                    // the step this update is
   }
 }
@@ -147,14 +143,10 @@ __global__ __launch_bounds__(OPT_THREADS) void recipe_sumsq_kernel(const float* 
       for (long long j = i; j < hi; ++j) { const float a = g[j] * inv; s += a * a; bad |= !isfinite(a); }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  bad = __syncthreads_or(bad);
+  block_sum_put(s, red);                                                      // (a sum of squares: no wave holds -0)
+  bad = __syncthreads_or(bad);                                                // the barrier between put and get
   if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int w = 0; w < OPT_THREADS / 64; ++w) t += red[w];
-    partial[blockIdx.x] = t;
+    partial[blockIdx.x] = block_sum_get<OPT_THREADS / 64>(red);
     flags[blockIdx.x] = bad;
     if (blockIdx.x == 0) {                                                    // this iteration: its rate, its scale, the step it would be
       const long long it = st->iteration;

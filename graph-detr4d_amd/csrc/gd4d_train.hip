@@ -25,12 +25,6 @@ struct LnBwdParams {
   float eps;
 };
 
-__device__ __forceinline__ float t_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // VPL = float4s of a row per lane (C <= 256 VPL), WAVES x RPW = 16 rows.  C <= 256 runs one row per wave (16 waves): the four
 // dependent wave reductions of a row (mean, variance, the two sums of the gradient) are a latency chain of ~2 us behind a
 // cold load, and a wave that walks four rows pays it four times (10.7 us per launch in the step, 30 launches).
@@ -69,7 +63,7 @@ __global__ __launch_bounds__(64 * WAVES) void layernorm_bwd_kernel(const LnBwdPa
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
       }
     }
-    const float mean = t_wave_sum(s) / (float)p.C;
+    const float mean = wave_sum(s) / (float)p.C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i)
@@ -77,7 +71,7 @@ __global__ __launch_bounds__(64 * WAVES) void layernorm_bwd_kernel(const LnBwdPa
         const float a = v[i].x - mean, b = v[i].y - mean, c2 = v[i].z - mean, e = v[i].w - mean;
         q += (a * a + b * b) + (c2 * c2 + e * e);
       }
-    const float rstd = 1.0f / sqrtf(t_wave_sum(q) / (float)p.C + p.eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)p.C + p.eps);
     float s1 = 0.f, s2 = 0.f;
     float4 xh[VPL], g[VPL];
 #pragma unroll
@@ -97,7 +91,7 @@ __global__ __launch_bounds__(64 * WAVES) void layernorm_bwd_kernel(const LnBwdPa
         ab[i].x += d[i].x; ab[i].y += d[i].y; ab[i].z += d[i].z; ab[i].w += d[i].w;
       }
     }
-    const float m1 = t_wave_sum(s1) / (float)p.C, m2 = t_wave_sum(s2) / (float)p.C;
+    const float m1 = wave_sum(s1) / (float)p.C, m2 = wave_sum(s2) / (float)p.C;
     float4* dx = reinterpret_cast<float4*>(p.dx + (size_t)row * p.C);
 #pragma unroll
     for (int i = 0; i < VPL; ++i)

@@ -28,13 +28,12 @@ import types
 
 import numpy as np
 import torch
-import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import functional as Fn
 from . import ops
-from .criterion import AssignResult, HungarianAssigner3D
+from .criterion import AssignResult, HungarianAssigner3D, _LayerLossFunction, build_assigner, reduce_mean_normalisers
 from .registry import BBOX_ASSIGNERS
 
 
@@ -125,22 +124,6 @@ class DistillHungarianAssigner3D(HungarianAssigner3D):
         return AssignResult(num_gts, gt_inds, None, labels=lab)
 
 
-class _DistillLossFunction(torch.autograd.Function):
-    """loss (NL, 2) from gd4d_distill_loss_fwd_bwd; the gradients come out of the same launch.  The teacher gets none."""
-
-    @staticmethod
-    def forward(ctx, s_cls, s_box, t_cls, t_box, assigned, code_weights, avg, reweight, wc, wr):
-        loss, gcls, gbox = ops.distill_loss_fwd_bwd(s_cls, s_box, t_cls, t_box, assigned, code_weights, avg, reweight, wc, wr)
-        ctx.save_for_backward(gcls, gbox)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        gcls, gbox = ctx.saved_tensors
-        gl = grad_loss.view(-1, 2)
-        return (gcls * gl[:, 0].view(-1, 1, 1, 1), gbox * gl[:, 1].view(-1, 1, 1, 1)) + (None,) * 8
-
-
 def distill_normalisers(batch, num_student, num_teacher, bg_cls_weight=0.0, sync_cls_avg_factor=True, device=None):
     """(cls_avg_factor, num_total_pos) of loss_distill_single (:893-905) as a 2-element device tensor.  PseudoSampler's positives are
     the matched student queries: min(Qs, Qt) per sample.  reduce_mean over the ranks: ONE all-reduce of both (num_total_pos is always
@@ -148,13 +131,7 @@ def distill_normalisers(batch, num_student, num_teacher, bg_cls_weight=0.0, sync
     num_pos = float(batch * min(num_student, num_teacher))
     num_neg = float(batch * num_student) - num_pos
     avg = torch.tensor([num_pos + num_neg * float(bg_cls_weight), num_pos], dtype=torch.float32, device=device)
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        local_cls = avg[0].clone()
-        dist.all_reduce(avg)
-        avg /= dist.get_world_size()
-        if not sync_cls_avg_factor:
-            avg[0] = local_cls
-    return avg
+    return reduce_mean_normalisers(avg, sync_cls_avg_factor)
 
 
 def _loss_weight(cfg, kind, **required):
@@ -191,16 +168,13 @@ def get_instance_distill_loss(teacher_outs, stu_outs, loss_cls_distill=None, los
     if asg is None:
         asg = dict(cls_cost=dict(type='DistillCrossEntropyLossCost', weight=1.0), reg_cost=dict(type='BBox3DL1Cost', weight=0.25),
                    iou_cost=dict(type='IoUCost', weight=0.0), pc_range=pc_range)
-    if isinstance(asg, dict):
-        asg = dict(asg)
-        asg.pop('type', None)
-        asg = DistillHungarianAssigner3D(**asg)
+    asg = build_assigner(asg, DistillHungarianAssigner3D)
     assigned = asg.assign_layers(s_cls, s_box, t_cls, t_box, host=host)
     cw = code_weights if code_weights is not None else [1.0] * 8 + [0.2, 0.2]
     cw = cw.detach().float().to(s_cls.device) if torch.is_tensor(cw) else torch.tensor(cw, dtype=torch.float32, device=s_cls.device)
     avg = avg_factors if avg_factors is not None else distill_normalisers(b, qs, qt, bg_cls_weight, sync_cls_avg_factor, s_cls.device)
-    loss = _DistillLossFunction.apply(s_cls.float().contiguous(), s_box.float().contiguous(), t_cls, t_box, assigned, cw.contiguous(),
-                                      avg, bool(reweight_score), wc, wr)
+    loss = _LayerLossFunction.apply(ops.distill_loss_fwd_bwd, s_cls.float().contiguous(), s_box.float().contiguous(), t_cls, t_box,
+                                    assigned, cw.contiguous(), avg, bool(reweight_score), wc, wr)            # (the teacher gets none)
     out = {}
     for l in range(nl):
         out[f'distill_loss_cls.{l}'] = loss[l, 0]
